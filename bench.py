@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the wifirx receive chain (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A step = one pass of the whole RX hot path (autocorrelation + sync_short + sync_long + FFT +
 LS equalise + hard demap + LLR, one fused HIP kernel) over one device-resident batch of
@@ -59,6 +59,9 @@ FREQUENCY = 5.89e9
 CFO_MAX = 2 * np.pi * 20e-6 * FREQUENCY / BANDWIDTH    # +-20 ppm of the carrier, rad/sample
 N_TEMPLATES = 1024
 PSDU_STRIDE = 320
+DUMP_FRAMES = 1024         # --dump-outputs: frames in the sample (fewer when the batch is smaller)
+DUMP_SEED = 20251015       # --dump-outputs: which frames; fixed, so that two builds dump the same ones
+DUMP_MAX_BYTES = 64 << 20
 
 
 def algorithmic_bytes_per_frame(slot_len, n_sym, n_bpsc):
@@ -83,7 +86,13 @@ def parse_args(argv=None):
     ap.add_argument("--pipeline-batches", type=int, default=6, help="batches of the pipelined demod / decode_mac figure (0 = skip; N = 1 only)")
     ap.add_argument("--no-variants", action="store_true", help="skip the other geometries / output sets / equalisers")
     ap.add_argument("--variant-frames", type=int, default=0, help="frames per variant batch (0 = as --frames)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a fixed, seeded sample of frames) as "
+                         "DIR/<name>.npy in float32 / float64, at most %d MB" % (DUMP_MAX_BYTES >> 20))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(n: int) -> int:
@@ -208,6 +217,36 @@ def ber_vs_tx(torch, idx_t, frames_np, tx, n_bpsc, capi):
     return {"coded_ber": bit_errors / bits if bits else None, "bit_errors": bit_errors, "bits_compared": bits,
             "frames_compared": n_good, "frames_not_demodulated": int(n - n_good),
             "what": "hard decisions (wifirx_out.idx) vs the transmitter's interleaved coded bits, before decode_mac"}
+
+
+def dump_outputs(torch, out_dir, n_frames, outputs, frame_dtype):
+    """--dump-outputs: the rows of a fixed, seeded sample of frames from every buffer the timed step hands its caller,
+    as <out_dir>/<name>.npy.  Floats stay as they are, integers become float32 (up to 16 bits) or float64: exact either
+    way.  The frame record is written one field per file (frame_<field>.npy), and frame_index.npy says which frames of
+    the batch the rows are.  `outputs` maps a name to a device tensor with one row per frame; "frames" is the 32-byte
+    record.  Returns the file names."""
+    def as_float(a):
+        return a if a.dtype.kind == "f" else a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+
+    def arrays_of(sel):
+        sel_t = torch.from_numpy(sel).to(next(iter(outputs.values())).device)
+        arrays = {"frame_index": sel.astype(np.float64)}
+        for k, t in outputs.items():
+            rows = t.index_select(0, sel_t).cpu().numpy()
+            if k == "frames":
+                rec = rows.view(frame_dtype).reshape(-1)
+                arrays.update(("frame_" + f, as_float(rec[f])) for f in frame_dtype.names)
+            else:
+                arrays[k] = as_float(rows)
+        return arrays
+
+    row_bytes = sum(a.nbytes for a in arrays_of(np.zeros(1, np.int64)).values())
+    n = min(n_frames, DUMP_FRAMES, DUMP_MAX_BYTES // row_bytes)
+    arrays = arrays_of(np.sort(np.random.default_rng(DUMP_SEED).choice(n_frames, size=n, replace=False)))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(k + ".npy" for k in arrays)
 
 
 class VariantArena:
@@ -499,6 +538,16 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before any later leg writes these buffers again
+        outs = {"frames": frames_t, "idx": idx_t, "llr": llr_t, "psdu": psdu_t}
+        if not out.idx:
+            del outs["idx"]
+        if not do_decode:
+            del outs["psdu"]
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(torch, args.dump_outputs, n_frames, outs, capi.FRAME_DTYPE)}
+
     total_samples = float(n_frames) * SLOT_LEN * world * args.steps
     value = total_samples / elapsed
     ms_per_step = elapsed / args.steps * 1e3
@@ -716,6 +765,8 @@ def main():
                 "device_clocks_before_run": clocks,
             },
         }
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         if pdu_leg is not None:
             t_pair = pdu_leg["demod_with_planes_ms"] + pdu_leg["decode_mac_ms"]
             result["samples_to_pdu"] = {"demod_ms": pdu_leg["demod_with_planes_ms"], "decode_mac_ms": pdu_leg["decode_mac_ms"],

@@ -65,3 +65,36 @@ def test_box_probe_library_is_fresh_and_not_part_of_the_product(bench):
         for fn in files:
             if fn.endswith((".py", ".hip", ".h", ".inc")) or fn == "Makefile":
                 assert "boxprobe" not in open(os.path.join(d, fn), errors="ignore").read(), fn
+
+
+def test_dump_outputs_writes_an_exact_seeded_sample_within_the_budget(bench, tmp_path):
+    """--dump-outputs: the same frames every time, every value exact in float32 / float64, the record one field per
+    file, and the whole sample within bench.DUMP_MAX_BYTES even when the rows are long."""
+    import torch
+    from wifirx import capi
+    n, n_val = 5000, 2400
+    rng = np.random.default_rng(7)
+    frames = np.zeros(n, capi.FRAME_DTYPE)
+    frames["flags"] = rng.integers(0, 2 ** 32, n, dtype=np.uint32)
+    frames["trigger"] = rng.integers(-2 ** 31, 2 ** 31, n, dtype=np.int32)
+    frames["cfo_fine"] = rng.standard_normal(n).astype(np.float32)
+    frames["psdu_len"] = rng.integers(0, 2 ** 16, n, dtype=np.uint16)
+    outs = {"frames": torch.from_numpy(frames.view(np.uint8).reshape(n, 32).copy()),
+            "idx": torch.from_numpy(rng.integers(0, 256, (n, n_val), dtype=np.uint8)),
+            "llr": torch.from_numpy(rng.standard_normal((n, 8 * n_val)).astype(np.float32))}
+    files = bench.dump_outputs(torch, str(tmp_path / "a"), n, outs, capi.FRAME_DTYPE)
+    bench.dump_outputs(torch, str(tmp_path / "b"), n, outs, capi.FRAME_DTYPE)
+    assert files == sorted(["frame_index.npy", "idx.npy", "llr.npy"] + ["frame_%s.npy" % f for f in capi.FRAME_DTYPE.names])
+    assert sorted(os.listdir(tmp_path / "a")) == files
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX_BYTES
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    sel = got["frame_index"].astype(np.int64)
+    assert 0 < len(sel) <= bench.DUMP_FRAMES and len(np.unique(sel)) == len(sel) and sel.max() < n
+    assert got["llr"].shape == (len(sel), 8 * n_val) and len(sel) < bench.DUMP_FRAMES     # 77 kB rows: fewer fit the budget
+    assert np.array_equal(got["idx"], outs["idx"].numpy()[sel])
+    assert np.array_equal(got["llr"], outs["llr"].numpy()[sel])
+    for f in capi.FRAME_DTYPE.names:
+        assert np.array_equal(got["frame_" + f], frames[f][sel]), f
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), got[f[:-4]]), f
