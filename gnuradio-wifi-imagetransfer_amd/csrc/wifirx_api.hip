@@ -77,6 +77,7 @@ struct wifirx_handle {
     int      decode_q = -1;         // WIFIRX_DECODE_Q (environment, tests): 1 / 0 = always / never the four-frames-per-lane decoder; -1: by batch size
     int32_t  llr_csi = 0;           // WIFIRX_P_LLR_CSI
     int32_t  stream_want_idx = 1;   // WIFIRX_P_STREAM_IDX
+    int32_t  stream_soft = 0;       // WIFIRX_P_STREAM_SOFT: stream batches decoded from LLRs (wifirx_decode_batch_soft)
     int64_t  sprocessed = 0;        // absolute index up to which pushes have been processed
     uint8_t* s_above = nullptr;     float2* s_A = nullptr;    int64_t s_above_cap = 0;
     std::vector<PendingTrig> pending;
@@ -86,6 +87,7 @@ struct wifirx_handle {
     void*  s_csi = nullptr;
     void*  s_stats = nullptr;
     void*  s_hbits = nullptr;
+    void*  s_llr = nullptr;   uint32_t s_llr_cap = 0;      // WIFIRX_P_STREAM_SOFT: LLR rows of the triggers (6 bits per carrier reserved)
     int    test_fail_alloc = 0, test_alloc_count = 0;      // WIFIRX_TEST_FAIL_ALLOC (allocation-failure tests)
     size_t test_decode_budget = 0;                         // WIFIRX_TEST_DECODE_BUDGET: bytes of survivor scratch a decode call may hold (tests)
     int    test_fail_decode_scratch = 0;                   // WIFIRX_TEST_FAIL_DECODE_SCRATCH: the next k scratch allocations fail (tests)
@@ -246,6 +248,7 @@ int wifirx_destroy(wifirx_handle* h)
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->s_pack) (void)hipFree(h->s_pack);
     if (h->dec_hbits) (void)hipFree(h->dec_hbits);
+    if (h->s_llr) (void)hipFree(h->s_llr);
     if (h->dec_perm) (void)hipFree(h->dec_perm);
     if (h->s_host) (void)hipHostFree(h->s_host);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -280,6 +283,10 @@ int wifirx_set_param(wifirx_handle* h, int id, double value)
         return WIFIRX_OK;
     case WIFIRX_P_STREAM_IDX:
         h->stream_want_idx = value != 0;
+        return WIFIRX_OK;
+    case WIFIRX_P_STREAM_SOFT:
+        if (value != 0 && value != 1) return fail(h, WIFIRX_EINVAL, "WIFIRX_P_STREAM_SOFT must be 0 or 1");
+        h->stream_soft = (int32_t)value;
         return WIFIRX_OK;
     case WIFIRX_P_DECODE_SMALL_MAX:
         if (!(value >= 0) || value > 4e9) return fail(h, WIFIRX_EINVAL, "decode threshold out of range");

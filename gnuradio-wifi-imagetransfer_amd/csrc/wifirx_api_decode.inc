@@ -143,3 +143,86 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
                                     (uint32_t)n_waves, fpw, perm, n_virtual));
     return WIFIRX_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Soft-decision decode_mac (NUMERICS.md rule 14, wr_decode_soft.hip): the same frames, scratch and result fields as
+// wifirx_decode_batch, the LLR rows (`llr_bits` per carrier reserved per row) instead of the hard decisions.
+static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t llr_bits);
+
+extern "C" int wifirx_decode_batch_soft(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out)
+{
+    if (!h || !out) return WIFIRX_EINVAL;
+    stream_worker_wait_idle(h);
+    if (h->cfg.llr_bits == 0) return fail(h, WIFIRX_EINVAL, "wifirx_decode_batch_soft needs a handle created with llr_bits > 0");
+    return decode_batch_soft_impl(h, n_slots, out, h->cfg.llr_bits);
+}
+
+static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t llr_bits)
+{
+    if (!out->on_device) return fail(h, WIFIRX_EINVAL, "wifirx_decode_batch_soft works on device buffers (out->on_device = 1)");
+    if (!out->frames || !out->llr || !out->psdu || out->psdu_stride == 0)
+        return fail(h, WIFIRX_EINVAL, "frames, llr and psdu (with psdu_stride) are required");
+    if (reinterpret_cast<uintptr_t>(out->llr) & 15) return fail(h, WIFIRX_EINVAL, "out->llr must be 16-byte aligned");
+    if (n_slots == 0) return WIFIRX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    // the hard path's pre-pass: longest trellis, decodable frames per rate (frames without WIFIRX_F_LLR are counted too;
+    // the kernel leaves them alone)
+    int rc = ensure(h, &h->dec_max, &h->dec_max_bytes, 256);
+    if (rc) return rc;
+    uint32_t pre[9] = { 0 };
+    HIP_TRY(h, hipMemsetAsync(h->dec_max, 0, 256, h->stream));
+    HIP_TRY(h, wr_launch_decode_maxsteps(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride,
+                                         reinterpret_cast<uint32_t*>(h->dec_max)));
+    HIP_TRY(h, hipMemcpyAsync(pre, h->dec_max, sizeof pre, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const uint32_t n_steps = pre[0];
+    if (n_steps == 0) return WIFIRX_OK;
+    // tasks of 64 frames (one per lane), each of one rate: several rates are grouped by rate on the device, every run
+    // starting on a task boundary; one launch per bits-per-carrier class over its range of tasks
+    const uint32_t fpw = 64;
+    uint32_t n_rates = 0, n_virtual = n_slots;
+    for (int e = 0; e < 8; e++) n_rates += pre[1 + e] != 0;
+    uint32_t starts[9] = { 0 };
+    for (int e = 0; e < 8; e++) starts[e + 1] = starts[e] + (pre[1 + e] + fpw - 1) / fpw * fpw;
+    const uint32_t* perm = nullptr;
+    if (n_rates > 1) {
+        n_virtual = starts[8];
+        rc = ensure(h, &h->dec_perm, &h->dec_perm_bytes, (size_t)n_virtual * sizeof(uint32_t));
+        if (rc) return rc;
+        HIP_TRY(h, hipMemsetAsync(h->dec_perm, 0xff, (size_t)n_virtual * sizeof(uint32_t), h->stream));
+        HIP_TRY(h, wr_launch_decode_perm(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride, starts,
+                                         reinterpret_cast<uint32_t*>(h->dec_max) + 16, reinterpret_cast<uint32_t*>(h->dec_perm)));
+        perm = reinterpret_cast<const uint32_t*>(h->dec_perm);
+    }
+    const size_t n_tasks = (n_virtual + fpw - 1) / fpw;
+    // per wave: 8 bytes of survivor bits per step and lane, the decoded words of its 64 frames (two spare words)
+    const size_t stride = (size_t)n_steps * 64 * 8 + ((size_t)n_steps / 32 + 2) * 64 * sizeof(uint32_t);
+    size_t budget = WR_DECODE_SCRATCH_BUDGET;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget = std::min<size_t>(budget, (mem_free + h->dec_scratch_bytes) / 10 * 7);
+        else (void)hipGetLastError();
+        if (h->test_decode_budget) budget = std::min<size_t>(budget, h->test_decode_budget);
+    }
+    // the kernel is grid-stride over tasks: if the scratch cannot be had, fewer waves (down to four) take longer
+    size_t n_waves = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_tasks, WR_DECODE_MAX_WAVES), budget / stride));
+    for (;;) {
+        rc = ensure(h, &h->dec_scratch, &h->dec_scratch_bytes, stride * n_waves);
+        if (rc == WIFIRX_OK) break;
+        if (rc != WIFIRX_ENOMEM || n_waves <= 4) return rc;
+        n_waves /= 2;
+    }
+    h->dec_last_waves = (uint32_t)n_waves;
+    const int nb_of_class[4] = { 1, 2, 4, 6 };
+    for (int c = 0; c < 4; c++) {
+        const int e0 = 2 * c, e1 = 2 * c + 1;
+        if (pre[1 + e0] == 0 && pre[1 + e1] == 0) continue;
+        // task range of the class: its runs in the permutation, or every task when the batch holds one rate
+        const uint32_t lo = perm ? starts[e0] / fpw : 0u, hi = perm ? starts[e1 + 1] / fpw : (uint32_t)n_tasks;
+        const uint32_t waves = (uint32_t)std::min<size_t>(n_waves, hi - lo);
+        HIP_TRY(h, wr_launch_decode_soft(h->stream, nb_of_class[c], n_slots, h->cfg.max_sym, llr_bits, out->frames, out->llr,
+                                         out->psdu, out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride,
+                                         n_steps, waves, perm, n_virtual, lo, hi));
+    }
+    return WIFIRX_OK;
+}

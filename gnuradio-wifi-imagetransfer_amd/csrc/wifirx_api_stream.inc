@@ -67,7 +67,7 @@ int stream_out_reserve(wifirx_handle* h, uint32_t n)
     h->s_cap = 0;
     for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
     const size_t per = (size_t)h->cfg.max_sym * 48;
-    // no LLR rows: wifirx_poll has no LLR output, the stream kernel gets a null LLR pointer
+    // no LLR rows here: wifirx_poll has no LLR output; with WIFIRX_P_STREAM_SOFT the decoder's rows come from stream_llr_reserve
     struct { void** p; size_t bytes; } req[] = {
         { &h->s_trig, cap * sizeof(wr::StreamTrig) },
         { &h->s_frames, cap * sizeof(wifirx_frame) },
@@ -87,6 +87,19 @@ int stream_out_reserve(wifirx_handle* h, uint32_t n)
         }
     }
     h->s_cap = cap;
+    return WIFIRX_OK;
+}
+
+// WIFIRX_P_STREAM_SOFT: LLR rows for the s_cap triggers the other rows hold (max_sym * 48 * 6 floats each), kept while the
+// handle lives; allocated only once the mode is on
+static int stream_llr_reserve(wifirx_handle* h)
+{
+    if (h->s_llr_cap >= h->s_cap) return WIFIRX_OK;
+    if (h->s_llr) { (void)hipFree(h->s_llr); h->s_llr = nullptr; }
+    h->s_llr_cap = 0;
+    hipError_t e = stream_malloc(h, &h->s_llr, (size_t)h->s_cap * h->cfg.max_sym * 48 * 6 * sizeof(float));
+    if (e != hipSuccess) return oom(h, "hipMalloc(stream LLR rows)", e);
+    h->s_llr_cap = h->s_cap;
     return WIFIRX_OK;
 }
 
@@ -197,6 +210,8 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
     const uint32_t np = (uint32_t)h->pending.size();
     if (np) {
         if ((rc = stream_out_reserve(h, np))) return rc;
+        const bool soft = h->stream_soft != 0;
+        if (soft && (rc = stream_llr_reserve(h))) return rc;
         std::vector<wr::StreamTrig> trig(np);
         std::vector<char> final_(np);
         for (uint32_t k = 0; k < np; k++) {
@@ -211,7 +226,8 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
             trig[k].pad = h->pending[k].have_cfo;   // the device computed when it first saw the trigger
             final_[k] = fin;
         }
-        const wr::DemodParams prm = params_of(h);
+        wr::DemodParams prm = params_of(h);
+        if (soft) prm.llr_bits = 6;                 // the stream's own LLR rows: every rate fits, whatever cfg.llr_bits says
         const size_t per = (size_t)h->cfg.max_sym * 48;
         HIP_TRY(h, hipMemcpyAsync(h->s_trig, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
         // hard decisions as bytes only when the caller polls them (WIFIRX_P_STREAM_IDX); decode_mac reads the bit planes
@@ -219,7 +235,7 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
         if (d_idx) HIP_TRY(h, hipMemsetAsync(d_idx, 0, np * per, h->stream));
         HIP_TRY(h, hipMemsetAsync(h->s_csi, 0, (size_t)np * 52 * sizeof(float2), h->stream));
         if (h->s_car) HIP_TRY(h, hipMemsetAsync(h->s_car, 0, np * per * sizeof(float2), h->stream));
-        const wr::DemodOut dout = { reinterpret_cast<wifirx_frame*>(h->s_frames), d_idx, nullptr,
+        const wr::DemodOut dout = { reinterpret_cast<wifirx_frame*>(h->s_frames), d_idx, soft ? reinterpret_cast<float*>(h->s_llr) : nullptr,
                                     reinterpret_cast<float2*>(h->s_car), reinterpret_cast<float2*>(h->s_csi),
                                     reinterpret_cast<float4*>(h->s_stats), reinterpret_cast<uint32_t*>(h->s_hbits) };
         HIP_TRY(h, wr_launch_demod_stream(h->stream, h->sbuf, h->sfill, reinterpret_cast<wr::StreamTrig*>(h->s_trig), np,
@@ -231,8 +247,9 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
         o.psdu = reinterpret_cast<uint8_t*>(h->s_psdu);
         o.psdu_stride = 2048;
         o.on_device = 1;
+        o.llr = soft ? reinterpret_cast<float*>(h->s_llr) : nullptr;
         stage("enqueue frame kernel");
-        if ((rc = decode_batch_impl(h, np, &o))) return rc;
+        if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6) : decode_batch_impl(h, np, &o))) return rc;
         stage("frame kernel + decode_mac");
         // the frame records first: they say how much of every output row is worth bringing back (rows are max_sym
         // symbols and 2048 bytes wide on the device, a frame usually fills a fraction of that)

@@ -1,0 +1,365 @@
+// wr_decode_soft.hip -- soft-decision decode_mac (NUMERICS.md rule 14): Viterbi K=7 (133,171) on the demodulator's
+// LLRs instead of its hard decisions, then descramble and CRC-32 as the hard path does (wr_decode.hip).
+//
+// One wavefront decodes 64 frames of ONE rate, one frame per lane.  The 64 path metrics of a lane's frame are float32
+// in 64 VGPRs, updated in place with the register rotation of decode_kernel (the state <-> register map turns by one
+// bit per step and is the identity again after six, so the add-compare-select is unrolled over six steps).  A state's
+// decision is the contract's comparison itself: v_cmp_lt_f32 (m1 < m0) into VCC, v_cndmask_b32 picks the survivor's
+// metric, v_addc_co_u32 (acc + acc + VCC) drops the decision into the lane's 32-bit accumulator -- three instructions per
+// state besides the two adds, and no NaN can ever decide (the +inf start metrics compare, they are never subtracted).
+//
+// The LLRs of the current OFDM symbol of every lane's frame are staged in LDS as rows of 64 lanes (row j = LLR j of the
+// symbol, 256 bytes): each lane reads its own symbol contiguously in float4s, and a trellis step then reads coded bits A
+// and B of all 64 frames from the two rows a per-rate table names (wave-uniform: scalar loads).  The kernel is
+// instantiated per bits-per-carrier class (NB = 1, 2, 4, 6 rows of 48), so that the LDS of a workgroup (one wave) is what
+// its rate needs: 12 / 24 / 48 / 72 kB + 4.5 kB of finish tables.
+//
+// The host groups the decodable frames by rate (decode_perm_kernel of wr_decode.hip: runs that start on 64-frame task
+// boundaries) and launches each class over its range of tasks.  Survivor bits: 8 bytes per step and lane in the handle's
+// decode scratch; trace-back, descramble and CRC follow per lane.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "wifirx.h"
+#include "wr_kernels.h"
+
+namespace wr {
+namespace soft {
+
+#define WR_SOFT_NORM_STEPS 24          // the common minimum leaves the metrics before every step t > 0, t % 24 == 0
+#define WR_SOFT_PUNCT 0xffffu          // table entry of a coded bit the transmitter dropped
+#define WR_SOFT_TAB_STRIDE 216         // steps per OFDM symbol at the highest rate
+
+// Where the de-punctured coded bit `ci` of ONE OFDM symbol sits among the symbol's 48 * n_bpsc LLRs (carrier * n_bpsc +
+// bit: the de-interleaver of the hard path, whose source is an LLR index here instead of a bit-plane position).
+constexpr uint32_t llr_of_coded(int punct, int n_bpsc, int ci)
+{
+    const int n_cbps = 48 * n_bpsc;
+    const int s = (n_bpsc / 2) < 1 ? 1 : (n_bpsc / 2);
+    int k = ci;
+    if (punct == 1) {                      // 2/3: every 4th bit dropped
+        const int r = ci & 3;
+        if (r == 3) return WR_SOFT_PUNCT;
+        k = (ci >> 2) * 3 + r;
+    } else if (punct == 2) {               // 3/4: bits 3,4 of every 6 dropped
+        const int g = ci / 6, r = ci - 6 * g;
+        if (r == 3 || r == 4) return WR_SOFT_PUNCT;
+        k = g * 4 + (r < 3 ? r : 3);
+    }
+    const int i = (n_cbps >> 4) * (k & 15) + (k >> 4);
+    return (uint32_t)(s * (i / s) + (i + n_cbps - (16 * i) / n_cbps) % s);
+}
+struct SoftTable { uint32_t e[8 * WR_SOFT_TAB_STRIDE]; };     // [enc][step of the symbol]: LLR of coded bit A | B << 16
+constexpr SoftTable make_soft_table()
+{
+    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
+    const int punct_tab[8] = { 0, 2, 0, 2, 0, 2, 1, 2 };
+    const int nbpsc_tab[8] = { 1, 1, 2, 2, 4, 4, 6, 6 };
+    SoftTable t{};
+    for (int enc = 0; enc < 8; enc++)
+        for (int tt = 0; tt < WR_SOFT_TAB_STRIDE; tt++) {
+            uint32_t v = WR_SOFT_PUNCT | (WR_SOFT_PUNCT << 16);
+            if (tt < ndbps_tab[enc])
+                v = llr_of_coded(punct_tab[enc], nbpsc_tab[enc], 2 * tt) | (llr_of_coded(punct_tab[enc], nbpsc_tab[enc], 2 * tt + 1) << 16);
+            t.e[enc * WR_SOFT_TAB_STRIDE + tt] = v;
+        }
+    return t;
+}
+__constant__ const SoftTable WR_SOFT_TABLE = make_soft_table();
+
+constexpr __host__ __device__ int rotr6(int s, int p) { return ((s >> p) | (s << (6 - p))) & 63; }
+constexpr __host__ __device__ int parity_of(int v) { return __builtin_popcount(v) & 1; }
+constexpr __host__ __device__ int nbpsc_of(int enc) { return enc < 2 ? 1 : enc < 4 ? 2 : enc < 6 ? 4 : 6; }
+constexpr __host__ __device__ int ndbps_of(int enc)      // (a select chain: a local table would live in scratch memory)
+{
+    return enc == 0 ? 24 : enc == 1 ? 36 : enc == 2 ? 48 : enc == 3 ? 72 : enc == 4 ? 96 : enc == 5 ? 144 : enc == 6 ? 192 : 216;
+}
+
+// trellis steps of a frame the soft decoder takes (the hard decoder's rule, WIFIRX_F_LLR, and LLR rows wide enough for
+// the rate), 0 for a frame it leaves alone
+__device__ __forceinline__ int frame_steps(uint32_t flags, int enc, int len, uint32_t psdu_stride, uint32_t max_sym,
+                                           uint32_t llr_bits, uint32_t n_steps_cap)
+{
+    const int n_dbps = ndbps_of(enc & 7);
+    const int n_sym = (16 + 8 * len + 6 + n_dbps - 1) / n_dbps;
+    const bool ok = (flags & WIFIRX_F_COMPLETE) && (flags & WIFIRX_F_LLR) && (uint32_t)nbpsc_of(enc & 7) <= llr_bits &&
+                    len <= (int)psdu_stride && len <= WIFIRX_MAX_PSDU && n_sym <= WIFIRX_MAX_SYM && n_sym <= (int)max_sym &&
+                    (uint32_t)(n_sym * n_dbps) <= n_steps_cap;
+    return ok ? n_sym * n_dbps : 0;
+}
+
+// One state of the add-compare-select: m = (c1 < c0) ? c1 : c0, and the decision (c1 < c0) shifted into acc from below.
+__device__ __forceinline__ void acs_state(float c0, float c1, float& m, uint32_t& acc)
+{
+    asm("v_cmp_lt_f32 vcc, %2, %3\n\t"
+        "v_cndmask_b32 %0, %3, %2, vcc\n\t"
+        "v_addc_co_u32 %1, vcc, %1, %1, vcc"
+        : "=v"(m), "+v"(acc)
+        : "v"(c1), "v"(c0)
+        : "vcc");
+}
+
+// one trellis step at register phase P: logical state s lives in pm[rotr6(s, P)].  bm[2 a + b]: branch metric of a
+// transition whose expected coded pair is (a, b).  acc[0] / acc[1]: the decisions of states 0..31 / 32..63, state s in
+// bit 31 - (s & 31).
+template <int P>
+__device__ __forceinline__ void acs_step(float (&pm)[64], const float (&bm)[4], uint32_t (&acc)[2])
+{
+#pragma unroll
+    for (int j = 0; j < 32; j++) {
+        const int a = parity_of((j << 1) & 0155), b = parity_of((j << 1) & 0117);
+        const float m = bm[2 * a + b], mb = bm[2 * (a ^ 1) + (b ^ 1)];
+        const int r0 = rotr6(j, P), r1 = rotr6(j + 32, P);
+        const float p0 = pm[r0], p1 = pm[r1];
+        // state 2j (input bit 0): from j with m (candidate 0), from j+32 with mb (candidate 1); state 2j+1: swapped
+        const float c00 = p0 + m, c01 = p1 + mb, c10 = p0 + mb, c11 = p1 + m;
+        acs_state(c00, c01, pm[r0], acc[j >> 4]);      // = register of logical state 2j at phase P+1
+        acs_state(c10, c11, pm[r1], acc[j >> 4]);      // = register of logical state 2j+1 at phase P+1
+    }
+}
+
+// CRC-32 "slicing by 4" and the scrambler's next 32 bits per state (workgroup LDS; the tables of the hard path's finish)
+struct FinishTables { uint32_t crc[4][256]; uint32_t scr[128]; };
+
+__device__ __forceinline__ void build_finish_tables(FinishTables& ft)
+{
+    for (int e = threadIdx.x; e < 256; e += blockDim.x) {
+        uint32_t c = (uint32_t)e;
+#pragma unroll
+        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1u)));
+        ft.crc[0][e] = c;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 256; e += blockDim.x) {
+        uint32_t c = ft.crc[0][e];
+        for (int k = 1; k < 4; k++) { c = (c >> 8) ^ ft.crc[0][c & 0xffu]; ft.crc[k][e] = c; }
+    }
+    for (int e = threadIdx.x; e < 128; e += blockDim.x) {
+        int state = e;
+        uint32_t w = 0;
+        for (int k = 0; k < 32; k++) {
+            const int fb = ((state >> 6) ^ (state >> 3)) & 1;
+            state = ((state << 1) & 0x7e) | fb;
+            w |= (uint32_t)fb << k;
+        }
+        ft.scr[e] = w;
+    }
+    __syncthreads();
+}
+
+// descramble (x^7+x^4+1, state from the first 7 decoded bits), bytes, CRC-32 of one frame; db = its decoded words
+// (word k = decoded bits 32 k .. 32 k + 31, stride 64 dwords, two spare words behind the last one)
+__device__ __forceinline__ void finish_frame(const uint32_t* __restrict__ db, int psdu_len, uint8_t* __restrict__ psdu,
+                                             bool dword_ok, wifirx_frame* __restrict__ rec, uint32_t flags,
+                                             const FinishTables& ft)
+{
+    uint32_t cur = db[0];
+    int state = 0;
+#pragma unroll
+    for (int i = 0; i < 7; i++) state |= (int)((cur >> i) & 1) << (6 - i);
+#pragma unroll
+    for (int i = 7; i < 16; i++) {             // the SERVICE field
+        int fb = ((state >> 6) ^ (state >> 3)) & 1;
+        state = ((state << 1) & 0x7e) | fb;
+    }
+    uint32_t crc = 0xffffffffu;
+    uint32_t nxt = db[64];
+    const int n_words = psdu_len >> 2;
+    for (int k = 0; k < n_words; k++) {
+        const uint32_t nn = db[(size_t)(k + 2) * 64];
+        const uint32_t sc = ft.scr[state];
+        state = (int)(__builtin_bitreverse32(sc) & 0x7fu);
+        const uint32_t d = __builtin_amdgcn_alignbit(nxt, cur, 16) ^ sc;    // positions 16 + 32 k .. + 31, descrambled
+        cur = nxt; nxt = nn;
+        if (dword_ok) *reinterpret_cast<uint32_t*>(psdu + 4 * k) = d;
+        else { psdu[4 * k] = (uint8_t)d; psdu[4 * k + 1] = (uint8_t)(d >> 8); psdu[4 * k + 2] = (uint8_t)(d >> 16); psdu[4 * k + 3] = (uint8_t)(d >> 24); }
+        const uint32_t x = crc ^ d;
+        crc = ft.crc[3][x & 0xffu] ^ ft.crc[2][(x >> 8) & 0xffu] ^ ft.crc[1][(x >> 16) & 0xffu] ^ ft.crc[0][x >> 24];
+    }
+    {
+        const uint32_t sc = ft.scr[state];
+        const uint32_t d = __builtin_amdgcn_alignbit(nxt, cur, 16) ^ sc;
+        for (int b = 4 * n_words; b < psdu_len; b++) {
+            const uint32_t byte = (d >> (8 * (b & 3))) & 0xffu;
+            psdu[b] = (uint8_t)byte;
+            crc = (crc >> 8) ^ ft.crc[0][(crc ^ byte) & 0xffu];
+        }
+    }
+    crc = ~crc;
+    uint32_t fl = flags | WIFIRX_F_DECODED;
+    if (psdu_len >= 4 && crc == 558161692u) fl |= WIFIRX_F_CRC_OK; else fl &= ~WIFIRX_F_CRC_OK;
+    rec->flags = fl;
+}
+
+// Tasks [task_lo, task_hi) of 64 frames each (grid-stride over n_waves_total waves, one wave per workgroup); frame k of
+// task T is perm[64 T + k] (0xffffffff: none), or slot 64 T + k without a permutation.  Every task holds frames of one
+// rate whose bits per carrier are NB.
+template <int NB>
+__global__ __launch_bounds__(64)
+void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, wifirx_frame* __restrict__ frames,
+                        const float* __restrict__ llr_all, uint8_t* __restrict__ psdu_all, uint32_t psdu_stride,
+                        uint8_t* __restrict__ scratch, size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves_total,
+                        const uint32_t* __restrict__ perm, uint32_t n_virtual, uint32_t task_lo, uint32_t task_hi)
+{
+    constexpr int N_CBPS = 48 * NB;
+    __shared__ float rows[N_CBPS * 64];          // LLR j of the current symbol of lane l's frame at rows[64 j + l]
+    __shared__ FinishTables ft;
+    build_finish_tables(ft);
+    const int lane = threadIdx.x;
+    const uint32_t wave = blockIdx.x;
+    float* roww = rows + lane;
+    uint32_t* surv = reinterpret_cast<uint32_t*>(scratch + (size_t)wave * scratch_stride);      // [step][lane][2]
+    uint32_t* dbits = surv + (size_t)n_steps_cap * 128;                                         // [word][lane]
+    const size_t row_stride = (size_t)max_sym * 48 * llr_bits;      // floats per frame
+
+    for (uint32_t task = task_lo + wave; task < task_hi; task += n_waves_total) {
+        const uint32_t v = task * 64u + (uint32_t)lane;
+        uint32_t slot = 0xffffffffu;
+        if (v < n_virtual) slot = perm ? perm[v] : v;
+        int n_data = 0, enc = 0;
+        if (slot < n_slots) {
+            enc = frames[slot].encoding & 7;
+            n_data = frame_steps(frames[slot].flags, enc, frames[slot].psdu_len, psdu_stride, max_sym, llr_bits, n_steps_cap);
+        } else {
+            slot = 0;
+        }
+        // the task's rate: that of its first frame; the host's grouping makes it every frame's (a frame of another rate
+        // would be left alone rather than decoded with the wrong tables)
+        const uint64_t act = __ballot(n_data > 0);
+        if (act == 0) continue;
+        const int enc_u = __builtin_amdgcn_readlane(enc, (int)__builtin_ctzll(act));
+        if (nbpsc_of(enc_u) != NB) continue;                 // wave-uniform; not this instance's class
+        if (enc != enc_u) n_data = 0;
+        int n_max = n_data;
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            int o = __shfl_xor(n_max, k, 64);
+            n_max = o > n_max ? o : n_max;
+        }
+        n_max = __builtin_amdgcn_readfirstlane(n_max);
+        const int nd_u = ndbps_of(enc_u);
+        const float4* src = reinterpret_cast<const float4*>(llr_all + (size_t)slot * row_stride);
+
+        // ---- add-compare-select ----
+        float pm[64];
+#pragma unroll
+        for (int s = 0; s < 64; s++) pm[s] = s == 0 ? 0.0f : __builtin_inff();
+        int best = 0;
+        int tt_u = 0, sym_u = 0, since_norm = 0;            // wave-uniform: step within the symbol, symbol, steps since the minimum left
+        for (int tg = 0; tg < n_max; tg += 6) {
+            if (since_norm == WR_SOFT_NORM_STEPS) {
+                // subtract the common minimum (register phase 0 here)
+                since_norm = 0;
+                float mn = pm[0];
+#pragma unroll
+                for (int s = 1; s < 64; s++) mn = fminf(mn, pm[s]);
+#pragma unroll
+                for (int s = 0; s < 64; s++) pm[s] = pm[s] - mn;
+            }
+            since_norm += 6;
+            if (tt_u == nd_u) { tt_u = 0; sym_u++; }
+            if (tt_u == 0 && tg < n_data) {
+                // a new OFDM symbol: its 48 NB LLRs, global (float4, contiguous per lane) -> the lane's column of the rows
+                const float4* sp = src + (size_t)sym_u * (N_CBPS / 4);
+#pragma unroll
+                for (int c = 0; c < N_CBPS / 4; c += 12) {
+                    float4 x[12];
+#pragma unroll
+                    for (int k = 0; k < 12; k++) x[k] = sp[c + k];
+#pragma unroll
+                    for (int k = 0; k < 12; k++) {
+                        roww[(4 * (c + k) + 0) * 64] = x[k].x;
+                        roww[(4 * (c + k) + 1) * 64] = x[k].y;
+                        roww[(4 * (c + k) + 2) * 64] = x[k].z;
+                        roww[(4 * (c + k) + 3) * 64] = x[k].w;
+                    }
+                }
+            }
+            const uint32_t* te = WR_SOFT_TABLE.e + (enc_u * WR_SOFT_TAB_STRIDE + tt_u);      // wave-uniform: scalar loads
+#define WR_SOFT_STEP(P)                                                                                   \
+            {                                                                                             \
+                const uint32_t e = te[P];                                                                 \
+                const uint32_t ea = e & 0xffffu, eb = e >> 16;                                            \
+                float la = roww[(ea == WR_SOFT_PUNCT ? 0u : ea) * 64];                                    \
+                float lb = roww[(eb == WR_SOFT_PUNCT ? 0u : eb) * 64];                                    \
+                if (ea == WR_SOFT_PUNCT || !__builtin_isfinite(la)) la = 0.0f;                            \
+                if (eb == WR_SOFT_PUNCT || !__builtin_isfinite(lb)) lb = 0.0f;                            \
+                const float a0 = fmaxf(la, 0.0f), a1 = fmaxf(-la, 0.0f);                                  \
+                const float b0 = fmaxf(lb, 0.0f), b1 = fmaxf(-lb, 0.0f);                                  \
+                const float bm[4] = { a0 + b0, a0 + b1, a1 + b0, a1 + b1 };                               \
+                uint32_t acc[2] = { 0u, 0u };                                                             \
+                acs_step<P>(pm, bm, acc);                                                                 \
+                *reinterpret_cast<uint2*>(surv + ((size_t)(tg + P) * 64 + lane) * 2) = make_uint2(acc[0], acc[1]); \
+            }
+            WR_SOFT_STEP(0) WR_SOFT_STEP(1) WR_SOFT_STEP(2) WR_SOFT_STEP(3) WR_SOFT_STEP(4) WR_SOFT_STEP(5)
+#undef WR_SOFT_STEP
+            {
+                const bool end = tg + 6 == n_data;
+                if (__any(end)) {
+                    // a frame just ended (register phase 0 again): smallest metric, lowest state
+                    float bv = pm[0];
+                    int bs = 0;
+#pragma unroll
+                    for (int s = 1; s < 64; s++)
+                        if (pm[s] < bv) { bv = pm[s]; bs = s; }
+                    if (end) best = bs;
+                }
+            }
+            tt_u += 6;
+        }
+        __threadfence_block();
+        // ---- trace-back: 32 decoded bits per word, words stored [word][lane]; the survivor rows are loaded ahead ----
+        {
+            int st = best;
+            uint32_t word = 0;
+            for (int t1 = n_max - 1; t1 >= 0; t1 -= 16) {
+                uint2 r[16];
+#pragma unroll
+                for (int k = 0; k < 16; k++) {
+                    const int t = t1 - k < 0 ? 0 : t1 - k;      // rows below n_max were all written: no branch around the loads
+                    r[k] = *reinterpret_cast<const uint2*>(surv + ((size_t)t * 64 + lane) * 2);
+                }
+#pragma unroll
+                for (int k = 0; k < 16; k++) {
+                    const int t = t1 - k;
+                    if (t >= 0 && t < n_data) {
+                        word |= (uint32_t)(st & 1) << (t & 31);
+                        const uint64_t w = ((uint64_t)r[k].x << 32) | r[k].y;         // state s in bit 63 - s
+                        const uint32_t hb = (uint32_t)(w >> (63 - st)) & 1u;
+                        st = (st >> 1) | (int)(hb << 5);
+                        if ((t & 31) == 0) { dbits[(size_t)(t >> 5) * 64 + lane] = word; word = 0; }
+                    }
+                }
+            }
+        }
+        __threadfence_block();
+        // ---- descramble, bytes, CRC-32 ----
+        if (n_data > 0)
+            finish_frame(dbits + lane, frames[slot].psdu_len, psdu_all + (size_t)slot * psdu_stride,
+                         ((reinterpret_cast<uintptr_t>(psdu_all) | psdu_stride) & 3) == 0, frames + slot, frames[slot].flags, ft);
+    }
+}
+
+}  // namespace soft
+}  // namespace wr
+
+extern "C" hipError_t wr_launch_decode_soft(hipStream_t st, int nb, uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits,
+                                            wifirx_frame* frames, const float* llr, uint8_t* psdu, uint32_t psdu_stride,
+                                            uint8_t* scratch, size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves,
+                                            const uint32_t* perm, uint32_t n_virtual, uint32_t task_lo, uint32_t task_hi)
+{
+    if (n_slots == 0 || n_waves == 0 || task_hi <= task_lo) return hipSuccess;
+    if (!perm) n_virtual = n_slots;
+#define WR_LAUNCH_SOFT(NB) hipLaunchKernelGGL(wr::soft::decode_soft_kernel<NB>, dim3(n_waves), dim3(64), 0, st, n_slots, max_sym, \
+                                              llr_bits, frames, llr, psdu, psdu_stride, scratch, scratch_stride, n_steps_cap, n_waves, \
+                                              perm, n_virtual, task_lo, task_hi)
+    switch (nb) {
+    case 1: WR_LAUNCH_SOFT(1); break;
+    case 2: WR_LAUNCH_SOFT(2); break;
+    case 4: WR_LAUNCH_SOFT(4); break;
+    case 6: WR_LAUNCH_SOFT(6); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef WR_LAUNCH_SOFT
+    return hipGetLastError();
+}

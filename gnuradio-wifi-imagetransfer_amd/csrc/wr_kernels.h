@@ -96,6 +96,10 @@ hipError_t wr_launch_decode_q(hipStream_t st, uint32_t n_slots, uint32_t max_sym
                               const uint32_t* perm, uint32_t n_virtual, int has_64qam, int overlap);
 hipError_t wr_launch_decode_perm(hipStream_t st, uint32_t n_slots, uint32_t max_sym, const wifirx_frame* frames,
                                  uint32_t psdu_stride, const uint32_t* starts8, uint32_t* cursor8, uint32_t* perm);
+hipError_t wr_launch_decode_soft(hipStream_t st, int nb, uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits,
+                                 wifirx_frame* frames, const float* llr, uint8_t* psdu, uint32_t psdu_stride,
+                                 uint8_t* scratch, size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves,
+                                 const uint32_t* perm, uint32_t n_virtual, uint32_t task_lo, uint32_t task_hi);
 hipError_t wr_launch_decode_small(hipStream_t st, uint32_t n_slots, uint32_t max_sym, wifirx_frame* frames,
                                   const uint32_t* hbits, uint8_t* psdu, uint32_t psdu_stride, uint8_t* scratch,
                                   size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves);

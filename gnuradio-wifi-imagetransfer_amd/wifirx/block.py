@@ -34,7 +34,8 @@ LINKTYPE_IEEE802_11 = 105
 
 class wifi_phy_rx(grshim.sync_block):
     def __init__(self, bandwidth=10e6, chan_est=LS, encoding=0, frequency=5.89e9, sensitivity=0.56,
-                 max_sym=511, publish_carrier=True, device=0, batch_samples=None, publish_csi=False, snr_probe=None):
+                 max_sym=511, publish_carrier=True, device=0, batch_samples=None, publish_csi=False, snr_probe=None,
+                 soft_decision=False):
         grshim.sync_block.__init__(self, name="wifi_phy_rx", in_sig=[np.complex64], out_sig=None)
         self.bandwidth = float(bandwidth)
         self.chan_est = int(chan_est)
@@ -68,6 +69,9 @@ class wifi_phy_rx(grshim.sync_block):
         self.batch_samples = min(int(batch_samples), capi.STREAM_BATCH_MAX)
         self._rx.set_param(capi.P_STREAM_BATCH, self.batch_samples)
         self._rx.set_param(capi.P_STREAM_IDX, 0)            # PDUs only: the hard decisions stay on the device
+        self.soft_decision = False
+        if soft_decision:
+            self.set_soft_decision(True)
         self._push = capi.lib().wifirx_push
         self._queued = capi.lib().wifirx_queued
         self._h = self._rx._h
@@ -111,6 +115,18 @@ class wifi_phy_rx(grshim.sync_block):
     def set_sensitivity(self, sensitivity):
         self.sensitivity = float(sensitivity)
         self._rx.set_param(capi.P_SENSITIVITY, self.sensitivity)
+
+    def get_soft_decision(self):
+        return self.soft_decision
+
+    def set_soft_decision(self, soft_decision):
+        """True: decode_mac runs the soft-decision Viterbi on channel-state-weighted LLRs (WIFIRX_P_STREAM_SOFT and
+        WIFIRX_P_LLR_CSI, NUMERICS.md rules 12 and 14) for the batches that run after the call; False: upstream's hard
+        decoder (the default).  `mac_out` PDUs keep their format either way."""
+        on = 1 if soft_decision else 0
+        self._rx.set_param(capi.P_STREAM_SOFT, on)
+        self._rx.set_param(capi.P_LLR_CSI, on)
+        self.soft_decision = bool(on)
 
     def get_encoding(self):
         return self.encoding

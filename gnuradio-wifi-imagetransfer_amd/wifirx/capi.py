@@ -20,6 +20,7 @@ EQ_LS, EQ_LMS, EQ_COMB, EQ_STA = 0, 1, 2, 3
 OK, EINVAL, ENODEV, ENOMEM, EHIP, ERANGE, EDEAD = 0, -1, -2, -3, -4, -5, -6      # WIFIRX_E*; EDEAD: the stream is dead, do not retry
 STREAM_BATCH_MAX = 1 << 27          # WIFIRX_STREAM_BATCH_MAX
 P_BANDWIDTH, P_FREQUENCY, P_SENSITIVITY, P_CHAN_EST, P_STREAM_BATCH, P_DECODE_SMALL_MAX, P_LLR_CSI, P_STREAM_IDX = 1, 2, 3, 4, 5, 6, 7, 8
+P_STREAM_SOFT = 9                   # stream mode: decode_mac on LLRs (wifirx_decode_batch_soft, NUMERICS.md rule 14)
 F_DETECTED, F_SYNC, F_SIGNAL, F_COMPLETE, F_LLR, F_DECODED, F_CRC_OK = 1, 2, 4, 8, 16, 32, 64
 
 FRAME_DTYPE = np.dtype([
@@ -35,7 +36,7 @@ EXPORTS = [
     "wifirx_get_stats", "wifirx_demod_batch", "wifirx_decode_batch", "wifirx_push", "wifirx_poll", "wifirx_poll_csi",
     "wifirx_sync", "wifirx_stream", "wifirx_synth_slots", "wifirx_dev_alloc", "wifirx_dev_free",
     "wifirx_memcpy_h2d", "wifirx_memcpy_d2h", "wifirx_time_demod", "wifirx_poll_ex", "wifirx_demod_batch_v",
-    "wifirx_push_consumed", "wifirx_queued",
+    "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft",
 ]
 
 
@@ -83,6 +84,7 @@ _lib.wifirx_set_param.argtypes = [C.c_void_p, C.c_int, C.c_double]
 _lib.wifirx_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
 _lib.wifirx_demod_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(Out)]
 _lib.wifirx_decode_batch.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out)]
+_lib.wifirx_decode_batch_soft.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out)]
 _lib.wifirx_demod_batch_v.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(Out)]
 _lib.wifirx_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
 _lib.wifirx_push_consumed.restype = C.c_size_t
@@ -197,7 +199,8 @@ class WifiRx:
 
     # -- batch mode, host buffers (PCIe-bound convenience path) --
     def demod_batch(self, iq: np.ndarray, slot_len: int, decode=False, psdu_stride=2048, want_csi=False,
-                    want_stats=False, want_hbits=False) -> dict:
+                    want_stats=False, want_hbits=False, soft=False) -> dict:
+        """soft=True (with decode): decode_mac on the LLRs (wifirx_decode_batch_soft; the handle needs llr_bits > 0)."""
         iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
         n_slots = iq.size // slot_len
         assert n_slots * slot_len == iq.size
@@ -223,7 +226,10 @@ class WifiRx:
                              want_hbits=want_hbits or DECODE_INPUT == "planes")
         try:
             self.demod_batch_dev(d_iq.ptr, slot_len, n_slots, dev)
-            self.decode_batch_dev(n_slots, dev)
+            if soft:
+                self.decode_batch_soft_dev(n_slots, dev)
+            else:
+                self.decode_batch_dev(n_slots, dev)
             self.sync()
             return self.download_out(dev, n_slots)
         finally:
@@ -279,6 +285,11 @@ class WifiRx:
     def decode_batch_dev(self, n_slots, dev):
         out = self._out_struct(dev)
         self._check(_lib.wifirx_decode_batch(self._h, n_slots, C.byref(out)))
+
+    def decode_batch_soft_dev(self, n_slots, dev):
+        """soft-decision decode_mac over the LLR rows of dev (alloc_out allocates them when the handle has llr_bits > 0)"""
+        out = self._out_struct(dev)
+        self._check(_lib.wifirx_decode_batch_soft(self._h, n_slots, C.byref(out)))
 
     def time_demod(self, iq_ptr, slot_len, n_slots, dev, iters=1) -> float:
         out = self._out_struct(dev)

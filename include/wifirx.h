@@ -142,6 +142,11 @@ typedef struct wifirx_config {
 /* stream mode: 0 = the hard decisions of the frames stay on the device (wifirx_poll* then delivers zeros for `idx`);
  * default 1.  A consumer of PDUs only (the wifi_phy_rx block) saves most of the device-to-host traffic of a push. */
 #define WIFIRX_P_STREAM_IDX 8
+/* stream mode: 1 = decode_mac runs on LLRs (wifirx_decode_batch_soft, NUMERICS.md rule 14) instead of the hard decisions.
+ * The frame kernel then writes LLRs with 6 bits per carrier reserved into rows the handle owns (max_sym * 48 * 6 floats
+ * per trigger, allocated once the mode is on), whatever cfg.llr_bits is; WIFIRX_P_LLR_CSI weights them as in batch mode.
+ * Default 0 (the upstream hard-decision decoder); other values are WIFIRX_EINVAL.  Batches run after the call use it. */
+#define WIFIRX_P_STREAM_SOFT 9
 
 typedef struct wifirx_handle wifirx_handle;
 
@@ -239,6 +244,14 @@ int  wifirx_demod_batch_v(wifirx_handle* h, const float* iq, int iq_on_device, c
  * stream (a pre-pass reads back the longest trellis of the batch to size the survivor scratch);
  * the decode kernel itself is then queued asynchronously. */
 int  wifirx_decode_batch(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out);
+
+/* Soft-decision decode_mac: wifirx_decode_batch with the Viterbi on the LLRs of out->llr (rows of
+ * max_sym * 48 * cfg.llr_bits floats, as wifirx_demod_batch writes them, 16-byte aligned) instead of the hard decisions;
+ * metrics, tie rule, normalisation and final state are NUMERICS.md rule 14.  It decodes the frames wifirx_decode_batch
+ * would that also carry WIFIRX_F_LLR, and leaves every other record as it is; WIFIRX_F_DECODED, WIFIRX_F_CRC_OK and
+ * out->psdu mean what they mean there.  WIFIRX_EINVAL when out->llr is NULL, the handle has llr_bits = 0, or the buffers
+ * are not on the device.  Same waiting, scratch and allocation behaviour as wifirx_decode_batch. */
+int  wifirx_decode_batch_soft(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out);
 
 /* Stream mode (what the GNU Radio block's work() calls): append `n` samples of the continuous
  * input stream (host or device memory; the library copies).  Frames that completed inside the
