@@ -8,6 +8,90 @@ extern "C" int wifirx_decode_batch(wifirx_handle* h, uint32_t n_slots, const wif
     return decode_batch_impl(h, n_slots, out);
 }
 
+// ---- what both decoders share: the pre-pass, the grouping by rate, the survivor scratch ----
+
+// The pre-pass: longest trellis of the batch (it sizes the survivor scratch) -> pre[0], 0 when nothing is decodable;
+// decodable frames per rate -> pre[1 + enc].  The one host sync of a decode call.
+static int decode_prepass(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t (&pre)[9])
+{
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure(h, &h->dec_max, &h->dec_max_bytes, 256);
+    if (rc) return rc;
+    // dec_max: [0] longest trellis, [1..8] decodable frames per rate, [16..23] cursors of the permutation kernel
+    HIP_TRY(h, hipMemsetAsync(h->dec_max, 0, 256, h->stream));
+    HIP_TRY(h, wr_launch_decode_maxsteps(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride,
+                                         reinterpret_cast<uint32_t*>(h->dec_max)));
+    HIP_TRY(h, hipMemcpyAsync(pre, h->dec_max, sizeof pre, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return WIFIRX_OK;
+}
+
+// Tasks of `fpw` frames, each of one rate.  Several rates in the batch: the decodable frames are grouped by rate (a
+// permutation, built on the device), every run starting on a task boundary -- the run of rate e is [starts[e],
+// starts[e + 1]) -- so that each wave's frames share one rate: the decoders then read where a coded bit sits through the
+// scalar unit for all of them (the per-lane look-ups of mixed waves cost +25 %), and frames decode_mac leaves alone take
+// no lane at all.  One rate: no permutation, frame k is slot k.
+struct DecodeGroups { uint32_t starts[9]; uint32_t n_virtual; const uint32_t* perm; };      // perm = nullptr: n_virtual = n_slots
+
+static int decode_group_by_rate(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, const uint32_t (&pre)[9],
+                                uint32_t fpw, DecodeGroups& g)
+{
+    uint32_t n_rates = 0;
+    g.starts[0] = 0;
+    for (int e = 0; e < 8; e++) {
+        n_rates += pre[1 + e] != 0;
+        g.starts[e + 1] = g.starts[e] + (pre[1 + e] + fpw - 1) / fpw * fpw;
+    }
+    g.n_virtual = n_rates > 1 ? g.starts[8] : n_slots;
+    g.perm = nullptr;
+    if (n_rates <= 1) return WIFIRX_OK;
+    int rc = ensure(h, &h->dec_perm, &h->dec_perm_bytes, (size_t)g.n_virtual * sizeof(uint32_t));
+    if (rc) return rc;
+    HIP_TRY(h, hipMemsetAsync(h->dec_perm, 0xff, (size_t)g.n_virtual * sizeof(uint32_t), h->stream));
+    HIP_TRY(h, wr_launch_decode_perm(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride, g.starts,
+                                     reinterpret_cast<uint32_t*>(h->dec_max) + 16, reinterpret_cast<uint32_t*>(h->dec_perm)));
+    g.perm = reinterpret_cast<const uint32_t*>(h->dec_perm);
+    return WIFIRX_OK;
+}
+
+// The scratch budget: WR_DECODE_SCRATCH_BUDGET at most, and no more than 70 % of what the device has free right now (plus
+// what this handle already holds for the purpose) -- a process that shares the GPU with other buffers, or holds several
+// handles, gets fewer waves instead of ENOMEM (ADVICE r03).  The slice is kept until wifirx_destroy (INTEGRATION.md:
+// footprint).
+static size_t decode_scratch_budget(wifirx_handle* h)
+{
+    size_t budget = WR_DECODE_SCRATCH_BUDGET;
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget = std::min<size_t>(budget, (mem_free + h->dec_scratch_bytes) / 10 * 7);
+    else (void)hipGetLastError();
+    if (h->test_decode_budget) budget = std::min<size_t>(budget, h->test_decode_budget);
+    return budget;
+}
+
+// `stride` bytes per wave for up to `want` waves, as many as the budget holds.  If the allocation fails all the same: half
+// the waves, and again, down to four -- the kernels are grid-stride over tasks, fewer waves only take longer.
+static int decode_alloc_scratch(wifirx_handle* h, size_t stride, size_t want, size_t budget, size_t& n_waves)
+{
+    n_waves = std::max<size_t>(1, std::min<size_t>(want, budget / stride));
+    for (;;) {
+        int rc;
+        if (h->test_fail_decode_scratch > 0 && h->test_fail_decode_scratch-- > 0) {
+            // test hook: a REAL failing hipMalloc (a size no device has), so that the retry runs with whatever state HIP keeps
+            // after an exhausted allocation -- the sticky last-error above all (ADVICE r04)
+            void* none = nullptr;
+            size_t none_bytes = 0;
+            rc = ensure(h, &none, &none_bytes, SIZE_MAX / 2);
+            if (rc == WIFIRX_OK) { (void)hipFree(none); rc = fail(h, WIFIRX_ENOMEM, "hipMalloc(decode scratch): test hook"); }
+        } else {
+            rc = ensure(h, &h->dec_scratch, &h->dec_scratch_bytes, stride * n_waves);
+        }
+        if (rc == WIFIRX_OK) return WIFIRX_OK;
+        if (rc != WIFIRX_ENOMEM || n_waves <= 4) return rc;
+        n_waves /= 2;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out)
 {
     if (!h || !out) return WIFIRX_EINVAL;
@@ -16,19 +100,10 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
         return fail(h, WIFIRX_EINVAL, "frames, hbits or idx, and psdu (with psdu_stride) are required");
     if (reinterpret_cast<uintptr_t>(out->hbits) & 15) return fail(h, WIFIRX_EINVAL, "out->hbits must be 16-byte aligned");
     if (n_slots == 0) return WIFIRX_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    // longest trellis in this batch: sizes the survivor scratch (64 bits per step and frame)
-    int rc = ensure(h, &h->dec_max, &h->dec_max_bytes, 256);
-    if (rc) return rc;
-    // dec_max: [0] longest trellis, [1..8] decodable frames per rate, [16..23] cursors of the permutation kernel
     uint32_t pre[9] = { 0 };
-    HIP_TRY(h, hipMemsetAsync(h->dec_max, 0, 256, h->stream));
-    HIP_TRY(h, wr_launch_decode_maxsteps(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride,
-                                         reinterpret_cast<uint32_t*>(h->dec_max)));
-    HIP_TRY(h, hipMemcpyAsync(pre, h->dec_max, sizeof pre, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = decode_prepass(h, n_slots, out, pre);
+    if (rc || pre[0] == 0) return rc;                         // (pre[0] == 0: nothing decodable)
     const uint32_t n_steps = pre[0];
-    if (n_steps == 0) return WIFIRX_OK;                       // nothing decodable
     // the decoders read the decisions as bit planes: the caller's (written by the demod kernel), or packed from idx here
     const uint32_t* hbits = out->hbits;
     if (!hbits) {
@@ -58,89 +133,39 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
     const bool use_q = h->decode_q == 1 || (h->decode_q < 0 && n_dec >= WR_DECODE_Q_MIN_FRAMES);
     const uint32_t fpw_max = use_q ? WR_DECODE_Q_FRAMES_PER_WAVE : WR_DECODE_FRAMES_PER_WAVE;
     size_t stride = use_q ? (size_t)n_steps * 64 * 32 + ((size_t)n_steps / 32 + 2) * WR_DECODE_Q_FRAMES_PER_WAVE * sizeof(uint32_t)
-                                : (size_t)n_steps * 64 * 16 + ((size_t)n_steps / 32 + 2) * WR_DECODE_FRAMES_PER_WAVE * sizeof(uint32_t);
+                          : (size_t)n_steps * 64 * 16 + ((size_t)n_steps / 32 + 2) * WR_DECODE_FRAMES_PER_WAVE * sizeof(uint32_t);
     // mid-size batches: fewer frames per wave, so that about a thousand waves share the work
     uint32_t fpw = (uint32_t)std::min<size_t>(fpw_max, std::max<size_t>(1, (n_slots + 1023) / 1024));
     if (use_q && h->decode_q < 0) fpw = fpw_max;
     if (h->decode_fpw) fpw = std::min<uint32_t>(fpw_max, h->decode_fpw);     // tests: full waves on small batches
-    // Several rates in the batch: the decodable frames are grouped by rate (a permutation, built on the device), every
-    // run starting on a task boundary, so that each wave's frames share one rate -- the decoder then reads where a coded
-    // bit sits through the scalar unit for all of them (the per-lane look-ups of mixed waves cost +25 %), and frames
-    // decode_mac leaves alone take no lane at all.
-    uint32_t n_rates = 0, n_virtual = n_slots;
-    for (int e = 0; e < 8; e++) n_rates += pre[1 + e] != 0;
-    const uint32_t* perm = nullptr;
-    if (n_rates > 1) {
-        uint32_t starts[8], at = 0;
-        for (int e = 0; e < 8; e++) { starts[e] = at; at += (pre[1 + e] + fpw - 1) / fpw * fpw; }
-        n_virtual = at;
-        rc = ensure(h, &h->dec_perm, &h->dec_perm_bytes, (size_t)n_virtual * sizeof(uint32_t));
-        if (rc) return rc;
-        HIP_TRY(h, hipMemsetAsync(h->dec_perm, 0xff, (size_t)n_virtual * sizeof(uint32_t), h->stream));
-        HIP_TRY(h, wr_launch_decode_perm(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride, starts,
-                                         reinterpret_cast<uint32_t*>(h->dec_max) + 16, reinterpret_cast<uint32_t*>(h->dec_perm)));
-        perm = reinterpret_cast<const uint32_t*>(h->dec_perm);
-    }
-    const size_t n_tasks = (n_virtual + fpw - 1) / fpw;
+    DecodeGroups g;
+    if ((rc = decode_group_by_rate(h, n_slots, out, pre, fpw, g))) return rc;
+    const size_t n_tasks = (g.n_virtual + fpw - 1) / fpw;
     // decode_q_kernel hides the trace-back under add-compare-select work when the batch fills the GPU with 256-frame tasks: mode 2
-    // (round 5, the default then) walks every block of 96 steps back speculatively while the task's own next block runs -- three waves
-    // per SIMD (168 registers; two for the 64-QAM instance), one scratch slice per wave + the walks' start states; mode 1 (round 3) defers a task's trace-back
-    // to the wave's next task -- it needs two tasks per wave and a double slice.  WIFIRX_DECODE_OVL = 0 / 1 / 2 forces a mode
-    // (tests, A/B).
-    // The scratch budget: WR_DECODE_SCRATCH_BUDGET at most, and no more than 70 % of what the device has free right now (plus what
-    // this handle already holds for the purpose) -- a process that shares the GPU with other buffers, or holds several handles,
-    // gets fewer waves instead of ENOMEM (ADVICE r03).  The slice is kept until wifirx_destroy (INTEGRATION.md: footprint).
-    size_t budget = WR_DECODE_SCRATCH_BUDGET;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget = std::min<size_t>(budget, (mem_free + h->dec_scratch_bytes) / 10 * 7);
-        else (void)hipGetLastError();
-        if (h->test_decode_budget) budget = std::min<size_t>(budget, h->test_decode_budget);
-    }
+    // (round 5) walks every block of 96 steps back speculatively while the task's own next block runs -- three waves per SIMD
+    // (168 registers; two for the 64-QAM instance), one scratch slice per wave + the walks' start states.  Mode 0: the trace-back
+    // behind each task.  WIFIRX_DECODE_OVL = 0 / 2 forces a mode (tests, A/B).
+    size_t budget = decode_scratch_budget(h);
     const size_t stride_spec = stride + ((size_t)n_steps / 96 + 2) * 64 * sizeof(uint32_t);
-    const size_t spec_waves = 1024u * ((pre[7] | pre[8]) ? 2 : WR_DQ_SPEC_WAVES);      // (the 64-QAM instance: two workgroups of its LDS fit a CU)
+    const size_t spec_waves = (size_t)h->n_simd * ((pre[7] | pre[8]) ? 2 : WR_DQ_SPEC_WAVES);      // (the 64-QAM instance: two workgroups of its LDS fit a CU)
     int mode = 0;
     if (use_q) {
         if (h->decode_ovl >= 0) mode = h->decode_ovl;
         else if (n_tasks >= WR_DECODE_MAX_WAVES / 2 && budget / stride_spec >= spec_waves) mode = 2;
     }
-    // If the allocation fails all the same: first without the overlap (fewer registers: more, smaller waves are possible), then with
-    // half the waves, and again, down to four waves -- the kernels are grid-stride over tasks, fewer waves only take longer.
+    // the scratch falls back to fewer waves only: the mode stays what was chosen
+    if (mode == 2) stride = stride_spec;
     size_t n_waves = 0;
-    const size_t stride1 = stride;
-    for (;;) {
-        stride = mode == 1 ? 2 * stride1 : mode == 2 ? stride_spec : stride1;
-        n_waves = mode == 1 ? std::min<size_t>((n_tasks + 1) / 2, WR_DECODE_MAX_WAVES / 2)
-                : mode == 2 ? std::min<size_t>(n_tasks, spec_waves) : std::min<size_t>(n_tasks, WR_DECODE_MAX_WAVES);
-        n_waves = std::max<size_t>(1, std::min<size_t>(n_waves, budget / stride));
-        if (h->test_fail_decode_scratch > 0 && h->test_fail_decode_scratch-- > 0) {
-            // test hook: a REAL failing hipMalloc (a size no device has), so that the retry runs with whatever state HIP keeps
-            // after an exhausted allocation -- the sticky last-error above all (ADVICE r04)
-            void* none = nullptr;
-            size_t none_bytes = 0;
-            rc = ensure(h, &none, &none_bytes, SIZE_MAX / 2);
-            if (rc == WIFIRX_OK) { (void)hipFree(none); rc = fail(h, WIFIRX_ENOMEM, "hipMalloc(decode scratch): test hook"); }
-        } else {
-            rc = ensure(h, &h->dec_scratch, &h->dec_scratch_bytes, stride * n_waves);
-        }
-        if (rc == WIFIRX_OK) break;
-        if (rc != WIFIRX_ENOMEM) return rc;
-        if (mode == 1) { mode = 0; continue; }
-        if (n_waves <= 4) return rc;
-        budget = stride * (n_waves / 2);
-    }
-    const bool overlap = mode != 0;
-    h->dec_last_waves = (uint32_t)n_waves;
-    h->dec_last_overlap = overlap;
-    h->dec_last_mode = mode;
+    if ((rc = decode_alloc_scratch(h, stride, std::min<size_t>(n_tasks, mode == 2 ? spec_waves : WR_DECODE_MAX_WAVES), budget, n_waves)))
+        return rc;
     if (use_q)
         HIP_TRY(h, wr_launch_decode_q(h->stream, n_slots, h->cfg.max_sym, out->frames, hbits, out->psdu,
                                       out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride, n_steps,
-                                      (uint32_t)n_waves, fpw, perm, n_virtual, (pre[7] | pre[8]) != 0, mode));
+                                      (uint32_t)n_waves, fpw, g.perm, g.n_virtual, (pre[7] | pre[8]) != 0, mode));
     else
         HIP_TRY(h, wr_launch_decode(h->stream, n_slots, h->cfg.max_sym, out->frames, hbits, out->psdu,
                                     out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride, n_steps,
-                                    (uint32_t)n_waves, fpw, perm, n_virtual));
+                                    (uint32_t)n_waves, fpw, g.perm, g.n_virtual));
     return WIFIRX_OK;
 }
 
@@ -164,65 +189,31 @@ static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifi
         return fail(h, WIFIRX_EINVAL, "frames, llr and psdu (with psdu_stride) are required");
     if (reinterpret_cast<uintptr_t>(out->llr) & 15) return fail(h, WIFIRX_EINVAL, "out->llr must be 16-byte aligned");
     if (n_slots == 0) return WIFIRX_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    // the hard path's pre-pass: longest trellis, decodable frames per rate (frames without WIFIRX_F_LLR are counted too;
-    // the kernel leaves them alone)
-    int rc = ensure(h, &h->dec_max, &h->dec_max_bytes, 256);
-    if (rc) return rc;
+    // the hard path's pre-pass (frames without WIFIRX_F_LLR are counted too; the kernel leaves them alone)
     uint32_t pre[9] = { 0 };
-    HIP_TRY(h, hipMemsetAsync(h->dec_max, 0, 256, h->stream));
-    HIP_TRY(h, wr_launch_decode_maxsteps(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride,
-                                         reinterpret_cast<uint32_t*>(h->dec_max)));
-    HIP_TRY(h, hipMemcpyAsync(pre, h->dec_max, sizeof pre, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = decode_prepass(h, n_slots, out, pre);
+    if (rc || pre[0] == 0) return rc;
     const uint32_t n_steps = pre[0];
-    if (n_steps == 0) return WIFIRX_OK;
-    // tasks of 64 frames (one per lane), each of one rate: several rates are grouped by rate on the device, every run
-    // starting on a task boundary; one launch per bits-per-carrier class over its range of tasks
+    // tasks of 64 frames (one per lane), each of one rate; one launch per bits-per-carrier class over its range of tasks
     const uint32_t fpw = 64;
-    uint32_t n_rates = 0, n_virtual = n_slots;
-    for (int e = 0; e < 8; e++) n_rates += pre[1 + e] != 0;
-    uint32_t starts[9] = { 0 };
-    for (int e = 0; e < 8; e++) starts[e + 1] = starts[e] + (pre[1 + e] + fpw - 1) / fpw * fpw;
-    const uint32_t* perm = nullptr;
-    if (n_rates > 1) {
-        n_virtual = starts[8];
-        rc = ensure(h, &h->dec_perm, &h->dec_perm_bytes, (size_t)n_virtual * sizeof(uint32_t));
-        if (rc) return rc;
-        HIP_TRY(h, hipMemsetAsync(h->dec_perm, 0xff, (size_t)n_virtual * sizeof(uint32_t), h->stream));
-        HIP_TRY(h, wr_launch_decode_perm(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride, starts,
-                                         reinterpret_cast<uint32_t*>(h->dec_max) + 16, reinterpret_cast<uint32_t*>(h->dec_perm)));
-        perm = reinterpret_cast<const uint32_t*>(h->dec_perm);
-    }
-    const size_t n_tasks = (n_virtual + fpw - 1) / fpw;
+    DecodeGroups g;
+    if ((rc = decode_group_by_rate(h, n_slots, out, pre, fpw, g))) return rc;
+    const size_t n_tasks = (g.n_virtual + fpw - 1) / fpw;
     // per wave: 8 bytes of survivor bits per step and lane, the decoded words of its 64 frames (two spare words)
     const size_t stride = (size_t)n_steps * 64 * 8 + ((size_t)n_steps / 32 + 2) * 64 * sizeof(uint32_t);
-    size_t budget = WR_DECODE_SCRATCH_BUDGET;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget = std::min<size_t>(budget, (mem_free + h->dec_scratch_bytes) / 10 * 7);
-        else (void)hipGetLastError();
-        if (h->test_decode_budget) budget = std::min<size_t>(budget, h->test_decode_budget);
-    }
-    // the kernel is grid-stride over tasks: if the scratch cannot be had, fewer waves (down to four) take longer
-    size_t n_waves = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_tasks, WR_DECODE_MAX_WAVES), budget / stride));
-    for (;;) {
-        rc = ensure(h, &h->dec_scratch, &h->dec_scratch_bytes, stride * n_waves);
-        if (rc == WIFIRX_OK) break;
-        if (rc != WIFIRX_ENOMEM || n_waves <= 4) return rc;
-        n_waves /= 2;
-    }
-    h->dec_last_waves = (uint32_t)n_waves;
+    size_t n_waves = 0;
+    if ((rc = decode_alloc_scratch(h, stride, std::min<size_t>(n_tasks, WR_DECODE_MAX_WAVES), decode_scratch_budget(h), n_waves)))
+        return rc;
     const int nb_of_class[4] = { 1, 2, 4, 6 };
     for (int c = 0; c < 4; c++) {
         const int e0 = 2 * c, e1 = 2 * c + 1;
         if (pre[1 + e0] == 0 && pre[1 + e1] == 0) continue;
         // task range of the class: its runs in the permutation, or every task when the batch holds one rate
-        const uint32_t lo = perm ? starts[e0] / fpw : 0u, hi = perm ? starts[e1 + 1] / fpw : (uint32_t)n_tasks;
+        const uint32_t lo = g.perm ? g.starts[e0] / fpw : 0u, hi = g.perm ? g.starts[e1 + 1] / fpw : (uint32_t)n_tasks;
         const uint32_t waves = (uint32_t)std::min<size_t>(n_waves, hi - lo);
         HIP_TRY(h, wr_launch_decode_soft(h->stream, nb_of_class[c], n_slots, h->cfg.max_sym, llr_bits, out->frames, out->llr,
                                          out->psdu, out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride,
-                                         n_steps, waves, perm, n_virtual, lo, hi));
+                                         n_steps, waves, g.perm, g.n_virtual, lo, hi));
     }
     return WIFIRX_OK;
 }

@@ -30,6 +30,7 @@
 
 #include "wifirx.h"
 #include "wr_kernels.h"
+#include "wr_decode.h"
 
 namespace wr {
 
@@ -39,12 +40,10 @@ namespace wr {
 #define WR_DEC_CHUNK      60                   // decode_small_kernel: trellis steps per pass (lane <-> step)
 #define WR_DEC_NORM_STEPS 120                  // decode_kernel: the common minimum leaves the metrics every so many steps
 
-// Where the coded bit at position `ci` of the de-punctured stream of ONE OFDM symbol comes from, in the bit-plane
+// Where the coded bit at position `ci` of the de-punctured stream of ONE OFDM symbol comes from (coded_index), in the bit-plane
 // form of the decisions (wifirx_out.hbits: word 2 b + h of a symbol = bit b of bins 32 h .. 32 h + 31): bits 0..4 the
 // bit of the word (= bin & 31), bits 5..8 the word, or WR_SRC_PUNCT when the transmitter dropped the coded bit.
 // Read as 16-bit planes (plane p = 4 b + (bin >> 4), bit bin & 15) the same entry is p = bits 4..8, bit = bits 0..3.
-// Every symbol carries 2 * n_dbps de-punctured positions and exactly n_cbps transmitted bits, so the map repeats from
-// symbol to symbol.
 #define WR_SRC_PUNCT 0x200u
 #define WR_DEC_TAB_STRIDE 216              // steps per OFDM symbol at the highest rate
 constexpr int bin_of_carrier(int c)         // data carrier 0..47 -> FFT bin, shifted order (bin 32 = DC)
@@ -59,21 +58,8 @@ constexpr int bin_of_carrier(int c)         // data carrier 0..47 -> FFT bin, sh
 }
 constexpr uint32_t coded_src(int punct, int n_bpsc, int ci)
 {
-    const int n_cbps = 48 * n_bpsc;
-    const int s = (n_bpsc / 2) < 1 ? 1 : (n_bpsc / 2);
-    int pidx = ci;
-    if (punct == 1) {                      // 2/3: every 4th bit dropped
-        const int r = ci & 3;
-        if (r == 3) return WR_SRC_PUNCT;
-        pidx = (ci >> 2) * 3 + r;
-    } else if (punct == 2) {               // 3/4: bits 3,4 of every 6 dropped
-        const int g = ci / 6, r = ci - 6 * g;
-        if (r == 3 || r == 4) return WR_SRC_PUNCT;
-        pidx = g * 4 + (r < 3 ? r : 3);
-    }
-    const int k = pidx;                    // < n_cbps: first symbol
-    const int i = (n_cbps >> 4) * (k & 15) + (k >> 4);
-    const int j = s * (i / s) + (i + n_cbps - (16 * i) / n_cbps) % s;
+    const int j = coded_index(punct, n_bpsc, ci);
+    if (j < 0) return WR_SRC_PUNCT;
     const int carrier = j / n_bpsc, bit = j - carrier * n_bpsc;
     const int bin = bin_of_carrier(carrier);
     return (uint32_t)(bin & 31) | ((uint32_t)(2 * bit + (bin >> 5)) << 5);
@@ -81,15 +67,12 @@ constexpr uint32_t coded_src(int punct, int n_bpsc, int ci)
 struct SrcTable { uint32_t e[8 * WR_DEC_TAB_STRIDE]; };    // [enc][step of the symbol]: coded bit A in the low half, B in the high half
 constexpr SrcTable make_src_table()
 {
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
-    const int punct_tab[8] = { 0, 2, 0, 2, 0, 2, 1, 2 };
-    const int nbpsc_tab[8] = { 1, 1, 2, 2, 4, 4, 6, 6 };
     SrcTable t{};
     for (int enc = 0; enc < 8; enc++)
         for (int tt = 0; tt < WR_DEC_TAB_STRIDE; tt++) {
             uint32_t v = WR_SRC_PUNCT | (WR_SRC_PUNCT << 16);
-            if (tt < ndbps_tab[enc])
-                v = coded_src(punct_tab[enc], nbpsc_tab[enc], 2 * tt) | (coded_src(punct_tab[enc], nbpsc_tab[enc], 2 * tt + 1) << 16);
+            if (tt < RATE_NDBPS[enc])
+                v = coded_src(RATE_PUNCT[enc], RATE_NBPSC[enc], 2 * tt) | (coded_src(RATE_PUNCT[enc], RATE_NBPSC[enc], 2 * tt + 1) << 16);
             t.e[enc * WR_DEC_TAB_STRIDE + tt] = v;
         }
     return t;
@@ -193,9 +176,6 @@ void decode_pack_kernel(uint32_t n_slots, uint32_t max_sym, const wifirx_frame* 
     }
 }
 
-constexpr __host__ __device__ int rotr6(int s, int p) { return ((s >> p) | (s << (6 - p))) & 63; }
-constexpr __host__ __device__ int parity_of(int v) { return __builtin_popcount(v) & 1; }
-
 // ---- packed 16-bit arithmetic (both halves at once; the compiler may schedule these freely) ----
 // Issue cost on gfx950 at 4-8 waves per SIMD (tools/valu_rate.hip): v_pk_* and the three-operand integer forms
 // (v_bfi_b32, v_add3_u32, ...) ~2.0 ns per wave-instruction, v_add_u32 1.5 ns, v_lshrrev_b32 1.3 ns.  Hence:
@@ -246,85 +226,6 @@ __device__ __forceinline__ uint32_t crc32_bit(uint32_t c, uint32_t bit)
 {
     uint32_t x = (c ^ bit) & 1u;
     return (c >> 1) ^ (0xedb88320u & (0u - x));
-}
-
-// Tables of the per-frame finish (workgroup LDS, built once per workgroup): crc[k][b] = CRC-32 (reflected 0xedb88320)
-// of byte b followed by k zero bytes ("slicing by 4"), scr[s] = the next 32 scrambler bits from LFSR state s.
-struct FinishTables { uint32_t crc[4][256]; uint32_t scr[128]; };
-
-__device__ __forceinline__ void build_finish_tables(FinishTables& ft)
-{
-    for (int e = threadIdx.x; e < 256; e += blockDim.x) {
-        uint32_t c = (uint32_t)e;
-#pragma unroll
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1u)));
-        ft.crc[0][e] = c;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 256; e += blockDim.x) {
-        uint32_t c = ft.crc[0][e];
-        for (int k = 1; k < 4; k++) { c = (c >> 8) ^ ft.crc[0][c & 0xffu]; ft.crc[k][e] = c; }
-    }
-    for (int e = threadIdx.x; e < 128; e += blockDim.x) {
-        int state = e;
-        uint32_t w = 0;
-        for (int k = 0; k < 32; k++) {
-            const int fb = ((state >> 6) ^ (state >> 3)) & 1;
-            state = ((state << 1) & 0x7e) | fb;
-            w |= (uint32_t)fb << k;
-        }
-        ft.scr[e] = w;
-    }
-    __syncthreads();
-}
-
-// descramble (x^7+x^4+1, state from the first 7 decoded bits), bytes, CRC-32 of one frame; db = its decoded words
-// (stride DBS dwords, two spare words behind the last one).  Four PSDU bytes per iteration: the 32 decoded bits from
-// position 16 + 32 k on (a funnel shift of two decoded words), the 32 scrambler bits from the table (the state after
-// them is their last seven, reversed), CRC by four table look-ups.  Bytes leave four at a time when the row is
-// dword-aligned (wave-uniform `dword_ok`).
-template <int DBS = 128>
-__device__ __forceinline__ void finish_frame(const uint32_t* __restrict__ db, int psdu_len, uint8_t* __restrict__ psdu,
-                                             bool dword_ok, wifirx_frame* __restrict__ rec, uint32_t flags,
-                                             const FinishTables& ft)
-{
-    uint32_t cur = db[0];
-    int state = 0;
-#pragma unroll
-    for (int i = 0; i < 7; i++) state |= (int)((cur >> i) & 1) << (6 - i);
-    // positions 7..15 belong to the SERVICE field: advance the scrambler
-#pragma unroll
-    for (int i = 7; i < 16; i++) {
-        int fb = ((state >> 6) ^ (state >> 3)) & 1;
-        state = ((state << 1) & 0x7e) | fb;
-    }
-    uint32_t crc = 0xffffffffu;
-    uint32_t nxt = db[DBS];
-    const int n_words = psdu_len >> 2;
-    for (int k = 0; k < n_words; k++) {
-        const uint32_t nn = db[(size_t)(k + 2) * DBS];                     // spare words behind the last one keep this in range
-        const uint32_t sc = ft.scr[state];
-        state = (int)(__builtin_bitreverse32(sc) & 0x7fu);
-        const uint32_t d = __builtin_amdgcn_alignbit(nxt, cur, 16) ^ sc;    // positions 16 + 32 k .. + 31, descrambled
-        cur = nxt; nxt = nn;
-        if (dword_ok) *reinterpret_cast<uint32_t*>(psdu + 4 * k) = d;
-        else { psdu[4 * k] = (uint8_t)d; psdu[4 * k + 1] = (uint8_t)(d >> 8); psdu[4 * k + 2] = (uint8_t)(d >> 16); psdu[4 * k + 3] = (uint8_t)(d >> 24); }
-        const uint32_t x = crc ^ d;
-        crc = ft.crc[3][x & 0xffu] ^ ft.crc[2][(x >> 8) & 0xffu] ^ ft.crc[1][(x >> 16) & 0xffu] ^ ft.crc[0][x >> 24];
-    }
-    {   // the last one to three bytes
-        const uint32_t sc = ft.scr[state];
-        const uint32_t d = __builtin_amdgcn_alignbit(nxt, cur, 16) ^ sc;
-        for (int b = 4 * n_words; b < psdu_len; b++) {
-            const uint32_t byte = (d >> (8 * (b & 3))) & 0xffu;
-            psdu[b] = (uint8_t)byte;
-            crc = (crc >> 8) ^ ft.crc[0][(crc ^ byte) & 0xffu];
-        }
-    }
-    crc = ~crc;
-    uint32_t fl = flags | WIFIRX_F_DECODED;
-    if (psdu_len >= 4 && crc == 558161692u) fl |= WIFIRX_F_CRC_OK; else fl &= ~WIFIRX_F_CRC_OK;
-    rec->flags = fl;
 }
 
 // Six lane-private LDS reads whose rows come from the scalar unit: word[lane] of the rows at byte addresses a[0..5]
@@ -781,79 +682,10 @@ __device__ __forceinline__ void acs_step_q(uint32_t (&pm)[64], const uint32_t (&
     }
 }
 
-// The trace-back of a task overlapped with the add-compare-select of the wave's NEXT task (template OVL).  Alone, the two
-// phases of all waves of a round coincide: nine milliseconds of pure survivor writes, then every wave reads its 4.9 MB
-// of survivor bits back at once (19 GB, HBM-bound, ~3.8 ms) with the vector ALUs idle.  Overlapped, a wave keeps the finished
-// task as "pending" (its states, its half of the wave's double scratch buffer) and, after every six add-compare-select
-// steps of the next task, walks the pending one back by six steps -- the survivor reads are spread over the next task's
-// arithmetic; only the last task of a wave is walked back on its own.  Two waves per SIMD then (each wave needs two tasks:
-// half as many waves, twice the scratch per wave, 256 registers).  Only tasks whose frames all run the same number of steps
-// are deferred; others are walked back on the spot as before.
-struct TbPending {
-    bool     active;                  // wave-uniform
-    int      st[4];
-    uint32_t slot[4];                 // 0xffffffff: no frame
-    uint32_t aw[4][3];
-    int      blk, grp;                // wave-uniform: next block of 96 steps, next group of six in it
-    const uint32_t* surv;
-    uint32_t* dbits;
-};
-
-// Six trace-back steps of a pending task (decode_q_kernel, OVL).  When a block of 96 steps is through, its three decoded
-// words per frame leave; when the last block is through, the frames are finished (descrambling, bytes, CRC).
-#define WR_DQ_PICKP(ST, LO, HI)                                                                           \
-    (__builtin_amdgcn_ubfe((((ST & 32) ? (HI) : (LO)) ^ 0x77777777u), (uint32_t)((ST & 31) ^ 3), 1u))
-__device__ __forceinline__ void tb_pending_group(TbPending& pend, int lane, wifirx_frame* __restrict__ frames,
-                                                 uint8_t* __restrict__ psdu_all, uint32_t psdu_stride, const FinishTables& ft)
-{
-    const uint32_t* srow = pend.surv + ((size_t)(pend.blk * 96 + 6 * pend.grp) * 64 + lane) * 8;
-    // (one array per word position: a select between two elements of ONE array becomes an indexed access in scratch memory)
-    uint32_t l0[6], u0[6], l1[6], u1[6], l2[6], u2[6], l3[6], u3[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const uint4* sp = reinterpret_cast<const uint4*>(srow + (size_t)k * 512);
-        const uint4 a = sp[0], b = sp[1];
-        l0[k] = a.x; u0[k] = b.x; l1[k] = a.z; u1[k] = b.z; l2[k] = a.y; u2[k] = b.y; l3[k] = a.w; u3[k] = b.w;
-    }
-#pragma unroll
-    for (int h = 0; h < 4; h++) {
-        const uint32_t v = __builtin_bitreverse32((uint32_t)pend.st[h]) >> 26;      // u_(t-5) .. u_t, oldest in bit 0
-        pend.aw[h][2] = __builtin_amdgcn_alignbit(pend.aw[h][2], pend.aw[h][1], 26);  // the triple moves UP by six ...
-        pend.aw[h][1] = __builtin_amdgcn_alignbit(pend.aw[h][1], pend.aw[h][0], 26);
-        pend.aw[h][0] = (pend.aw[h][0] << 6) | v;                                      // ... the older steps' bits enter below
-    }
-#pragma unroll
-    for (int q = 5; q >= 0; q--) {
-        const uint32_t h0 = WR_DQ_PICKP(pend.st[0], l0[q], u0[q]), h1 = WR_DQ_PICKP(pend.st[1], l1[q], u1[q]);
-        const uint32_t h2 = WR_DQ_PICKP(pend.st[2], l2[q], u2[q]), h3 = WR_DQ_PICKP(pend.st[3], l3[q], u3[q]);
-        pend.st[0] = (pend.st[0] >> 1) | (int)(h0 << 5);
-        pend.st[1] = (pend.st[1] >> 1) | (int)(h1 << 5);
-        pend.st[2] = (pend.st[2] >> 1) | (int)(h2 << 5);
-        pend.st[3] = (pend.st[3] >> 1) | (int)(h3 << 5);
-    }
-    if (--pend.grp < 0) {
-#pragma unroll
-        for (int w = 0; w < 3; w++)
-#pragma unroll
-            for (int h = 0; h < 4; h++) { pend.dbits[(size_t)(pend.blk * 3 + w) * 256 + 64 * h + lane] = pend.aw[h][w]; pend.aw[h][w] = 0u; }
-        pend.grp = 15;
-        if (--pend.blk < 0) {
-            __threadfence_block();
-#pragma unroll
-            for (int h = 0; h < 4; h++) {
-                const uint32_t slot = pend.slot[h];
-                if (slot != 0xffffffffu)
-                    finish_frame<256>(pend.dbits + 64 * h + lane, frames[slot].psdu_len, psdu_all + (size_t)slot * psdu_stride,
-                                      ((reinterpret_cast<uintptr_t>(psdu_all) | psdu_stride) & 3) == 0, frames + slot, frames[slot].flags, ft);
-            }
-            pend.active = false;
-        }
-    }
-}
-
-// The trace-back of a task overlapped with ITS OWN add-compare-select (template MODE = 2, round 5).  The overlap above hides the
-// trace-back of a task under the arithmetic of the wave's NEXT task -- with two tasks per wave (a million frames = 3 907 tasks over
-// 2 048 waves) every second trace-back still ran on its own, all waves at once: 10 GB of survivor reads, 1.9 of 12.1 ms.  Here every
+// The trace-back of a task overlapped with ITS OWN add-compare-select (template MODE = 2, round 5).  Round 3 hid the trace-back
+// of a task under the arithmetic of the wave's NEXT task (a mode since removed) -- with two tasks per wave (a million frames =
+// 3 907 tasks over 2 048 waves) every second trace-back still ran on its own, all waves at once: 10 GB of survivor reads, 1.9 of
+// 12.1 ms.  Here every
 // block of 96 steps is walked back SPECULATIVELY while the next block's add-compare-select runs: when the trellis has reached
 // boundary B_(j+1) = 96 (j + 1), a walk starts there in the state with the smallest metric (any state would do for correctness),
 // goes back through block j six steps per group of six trellis steps, and leaves the block's 96 decoded bits.  Survivor paths
@@ -869,6 +701,10 @@ struct SpecWalk {
     uint32_t aw[4][3];
     int      blk, grp;                // wave-uniform: the block being walked, the next group of six in it
 };
+
+// the survivor bit of state ST in decode_q_kernel's rows (LO: the word of states 0..31, HI: that of 32..63)
+#define WR_DQ_PICKP(ST, LO, HI)                                                                           \
+    (__builtin_amdgcn_ubfe((((ST & 32) ? (HI) : (LO)) ^ 0x77777777u), (uint32_t)((ST & 31) ^ 3), 1u))
 
 // Six steps of the speculative walk.  When the block is through: its three decoded words per frame leave, and the state the walk
 // arrived in at the block's lower boundary is compared with the start state of the walk before (link_ref, a byte per frame): a
@@ -917,10 +753,10 @@ __device__ __forceinline__ void spec_walk_group(SpecWalk& sw, int lane, const ui
 }
 #undef WR_DQ_PICKP
 
-// MODE: 0 = a task's trace-back behind its add-compare-select; 1 = overlapped with the wave's next task (above); 2 = speculative
-// walks overlapped with the task's own add-compare-select (above).
+// MODE: 0 = a task's trace-back behind its add-compare-select; 2 = speculative walks overlapped with the task's own
+// add-compare-select (above).
 template <int ROWS, int MODE>        // LDS rows per wave: 32 (rates up to 16-QAM: 8 staged words x 4), 48 (64-QAM: one symbol of 12 words)
-__global__ __launch_bounds__(256, MODE == 2 ? (ROWS == 32 ? WR_DQ_SPEC_WAVES : 2) : MODE ? 2 : (ROWS == 32 ? 4 : 3))      // (48 rows: 52.5 kB of LDS per workgroup -- two fit a CU anyway)
+__global__ __launch_bounds__(256, MODE == 2 ? (ROWS == 32 ? WR_DQ_SPEC_WAVES : 2) : (ROWS == 32 ? 4 : 3))      // (48 rows: 52.5 kB of LDS per workgroup -- two fit a CU anyway)
 void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict__ frames,
                      const uint32_t* __restrict__ hbits_all, uint8_t* __restrict__ psdu_all, uint32_t psdu_stride,
                      uint8_t* __restrict__ scratch, size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves_total,
@@ -928,7 +764,7 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
 {
     // the current OFDM symbols of the wave's frames: row 4 w + 2 c + g (w = word of the staged 8-word block, c = 0: frames
     // h = 0, 1; c = 1: frames h = 2, 3; g = 16-bit plane of the word) = plane of the first frame | that of the second << 16
-    constexpr bool OVL = MODE == 1, SPEC = MODE == 2;
+    constexpr bool SPEC = MODE == 2;
     __shared__ uint32_t sym_all[4][ROWS * 64];
     __shared__ FinishTables ft;
     build_finish_tables(ft);
@@ -939,13 +775,9 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
     uint32_t* symw = sym_all[wv] + lane;
     const uint32_t sym_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)sym_all[wv]);
     const size_t n_data_cap = n_steps_cap;
-    // scratch of the wave: [step][lane][8 words] of survivor bits + [word][h][lane] of decoded bits; OVL: two such halves
-    // (SPEC: + [boundary][lane] the start states of the speculative walks, a byte per frame)
-    const size_t half_words = n_data_cap * 512 + (n_data_cap / 32 + 2) * 256;
-    uint32_t* const scr0 = reinterpret_cast<uint32_t*>(scratch + (size_t)wave * scratch_stride);
-    int buf = 0;
-    TbPending pend;
-    pend.active = false;
+    // scratch of the wave: [step][lane][8 words] of survivor bits + [word][h][lane] of decoded bits (SPEC: + [boundary][lane]
+    // the start states of the speculative walks, a byte per frame)
+    uint32_t* const surv = reinterpret_cast<uint32_t*>(scratch + (size_t)wave * scratch_stride);
     const uint32_t k1 = 0x01010101u;
     uint32_t sel0 = 0x03020100u;                      // v_perm_b32 selector "every byte from the second source", kept in a register
     asm volatile("" : "+v"(sel0));
@@ -988,7 +820,6 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
         if (ROWS < 48 && enc_u >= 6) continue;                                      // (the host launches the 48-row instance when 64-QAM frames exist)
         const int sym_blk = blk_w / nw_u;
 
-        uint32_t* surv = scr0 + (OVL ? (size_t)buf * half_words : 0);
         uint32_t* dbits = surv + n_data_cap * 512;
         uint32_t* rec = dbits + (n_data_cap / 32 + 2) * 256;         // SPEC only (the host sized the slice for it)
         uint32_t pm[64];
@@ -1122,7 +953,6 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
                 }
             }
             tt_u += 6;
-            if (OVL && pend.active) tb_pending_group(pend, lane, frames, psdu_all, psdu_stride, ft);
             if (SPEC && n_fast > 0) {
                 if (sw.active) spec_walk_group(sw, lane, surv, dbits, link_ref, fb);
                 const int done = tg + 6;
@@ -1150,7 +980,6 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
         };
         group(std::true_type{}, 0);
         for (int tg = 6; tg < n_max; tg += 6) group(std::false_type{}, tg);
-        if (OVL) { while (pend.active) tb_pending_group(pend, lane, frames, psdu_all, psdu_stride, ft); }      // a pending task with a longer trellis: the rest of it
         __threadfence_block();
         // ---- traceback of the four frames of a lane: 32 decoded bits per word, words stored [word][h][lane].  A step of
         //      a frame reads ITS two survivor words of the row (compile-time positions), picks the half by bit 5 of the
@@ -1192,23 +1021,6 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
                         }
                     }
                 }
-            }
-            if (OVL && n_fast > 0) {
-                // the blocks of 96 steps are walked back while the wave's next task runs (or right after the task loop)
-                pend.active = true;
-#pragma unroll
-                for (int h = 0; h < 4; h++) {
-                    pend.st[h] = st[h];
-                    pend.slot[h] = n_data[h] > 0 ? slot_of[h] : 0xffffffffu;
-#pragma unroll
-                    for (int w = 0; w < 3; w++) pend.aw[h][w] = 0u;
-                }
-                pend.blk = n_fast / 96 - 1;
-                pend.grp = 15;
-                pend.surv = surv;
-                pend.dbits = dbits;
-                buf ^= 1;
-                continue;
             }
             for (int blk = n_fast / 96 - 1; blk >= 0; blk--) {
                 // the 96 decoded bits of the block per frame: the groups come from the top step down, so every six steps the
@@ -1270,7 +1082,6 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
             }
         }
     }
-    if (OVL) { while (pend.active) tb_pending_group(pend, lane, frames, psdu_all, psdu_stride, ft); }      // the wave's last deferred task: on its own
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1544,16 +1355,16 @@ extern "C" hipError_t wr_launch_decode(hipStream_t st, uint32_t n_slots, uint32_
 extern "C" hipError_t wr_launch_decode_q(hipStream_t st, uint32_t n_slots, uint32_t max_sym, wifirx_frame* frames,
                                          const uint32_t* hbits, uint8_t* psdu, uint32_t psdu_stride, uint8_t* scratch,
                                          size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves, uint32_t frames_per_wave,
-                                         const uint32_t* perm, uint32_t n_virtual, int has_64qam, int overlap)
+                                         const uint32_t* perm, uint32_t n_virtual, int has_64qam, int mode)
 {
-    // overlap: 0 = trace-back behind the task, 1 = under the wave's next task (double scratch slice), 2 = speculative walks under the
-    // task's own add-compare-select (slice + (n_steps_cap / 96 + 2) x 256 bytes of start states)
+    // mode: 0 = trace-back behind the task, 2 = speculative walks under the task's own add-compare-select (slice + (n_steps_cap / 96
+    // + 2) x 256 bytes of start states)
     if (n_slots == 0 || n_waves == 0) return hipSuccess;
     if (!perm) n_virtual = n_slots;
 #define WR_LAUNCH_Q(ROWS, MODE) hipLaunchKernelGGL((wr::decode_q_kernel<ROWS, MODE>), dim3((n_waves + 3) / 4), dim3(256), 0, st, n_slots, max_sym, \
                                                    frames, hbits, psdu, psdu_stride, scratch, scratch_stride, n_steps_cap, n_waves, frames_per_wave, perm, n_virtual)
-    if (has_64qam) { if (overlap == 2) WR_LAUNCH_Q(48, 2); else if (overlap) WR_LAUNCH_Q(48, 1); else WR_LAUNCH_Q(48, 0); }
-    else           { if (overlap == 2) WR_LAUNCH_Q(32, 2); else if (overlap) WR_LAUNCH_Q(32, 1); else WR_LAUNCH_Q(32, 0); }
+    if (has_64qam) { if (mode == 2) WR_LAUNCH_Q(48, 2); else WR_LAUNCH_Q(48, 0); }
+    else           { if (mode == 2) WR_LAUNCH_Q(32, 2); else WR_LAUNCH_Q(32, 0); }
 #undef WR_LAUNCH_Q
     return hipGetLastError();
 }

@@ -22,6 +22,7 @@
 
 #include "wifirx.h"
 #include "wr_kernels.h"
+#include "wr_decode.h"
 
 namespace wr {
 namespace soft {
@@ -30,45 +31,27 @@ namespace soft {
 #define WR_SOFT_PUNCT 0xffffu          // table entry of a coded bit the transmitter dropped
 #define WR_SOFT_TAB_STRIDE 216         // steps per OFDM symbol at the highest rate
 
-// Where the de-punctured coded bit `ci` of ONE OFDM symbol sits among the symbol's 48 * n_bpsc LLRs (carrier * n_bpsc +
-// bit: the de-interleaver of the hard path, whose source is an LLR index here instead of a bit-plane position).
+// [enc][step of the symbol]: the LLR index (coded_index: carrier * n_bpsc + bit) of coded bit A | that of B << 16
+struct SoftTable { uint32_t e[8 * WR_SOFT_TAB_STRIDE]; };
 constexpr uint32_t llr_of_coded(int punct, int n_bpsc, int ci)
 {
-    const int n_cbps = 48 * n_bpsc;
-    const int s = (n_bpsc / 2) < 1 ? 1 : (n_bpsc / 2);
-    int k = ci;
-    if (punct == 1) {                      // 2/3: every 4th bit dropped
-        const int r = ci & 3;
-        if (r == 3) return WR_SOFT_PUNCT;
-        k = (ci >> 2) * 3 + r;
-    } else if (punct == 2) {               // 3/4: bits 3,4 of every 6 dropped
-        const int g = ci / 6, r = ci - 6 * g;
-        if (r == 3 || r == 4) return WR_SOFT_PUNCT;
-        k = g * 4 + (r < 3 ? r : 3);
-    }
-    const int i = (n_cbps >> 4) * (k & 15) + (k >> 4);
-    return (uint32_t)(s * (i / s) + (i + n_cbps - (16 * i) / n_cbps) % s);
+    const int j = coded_index(punct, n_bpsc, ci);
+    return j < 0 ? WR_SOFT_PUNCT : (uint32_t)j;
 }
-struct SoftTable { uint32_t e[8 * WR_SOFT_TAB_STRIDE]; };     // [enc][step of the symbol]: LLR of coded bit A | B << 16
 constexpr SoftTable make_soft_table()
 {
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
-    const int punct_tab[8] = { 0, 2, 0, 2, 0, 2, 1, 2 };
-    const int nbpsc_tab[8] = { 1, 1, 2, 2, 4, 4, 6, 6 };
     SoftTable t{};
     for (int enc = 0; enc < 8; enc++)
         for (int tt = 0; tt < WR_SOFT_TAB_STRIDE; tt++) {
             uint32_t v = WR_SOFT_PUNCT | (WR_SOFT_PUNCT << 16);
-            if (tt < ndbps_tab[enc])
-                v = llr_of_coded(punct_tab[enc], nbpsc_tab[enc], 2 * tt) | (llr_of_coded(punct_tab[enc], nbpsc_tab[enc], 2 * tt + 1) << 16);
+            if (tt < RATE_NDBPS[enc])
+                v = llr_of_coded(RATE_PUNCT[enc], RATE_NBPSC[enc], 2 * tt) | (llr_of_coded(RATE_PUNCT[enc], RATE_NBPSC[enc], 2 * tt + 1) << 16);
             t.e[enc * WR_SOFT_TAB_STRIDE + tt] = v;
         }
     return t;
 }
 __constant__ const SoftTable WR_SOFT_TABLE = make_soft_table();
 
-constexpr __host__ __device__ int rotr6(int s, int p) { return ((s >> p) | (s << (6 - p))) & 63; }
-constexpr __host__ __device__ int parity_of(int v) { return __builtin_popcount(v) & 1; }
 constexpr __host__ __device__ int nbpsc_of(int enc) { return enc < 2 ? 1 : enc < 4 ? 2 : enc < 6 ? 4 : 6; }
 constexpr __host__ __device__ int ndbps_of(int enc)      // (a select chain: a local table would live in scratch memory)
 {
@@ -116,79 +99,6 @@ __device__ __forceinline__ void acs_step(float (&pm)[64], const float (&bm)[4], 
         acs_state(c00, c01, pm[r0], acc[j >> 4]);      // = register of logical state 2j at phase P+1
         acs_state(c10, c11, pm[r1], acc[j >> 4]);      // = register of logical state 2j+1 at phase P+1
     }
-}
-
-// CRC-32 "slicing by 4" and the scrambler's next 32 bits per state (workgroup LDS; the tables of the hard path's finish)
-struct FinishTables { uint32_t crc[4][256]; uint32_t scr[128]; };
-
-__device__ __forceinline__ void build_finish_tables(FinishTables& ft)
-{
-    for (int e = threadIdx.x; e < 256; e += blockDim.x) {
-        uint32_t c = (uint32_t)e;
-#pragma unroll
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1u)));
-        ft.crc[0][e] = c;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 256; e += blockDim.x) {
-        uint32_t c = ft.crc[0][e];
-        for (int k = 1; k < 4; k++) { c = (c >> 8) ^ ft.crc[0][c & 0xffu]; ft.crc[k][e] = c; }
-    }
-    for (int e = threadIdx.x; e < 128; e += blockDim.x) {
-        int state = e;
-        uint32_t w = 0;
-        for (int k = 0; k < 32; k++) {
-            const int fb = ((state >> 6) ^ (state >> 3)) & 1;
-            state = ((state << 1) & 0x7e) | fb;
-            w |= (uint32_t)fb << k;
-        }
-        ft.scr[e] = w;
-    }
-    __syncthreads();
-}
-
-// descramble (x^7+x^4+1, state from the first 7 decoded bits), bytes, CRC-32 of one frame; db = its decoded words
-// (word k = decoded bits 32 k .. 32 k + 31, stride 64 dwords, two spare words behind the last one)
-__device__ __forceinline__ void finish_frame(const uint32_t* __restrict__ db, int psdu_len, uint8_t* __restrict__ psdu,
-                                             bool dword_ok, wifirx_frame* __restrict__ rec, uint32_t flags,
-                                             const FinishTables& ft)
-{
-    uint32_t cur = db[0];
-    int state = 0;
-#pragma unroll
-    for (int i = 0; i < 7; i++) state |= (int)((cur >> i) & 1) << (6 - i);
-#pragma unroll
-    for (int i = 7; i < 16; i++) {             // the SERVICE field
-        int fb = ((state >> 6) ^ (state >> 3)) & 1;
-        state = ((state << 1) & 0x7e) | fb;
-    }
-    uint32_t crc = 0xffffffffu;
-    uint32_t nxt = db[64];
-    const int n_words = psdu_len >> 2;
-    for (int k = 0; k < n_words; k++) {
-        const uint32_t nn = db[(size_t)(k + 2) * 64];
-        const uint32_t sc = ft.scr[state];
-        state = (int)(__builtin_bitreverse32(sc) & 0x7fu);
-        const uint32_t d = __builtin_amdgcn_alignbit(nxt, cur, 16) ^ sc;    // positions 16 + 32 k .. + 31, descrambled
-        cur = nxt; nxt = nn;
-        if (dword_ok) *reinterpret_cast<uint32_t*>(psdu + 4 * k) = d;
-        else { psdu[4 * k] = (uint8_t)d; psdu[4 * k + 1] = (uint8_t)(d >> 8); psdu[4 * k + 2] = (uint8_t)(d >> 16); psdu[4 * k + 3] = (uint8_t)(d >> 24); }
-        const uint32_t x = crc ^ d;
-        crc = ft.crc[3][x & 0xffu] ^ ft.crc[2][(x >> 8) & 0xffu] ^ ft.crc[1][(x >> 16) & 0xffu] ^ ft.crc[0][x >> 24];
-    }
-    {
-        const uint32_t sc = ft.scr[state];
-        const uint32_t d = __builtin_amdgcn_alignbit(nxt, cur, 16) ^ sc;
-        for (int b = 4 * n_words; b < psdu_len; b++) {
-            const uint32_t byte = (d >> (8 * (b & 3))) & 0xffu;
-            psdu[b] = (uint8_t)byte;
-            crc = (crc >> 8) ^ ft.crc[0][(crc ^ byte) & 0xffu];
-        }
-    }
-    crc = ~crc;
-    uint32_t fl = flags | WIFIRX_F_DECODED;
-    if (psdu_len >= 4 && crc == 558161692u) fl |= WIFIRX_F_CRC_OK; else fl &= ~WIFIRX_F_CRC_OK;
-    rec->flags = fl;
 }
 
 // Tasks [task_lo, task_hi) of 64 frames each (grid-stride over n_waves_total waves, one wave per workgroup); frame k of
@@ -335,7 +245,7 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
         __threadfence_block();
         // ---- descramble, bytes, CRC-32 ----
         if (n_data > 0)
-            finish_frame(dbits + lane, frames[slot].psdu_len, psdu_all + (size_t)slot * psdu_stride,
+            finish_frame<64>(dbits + lane, frames[slot].psdu_len, psdu_all + (size_t)slot * psdu_stride,
                          ((reinterpret_cast<uintptr_t>(psdu_all) | psdu_stride) & 3) == 0, frames + slot, frames[slot].flags, ft);
     }
 }
