@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "wifirx.h"
 #include "wr_device.h"
@@ -95,9 +96,7 @@ struct DetectQuadState {
     float Br[2], Bi[2], Bp[3];    // totals of blocks m-1, m-2 (, m-3)
 };
 
-#ifndef WR_DQ_GROUP
 #define WR_DQ_GROUP 4             // blocks per request group
-#endif
 
 __device__ __forceinline__ void detect_quad_load(const float2* __restrict__ x, int n_samp, int m0, int r, c32 (&v)[WR_DQ_GROUP])
 {
@@ -314,6 +313,50 @@ void demod_stream_kernel(const float2* __restrict__ x, long n_samp, const Stream
         __builtin_amdgcn_wave_barrier();
     }
     frames_quad<EQ, HB, XK>(seed, prm, lds[wave], lane, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Launches.  The instance for the channel estimator and the bit-plane output (hbits) of a launch: f(EQ, HB) as integral
+// constants.
+template <class F>
+static inline void demod_instance(const DemodParams* prm, const DemodOut* out, F f)
+{
+    auto eq = [&](auto eq_c) {
+        if (out->hbits) f(eq_c, std::true_type{});
+        else            f(eq_c, std::false_type{});
+    };
+    switch (prm->chan_est) {
+    case WIFIRX_EQ_LMS:  eq(std::integral_constant<int, WIFIRX_EQ_LMS>{}); break;
+    case WIFIRX_EQ_COMB: eq(std::integral_constant<int, WIFIRX_EQ_COMB>{}); break;
+    case WIFIRX_EQ_STA:  eq(std::integral_constant<int, WIFIRX_EQ_STA>{}); break;
+    default:             eq(std::integral_constant<int, WIFIRX_EQ_LS>{}); break;
+    }
+}
+
+// The kernels of one output-set class: wr_kernels.hip calls these with XK = false, wr_kernels_x.hip with XK = true, so every
+// instance is compiled in the translation unit that launches it.
+template <bool XK>
+static hipError_t launch_demod_batch(hipStream_t st, const float2* iq, uint32_t slot_len, uint32_t n_slots, const DemodParams* prm,
+                                     const DemodOut* out, const uint64_t* slot_off)
+{
+    const dim3 grid((n_slots + 4 * WR_WAVES_PER_BLOCK - 1) / (4 * WR_WAVES_PER_BLOCK)), block(64 * WR_WAVES_PER_BLOCK);
+    demod_instance(prm, out, [&](auto eq_c, auto hb_c) {
+        hipLaunchKernelGGL((demod_batch_kernel<decltype(eq_c)::value, decltype(hb_c)::value, XK>), grid, block, 0, st,
+                           iq, slot_len, n_slots, *prm, *out, slot_off);
+    });
+    return hipGetLastError();
+}
+
+template <bool XK>
+static hipError_t launch_demod_stream(hipStream_t st, const float2* x, int64_t n_samp, const StreamTrig* trig, uint32_t n_trig,
+                                      const DemodParams* prm, const float2* A, const DemodOut* out)
+{
+    const dim3 grid((n_trig + 4 * WR_WAVES_PER_BLOCK - 1) / (4 * WR_WAVES_PER_BLOCK)), block(64 * WR_WAVES_PER_BLOCK);
+    demod_instance(prm, out, [&](auto eq_c, auto hb_c) {
+        hipLaunchKernelGGL((demod_stream_kernel<decltype(eq_c)::value, decltype(hb_c)::value, XK>), grid, block, 0, st,
+                           x, (long)n_samp, trig, n_trig, *prm, A, *out);
+    });
+    return hipGetLastError();
 }
 
 }  // namespace wr

@@ -64,12 +64,7 @@ struct StreamTrig {
 // which translation unit's kernels a launch takes (wave-uniform facts the host knows): XK = any output set but decisions + LLRs
 static inline bool wr_demod_wants_x(const wr::DemodParams* prm, const wr::DemodOut* out)
 {
-#if defined(WR_X_LOOPS) && !WR_X_LOOPS
-    (void)prm; (void)out;
-    return false;
-#else
     return out->carrier != nullptr || out->sym_stats != nullptr || out->idx == nullptr || out->llr == nullptr || prm->llr_csi != 0;
-#endif
 }
 
 extern "C" {

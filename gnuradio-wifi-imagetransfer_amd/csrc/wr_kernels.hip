@@ -53,18 +53,7 @@ extern "C" hipError_t wr_launch_demod_batch(hipStream_t st, const float2* iq, ui
 {
     if (n_slots == 0) return hipSuccess;
     if (wr_demod_wants_x(prm, out)) return wr_launch_demod_batch_x(st, iq, slot_len, n_slots, prm, out, slot_off);
-    dim3 grid((n_slots + 4 * WR_WAVES_PER_BLOCK - 1) / (4 * WR_WAVES_PER_BLOCK)), block(64 * WR_WAVES_PER_BLOCK);
-#define WR_LAUNCH_BATCH(EQ, HB) hipLaunchKernelGGL((wr::demod_batch_kernel<EQ, HB, false>), grid, block, 0, st, iq, slot_len, n_slots, *prm, *out, slot_off)
-#define WR_LAUNCH_BATCH_EQ(EQ) { if (out->hbits) WR_LAUNCH_BATCH(EQ, true); else WR_LAUNCH_BATCH(EQ, false); }
-    switch (prm->chan_est) {
-    case WIFIRX_EQ_LMS:  WR_LAUNCH_BATCH_EQ(WIFIRX_EQ_LMS) break;
-    case WIFIRX_EQ_COMB: WR_LAUNCH_BATCH_EQ(WIFIRX_EQ_COMB) break;
-    case WIFIRX_EQ_STA:  WR_LAUNCH_BATCH_EQ(WIFIRX_EQ_STA) break;
-    default:             WR_LAUNCH_BATCH_EQ(WIFIRX_EQ_LS) break;
-    }
-#undef WR_LAUNCH_BATCH_EQ
-#undef WR_LAUNCH_BATCH
-    return hipGetLastError();
+    return wr::launch_demod_batch<false>(st, iq, slot_len, n_slots, prm, out, slot_off);
 }
 
 extern "C" hipError_t wr_launch_stream_detect(hipStream_t st, const float2* x, int64_t n_samp, int64_t tile0,
@@ -82,16 +71,5 @@ extern "C" hipError_t wr_launch_demod_stream(hipStream_t st, const float2* x, in
 {
     if (n_trig == 0) return hipSuccess;
     if (wr_demod_wants_x(prm, out)) return wr_launch_demod_stream_x(st, x, n_samp, trig, n_trig, prm, A, out);
-    dim3 grid((n_trig + 4 * WR_WAVES_PER_BLOCK - 1) / (4 * WR_WAVES_PER_BLOCK)), block(64 * WR_WAVES_PER_BLOCK);
-#define WR_LAUNCH_STREAM(EQ, HB) hipLaunchKernelGGL((wr::demod_stream_kernel<EQ, HB, false>), grid, block, 0, st, x, (long)n_samp, trig, n_trig, *prm, A, *out)
-#define WR_LAUNCH_STREAM_EQ(EQ) { if (out->hbits) WR_LAUNCH_STREAM(EQ, true); else WR_LAUNCH_STREAM(EQ, false); }
-    switch (prm->chan_est) {
-    case WIFIRX_EQ_LMS:  WR_LAUNCH_STREAM_EQ(WIFIRX_EQ_LMS) break;
-    case WIFIRX_EQ_COMB: WR_LAUNCH_STREAM_EQ(WIFIRX_EQ_COMB) break;
-    case WIFIRX_EQ_STA:  WR_LAUNCH_STREAM_EQ(WIFIRX_EQ_STA) break;
-    default:             WR_LAUNCH_STREAM_EQ(WIFIRX_EQ_LS) break;
-    }
-#undef WR_LAUNCH_STREAM_EQ
-#undef WR_LAUNCH_STREAM
-    return hipGetLastError();
+    return wr::launch_demod_stream<false>(st, x, n_samp, trig, n_trig, prm, A, out);
 }

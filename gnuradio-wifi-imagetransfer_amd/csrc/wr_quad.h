@@ -21,64 +21,18 @@
 
 namespace wr {
 
-#ifndef WR_SPLIT_SYMBOL_LOOP
-#define WR_SPLIT_SYMBOL_LOOP 1
-#endif
-#ifndef WR_PLAIN_STORES
-#define WR_PLAIN_STORES 1
-#endif
-#ifndef WR_CONST_DATA_MASK
-#define WR_CONST_DATA_MASK 1
-#endif
-#ifndef WR_NB_LOOPS
-#define WR_NB_LOOPS 2       // 1: BPSK and QPSK only, 2: all four constellations (loops of their own for 16- and 64-QAM bring nothing by themselves; they carry the whole-line stores)
-#endif
-#ifndef WR_POLARITY_WINDOW
-#define WR_POLARITY_WINDOW 1
-#endif
-#ifndef WR_T4_POINTER
-#define WR_T4_POINTER 1
-#endif
-#ifndef WR_STORE_AS_LINES
-#define WR_STORE_AS_LINES 3       // 1: BPSK / QPSK rows in the kernels without plane output only, 2: in both, 3: 16- / 64-QAM rows as well (needs WR_NB_LOOPS 2)
-#endif
-#ifndef WR_FLAT_STAGING
-#define WR_FLAT_STAGING 1        // store_bins_lines: the four bins of a lane staged without per-bin execution masks (BPSK .. 16-QAM)
-#endif
-#ifndef WR_GLOBAL_SAMPLE_LOADS
-#define WR_GLOBAL_SAMPLE_LOADS 1
-#endif
-#ifndef WR_DMA_PREFETCH
-#define WR_DMA_PREFETCH 1        // BPSK / QPSK loops of the usual output set: the next symbol's samples by LDS-DMA (global_load_lds_dwordx4), requested while this symbol is computed
-#endif
-#define WR_QLDS_PFX (WR_DMA_PREFETCH ? 256 : 0)       // floats behind the LLR-weight area that complete the 2-kB prefetch buffer (4 frames x 64 samples x 8 B)
-#ifndef WR_LTS_SKIP_IDLE
-#define WR_LTS_SKIP_IDLE 1       // LTS candidate rounds 3..7 run for the frame of a pair that needs them only (was: both frames of the pair)
-#endif
-#ifndef WR_X_LOOPS
-#define WR_X_LOOPS 1             // constellation loops with whole-line stores for the other output sets too (carrier, weights, moments, planes alone)
-#endif
-#ifndef WR_NT_LOADS
-#define WR_NT_LOADS 1            // the symbol loop's sample loads as non-temporal (streaming) loads
-#endif
-#ifndef WR_NT_STORES
-#define WR_NT_STORES 1           // store_bins_lines / store_rows_x: the whole-line 16-byte pieces as non-temporal stores (2: the decisions' dwords too -- slower)
-#endif
 // LDS of the symbol loop, per wave (floats).  The scratch area at the front serves the FFT transposes (512 floats), the SIGNAL
 // decoder's survivor words, STA's window exchange and the staging of a symbol's output rows (store_bins_lines: 432 floats
 // for BPSK / QPSK rows, 1200 for 64-QAM = 4 x 1152 B of LLRs + 4 x 48 decisions).  The COMB instance keeps the short scratch
 // area (its running estimate d_H takes another 2 kB; with the long one sixteen waves would no longer fit a CU's 160 kB) and
 // with it the per-bin stores for 16- / 64-QAM rows.
-#ifndef WR_QLDS_LONG
-#define WR_QLDS_LONG 1200
-#endif
-#define WR_QLDS_SCRATCH_EQ(EQ) ((EQ) == WIFIRX_EQ_COMB ? 768 : WR_QLDS_LONG)
+#define WR_QLDS_SCRATCH_EQ(EQ) ((EQ) == WIFIRX_EQ_COMB ? 768 : 1200)
 #define WR_QLDS_H(S)       (S)                        // 4 x 64 float2: channel estimate, lane-private slots
 #define WR_QLDS_TW(S)      (WR_QLDS_H(S) + 512)       // 6 x 16 float2: stage-1/2 twiddles by row lane
 #define WR_QLDS_PREV(S)    (WR_QLDS_TW(S) + 192)      // 4 rows x 4 float2: pilots of the previous symbol (LMS / COMB / STA: rows of 6 float2, the fifth = the frame's phase increment Qp)
 #define WR_QLDS_W(S)       (WR_QLDS_PREV(S) + 48)     // 4 x 64 floats: |H|^2 of the LS estimate (LLR weight, lane-private slots)
-#define WR_QLDS_PF(S)      (WR_QLDS_W(S))             // the prefetch buffer of the usual output set's loops: the weight area (idle there: weights are an XK output) + WR_QLDS_PFX
-#define WR_QLDS_STAT(S)    (WR_QLDS_W(S) + 256 + WR_QLDS_PFX)       // 4 rows x 4 floats: running sums of |y|, |y|^2, |y|^4 (sym_stats output)
+#define WR_QLDS_PF(S)      (WR_QLDS_W(S))             // the LDS-DMA prefetch buffer (4 frames x 64 samples x 8 B = 2 kB): the weight area (idle in the loops that prefetch) + 256 floats behind it
+#define WR_QLDS_STAT(S)    (WR_QLDS_PF(S) + 512)      // 4 rows x 4 floats: running sums of |y|, |y|^2, |y|^4 (sym_stats output)
 #define WR_QLDS_FLOATS(S)  (WR_QLDS_STAT(S) + 16)     // per wave; the preamble phase uses the first 1536 floats for two frames' samples
 #define WR_QLDS_DH(S)      (WR_QLDS_FLOATS(S))        // COMB only: 4 x 64 float2, the running estimate d_H
 #define WR_QLDS_FLOATS_EQ(EQ) (WR_QLDS_FLOATS(WR_QLDS_SCRATCH_EQ(EQ)) + ((EQ) == WIFIRX_EQ_COMB ? 512 : 0))
@@ -88,12 +42,9 @@ namespace wr {
 typedef float wr_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float2 load_global_f2(const float2* p)
 {
-#if WR_GLOBAL_SAMPLE_LOADS && defined(__HIP_DEVICE_COMPILE__)
-#if WR_NT_LOADS
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (a non-temporal load: the samples are read once)
     const wr_f2 v = __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) wr_f2*>(reinterpret_cast<uintptr_t>(p)));
-#else
-    const wr_f2 v = *reinterpret_cast<const __attribute__((address_space(1))) wr_f2*>(reinterpret_cast<uintptr_t>(p));
-#endif
     return make_float2(v.x, v.y);
 #else
     return *p;
@@ -464,7 +415,7 @@ __device__ __forceinline__ void lts_candidates2(const wr_i4 (&acc)[5], const boo
         int best[2] = { 0, 0 }, lmax[2] = { 0, 0 };
 #pragma unroll
         for (int e = 0; e < 2; e++) {                           // rounds 0..2: no branch in here (both frames run them); the candidate rounds
-            if (WR_LTS_SKIP_IDLE && r > 2 && !need[e]) continue; // behind them only for the frame that needs them (wave-uniform)
+            if (r > 2 && !need[e]) continue;                   // behind them only for the frame that needs them (wave-uniform)
             int m = K[e][0];
 #pragma unroll
             for (int n = 1; n < 6; n++) m = K[e][n] > m ? K[e][n] : m;
@@ -485,7 +436,7 @@ __device__ __forceinline__ void lts_candidates2(const wr_i4 (&acc)[5], const boo
         int w[2] = { 0, 0 };
 #pragma unroll
         for (int e = 0; e < 2; e++) {
-            if (WR_LTS_SKIP_IDLE && r >= 2 && !need[e]) continue;
+            if (r >= 2 && !need[e]) continue;
             const int L = L0 - 64 * e;
             const uint64_t hit = __ballot(lmax[e] == best[e]);
             if (__builtin_popcountll(hit) == 1) {               // wave-uniform; the usual case
@@ -785,14 +736,10 @@ __device__ __forceinline__ void store_bins(const c32 (&Y)[4], const int (&carrie
     const bool has_idx = PLAIN ? true : has_idx_, has_car = PLAIN ? false : has_car_, want_llr = PLAIN ? true : want_llr_;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-#if WR_CONST_DATA_MASK
         // which lanes hold a data sub-carrier in register j is a constant of the lane <-> bin map (bins r + 16 j): the
         // execution mask comes from a scalar constant, not from a comparison of the carrier number
         const uint64_t row_bits = j == 0 ? 0xF7C0ull : j == 1 ? 0xFDFFull : j == 2 ? 0xFF7Eull : 0x07DFull;      // (the loop is unrolled)
         if (!(ok && __builtin_amdgcn_inverse_ballot_w64(row_bits * 0x0001000100010001ull))) continue;
-#else
-        if (!(ok && carrier[j] >= 0)) continue;
-#endif
         const uint32_t oq = (uint32_t)(q * 48 + carrier[j]);
         const uint32_t o = row_o + oq;
         if (has_idx) idx[o] = decide(Y[j], NB);
@@ -820,15 +767,11 @@ __device__ __forceinline__ void store_bins(const c32 (&Y)[4], const int (&carrie
     }
 }
 
-// a 16-byte piece / a dword of an output row (WR_NT_STORES: as a streaming store -- the rows are written once and never read here)
+// a 16-byte piece of an output row, as a streaming store: the rows are written once and never read here
 typedef float wr_f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_piece(char* p, float4 v)
 {
-#if WR_NT_STORES
     __builtin_nontemporal_store(wr_f4v{ v.x, v.y, v.z, v.w }, reinterpret_cast<wr_f4v*>(p));
-#else
-    *reinterpret_cast<float4*>(p) = v;
-#endif
 }
 // a dword of a row's decisions: ALWAYS a plain store.  A row of decisions is 48 bytes -- never a whole 128-byte line --, and a
 // streaming store of part of a line leaves the L2 before the rest of the line has arrived: the memory probe's stores alone take
@@ -836,11 +779,7 @@ __device__ __forceinline__ void store_piece(char* p, float4 v)
 // 12.0 against 9.75 ms (bench.py roofline.box, profiles/r04_box_nt_decisions.json) -- the "slow box" of round 3's driver run.
 __device__ __forceinline__ void store_word(uint8_t* p, uint32_t v)
 {
-#if WR_NT_STORES > 1
-    __builtin_nontemporal_store(v, reinterpret_cast<uint32_t*>(p));
-#else
     *reinterpret_cast<uint32_t*>(p) = v;
-#endif
 }
 
 // The same stores as whole 16-byte pieces: a row's LLRs of one symbol are 192 NB contiguous bytes (192 / 384 / 768 / 1152)
@@ -869,7 +808,6 @@ __device__ __forceinline__ void store_bins_lines(const c32 (&Y)[4], const int (&
     char* srow = reinterpret_cast<char*>(stage) + row * ROWB;
     uint8_t* irow = reinterpret_cast<uint8_t*>(stage) + IDX0 + row * 48;
     __builtin_amdgcn_wave_barrier();
-#if WR_FLAT_STAGING
     if (NB <= 4) {
         // one straight piece of code for the four bins of a lane: EVERY lane writes, the lanes whose bin carries no data (pilots,
         // DC, guards: a constant of the lane <-> bin map) into a dump area behind the rows.  The four per-bin regions under an
@@ -885,12 +823,9 @@ __device__ __forceinline__ void store_bins_lines(const c32 (&Y)[4], const int (&
             if (NB == 1)      *reinterpret_cast<float*>(lw) = Y[j].re;
             else if (NB == 2) *reinterpret_cast<float2*>(lw) = make_float2(Y[j].re, Y[j].im);
             else              *reinterpret_cast<float4*>(lw) = make_float4(Y[j].re, WR_T16_2 - __builtin_fabsf(Y[j].re), Y[j].im, WR_T16_2 - __builtin_fabsf(Y[j].im));
-#ifndef WR_DBG_NO_IDX_STAGING      // (measurement only: profiles/r05_lds_bank_conflicts.txt)
             *iw = decide(Y[j], NB);
-#endif
         }
     } else
-#endif
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const uint64_t row_bits = j == 0 ? 0xF7C0ull : j == 1 ? 0xFDFFull : j == 2 ? 0xFF7Eull : 0x07DFull;      // (the loop is unrolled)
@@ -1289,10 +1224,7 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
     // between the hi-planes, 144 between rows (= 16 banks apart modulo 32) -- the four accesses of a phase are ONE lane address +
     // constants: four address registers instead of sixteen, and the accesses pair into ds_write2_b64 / ds_read2_b64 (eight LDS
     // instructions fewer per symbol).  4 x 144 x 8 = 4 608 bytes of the scratch area (4 800).
-    #ifndef WR_TP_PAD
-#define WR_TP_PAD 1
-#endif
-    constexpr bool TP_PAD = WR_TP_PAD && EQ != WIFIRX_EQ_COMB;
+    constexpr bool TP_PAD = EQ != WIFIRX_EQ_COMB;
     float2* ql = reinterpret_cast<float2*>(qlds) + (TP_PAD ? 144 * row : 128 * (row >> 1) + 16 * (row & 1));
     const int m4 = 4 * (r & 3), c2 = r >> 2;
     // transpose A: stage-1 output q of lane r=(m, c) is element (q, m, c); lane (q1=c2, m) reads (q1, m, j)
@@ -1310,11 +1242,9 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
     // BPSK / QPSK rows can leave as whole 16-byte pieces (store_bins_lines) when the output rows are aligned for it
     const bool lines_ok = (reinterpret_cast<uintptr_t>(idx) & 3) == 0 && (reinterpret_cast<uintptr_t>(llr) & 15) == 0 && ((per * prm.llr_bits) & 3) == 0;
 
-    int pk = 0;                                                // (s - 2) mod 127: index into the pilot polarity sequence
-    uint64_t polw = WR_POLARITY_NEG_LO;                        // ... or: the sequence from the current symbol on,
-    int poln = 64;                                             //     the bits left in the window
-    int polhi = 0;                                             //     and which half of the 127 it came from (scalar 0 / 1)
-    (void)pk;
+    uint64_t polw = WR_POLARITY_NEG_LO;                        // the pilot polarity sequence from the current symbol on,
+    int poln = 64;                                             // the bits left in the window
+    int polhi = 0;                                             // and which half of the 127 it came from (scalar 0 / 1)
     float t4 = WR_T4_64F[0];                                   // float32 (2 pi s 80) / 64 of the current symbol
     const float* t4_next = WR_T4_64F + 1;                      // data loop: where the factor after next stands
     // One symbol of the four frames.  DATA (compile time): the symbol is known to be a data symbol (s >= 3) -- the steady
@@ -1398,11 +1328,7 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
             if (PC) {
                 // the DMA of this symbol's samples was issued before the stores of the symbol before: NK pieces + one dword of
                 // decisions (+ the stores of the plane words: 1 / 1 / 2 / 3) may still be in flight behind it (the counter is in order)
-#ifdef WR_PF_WAIT_ALL
-                constexpr int NST = 0;
-#else
                 constexpr int NST = (12 * (NBC ? NBC : 1) + 15) / 16 + 1 + (HB ? ((NBC ? NBC : 1) + 1) / 2 : 0);
-#endif
                 if (XC) {
                     // the XK instances: how many stores a symbol issues is a constant of the launch (which outputs are wanted),
                     // not of the instance -- the immediate of the wait is picked by a scalar switch
@@ -1486,12 +1412,8 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
             // upstream: 2 pi s 80 (eps0 + d_er) / 64 in double; spec: the factor that depends on s alone comes from a
             // float32 table, eps0 and d_er are float32
             const float kf = t4 * (eps0 + d_er);
-#if WR_T4_POINTER
             if (DATA) { t4 = PC ? load_const_f(t4_next) : *t4_next; t4_next++; }             // the next symbol's factor (s + 1 <= 514: inside the table), requested a whole iteration early
             else { t4 = WR_T4_64F[s + 1]; t4_next = WR_T4_64F + (s + 2); }
-#else
-            t4 = WR_T4_64F[s < 518 ? s + 1 : 519];              // the next symbol's factor: requested a whole iteration early
-#endif
             // b = phasor of bin r + 16; lane 0 of the row holds exp(-j kf 16), whose conjugate is the step
             c32 b;
             sp_sincos_small(kf * (float)(r - 16), b.im, b.re);
@@ -1510,17 +1432,12 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
         c32 S, cur0, cur1, cur2, cur3;
         float er = 0.0f;
         if (DATA || s >= 2) {
-#if WR_POLARITY_WINDOW
             // the polarity sequence as a window that moves one bit per symbol (two scalar shifts; refilled every 64 / 63 symbols)
             sgn = (uint32_t)polw << 31;
             polw >>= 1;
             // (the refill -- every 64th / 63rd symbol -- as a branch the scalar unit almost never takes: written without the hint it
             //  became ten always-executed scalar selects and a detour of the flag through a vector register per symbol)
             if (__builtin_expect(--poln == 0, 0)) { polhi ^= 1; polw = polhi ? WR_POLARITY_NEG_HI : WR_POLARITY_NEG_LO; poln = 64 - polhi; }
-#else
-            const uint64_t bits = pk < 64 ? (WR_POLARITY_NEG_LO >> pk) : (WR_POLARITY_NEG_HI >> (pk - 64));
-            sgn = (uint32_t)(bits & 1ull) << 31;
-#endif
             S = cflip(csub(cadd(cadd(X11, X39), X25), X53), sgn);
             cur0 = cflip(X11, sgn);
             cur1 = cflip(X25, sgn);
@@ -1531,9 +1448,6 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
             c32 acc = cadd(cadd(cadd(sp_conj_mul(prev0, cur0), sp_conj_mul(prev1, cur1)),
                                 sp_conj_mul(prev2, cur2)), sp_conj_mul(prev3, cur3));
             er = sp_atan2(acc.im, acc.re) * er_scale;
-#if !WR_POLARITY_WINDOW
-            pk = pk == 126 ? 0 : pk + 1;                       // (s - 2) mod 127 of the next symbol
-#endif
         } else {
             S = cadd(cadd(csub(X11, X25), X39), X53);
             cur0 = X11; cur1 = cneg(X25); cur2 = X39; cur3 = X53;
@@ -1764,7 +1678,7 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
                     if (HB) { __builtin_amdgcn_sched_barrier(0);
                               store_hbits<(NBC ? NBC : 1)>(Y, act, q, hb_all + (size_t)(unsigned)out_l * (prm.max_sym * 12u), r); }
                 } else if (NBC != 0) {
-                    if (WR_STORE_AS_LINES && (NBC <= 2 || (WR_STORE_AS_LINES > 2 && !COMB)) && (!HB || WR_STORE_AS_LINES > 1) && (PC || lines_ok))     // (a prefetch loop is entered only with lines_ok)
+                    if ((NBC <= 2 || !COMB) && (PC || lines_ok))     // (a prefetch loop is entered only with lines_ok)
                         store_bins_lines<(NBC ? NBC : 1), EQ != WIFIRX_EQ_LS>(Y, carrier, act, q, idx, llr, row_o, row_l, qlds, row, r);
                     else
                     store_bins<(NBC ? NBC : 1), false, true>(Y, carrier, act, q, idx, car, llr, true, false, true, w1, row_o, row_l);
@@ -1812,7 +1726,6 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
 #if defined(WR_ABLATE) && WR_ABLATE == 3      // timing experiment: preamble + the two LTS symbols + SIGNAL, no data symbol
         more = false;
 #endif
-#if WR_SPLIT_SYMBOL_LOOP
         uint64_t has_data = 0;
         if (more) {
             // the data symbols of a row: 3 .. n_sym + 2, as far as the copied samples (off0 + 64 <= L) and the output rows
@@ -1826,76 +1739,57 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
             const int nb_first = has_data ? __builtin_amdgcn_readlane(n_bpsc, (int)__builtin_ctzll(has_data)) : 0;
             nbu_all = (has_data & ~__ballot(n_bpsc == nb_first)) == 0 ? nb_first : 0;
             // the usual output set: decisions + LLRs for every row with data symbols, no equalised points
-            plain_all = WR_PLAIN_STORES && idx_all != nullptr && car_all == nullptr && (has_data & ~__ballot(want_llr)) == 0;
+            plain_all = idx_all != nullptr && car_all == nullptr && (has_data & ~__ballot(want_llr)) == 0;
         }
-        const bool special = !XK && WR_NB_LOOPS && more && nbu_all > 0 && plain_all && !(prm.llr_csi != 0 && llr_all != nullptr) &&
+        const bool special = !XK && more && nbu_all > 0 && plain_all && !(prm.llr_csi != 0 && llr_all != nullptr) &&
                              lo_zero && stat_all == nullptr;      // wave-uniform
-#if WR_X_LOOPS
-      if constexpr (XK) {
-        // any other output set of a wave whose rows share a constellation (round 4): the equalised points of the `carrier` port,
-        // weighted LLRs, the probe's moments, planes alone -- constellation loops with store_rows_x()
-        const uint64_t llr_rows = has_data & __ballot(want_llr);
-        const bool special_x = WR_NB_LOOPS && more && nbu_all > 0 && !special && lo_zero && (llr_rows == 0 || llr_rows == has_data) &&
-                               (reinterpret_cast<uintptr_t>(idx) & 3) == 0 && (reinterpret_cast<uintptr_t>(llr) & 15) == 0 &&
-                               (reinterpret_cast<uintptr_t>(car) & 15) == 0 && ((per * prm.llr_bits) & 3) == 0 && (per & 1) == 0;
-        x_idx = idx_all != nullptr;
-        x_llr = llr_rows != 0;
-        x_car = car_all != nullptr;
-        x_csi = prm.llr_csi != 0 && llr_all != nullptr;
-        typedef std::true_type with_x;
-#if WR_DMA_PREFETCH
-        // ... with the samples by LDS-DMA when the weight area is idle (no weighted LLRs) and every row ends at the same symbol
-        bool pfx = false;
-        // (... and LLR or point rows are written: with the planes alone the wait has next to nothing to skip, 9.99 vs 10.06 ms)
-        if (special_x && !x_csi && (x_llr || x_car) && (!COMB || nbu_all <= 2)) {
-            pfx = pf_setup(has_data, s);
-            const int nk = (12 * nbu_all + 15) / 16;
-            pf_nst = (x_llr ? nk : 0) + (x_idx ? 1 : 0) + (x_car ? 2 : 0) + (HB ? (nbu_all + 1) / 2 : 0);
+        bool pf = false;        // (wave-uniform) the samples by LDS-DMA, one symbol ahead
+        bool loops = false;     // (wave-uniform) the data symbols as the loop of the constellation all rows share (nbu_all)
+        if constexpr (XK) {
+            // any other output set of a wave whose rows share a constellation (round 4): the equalised points of the `carrier` port,
+            // weighted LLRs, the probe's moments, planes alone -- constellation loops with store_rows_x()
+            const uint64_t llr_rows = has_data & __ballot(want_llr);
+            loops = more && nbu_all > 0 && !special && lo_zero && (llr_rows == 0 || llr_rows == has_data) &&
+                    (reinterpret_cast<uintptr_t>(idx) & 3) == 0 && (reinterpret_cast<uintptr_t>(llr) & 15) == 0 &&
+                    (reinterpret_cast<uintptr_t>(car) & 15) == 0 && ((per * prm.llr_bits) & 3) == 0 && (per & 1) == 0;
+            x_idx = idx_all != nullptr;
+            x_llr = llr_rows != 0;
+            x_car = car_all != nullptr;
+            x_csi = prm.llr_csi != 0 && llr_all != nullptr;
+            // ... with the prefetch when the weight area is idle (no weighted LLRs) and every row ends at the same symbol
+            // (... and LLR or point rows are written: with the planes alone the wait has next to nothing to skip, 9.99 vs 10.06 ms)
+            if (loops && !x_csi && (x_llr || x_car) && (!COMB || nbu_all <= 2)) {
+                pf = pf_setup(has_data, s);
+                const int nk = (12 * nbu_all + 15) / 16;
+                pf_nst = (x_llr ? nk : 0) + (x_idx ? 1 : 0) + (x_car ? 2 : 0) + (HB ? (nbu_all + 1) / 2 : 0);
+            }
+        } else {
+            // the prefetch when every row with data symbols ends at the same symbol, the rows leave as whole lines (the store count
+            // the wait relies on), and the rows' samples lie within 2^30 bytes above the first row's
+            loops = special;
+            if (special && (!COMB || nbu_all <= 2) && lines_ok) pf = pf_setup(has_data, s);
         }
-        typedef std::true_type with_px;
-        if (pfx && nbu_all == 1)           { for (; s < pf_end; s++) (void)symbol(std::true_type{}, std::integral_constant<int, 1>{}, with_x{}, with_px{}, s); more = false; }
-        else if (pfx && nbu_all == 2)      { for (; s < pf_end; s++) (void)symbol(std::true_type{}, std::integral_constant<int, 2>{}, with_x{}, with_px{}, s); more = false; }
-#if WR_NB_LOOPS > 1
-        else if (!COMB && pfx && nbu_all == 4) { for (; s < pf_end; s++) (void)symbol(std::true_type{}, std::integral_constant<int, 4>{}, with_x{}, with_px{}, s); more = false; }
-        else if (!COMB && pfx && nbu_all == 6) { for (; s < pf_end; s++) (void)symbol(std::true_type{}, std::integral_constant<int, 6>{}, with_x{}, with_px{}, s); more = false; }
-#endif
-        else
-#endif
-        if (special_x && nbu_all == 1)      for (; more; s++) more = symbol(std::true_type{}, std::integral_constant<int, 1>{}, with_x{}, no_p{}, s);
-        else if (special_x && nbu_all == 2) for (; more; s++) more = symbol(std::true_type{}, std::integral_constant<int, 2>{}, with_x{}, no_p{}, s);
-#if WR_NB_LOOPS > 1
-        else if (!COMB && special_x && nbu_all == 4) for (; more; s++) more = symbol(std::true_type{}, std::integral_constant<int, 4>{}, with_x{}, no_p{}, s);
-        else if (!COMB && special_x && nbu_all == 6) for (; more; s++) more = symbol(std::true_type{}, std::integral_constant<int, 6>{}, with_x{}, no_p{}, s);
-#endif
-        else                              for (; more; s++) more = symbol(std::true_type{}, nb_any{}, no_x{}, no_p{}, s);
-      } else
-#endif
-      {
-#if WR_DMA_PREFETCH
-        // The samples by LDS-DMA, one symbol ahead: when every row with data symbols ends at the same symbol, the rows leave as
-        // whole lines (the store count the wait relies on), and the rows' samples lie within 2^30 bytes above the first row's.
-        bool pf = false;
-        if (special && (!COMB || nbu_all <= 2) && lines_ok) pf = pf_setup(has_data, s);        // wave-uniform
+        // One loop per constellation, with the prefetch (to pf_end) or without; the general loop takes rows of different
+        // constellations and the output sets the loops are not for.  No 16- / 64-QAM loops in the COMB instance: its scratch area
+        // is too short for these rows' line stores, and the loops alone cost it 6 %.  The arms are written out here, in this
+        // order, rather than through a helper: the compiler lays the loops out in the order it meets them, and a helper that holds
+        // a loop is optimised on its own before it is inlined -- either way the kernels' code changes.
+        typedef std::integral_constant<bool, XK> x_c;
+        typedef std::true_type data;
         typedef std::true_type with_p;
-        if (pf && nbu_all == 1)           { for (; s < pf_end; s++) (void)symbol(std::true_type{}, std::integral_constant<int, 1>{}, no_x{}, with_p{}, s); more = false; }
-        else if (pf && nbu_all == 2)      { for (; s < pf_end; s++) (void)symbol(std::true_type{}, std::integral_constant<int, 2>{}, no_x{}, with_p{}, s); more = false; }
-#if WR_NB_LOOPS > 1
-        else if (!COMB && pf && nbu_all == 4) { for (; s < pf_end; s++) (void)symbol(std::true_type{}, std::integral_constant<int, 4>{}, no_x{}, with_p{}, s); more = false; }
-        else if (!COMB && pf && nbu_all == 6) { for (; s < pf_end; s++) (void)symbol(std::true_type{}, std::integral_constant<int, 6>{}, no_x{}, with_p{}, s); more = false; }
-#endif
-        else
-#endif
-        if (special && nbu_all == 1)      for (; more; s++) more = symbol(std::true_type{}, std::integral_constant<int, 1>{}, no_x{}, no_p{}, s);
-        else if (special && nbu_all == 2) for (; more; s++) more = symbol(std::true_type{}, std::integral_constant<int, 2>{}, no_x{}, no_p{}, s);
-#if WR_NB_LOOPS > 1     // (not in the COMB instance: its scratch area is too short for these rows' line stores, and the loops alone cost it 6 %)
-        else if (!COMB && special && nbu_all == 4) for (; more; s++) more = symbol(std::true_type{}, std::integral_constant<int, 4>{}, no_x{}, no_p{}, s);
-        else if (!COMB && special && nbu_all == 6) for (; more; s++) more = symbol(std::true_type{}, std::integral_constant<int, 6>{}, no_x{}, no_p{}, s);
-#endif
-        else                              for (; more; s++) more = symbol(std::true_type{}, nb_any{}, no_x{}, no_p{}, s);
-      }
-#else
-        for (; more; s++) more = symbol(std::false_type{}, nb_any{}, no_x{}, no_p{}, s);
-#endif
+        typedef std::integral_constant<int, 1> nb1;
+        typedef std::integral_constant<int, 2> nb2;
+        typedef std::integral_constant<int, 4> nb4;
+        typedef std::integral_constant<int, 6> nb6;
+        if (pf && nbu_all == 1)                  { for (; s < pf_end; s++) (void)symbol(data{}, nb1{}, x_c{}, with_p{}, s); more = false; }
+        else if (pf && nbu_all == 2)             { for (; s < pf_end; s++) (void)symbol(data{}, nb2{}, x_c{}, with_p{}, s); more = false; }
+        else if (!COMB && pf && nbu_all == 4)    { for (; s < pf_end; s++) (void)symbol(data{}, nb4{}, x_c{}, with_p{}, s); more = false; }
+        else if (!COMB && pf && nbu_all == 6)    { for (; s < pf_end; s++) (void)symbol(data{}, nb6{}, x_c{}, with_p{}, s); more = false; }
+        else if (loops && nbu_all == 1)          for (; more; s++) more = symbol(data{}, nb1{}, x_c{}, no_p{}, s);
+        else if (loops && nbu_all == 2)          for (; more; s++) more = symbol(data{}, nb2{}, x_c{}, no_p{}, s);
+        else if (!COMB && loops && nbu_all == 4) for (; more; s++) more = symbol(data{}, nb4{}, x_c{}, no_p{}, s);
+        else if (!COMB && loops && nbu_all == 6) for (; more; s++) more = symbol(data{}, nb6{}, x_c{}, no_p{}, s);
+        else                                     for (; more; s++) more = symbol(data{}, nb_any{}, no_x{}, no_p{}, s);
     }
     if (r == 0 && out >= 0) {
         wifirx_frame fr;

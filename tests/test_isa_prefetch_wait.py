@@ -1,4 +1,4 @@
-"""the counted `s_waitcnt vmcnt(NST)` at the top of a prefetch loop (csrc/wr_quad.h, WR_DMA_PREFETCH) is right only
+"""the counted `s_waitcnt vmcnt(NST)` at the top of a prefetch loop (csrc/wr_quad.h, frames_quad: PC) is right only
 while at least NST vector-memory instructions are issued between the LDS-DMA pair and that wait -- gfx950 retires loads, stores and
 LDS-DMA in order on ONE counter, so "at most NST outstanding" means "the DMA has landed" only if NST younger operations exist.  With
 fewer (a store merged or dropped by the compiler, an edit of store_bins_lines / store_hbits) the wave would read the previous

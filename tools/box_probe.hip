@@ -26,7 +26,7 @@
 #define BOXPROBE_SRC_SHA "unknown"
 #endif
 
-// the symbol loop's loads and stores as the kernel issues them (csrc/wr_quad.h: WR_NT_LOADS, WR_NT_STORES)
+// the symbol loop's loads and stores as the kernel issues them (csrc/wr_quad.h: load_global_f2, store_piece -- both non-temporal)
 #ifndef BOXPROBE_NT_LOADS
 #define BOXPROBE_NT_LOADS 1
 #endif
