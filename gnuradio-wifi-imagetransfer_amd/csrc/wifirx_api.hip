@@ -79,6 +79,7 @@ struct wifirx_handle {
     int32_t  llr_csi = 0;           // WIFIRX_P_LLR_CSI
     int32_t  stream_want_idx = 1;   // WIFIRX_P_STREAM_IDX
     int32_t  stream_soft = 0;       // WIFIRX_P_STREAM_SOFT: stream batches decoded from LLRs (wifirx_decode_batch_soft)
+    int32_t  llr_format = WIFIRX_LLR_F32;   // WIFIRX_P_LLR_FORMAT: the LLR rows of the batch calls (stream mode keeps float32)
     int64_t  sprocessed = 0;        // absolute index up to which pushes have been processed
     uint8_t* s_above = nullptr;     float2* s_A = nullptr;    int64_t s_above_cap = 0;
     std::vector<PendingTrig> pending;
@@ -289,6 +290,11 @@ int wifirx_set_param(wifirx_handle* h, int id, double value)
         if (value != 0 && value != 1) return fail(h, WIFIRX_EINVAL, "WIFIRX_P_STREAM_SOFT must be 0 or 1");
         h->stream_soft = (int32_t)value;
         return WIFIRX_OK;
+    case WIFIRX_P_LLR_FORMAT:
+        if (value != WIFIRX_LLR_F32 && value != WIFIRX_LLR_BF16)
+            return fail(h, WIFIRX_EINVAL, "WIFIRX_P_LLR_FORMAT must be WIFIRX_LLR_F32 (0) or WIFIRX_LLR_BF16 (1)");
+        h->llr_format = (int32_t)value;
+        return WIFIRX_OK;
     case WIFIRX_P_DECODE_SMALL_MAX:
         if (!(value >= 0) || value > 4e9) return fail(h, WIFIRX_EINVAL, "decode threshold out of range");
         h->decode_small_max = (uint32_t)value;
@@ -360,6 +366,17 @@ int wifirx_memcpy_d2h(wifirx_handle* h, void* dst, const void* src, size_t bytes
 }
 
 // ---- batch mode -----------------------------------------------------------------------------
+
+// bytes of one LLR value in the handle's batch format (WIFIRX_P_LLR_FORMAT)
+static size_t llr_value_bytes(const wifirx_handle* h) { return h->llr_format == WIFIRX_LLR_BF16 ? 2 : sizeof(float); }
+
+// the demod launch of the handle's LLR format: the float32 and the bf16 rows are written by kernel instances of their own
+static hipError_t launch_demod_batch_fmt(const wifirx_handle* h, const float2* iq, uint32_t slot_len, uint32_t n_slots,
+                                         const wr::DemodParams* prm, const wr::DemodOut* out, const uint64_t* slot_off)
+{
+    if (h->llr_format == WIFIRX_LLR_BF16) return wr_launch_demod_batch_bf16(h->stream, iq, slot_len, n_slots, prm, out, slot_off);
+    return wr_launch_demod_batch(h->stream, iq, slot_len, n_slots, prm, out, slot_off);
+}
 
 static int check_batch(wifirx_handle* h, uint32_t slot_len, uint32_t n_slots, const wifirx_out* out)
 {
@@ -438,9 +455,9 @@ static int demod_batch_impl(wifirx_handle* h, const float* iq, int iq_on_device,
             HIP_TRY(h, hipMemsetAsync(d_idx, 0, idx_n, h->stream));
         }
         if (out->llr) {
-            if ((rc = ensure(h, &h->stage_llr, &h->stage_llr_bytes, idx_n * h->cfg.llr_bits * sizeof(float)))) return rc;
+            if ((rc = ensure(h, &h->stage_llr, &h->stage_llr_bytes, idx_n * h->cfg.llr_bits * llr_value_bytes(h)))) return rc;
             d_llr = reinterpret_cast<float*>(h->stage_llr);
-            HIP_TRY(h, hipMemsetAsync(d_llr, 0, idx_n * h->cfg.llr_bits * sizeof(float), h->stream));
+            HIP_TRY(h, hipMemsetAsync(d_llr, 0, idx_n * h->cfg.llr_bits * llr_value_bytes(h), h->stream));
         }
         if (out->carrier) {
             if ((rc = ensure(h, &h->stage_car, &h->stage_car_bytes, idx_n * sizeof(float2)))) return rc;
@@ -463,12 +480,12 @@ static int demod_batch_impl(wifirx_handle* h, const float* iq, int iq_on_device,
         }
     }
     const wr::DemodOut dout = { d_fr, d_idx, d_llr, d_car, d_csi, d_stats, d_hb };
-    HIP_TRY(h, wr_launch_demod_batch(h->stream, d_iq, slot_len, n_slots, &prm, &dout, d_off));
+    HIP_TRY(h, launch_demod_batch_fmt(h, d_iq, slot_len, n_slots, &prm, &dout, d_off));
     h->stats.samples_in += n_iq;
     if (!out->on_device) {
         HIP_TRY(h, hipMemcpyAsync(out->frames, d_fr, n_slots * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
         if (out->idx) HIP_TRY(h, hipMemcpyAsync(out->idx, d_idx, idx_n, hipMemcpyDeviceToHost, h->stream));
-        if (out->llr) HIP_TRY(h, hipMemcpyAsync(out->llr, d_llr, idx_n * h->cfg.llr_bits * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (out->llr) HIP_TRY(h, hipMemcpyAsync(out->llr, d_llr, idx_n * h->cfg.llr_bits * llr_value_bytes(h), hipMemcpyDeviceToHost, h->stream));
         if (out->carrier) HIP_TRY(h, hipMemcpyAsync(out->carrier, d_car, idx_n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
         if (out->csi) HIP_TRY(h, hipMemcpyAsync(out->csi, d_csi, (size_t)n_slots * 52 * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
         if (out->sym_stats) HIP_TRY(h, hipMemcpyAsync(out->sym_stats, d_stats, (size_t)n_slots * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
@@ -504,7 +521,7 @@ int wifirx_time_demod(wifirx_handle* h, const float* iq_dev, uint32_t slot_len, 
         HIP_TRY(h, hipEventRecord(ev.e0, h->stream));
         const wr::DemodOut dout = { out->frames, out->idx, out->llr, reinterpret_cast<float2*>(out->carrier),
                                     reinterpret_cast<float2*>(out->csi), reinterpret_cast<float4*>(out->sym_stats), out->hbits };
-        HIP_TRY(h, wr_launch_demod_batch(h->stream, reinterpret_cast<const float2*>(iq_dev), slot_len, n_slots, &prm, &dout, nullptr));
+        HIP_TRY(h, launch_demod_batch_fmt(h, reinterpret_cast<const float2*>(iq_dev), slot_len, n_slots, &prm, &dout, nullptr));
         HIP_TRY(h, hipEventRecord(ev.e1, h->stream));
         HIP_TRY(h, hipEventSynchronize(ev.e1));
         float ms = 0;

@@ -172,17 +172,18 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
 // ---------------------------------------------------------------------------------------------
 // Soft-decision decode_mac (NUMERICS.md rule 14, wr_decode_soft.hip): the same frames, scratch and result fields as
 // wifirx_decode_batch, the LLR rows (`llr_bits` per carrier reserved per row) instead of the hard decisions.
-static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t llr_bits);
+// bf16: the rows are WIFIRX_LLR_BF16 values (the handle's batch format; stream mode passes false).
+static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t llr_bits, bool bf16);
 
 extern "C" int wifirx_decode_batch_soft(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out)
 {
     if (!h || !out) return WIFIRX_EINVAL;
     stream_worker_wait_idle(h);
     if (h->cfg.llr_bits == 0) return fail(h, WIFIRX_EINVAL, "wifirx_decode_batch_soft needs a handle created with llr_bits > 0");
-    return decode_batch_soft_impl(h, n_slots, out, h->cfg.llr_bits);
+    return decode_batch_soft_impl(h, n_slots, out, h->cfg.llr_bits, h->llr_format == WIFIRX_LLR_BF16);
 }
 
-static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t llr_bits)
+static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t llr_bits, bool bf16)
 {
     if (!out->on_device) return fail(h, WIFIRX_EINVAL, "wifirx_decode_batch_soft works on device buffers (out->on_device = 1)");
     if (!out->frames || !out->llr || !out->psdu || out->psdu_stride == 0)
@@ -211,6 +212,12 @@ static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifi
         // task range of the class: its runs in the permutation, or every task when the batch holds one rate
         const uint32_t lo = g.perm ? g.starts[e0] / fpw : 0u, hi = g.perm ? g.starts[e1 + 1] / fpw : (uint32_t)n_tasks;
         const uint32_t waves = (uint32_t)std::min<size_t>(n_waves, hi - lo);
+        if (bf16)
+            HIP_TRY(h, wr_launch_decode_soft_bf16(h->stream, nb_of_class[c], n_slots, h->cfg.max_sym, llr_bits, out->frames,
+                                                  reinterpret_cast<const uint16_t*>(out->llr), out->psdu, out->psdu_stride,
+                                                  reinterpret_cast<uint8_t*>(h->dec_scratch), stride, n_steps, waves, g.perm,
+                                                  g.n_virtual, lo, hi));
+        else
         HIP_TRY(h, wr_launch_decode_soft(h->stream, nb_of_class[c], n_slots, h->cfg.max_sym, llr_bits, out->frames, out->llr,
                                          out->psdu, out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride,
                                          n_steps, waves, g.perm, g.n_virtual, lo, hi));

@@ -249,7 +249,7 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
         o.on_device = 1;
         o.llr = soft ? reinterpret_cast<float*>(h->s_llr) : nullptr;
         stage("enqueue frame kernel");
-        if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6) : decode_batch_impl(h, np, &o))) return rc;
+        if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
         stage("frame kernel + decode_mac");
         // the frame records first: they say how much of every output row is worth bringing back (rows are max_sym
         // symbols and 2048 bytes wide on the device, a frame usually fills a fraction of that)

@@ -14,11 +14,16 @@
 // instantiated per bits-per-carrier class (NB = 1, 2, 4, 6 rows of 48), so that the LDS of a workgroup (one wave) is what
 // its rate needs: 12 / 24 / 48 / 72 kB + 4.5 kB of finish tables.
 //
+// bf16 rows (WIFIRX_LLR_BF16, NUMERICS.md rule 15; BF = true): the same kernel with the rows staged as the 16-bit values
+// themselves -- 6 / 12 / 24 / 36 kB --, still loaded as 16-byte vectors contiguous per lane; a trellis step widens the two
+// values it reads (exactly: a shift by 16) and goes on with rule 14 unchanged.
+//
 // The host groups the decodable frames by rate (decode_perm_kernel of wr_decode.hip: runs that start on 64-frame task
 // boundaries) and launches each class over its range of tasks.  Survivor bits: 8 bytes per step and lane in the handle's
 // decode scratch; trace-back, descramble and CRC follow per lane.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "wifirx.h"
 #include "wr_kernels.h"
@@ -103,8 +108,8 @@ __device__ __forceinline__ void acs_step(float (&pm)[64], const float (&bm)[4], 
 
 // Tasks [task_lo, task_hi) of 64 frames each (grid-stride over n_waves_total waves, one wave per workgroup); frame k of
 // task T is perm[64 T + k] (0xffffffff: none), or slot 64 T + k without a permutation.  Every task holds frames of one
-// rate whose bits per carrier are NB.
-template <int NB>
+// rate whose bits per carrier are NB.  BF: llr_all holds bf16 values (uint16_t) instead of floats.
+template <int NB, bool BF = false>
 __global__ __launch_bounds__(64)
 void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, wifirx_frame* __restrict__ frames,
                         const float* __restrict__ llr_all, uint8_t* __restrict__ psdu_all, uint32_t psdu_stride,
@@ -112,15 +117,16 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
                         const uint32_t* __restrict__ perm, uint32_t n_virtual, uint32_t task_lo, uint32_t task_hi)
 {
     constexpr int N_CBPS = 48 * NB;
-    __shared__ float rows[N_CBPS * 64];          // LLR j of the current symbol of lane l's frame at rows[64 j + l]
+    typedef std::conditional_t<BF, uint16_t, float> row_t;
+    __shared__ row_t rows[N_CBPS * 64];          // LLR j of the current symbol of lane l's frame at rows[64 j + l]
     __shared__ FinishTables ft;
     build_finish_tables(ft);
     const int lane = threadIdx.x;
     const uint32_t wave = blockIdx.x;
-    float* roww = rows + lane;
+    row_t* roww = rows + lane;
     uint32_t* surv = reinterpret_cast<uint32_t*>(scratch + (size_t)wave * scratch_stride);      // [step][lane][2]
     uint32_t* dbits = surv + (size_t)n_steps_cap * 128;                                         // [word][lane]
-    const size_t row_stride = (size_t)max_sym * 48 * llr_bits;      // floats per frame
+    const size_t row_stride = (size_t)max_sym * 48 * llr_bits;      // values per frame
 
     for (uint32_t task = task_lo + wave; task < task_hi; task += n_waves_total) {
         const uint32_t v = task * 64u + (uint32_t)lane;
@@ -148,7 +154,8 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
         }
         n_max = __builtin_amdgcn_readfirstlane(n_max);
         const int nd_u = ndbps_of(enc_u);
-        const float4* src = reinterpret_cast<const float4*>(llr_all + (size_t)slot * row_stride);
+        const float4* src = BF ? reinterpret_cast<const float4*>(reinterpret_cast<const uint16_t*>(llr_all) + (size_t)slot * row_stride)
+                               : reinterpret_cast<const float4*>(llr_all + (size_t)slot * row_stride);
 
         // ---- add-compare-select ----
         float pm[64];
@@ -168,6 +175,26 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
             }
             since_norm += 6;
             if (tt_u == nd_u) { tt_u = 0; sym_u++; }
+            if (BF && tt_u == 0 && tg < n_data) {
+                // the same for bf16 rows: eight values per 16-byte load, 6 / 12 / 24 / 36 loads per symbol
+                constexpr int NV = N_CBPS / 8, CH = NV < 12 ? NV : 12;
+                const float4* sp = src + (size_t)sym_u * NV;
+#pragma unroll
+                for (int c = 0; c < NV; c += CH) {
+                    uint4 x[CH];
+#pragma unroll
+                    for (int k = 0; k < CH; k++) x[k] = __builtin_bit_cast(uint4, sp[c + k]);
+#pragma unroll
+                    for (int k = 0; k < CH; k++) {
+                        const uint32_t w[4] = { x[k].x, x[k].y, x[k].z, x[k].w };
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            roww[(8 * (c + k) + 2 * i) * 64] = (uint16_t)w[i];
+                            roww[(8 * (c + k) + 2 * i + 1) * 64] = (uint16_t)(w[i] >> 16);
+                        }
+                    }
+                }
+            } else
             if (tt_u == 0 && tg < n_data) {
                 // a new OFDM symbol: its 48 NB LLRs, global (float4, contiguous per lane) -> the lane's column of the rows
                 const float4* sp = src + (size_t)sym_u * (N_CBPS / 4);
@@ -178,20 +205,22 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
                     for (int k = 0; k < 12; k++) x[k] = sp[c + k];
 #pragma unroll
                     for (int k = 0; k < 12; k++) {
-                        roww[(4 * (c + k) + 0) * 64] = x[k].x;
-                        roww[(4 * (c + k) + 1) * 64] = x[k].y;
-                        roww[(4 * (c + k) + 2) * 64] = x[k].z;
-                        roww[(4 * (c + k) + 3) * 64] = x[k].w;
+                        roww[(4 * (c + k) + 0) * 64] = (row_t)x[k].x;
+                        roww[(4 * (c + k) + 1) * 64] = (row_t)x[k].y;
+                        roww[(4 * (c + k) + 2) * 64] = (row_t)x[k].z;
+                        roww[(4 * (c + k) + 3) * 64] = (row_t)x[k].w;
                     }
                 }
             }
             const uint32_t* te = WR_SOFT_TABLE.e + (enc_u * WR_SOFT_TAB_STRIDE + tt_u);      // wave-uniform: scalar loads
+// an LLR as the trellis reads it: float32 rows as they are, bf16 rows widened (exactly: the 16 bits above 16 zero bits)
+#define WR_SOFT_ROW(v) (BF ? __uint_as_float((uint32_t)(v) << 16) : (v))
 #define WR_SOFT_STEP(P)                                                                                   \
             {                                                                                             \
                 const uint32_t e = te[P];                                                                 \
                 const uint32_t ea = e & 0xffffu, eb = e >> 16;                                            \
-                float la = roww[(ea == WR_SOFT_PUNCT ? 0u : ea) * 64];                                    \
-                float lb = roww[(eb == WR_SOFT_PUNCT ? 0u : eb) * 64];                                    \
+                float la = WR_SOFT_ROW(roww[(ea == WR_SOFT_PUNCT ? 0u : ea) * 64]);                       \
+                float lb = WR_SOFT_ROW(roww[(eb == WR_SOFT_PUNCT ? 0u : eb) * 64]);                       \
                 if (ea == WR_SOFT_PUNCT || !__builtin_isfinite(la)) la = 0.0f;                            \
                 if (eb == WR_SOFT_PUNCT || !__builtin_isfinite(lb)) lb = 0.0f;                            \
                 const float a0 = fmaxf(la, 0.0f), a1 = fmaxf(-la, 0.0f);                                  \
@@ -203,6 +232,7 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
             }
             WR_SOFT_STEP(0) WR_SOFT_STEP(1) WR_SOFT_STEP(2) WR_SOFT_STEP(3) WR_SOFT_STEP(4) WR_SOFT_STEP(5)
 #undef WR_SOFT_STEP
+#undef WR_SOFT_ROW
             {
                 const bool end = tg + 6 == n_data;
                 if (__any(end)) {
@@ -262,6 +292,28 @@ extern "C" hipError_t wr_launch_decode_soft(hipStream_t st, int nb, uint32_t n_s
     if (!perm) n_virtual = n_slots;
 #define WR_LAUNCH_SOFT(NB) hipLaunchKernelGGL(wr::soft::decode_soft_kernel<NB>, dim3(n_waves), dim3(64), 0, st, n_slots, max_sym, \
                                               llr_bits, frames, llr, psdu, psdu_stride, scratch, scratch_stride, n_steps_cap, n_waves, \
+                                              perm, n_virtual, task_lo, task_hi)
+    switch (nb) {
+    case 1: WR_LAUNCH_SOFT(1); break;
+    case 2: WR_LAUNCH_SOFT(2); break;
+    case 4: WR_LAUNCH_SOFT(4); break;
+    case 6: WR_LAUNCH_SOFT(6); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef WR_LAUNCH_SOFT
+    return hipGetLastError();
+}
+
+extern "C" hipError_t wr_launch_decode_soft_bf16(hipStream_t st, int nb, uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits,
+                                                 wifirx_frame* frames, const uint16_t* llr, uint8_t* psdu, uint32_t psdu_stride,
+                                                 uint8_t* scratch, size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves,
+                                                 const uint32_t* perm, uint32_t n_virtual, uint32_t task_lo, uint32_t task_hi)
+{
+    if (n_slots == 0 || n_waves == 0 || task_hi <= task_lo) return hipSuccess;
+    if (!perm) n_virtual = n_slots;
+    const float* llr_f = reinterpret_cast<const float*>(llr);      // (the kernel's parameter; BF reads it as uint16_t)
+#define WR_LAUNCH_SOFT(NB) hipLaunchKernelGGL((wr::soft::decode_soft_kernel<NB, true>), dim3(n_waves), dim3(64), 0, st, n_slots, max_sym, \
+                                              llr_bits, frames, llr_f, psdu, psdu_stride, scratch, scratch_stride, n_steps_cap, n_waves, \
                                               perm, n_virtual, task_lo, task_hi)
     switch (nb) {
     case 1: WR_LAUNCH_SOFT(1); break;

@@ -185,8 +185,8 @@ __device__ __forceinline__ void detect_quad(const float2* __restrict__ x, int n_
 // ---------------------------------------------------------------------------------------------
 // batch kernel: one wave = 4 consecutive slots, WR_WAVES_PER_BLOCK waves per workgroup.
 // Preamble phase per slot with the whole wave (lane = sample / lag), then the four frames walk their
-// symbols together (wr_quad.h).
-template <int EQ, bool HB, bool XK>
+// symbols together (wr_quad.h).  BF: bf16 LLR rows (wr_kernels_b.hip; frames_quad).
+template <int EQ, bool HB, bool XK, bool BF = false>
 __global__ __launch_bounds__(64 * WR_WAVES_PER_BLOCK, EQ == WIFIRX_EQ_STA ? WR_DEMOD_WAVES_PER_SIMD_STA : WR_DEMOD_WAVES_PER_SIMD)
 void demod_batch_kernel(const float2* __restrict__ iq, uint32_t slot_len, uint32_t n_slots,
                         DemodParams prm, DemodOut out, const uint64_t* __restrict__ slot_off)
@@ -267,7 +267,7 @@ void demod_batch_kernel(const float2* __restrict__ iq, uint32_t slot_len, uint32
     if ((lane & 15) == 0 && seed.out >= 0) { wifirx_frame* frames = out.frames; frames[seed.out].flags = seed.flags; frames[seed.out].frame_start = seed.fs; frames[seed.out].cfo_fine = seed.cfo_f; frames[seed.out].trigger = (int)seed.t; }
     return;
 #endif
-    frames_quad<EQ, HB, XK>(seed, prm, lds[wave], lane, out);
+    frames_quad<EQ, HB, XK, BF>(seed, prm, lds[wave], lane, out);
 }
 
 // one wave per four selected triggers of the stream
@@ -334,14 +334,14 @@ static inline void demod_instance(const DemodParams* prm, const DemodOut* out, F
 }
 
 // The kernels of one output-set class: wr_kernels.hip calls these with XK = false, wr_kernels_x.hip with XK = true, so every
-// instance is compiled in the translation unit that launches it.
-template <bool XK>
+// instance is compiled in the translation unit that launches it.  BF (batch only): the bf16 LLR instances, wr_kernels_b.hip.
+template <bool XK, bool BF = false>
 static hipError_t launch_demod_batch(hipStream_t st, const float2* iq, uint32_t slot_len, uint32_t n_slots, const DemodParams* prm,
                                      const DemodOut* out, const uint64_t* slot_off)
 {
     const dim3 grid((n_slots + 4 * WR_WAVES_PER_BLOCK - 1) / (4 * WR_WAVES_PER_BLOCK)), block(64 * WR_WAVES_PER_BLOCK);
     demod_instance(prm, out, [&](auto eq_c, auto hb_c) {
-        hipLaunchKernelGGL((demod_batch_kernel<decltype(eq_c)::value, decltype(hb_c)::value, XK>), grid, block, 0, st,
+        hipLaunchKernelGGL((demod_batch_kernel<decltype(eq_c)::value, decltype(hb_c)::value, XK, BF>), grid, block, 0, st,
                            iq, slot_len, n_slots, *prm, *out, slot_off);
     });
     return hipGetLastError();

@@ -74,6 +74,11 @@ hipError_t wr_launch_demod_stream_x(hipStream_t st, const float2* x, int64_t n_s
                                     uint32_t n_trig, const wr::DemodParams* prm, const float2* A, const wr::DemodOut* out);
 hipError_t wr_launch_demod_batch(hipStream_t st, const float2* iq, uint32_t slot_len, uint32_t n_slots,
                                  const wr::DemodParams* prm, const wr::DemodOut* out, const uint64_t* slot_off);
+// the same launches with bf16 LLR rows (dout.llr = the first uint16_t; WIFIRX_LLR_BF16): wr_kernels_b.hip / wr_kernels_bx.hip
+hipError_t wr_launch_demod_batch_bf16(hipStream_t st, const float2* iq, uint32_t slot_len, uint32_t n_slots,
+                                      const wr::DemodParams* prm, const wr::DemodOut* out, const uint64_t* slot_off);
+hipError_t wr_launch_demod_batch_bf16_x(hipStream_t st, const float2* iq, uint32_t slot_len, uint32_t n_slots,
+                                        const wr::DemodParams* prm, const wr::DemodOut* out, const uint64_t* slot_off);
 hipError_t wr_launch_synth(hipStream_t st, const float2* templates, uint32_t n_templates, uint32_t frame_len,
                            float2* slots, uint32_t slot_len, uint32_t n_slots, uint32_t lead, float gain,
                            float noise, float cfo_max, uint64_t seed, float* cfo_out);
@@ -95,6 +100,11 @@ hipError_t wr_launch_decode_soft(hipStream_t st, int nb, uint32_t n_slots, uint3
                                  wifirx_frame* frames, const float* llr, uint8_t* psdu, uint32_t psdu_stride,
                                  uint8_t* scratch, size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves,
                                  const uint32_t* perm, uint32_t n_virtual, uint32_t task_lo, uint32_t task_hi);
+// the same over bf16 LLR rows (llr = their first uint16_t)
+hipError_t wr_launch_decode_soft_bf16(hipStream_t st, int nb, uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits,
+                                      wifirx_frame* frames, const uint16_t* llr, uint8_t* psdu, uint32_t psdu_stride,
+                                      uint8_t* scratch, size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves,
+                                      const uint32_t* perm, uint32_t n_virtual, uint32_t task_lo, uint32_t task_hi);
 hipError_t wr_launch_decode_small(hipStream_t st, uint32_t n_slots, uint32_t max_sym, wifirx_frame* frames,
                                   const uint32_t* hbits, uint8_t* psdu, uint32_t psdu_stride, uint8_t* scratch,
                                   size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves);

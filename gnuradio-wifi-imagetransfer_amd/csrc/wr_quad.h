@@ -719,6 +719,12 @@ __device__ __forceinline__ float row_xor_sum16(float v)
     return v;
 }
 
+// bf16 LLRs (NUMERICS.md rule 15): the round-to-nearest-even conversion of the float32 value, NaN to a NaN, +-inf and
+// subnormals kept -- what v_cvt_pk_bf16_f32 does (hipcc emits it for the cast), two values per instruction.
+typedef __bf16 wr_bf2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint16_t bf16_of(float a) { return __builtin_bit_cast(uint16_t, (__bf16)a); }
+__device__ __forceinline__ uint32_t bf16_pk(float lo, float hi) { return __builtin_bit_cast(uint32_t, wr_bf2{ (__bf16)lo, (__bf16)hi }); }
+
 // a6 + a7 stores of one lane's four bins for constellation NB (compile-time: no per-lane branching on it).
 // ok = row active; the pointers are the row's output slices.
 // CSI: every LLR is multiplied by w[j] = |H|^2 of its sub-carrier (spec rule 12).
@@ -727,7 +733,9 @@ __device__ __forceinline__ float row_xor_sum16(float v)
 // PLAIN: the caller has established (wave-uniform) that decisions and LLRs are wanted by every row with a symbol and the
 // equalised points by none -- the usual output set; the flags are then compile-time and the four bins leave without a
 // scalar branch per output and bin.
-template <int NB, bool CSI, bool PLAIN = false>
+// BF: the LLR rows hold bf16 values (WIFIRX_LLR_BF16, NUMERICS.md rule 15): `llr` is then their first uint16_t, and every
+// value leaves as a 2-byte store of its own (the rows of this path need only be 2-byte aligned).
+template <int NB, bool CSI, bool PLAIN = false, bool BF = false>
 __device__ __forceinline__ void store_bins(const c32 (&Y)[4], const int (&carrier)[4], bool ok, int q,
                                            uint8_t* __restrict__ idx, float2* __restrict__ car,
                                            float* __restrict__ llr, bool has_idx_, bool has_car_, bool want_llr_,
@@ -745,7 +753,25 @@ __device__ __forceinline__ void store_bins(const c32 (&Y)[4], const int (&carrie
         if (has_idx) idx[o] = decide(Y[j], NB);
         // byte distances in 32 bits: base pointer from scalar registers + one offset register per store
         if (has_car) *reinterpret_cast<float2*>(reinterpret_cast<char*>(car) + (uint32_t)(o * 8u)) = make_float2(Y[j].re, Y[j].im);
-        if (want_llr) {
+        if constexpr (BF) {
+            if (want_llr) {
+                const float are = __builtin_fabsf(Y[j].re), aim = __builtin_fabsf(Y[j].im);
+                uint16_t* hp = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(llr) + (uint32_t)((row_l + oq * NB) * 2u));
+                const float wj = CSI ? w[j] : 1.0f;
+#define WR_WT(v) bf16_of(CSI ? (v) * wj : (v))
+                if (NB == 1) {
+                    hp[0] = WR_WT(Y[j].re);
+                } else if (NB == 2) {
+                    hp[0] = WR_WT(Y[j].re); hp[1] = WR_WT(Y[j].im);
+                } else if (NB == 4) {
+                    hp[0] = WR_WT(Y[j].re); hp[1] = WR_WT(WR_T16_2 - are); hp[2] = WR_WT(Y[j].im); hp[3] = WR_WT(WR_T16_2 - aim);
+                } else {
+                    hp[0] = WR_WT(Y[j].re); hp[1] = WR_WT(WR_T64_4 - are); hp[2] = WR_WT(WR_T64_2 - __builtin_fabsf(are - WR_T64_4));
+                    hp[3] = WR_WT(Y[j].im); hp[4] = WR_WT(WR_T64_4 - aim); hp[5] = WR_WT(WR_T64_2 - __builtin_fabsf(aim - WR_T64_4));
+                }
+#undef WR_WT
+            }
+        } else if (want_llr) {
             const float are = __builtin_fabsf(Y[j].re), aim = __builtin_fabsf(Y[j].im);
             float* lp = reinterpret_cast<float*>(reinterpret_cast<char*>(llr) + (uint32_t)((row_l + oq * NB) * 4u));
             const float wj = CSI ? w[j] : 1.0f;
@@ -797,14 +823,17 @@ __device__ __forceinline__ void store_word(uint8_t* p, uint32_t v)
 // those instances the pair was spilled, and its reload inside the loop is a vector memory operation the counted wait of the
 // prefetch cannot skip (tests/test_isa_prefetch_wait.py; LMS -6 %).  The LS instances have the registers and lose 0.8 % (plane
 // output) to the extra additions: they keep the pointer sum (profiles/r05_ab_spills_in_prefetch_loops.txt).
-template <int NB, bool OFF32 = false>
+// BF (bf16 rows, rule 15): every value is converted once, where the lane drops it into the staging rows -- half as long (96 NB
+// bytes: 6 / 12 / 24 / 36 pieces per row), so the pieces are as well; the stores and the decisions are as above.
+template <int NB, bool OFF32 = false, bool BF = false>
 __device__ __forceinline__ void store_bins_lines(const c32 (&Y)[4], const int (&carrier)[4], bool ok, int q,
                                                  uint8_t* __restrict__ idx, float* __restrict__ llr,
                                                  uint32_t row_o, uint32_t row_l, float* stage, int row, int r)
 {
     static_assert(NB == 1 || NB == 2 || NB == 4 || NB == 6, "constellation");
     // 16- / 64-QAM rows (768 / 1152 bytes of LLRs per symbol: 48 / 72 pieces) need the long scratch area (WR_QLDS_SCRATCH_EQ)
-    constexpr int ROWB = 192 * NB, IDX0 = NB <= 2 ? 1536 : 4 * ROWB;
+    constexpr int VB = BF ? 2 : 4;                  // bytes per LLR value
+    constexpr int ROWB = 48 * VB * NB, IDX0 = NB <= 2 ? (BF ? 768 : 1536) : 4 * ROWB;
     char* srow = reinterpret_cast<char*>(stage) + row * ROWB;
     uint8_t* irow = reinterpret_cast<uint8_t*>(stage) + IDX0 + row * 48;
     __builtin_amdgcn_wave_barrier();
@@ -813,13 +842,19 @@ __device__ __forceinline__ void store_bins_lines(const c32 (&Y)[4], const int (&
         // DC, guards: a constant of the lane <-> bin map) into a dump area behind the rows.  The four per-bin regions under an
         // execution mask of their own cost three scalar instructions and a branch each, and kept every compare -> select pair
         // of the decisions back to back (two idle issue slots per pair).  (64-QAM: the scratch area has no room for a dump.)
-        constexpr int ESZ = 4 * NB, DUMP_L = IDX0 + 192, DUMP_I = DUMP_L + 64 * ESZ;
+        constexpr int ESZ = VB * NB, DUMP_L = IDX0 + 192, DUMP_I = DUMP_L + 64 * ESZ;
         const int lane = 16 * row + r;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const bool data = carrier[j] >= 0;
             char* lw = data ? srow + ESZ * carrier[j] : reinterpret_cast<char*>(stage) + DUMP_L + ESZ * lane;
             uint8_t* iw = data ? irow + carrier[j] : reinterpret_cast<uint8_t*>(stage) + DUMP_I + lane;
+            if constexpr (BF) {
+                if (NB == 1)      *reinterpret_cast<uint16_t*>(lw) = bf16_of(Y[j].re);
+                else if (NB == 2) *reinterpret_cast<uint32_t*>(lw) = bf16_pk(Y[j].re, Y[j].im);
+                else              *reinterpret_cast<uint2*>(lw) = make_uint2(bf16_pk(Y[j].re, WR_T16_2 - __builtin_fabsf(Y[j].re)),
+                                                                             bf16_pk(Y[j].im, WR_T16_2 - __builtin_fabsf(Y[j].im)));
+            } else
             if (NB == 1)      *reinterpret_cast<float*>(lw) = Y[j].re;
             else if (NB == 2) *reinterpret_cast<float2*>(lw) = make_float2(Y[j].re, Y[j].im);
             else              *reinterpret_cast<float4*>(lw) = make_float4(Y[j].re, WR_T16_2 - __builtin_fabsf(Y[j].re), Y[j].im, WR_T16_2 - __builtin_fabsf(Y[j].im));
@@ -831,6 +866,19 @@ __device__ __forceinline__ void store_bins_lines(const c32 (&Y)[4], const int (&
         const uint64_t row_bits = j == 0 ? 0xF7C0ull : j == 1 ? 0xFDFFull : j == 2 ? 0xFF7Eull : 0x07DFull;      // (the loop is unrolled)
         if (!__builtin_amdgcn_inverse_ballot_w64(row_bits * 0x0001000100010001ull)) continue;
         const float are = __builtin_fabsf(Y[j].re), aim = __builtin_fabsf(Y[j].im);
+        if constexpr (BF) {
+            // 64-QAM: the six values of a bin are 12 bytes (4-byte aligned): three packed pairs
+            const uint32_t ci = (uint32_t)(carrier[j] + 48 * row);
+            uint32_t l12;
+            if (OFF32) asm volatile("v_mul_u32_u24 %0, 12, %1" : "=v"(l12) : "v"(ci));     // (as the float32 OFF32 arm below)
+            else       l12 = 12u * ci;
+            uint32_t* l3 = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(stage) + l12);
+            l3[0] = bf16_pk(Y[j].re, WR_T64_4 - are);
+            l3[1] = bf16_pk(WR_T64_2 - __builtin_fabsf(are - WR_T64_4), Y[j].im);
+            l3[2] = bf16_pk(WR_T64_4 - aim, WR_T64_2 - __builtin_fabsf(aim - WR_T64_4));
+            reinterpret_cast<uint8_t*>(stage)[IDX0 + ci] = decide(Y[j], NB);
+            continue;
+        } else
         if (NB == 1)      *reinterpret_cast<float*>(srow + 4 * carrier[j]) = Y[j].re;
         else if (NB == 2) *reinterpret_cast<float2*>(srow + 8 * carrier[j]) = make_float2(Y[j].re, Y[j].im);
         else if (NB == 4) *reinterpret_cast<float4*>(srow + 16 * carrier[j]) = make_float4(Y[j].re, WR_T16_2 - are, Y[j].im, WR_T16_2 - aim);
@@ -858,7 +906,9 @@ __device__ __forceinline__ void store_bins_lines(const c32 (&Y)[4], const int (&
     }
     __builtin_amdgcn_wave_barrier();
     // piece r + 16 k of the row, k = 0 .. (12 NB - 1) / 16 (the last k for the lanes that still have one)
-    constexpr int NK = (12 * NB + 15) / 16, TAIL = 12 * NB - 16 * (NK - 1);       // BPSK 1 / 12, QPSK 2 / 8, 16-QAM 3 / 16, 64-QAM 5 / 8
+    constexpr int PPR = 3 * VB * NB;                // pieces per row
+    constexpr int NK = (PPR + 15) / 16, TAIL = PPR - 16 * (NK - 1);       // BPSK 1 / 12, QPSK 2 / 8, 16-QAM 3 / 16, 64-QAM 5 / 8
+                                                                         // (bf16: 1 / 6, 1 / 12, 2 / 8, 3 / 4)
     // (separate variables, not an array: an array indexed in a loop under a lane condition stays in scratch memory)
 #define WR_PIECE(k) (*reinterpret_cast<const float4*>(srow + 256 * (k) + 16 * (((k) == NK - 1 && TAIL == 8) ? (r & 7) : r)))     // (BPSK: lanes 12..15 read into the next row's area, and store nothing)
     const float4 p0 = WR_PIECE(0);
@@ -872,8 +922,8 @@ __device__ __forceinline__ void store_bins_lines(const c32 (&Y)[4], const int (&
     __builtin_amdgcn_wave_barrier();
     if (ok) {
         char* const lb = reinterpret_cast<char*>(llr);
-        const uint32_t lo = (row_l + (uint32_t)(q * 48 * NB)) * 4u + 16u * r;
-        char* const lp = reinterpret_cast<char*>(llr) + (uint32_t)((row_l + (uint32_t)(q * 48 * NB)) * 4u + 16u * r);
+        const uint32_t lo = (row_l + (uint32_t)(q * 48 * NB)) * (uint32_t)VB + 16u * r;
+        char* const lp = reinterpret_cast<char*>(llr) + (uint32_t)((row_l + (uint32_t)(q * 48 * NB)) * (uint32_t)VB + 16u * r);
 #define WR_PIECE_AT(K) (OFF32 ? lb + (uint32_t)(lo + 256u * (K)) : lp + 256 * (K))
         if (NK > 1 || r < TAIL)            store_piece(lp, p0);
         if (NK > 2 || (NK == 2 && r < TAIL)) store_piece(WR_PIECE_AT(1), p1);
@@ -891,15 +941,19 @@ __device__ __forceinline__ void store_bins_lines(const c32 (&Y)[4], const int (&
 // branches); the constellation is compile time.  Same values, same addresses as store_bins().  For QPSK rows without weights the
 // LLR row IS the carrier row (re, im per carrier): the pieces are stored twice, not staged twice.
 // Requires (caller, wave-uniform): idx 4-byte, llr and car 16-byte aligned rows; has_llr = every active row wants LLRs.
-template <int NB, bool OFF32 = false>      // OFF32: as store_bins_lines
+// BF: bf16 LLR rows as in store_bins_lines (the weight is applied in float32, then the product converted); a QPSK row of bf16
+// LLRs is no longer the carrier row, so the points are staged on their own.
+template <int NB, bool OFF32 = false, bool BF = false>      // OFF32: as store_bins_lines
 __device__ __forceinline__ void store_rows_x(const c32 (&Y)[4], const int (&carrier)[4], bool ok, int q,
                                              uint8_t* __restrict__ idx, float* __restrict__ llr, float2* __restrict__ car,
                                              bool has_idx, bool has_llr, bool has_car, bool csi, const float* Wl,
                                              uint32_t row_o, uint32_t row_l, float* stage, int row, int r)
 {
     static_assert(NB == 1 || NB == 2 || NB == 4 || NB == 6, "constellation");
-    constexpr int ROWB = 192 * NB, IDX0 = NB <= 2 ? 1536 : 4 * ROWB;
-    constexpr int NK = (12 * NB + 15) / 16, TAIL = 12 * NB - 16 * (NK - 1);
+    constexpr int VB = BF ? 2 : 4;                  // bytes per LLR value
+    constexpr int ROWB = 48 * VB * NB, IDX0 = NB <= 2 ? (BF ? 768 : 1536) : 4 * ROWB;
+    constexpr int PPR = 3 * VB * NB;                // pieces per row
+    constexpr int NK = (PPR + 15) / 16, TAIL = PPR - 16 * (NK - 1);
     char* srow = reinterpret_cast<char*>(stage) + row * ROWB;
     uint8_t* irow = reinterpret_cast<uint8_t*>(stage) + IDX0 + row * 48;
     float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = p0;
@@ -917,6 +971,18 @@ __device__ __forceinline__ void store_rows_x(const c32 (&Y)[4], const int (&carr
             const float are = __builtin_fabsf(Y[j].re), aim = __builtin_fabsf(Y[j].im);
             // (x * 1.0f is x for every float: the unweighted values are those of store_bins_lines)
 #define WR_WT(v) (csi ? (v) * w[j] : (v))
+            if constexpr (BF) {
+                if (NB == 1)      *reinterpret_cast<uint16_t*>(srow + 2 * carrier[j]) = bf16_of(WR_WT(Y[j].re));
+                else if (NB == 2) *reinterpret_cast<uint32_t*>(srow + 4 * carrier[j]) = bf16_pk(WR_WT(Y[j].re), WR_WT(Y[j].im));
+                else if (NB == 4) *reinterpret_cast<uint2*>(srow + 8 * carrier[j]) = make_uint2(bf16_pk(WR_WT(Y[j].re), WR_WT(WR_T16_2 - are)),
+                                                                                                 bf16_pk(WR_WT(Y[j].im), WR_WT(WR_T16_2 - aim)));
+                else {
+                    uint32_t* l3 = reinterpret_cast<uint32_t*>(srow + 12 * carrier[j]);
+                    l3[0] = bf16_pk(WR_WT(Y[j].re), WR_WT(WR_T64_4 - are));
+                    l3[1] = bf16_pk(WR_WT(WR_T64_2 - __builtin_fabsf(are - WR_T64_4)), WR_WT(Y[j].im));
+                    l3[2] = bf16_pk(WR_WT(WR_T64_4 - aim), WR_WT(WR_T64_2 - __builtin_fabsf(aim - WR_T64_4)));
+                }
+            } else
             if (NB == 1)      *reinterpret_cast<float*>(srow + 4 * carrier[j]) = WR_WT(Y[j].re);
             else if (NB == 2) *reinterpret_cast<float2*>(srow + 8 * carrier[j]) = make_float2(WR_WT(Y[j].re), WR_WT(Y[j].im));
             else if (NB == 4) *reinterpret_cast<float4*>(srow + 16 * carrier[j]) = make_float4(WR_WT(Y[j].re), WR_WT(WR_T16_2 - are), WR_WT(Y[j].im), WR_WT(WR_T16_2 - aim));
@@ -944,8 +1010,8 @@ __device__ __forceinline__ void store_rows_x(const c32 (&Y)[4], const int (&carr
         if (ok) {
             if (has_llr) {
                 char* const lb = reinterpret_cast<char*>(llr);
-                const uint32_t lo = (row_l + (uint32_t)(q * 48 * NB)) * 4u + 16u * r;
-                char* const lp = reinterpret_cast<char*>(llr) + (uint32_t)((row_l + (uint32_t)(q * 48 * NB)) * 4u + 16u * r);
+                const uint32_t lo = (row_l + (uint32_t)(q * 48 * NB)) * (uint32_t)VB + 16u * r;
+                char* const lp = reinterpret_cast<char*>(llr) + (uint32_t)((row_l + (uint32_t)(q * 48 * NB)) * (uint32_t)VB + 16u * r);
 #define WR_PIECE_AT(K) (OFF32 ? lb + (uint32_t)(lo + 256u * (K)) : lp + 256 * (K))
                 if (NK > 1 || r < TAIL)            store_piece(lp, p0);
                 if (NK > 2 || (NK == 2 && r < TAIL)) store_piece(WR_PIECE_AT(1), p1);
@@ -958,7 +1024,8 @@ __device__ __forceinline__ void store_rows_x(const c32 (&Y)[4], const int (&carr
         }
     }
     if (has_car) {
-        if (!(NB == 2 && has_llr && !csi)) {       // (wave-uniform) the points staged on their own: 4 rows x 384 bytes
+        constexpr bool QPSK_F32 = NB == 2 && !BF;     // (a row of float32 QPSK LLRs is the carrier row)
+        if (!(QPSK_F32 && has_llr && !csi)) {       // (wave-uniform) the points staged on their own: 4 rows x 384 bytes
             char* crow = reinterpret_cast<char*>(stage) + row * 384;
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -1096,7 +1163,9 @@ __device__ __forceinline__ c32 point_of(unsigned idx, int n_bpsc)
 // keep their register allocation.
 // XK: the kernel instance for every output set but decisions + LLRs (wr_kernels_x.hip): its constellation loops end in
 // store_rows_x(); the instance with XK = false keeps the loops of the usual set and nothing else (wr_demod.h).
-template <int EQ, bool HB, bool XK>
+// BF: the LLR rows are bf16 (WIFIRX_LLR_BF16, NUMERICS.md rule 15): dout.llr is then the first uint16_t of the rows; the
+// instances of the float32 format keep their code.
+template <int EQ, bool HB, bool XK, bool BF = false>
 __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodParams& prm, float* qlds, int lane,
                                             const DemodOut& dout)
 {
@@ -1238,6 +1307,8 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
     const uint32_t row_l = row_o * prm.llr_bits;
     uint8_t* idx = idx_all ? idx_all + (size_t)out_base * per : nullptr;
     float*   llr = llr_all ? llr_all + (size_t)out_base * per * prm.llr_bits : nullptr;
+    if constexpr (BF)          // (the same element offset in bf16 values)
+        llr = llr_all ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(llr_all) + (size_t)out_base * per * prm.llr_bits) : nullptr;
     float2*  car = car_all ? car_all + (size_t)out_base * per : nullptr;
     // BPSK / QPSK rows can leave as whole 16-byte pieces (store_bins_lines) when the output rows are aligned for it
     const bool lines_ok = (reinterpret_cast<uintptr_t>(idx) & 3) == 0 && (reinterpret_cast<uintptr_t>(llr) & 15) == 0 && ((per * prm.llr_bits) & 3) == 0;
@@ -1328,7 +1399,7 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
             if (PC) {
                 // the DMA of this symbol's samples was issued before the stores of the symbol before: NK pieces + one dword of
                 // decisions (+ the stores of the plane words: 1 / 1 / 2 / 3) may still be in flight behind it (the counter is in order)
-                constexpr int NST = (12 * (NBC ? NBC : 1) + 15) / 16 + 1 + (HB ? ((NBC ? NBC : 1) + 1) / 2 : 0);
+                constexpr int NST = ((BF ? 6 : 12) * (NBC ? NBC : 1) + 15) / 16 + 1 + (HB ? ((NBC ? NBC : 1) + 1) / 2 : 0);
                 if (XC) {
                     // the XK instances: how many stores a symbol issues is a constant of the launch (which outputs are wanted),
                     // not of the instance -- the immediate of the wait is picked by a scalar switch
@@ -1668,20 +1739,20 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
 #define WR_STORE(NB, OK)                                                                                        \
                 { if (no_bins) { }                                                                                      \
                   else if (csi) { const float wq[4] = { Wl[0], Wl[64], Wl[128], Wl[192] };                                   \
-                             store_bins<NB, true>(Y, carrier, OK, q, idx, car, llr, has_idx, has_car, want_llr, wq, row_o, row_l); }  \
-                  else if (DATA && plain_all) store_bins<NB, false, true>(Y, carrier, OK, q, idx, car, llr, true, false, true, w1, row_o, row_l); \
-                  else     store_bins<NB, false>(Y, carrier, OK, q, idx, car, llr, has_idx, has_car, want_llr, w1, row_o, row_l); \
+                             store_bins<NB, true, false, BF>(Y, carrier, OK, q, idx, car, llr, has_idx, has_car, want_llr, wq, row_o, row_l); }  \
+                  else if (DATA && plain_all) store_bins<NB, false, true, BF>(Y, carrier, OK, q, idx, car, llr, true, false, true, w1, row_o, row_l); \
+                  else     store_bins<NB, false, false, BF>(Y, carrier, OK, q, idx, car, llr, has_idx, has_car, want_llr, w1, row_o, row_l); \
                   if (HB) { __builtin_amdgcn_sched_barrier(0);                                                          \
                             store_hbits<NB>(Y, OK, q, hb_all + (size_t)(unsigned)out_l * (prm.max_sym * 12u), r); } }
                 if (NBC != 0 && XC) {
-                    store_rows_x<(NBC ? NBC : 1), EQ != WIFIRX_EQ_LS>(Y, carrier, act, q, idx, llr, car, x_idx, x_llr, x_car, x_csi, Wl, row_o, row_l, qlds, row, r);
+                    store_rows_x<(NBC ? NBC : 1), EQ != WIFIRX_EQ_LS, BF>(Y, carrier, act, q, idx, llr, car, x_idx, x_llr, x_car, x_csi, Wl, row_o, row_l, qlds, row, r);
                     if (HB) { __builtin_amdgcn_sched_barrier(0);
                               store_hbits<(NBC ? NBC : 1)>(Y, act, q, hb_all + (size_t)(unsigned)out_l * (prm.max_sym * 12u), r); }
                 } else if (NBC != 0) {
                     if ((NBC <= 2 || !COMB) && (PC || lines_ok))     // (a prefetch loop is entered only with lines_ok)
-                        store_bins_lines<(NBC ? NBC : 1), EQ != WIFIRX_EQ_LS>(Y, carrier, act, q, idx, llr, row_o, row_l, qlds, row, r);
+                        store_bins_lines<(NBC ? NBC : 1), EQ != WIFIRX_EQ_LS, BF>(Y, carrier, act, q, idx, llr, row_o, row_l, qlds, row, r);
                     else
-                    store_bins<(NBC ? NBC : 1), false, true>(Y, carrier, act, q, idx, car, llr, true, false, true, w1, row_o, row_l);
+                    store_bins<(NBC ? NBC : 1), false, true, BF>(Y, carrier, act, q, idx, car, llr, true, false, true, w1, row_o, row_l);
                     if (HB) { __builtin_amdgcn_sched_barrier(0);
                               store_hbits<(NBC ? NBC : 1)>(Y, act, q, hb_all + (size_t)(unsigned)out_l * (prm.max_sym * 12u), r); }
                 } else if (uniform) {
@@ -1760,7 +1831,7 @@ __device__ __forceinline__ void frames_quad(const QuadSeed& seed, const DemodPar
             // (... and LLR or point rows are written: with the planes alone the wait has next to nothing to skip, 9.99 vs 10.06 ms)
             if (loops && !x_csi && (x_llr || x_car) && (!COMB || nbu_all <= 2)) {
                 pf = pf_setup(has_data, s);
-                const int nk = (12 * nbu_all + 15) / 16;
+                const int nk = ((BF ? 6 : 12) * nbu_all + 15) / 16;
                 pf_nst = (x_llr ? nk : 0) + (x_idx ? 1 : 0) + (x_car ? 2 : 0) + (HB ? (nbu_all + 1) / 2 : 0);
             }
         } else {

@@ -21,6 +21,9 @@ OK, EINVAL, ENODEV, ENOMEM, EHIP, ERANGE, EDEAD = 0, -1, -2, -3, -4, -5, -6     
 STREAM_BATCH_MAX = 1 << 27          # WIFIRX_STREAM_BATCH_MAX
 P_BANDWIDTH, P_FREQUENCY, P_SENSITIVITY, P_CHAN_EST, P_STREAM_BATCH, P_DECODE_SMALL_MAX, P_LLR_CSI, P_STREAM_IDX = 1, 2, 3, 4, 5, 6, 7, 8
 P_STREAM_SOFT = 9                   # stream mode: decode_mac on LLRs (wifirx_decode_batch_soft, NUMERICS.md rule 14)
+P_LLR_FORMAT = 10                   # LLR format of the batch calls (NUMERICS.md rule 15); stream mode keeps float32
+LLR_F32, LLR_BF16 = 0, 1            # WIFIRX_LLR_*
+_LLR_FORMATS = {"f32": LLR_F32, "bf16": LLR_BF16}
 F_DETECTED, F_SYNC, F_SIGNAL, F_COMPLETE, F_LLR, F_DECODED, F_CRC_OK = 1, 2, 4, 8, 16, 32, 64
 
 FRAME_DTYPE = np.dtype([
@@ -38,6 +41,13 @@ EXPORTS = [
     "wifirx_memcpy_h2d", "wifirx_memcpy_d2h", "wifirx_time_demod", "wifirx_poll_ex", "wifirx_demod_batch_v",
     "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft",
 ]
+
+
+def bf16_to_f32(bits) -> np.ndarray:
+    """bf16 bit patterns (np.uint16, as the batch calls return them with llr_format="bf16") -> the float32 values they
+    stand for: exact, the 16 bits become the upper half of the float32 word"""
+    b = np.asarray(bits, dtype=np.uint16)
+    return (b.astype(np.uint32) << 16).view(np.float32)
 
 
 class WifiRxError(RuntimeError):
@@ -147,7 +157,11 @@ class WifiRx:
     """One receive chain = one handle = one HIP stream."""
 
     def __init__(self, bandwidth=20e6, frequency=5.89e9, sensitivity=0.56, min_plateau=2, chan_est=EQ_LS,
-                 max_sym=64, llr_bits=0, want_carrier=False, device=0, max_batch=0, max_slot_len=0):
+                 max_sym=64, llr_bits=0, want_carrier=False, device=0, max_batch=0, max_slot_len=0, llr_format="f32"):
+        """llr_format: "f32" (default) or "bf16" -- the LLR rows of the batch calls (WIFIRX_P_LLR_FORMAT); in bf16 mode the
+        LLRs come back as np.uint16 bit patterns (bf16_to_f32 widens them)."""
+        if llr_format not in _LLR_FORMATS:
+            raise ValueError("llr_format must be 'f32' or 'bf16'")
         self.cfg = Config(ABI_VERSION, device, bandwidth, frequency, sensitivity, min_plateau, chan_est,
                           max_sym, llr_bits, int(bool(want_carrier)), max_batch, max_slot_len)
         h = C.c_void_p()
@@ -155,6 +169,9 @@ class WifiRx:
         if rc != 0:
             raise WifiRxError(rc, _lib.wifirx_last_error(None).decode())
         self._h = h
+        self.llr_format = LLR_F32
+        if _LLR_FORMATS[llr_format] != LLR_F32:
+            self.set_llr_format(llr_format)
 
     # -- plumbing --
     def _check(self, rc):
@@ -182,6 +199,15 @@ class WifiRx:
 
     def set_param(self, pid, value):
         self._check(_lib.wifirx_set_param(self._h, pid, float(value)))
+        if pid == P_LLR_FORMAT:
+            self.llr_format = int(value)
+
+    def set_llr_format(self, fmt):
+        """"f32" / "bf16" (or LLR_F32 / LLR_BF16): the format of the LLR rows of later batch calls"""
+        self.set_param(P_LLR_FORMAT, _LLR_FORMATS[fmt] if isinstance(fmt, str) else fmt)
+
+    def _llr_dtype(self):
+        return np.uint16 if self.llr_format == LLR_BF16 else np.float32
 
     def stats(self) -> dict:
         st = Stats()
@@ -207,7 +233,7 @@ class WifiRx:
         ms = self.cfg.max_sym
         frames = np.zeros(n_slots, dtype=FRAME_DTYPE)
         idx = np.zeros((n_slots, ms, 48), dtype=np.uint8)
-        llr = np.zeros((n_slots, ms * 48 * self.cfg.llr_bits), dtype=np.float32) if self.cfg.llr_bits else None
+        llr = np.zeros((n_slots, ms * 48 * self.cfg.llr_bits), dtype=self._llr_dtype()) if self.cfg.llr_bits else None
         car = np.zeros((n_slots, ms, 48), dtype=np.complex64) if self.cfg.want_carrier else None
         psdu = np.zeros((n_slots, psdu_stride), dtype=np.uint8) if decode else None
         if not decode:
@@ -245,7 +271,7 @@ class WifiRx:
         ms = self.cfg.max_sym
         frames = np.zeros(n_slots, dtype=FRAME_DTYPE)
         idx = np.zeros((n_slots, ms, 48), dtype=np.uint8)
-        llr = np.zeros((n_slots, ms * 48 * self.cfg.llr_bits), dtype=np.float32) if self.cfg.llr_bits else None
+        llr = np.zeros((n_slots, ms * 48 * self.cfg.llr_bits), dtype=self._llr_dtype()) if self.cfg.llr_bits else None
         car = np.zeros((n_slots, ms, 48), dtype=np.complex64) if self.cfg.want_carrier else None
         out = Out(_np_ptr(frames), _np_ptr(idx), _np_ptr(llr), _np_ptr(car), None, 0, 0, None, None)
         self._check(_lib.wifirx_demod_batch_v(self._h, _np_ptr(iq), 0, _np_ptr(off), n_slots, C.byref(out)))
@@ -260,7 +286,7 @@ class WifiRx:
         d["frames"] = self.alloc(n_slots * 32)
         d["idx"] = self.alloc(n_slots * ms * 48) if want_idx else None
         d["hbits"] = self.alloc(n_slots * ms * 48) if want_hbits else None
-        d["llr"] = self.alloc(n_slots * ms * 48 * self.cfg.llr_bits * 4) if self.cfg.llr_bits else None
+        d["llr"] = self.alloc(n_slots * ms * 48 * self.cfg.llr_bits * np.dtype(self._llr_dtype()).itemsize) if self.cfg.llr_bits else None
         d["carrier"] = self.alloc(n_slots * ms * 48 * 8) if self.cfg.want_carrier else None
         d["psdu"] = self.alloc(n_slots * psdu_stride) if psdu_stride else None
         for k in ("frames", "idx", "llr", "carrier", "psdu", "csi", "sym_stats", "hbits"):      # the kernels only write what a frame fills
@@ -310,7 +336,7 @@ class WifiRx:
         if dev.get("csi") is not None:
             r["csi"] = dev["csi"].download(np.complex64, n_slots * 52).reshape(n_slots, 52)
         if dev.get("llr") is not None:
-            r["llr"] = dev["llr"].download(np.float32, n_slots * ms * 48 * self.cfg.llr_bits).reshape(n_slots, -1)
+            r["llr"] = dev["llr"].download(self._llr_dtype(), n_slots * ms * 48 * self.cfg.llr_bits).reshape(n_slots, -1)
         if dev.get("carrier") is not None:
             r["carrier"] = dev["carrier"].download(np.complex64, n_slots * ms * 48).reshape(n_slots, ms, 48)
         if dev.get("psdu") is not None:

@@ -147,6 +147,16 @@ typedef struct wifirx_config {
  * per trigger, allocated once the mode is on), whatever cfg.llr_bits is; WIFIRX_P_LLR_CSI weights them as in batch mode.
  * Default 0 (the upstream hard-decision decoder); other values are WIFIRX_EINVAL.  Batches run after the call use it. */
 #define WIFIRX_P_STREAM_SOFT 9
+/* LLR format of the batch calls made after it is set (NUMERICS.md rule 15): WIFIRX_LLR_F32 (default) = float32 values;
+ * WIFIRX_LLR_BF16 = bfloat16 values, each the IEEE round-to-nearest-even conversion of the float32 LLR the default format
+ * would write (weight of WIFIRX_P_LLR_CSI included; NaN stays a NaN, +-inf and subnormals are kept).  In bf16 mode
+ * wifirx_out.llr points to uint16_t bit patterns with the same element layout, so its strides and sizes are half the float32
+ * ones in bytes.  It applies to wifirx_demod_batch / wifirx_demod_batch_v (device and host outputs), wifirx_time_demod and
+ * wifirx_decode_batch_soft (which reads rows in the handle's current format).  Stream mode ignores it: wifirx_push / wifirx_poll*,
+ * the WIFIRX_P_STREAM_SOFT rows and the GNU Radio block keep float32.  Other values are WIFIRX_EINVAL. */
+#define WIFIRX_P_LLR_FORMAT 10
+#define WIFIRX_LLR_F32  0
+#define WIFIRX_LLR_BF16 1
 
 typedef struct wifirx_handle wifirx_handle;
 
@@ -156,7 +166,10 @@ typedef struct wifirx_handle wifirx_handle;
  *   frames  [n_slots]
  *   idx     [n_slots][max_sym][48]            hard decisions, one constellation index per byte
  *                                              (output 0 of frame_equalizer, grc:550-569)
- *   llr     [n_slots][max_sym*48*llr_bits]    per frame packed [sym][carrier][bit 0..n_bpsc-1]
+ *   llr     [n_slots][max_sym*48*llr_bits]    per frame packed [sym][carrier][bit 0..n_bpsc-1]: element
+ *                                              (q*48 + k)*n_bpsc + b of a frame = bit b of carrier k of data
+ *                                              symbol q.  float32 values, or uint16_t bf16 bit patterns (half
+ *                                              the bytes) when WIFIRX_P_LLR_FORMAT = WIFIRX_LLR_BF16
  *   carrier [n_slots][max_sym][48][2]         equalised points (re,im): the `symbols` message port
  *   psdu    [n_slots][psdu_stride]            decode_mac output: MAC frame incl. FCS position
  *                                              (bytes 0..psdu_len-1), valid when WIFIRX_F_CRC_OK
@@ -246,7 +259,8 @@ int  wifirx_demod_batch_v(wifirx_handle* h, const float* iq, int iq_on_device, c
 int  wifirx_decode_batch(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out);
 
 /* Soft-decision decode_mac: wifirx_decode_batch with the Viterbi on the LLRs of out->llr (rows of
- * max_sym * 48 * cfg.llr_bits floats, as wifirx_demod_batch writes them, 16-byte aligned) instead of the hard decisions;
+ * max_sym * 48 * cfg.llr_bits values in the handle's WIFIRX_P_LLR_FORMAT, as wifirx_demod_batch writes them, the buffer
+ * 16-byte aligned; bf16 values are widened exactly to float32 first) instead of the hard decisions;
  * metrics, tie rule, normalisation and final state are NUMERICS.md rule 14.  It decodes the frames wifirx_decode_batch
  * would that also carry WIFIRX_F_LLR, and leaves every other record as it is; WIFIRX_F_DECODED, WIFIRX_F_CRC_OK and
  * out->psdu mean what they mean there.  WIFIRX_EINVAL when out->llr is NULL, the handle has llr_bits = 0, or the buffers
