@@ -22,6 +22,7 @@
 
 #include "wifirx.h"
 #include "wr_kernels.h"
+#include "wr_tx.h"
 
 // A finished frame of the stream: its record and where its outputs sit in the (shared) host copy of its batch.
 struct PolledFrame {
@@ -55,6 +56,8 @@ struct wifirx_handle {
     void*  stage_stats = nullptr;   size_t stage_stats_bytes = 0;
     void*  stage_hbits = nullptr;   size_t stage_hbits_bytes = 0;
     void*  stage_off = nullptr;     size_t stage_off_bytes = 0;      // slot offsets of wifirx_demod_batch_v
+    void*  tx_psdu = nullptr;       size_t tx_psdu_bytes = 0;        // wifirx_tx_batch: host PSDUs
+    void*  tx_meta = nullptr;       size_t tx_meta_bytes = 0;        // wifirx_tx_batch: lengths, seeds, row offsets
 
     // decode workspace
     void*  dec_scratch = nullptr;   size_t dec_scratch_bytes = 0;
@@ -252,6 +255,8 @@ int wifirx_destroy(wifirx_handle* h)
     if (h->dec_hbits) (void)hipFree(h->dec_hbits);
     if (h->s_llr) (void)hipFree(h->s_llr);
     if (h->dec_perm) (void)hipFree(h->dec_perm);
+    if (h->tx_psdu) (void)hipFree(h->tx_psdu);
+    if (h->tx_meta) (void)hipFree(h->tx_meta);
     if (h->s_host) (void)hipHostFree(h->s_host);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -570,3 +575,4 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 
 #include "wifirx_api_decode.inc"
 #include "wifirx_api_stream.inc"
+#include "wifirx_api_tx.inc"

@@ -1,4 +1,5 @@
-"""``wifi_phy_rx`` -- drop-in for the RX half of the reference's ``wifi_phy_hier`` hier block.
+"""``wifi_phy_rx`` -- drop-in for the RX half of the reference's ``wifi_phy_hier`` hier block (``wifi_phy_tx``, at the
+end of this file, is the TX half).
 
 Port names, parameters and setters are those of gnu_radio/wifi_phy_hier.grc (pad ``samp_in``
 :587-604, message pads ``mac_out`` / ``carrier`` :605-640, parameters ``bandwidth``, ``chan_est``,
@@ -24,7 +25,7 @@ import math
 
 import numpy as np
 
-from . import capi, grshim, probe
+from . import capi, grshim, probe, txgen
 
 LS, LMS, COMB, STA = 0, 1, 2, 3
 _C64 = np.dtype(np.complex64)
@@ -258,4 +259,72 @@ class wifi_phy_rx(grshim.sync_block):
 
     def close(self):
         """Release the library handle (device buffers, stream)."""
+        self._rx.close()
+
+
+class wifi_phy_tx(grshim.sync_block):
+    """Drop-in for the TX half of ``wifi_phy_hier`` (mapper, SIGNAL, chunks->symbols, carrier allocator, IFFT, cyclic
+    prefixer; gnu_radio/wifi_phy_hier.grc:279-479,570-586), optionally with ``foo.packet_pad2``'s zeros folded in
+    (``pad_front=100, pad_tail=1000`` = gnu_radio/IRS_user.py:193).
+
+    * ``mac_in``: the ``(meta, u8vector)`` PDU that ``ieee802_11.mac`` sends from ``phy out`` -- the PSDU, FCS included.
+    * ``samp_out``: the frames back to back in arrival order, each ``pad_front`` zeros + frame + ``pad_tail`` zeros.
+
+    The scrambler seed runs 1..127 from frame to frame across ``work()`` calls, as the mapper's does.  Every ``work()``
+    builds all PDUs queued since the last one in one device call (wifirx_tx_batch); what does not fit ``output_items[0]``
+    is handed out by the following calls.  The block emits base-band at the hier block's level: IRS_user's x0.5 gain
+    stays in the flowgraph."""
+
+    def __init__(self, encoding=0, pad_front=0, pad_tail=0, device=0):
+        grshim.sync_block.__init__(self, name="wifi_phy_tx", in_sig=None, out_sig=[np.complex64])
+        self.set_encoding(encoding)
+        self.pad_front, self.pad_tail = int(pad_front), int(pad_tail)
+        if self.pad_front < 0 or self.pad_tail < 0:
+            raise ValueError("pad_front and pad_tail must be >= 0")
+        self._rx = capi.WifiRx(max_sym=1, device=device)          # the handle's receive side stays unused
+        self._queue = []                                            # PSDUs (bytes) waiting for work()
+        self._carry = np.zeros(0, dtype=np.complex64)               # built samples not yet handed out
+        self._n_frames = 0                                          # frames built so far: the next seed
+        self.message_port_register_in(grshim.intern("mac_in"))
+        self.set_msg_handler(grshim.intern("mac_in"), self._on_pdu)
+
+    def get_encoding(self):
+        return self.encoding
+
+    def set_encoding(self, encoding):
+        encoding = int(encoding)
+        if not 0 <= encoding <= 7:
+            raise ValueError("encoding must be 0..7")
+        self.encoding = encoding
+
+    def _on_pdu(self, msg):
+        vec = grshim.to_python(msg)[1]
+        self._queue.append(np.asarray(vec, dtype=np.uint8).tobytes())
+
+    def _build(self):
+        psdus, self._queue = self._queue, []
+        n = len(psdus)
+        seeds = (np.arange(self._n_frames, self._n_frames + n) % 127) + 1
+        rows = [self.pad_front + txgen.frame_samples(len(p), self.encoding) + self.pad_tail for p in psdus]
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        row_off[1:] = np.cumsum(rows)
+        x = self._rx.tx_batch(psdus, self.encoding, seeds=seeds, lead=self.pad_front, row_off=row_off)
+        self._n_frames += n
+        self._carry = np.concatenate([self._carry, x]) if self._carry.size else x
+
+    def work(self, input_items, output_items):
+        if self._queue:
+            self._build()
+        out = output_items[0]
+        n = min(len(out), self._carry.size)
+        out[:n] = self._carry[:n]
+        self._carry = self._carry[n:]
+        return n
+
+    def pending(self):
+        """samples built and not yet handed out"""
+        return int(self._carry.size)
+
+    def close(self):
+        """Release the library handle."""
         self._rx.close()

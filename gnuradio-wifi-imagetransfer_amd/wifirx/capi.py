@@ -39,7 +39,7 @@ EXPORTS = [
     "wifirx_get_stats", "wifirx_demod_batch", "wifirx_decode_batch", "wifirx_push", "wifirx_poll", "wifirx_poll_csi",
     "wifirx_sync", "wifirx_stream", "wifirx_synth_slots", "wifirx_dev_alloc", "wifirx_dev_free",
     "wifirx_memcpy_h2d", "wifirx_memcpy_d2h", "wifirx_time_demod", "wifirx_poll_ex", "wifirx_demod_batch_v",
-    "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft",
+    "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft", "wifirx_tx_batch",
 ]
 
 
@@ -110,6 +110,8 @@ _lib.wifirx_sync.argtypes = [C.c_void_p]
 _lib.wifirx_synth_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint64,
                                     C.c_void_p]
+_lib.wifirx_tx_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p,
+                                 C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -349,6 +351,69 @@ class WifiRx:
         n_t, flen = templates.shape
         self._check(_lib.wifirx_synth_slots(self._h, _np_ptr(templates), 0, n_t, flen, slots_ptr, slot_len,
                                             n_slots, lead, snr_db, cfo_max, seed, cfo_out_ptr))
+
+    def synth_slots_dev(self, templates_ptr, n_templates, frame_len, slots_ptr, slot_len, n_slots, lead, snr_db, cfo_max,
+                        seed, cfo_out_ptr=None):
+        """synth_slots over templates already on the device (n_templates rows of frame_len samples, e.g. tx_batch_dev's)"""
+        self._check(_lib.wifirx_synth_slots(self._h, templates_ptr, 1, n_templates, frame_len, slots_ptr, slot_len,
+                                            n_slots, lead, snr_db, cfo_max, seed, cfo_out_ptr))
+
+    # -- transmitter (wifirx_tx_batch) --
+    @staticmethod
+    def _tx_psdus(psdus, psdu_len=None):
+        """list of bytes, or a 2-D uint8 array (+ optional lengths) -> (host array [n, stride] uint8, lengths uint32)"""
+        if isinstance(psdus, np.ndarray):
+            arr = np.ascontiguousarray(psdus, dtype=np.uint8)
+            if arr.ndim != 2:
+                raise ValueError("psdus must be a 2-D uint8 array or a list of bytes")
+            lens = np.full(arr.shape[0], arr.shape[1], np.uint32) if psdu_len is None else np.asarray(psdu_len, np.uint32)
+            return arr, np.ascontiguousarray(lens)
+        lens = np.array([len(p) for p in psdus], dtype=np.uint32)
+        arr = np.zeros((len(psdus), max(int(lens.max(initial=0)), 1)), dtype=np.uint8)
+        for i, p in enumerate(psdus):
+            arr[i, :len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
+        return arr, lens
+
+    def tx_batch_dev(self, samples_ptr, samples_cap, psdus, encoding, seeds=None, lead=0, row_len=None, row_off=None,
+                     psdu_len=None, psdu_stride=None):
+        """wifirx_tx_batch into device memory (samples_cap complex64 samples at samples_ptr).  psdus: host PSDUs (see
+        tx_batch), or an int device pointer with psdu_len (host lengths) and psdu_stride.  Asynchronous on the handle's
+        stream.  Returns the lengths used."""
+        if isinstance(psdus, int):
+            lens = np.ascontiguousarray(psdu_len, dtype=np.uint32)
+            ptr, on_dev, stride, keep = psdus, 1, int(psdu_stride), None
+        else:
+            keep, lens = self._tx_psdus(psdus, psdu_len)
+            ptr, on_dev, stride = _np_ptr(keep), 0, keep.shape[1]
+        n = lens.size
+        sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint8), (n,)))
+        ro = None if row_off is None else np.ascontiguousarray(row_off, dtype=np.uint64)
+        if ro is not None and ro.size != n + 1:
+            raise ValueError("row_off needs n_frames + 1 entries")
+        self._check(_lib.wifirx_tx_batch(self._h, int(encoding), ptr, on_dev, stride, _np_ptr(lens), _np_ptr(sd), n,
+                                         samples_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0), int(lead)))
+        return lens
+
+    def tx_batch(self, psdus, encoding, seeds=None, lead=0, row_len=None, row_off=None, psdu_len=None):
+        """Base-band frames of `psdus` (list of bytes, or a 2-D uint8 array with optional psdu_len) at one encoding, built on
+        the device.  Fixed rows (row_len; default lead + the longest frame): returns [n, row_len] complex64, frame i at
+        [i, lead:lead + frame].  row_off ([n + 1] sample offsets): returns the packed 1-D stream of samples
+        [row_off[0], row_off[n]), frame i `lead` samples into its row."""
+        from . import txgen
+        arr, lens = self._tx_psdus(psdus, psdu_len)
+        n = lens.size
+        if row_off is None and row_len is None:
+            row_len = lead + max((txgen.frame_samples(int(l), encoding) for l in lens), default=0)
+        total = int(row_off[-1]) if row_off is not None else n * int(row_len)
+        buf = self.alloc(max(total, 1) * 8)
+        try:
+            self.tx_batch_dev(buf.ptr, total, arr, encoding, seeds, lead, row_len, row_off, psdu_len=lens)
+            out = buf.download(np.complex64, total)      # wifirx_memcpy_d2h is ordered behind the kernel on the stream
+        finally:
+            buf.free()
+        if row_off is not None:
+            return out[int(row_off[0]):]
+        return out.reshape(n, int(row_len))
 
     # -- stream mode --
     def push(self, iq: np.ndarray):

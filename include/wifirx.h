@@ -1,5 +1,6 @@
 /*
- * wifirx.h -- C ABI of libwifirx.so: the MI355X-native IEEE 802.11a/g OFDM PHY receive chain.
+ * wifirx.h -- C ABI of libwifirx.so: the MI355X-native IEEE 802.11a/g OFDM PHY receive chain (and, wifirx_tx_batch, the
+ * transmitter that feeds it).
  *
  * This is the drop-in boundary for the RX half of the reference's `wifi_phy_hier` hier block
  * (gnu_radio/wifi_phy_hier.grc:100-260,480-569,698-768), which IRS_AP inlines block for block
@@ -315,6 +316,31 @@ int  wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_
                         uint32_t n_templates, uint32_t frame_len, float* slots, uint32_t slot_len,
                         uint32_t n_slots, uint32_t lead, float snr_db, float cfo_max,
                         uint64_t seed, float* cfo_out);
+
+/* TX half of wifi_phy_hier (mapper, SIGNAL, chunks->symbols, allocator, IFFT, cyclic prefixer;
+ * gnu_radio/wifi_phy_hier.grc:279-479,570-586) for n_frames PSDUs at one encoding: the base-band frames the hier block
+ * emits at `samp_out` (before IRS_user's x0.5 gain), (5 + n_sym) * 80 + 1 samples each, n_sym = ceil((16 + 8 L + 6) / N_DBPS).
+ * Frame i = SERVICE (16 zero bits) + PSDU i (LSB first) + 6 tail bits + pad, scrambled (x^7 + x^4 + 1, initial state seeds[i]),
+ * tail re-zeroed, (133,171)-encoded, punctured, interleaved, mapped; behind the 4 sync words and the SIGNAL symbol, with
+ * pilots of polarity p_n; arithmetic = NUMERICS.md rule 16.  One kernel launch per call.
+ *   psdu      frame i at psdu + i * psdu_stride (psdu_stride >= every psdu_len); device memory when psdu_on_device
+ *   psdu_len  HOST [n_frames], 1..4095 bytes
+ *   seeds     HOST [n_frames], 1..127; NULL = (i % 127) + 1 (the mapper's per-frame increment)
+ *   samples   DEVICE complex64 (8-byte aligned), samples_cap samples long
+ *   rows      row i = samples [row_off[i], row_off[i+1]) when row_off (HOST [n_frames + 1], non-decreasing) is given,
+ *             [i row_len, (i+1) row_len) otherwise.  Frame i starts `lead` samples into row i; every other sample of the row
+ *             is written 0.  Samples outside the rows are not touched.  Fixed rows = the slots wifirx_demod_batch reads;
+ *             row_off with lead = 100 and rows of 100 + frame + 1000 = foo.packet_pad2's stream (IRS_user.py:193).
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for an unknown encoding, psdu_len 0 or > 4095 or above
+ * psdu_stride, a seed outside 1..127, a decreasing row_off, NULL psdu / psdu_len / samples; WIFIRX_ERANGE when a frame plus
+ * lead does not fit its row or the rows end behind samples_cap.  n_frames = 0 does nothing and returns WIFIRX_OK.
+ * ORDER: the call waits for the handle's stream until its host inputs (psdu_len, seeds, row_off, host PSDUs) are copied, so
+ * they may be reused when it returns; the kernel then runs asynchronously on the handle's stream (hipStreamNonBlocking:
+ * it is not ordered against the legacy default stream).  Device PSDUs and `samples` must stay valid until it has run --
+ * wifirx_sync(), or an event recorded on wifirx_stream(); later calls on the same handle are ordered behind it. */
+int  wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* psdu, int psdu_on_device, uint32_t psdu_stride,
+                     const uint32_t* psdu_len, const uint8_t* seeds, uint32_t n_frames, float* samples, uint64_t samples_cap,
+                     const uint64_t* row_off, uint64_t row_len, uint32_t lead);
 
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);
