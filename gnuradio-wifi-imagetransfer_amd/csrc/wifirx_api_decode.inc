@@ -115,7 +115,7 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
     }
     if (n_slots <= h->decode_small_max) {
         // few frames: one wave per frame (8 B of survivor bits per step + the decoded words of the frame)
-        const size_t stride = ((size_t)n_steps + (size_t)n_steps / 60 + 4) * sizeof(uint64_t);
+        const size_t stride = wr::dec_small_slice(n_steps);
         const size_t n_waves = std::min<size_t>(n_slots, WR_DECODE_MAX_WAVES);
         rc = ensure(h, &h->dec_scratch, &h->dec_scratch_bytes, stride * n_waves);
         if (rc) return rc;
@@ -125,15 +125,14 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
         return WIFIRX_OK;
     }
     // per wave: the survivor bits of every step and lane (16 B for two frames per lane, 32 B for four) and the decoded words of
-    // the lane's frames (layouts in wr_decode.hip).  Four frames per lane (decode_q_kernel: byte metrics, 256 frames per
+    // the lane's frames (layouts in wr_kernels.h).  Four frames per lane (decode_q_kernel: byte metrics, 256 frames per
     // wave) when the batch holds enough decodable frames to fill the GPU with such waves; WIFIRX_DECODE_Q=1 / 0 forces /
     // forbids it (tests).
     uint32_t n_dec = 0;
     for (int e = 0; e < 8; e++) n_dec += pre[1 + e];
     const bool use_q = h->decode_q == 1 || (h->decode_q < 0 && n_dec >= WR_DECODE_Q_MIN_FRAMES);
     const uint32_t fpw_max = use_q ? WR_DECODE_Q_FRAMES_PER_WAVE : WR_DECODE_FRAMES_PER_WAVE;
-    size_t stride = use_q ? (size_t)n_steps * 64 * 32 + ((size_t)n_steps / 32 + 2) * WR_DECODE_Q_FRAMES_PER_WAVE * sizeof(uint32_t)
-                          : (size_t)n_steps * 64 * 16 + ((size_t)n_steps / 32 + 2) * WR_DECODE_FRAMES_PER_WAVE * sizeof(uint32_t);
+    size_t stride = use_q ? wr::dec_q_slice(n_steps, false) : wr::dec_pair_slice(n_steps);
     // mid-size batches: fewer frames per wave, so that about a thousand waves share the work
     uint32_t fpw = (uint32_t)std::min<size_t>(fpw_max, std::max<size_t>(1, (n_slots + 1023) / 1024));
     if (use_q && h->decode_q < 0) fpw = fpw_max;
@@ -146,7 +145,7 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
     // (168 registers; two for the 64-QAM instance), one scratch slice per wave + the walks' start states.  Mode 0: the trace-back
     // behind each task.  WIFIRX_DECODE_OVL = 0 / 2 forces a mode (tests, A/B).
     size_t budget = decode_scratch_budget(h);
-    const size_t stride_spec = stride + ((size_t)n_steps / 96 + 2) * 64 * sizeof(uint32_t);
+    const size_t stride_spec = wr::dec_q_slice(n_steps, true);
     const size_t spec_waves = (size_t)h->n_simd * ((pre[7] | pre[8]) ? 2 : WR_DQ_SPEC_WAVES);      // (the 64-QAM instance: two workgroups of its LDS fit a CU)
     int mode = 0;
     if (use_q) {
@@ -201,7 +200,7 @@ static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifi
     if ((rc = decode_group_by_rate(h, n_slots, out, pre, fpw, g))) return rc;
     const size_t n_tasks = (g.n_virtual + fpw - 1) / fpw;
     // per wave: 8 bytes of survivor bits per step and lane, the decoded words of its 64 frames (two spare words)
-    const size_t stride = (size_t)n_steps * 64 * 8 + ((size_t)n_steps / 32 + 2) * 64 * sizeof(uint32_t);
+    const size_t stride = wr::dec_soft_slice(n_steps);
     size_t n_waves = 0;
     if ((rc = decode_alloc_scratch(h, stride, std::min<size_t>(n_tasks, WR_DECODE_MAX_WAVES), decode_scratch_budget(h), n_waves)))
         return rc;

@@ -8,10 +8,32 @@
 
 namespace wr {
 
-// per rate (SIGNAL encoding 0..7): data bits per OFDM symbol, puncturing (0 = 1/2, 1 = 2/3, 2 = 3/4), coded bits per carrier
+// per rate (SIGNAL encoding 0..7): data bits per OFDM symbol, coded bits per carrier, puncturing (0 = 1/2, 1 = 2/3,
+// 2 = 3/4), bit-plane words per symbol (wifirx_out.hbits: two per coded bit of a carrier).  n_dbps comes from a table in
+// constant memory (one load; as a select chain it compiled to a branch tree in front of frame_steps' division, 17 more
+// registers in decode_pack_kernel); the others are select chains.
 constexpr int RATE_NDBPS[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
-constexpr int RATE_PUNCT[8] = { 0, 2, 0, 2, 0, 2, 1, 2 };
-constexpr int RATE_NBPSC[8] = { 1, 1, 2, 2, 4, 4, 6, 6 };
+constexpr __host__ __device__ int ndbps_of(int enc) { return RATE_NDBPS[enc]; }
+constexpr __host__ __device__ int nbpsc_of(int enc) { return enc < 2 ? 1 : enc < 4 ? 2 : enc < 6 ? 4 : 6; }
+constexpr __host__ __device__ int punct_of(int enc) { return enc == 6 ? 1 : (enc & 1) ? 2 : 0; }
+constexpr __host__ __device__ int words_per_sym(int enc) { return 2 * nbpsc_of(enc); }
+
+// Trellis steps of a frame decode_mac accepts (n_sym * n_dbps, a multiple of 12), 0 for a frame it leaves alone.  The one
+// rule for which frames get decoded: the pre-pass (decode_maxsteps_kernel, with a cap that cannot bind) counts the frames it
+// accepts per rate and sets n_steps_cap to their longest trellis, decode_perm_kernel groups exactly those frames by rate,
+// and every decode kernel takes exactly those frames.  So a frame the pre-pass counts is a frame the kernels decode, and
+// every task of the throughput kernels (decode_kernel, decode_q_kernel, the soft kernel) holds frames of one rate -- they
+// read the task's rate from its first active lane.  (The soft kernel adds two conditions, soft_frame_steps: the pre-pass
+// still counts the frames it leaves alone.)
+__device__ __forceinline__ int frame_steps(uint32_t flags, int enc, int len, uint32_t psdu_stride, uint32_t max_sym,
+                                           uint32_t n_steps_cap)
+{
+    const int n_dbps = ndbps_of(enc & 7);
+    const int n_sym = (16 + 8 * len + 6 + n_dbps - 1) / n_dbps;
+    const bool ok = (flags & WIFIRX_F_COMPLETE) && len <= (int)psdu_stride && len <= WIFIRX_MAX_PSDU &&
+                    n_sym <= WIFIRX_MAX_SYM && n_sym <= (int)max_sym && (uint32_t)(n_sym * n_dbps) <= n_steps_cap;
+    return ok ? n_sym * n_dbps : 0;
+}
 
 // Where the coded bit at position `ci` of the de-punctured stream of ONE OFDM symbol was received: de-puncturing, then
 // the de-interleaver, give its index among the symbol's 48 * n_bpsc coded bits (carrier * n_bpsc + bit), or -1 when the
@@ -37,6 +59,25 @@ constexpr int coded_index(int punct, int n_bpsc, int ci)
 
 constexpr __host__ __device__ int rotr6(int s, int p) { return ((s >> p) | (s << (6 - p))) & 63; }
 constexpr __host__ __device__ int parity_of(int v) { return __builtin_popcount(v) & 1; }
+
+// Per-rate tables of one OFDM symbol: entry [enc][step tt of the symbol] = entry(n_bpsc, j) of coded bit 2 tt in the low half
+// and of coded bit 2 tt + 1 in the high half, where j is the bit's coded_index (-1: dropped by the transmitter, and for the
+// steps past the rate's n_dbps).
+constexpr int RATE_TAB_STRIDE = 216;      // steps per OFDM symbol at the highest rate
+struct RateTable { uint32_t e[8 * RATE_TAB_STRIDE]; };
+template <typename Entry>
+constexpr RateTable make_rate_table(Entry entry)
+{
+    RateTable t{};
+    for (int enc = 0; enc < 8; enc++)
+        for (int tt = 0; tt < RATE_TAB_STRIDE; tt++) {
+            const int nb = nbpsc_of(enc), pu = punct_of(enc);
+            const bool in = tt < ndbps_of(enc);
+            const int ja = in ? coded_index(pu, nb, 2 * tt) : -1, jb = in ? coded_index(pu, nb, 2 * tt + 1) : -1;
+            t.e[enc * RATE_TAB_STRIDE + tt] = entry(nb, ja) | (entry(nb, jb) << 16);
+        }
+    return t;
+}
 
 // Tables of the per-frame finish (workgroup LDS, built once per workgroup): crc[k][b] = CRC-32 (reflected 0xedb88320)
 // of byte b followed by k zero bytes ("slicing by 4"), scr[s] = the next 32 scrambler bits from LFSR state s.

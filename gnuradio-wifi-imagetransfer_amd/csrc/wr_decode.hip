@@ -18,8 +18,8 @@
 // The received coded bits come as the bit planes of the hard decisions (wifirx_out.hbits: written by the demod
 // kernels, or packed from `idx` by decode_pack_kernel): each lane copies the words of the current OFDM symbol of its
 // two frames into lane-private LDS slots and picks the coded bits of a trellis step from there -- where a coded bit
-// sits (de-puncturing + de-interleaving) is a per-rate table of one OFDM symbol, read through the scalar unit when all
-// frames of the wave share a rate.
+// sits (de-puncturing + de-interleaving) is a per-rate table of one OFDM symbol, read through the scalar unit: every task
+// is of one rate (wr_decode.h, frame_steps).
 //
 // Results are bit-identical to the oracle's viterbi_decode(): same metrics (Hamming, erasures free),
 // same tie rule (the survivor with older bit 0 wins), same final state rule (smallest metric, lowest
@@ -34,9 +34,7 @@
 
 namespace wr {
 
-#ifndef WR_DEC_WAVES_PER_SIMD
 #define WR_DEC_WAVES_PER_SIMD 4
-#endif
 #define WR_DEC_CHUNK      60                   // decode_small_kernel: trellis steps per pass (lane <-> step)
 #define WR_DEC_NORM_STEPS 120                  // decode_kernel: the common minimum leaves the metrics every so many steps
 
@@ -45,7 +43,6 @@ namespace wr {
 // bit of the word (= bin & 31), bits 5..8 the word, or WR_SRC_PUNCT when the transmitter dropped the coded bit.
 // Read as 16-bit planes (plane p = 4 b + (bin >> 4), bit bin & 15) the same entry is p = bits 4..8, bit = bits 0..3.
 #define WR_SRC_PUNCT 0x200u
-#define WR_DEC_TAB_STRIDE 216              // steps per OFDM symbol at the highest rate
 constexpr int bin_of_carrier(int c)         // data carrier 0..47 -> FFT bin, shifted order (bin 32 = DC)
 {
     int i = c + 6;
@@ -56,33 +53,19 @@ constexpr int bin_of_carrier(int c)         // data carrier 0..47 -> FFT bin, sh
     if (i >= 53) i++;
     return i;
 }
-constexpr uint32_t coded_src(int punct, int n_bpsc, int ci)
+constexpr uint32_t coded_src(int n_bpsc, int j)      // j = coded_index of the bit, -1 when dropped
 {
-    const int j = coded_index(punct, n_bpsc, ci);
     if (j < 0) return WR_SRC_PUNCT;
     const int carrier = j / n_bpsc, bit = j - carrier * n_bpsc;
     const int bin = bin_of_carrier(carrier);
     return (uint32_t)(bin & 31) | ((uint32_t)(2 * bit + (bin >> 5)) << 5);
 }
-struct SrcTable { uint32_t e[8 * WR_DEC_TAB_STRIDE]; };    // [enc][step of the symbol]: coded bit A in the low half, B in the high half
-constexpr SrcTable make_src_table()
-{
-    SrcTable t{};
-    for (int enc = 0; enc < 8; enc++)
-        for (int tt = 0; tt < WR_DEC_TAB_STRIDE; tt++) {
-            uint32_t v = WR_SRC_PUNCT | (WR_SRC_PUNCT << 16);
-            if (tt < RATE_NDBPS[enc])
-                v = coded_src(RATE_PUNCT[enc], RATE_NBPSC[enc], 2 * tt) | (coded_src(RATE_PUNCT[enc], RATE_NBPSC[enc], 2 * tt + 1) << 16);
-            t.e[enc * WR_DEC_TAB_STRIDE + tt] = v;
-        }
-    return t;
-}
-__constant__ const SrcTable WR_SRC_TABLE = make_src_table();
+__constant__ const RateTable WR_SRC_TABLE = make_rate_table(coded_src);      // [enc][step of the symbol]: coded bit A | B << 16
 
 // the workgroup's copy in LDS (lane-dependent look-ups)
 __device__ __forceinline__ void copy_src_table(uint32_t* tab)
 {
-    for (int e = threadIdx.x; e < 8 * WR_DEC_TAB_STRIDE; e += blockDim.x) tab[e] = WR_SRC_TABLE.e[e];
+    for (int e = threadIdx.x; e < 8 * RATE_TAB_STRIDE; e += blockDim.x) tab[e] = WR_SRC_TABLE.e[e];
 }
 
 // The received value (0, 1, or 2 = punctured / beyond the tile) of the coded bits A and B of step t of one frame.
@@ -101,18 +84,6 @@ __device__ __forceinline__ void gather_step(const uint32_t* tile, int sym0, int 
         if (!(ea & WR_SRC_PUNCT)) ra = (int)((sp[(ea >> 5) & 15u] >> (ea & 31u)) & 1u);
         if (!(eb & WR_SRC_PUNCT)) rb = (int)((sp[(eb >> 5) & 15u] >> (eb & 31u)) & 1u);
     }
-}
-
-// trellis steps of a frame decode_mac accepts (a multiple of 12), 0 for a frame it leaves alone
-__device__ __forceinline__ int frame_steps(uint32_t flags, int enc, int len, uint32_t psdu_stride, uint32_t max_sym,
-                                           uint32_t n_steps_cap)
-{
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
-    const int n_dbps = ndbps_tab[enc & 7];
-    const int n_sym = (16 + 8 * len + 6 + n_dbps - 1) / n_dbps;
-    const bool ok = (flags & WIFIRX_F_COMPLETE) && len <= (int)psdu_stride && len <= WIFIRX_MAX_PSDU &&
-                    n_sym <= WIFIRX_MAX_SYM && n_sym <= (int)max_sym && (uint32_t)(n_sym * n_dbps) <= n_steps_cap;
-    return ok ? n_sym * n_dbps : 0;
 }
 
 #define WR_RECIP32(d) (uint32_t)((0x100000000ull + (d) - 1) / (d))      /* ceil(2^32 / d) */
@@ -144,15 +115,14 @@ void decode_pack_kernel(uint32_t n_slots, uint32_t max_sym, const wifirx_frame* 
 {
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
     const bool idx4 = ((reinterpret_cast<uintptr_t>(idx_all) | ((size_t)max_sym * 48)) & 3) == 0;
     for (uint32_t slot = blockIdx.x * 4 + wv; slot < n_slots; slot += gridDim.x * 4) {
         const wifirx_frame fr = frames[slot];
         const int enc = fr.encoding & 7;
         const int n_data = frame_steps(fr.flags, enc, fr.psdu_len, psdu_stride, max_sym, n_steps_cap);
         if (n_data == 0) continue;                                    // wave-uniform: one frame per wave
-        const int n_sym = n_data / ndbps_tab[enc];
-        const int nb = enc < 2 ? 1 : enc < 4 ? 2 : enc < 6 ? 4 : 6;
+        const int n_sym = n_data / ndbps_of(enc);
+        const int nb = nbpsc_of(enc);
         const uint8_t* fidx = idx_all + (size_t)slot * max_sym * 48;
         uint32_t* fhb = hbits_all + (size_t)slot * max_sym * 12;
         for (int q = lane; q < n_sym; q += 64) {
@@ -248,10 +218,8 @@ __device__ __forceinline__ void lds_rows6(const uint32_t (&a)[6], uint32_t (&w)[
                  : "memory");
 }
 
-// MIXED = false: the tasks whose frames all share one rate (the usual case: where a coded bit sits is then the same
-// for every lane, and comes through the scalar unit).  MIXED = true: the other tasks (per-lane look-ups).  Both kernels are
-// launched over the same tasks, one after the other on the stream, and each leaves the other's tasks alone.
-template <bool MIXED>
+// Every task is of one rate (wr_decode.h, frame_steps): where a coded bit sits is the same for every lane, and comes
+// through the scalar unit.
 __global__ __launch_bounds__(256, WR_DEC_WAVES_PER_SIMD)
 void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict__ frames,
                    const uint32_t* __restrict__ hbits_all, uint8_t* __restrict__ psdu_all, uint32_t psdu_stride,
@@ -261,13 +229,11 @@ void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict_
     // perm != nullptr: the wave's frames are perm[base + ...] (0xffffffff: no frame) -- the decodable frames of a batch
     // with several rates, grouped by rate into runs that start on task boundaries (decode_perm_kernel), so that every
     // task is of one rate; perm == nullptr: frame k is slot k, n_virtual = n_slots.
-    // the current OFDM symbols of the wave's frames, lane-private columns.  One rate: row 2 w + g (w = word of the staged
-    // block, g = 0, 1) = 16-bit plane g of the word of frame A | that of frame B << 16 (plane p of a symbol = row 2 n_w s + p
-    // for the s-th symbol of the block); mixed rates: row 12 h + k = word k of the current symbol of the frame of half h.
-    __shared__ uint32_t sym_all[4][(MIXED ? 24 : 32) * 64];
-    __shared__ uint32_t src_tab[MIXED ? 8 * WR_DEC_TAB_STRIDE : 1];
+    // the current OFDM symbols of the wave's frames, lane-private columns: row 2 w + g (w = word of the staged block, g = 0, 1)
+    // = 16-bit plane g of the word of frame A | that of frame B << 16 (plane p of a symbol = row 2 n_w s + p for the s-th
+    // symbol of the block)
+    __shared__ uint32_t sym_all[4][32 * 64];
     __shared__ FinishTables ft;
-    if (MIXED) copy_src_table(src_tab);
     build_finish_tables(ft);
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
@@ -275,11 +241,10 @@ void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict_
     if (wave >= n_waves_total) return;
     uint32_t* symw = sym_all[wv] + lane;
     const uint32_t sym_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)sym_all[wv]);     // LDS byte address of the wave's rows
-    const size_t n_data_cap = n_steps_cap;               // trellis steps the scratch slice of a wave holds
-    uint32_t* surv = reinterpret_cast<uint32_t*>(scratch + (size_t)wave * scratch_stride);   // [step][lane][4 pieces]
-    uint32_t* dbits = surv + n_data_cap * 256;                                               // [word][A/B][lane]
+    uint8_t* const slice = scratch + (size_t)wave * scratch_stride;                                  // (layout: wr_kernels.h)
+    uint32_t* surv = reinterpret_cast<uint32_t*>(slice);                                             // [step][lane][4 pieces]
+    uint32_t* dbits = reinterpret_cast<uint32_t*>(slice + dec_pair_dbits_at(n_steps_cap));           // [word][A/B][lane]
     const uint32_t k1 = 0x00010001u;
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
     const uint32_t hb_stride = max_sym * 12;             // words per frame
 
     // A wave's tasks (frames_per_wave <= 128 frames each, grid-stride); lane l owns frames base + l (l < fA) and
@@ -289,7 +254,7 @@ void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict_
     for (uint32_t task = wave; task < n_tasks; task += n_waves_total) {
         const uint32_t base = task * frames_per_wave;
         // ---- my two frames ----
-        int n_data[2], enc[2];
+        int n_data[2], enc_any = 0;
         uint32_t slot_of[2];
         int n_max = 0;
 #pragma unroll
@@ -298,10 +263,10 @@ void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict_
             uint32_t slot = 0xffffffffu;
             if ((uint32_t)lane < (h ? fB : fA) && v < n_virtual) slot = perm ? perm[v] : v;
             n_data[h] = 0;
-            enc[h] = 0;
             if (slot < n_slots) {
-                enc[h] = frames[slot].encoding & 7;
-                n_data[h] = frame_steps(frames[slot].flags, enc[h], frames[slot].psdu_len, psdu_stride, max_sym, n_steps_cap);
+                const int e = frames[slot].encoding & 7;
+                n_data[h] = frame_steps(frames[slot].flags, e, frames[slot].psdu_len, psdu_stride, max_sym, n_steps_cap);
+                if (n_data[h]) enc_any = e;
             }
             slot_of[h] = slot < n_slots ? slot : 0u;
             n_max = n_data[h] > n_max ? n_data[h] : n_max;
@@ -315,15 +280,12 @@ void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict_
         }
         n_max = __builtin_amdgcn_readfirstlane(n_max);
         if (n_max == 0) continue;
-        // one rate for all frames of the task?
-        const uint64_t actA = __ballot(n_data[0] > 0), actB = __ballot(n_data[1] > 0);
-        const int enc_u = actA ? __builtin_amdgcn_readlane(enc[0], (int)__builtin_ctzll(actA))
-                               : __builtin_amdgcn_readlane(enc[1], (int)__builtin_ctzll(actB));
-        const bool uni_rate = __all((n_data[0] == 0 || enc[0] == enc_u) && (n_data[1] == 0 || enc[1] == enc_u));
-        if (uni_rate == MIXED) continue;                 // the other kernel's task
-        const int nd_u = ndbps_tab[enc_u];
-        const int nw_u = enc_u < 2 ? 2 : enc_u < 4 ? 4 : enc_u < 6 ? 8 : 12;        // words per symbol
-        const int sym_blk = enc_u < 2 ? 8 : enc_u < 4 ? 4 : enc_u < 6 ? 2 : 1;      // symbols staged together (one rate)
+        // the task's rate: that of its first active lane
+        const uint64_t any = __ballot(n_data[0] > 0 || n_data[1] > 0);
+        const int enc_u = __builtin_amdgcn_readlane(enc_any, (int)__builtin_ctzll(any));
+        const int nd_u = ndbps_of(enc_u);
+        const int nw_u = words_per_sym(enc_u);
+        const int sym_blk = enc_u < 2 ? 8 : enc_u < 4 ? 4 : enc_u < 6 ? 2 : 1;      // symbols staged together
         const int n_ld = enc_u < 6 ? 16 : 12;                                       // = sym_blk * nw_u words
 
         // ---- phase 2: add-compare-select ----
@@ -331,8 +293,7 @@ void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict_
 #pragma unroll
         for (int s = 0; s < 64; s++) pm[s] = (s == 0) ? 0u : WR_DEC_START_PENALTY;
         int best[2] = { 0, 0 };                         // final states, taken when the frames end
-        int tt_u = 0, sym_u = 0, since_norm = 0;        // wave-uniform: step within the symbol, symbol (one rate), steps since the minimum left
-        uint32_t pos[2] = { 0u, 0u };                   // mixed rates, per lane and half: symbol << 8 | step within the symbol
+        int tt_u = 0, sym_u = 0, since_norm = 0;        // wave-uniform: step within the symbol, symbol, steps since the minimum left
         for (int tg = 0; tg < n_max; tg += 6) {
             if (since_norm == WR_DEC_NORM_STEPS) {
                 // subtract the common minimum of each frame (register phase 0 here; decisions see differences only)
@@ -344,112 +305,68 @@ void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict_
                 for (int s = 0; s < 64; s++) pm[s] = pk_sub(pm[s], mn);
             }
             since_norm += 6;
-            // ---- a new OFDM symbol: its bit-plane words, global -> lane-private LDS ----
-            if (!MIXED) {
-                // 16 words (64 bytes: a whole memory segment) per frame at a time = 8 / 4 / 2 symbols at 1 / 2 / 4 bits per
-                // carrier; 12 words = one symbol at 6
-                if (tt_u == nd_u) { tt_u = 0; sym_u++; }
-                if (tt_u == 0 && (sym_u & (sym_blk - 1)) == 0) {
-                    const bool okA = tg < n_data[0], okB = tg < n_data[1];
-                    const uint32_t* pa = rowA + (uint32_t)(sym_u * nw_u);
-                    const uint32_t* pb = rowB + (uint32_t)(sym_u * nw_u);
-                    const uint32_t room = hb_stride - (uint32_t)(sym_u * nw_u);      // words left in a frame's row
+            // ---- a new block of OFDM symbols: its bit-plane words, global -> lane-private LDS.  16 words (64 bytes: a whole
+            //      memory segment) per frame at a time = 8 / 4 / 2 symbols at 1 / 2 / 4 bits per carrier; 12 words = one
+            //      symbol at 6 ----
+            if (tt_u == nd_u) { tt_u = 0; sym_u++; }
+            if (tt_u == 0 && (sym_u & (sym_blk - 1)) == 0) {
+                const bool okA = tg < n_data[0], okB = tg < n_data[1];
+                const uint32_t* pa = rowA + (uint32_t)(sym_u * nw_u);
+                const uint32_t* pb = rowB + (uint32_t)(sym_u * nw_u);
+                const uint32_t room = hb_stride - (uint32_t)(sym_u * nw_u);      // words left in a frame's row
 #pragma unroll
-                    for (int k = 0; k < 16; k += 4) {
-                        if (k < n_ld) {
-                            uint4 a = make_uint4(0u, 0u, 0u, 0u), b = make_uint4(0u, 0u, 0u, 0u);
-                            if (okA && (uint32_t)k + 4 <= room) a = *reinterpret_cast<const uint4*>(pa + k);
-                            if (okB && (uint32_t)k + 4 <= room) b = *reinterpret_cast<const uint4*>(pb + k);
-                            uint32_t* d = symw + 2 * k * 64;
-                            d[0 * 64] = (a.x & 0xffffu) | (b.x << 16);  d[1 * 64] = (a.x >> 16) | (b.x & 0xffff0000u);
-                            d[2 * 64] = (a.y & 0xffffu) | (b.y << 16);  d[3 * 64] = (a.y >> 16) | (b.y & 0xffff0000u);
-                            d[4 * 64] = (a.z & 0xffffu) | (b.z << 16);  d[5 * 64] = (a.z >> 16) | (b.z & 0xffff0000u);
-                            d[6 * 64] = (a.w & 0xffffu) | (b.w << 16);  d[7 * 64] = (a.w >> 16) | (b.w & 0xffff0000u);
-                        }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const int nd = ndbps_tab[enc[h]];
-                    if ((int)(pos[h] & 0xffu) == nd) pos[h] = (pos[h] & ~0xffu) + 0x100u;
-                    if ((pos[h] & 0xffu) == 0u && tg < n_data[h]) {
-                        const int nw = enc[h] < 2 ? 2 : enc[h] < 4 ? 4 : enc[h] < 6 ? 8 : 12;
-                        const uint32_t* ps = (h ? rowB : rowA) + (pos[h] >> 8) * (uint32_t)nw;
-                        for (int k = 0; k < nw; k++) symw[(12 * h + k) * 64] = ps[k];
+                for (int k = 0; k < 16; k += 4) {
+                    if (k < n_ld) {
+                        uint4 a = make_uint4(0u, 0u, 0u, 0u), b = make_uint4(0u, 0u, 0u, 0u);
+                        if (okA && (uint32_t)k + 4 <= room) a = *reinterpret_cast<const uint4*>(pa + k);
+                        if (okB && (uint32_t)k + 4 <= room) b = *reinterpret_cast<const uint4*>(pb + k);
+                        uint32_t* d = symw + 2 * k * 64;
+                        d[0 * 64] = (a.x & 0xffffu) | (b.x << 16);  d[1 * 64] = (a.x >> 16) | (b.x & 0xffff0000u);
+                        d[2 * 64] = (a.y & 0xffffu) | (b.y << 16);  d[3 * 64] = (a.y >> 16) | (b.y & 0xffff0000u);
+                        d[4 * 64] = (a.z & 0xffffu) | (b.z << 16);  d[5 * 64] = (a.z >> 16) | (b.z & 0xffff0000u);
+                        d[6 * 64] = (a.w & 0xffffu) | (b.w << 16);  d[7 * 64] = (a.w >> 16) | (b.w & 0xffff0000u);
                     }
                 }
             }
             const bool mine0 = tg < n_data[0], mine1 = tg < n_data[1];
-            // one trellis step: the coded bits A, B of both frames (ta, tb: frame A in bit 0, frame B in bit 16) and
-            // whether they were transmitted (va, vb)
-#define WR_ACS(P, ta, tb, va, vb)                                                                         \
-                    {                                                                                     \
-                        const uint32_t nv = (va) + (vb);      /* a set bit implies its valid bit */       \
-                        uint32_t M[2][2];                                                                 \
-                        M[0][0] = (ta) + (tb);                                                            \
-                        M[0][1] = (ta) + (vb) - (tb);                                                     \
-                        M[1][1] = nv - M[0][0];                                                           \
-                        M[1][0] = nv - M[0][1];                                                           \
-                        uint32_t acc[4];                                                                  \
-                        acs_step<P>(pm, M, acc);                                                          \
-                        *reinterpret_cast<uint4*>(surv + ((size_t)(tg + P) * 64 + lane) * 4) =            \
-                            make_uint4(acc[0], acc[1], acc[2], acc[3]);                                   \
-                    }
-            if (!MIXED) {
-                // Three steps at a time: their six rows (A and B of each step) are read together, rows and bit positions
-                // from the scalar unit; a punctured position reads plane 0 and is masked away (no branches).
-                const uint32_t* te = WR_SRC_TABLE.e + (enc_u * WR_DEC_TAB_STRIDE + tt_u);      // wave-uniform: scalar loads
-                const uint32_t blk_lds = sym_lds + (uint32_t)((sym_u & (sym_blk - 1)) * nw_u) * 512u;      // this symbol's rows
-                uint32_t e[6];
+            // Three steps at a time: their six rows (A and B of each step) are read together, rows and bit positions from the
+            // scalar unit; a punctured position reads plane 0 and is masked away (no branches).
+            const uint32_t* te = WR_SRC_TABLE.e + (enc_u * RATE_TAB_STRIDE + tt_u);      // wave-uniform: scalar loads
+            const uint32_t blk_lds = sym_lds + (uint32_t)((sym_u & (sym_blk - 1)) * nw_u) * 512u;      // this symbol's rows
+            uint32_t e[6];
 #pragma unroll
-                for (int P = 0; P < 6; P++) e[P] = te[P];
+            for (int P = 0; P < 6; P++) e[P] = te[P];
 #define WR_FETCH3(Q)                                                                                      \
-                uint32_t rr##Q[6], ww##Q[6];                                                              \
-                _Pragma("unroll") for (int k = 0; k < 3; k++) {                                           \
-                    rr##Q[k] = blk_lds + ((e[Q + k] << 4) & 0x1f00u);      /* plane p = bits 4..8 of the half: row p, 256 bytes each */ \
-                    rr##Q[3 + k] = blk_lds + ((e[Q + k] >> 12) & 0x1f00u);                                \
-                }                                                                                         \
-                lds_rows6(rr##Q, ww##Q);
+            uint32_t rr##Q[6], ww##Q[6];                                                                  \
+            _Pragma("unroll") for (int k = 0; k < 3; k++) {                                               \
+                rr##Q[k] = blk_lds + ((e[Q + k] << 4) & 0x1f00u);      /* plane p = bits 4..8 of the half: row p, 256 bytes each */ \
+                rr##Q[3 + k] = blk_lds + ((e[Q + k] >> 12) & 0x1f00u);                                    \
+            }                                                                                             \
+            lds_rows6(rr##Q, ww##Q);
+// one trellis step: the coded bits A, B of both frames (ta, tb: frame A in bit 0, frame B in bit 16) and whether they were
+// transmitted (va, vb)
 #define WR_ACS_U(P, Q)                                                                                    \
-                {                                                                                         \
-                    const uint32_t ea = e[P] & 0xffffu, eb = e[P] >> 16;                                  \
-                    const uint32_t va = k1 & (((ea >> 9) & 1u) - 1u), vb = k1 & (((eb >> 9) & 1u) - 1u);  \
-                    const uint32_t ta = (ww##Q[P - Q] >> (ea & 15u)) & va, tb = (ww##Q[3 + P - Q] >> (eb & 15u)) & vb; \
-                    WR_ACS(P, ta, tb, va, vb)                                                             \
-                }
-                if (mine0 || mine1) {
-                    { WR_FETCH3(0)  WR_ACS_U(0, 0) WR_ACS_U(1, 0) WR_ACS_U(2, 0) }
-                    { WR_FETCH3(3)  WR_ACS_U(3, 3) WR_ACS_U(4, 3) WR_ACS_U(5, 3) }
-                }
+            {                                                                                             \
+                const uint32_t ea = e[P] & 0xffffu, eb = e[P] >> 16;                                      \
+                const uint32_t va = k1 & (((ea >> 9) & 1u) - 1u), vb = k1 & (((eb >> 9) & 1u) - 1u);      \
+                const uint32_t ta = (ww##Q[P - Q] >> (ea & 15u)) & va, tb = (ww##Q[3 + P - Q] >> (eb & 15u)) & vb; \
+                const uint32_t nv = va + vb;      /* a set bit implies its valid bit */                   \
+                uint32_t M[2][2];                                                                         \
+                M[0][0] = ta + tb;                                                                        \
+                M[0][1] = ta + vb - tb;                                                                   \
+                M[1][1] = nv - M[0][0];                                                                   \
+                M[1][0] = nv - M[0][1];                                                                   \
+                uint32_t acc[4];                                                                          \
+                acs_step<P>(pm, M, acc);                                                                  \
+                *reinterpret_cast<uint4*>(surv + ((size_t)(tg + P) * 64 + lane) * 4) =                    \
+                    make_uint4(acc[0], acc[1], acc[2], acc[3]);                                           \
+            }
+            if (mine0 || mine1) {
+                { WR_FETCH3(0)  WR_ACS_U(0, 0) WR_ACS_U(1, 0) WR_ACS_U(2, 0) }
+                { WR_FETCH3(3)  WR_ACS_U(3, 3) WR_ACS_U(4, 3) WR_ACS_U(5, 3) }
+            }
 #undef WR_ACS_U
 #undef WR_FETCH3
-            } else {
-                // six steps of coded bits: pw[0] / pw[2] = bits A / B (step P of frame A in bit P, of frame B in bit 16 + P),
-                // pw[1] / pw[3] = whether they were transmitted
-                uint32_t pw[4] = { 0u, 0u, 0u, 0u };
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const uint32_t* te = src_tab + enc[h] * WR_DEC_TAB_STRIDE + (int)(pos[h] & 0xffu);
-                    const uint32_t* sw = symw + 12 * h * 64;
-#pragma unroll
-                    for (int P = 0; P < 6; P++) {
-                        const uint32_t e = te[P];
-                        const uint32_t ea = e & 0xffffu, eb = e >> 16;
-                        const uint32_t va = ((ea >> 9) & 1u) ^ 1u, vb = ((eb >> 9) & 1u) ^ 1u;
-                        pw[0] |= ((sw[((ea >> 5) & 15u) * 64] >> (ea & 31u)) & va) << (16 * h + P);
-                        pw[1] |= va << (16 * h + P);
-                        pw[2] |= ((sw[((eb >> 5) & 15u) * 64] >> (eb & 31u)) & vb) << (16 * h + P);
-                        pw[3] |= vb << (16 * h + P);
-                    }
-                }
-                if (mine0 || mine1) {
-#define WR_ACS_M(P) WR_ACS(P, (pw[0] >> P) & k1, (pw[2] >> P) & k1, (pw[1] >> P) & k1, (pw[3] >> P) & k1)
-                    WR_ACS_M(0) WR_ACS_M(1) WR_ACS_M(2) WR_ACS_M(3) WR_ACS_M(4) WR_ACS_M(5)
-#undef WR_ACS_M
-                }
-            }
-#undef WR_ACS
             {
                 const bool end0 = mine0 && tg + 6 == n_data[0], end1 = mine1 && tg + 6 == n_data[1];
                 if (__any(end0 || end1)) {
@@ -467,7 +384,6 @@ void decode_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restrict_
                 }
             }
             tt_u += 6;
-            if (MIXED) { pos[0] += 6u; pos[1] += 6u; }
         }
         __threadfence_block();
         // ---- traceback of both frames: 32 decoded bits per word, words stored [word][A/B][lane].  The survivor
@@ -774,14 +690,13 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
     if (wave >= n_waves_total) return;
     uint32_t* symw = sym_all[wv] + lane;
     const uint32_t sym_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)sym_all[wv]);
-    const size_t n_data_cap = n_steps_cap;
-    // scratch of the wave: [step][lane][8 words] of survivor bits + [word][h][lane] of decoded bits (SPEC: + [boundary][lane]
-    // the start states of the speculative walks, a byte per frame)
-    uint32_t* const surv = reinterpret_cast<uint32_t*>(scratch + (size_t)wave * scratch_stride);
+    // scratch of the wave (layout: wr_kernels.h): [step][lane][8 words] of survivor bits, [word][h][lane] of decoded bits, (SPEC)
+    // [boundary][lane] the start states of the speculative walks
+    uint8_t* const slice = scratch + (size_t)wave * scratch_stride;
+    uint32_t* const surv = reinterpret_cast<uint32_t*>(slice);
     const uint32_t k1 = 0x01010101u;
     uint32_t sel0 = 0x03020100u;                      // v_perm_b32 selector "every byte from the second source", kept in a register
     asm volatile("" : "+v"(sel0));
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
     const uint32_t hb_stride = max_sym * 12;
 
     const uint32_t n_tasks = (n_virtual + frames_per_wave - 1) / frames_per_wave;
@@ -814,14 +729,14 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
         // the task's rate (every frame of a task shares it: the caller groups by rate)
         const uint64_t any = __ballot(n_data[0] > 0 || n_data[1] > 0 || n_data[2] > 0 || n_data[3] > 0);
         const int enc_u = __builtin_amdgcn_readlane(enc_any, (int)__builtin_ctzll(any));
-        const int nd_u = ndbps_tab[enc_u];
-        const int nw_u = enc_u < 2 ? 2 : enc_u < 4 ? 4 : enc_u < 6 ? 8 : 12;        // words per symbol
+        const int nd_u = ndbps_of(enc_u);
+        const int nw_u = words_per_sym(enc_u);
         const int blk_w = enc_u < 6 ? 8 : 12;                                       // words staged together: 4 / 2 / 1 / 1 symbols
         if (ROWS < 48 && enc_u >= 6) continue;                                      // (the host launches the 48-row instance when 64-QAM frames exist)
         const int sym_blk = blk_w / nw_u;
 
-        uint32_t* dbits = surv + n_data_cap * 512;
-        uint32_t* rec = dbits + (n_data_cap / 32 + 2) * 256;         // SPEC only (the host sized the slice for it)
+        uint32_t* dbits = reinterpret_cast<uint32_t*>(slice + dec_q_dbits_at(n_steps_cap));
+        uint32_t* rec = reinterpret_cast<uint32_t*>(slice + dec_q_rec_at(n_steps_cap));      // SPEC only (the host sized the slice for it)
         uint32_t pm[64];
         int best[4] = { 0, 0, 0, 0 };
         int tt_u = 0, sym_u = 0, since_norm = 0;
@@ -871,7 +786,7 @@ void decode_q_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __restric
             const bool mine = tg < n_data[0] || tg < n_data[1] || tg < n_data[2] || tg < n_data[3];
             // six steps: their coded bits A, B of the four frames as bytes (1 = a one was received), and whether the
             // position was transmitted at all (wave-uniform: one rate)
-            const uint32_t* te = WR_SRC_TABLE.e + (enc_u * WR_DEC_TAB_STRIDE + tt_u);
+            const uint32_t* te = WR_SRC_TABLE.e + (enc_u * RATE_TAB_STRIDE + tt_u);
             const uint32_t blk_lds = sym_lds + (uint32_t)((sym_u % sym_blk) * nw_u) * 1024u;      // this symbol's rows (4 rows of 256 B per word)
             uint32_t e[6];
 #pragma unroll
@@ -1104,7 +1019,7 @@ void decode_small_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __res
                          uint8_t* __restrict__ scratch, size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves_total)
 {
     __shared__ uint32_t tile_all[4][60 * 12];
-    __shared__ uint32_t src_tab[8 * WR_DEC_TAB_STRIDE];
+    __shared__ uint32_t src_tab[8 * RATE_TAB_STRIDE];
     copy_src_table(src_tab);
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -1112,30 +1027,28 @@ void decode_small_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __res
     const uint32_t wave = blockIdx.x * 4 + wv;
     if (wave >= n_waves_total) return;
     uint32_t* tile = tile_all[wv];
-    uint64_t* dec = reinterpret_cast<uint64_t*>(scratch + (size_t)wave * scratch_stride);     // survivor word per step
-    uint64_t* words = dec + n_steps_cap;                                                      // decoded bits, 60 per word
+    uint8_t* const slice = scratch + (size_t)wave * scratch_stride;                          // (layout: wr_kernels.h)
+    uint64_t* dec = reinterpret_cast<uint64_t*>(slice);                                       // survivor word per step
+    uint64_t* words = reinterpret_cast<uint64_t*>(slice + dec_small_words_at(n_steps_cap));   // decoded bits, 60 per word
 
     // trellis constants of state `lane`: predecessors p0 = s >> 1 and p1 = p0 | 32, input bit s & 1
     const int s = lane, u = s & 1, p0 = s >> 1, p1 = (s >> 1) | 32;
     const int f0 = (p0 << 1) | u;
     const int a0 = __builtin_popcount(f0 & 0155) & 1, b0 = __builtin_popcount(f0 & 0117) & 1;
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
     const uint32_t recip_tab[8] = { WR_RECIP32(24), WR_RECIP32(36), WR_RECIP32(48), WR_RECIP32(72),
                                     WR_RECIP32(96), WR_RECIP32(144), WR_RECIP32(192), WR_RECIP32(216) };
 
     for (uint32_t slot = wave; slot < n_slots; slot += n_waves_total) {
         const wifirx_frame fr = frames[slot];
         const int enc = fr.encoding & 7, psdu_len = fr.psdu_len;
-        const int n_dbps = ndbps_tab[enc];
-        const int n_sym = (16 + 8 * psdu_len + 6 + n_dbps - 1) / n_dbps;
-        const bool ok = (fr.flags & WIFIRX_F_COMPLETE) && psdu_len <= (int)psdu_stride && psdu_len <= WIFIRX_MAX_PSDU &&
-                        n_sym <= WIFIRX_MAX_SYM && n_sym <= (int)max_sym && (uint32_t)(n_sym * n_dbps) <= n_steps_cap;
-        if (!ok) continue;                                       // wave-uniform: one frame per wave
-        const int n_data = n_sym * n_dbps;
-        const int n_words = enc < 2 ? 2 : enc < 4 ? 4 : enc < 6 ? 8 : 12;           // bit-plane words per symbol
+        const int n_data = frame_steps(fr.flags, enc, psdu_len, psdu_stride, max_sym, n_steps_cap);
+        if (n_data == 0) continue;                               // wave-uniform: one frame per wave
+        const int n_dbps = ndbps_of(enc);
+        const int n_sym = __builtin_amdgcn_readfirstlane(n_data / n_dbps);      // (wave-uniform: the tile loop below stays unrolled)
+        const int n_words = words_per_sym(enc);                  // bit-plane words per symbol
         const uint32_t* fhb = hbits_all + (size_t)slot * max_sym * 12;
         const uint32_t recip = recip_tab[enc];
-        const uint32_t* tab_enc = src_tab + enc * WR_DEC_TAB_STRIDE;
+        const uint32_t* tab_enc = src_tab + enc * RATE_TAB_STRIDE;
 
         // ---- add-compare-select: tiles of 60 symbols, chunks of 60 trellis steps ----
         int pm = (s == 0) ? 0 : (1 << 24);
@@ -1237,13 +1150,12 @@ void decode_small_kernel(uint32_t n_slots, uint32_t max_sym, wifirx_frame* __res
     }
 }
 
-// longest trellis (in steps) among the frames decode_kernel would accept -> out[0]; how many of them there are per
-// rate -> out[1 + enc]
+// longest trellis (in steps) among the frames decode_mac accepts (frame_steps without a cap) -> out[0]; how many of them
+// there are per rate -> out[1 + enc]
 __global__ __launch_bounds__(256)
 void decode_maxsteps_kernel(uint32_t n_slots, uint32_t max_sym, const wifirx_frame* __restrict__ frames,
                             uint32_t psdu_stride, uint32_t* __restrict__ out)
 {
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
     uint32_t best = 0;
     uint32_t cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };          // wave-uniform (counted by ballot)
     const uint32_t n_round = (n_slots + 63u) & ~63u;         // whole waves walk the loop: the ballots need every lane
@@ -1251,11 +1163,8 @@ void decode_maxsteps_kernel(uint32_t n_slots, uint32_t max_sym, const wifirx_fra
         int enc = -1;
         if (i < n_slots) {
             const wifirx_frame fr = frames[i];
-            const int nd = ndbps_tab[fr.encoding & 7], len = fr.psdu_len;
-            const int n_sym = (16 + 8 * len + 6 + nd - 1) / nd;
-            if ((fr.flags & WIFIRX_F_COMPLETE) && len <= (int)psdu_stride && len <= WIFIRX_MAX_PSDU &&
-                n_sym <= WIFIRX_MAX_SYM && n_sym <= (int)max_sym) {
-                uint32_t v = (uint32_t)(n_sym * nd);
+            const uint32_t v = (uint32_t)frame_steps(fr.flags, fr.encoding & 7, fr.psdu_len, psdu_stride, max_sym, 0xffffffffu);
+            if (v) {
                 best = v > best ? v : best;
                 enc = fr.encoding & 7;
             }
@@ -1277,25 +1186,20 @@ void decode_maxsteps_kernel(uint32_t n_slots, uint32_t max_sym, const wifirx_fra
 
 // The decodable frames of a batch grouped by rate: perm[start[enc] + k] = slot of the k-th such frame found (the order
 // inside a run is whatever the atomics make it -- which frames share a wave does not change any frame's result).  The
-// runs start on task boundaries (start[] from the host), so every task of decode_kernel is of one rate; entries between
-// the runs stay 0xffffffff (set by the caller).
+// runs start on task boundaries (start[] from the host), so every task of the throughput kernels is of one rate; entries
+// between the runs stay 0xffffffff (set by the caller).
 struct PermStarts { uint32_t s[8]; };
 __global__ __launch_bounds__(256)
 void decode_perm_kernel(uint32_t n_slots, uint32_t max_sym, const wifirx_frame* __restrict__ frames, uint32_t psdu_stride,
                         PermStarts start, uint32_t* __restrict__ cursor, uint32_t* __restrict__ perm)
 {
-    const int ndbps_tab[8] = { 24, 36, 48, 72, 96, 144, 192, 216 };
     const int lane = threadIdx.x & 63;
     const uint32_t n_round = (n_slots + 63u) & ~63u;         // whole waves walk the loop: the ballots need every lane
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += gridDim.x * blockDim.x) {
         int enc = -1;
         if (i < n_slots) {
             const wifirx_frame fr = frames[i];
-            const int e = fr.encoding & 7, nd = ndbps_tab[e], len = fr.psdu_len;
-            const int n_sym = (16 + 8 * len + 6 + nd - 1) / nd;
-            if ((fr.flags & WIFIRX_F_COMPLETE) && len <= (int)psdu_stride && len <= WIFIRX_MAX_PSDU &&
-                n_sym <= WIFIRX_MAX_SYM && n_sym <= (int)max_sym)
-                enc = e;
+            if (frame_steps(fr.flags, fr.encoding & 7, fr.psdu_len, psdu_stride, max_sym, 0xffffffffu)) enc = fr.encoding & 7;
         }
         // one atomic per wave and rate (a million lanes adding to eight counters would queue up behind each other); the
         // frames of a wave keep their order inside the run
@@ -1341,14 +1245,8 @@ extern "C" hipError_t wr_launch_decode(hipStream_t st, uint32_t n_slots, uint32_
 {
     if (n_slots == 0 || n_waves == 0) return hipSuccess;
     if (!perm) n_virtual = n_slots;
-    // the tasks with one rate, then those with several (each kernel skips the other's; the scratch is shared).  With a
-    // permutation every task is of one rate and the second kernel has nothing to do.
-    uint32_t blocks = (n_waves + 3) / 4;
-    hipLaunchKernelGGL(wr::decode_kernel<false>, dim3(blocks), dim3(256), 0, st, n_slots, max_sym, frames, hbits, psdu,
+    hipLaunchKernelGGL(wr::decode_kernel, dim3((n_waves + 3) / 4), dim3(256), 0, st, n_slots, max_sym, frames, hbits, psdu,
                        psdu_stride, scratch, scratch_stride, n_steps_cap, n_waves, frames_per_wave, perm, n_virtual);
-    if (!perm)
-        hipLaunchKernelGGL(wr::decode_kernel<true>, dim3(blocks), dim3(256), 0, st, n_slots, max_sym, frames, hbits, psdu,
-                           psdu_stride, scratch, scratch_stride, n_steps_cap, n_waves, frames_per_wave, perm, n_virtual);
     return hipGetLastError();
 }
 
@@ -1357,8 +1255,7 @@ extern "C" hipError_t wr_launch_decode_q(hipStream_t st, uint32_t n_slots, uint3
                                          size_t scratch_stride, uint32_t n_steps_cap, uint32_t n_waves, uint32_t frames_per_wave,
                                          const uint32_t* perm, uint32_t n_virtual, int has_64qam, int mode)
 {
-    // mode: 0 = trace-back behind the task, 2 = speculative walks under the task's own add-compare-select (slice + (n_steps_cap / 96
-    // + 2) x 256 bytes of start states)
+    // mode: 0 = trace-back behind the task, 2 = speculative walks under the task's own add-compare-select (slice: dec_q_slice)
     if (n_slots == 0 || n_waves == 0) return hipSuccess;
     if (!perm) n_virtual = n_slots;
 #define WR_LAUNCH_Q(ROWS, MODE) hipLaunchKernelGGL((wr::decode_q_kernel<ROWS, MODE>), dim3((n_waves + 3) / 4), dim3(256), 0, st, n_slots, max_sym, \

@@ -34,46 +34,18 @@ namespace soft {
 
 #define WR_SOFT_NORM_STEPS 24          // the common minimum leaves the metrics before every step t > 0, t % 24 == 0
 #define WR_SOFT_PUNCT 0xffffu          // table entry of a coded bit the transmitter dropped
-#define WR_SOFT_TAB_STRIDE 216         // steps per OFDM symbol at the highest rate
 
 // [enc][step of the symbol]: the LLR index (coded_index: carrier * n_bpsc + bit) of coded bit A | that of B << 16
-struct SoftTable { uint32_t e[8 * WR_SOFT_TAB_STRIDE]; };
-constexpr uint32_t llr_of_coded(int punct, int n_bpsc, int ci)
-{
-    const int j = coded_index(punct, n_bpsc, ci);
-    return j < 0 ? WR_SOFT_PUNCT : (uint32_t)j;
-}
-constexpr SoftTable make_soft_table()
-{
-    SoftTable t{};
-    for (int enc = 0; enc < 8; enc++)
-        for (int tt = 0; tt < WR_SOFT_TAB_STRIDE; tt++) {
-            uint32_t v = WR_SOFT_PUNCT | (WR_SOFT_PUNCT << 16);
-            if (tt < RATE_NDBPS[enc])
-                v = llr_of_coded(RATE_PUNCT[enc], RATE_NBPSC[enc], 2 * tt) | (llr_of_coded(RATE_PUNCT[enc], RATE_NBPSC[enc], 2 * tt + 1) << 16);
-            t.e[enc * WR_SOFT_TAB_STRIDE + tt] = v;
-        }
-    return t;
-}
-__constant__ const SoftTable WR_SOFT_TABLE = make_soft_table();
-
-constexpr __host__ __device__ int nbpsc_of(int enc) { return enc < 2 ? 1 : enc < 4 ? 2 : enc < 6 ? 4 : 6; }
-constexpr __host__ __device__ int ndbps_of(int enc)      // (a select chain: a local table would live in scratch memory)
-{
-    return enc == 0 ? 24 : enc == 1 ? 36 : enc == 2 ? 48 : enc == 3 ? 72 : enc == 4 ? 96 : enc == 5 ? 144 : enc == 6 ? 192 : 216;
-}
+constexpr uint32_t llr_of_coded(int, int j) { return j < 0 ? WR_SOFT_PUNCT : (uint32_t)j; }
+__constant__ const RateTable WR_SOFT_TABLE = make_rate_table(llr_of_coded);
 
 // trellis steps of a frame the soft decoder takes (the hard decoder's rule, WIFIRX_F_LLR, and LLR rows wide enough for
 // the rate), 0 for a frame it leaves alone
-__device__ __forceinline__ int frame_steps(uint32_t flags, int enc, int len, uint32_t psdu_stride, uint32_t max_sym,
-                                           uint32_t llr_bits, uint32_t n_steps_cap)
+__device__ __forceinline__ int soft_frame_steps(uint32_t flags, int enc, int len, uint32_t psdu_stride, uint32_t max_sym,
+                                                uint32_t llr_bits, uint32_t n_steps_cap)
 {
-    const int n_dbps = ndbps_of(enc & 7);
-    const int n_sym = (16 + 8 * len + 6 + n_dbps - 1) / n_dbps;
-    const bool ok = (flags & WIFIRX_F_COMPLETE) && (flags & WIFIRX_F_LLR) && (uint32_t)nbpsc_of(enc & 7) <= llr_bits &&
-                    len <= (int)psdu_stride && len <= WIFIRX_MAX_PSDU && n_sym <= WIFIRX_MAX_SYM && n_sym <= (int)max_sym &&
-                    (uint32_t)(n_sym * n_dbps) <= n_steps_cap;
-    return ok ? n_sym * n_dbps : 0;
+    if (!(flags & WIFIRX_F_LLR) || (uint32_t)nbpsc_of(enc & 7) > llr_bits) return 0;
+    return frame_steps(flags, enc, len, psdu_stride, max_sym, n_steps_cap);
 }
 
 // One state of the add-compare-select: m = (c1 < c0) ? c1 : c0, and the decision (c1 < c0) shifted into acc from below.
@@ -124,8 +96,9 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
     const int lane = threadIdx.x;
     const uint32_t wave = blockIdx.x;
     row_t* roww = rows + lane;
-    uint32_t* surv = reinterpret_cast<uint32_t*>(scratch + (size_t)wave * scratch_stride);      // [step][lane][2]
-    uint32_t* dbits = surv + (size_t)n_steps_cap * 128;                                         // [word][lane]
+    uint8_t* const slice = scratch + (size_t)wave * scratch_stride;                              // (layout: wr_kernels.h)
+    uint32_t* surv = reinterpret_cast<uint32_t*>(slice);                                         // [step][lane][2]
+    uint32_t* dbits = reinterpret_cast<uint32_t*>(slice + dec_soft_dbits_at(n_steps_cap));       // [word][lane]
     const size_t row_stride = (size_t)max_sym * 48 * llr_bits;      // values per frame
 
     for (uint32_t task = task_lo + wave; task < task_hi; task += n_waves_total) {
@@ -135,7 +108,7 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
         int n_data = 0, enc = 0;
         if (slot < n_slots) {
             enc = frames[slot].encoding & 7;
-            n_data = frame_steps(frames[slot].flags, enc, frames[slot].psdu_len, psdu_stride, max_sym, llr_bits, n_steps_cap);
+            n_data = soft_frame_steps(frames[slot].flags, enc, frames[slot].psdu_len, psdu_stride, max_sym, llr_bits, n_steps_cap);
         } else {
             slot = 0;
         }
@@ -212,7 +185,7 @@ void decode_soft_kernel(uint32_t n_slots, uint32_t max_sym, uint32_t llr_bits, w
                     }
                 }
             }
-            const uint32_t* te = WR_SOFT_TABLE.e + (enc_u * WR_SOFT_TAB_STRIDE + tt_u);      // wave-uniform: scalar loads
+            const uint32_t* te = WR_SOFT_TABLE.e + (enc_u * RATE_TAB_STRIDE + tt_u);      // wave-uniform: scalar loads
 // an LLR as the trellis reads it: float32 rows as they are, bf16 rows widened (exactly: the 16 bits above 16 zero bits)
 #define WR_SOFT_ROW(v) (BF ? __uint_as_float((uint32_t)(v) << 16) : (v))
 #define WR_SOFT_STEP(P)                                                                                   \

@@ -16,11 +16,9 @@
 #endif
 #define WR_STREAM_SPAN     16       // tiles of 64 samples one wave scans in stream-mode detection
 #define WR_DECODE_MAX_WAVES 4096    // waves of the decode kernel (grid-stride; each owns a scratch slice)
-#ifndef WR_DQ_SPEC_WAVES
 #define WR_DQ_SPEC_WAVES 3          // decode_q_kernel with the speculative trace-back (rates up to 16-QAM): waves per SIMD.  3 = 168 registers,
                                     // 62 spilled but 9 accesses inside the group loop of 6 300 instructions: 12.6 -> 11.45 ms per million frames
                                     // (2: 231 registers, no spill; 4: 128 registers, 202 spilled, 14.7 ms) -- profiles/r05_ab_decode_waves.txt
-#endif
 #define WR_DECODE_SMALL_MAX 16384      // batches up to this many frames take the wave-per-frame decode kernel
 #define WR_DECODE_FRAMES_PER_WAVE 128   // two frames per lane: packed 16-bit path metrics
 #define WR_DECODE_Q_FRAMES_PER_WAVE 256 // four frames per lane: byte path metrics (decode_q_kernel)
@@ -50,6 +48,24 @@ struct DemodOut {
     float4*       sym_stats;    // per frame: sum |y|, sum |y|^2, sum |y|^4 over its equalised data symbols, 0
     uint32_t*     hbits;        // the decisions as bit planes, max_sym * 12 words per frame (wifirx_out.hbits)
 };
+
+// The survivor-scratch slice of one decode wave, for trellises of up to n steps: its size and the byte offsets of its parts.
+// The host sizes the slices with these, the kernels find their parts with them.  Decoded words come with two spare words
+// per frame (finish_frame reads one word ahead).
+// decode_small_kernel (one frame per wave): a 64-bit survivor word per step, then the decoded words (60 bits in 64)
+constexpr __host__ __device__ size_t dec_small_words_at(size_t n) { return n * 8; }
+constexpr __host__ __device__ size_t dec_small_slice(size_t n) { return dec_small_words_at(n) + (n / 60 + 4) * 8; }
+// decode_kernel (two frames per lane): [step][lane] 16 B of survivor bits, then [word][A/B][lane] decoded words
+constexpr __host__ __device__ size_t dec_pair_dbits_at(size_t n) { return n * 64 * 16; }
+constexpr __host__ __device__ size_t dec_pair_slice(size_t n) { return dec_pair_dbits_at(n) + (n / 32 + 2) * 128 * 4; }
+// decode_q_kernel (four frames per lane): [step][lane] 32 B of survivor bits, then [word][h][lane] decoded words, then with
+// MODE 2 [boundary][lane] the start states of the speculative walks (a byte per frame)
+constexpr __host__ __device__ size_t dec_q_dbits_at(size_t n) { return n * 64 * 32; }
+constexpr __host__ __device__ size_t dec_q_rec_at(size_t n) { return dec_q_dbits_at(n) + (n / 32 + 2) * 256 * 4; }
+constexpr __host__ __device__ size_t dec_q_slice(size_t n, bool spec) { return dec_q_rec_at(n) + (spec ? (n / 96 + 2) * 64 * 4 : 0); }
+// decode_soft_kernel (one frame per lane): [step][lane] 8 B of survivor bits, then [word][lane] decoded words
+constexpr __host__ __device__ size_t dec_soft_dbits_at(size_t n) { return n * 64 * 8; }
+constexpr __host__ __device__ size_t dec_soft_slice(size_t n) { return dec_soft_dbits_at(n) + (n / 32 + 2) * 64 * 4; }
 
 // one detected frame of a continuous stream (stream mode)
 struct StreamTrig {

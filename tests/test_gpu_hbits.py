@@ -81,7 +81,7 @@ def _mixed_batch(seed=5):
 
 
 def test_planes_mixed_rates_and_decode_from_planes_only(capi, orc, monkeypatch):
-    """one wave of the throughput decoder holds frames of all rates (the per-lane look-up path): planes on the device,
+    """a batch of all rates reaches the throughput decoder grouped by rate (every task of one rate): planes on the device,
     no `idx` buffer at all"""
     monkeypatch.setenv("WIFIRX_DECODE_SMALL_MAX", "0")
     monkeypatch.setenv("WIFIRX_DECODE_FPW", "128")

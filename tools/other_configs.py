@@ -61,7 +61,7 @@ def main():
     if only is not None:
         print(json.dumps({"cases": res, "equalisers": []}))
         return
-    # several rates in one batch (decode_mac's per-lane look-up kernel): QPSK-1/2 and 16-QAM-3/4 frames alternate
+    # several rates in one batch (decode_mac groups the frames by rate): QPSK-1/2 and 16-QAM-3/4 frames alternate
     if not os.environ.get("WIFIRX_ONLY_EQ"):
         plen, slot_len = 294, 4608
         ta = txgen.encode_psdus(txgen.make_psdus(128, plen, seed=5), 2)

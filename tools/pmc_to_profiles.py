@@ -24,7 +24,7 @@ def main():
     acc = collections.defaultdict(lambda: collections.defaultdict(list))
     for f in glob.glob(src + "/p*/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            # template arguments stay in the name: demod_batch_kernel<EQ, planes> and decode_kernel<mixed> are different kernels
+            # template arguments stay in the name: demod_batch_kernel<EQ, planes> and decode_q_kernel<ROWS, MODE> name several kernels each
             acc[r["Kernel_Name"].split("(")[0].replace("void ", "").strip()][r["Counter_Name"]].append(
                 float(r["Counter_Value"]))
     with open(prefix + "_pmc_summary.csv", "w") as out:
