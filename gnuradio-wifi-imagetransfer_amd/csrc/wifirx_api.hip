@@ -16,6 +16,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <thread>
 #include <string>
 #include <vector>
@@ -38,83 +39,147 @@ struct PendingTrig {
     bool    have_cfo;
 };
 
-struct wifirx_handle {
-    wifirx_config cfg;
-    int           device = 0;
-    hipStream_t   stream = nullptr;
-    std::string   err;
-    wifirx_stats  stats{};
+namespace {
 
-    // batch staging (host-buffer path only)
-    void*  stage_iq = nullptr;      size_t stage_iq_bytes = 0;
-    void*  stage_frames = nullptr;  size_t stage_frames_bytes = 0;
-    void*  stage_idx = nullptr;     size_t stage_idx_bytes = 0;
-    void*  stage_llr = nullptr;     size_t stage_llr_bytes = 0;
-    void*  stage_car = nullptr;     size_t stage_car_bytes = 0;
-    void*  stage_psdu = nullptr;    size_t stage_psdu_bytes = 0;
-    void*  stage_csi = nullptr;     size_t stage_csi_bytes = 0;
-    void*  stage_stats = nullptr;   size_t stage_stats_bytes = 0;
-    void*  stage_hbits = nullptr;   size_t stage_hbits_bytes = 0;
-    void*  stage_off = nullptr;     size_t stage_off_bytes = 0;      // slot offsets of wifirx_demod_batch_v
-    void*  tx_psdu = nullptr;       size_t tx_psdu_bytes = 0;        // wifirx_tx_batch: host PSDUs
-    void*  tx_meta = nullptr;       size_t tx_meta_bytes = 0;        // wifirx_tx_batch: lengths, seeds, row offsets
+int oom(wifirx_handle* h, const char* what, hipError_t e);
 
-    // decode workspace
-    void*  dec_scratch = nullptr;   size_t dec_scratch_bytes = 0;
-    void*  dec_max = nullptr;       size_t dec_max_bytes = 0;
-    void*  dec_perm = nullptr;      size_t dec_perm_bytes = 0;    // decode_mac over several rates: frames grouped by rate
-    void*  dec_hbits = nullptr;     size_t dec_hbits_bytes = 0;   // decode_mac over `idx` alone: its bit planes (wifirx_out.hbits form)
-    void*  s_pack = nullptr;        size_t s_pack_bytes = 0;      // stream outputs, rows cut to their filled width
-    void*  s_host = nullptr;        size_t s_host_bytes = 0;      // pinned landing zone of the packed outputs
+// An owning device (hipMalloc) or pinned host (hipHostMalloc) allocation: freed by its destructor, moved, never copied.
+template <bool Pinned>
+struct Buffer {
+    void*  p = nullptr;
+    size_t bytes = 0;
 
-    // stream mode
-    float2*  sbuf = nullptr;        int64_t sbuf_cap = 0;     // device sample buffer
+    Buffer() = default;
+    Buffer(const Buffer&) = delete;
+    Buffer& operator=(const Buffer&) = delete;
+    Buffer(Buffer&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    Buffer& operator=(Buffer&& o) noexcept
+    {
+        if (this != &o) { reset(); std::swap(p, o.p); std::swap(bytes, o.bytes); }
+        return *this;
+    }
+    ~Buffer() { reset(); }
+
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    void reset()
+    {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        bytes = 0;
+    }
+    // exactly `n` bytes; what the buffer held is freed first, and a failure leaves it empty
+    int alloc(wifirx_handle* h, size_t n, const char* what)
+    {
+        reset();
+        hipError_t e = Pinned ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n);
+        if (e != hipSuccess) { p = nullptr; return oom(h, what, e); }
+        bytes = n;
+        return WIFIRX_OK;
+    }
+    // at least `need` bytes: a device buffer grows to exactly `need`, a pinned one to half as much again
+    int reserve(wifirx_handle* h, size_t need)
+    {
+        if (bytes >= need) return WIFIRX_OK;
+        return Pinned ? alloc(h, need + need / 2, "hipHostMalloc") : alloc(h, need, "hipMalloc");
+    }
+};
+using DevBuf = Buffer<false>;
+using PinnedBuf = Buffer<true>;
+
+// wifirx_set_param's settings beyond the wifirx_config
+struct Tunables {
+    int32_t  llr_csi = 0;                              // WIFIRX_P_LLR_CSI
+    int32_t  llr_format = WIFIRX_LLR_F32;              // WIFIRX_P_LLR_FORMAT: the LLR rows of the batch calls (stream mode keeps float32)
+    int32_t  stream_want_idx = 1;                      // WIFIRX_P_STREAM_IDX
+    int32_t  stream_soft = 0;                          // WIFIRX_P_STREAM_SOFT: stream batches decoded from LLRs (wifirx_decode_batch_soft)
+    int64_t  stream_batch = 0;                         // WIFIRX_P_STREAM_BATCH
+    uint32_t decode_small_max = WR_DECODE_SMALL_MAX;   // WIFIRX_P_DECODE_SMALL_MAX
+};
+
+// Environment overrides and test hooks, read once by wifirx_create (read_environment)
+struct Environment {
+    uint32_t decode_fpw = 0;        // WIFIRX_DECODE_FPW (tests): frames per wave of the throughput decoder
+    int      decode_ovl = -1;       // WIFIRX_DECODE_OVL (tests): 0 = trace-back behind each task, 2 = speculative walks under the task's own add-compare-select; -1: by batch size
+    int      decode_q = -1;         // WIFIRX_DECODE_Q (tests): 1 / 0 = always / never the four-frames-per-lane decoder; -1: by batch size
+    int      fail_alloc = 0, alloc_count = 0;      // WIFIRX_TEST_FAIL_ALLOC (allocation-failure tests)
+    size_t   decode_budget = 0;                    // WIFIRX_TEST_DECODE_BUDGET: bytes of survivor scratch a decode call may hold (tests)
+    int      fail_decode_scratch = 0;              // WIFIRX_TEST_FAIL_DECODE_SCRATCH: the next k scratch allocations fail (tests)
+    int      fail_carry = 0, carry_count = 0;      // WIFIRX_TEST_FAIL_CARRY (a failure behind the commit of a stream pass)
+};
+
+// batch staging (host-buffer path only)
+struct Staging {
+    DevBuf iq, frames, idx, llr, car, csi, stats, hbits;
+    DevBuf off;                     // slot offsets of wifirx_demod_batch_v
+    DevBuf tx_psdu, tx_meta;        // wifirx_tx_batch: host PSDUs; lengths, seeds, row offsets
+};
+
+// decode workspace
+struct DecodeWork {
+    DevBuf scratch, max;
+    DevBuf perm;                    // decode_mac over several rates: frames grouped by rate
+    DevBuf hbits;                   // decode_mac over `idx` alone: its bit planes (wifirx_out.hbits form)
+};
+
+// stream mode (wifirx_api_stream.inc)
+struct StreamState {
+    DevBuf   sbuf;                  // device sample buffer of sbuf_cap samples
+    DevBuf   above, A;              // the detection side buffers, sized by sbuf_cap too
+    int64_t  sbuf_cap = 0;
     int64_t  sbase = 0;             // absolute index of sbuf[0] (multiple of 64)
     int64_t  sfill = 0;             // valid samples in sbuf
     int64_t  sdetected = 0;         // absolute index up to which triggers have been selected
-    int64_t  last_trig = -(1ll << 40);
-    int64_t  stream_batch = 0;      // WIFIRX_P_STREAM_BATCH
-    uint32_t decode_small_max = WR_DECODE_SMALL_MAX;   // WIFIRX_P_DECODE_SMALL_MAX
-    uint32_t decode_fpw = 0;        // WIFIRX_DECODE_FPW (environment, tests): frames per wave of the throughput decoder
-    int      decode_ovl = -1;       // WIFIRX_DECODE_OVL (environment, tests): 0 = trace-back behind each task, 2 = speculative walks under the task's own add-compare-select; -1: by batch size
-    uint32_t n_simd = 1024;         // SIMDs of the device (4 per CU): sizes the speculative trace-back's launch
-    int      decode_q = -1;         // WIFIRX_DECODE_Q (environment, tests): 1 / 0 = always / never the four-frames-per-lane decoder; -1: by batch size
-    int32_t  llr_csi = 0;           // WIFIRX_P_LLR_CSI
-    int32_t  stream_want_idx = 1;   // WIFIRX_P_STREAM_IDX
-    int32_t  stream_soft = 0;       // WIFIRX_P_STREAM_SOFT: stream batches decoded from LLRs (wifirx_decode_batch_soft)
-    int32_t  llr_format = WIFIRX_LLR_F32;   // WIFIRX_P_LLR_FORMAT: the LLR rows of the batch calls (stream mode keeps float32)
     int64_t  sprocessed = 0;        // absolute index up to which pushes have been processed
-    uint8_t* s_above = nullptr;     float2* s_A = nullptr;    int64_t s_above_cap = 0;
+    int64_t  last_trig = -(1ll << 40);
     std::vector<PendingTrig> pending;
     std::deque<PolledFrame>  queue;
-    void*  s_trig = nullptr;  void* s_frames = nullptr;  void* s_idx = nullptr;
-    void*  s_car = nullptr;   void* s_psdu = nullptr;    uint32_t s_cap = 0;
-    void*  s_csi = nullptr;
-    void*  s_stats = nullptr;
-    void*  s_hbits = nullptr;
-    void*  s_llr = nullptr;   uint32_t s_llr_cap = 0;      // WIFIRX_P_STREAM_SOFT: LLR rows of the triggers (6 bits per carrier reserved)
-    int    test_fail_alloc = 0, test_alloc_count = 0;      // WIFIRX_TEST_FAIL_ALLOC (allocation-failure tests)
-    size_t test_decode_budget = 0;                         // WIFIRX_TEST_DECODE_BUDGET: bytes of survivor scratch a decode call may hold (tests)
-    int    test_fail_decode_scratch = 0;                   // WIFIRX_TEST_FAIL_DECODE_SCRATCH: the next k scratch allocations fail (tests)
-    int    test_fail_carry = 0, test_carry_count = 0;      // WIFIRX_TEST_FAIL_CARRY (a failure behind the commit of a stream pass)
-    bool   stream_dead = false;                            // the carry step failed after it had begun to move the sample buffer
-    std::string stream_dead_msg;
-
-    // Host-buffer stream path (what a GNU Radio work() drives; wifirx_api_stream.inc): pushes are copied into one of two
-    // pinned staging buffers of one batch each; a full one is handed to the worker thread, which runs the device
-    // pipeline for it while the caller fills the other.  `mu` guards the job slot, the frame queue and the statistics.
-    std::mutex              mu;
-    std::condition_variable cv;
-    std::thread             worker;
-    bool    w_started = false, w_stop = false, w_busy = false, w_has_job = false;
-    const float* w_job_ptr = nullptr;   size_t w_job_n = 0;   bool w_job_flush = false;
-    int     w_rc = 0;                   std::string w_err;     // first failure of a batch, reported by the next call
-    std::string w_err_local;            // the worker's own error text (only the worker writes it; h->err belongs to the caller's thread)
-    bool    w_retry = false;            // the failed batch is still staged (its ring buffer untouched): the next push / flush re-submits it
-    const float* w_retry_ptr = nullptr; size_t w_retry_n = 0;   bool w_retry_flush = false;
-    float2* ring[2] = { nullptr, nullptr };   size_t ring_cap = 0, ring_fill = 0;   int ring_cur = 0;
-    size_t  push_consumed = 0;          // wifirx_push_consumed
     std::atomic<uint32_t> n_queued{0};  // frames waiting for wifirx_poll (wifirx_queued: read without the lock)
+    DevBuf   trig, frames, idx, car, psdu, csi, stats, hbits;     // output rows of out_cap triggers
+    uint32_t out_cap = 0;
+    DevBuf   llr;                   // WIFIRX_P_STREAM_SOFT: LLR rows of the triggers (6 bits per carrier reserved)
+    DevBuf   pack;                  // stream outputs, rows cut to their filled width
+    PinnedBuf host;                 // pinned landing zone of the packed outputs
+    bool     dead = false;          // the carry step failed after it had begun to move the sample buffer
+    std::string dead_msg;
+    size_t   push_consumed = 0;     // wifirx_push_consumed
+};
+
+// A batch handed to the worker: `n` samples at `ptr` (a ring buffer), and whether it ends with a flush
+struct Job { const float* ptr; size_t n; bool flush; };
+
+// Host-buffer stream path (what a GNU Radio work() drives; wifirx_api_stream.inc): pushes are copied into one of two
+// pinned staging buffers of one batch each; a full one is handed to the worker thread, which runs the device pipeline
+// for it while the caller fills the other.  `mu` guards the job and retry slots, the frame queue, the statistics and the
+// dead flag.
+struct Worker {
+    mutable std::mutex      mu;
+    std::condition_variable cv;
+    std::thread             thread;     // joinable while the worker runs
+    bool    stop = false, busy = false;
+    std::optional<Job> job;
+    std::optional<Job> retry;           // the failed batch is still staged (its ring buffer untouched): the next push / flush re-submits it
+    int     rc = 0;                     std::string err;     // first failure of a batch, reported by the next call
+    std::string err_local;              // the worker's own error text (only the worker writes it; h->err belongs to the caller's thread)
+    PinnedBuf ring[2];                  size_t ring_cap = 0, ring_fill = 0;   int ring_cur = 0;
+};
+
+}  // namespace
+
+// Members are released by their destructors: wifirx_destroy joins the worker and makes the device current first, and
+// destroys the HIP stream after them.
+struct wifirx_handle {
+    wifirx_config cfg;
+    Tunables      tune;
+    Environment   env;
+    int           device = 0;
+    uint32_t      n_simd = 1024;    // SIMDs of the device (4 per CU): sizes the speculative trace-back's launch
+    hipStream_t   stream = nullptr;
+    std::string   err;
+    wifirx_stats  stats{};
+    Staging       stage;
+    DecodeWork    dec;
+    StreamState   st;
+    Worker        w;
 };
 
 namespace {
@@ -123,10 +188,10 @@ thread_local std::string g_err;
 thread_local bool t_is_worker = false;      // set by the handle's stream worker thread
 
 // h->err is written by the caller's thread only (one handle = calls serialised by the caller); the stream worker keeps
-// its text in w_err_local until the caller's next push / flush takes it over (stream_worker_take_error).
+// its text in w.err_local until the caller's next push / flush takes it over (stream_worker_take_error).
 int fail(wifirx_handle* h, int code, const std::string& msg)
 {
-    if (h) { if (t_is_worker) h->w_err_local = msg; else h->err = msg; }
+    if (h) { if (t_is_worker) h->w.err_local = msg; else h->err = msg; }
     g_err = msg;
     return code;
 }
@@ -147,25 +212,25 @@ int oom(wifirx_handle* h, const char* what, hipError_t e)
     return fail(h, WIFIRX_ENOMEM, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-int ensure(wifirx_handle* h, void** p, size_t* have, size_t need)
+// The environment overrides (tests, measurement); returns the stream priority WIFIRX_STREAM_PRIORITY asks for.
+int read_environment(wifirx_handle* h)
 {
-    if (*have >= need) return WIFIRX_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    hipError_t e = hipMalloc(p, need);
-    if (e != hipSuccess) return oom(h, "hipMalloc", e);
-    *have = need;
-    return WIFIRX_OK;
-}
-
-int ensure_pinned(wifirx_handle* h, void** p, size_t* have, size_t need)
-{
-    if (*have >= need) return WIFIRX_OK;
-    if (*p) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
-    need += need / 2;
-    hipError_t e = hipHostMalloc(p, need, hipHostMallocDefault);
-    if (e != hipSuccess) return oom(h, "hipHostMalloc", e);
-    *have = need;
-    return WIFIRX_OK;
+    Environment& v = h->env;
+    if (const char* e = std::getenv("WIFIRX_DECODE_SMALL_MAX")) h->tune.decode_small_max = (uint32_t)std::strtoul(e, nullptr, 10);   // tests pick the decode kernel with this
+    if (const char* e = std::getenv("WIFIRX_DECODE_FPW")) v.decode_fpw = (uint32_t)std::strtoul(e, nullptr, 10);
+    if (const char* e = std::getenv("WIFIRX_DECODE_Q")) v.decode_q = std::atoi(e) != 0;
+    if (const char* e = std::getenv("WIFIRX_DECODE_OVL")) { const int m = std::atoi(e); if (m == 0 || m == 2) v.decode_ovl = m; }
+    if (const char* e = std::getenv("WIFIRX_TEST_FAIL_ALLOC")) v.fail_alloc = std::atoi(e);
+    if (const char* e = std::getenv("WIFIRX_TEST_FAIL_CARRY")) v.fail_carry = std::atoi(e);
+    if (const char* e = std::getenv("WIFIRX_TEST_DECODE_BUDGET")) v.decode_budget = (size_t)std::strtoull(e, nullptr, 10);
+    if (const char* e = std::getenv("WIFIRX_TEST_FAIL_DECODE_SCRATCH")) v.fail_decode_scratch = std::atoi(e);
+    // WIFIRX_STREAM_PRIORITY = high | low (measurement: two handles whose kernels share the GPU, tools/coresident_probe.py)
+    int prio = 0, prio_lo = 0, prio_hi = 0;
+    if (const char* e = std::getenv("WIFIRX_STREAM_PRIORITY")) {
+        if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess) prio = e[0] == 'h' ? prio_hi : e[0] == 'l' ? prio_lo : 0;
+        else (void)hipGetLastError();
+    }
+    return prio;
 }
 
 wr::DemodParams params_of(const wifirx_handle* h)
@@ -178,7 +243,7 @@ wr::DemodParams params_of(const wifirx_handle* h)
     p.max_sym = h->cfg.max_sym;
     p.llr_bits = h->cfg.llr_bits;
     p.chan_est = h->cfg.chan_est;
-    p.llr_csi = h->llr_csi;
+    p.llr_csi = h->tune.llr_csi;
     return p;
 }
 
@@ -218,20 +283,7 @@ int wifirx_create(const wifirx_config* cfg, wifirx_handle** out)
     h->cfg = *cfg;
     h->device = cfg->device;
     h->n_simd = 4u * (uint32_t)prop.multiProcessorCount;
-    if (const char* e = std::getenv("WIFIRX_DECODE_SMALL_MAX")) h->decode_small_max = (uint32_t)std::strtoul(e, nullptr, 10);   // tests pick the decode kernel with this
-    if (const char* e = std::getenv("WIFIRX_DECODE_FPW")) h->decode_fpw = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = std::getenv("WIFIRX_DECODE_Q")) h->decode_q = std::atoi(e) != 0;
-    if (const char* e = std::getenv("WIFIRX_DECODE_OVL")) { const int m = std::atoi(e); if (m == 0 || m == 2) h->decode_ovl = m; }
-    if (const char* e = std::getenv("WIFIRX_TEST_FAIL_ALLOC")) h->test_fail_alloc = std::atoi(e);
-    if (const char* e = std::getenv("WIFIRX_TEST_FAIL_CARRY")) h->test_fail_carry = std::atoi(e);
-    if (const char* e = std::getenv("WIFIRX_TEST_DECODE_BUDGET")) h->test_decode_budget = (size_t)std::strtoull(e, nullptr, 10);
-    if (const char* e = std::getenv("WIFIRX_TEST_FAIL_DECODE_SCRATCH")) h->test_fail_decode_scratch = std::atoi(e);
-    // WIFIRX_STREAM_PRIORITY = high | low (environment; measurement: two handles whose kernels share the GPU, tools/coresident_probe.py)
-    int prio = 0, prio_lo = 0, prio_hi = 0;
-    if (const char* e = std::getenv("WIFIRX_STREAM_PRIORITY")) {
-        if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess) prio = e[0] == 'h' ? prio_hi : e[0] == 'l' ? prio_lo : 0;
-        else (void)hipGetLastError();
-    }
+    const int prio = read_environment(h);
     if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio) != hipSuccess) {
         delete h;
         return fail(nullptr, WIFIRX_EHIP, "hipStreamCreate failed");
@@ -243,23 +295,12 @@ int wifirx_create(const wifirx_config* cfg, wifirx_handle** out)
 int wifirx_destroy(wifirx_handle* h)
 {
     if (!h) return WIFIRX_EINVAL;
-    stream_worker_stop(h);
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (float2* r : h->ring) if (r) (void)hipHostFree(r);
-    void* bufs[] = { h->stage_iq, h->stage_frames, h->stage_idx, h->stage_llr, h->stage_car, h->stage_psdu, h->stage_csi, h->stage_stats, h->stage_hbits, h->stage_off, h->s_stats,
-                     h->dec_scratch, h->dec_max, h->sbuf, h->s_above, h->s_A, h->s_trig, h->s_frames, h->s_idx,
-                     h->s_car, h->s_psdu, h->s_csi, h->s_hbits };
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    if (h->s_pack) (void)hipFree(h->s_pack);
-    if (h->dec_hbits) (void)hipFree(h->dec_hbits);
-    if (h->s_llr) (void)hipFree(h->s_llr);
-    if (h->dec_perm) (void)hipFree(h->dec_perm);
-    if (h->tx_psdu) (void)hipFree(h->tx_psdu);
-    if (h->tx_meta) (void)hipFree(h->tx_meta);
-    if (h->s_host) (void)hipHostFree(h->s_host);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    stream_worker_stop(h);                  // the worker uses the buffers
+    (void)hipSetDevice(h->device);          // the buffers free themselves on the handle's device
+    hipStream_t stream = h->stream;
+    if (stream) (void)hipStreamSynchronize(stream);
     delete h;
+    if (stream) (void)hipStreamDestroy(stream);
     return WIFIRX_OK;
 }
 
@@ -286,28 +327,28 @@ int wifirx_set_param(wifirx_handle* h, int id, double value)
         h->cfg.chan_est = (int)value;
         return WIFIRX_OK;
     case WIFIRX_P_LLR_CSI:
-        h->llr_csi = value != 0;
+        h->tune.llr_csi = value != 0;
         return WIFIRX_OK;
     case WIFIRX_P_STREAM_IDX:
-        h->stream_want_idx = value != 0;
+        h->tune.stream_want_idx = value != 0;
         return WIFIRX_OK;
     case WIFIRX_P_STREAM_SOFT:
         if (value != 0 && value != 1) return fail(h, WIFIRX_EINVAL, "WIFIRX_P_STREAM_SOFT must be 0 or 1");
-        h->stream_soft = (int32_t)value;
+        h->tune.stream_soft = (int32_t)value;
         return WIFIRX_OK;
     case WIFIRX_P_LLR_FORMAT:
         if (value != WIFIRX_LLR_F32 && value != WIFIRX_LLR_BF16)
             return fail(h, WIFIRX_EINVAL, "WIFIRX_P_LLR_FORMAT must be WIFIRX_LLR_F32 (0) or WIFIRX_LLR_BF16 (1)");
-        h->llr_format = (int32_t)value;
+        h->tune.llr_format = (int32_t)value;
         return WIFIRX_OK;
     case WIFIRX_P_DECODE_SMALL_MAX:
         if (!(value >= 0) || value > 4e9) return fail(h, WIFIRX_EINVAL, "decode threshold out of range");
-        h->decode_small_max = (uint32_t)value;
+        h->tune.decode_small_max = (uint32_t)value;
         return WIFIRX_OK;
     case WIFIRX_P_STREAM_BATCH:
         // two pinned staging buffers of one batch each: at most 2^27 samples (1 GiB) per buffer
         if (!(value >= 0) || value > (double)WIFIRX_STREAM_BATCH_MAX) return fail(h, WIFIRX_EINVAL, "stream batch out of range (0 .. WIFIRX_STREAM_BATCH_MAX)");
-        h->stream_batch = (int64_t)value;
+        h->tune.stream_batch = (int64_t)value;
         return WIFIRX_OK;
     default:
         return fail(h, WIFIRX_EINVAL, "unknown parameter id");
@@ -317,7 +358,7 @@ int wifirx_set_param(wifirx_handle* h, int id, double value)
 int wifirx_get_stats(const wifirx_handle* h, wifirx_stats* st)
 {
     if (!h || !st) return WIFIRX_EINVAL;
-    std::lock_guard<std::mutex> lk(const_cast<wifirx_handle*>(h)->mu);
+    std::lock_guard<std::mutex> lk(h->w.mu);
     *st = h->stats;
     return WIFIRX_OK;
 }
@@ -373,13 +414,13 @@ int wifirx_memcpy_d2h(wifirx_handle* h, void* dst, const void* src, size_t bytes
 // ---- batch mode -----------------------------------------------------------------------------
 
 // bytes of one LLR value in the handle's batch format (WIFIRX_P_LLR_FORMAT)
-static size_t llr_value_bytes(const wifirx_handle* h) { return h->llr_format == WIFIRX_LLR_BF16 ? 2 : sizeof(float); }
+static size_t llr_value_bytes(const wifirx_handle* h) { return h->tune.llr_format == WIFIRX_LLR_BF16 ? 2 : sizeof(float); }
 
 // the demod launch of the handle's LLR format: the float32 and the bf16 rows are written by kernel instances of their own
 static hipError_t launch_demod_batch_fmt(const wifirx_handle* h, const float2* iq, uint32_t slot_len, uint32_t n_slots,
                                          const wr::DemodParams* prm, const wr::DemodOut* out, const uint64_t* slot_off)
 {
-    if (h->llr_format == WIFIRX_LLR_BF16) return wr_launch_demod_batch_bf16(h->stream, iq, slot_len, n_slots, prm, out, slot_off);
+    if (h->tune.llr_format == WIFIRX_LLR_BF16) return wr_launch_demod_batch_bf16(h->stream, iq, slot_len, n_slots, prm, out, slot_off);
     return wr_launch_demod_batch(h->stream, iq, slot_len, n_slots, prm, out, slot_off);
 }
 
@@ -433,68 +474,44 @@ static int demod_batch_impl(wifirx_handle* h, const float* iq, int iq_on_device,
                                       : (size_t)slot_len * n_slots;
     const uint64_t* d_off = nullptr;
     if (slot_off_host) {
-        if ((rc = ensure(h, &h->stage_off, &h->stage_off_bytes, ((size_t)n_slots + 1) * sizeof(uint64_t)))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->stage_off, slot_off_host, ((size_t)n_slots + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-        d_off = reinterpret_cast<const uint64_t*>(h->stage_off);
+        if ((rc = h->stage.off.reserve(h, ((size_t)n_slots + 1) * sizeof(uint64_t)))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->stage.off.p, slot_off_host, ((size_t)n_slots + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+        d_off = h->stage.off.as<const uint64_t>();
     }
     const size_t idx_n = (size_t)n_slots * h->cfg.max_sym * 48;
     const float2* d_iq = reinterpret_cast<const float2*>(iq);
     if (!iq_on_device) {
-        if ((rc = ensure(h, &h->stage_iq, &h->stage_iq_bytes, n_iq * sizeof(float2)))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->stage_iq, iq, n_iq * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-        d_iq = reinterpret_cast<const float2*>(h->stage_iq);
+        if ((rc = h->stage.iq.reserve(h, n_iq * sizeof(float2)))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->stage.iq.p, iq, n_iq * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+        d_iq = h->stage.iq.as<const float2>();
     }
-    wifirx_frame* d_fr = out->frames;
-    uint8_t* d_idx = out->idx;
-    float*   d_llr = out->llr;
-    float2*  d_car = reinterpret_cast<float2*>(out->carrier);
-    float2*  d_csi = reinterpret_cast<float2*>(out->csi);
-    float4*  d_stats = reinterpret_cast<float4*>(out->sym_stats);
-    uint32_t* d_hb = out->hbits;
-    if (!out->on_device) {
-        if ((rc = ensure(h, &h->stage_frames, &h->stage_frames_bytes, n_slots * sizeof(wifirx_frame)))) return rc;
-        d_fr = reinterpret_cast<wifirx_frame*>(h->stage_frames);
-        if (out->idx) {
-            if ((rc = ensure(h, &h->stage_idx, &h->stage_idx_bytes, idx_n))) return rc;
-            d_idx = reinterpret_cast<uint8_t*>(h->stage_idx);
-            HIP_TRY(h, hipMemsetAsync(d_idx, 0, idx_n, h->stream));
-        }
-        if (out->llr) {
-            if ((rc = ensure(h, &h->stage_llr, &h->stage_llr_bytes, idx_n * h->cfg.llr_bits * llr_value_bytes(h)))) return rc;
-            d_llr = reinterpret_cast<float*>(h->stage_llr);
-            HIP_TRY(h, hipMemsetAsync(d_llr, 0, idx_n * h->cfg.llr_bits * llr_value_bytes(h), h->stream));
-        }
-        if (out->carrier) {
-            if ((rc = ensure(h, &h->stage_car, &h->stage_car_bytes, idx_n * sizeof(float2)))) return rc;
-            d_car = reinterpret_cast<float2*>(h->stage_car);
-            HIP_TRY(h, hipMemsetAsync(d_car, 0, idx_n * sizeof(float2), h->stream));
-        }
-        if (out->csi) {
-            if ((rc = ensure(h, &h->stage_csi, &h->stage_csi_bytes, (size_t)n_slots * 52 * sizeof(float2)))) return rc;
-            d_csi = reinterpret_cast<float2*>(h->stage_csi);
-            HIP_TRY(h, hipMemsetAsync(d_csi, 0, (size_t)n_slots * 52 * sizeof(float2), h->stream));
-        }
-        if (out->sym_stats) {
-            if ((rc = ensure(h, &h->stage_stats, &h->stage_stats_bytes, (size_t)n_slots * sizeof(float4)))) return rc;
-            d_stats = reinterpret_cast<float4*>(h->stage_stats);
-        }
-        if (out->hbits) {
-            if ((rc = ensure(h, &h->stage_hbits, &h->stage_hbits_bytes, idx_n))) return rc;
-            d_hb = reinterpret_cast<uint32_t*>(h->stage_hbits);
-            HIP_TRY(h, hipMemsetAsync(d_hb, 0, idx_n, h->stream));
-        }
+    // the outputs: the caller's buffer, the staging buffer that stands in for it when it is on the host, its bytes, and
+    // whether that staging buffer is zero-filled first; `dev` is what the kernel writes
+    struct Staged { void* user; DevBuf& stage; size_t bytes; bool zero; void* dev = nullptr; };
+    Staged so[] = {
+        { out->frames,    h->stage.frames, n_slots * sizeof(wifirx_frame), false },
+        { out->idx,       h->stage.idx,    idx_n, true },
+        { out->llr,       h->stage.llr,    idx_n * h->cfg.llr_bits * llr_value_bytes(h), true },
+        { out->carrier,   h->stage.car,    idx_n * sizeof(float2), true },
+        { out->csi,       h->stage.csi,    (size_t)n_slots * 52 * sizeof(float2), true },
+        { out->sym_stats, h->stage.stats,  (size_t)n_slots * sizeof(float4), false },
+        { out->hbits,     h->stage.hbits,  idx_n, true },
+    };
+    for (Staged& s : so) {
+        s.dev = s.user;
+        if (out->on_device || !s.user) continue;
+        if ((rc = s.stage.reserve(h, s.bytes))) return rc;
+        s.dev = s.stage.p;
+        if (s.zero) HIP_TRY(h, hipMemsetAsync(s.dev, 0, s.bytes, h->stream));
     }
-    const wr::DemodOut dout = { d_fr, d_idx, d_llr, d_car, d_csi, d_stats, d_hb };
+    const wr::DemodOut dout = { static_cast<wifirx_frame*>(so[0].dev), static_cast<uint8_t*>(so[1].dev), static_cast<float*>(so[2].dev),
+                                static_cast<float2*>(so[3].dev), static_cast<float2*>(so[4].dev), static_cast<float4*>(so[5].dev),
+                                static_cast<uint32_t*>(so[6].dev) };
     HIP_TRY(h, launch_demod_batch_fmt(h, d_iq, slot_len, n_slots, &prm, &dout, d_off));
     h->stats.samples_in += n_iq;
     if (!out->on_device) {
-        HIP_TRY(h, hipMemcpyAsync(out->frames, d_fr, n_slots * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
-        if (out->idx) HIP_TRY(h, hipMemcpyAsync(out->idx, d_idx, idx_n, hipMemcpyDeviceToHost, h->stream));
-        if (out->llr) HIP_TRY(h, hipMemcpyAsync(out->llr, d_llr, idx_n * h->cfg.llr_bits * llr_value_bytes(h), hipMemcpyDeviceToHost, h->stream));
-        if (out->carrier) HIP_TRY(h, hipMemcpyAsync(out->carrier, d_car, idx_n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-        if (out->csi) HIP_TRY(h, hipMemcpyAsync(out->csi, d_csi, (size_t)n_slots * 52 * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-        if (out->sym_stats) HIP_TRY(h, hipMemcpyAsync(out->sym_stats, d_stats, (size_t)n_slots * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-        if (out->hbits) HIP_TRY(h, hipMemcpyAsync(out->hbits, d_hb, idx_n, hipMemcpyDeviceToHost, h->stream));
+        for (const Staged& s : so)
+            if (s.user) HIP_TRY(h, hipMemcpyAsync(s.user, s.dev, s.bytes, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         for (uint32_t i = 0; i < n_slots; i++) {
             uint32_t f = out->frames[i].flags;
@@ -547,17 +564,13 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
     stream_worker_wait_idle(h);
     HIP_TRY(h, hipSetDevice(h->device));
     const float2* d_t = reinterpret_cast<const float2*>(templates);
-    void* tmp = nullptr;
+    DevBuf tmp;                             // freed on return, after the synchronisation below
     if (!templates_on_device) {
         size_t bytes = (size_t)n_templates * frame_len * sizeof(float2);
-        hipError_t e = hipMalloc(&tmp, bytes);
-        if (e != hipSuccess) return oom(h, "hipMalloc(templates)", e);
-        e = hipMemcpyAsync(tmp, templates, bytes, hipMemcpyHostToDevice, h->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(tmp);
-            return fail(h, WIFIRX_EHIP, std::string("template upload: ") + hipGetErrorString(e));
-        }
-        d_t = reinterpret_cast<const float2*>(tmp);
+        if (int rc = tmp.alloc(h, bytes, "hipMalloc(templates)")) return rc;
+        hipError_t e = hipMemcpyAsync(tmp.p, templates, bytes, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) return fail(h, WIFIRX_EHIP, std::string("template upload: ") + hipGetErrorString(e));
+        d_t = tmp.as<const float2>();
     }
     // snr_db = NaN: the noiseless channel (gain 1, no AWGN) -- what txgen.impair(snr_db=None) is on the host
     const bool noiseless = std::isnan(snr_db);
@@ -565,7 +578,6 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
     hipError_t e = wr_launch_synth(h->stream, d_t, n_templates, frame_len, reinterpret_cast<float2*>(slots), slot_len,
                                    n_slots, lead, gain, noiseless ? 0.0f : 1.0f, cfo_max, seed, cfo_out);
     hipError_t e2 = hipStreamSynchronize(h->stream);
-    if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) return fail(h, WIFIRX_EHIP, std::string("synth launch: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(h, WIFIRX_EHIP, std::string("synth sync: ") + hipGetErrorString(e2));
     return WIFIRX_OK;

@@ -15,13 +15,13 @@ extern "C" int wifirx_decode_batch(wifirx_handle* h, uint32_t n_slots, const wif
 static int decode_prepass(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t (&pre)[9])
 {
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure(h, &h->dec_max, &h->dec_max_bytes, 256);
+    int rc = h->dec.max.reserve(h, 256);
     if (rc) return rc;
     // dec_max: [0] longest trellis, [1..8] decodable frames per rate, [16..23] cursors of the permutation kernel
-    HIP_TRY(h, hipMemsetAsync(h->dec_max, 0, 256, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->dec.max.p, 0, 256, h->stream));
     HIP_TRY(h, wr_launch_decode_maxsteps(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride,
-                                         reinterpret_cast<uint32_t*>(h->dec_max)));
-    HIP_TRY(h, hipMemcpyAsync(pre, h->dec_max, sizeof pre, hipMemcpyDeviceToHost, h->stream));
+                                         h->dec.max.as<uint32_t>()));
+    HIP_TRY(h, hipMemcpyAsync(pre, h->dec.max.p, sizeof pre, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return WIFIRX_OK;
 }
@@ -45,12 +45,12 @@ static int decode_group_by_rate(wifirx_handle* h, uint32_t n_slots, const wifirx
     g.n_virtual = n_rates > 1 ? g.starts[8] : n_slots;
     g.perm = nullptr;
     if (n_rates <= 1) return WIFIRX_OK;
-    int rc = ensure(h, &h->dec_perm, &h->dec_perm_bytes, (size_t)g.n_virtual * sizeof(uint32_t));
+    int rc = h->dec.perm.reserve(h, (size_t)g.n_virtual * sizeof(uint32_t));
     if (rc) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->dec_perm, 0xff, (size_t)g.n_virtual * sizeof(uint32_t), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->dec.perm.p, 0xff, (size_t)g.n_virtual * sizeof(uint32_t), h->stream));
     HIP_TRY(h, wr_launch_decode_perm(h->stream, n_slots, h->cfg.max_sym, out->frames, out->psdu_stride, g.starts,
-                                     reinterpret_cast<uint32_t*>(h->dec_max) + 16, reinterpret_cast<uint32_t*>(h->dec_perm)));
-    g.perm = reinterpret_cast<const uint32_t*>(h->dec_perm);
+                                     h->dec.max.as<uint32_t>() + 16, h->dec.perm.as<uint32_t>()));
+    g.perm = h->dec.perm.as<const uint32_t>();
     return WIFIRX_OK;
 }
 
@@ -62,9 +62,9 @@ static size_t decode_scratch_budget(wifirx_handle* h)
 {
     size_t budget = WR_DECODE_SCRATCH_BUDGET;
     size_t mem_free = 0, mem_total = 0;
-    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget = std::min<size_t>(budget, (mem_free + h->dec_scratch_bytes) / 10 * 7);
+    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget = std::min<size_t>(budget, (mem_free + h->dec.scratch.bytes) / 10 * 7);
     else (void)hipGetLastError();
-    if (h->test_decode_budget) budget = std::min<size_t>(budget, h->test_decode_budget);
+    if (h->env.decode_budget) budget = std::min<size_t>(budget, h->env.decode_budget);
     return budget;
 }
 
@@ -75,15 +75,14 @@ static int decode_alloc_scratch(wifirx_handle* h, size_t stride, size_t want, si
     n_waves = std::max<size_t>(1, std::min<size_t>(want, budget / stride));
     for (;;) {
         int rc;
-        if (h->test_fail_decode_scratch > 0 && h->test_fail_decode_scratch-- > 0) {
+        if (h->env.fail_decode_scratch > 0 && h->env.fail_decode_scratch-- > 0) {
             // test hook: a REAL failing hipMalloc (a size no device has), so that the retry runs with whatever state HIP keeps
             // after an exhausted allocation -- the sticky last-error above all (ADVICE r04)
-            void* none = nullptr;
-            size_t none_bytes = 0;
-            rc = ensure(h, &none, &none_bytes, SIZE_MAX / 2);
-            if (rc == WIFIRX_OK) { (void)hipFree(none); rc = fail(h, WIFIRX_ENOMEM, "hipMalloc(decode scratch): test hook"); }
+            DevBuf none;
+            rc = none.reserve(h, SIZE_MAX / 2);
+            if (rc == WIFIRX_OK) rc = fail(h, WIFIRX_ENOMEM, "hipMalloc(decode scratch): test hook");
         } else {
-            rc = ensure(h, &h->dec_scratch, &h->dec_scratch_bytes, stride * n_waves);
+            rc = h->dec.scratch.reserve(h, stride * n_waves);
         }
         if (rc == WIFIRX_OK) return WIFIRX_OK;
         if (rc != WIFIRX_ENOMEM || n_waves <= 4) return rc;
@@ -107,20 +106,20 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
     // the decoders read the decisions as bit planes: the caller's (written by the demod kernel), or packed from idx here
     const uint32_t* hbits = out->hbits;
     if (!hbits) {
-        rc = ensure(h, &h->dec_hbits, &h->dec_hbits_bytes, (size_t)n_slots * h->cfg.max_sym * 48);
+        rc = h->dec.hbits.reserve(h, (size_t)n_slots * h->cfg.max_sym * 48);
         if (rc) return rc;
         HIP_TRY(h, wr_launch_decode_pack(h->stream, n_slots, h->cfg.max_sym, out->frames, out->idx, out->psdu_stride,
-                                         reinterpret_cast<uint32_t*>(h->dec_hbits), n_steps));
-        hbits = reinterpret_cast<const uint32_t*>(h->dec_hbits);
+                                         h->dec.hbits.as<uint32_t>(), n_steps));
+        hbits = h->dec.hbits.as<const uint32_t>();
     }
-    if (n_slots <= h->decode_small_max) {
+    if (n_slots <= h->tune.decode_small_max) {
         // few frames: one wave per frame (8 B of survivor bits per step + the decoded words of the frame)
         const size_t stride = wr::dec_small_slice(n_steps);
         const size_t n_waves = std::min<size_t>(n_slots, WR_DECODE_MAX_WAVES);
-        rc = ensure(h, &h->dec_scratch, &h->dec_scratch_bytes, stride * n_waves);
+        rc = h->dec.scratch.reserve(h, stride * n_waves);
         if (rc) return rc;
         HIP_TRY(h, wr_launch_decode_small(h->stream, n_slots, h->cfg.max_sym, out->frames, hbits, out->psdu,
-                                          out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride, n_steps,
+                                          out->psdu_stride, h->dec.scratch.as<uint8_t>(), stride, n_steps,
                                           (uint32_t)n_waves));
         return WIFIRX_OK;
     }
@@ -130,13 +129,13 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
     // forbids it (tests).
     uint32_t n_dec = 0;
     for (int e = 0; e < 8; e++) n_dec += pre[1 + e];
-    const bool use_q = h->decode_q == 1 || (h->decode_q < 0 && n_dec >= WR_DECODE_Q_MIN_FRAMES);
+    const bool use_q = h->env.decode_q == 1 || (h->env.decode_q < 0 && n_dec >= WR_DECODE_Q_MIN_FRAMES);
     const uint32_t fpw_max = use_q ? WR_DECODE_Q_FRAMES_PER_WAVE : WR_DECODE_FRAMES_PER_WAVE;
     size_t stride = use_q ? wr::dec_q_slice(n_steps, false) : wr::dec_pair_slice(n_steps);
     // mid-size batches: fewer frames per wave, so that about a thousand waves share the work
     uint32_t fpw = (uint32_t)std::min<size_t>(fpw_max, std::max<size_t>(1, (n_slots + 1023) / 1024));
-    if (use_q && h->decode_q < 0) fpw = fpw_max;
-    if (h->decode_fpw) fpw = std::min<uint32_t>(fpw_max, h->decode_fpw);     // tests: full waves on small batches
+    if (use_q && h->env.decode_q < 0) fpw = fpw_max;
+    if (h->env.decode_fpw) fpw = std::min<uint32_t>(fpw_max, h->env.decode_fpw);     // tests: full waves on small batches
     DecodeGroups g;
     if ((rc = decode_group_by_rate(h, n_slots, out, pre, fpw, g))) return rc;
     const size_t n_tasks = (g.n_virtual + fpw - 1) / fpw;
@@ -149,7 +148,7 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
     const size_t spec_waves = (size_t)h->n_simd * ((pre[7] | pre[8]) ? 2 : WR_DQ_SPEC_WAVES);      // (the 64-QAM instance: two workgroups of its LDS fit a CU)
     int mode = 0;
     if (use_q) {
-        if (h->decode_ovl >= 0) mode = h->decode_ovl;
+        if (h->env.decode_ovl >= 0) mode = h->env.decode_ovl;
         else if (n_tasks >= WR_DECODE_MAX_WAVES / 2 && budget / stride_spec >= spec_waves) mode = 2;
     }
     // the scratch falls back to fewer waves only: the mode stays what was chosen
@@ -159,11 +158,11 @@ static int decode_batch_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_ou
         return rc;
     if (use_q)
         HIP_TRY(h, wr_launch_decode_q(h->stream, n_slots, h->cfg.max_sym, out->frames, hbits, out->psdu,
-                                      out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride, n_steps,
+                                      out->psdu_stride, h->dec.scratch.as<uint8_t>(), stride, n_steps,
                                       (uint32_t)n_waves, fpw, g.perm, g.n_virtual, (pre[7] | pre[8]) != 0, mode));
     else
         HIP_TRY(h, wr_launch_decode(h->stream, n_slots, h->cfg.max_sym, out->frames, hbits, out->psdu,
-                                    out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride, n_steps,
+                                    out->psdu_stride, h->dec.scratch.as<uint8_t>(), stride, n_steps,
                                     (uint32_t)n_waves, fpw, g.perm, g.n_virtual));
     return WIFIRX_OK;
 }
@@ -179,7 +178,7 @@ extern "C" int wifirx_decode_batch_soft(wifirx_handle* h, uint32_t n_slots, cons
     if (!h || !out) return WIFIRX_EINVAL;
     stream_worker_wait_idle(h);
     if (h->cfg.llr_bits == 0) return fail(h, WIFIRX_EINVAL, "wifirx_decode_batch_soft needs a handle created with llr_bits > 0");
-    return decode_batch_soft_impl(h, n_slots, out, h->cfg.llr_bits, h->llr_format == WIFIRX_LLR_BF16);
+    return decode_batch_soft_impl(h, n_slots, out, h->cfg.llr_bits, h->tune.llr_format == WIFIRX_LLR_BF16);
 }
 
 static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* out, uint32_t llr_bits, bool bf16)
@@ -214,11 +213,11 @@ static int decode_batch_soft_impl(wifirx_handle* h, uint32_t n_slots, const wifi
         if (bf16)
             HIP_TRY(h, wr_launch_decode_soft_bf16(h->stream, nb_of_class[c], n_slots, h->cfg.max_sym, llr_bits, out->frames,
                                                   reinterpret_cast<const uint16_t*>(out->llr), out->psdu, out->psdu_stride,
-                                                  reinterpret_cast<uint8_t*>(h->dec_scratch), stride, n_steps, waves, g.perm,
+                                                  h->dec.scratch.as<uint8_t>(), stride, n_steps, waves, g.perm,
                                                   g.n_virtual, lo, hi));
         else
         HIP_TRY(h, wr_launch_decode_soft(h->stream, nb_of_class[c], n_slots, h->cfg.max_sym, llr_bits, out->frames, out->llr,
-                                         out->psdu, out->psdu_stride, reinterpret_cast<uint8_t*>(h->dec_scratch), stride,
+                                         out->psdu, out->psdu_stride, h->dec.scratch.as<uint8_t>(), stride,
                                          n_steps, waves, g.perm, g.n_virtual, lo, hi));
     }
     return WIFIRX_OK;

@@ -10,50 +10,36 @@ namespace {
 const int64_t kHistory = 256;     // samples kept in front of the detection frontier (2 tiles + delay 16, rounded)
 
 // Test hook for the allocation-failure paths (tests/test_gpu_stream.py): a handle created with
-// WIFIRX_TEST_FAIL_ALLOC=<k> in the environment fails its k-th stream-mode hipMalloc (counted from 1) once.
-hipError_t stream_malloc(wifirx_handle* h, void** p, size_t bytes)
+// WIFIRX_TEST_FAIL_ALLOC=<k> in the environment fails its k-th stream-mode allocation (counted from 1) once.
+int stream_alloc(wifirx_handle* h, DevBuf& b, size_t bytes, const char* what)
 {
-    if (h->test_fail_alloc > 0 && ++h->test_alloc_count == h->test_fail_alloc) { *p = nullptr; return hipErrorOutOfMemory; }
-    return hipMalloc(p, bytes);
+    if (h->env.fail_alloc > 0 && ++h->env.alloc_count == h->env.fail_alloc) { b.reset(); return oom(h, what, hipErrorOutOfMemory); }
+    return b.alloc(h, bytes, what);
 }
 
 // Grows the sample buffer and the two detection side buffers together.  All three are allocated before anything of
 // the handle changes: after a failure the old buffers and capacities are still in place and a later push starts over.
 int stream_reserve(wifirx_handle* h, int64_t need)
 {
-    if (need <= h->sbuf_cap) return WIFIRX_OK;
+    StreamState& s = h->st;
+    if (need <= s.sbuf_cap) return WIFIRX_OK;
     int64_t cap = std::max<int64_t>(need + need / 2, 1 << 16);
     cap = (cap + 63) / 64 * 64;
-    float2* nb = nullptr;
-    uint8_t* n_above = nullptr;
-    float2* n_A = nullptr;
-    auto drop = [&]() {
-        if (nb) (void)hipFree(nb);
-        if (n_above) (void)hipFree(n_above);
-        if (n_A) (void)hipFree(n_A);
-    };
-    hipError_t e = stream_malloc(h, (void**)&nb, (size_t)cap * sizeof(float2));
-    if (e == hipSuccess) e = stream_malloc(h, (void**)&n_above, (size_t)(cap / 64 + 2) * sizeof(uint64_t));
-    if (e == hipSuccess) e = stream_malloc(h, (void**)&n_A, (size_t)cap * sizeof(float2));
-    if (e != hipSuccess) {
-        drop();
-        return oom(h, "hipMalloc(stream buffers)", e);
-    }
-    if (h->sbuf && h->sfill > 0)
-        e = hipMemcpyAsync(nb, h->sbuf, (size_t)h->sfill * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
+    DevBuf nb, n_above, n_A;
+    const char* what = "hipMalloc(stream buffers)";
+    int rc = stream_alloc(h, nb, (size_t)cap * sizeof(float2), what);
+    if (!rc) rc = stream_alloc(h, n_above, (size_t)(cap / 64 + 2) * sizeof(uint64_t), what);
+    if (!rc) rc = stream_alloc(h, n_A, (size_t)cap * sizeof(float2), what);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    if (s.sbuf.p && s.sfill > 0)
+        e = hipMemcpyAsync(nb.p, s.sbuf.p, (size_t)s.sfill * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        drop();
-        return fail(h, WIFIRX_EHIP, std::string("stream buffer move: ") + hipGetErrorString(e));
-    }
-    if (h->sbuf) (void)hipFree(h->sbuf);
-    if (h->s_above) (void)hipFree(h->s_above);
-    if (h->s_A) (void)hipFree(h->s_A);
-    h->sbuf = nb;
-    h->s_above = n_above;
-    h->s_A = n_A;
-    h->sbuf_cap = cap;
-    h->s_above_cap = cap;
+    if (e != hipSuccess) return fail(h, WIFIRX_EHIP, std::string("stream buffer move: ") + hipGetErrorString(e));
+    s.sbuf = std::move(nb);
+    s.above = std::move(n_above);
+    s.A = std::move(n_A);
+    s.sbuf_cap = cap;
     return WIFIRX_OK;
 }
 
@@ -61,46 +47,41 @@ int stream_reserve(wifirx_handle* h, int64_t need)
 // being replaced, so a failed allocation leaves "no buffers, capacity 0" and the next push allocates again.
 int stream_out_reserve(wifirx_handle* h, uint32_t n)
 {
-    if (n <= h->s_cap) return WIFIRX_OK;
+    StreamState& s = h->st;
+    if (n <= s.out_cap) return WIFIRX_OK;
     uint32_t cap = std::max<uint32_t>(n * 2, 64);
-    void** bufs[] = { &h->s_trig, &h->s_frames, &h->s_idx, &h->s_car, &h->s_psdu, &h->s_csi, &h->s_stats, &h->s_hbits };
-    h->s_cap = 0;
-    for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
     const size_t per = (size_t)h->cfg.max_sym * 48;
     // no LLR rows here: wifirx_poll has no LLR output; with WIFIRX_P_STREAM_SOFT the decoder's rows come from stream_llr_reserve
-    struct { void** p; size_t bytes; } req[] = {
-        { &h->s_trig, cap * sizeof(wr::StreamTrig) },
-        { &h->s_frames, cap * sizeof(wifirx_frame) },
-        { &h->s_idx, cap * per },
-        { &h->s_car, h->cfg.want_carrier ? cap * per * sizeof(float2) : 0 },
-        { &h->s_psdu, (size_t)cap * 2048 },
-        { &h->s_csi, (size_t)cap * 52 * sizeof(float2) },
-        { &h->s_stats, (size_t)cap * sizeof(float4) },
-        { &h->s_hbits, cap * per },              // the decisions as bit planes: what decode_mac reads
+    struct { DevBuf& b; size_t bytes; } req[] = {
+        { s.trig, cap * sizeof(wr::StreamTrig) },
+        { s.frames, cap * sizeof(wifirx_frame) },
+        { s.idx, cap * per },
+        { s.car, h->cfg.want_carrier ? cap * per * sizeof(float2) : 0 },
+        { s.psdu, (size_t)cap * 2048 },
+        { s.csi, (size_t)cap * 52 * sizeof(float2) },
+        { s.stats, (size_t)cap * sizeof(float4) },
+        { s.hbits, cap * per },                 // the decisions as bit planes: what decode_mac reads
     };
+    s.out_cap = 0;
+    for (auto& r : req) r.b.reset();
     for (auto& r : req) {
         if (!r.bytes) continue;
-        hipError_t e = stream_malloc(h, r.p, r.bytes);
-        if (e != hipSuccess) {
-            for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
-            return oom(h, "hipMalloc(stream outputs)", e);
+        if (int rc = stream_alloc(h, r.b, r.bytes, "hipMalloc(stream outputs)")) {
+            for (auto& q : req) q.b.reset();
+            return rc;
         }
     }
-    h->s_cap = cap;
+    s.out_cap = cap;
     return WIFIRX_OK;
 }
 
-// WIFIRX_P_STREAM_SOFT: LLR rows for the s_cap triggers the other rows hold (max_sym * 48 * 6 floats each), kept while the
-// handle lives; allocated only once the mode is on
+// WIFIRX_P_STREAM_SOFT: LLR rows for the out_cap triggers the other rows hold (max_sym * 48 * 6 floats each), kept while
+// the handle lives; allocated only once the mode is on
 static int stream_llr_reserve(wifirx_handle* h)
 {
-    if (h->s_llr_cap >= h->s_cap) return WIFIRX_OK;
-    if (h->s_llr) { (void)hipFree(h->s_llr); h->s_llr = nullptr; }
-    h->s_llr_cap = 0;
-    hipError_t e = stream_malloc(h, &h->s_llr, (size_t)h->s_cap * h->cfg.max_sym * 48 * 6 * sizeof(float));
-    if (e != hipSuccess) return oom(h, "hipMalloc(stream LLR rows)", e);
-    h->s_llr_cap = h->s_cap;
-    return WIFIRX_OK;
+    const size_t need = (size_t)h->st.out_cap * h->cfg.max_sym * 48 * 6 * sizeof(float);
+    if (h->st.llr.bytes >= need) return WIFIRX_OK;
+    return stream_alloc(h, h->st.llr, need, "hipMalloc(stream LLR rows)");
 }
 
 // What a pass of the stream pipeline changes before its results are queued; put back when the pass fails, so that a
@@ -111,19 +92,19 @@ struct StreamRollback {
     int64_t  sfill, sprocessed, sdetected, last_trig;
     size_t   n_pending;
     uint64_t samples_in, frames_detected;
-    explicit StreamRollback(wifirx_handle* hh) : h(hh), sfill(hh->sfill), sprocessed(hh->sprocessed), sdetected(hh->sdetected),
-        last_trig(hh->last_trig), n_pending(hh->pending.size())
+    explicit StreamRollback(wifirx_handle* hh) : h(hh), sfill(hh->st.sfill), sprocessed(hh->st.sprocessed), sdetected(hh->st.sdetected),
+        last_trig(hh->st.last_trig), n_pending(hh->st.pending.size())
     {
-        std::lock_guard<std::mutex> lk(h->mu);
+        std::lock_guard<std::mutex> lk(h->w.mu);
         samples_in = h->stats.samples_in;
         frames_detected = h->stats.frames_detected;
     }
     ~StreamRollback()
     {
         if (!armed) return;
-        h->sfill = sfill; h->sprocessed = sprocessed; h->sdetected = sdetected; h->last_trig = last_trig;
-        h->pending.resize(n_pending);
-        std::lock_guard<std::mutex> lk(h->mu);
+        h->st.sfill = sfill; h->st.sprocessed = sprocessed; h->st.sdetected = sdetected; h->st.last_trig = last_trig;
+        h->st.pending.resize(n_pending);
+        std::lock_guard<std::mutex> lk(h->w.mu);
         h->stats.samples_in = samples_in;
         h->stats.frames_detected = frames_detected;
     }
@@ -143,41 +124,42 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
         std::fprintf(stderr, "[wifirx_push] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
         t_prev = t;
     };
+    StreamState& st = h->st;
     {
         std::string dead;
-        { std::lock_guard<std::mutex> lk(h->mu); if (h->stream_dead) dead = h->stream_dead_msg; }
+        { std::lock_guard<std::mutex> lk(h->w.mu); if (st.dead) dead = st.dead_msg; }
         if (!dead.empty()) return fail(h, WIFIRX_EDEAD, dead);       // (nothing is consumed, and repeating the push will not help)
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = stream_reserve(h, h->sfill + (int64_t)n + 64);
+    int rc = stream_reserve(h, st.sfill + (int64_t)n + 64);
     if (rc) return rc;
     StreamRollback undo(h);
     if (n) {
-        HIP_TRY(h, hipMemcpyAsync(h->sbuf + h->sfill, iq, n * sizeof(float2),
+        HIP_TRY(h, hipMemcpyAsync(st.sbuf.as<float2>() + st.sfill, iq, n * sizeof(float2),
                                   iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        h->sfill += (int64_t)n;
-        { std::lock_guard<std::mutex> lk(h->mu); h->stats.samples_in += n; }
+        st.sfill += (int64_t)n;
+        { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.samples_in += n; }
     }
     stage("reserve + enqueue input copy");
-    if (!flush && h->stream_batch > 0 && h->sbase + h->sfill - h->sprocessed < h->stream_batch) {
+    if (!flush && h->tune.stream_batch > 0 && st.sbase + st.sfill - st.sprocessed < h->tune.stream_batch) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));         // the caller may reuse its buffer
         undo.armed = false;
         return WIFIRX_OK;                                       // keep collecting
     }
-    h->sprocessed = h->sbase + h->sfill;
-    const int64_t end_abs = h->sbase + h->sfill;
+    st.sprocessed = st.sbase + st.sfill;
+    const int64_t end_abs = st.sbase + st.sfill;
     const int mp = h->cfg.min_plateau;
 
     // (1) detection over the tiles that hold not yet scanned samples (plus one tile of mask history)
-    if (end_abs > h->sdetected) {
-        int64_t t_first = (h->sdetected - h->sbase) / 64;
+    if (end_abs > st.sdetected) {
+        int64_t t_first = (st.sdetected - st.sbase) / 64;
         if (t_first > 0) t_first -= 1;
-        const int64_t t_end = (h->sfill + 63) / 64;
+        const int64_t t_end = (st.sfill + 63) / 64;
         const int64_t n_tiles = t_end - t_first;
-        HIP_TRY(h, wr_launch_stream_detect(h->stream, h->sbuf, h->sfill, t_first, n_tiles, h->cfg.sensitivity,
-                                           reinterpret_cast<uint64_t*>(h->s_above), h->s_A));
+        HIP_TRY(h, wr_launch_stream_detect(h->stream, st.sbuf.as<float2>(), st.sfill, t_first, n_tiles, h->cfg.sensitivity,
+                                           st.above.as<uint64_t>(), st.A.as<float2>()));
         std::vector<uint64_t> masks((size_t)n_tiles);
-        HIP_TRY(h, hipMemcpyAsync(masks.data(), reinterpret_cast<uint64_t*>(h->s_above) + t_first,
+        HIP_TRY(h, hipMemcpyAsync(masks.data(), st.above.as<uint64_t>() + t_first,
                                   (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         stage("input copy + detect + masks");
@@ -189,72 +171,72 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
             if (!m) continue;               // no sample of the tile above the threshold: no plateau can end in it (most tiles: 0.17 -> 0.03 ms per 4 M samples)
             uint64_t hit = m;
             for (int j = 1; j <= mp; j++) hit &= (m << j) | (j < 64 ? (prev >> (64 - j)) : 0);
-            const int64_t tile_abs = h->sbase + (t_first + tl) * 64;
+            const int64_t tile_abs = st.sbase + (t_first + tl) * 64;
             while (hit) {
                 int l = __builtin_ctzll(hit);
                 hit &= hit - 1;
                 int64_t pos = tile_abs + l;
-                if (pos < h->sdetected || pos >= end_abs) continue;
-                if (pos - h->last_trig <= WIFIRX_MIN_GAP) continue;
-                h->pending.push_back({ pos, 0.0f, false });
-                h->last_trig = pos;
+                if (pos < st.sdetected || pos >= end_abs) continue;
+                if (pos - st.last_trig <= WIFIRX_MIN_GAP) continue;
+                st.pending.push_back({ pos, 0.0f, false });
+                st.last_trig = pos;
                 n_new_trig++;
             }
         }
-        h->sdetected = end_abs;
-        { std::lock_guard<std::mutex> lk(h->mu); h->stats.frames_detected += n_new_trig; }
+        st.sdetected = end_abs;
+        { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.frames_detected += n_new_trig; }
         stage("host state machine");
     }
 
     // (3) every pending trigger whose samples are (partly) here
-    const uint32_t np = (uint32_t)h->pending.size();
+    const uint32_t np = (uint32_t)st.pending.size();
     if (np) {
         if ((rc = stream_out_reserve(h, np))) return rc;
-        const bool soft = h->stream_soft != 0;
+        const bool soft = h->tune.stream_soft != 0;
         if (soft && (rc = stream_llr_reserve(h))) return rc;
         std::vector<wr::StreamTrig> trig(np);
         std::vector<char> final_(np);
         for (uint32_t k = 0; k < np; k++) {
-            const int64_t pos = h->pending[k].pos;
+            const int64_t pos = st.pending[k].pos;
             int64_t L = end_abs - (pos - 16);
             bool fin = flush;
-            if (k + 1 < np && h->pending[k + 1].pos - pos <= L) { L = h->pending[k + 1].pos - pos; fin = true; }
+            if (k + 1 < np && st.pending[k + 1].pos - pos <= L) { L = st.pending[k + 1].pos - pos; fin = true; }
             if (L >= WIFIRX_MAX_SAMPLES) { L = WIFIRX_MAX_SAMPLES; fin = true; }
-            trig[k].pos = pos - h->sbase;
+            trig[k].pos = pos - st.sbase;
             trig[k].usable = L;
-            trig[k].cfo = h->pending[k].cfo;        // A[] of an earlier push is gone: reuse the value
-            trig[k].pad = h->pending[k].have_cfo;   // the device computed when it first saw the trigger
+            trig[k].cfo = st.pending[k].cfo;        // A[] of an earlier push is gone: reuse the value
+            trig[k].pad = st.pending[k].have_cfo;   // the device computed when it first saw the trigger
             final_[k] = fin;
         }
         wr::DemodParams prm = params_of(h);
         if (soft) prm.llr_bits = 6;                 // the stream's own LLR rows: every rate fits, whatever cfg.llr_bits says
         const size_t per = (size_t)h->cfg.max_sym * 48;
-        HIP_TRY(h, hipMemcpyAsync(h->s_trig, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(st.trig.p, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
         // hard decisions as bytes only when the caller polls them (WIFIRX_P_STREAM_IDX); decode_mac reads the bit planes
-        uint8_t* d_idx = h->stream_want_idx ? reinterpret_cast<uint8_t*>(h->s_idx) : nullptr;
+        uint8_t* d_idx = h->tune.stream_want_idx ? st.idx.as<uint8_t>() : nullptr;
         if (d_idx) HIP_TRY(h, hipMemsetAsync(d_idx, 0, np * per, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->s_csi, 0, (size_t)np * 52 * sizeof(float2), h->stream));
-        if (h->s_car) HIP_TRY(h, hipMemsetAsync(h->s_car, 0, np * per * sizeof(float2), h->stream));
-        const wr::DemodOut dout = { reinterpret_cast<wifirx_frame*>(h->s_frames), d_idx, soft ? reinterpret_cast<float*>(h->s_llr) : nullptr,
-                                    reinterpret_cast<float2*>(h->s_car), reinterpret_cast<float2*>(h->s_csi),
-                                    reinterpret_cast<float4*>(h->s_stats), reinterpret_cast<uint32_t*>(h->s_hbits) };
-        HIP_TRY(h, wr_launch_demod_stream(h->stream, h->sbuf, h->sfill, reinterpret_cast<wr::StreamTrig*>(h->s_trig), np,
-                                          &prm, h->s_A, &dout));
+        HIP_TRY(h, hipMemsetAsync(st.csi.p, 0, (size_t)np * 52 * sizeof(float2), h->stream));
+        if (st.car.p) HIP_TRY(h, hipMemsetAsync(st.car.p, 0, np * per * sizeof(float2), h->stream));
+        const wr::DemodOut dout = { st.frames.as<wifirx_frame>(), d_idx, soft ? st.llr.as<float>() : nullptr,
+                                    st.car.as<float2>(), st.csi.as<float2>(),
+                                    st.stats.as<float4>(), st.hbits.as<uint32_t>() };
+        HIP_TRY(h, wr_launch_demod_stream(h->stream, st.sbuf.as<float2>(), st.sfill, st.trig.as<wr::StreamTrig>(), np,
+                                          &prm, st.A.as<float2>(), &dout));
         wifirx_out o{};
-        o.frames = reinterpret_cast<wifirx_frame*>(h->s_frames);
+        o.frames = st.frames.as<wifirx_frame>();
         o.idx = d_idx;
-        o.hbits = reinterpret_cast<uint32_t*>(h->s_hbits);
-        o.psdu = reinterpret_cast<uint8_t*>(h->s_psdu);
+        o.hbits = st.hbits.as<uint32_t>();
+        o.psdu = st.psdu.as<uint8_t>();
         o.psdu_stride = 2048;
         o.on_device = 1;
-        o.llr = soft ? reinterpret_cast<float*>(h->s_llr) : nullptr;
+        o.llr = soft ? st.llr.as<float>() : nullptr;
         stage("enqueue frame kernel");
         if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
         stage("frame kernel + decode_mac");
         // the frame records first: they say how much of every output row is worth bringing back (rows are max_sym
         // symbols and 2048 bytes wide on the device, a frame usually fills a fraction of that)
         std::vector<wifirx_frame> fr(np);
-        HIP_TRY(h, hipMemcpyAsync(fr.data(), h->s_frames, np * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(fr.data(), st.frames.p, np * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         size_t w_sym = 0, w_psdu = 0;
         for (uint32_t k = 0; k < np; k++) {
@@ -266,34 +248,33 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
         // Hard decisions travel only when the stream wants them (WIFIRX_P_STREAM_IDX), equalised points only for
         // handles created with want_carrier.
         auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-        const size_t w_idx = h->stream_want_idx ? w_sym : 0;
-        const size_t w_car = h->s_car ? w_sym * 2 * sizeof(float) : 0;
+        const size_t w_idx = h->tune.stream_want_idx ? w_sym : 0;
+        const size_t w_car = st.car.p ? w_sym * 2 * sizeof(float) : 0;
         const size_t o_psdu = 0, b_psdu = up16((size_t)np * w_psdu);
         const size_t o_idx = o_psdu + b_psdu, b_idx = up16((size_t)np * w_idx);
         const size_t o_car = o_idx + b_idx, b_car = up16((size_t)np * w_car);
         const size_t o_csi = o_car + b_car, b_csi = up16((size_t)np * 52 * sizeof(float2));
         const size_t o_stats = o_csi + b_csi, b_stats = up16((size_t)np * sizeof(float4));
         const size_t b_all = o_stats + b_stats;
-        if ((rc = ensure(h, &h->s_pack, &h->s_pack_bytes, b_all))) return rc;
-        if ((rc = ensure_pinned(h, &h->s_host, &h->s_host_bytes, b_all))) return rc;
-        uint8_t* pk = reinterpret_cast<uint8_t*>(h->s_pack);
+        if ((rc = st.pack.reserve(h, b_all))) return rc;
+        if ((rc = st.host.reserve(h, b_all))) return rc;
+        uint8_t* pk = st.pack.as<uint8_t>();
         if (w_psdu)
-            HIP_TRY(h, hipMemcpy2DAsync(pk + o_psdu, w_psdu, h->s_psdu, 2048, w_psdu, np, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(h, hipMemcpy2DAsync(pk + o_psdu, w_psdu, st.psdu.p, 2048, w_psdu, np, hipMemcpyDeviceToDevice, h->stream));
         if (w_idx)
-            HIP_TRY(h, hipMemcpy2DAsync(pk + o_idx, w_idx, h->s_idx, per, w_idx, np, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(h, hipMemcpy2DAsync(pk + o_idx, w_idx, st.idx.p, per, w_idx, np, hipMemcpyDeviceToDevice, h->stream));
         if (w_car)
-            HIP_TRY(h, hipMemcpy2DAsync(pk + o_car, w_car, h->s_car, per * 2 * sizeof(float), w_car, np, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(pk + o_csi, h->s_csi, (size_t)np * 52 * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(pk + o_stats, h->s_stats, (size_t)np * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->s_host, h->s_pack, b_all, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpy2DAsync(pk + o_car, w_car, st.car.p, per * 2 * sizeof(float), w_car, np, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(pk + o_csi, st.csi.p, (size_t)np * 52 * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(pk + o_stats, st.stats.p, (size_t)np * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(st.host.p, st.pack.p, b_all, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         stage("outputs to host");
         // one heap copy of the batch's outputs, shared by its frames (no per-frame allocations)
-        auto blob = std::make_shared<std::vector<uint8_t>>(reinterpret_cast<const uint8_t*>(h->s_host),
-                                                           reinterpret_cast<const uint8_t*>(h->s_host) + b_all);
+        auto blob = std::make_shared<std::vector<uint8_t>>(st.host.as<const uint8_t>(), st.host.as<const uint8_t>() + b_all);
         std::vector<PendingTrig> keep;
         undo.armed = false;                                 // nothing below can fail: the pass is committed
-        std::lock_guard<std::mutex> lk(h->mu);              // queue + statistics
+        std::lock_guard<std::mutex> lk(h->w.mu);            // queue + statistics
         for (uint32_t k = 0; k < np; k++) {
             wifirx_frame f = fr[k];
             const bool complete = (f.flags & WIFIRX_F_COMPLETE) != 0;
@@ -301,13 +282,13 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
             // a frame is settled when it is complete, when it failed for a reason more samples cannot
             // cure, or when no more samples can come (next trigger / MAX_SAMPLES / flush)
             if (!(complete || !truncated || final_[k])) {
-                PendingTrig pt = h->pending[k];
+                PendingTrig pt = st.pending[k];
                 pt.cfo = f.cfo_coarse;
                 pt.have_cfo = true;
                 keep.push_back(pt);
                 continue;
             }
-            f.trigger = (int32_t)(h->pending[k].pos & 0x7fffffff);
+            f.trigger = (int32_t)(st.pending[k].pos & 0x7fffffff);
             PolledFrame pf;
             pf.fr = f;
             pf.blob = blob;
@@ -323,10 +304,10 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
             h->stats.frames_complete += complete;
             h->stats.frames_crc_ok += (f.flags & WIFIRX_F_CRC_OK) != 0;
             h->stats.frames_dropped += (f.flags & WIFIRX_F_CRC_OK) == 0;
-            h->queue.push_back(std::move(pf));
+            st.queue.push_back(std::move(pf));
         }
-        h->n_queued.store((uint32_t)h->queue.size(), std::memory_order_release);
-        h->pending.swap(keep);
+        st.n_queued.store((uint32_t)st.queue.size(), std::memory_order_release);
+        st.pending.swap(keep);
         stage("queue frames");
     }
 
@@ -337,36 +318,36 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
     //     must; the next pass moves it); one after the move began leaves a buffer that cannot be trusted: the stream is
     //     marked dead and every later push says so (WIFIRX_EDEAD, never "retry").
     undo.armed = false;
-    int64_t keep_from = h->sdetected - kHistory;
-    if (!h->pending.empty()) keep_from = std::min(keep_from, h->pending.front().pos - 16);
-    if (keep_from < h->sbase) keep_from = h->sbase;
+    int64_t keep_from = st.sdetected - kHistory;
+    if (!st.pending.empty()) keep_from = std::min(keep_from, st.pending.front().pos - 16);
+    if (keep_from < st.sbase) keep_from = st.sbase;
     keep_from = keep_from / 64 * 64;
-    if (keep_from > h->sbase) {
-        const int64_t off = keep_from - h->sbase, left = h->sfill - off;
+    if (keep_from > st.sbase) {
+        const int64_t off = keep_from - st.sbase, left = st.sfill - off;
         hipError_t ce = hipSuccess;
         bool touched = false;
         // test hook (tests/test_gpu_stream.py): WIFIRX_TEST_FAIL_CARRY=<k> fails the k-th carry before / =-<k> after the move began
-        if (h->test_fail_carry != 0 && ++h->test_carry_count == std::abs(h->test_fail_carry)) {
+        if (h->env.fail_carry != 0 && ++h->env.carry_count == std::abs(h->env.fail_carry)) {
             ce = hipErrorUnknown;
-            touched = h->test_fail_carry < 0;
+            touched = h->env.fail_carry < 0;
         }
         if (ce == hipSuccess && left > 0) {
             // overlapping move: stage through the A buffer (same capacity, free between pushes)
-            ce = hipMemcpyAsync(h->s_A, h->sbuf + off, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
+            ce = hipMemcpyAsync(st.A.p, st.sbuf.as<float2>() + off, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
             if (ce == hipSuccess) {
                 touched = true;
-                ce = hipMemcpyAsync(h->sbuf, h->s_A, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
+                ce = hipMemcpyAsync(st.sbuf.p, st.A.p, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
             }
         }
         if (ce == hipSuccess) ce = hipStreamSynchronize(h->stream);
         if (ce == hipSuccess) {
-            h->sbase = keep_from;
-            h->sfill = left > 0 ? left : 0;
+            st.sbase = keep_from;
+            st.sfill = left > 0 ? left : 0;
         } else if (touched) {
-            std::lock_guard<std::mutex> lk(h->mu);
-            h->stream_dead = true;
-            h->stream_dead_msg = std::string("stream sample buffer lost in the carry step: ") + hipGetErrorString(ce) +
-                                 " (frames up to here were delivered; destroy the handle)";
+            std::lock_guard<std::mutex> lk(h->w.mu);
+            st.dead = true;
+            st.dead_msg = std::string("stream sample buffer lost in the carry step: ") + hipGetErrorString(ce) +
+                          " (frames up to here were delivered; destroy the handle)";
         } else {
             (void)hipGetLastError();        // nothing was moved: the next pass carries from the same base
         }
@@ -379,60 +360,59 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
 static void stream_worker_main(wifirx_handle* h)
 {
     t_is_worker = true;
-    std::unique_lock<std::mutex> lk(h->mu);
+    Worker& w = h->w;
+    std::unique_lock<std::mutex> lk(w.mu);
     for (;;) {
-        h->cv.wait(lk, [&] { return h->w_has_job || h->w_stop; });
-        if (!h->w_has_job) return;                          // stop requested, nothing queued
-        const float* p = h->w_job_ptr;
-        const size_t n = h->w_job_n;
-        const bool fl = h->w_job_flush;
-        h->w_has_job = false;
+        w.cv.wait(lk, [&] { return w.job || w.stop; });
+        if (!w.job) return;                                 // stop requested, nothing queued
+        const Job job = *w.job;
+        w.job.reset();
         lk.unlock();
         int rc;
         try {
-            rc = stream_process(h, p, n, 0, fl);
+            rc = stream_process(h, job.ptr, job.n, 0, job.flush);
         } catch (const std::exception& e) {          // nothing may escape a thread (or the C boundary)
             rc = WIFIRX_ENOMEM;
-            h->w_err_local = std::string("stream worker: ") + e.what();
+            w.err_local = std::string("stream worker: ") + e.what();
         }
         lk.lock();
         if (rc != WIFIRX_OK) {
-            if (h->w_rc == WIFIRX_OK) { h->w_rc = rc; h->w_err = h->w_err_local; }
+            if (w.rc == WIFIRX_OK) { w.rc = rc; w.err = w.err_local; }
             // stream_process is all or nothing: the batch is still whole in its staging buffer (the caller fills the other
             // one and cannot hand that over before this one is settled) -- keep it for another attempt
-            h->w_retry = true; h->w_retry_ptr = p; h->w_retry_n = n; h->w_retry_flush = fl;
+            w.retry = job;
         }
-        h->w_busy = false;
-        h->cv.notify_all();
+        w.busy = false;
+        w.cv.notify_all();
     }
 }
 
 static void stream_worker_wait_idle(wifirx_handle* h)
 {
-    if (!h->w_started) return;
-    std::unique_lock<std::mutex> lk(h->mu);
-    h->cv.wait(lk, [&] { return !h->w_busy; });
+    if (!h->w.thread.joinable()) return;
+    std::unique_lock<std::mutex> lk(h->w.mu);
+    h->w.cv.wait(lk, [&] { return !h->w.busy; });
 }
 
 static void stream_worker_stop(wifirx_handle* h)
 {
-    if (!h->w_started) return;
+    Worker& w = h->w;
+    if (!w.thread.joinable()) return;
     {
-        std::unique_lock<std::mutex> lk(h->mu);
-        h->cv.wait(lk, [&] { return !h->w_busy; });
-        h->w_stop = true;
-        h->cv.notify_all();
+        std::unique_lock<std::mutex> lk(w.mu);
+        w.cv.wait(lk, [&] { return !w.busy; });
+        w.stop = true;
+        w.cv.notify_all();
     }
-    h->worker.join();
-    h->w_started = false;
+    w.thread.join();
 }
 
 // the failure of an earlier batch, if any (reported once, by the next push / flush)
 static int stream_worker_take_error(wifirx_handle* h)
 {
-    std::lock_guard<std::mutex> lk(h->mu);
-    const int rc = h->w_rc;
-    if (rc != WIFIRX_OK) { h->err = h->w_err; h->w_rc = WIFIRX_OK; }
+    std::lock_guard<std::mutex> lk(h->w.mu);
+    const int rc = h->w.rc;
+    if (rc != WIFIRX_OK) { h->err = h->w.err; h->w.rc = WIFIRX_OK; }
     return rc;
 }
 
@@ -440,17 +420,15 @@ static int stream_worker_take_error(wifirx_handle* h)
 // before anything behind it in the stream.  Returns its result.
 static int stream_resubmit_failed(wifirx_handle* h)
 {
+    Worker& w = h->w;
     {
-        std::unique_lock<std::mutex> lk(h->mu);
-        if (!h->w_retry) return WIFIRX_OK;                  // the usual case: no wait -- the worker may be busy with a good batch
-        h->cv.wait(lk, [&] { return !h->w_busy; });         // (a failed batch leaves the worker idle)
-        h->w_job_ptr = h->w_retry_ptr;
-        h->w_job_n = h->w_retry_n;
-        h->w_job_flush = h->w_retry_flush;
-        h->w_retry = false;
-        h->w_has_job = true;
-        h->w_busy = true;
-        h->cv.notify_all();
+        std::unique_lock<std::mutex> lk(w.mu);
+        if (!w.retry) return WIFIRX_OK;                     // the usual case: no wait -- the worker may be busy with a good batch
+        w.cv.wait(lk, [&] { return !w.busy; });            // (a failed batch leaves the worker idle)
+        w.job = w.retry;
+        w.retry.reset();
+        w.busy = true;
+        w.cv.notify_all();
     }
     stream_worker_wait_idle(h);
     return stream_worker_take_error(h);
@@ -459,18 +437,16 @@ static int stream_resubmit_failed(wifirx_handle* h)
 // hand the current staging buffer to the worker (waits until the previous batch has left the device pipeline)
 static int stream_submit(wifirx_handle* h, bool flush)
 {
+    Worker& w = h->w;
     {
-        std::unique_lock<std::mutex> lk(h->mu);
-        h->cv.wait(lk, [&] { return !h->w_busy; });
-        h->w_job_ptr = reinterpret_cast<const float*>(h->ring[h->ring_cur]);
-        h->w_job_n = h->ring_fill;
-        h->w_job_flush = flush;
-        h->w_has_job = true;
-        h->w_busy = true;
-        h->cv.notify_all();
+        std::unique_lock<std::mutex> lk(w.mu);
+        w.cv.wait(lk, [&] { return !w.busy; });
+        w.job = Job{ w.ring[w.ring_cur].as<const float>(), w.ring_fill, flush };
+        w.busy = true;
+        w.cv.notify_all();
     }
-    h->ring_cur ^= 1;
-    h->ring_fill = 0;
+    w.ring_cur ^= 1;
+    w.ring_fill = 0;
     return WIFIRX_OK;
 }
 
@@ -507,10 +483,10 @@ static void stage_copy(void* dst_, const void* src_, size_t bytes)
 // staged (the worker's retry slot) and the next call starts with it again.
 static int stream_drain_staged(wifirx_handle* h)
 {
-    if (!h->w_started) return WIFIRX_OK;
+    if (!h->w.thread.joinable()) return WIFIRX_OK;
     int rc = stream_resubmit_failed(h);
     if (rc) return rc;
-    if (h->ring_fill) stream_submit(h, false);
+    if (h->w.ring_fill) stream_submit(h, false);
     stream_worker_wait_idle(h);
     return stream_worker_take_error(h);
 }
@@ -518,16 +494,16 @@ static int stream_drain_staged(wifirx_handle* h)
 extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_on_device)
 {
     if (!h) return WIFIRX_EINVAL;
-    h->push_consumed = 0;
+    h->st.push_consumed = 0;
     if (n > 0 && !iq) return fail(h, WIFIRX_EINVAL, "iq is null");
     const bool flush = (n == 0);
     // Device input, or no batching: the pipeline runs in the caller's thread, as one pass per push.
-    if (iq_on_device || h->stream_batch <= 0) {
+    if (iq_on_device || h->tune.stream_batch <= 0) {
         const int drc = stream_drain_staged(h);                   // samples staged before the mode changed
         if (drc) return drc;
         try {
             const int rc = stream_process(h, iq, n, iq_on_device, flush);
-            if (rc == WIFIRX_OK) h->push_consumed = n;
+            if (rc == WIFIRX_OK) h->st.push_consumed = n;
             return rc;
         } catch (const std::exception& e) {
             return fail(h, WIFIRX_ENOMEM, std::string("wifirx_push: ") + e.what());
@@ -540,36 +516,33 @@ extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_o
     int rc = stream_worker_take_error(h);
     if (rc) return rc;
     if ((rc = stream_resubmit_failed(h))) return rc;
-    const size_t cap = (size_t)h->stream_batch;
-    if (h->ring_cap != cap) {
+    Worker& w = h->w;
+    const size_t cap = (size_t)h->tune.stream_batch;
+    if (w.ring_cap != cap) {
         if ((rc = stream_drain_staged(h))) return rc;           // what was staged under the old batch size runs as a short batch
         HIP_TRY(h, hipSetDevice(h->device));
-        for (int k = 0; k < 2; k++) {
-            if (h->ring[k]) { (void)hipHostFree(h->ring[k]); h->ring[k] = nullptr; }
-        }
-        h->ring_cap = 0;
-        for (int k = 0; k < 2; k++) {
-            hipError_t e = hipHostMalloc((void**)&h->ring[k], cap * sizeof(float2), hipHostMallocDefault);
-            if (e != hipSuccess) {
-                for (int j = 0; j < 2; j++) if (h->ring[j]) { (void)hipHostFree(h->ring[j]); h->ring[j] = nullptr; }
-                return oom(h, "hipHostMalloc(staging)", e);
+        for (PinnedBuf& r : w.ring) r.reset();
+        w.ring_cap = 0;
+        for (PinnedBuf& r : w.ring) {
+            if ((rc = r.alloc(h, cap * sizeof(float2), "hipHostMalloc(staging)"))) {
+                for (PinnedBuf& q : w.ring) q.reset();
+                return rc;
             }
         }
-        h->ring_cap = cap;
-        h->ring_cur = 0;
+        w.ring_cap = cap;
+        w.ring_cur = 0;
     }
-    if (!h->w_started) {
-        h->w_stop = false;
+    if (!w.thread.joinable()) {
+        w.stop = false;
         try {
-            h->worker = std::thread(stream_worker_main, h);
+            w.thread = std::thread(stream_worker_main, h);
         } catch (const std::exception& e) {
             return fail(h, WIFIRX_ENOMEM, std::string("cannot start the stream worker thread: ") + e.what());
         }
-        h->w_started = true;
     }
     const float2* src = reinterpret_cast<const float2*>(iq);
     for (;;) {
-        if (h->ring_fill == cap) {
+        if (w.ring_fill == cap) {
             // hand-over.  The batch before this one must be through first (the worker takes one at a time); if it failed
             // it stays in the retry slot, this full buffer stays staged, and the call stops here: what it has staged so
             // far is consumed, the rest is the caller's to push again.
@@ -578,10 +551,10 @@ extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_o
             stream_submit(h, false);
         }
         if (!n) break;
-        const size_t take = std::min(n, cap - h->ring_fill);
-        stage_copy(h->ring[h->ring_cur] + h->ring_fill, src, take * sizeof(float2));
-        h->ring_fill += take;
-        h->push_consumed += take;
+        const size_t take = std::min(n, cap - w.ring_fill);
+        stage_copy(w.ring[w.ring_cur].as<float2>() + w.ring_fill, src, take * sizeof(float2));
+        w.ring_fill += take;
+        h->st.push_consumed += take;
         src += take;
         n -= take;
     }
@@ -593,9 +566,9 @@ extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_o
     return WIFIRX_OK;
 }
 
-extern "C" uint32_t wifirx_queued(const wifirx_handle* h) { return h ? h->n_queued.load(std::memory_order_acquire) : 0; }
+extern "C" uint32_t wifirx_queued(const wifirx_handle* h) { return h ? h->st.n_queued.load(std::memory_order_acquire) : 0; }
 
-extern "C" size_t wifirx_push_consumed(const wifirx_handle* h) { return h ? h->push_consumed : 0; }
+extern "C" size_t wifirx_push_consumed(const wifirx_handle* h) { return h ? h->st.push_consumed : 0; }
 
 extern "C" int wifirx_poll(wifirx_handle* h, wifirx_frame* frames, uint8_t* psdu, uint32_t psdu_stride,
                            uint8_t* idx, float* carrier, uint32_t cap, uint32_t* n_out)
@@ -624,9 +597,9 @@ extern "C" int wifirx_poll_ex(wifirx_handle* h, const wifirx_poll_out* out, uint
     float* csi = out->csi;
     const size_t per = (size_t)h->cfg.max_sym * 48;
     uint32_t n = 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    while (n < cap && !h->queue.empty()) {
-        PolledFrame& pf = h->queue.front();
+    std::lock_guard<std::mutex> lk(h->w.mu);
+    while (n < cap && !h->st.queue.empty()) {
+        PolledFrame& pf = h->st.queue.front();
         const uint8_t* bl = pf.blob->data();
         frames[n] = pf.fr;
         if (psdu && psdu_stride) {
@@ -644,10 +617,10 @@ extern "C" int wifirx_poll_ex(wifirx_handle* h, const wifirx_poll_out* out, uint
             if (pf.n_car) std::memcpy(carrier + n * per * 2, bl + pf.o_car, (size_t)pf.n_car * sizeof(float));
             std::memset(carrier + n * per * 2 + pf.n_car, 0, (per * 2 - pf.n_car) * sizeof(float));
         }
-        h->queue.pop_front();
+        h->st.queue.pop_front();
         n++;
     }
-    h->n_queued.store((uint32_t)h->queue.size(), std::memory_order_release);
+    h->st.n_queued.store((uint32_t)h->st.queue.size(), std::memory_order_release);
     *n_out = n;
     return WIFIRX_OK;
 }

@@ -70,19 +70,19 @@ extern "C" int wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* ps
             tr[t] = r;
         }
     }
-    int rc = ensure(h, &h->tx_meta, &h->tx_meta_bytes, meta_bytes);
+    int rc = h->stage.tx_meta.reserve(h, meta_bytes);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->tx_meta, meta.data(), meta_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->stage.tx_meta.p, meta.data(), meta_bytes, hipMemcpyHostToDevice, h->stream));
     const uint8_t* d_psdu = psdu;
     if (!psdu_on_device) {
-        if ((rc = ensure(h, &h->tx_psdu, &h->tx_psdu_bytes, psdu_extent))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->tx_psdu, psdu, psdu_extent, hipMemcpyHostToDevice, h->stream));
-        d_psdu = reinterpret_cast<const uint8_t*>(h->tx_psdu);
+        if ((rc = h->stage.tx_psdu.reserve(h, psdu_extent))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->stage.tx_psdu.p, psdu, psdu_extent, hipMemcpyHostToDevice, h->stream));
+        d_psdu = h->stage.tx_psdu.as<const uint8_t>();
     }
     // the host arrays (the caller's and `meta`) may go once this returns: wait for the copies, not for the kernel
     HIP_TRY(h, hipStreamSynchronize(h->stream));
 
-    uint8_t* dm = reinterpret_cast<uint8_t*>(h->tx_meta);
+    uint8_t* dm = h->stage.tx_meta.as<uint8_t>();
     a.psdu = d_psdu;
     a.len = reinterpret_cast<const uint32_t*>(dm + o_len);
     a.seeds = seeds ? dm + o_seed : nullptr;
