@@ -5,6 +5,7 @@
 #include <emmintrin.h>      // SSE2 streaming stores of the staging copy (x86-64 baseline)
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -25,13 +26,12 @@
 #include "wr_kernels.h"
 #include "wr_tx.h"
 
-// A finished frame of the stream: its record and where its outputs sit in the (shared) host copy of its batch.
-struct PolledFrame {
-    wifirx_frame                           fr;
-    std::shared_ptr<std::vector<uint8_t>>  blob;
-    size_t   o_psdu = 0, o_idx = 0, o_car = 0, o_csi = 0, o_stats = 0;     // byte offsets into *blob
-    uint32_t n_psdu = 0, n_idx = 0, n_car = 0;                              // bytes, bytes, floats
-};
+// The stream's per-frame outputs (stream_outs, wifirx_api_stream.inc) and the host copy of a batch of them, shared by its
+// frames: output o of frame k is the width[o] bytes at blob[off[o] + k * width[o]] (width 0: the handle did not produce o).
+// A PolledFrame is a finished frame of the stream: its record and its row k of the batch it came with.
+enum StreamOutput { SO_PSDU, SO_IDX, SO_CAR, SO_CSI, SO_STATS, SO_N };
+struct StreamBatch { std::vector<uint8_t> blob; size_t off[SO_N], width[SO_N]; };
+struct PolledFrame { wifirx_frame fr; std::shared_ptr<const StreamBatch> batch; uint32_t k; };
 
 struct PendingTrig {
     int64_t pos;        // absolute stream index of the trigger

@@ -84,6 +84,27 @@ static int stream_llr_reserve(wifirx_handle* h)
     return stream_alloc(h, h->st.llr, need, "hipMalloc(stream LLR rows)");
 }
 
+// The stream's per-frame outputs, in the order of StreamBatch and wifirx_poll_out: the device rows of out_cap triggers,
+// the bytes of a row (a caller's row is as long; psdu: psdu_stride), whether this handle produces the output, whether it
+// is zero-filled before the frame kernel, and the bytes of a frame's row worth bringing back (null: the whole row).
+struct StreamOut {
+    const DevBuf* dev; size_t pitch; bool produced, zero; size_t (*filled)(const wifirx_frame&);
+    size_t bytes(const wifirx_frame& f) const { return filled ? filled(f) : pitch; }
+};
+
+std::array<StreamOut, SO_N> stream_outs(const wifirx_handle* h)
+{
+    const StreamState& s = h->st;
+    const size_t per = (size_t)h->cfg.max_sym * 48;
+    return {{
+        { &s.psdu, 2048, true, false, [](const wifirx_frame& f) { return (f.flags & WIFIRX_F_DECODED) ? std::min<size_t>(f.psdu_len, 2048) : 0; } },
+        { &s.idx, per, h->tune.stream_want_idx != 0, true, [](const wifirx_frame& f) { return (size_t)f.n_sym_out * 48; } },
+        { &s.car, per * sizeof(float2), h->cfg.want_carrier != 0, true, [](const wifirx_frame& f) { return f.n_sym_out * 48 * sizeof(float2); } },
+        { &s.csi, 52 * sizeof(float2), true, true, nullptr },
+        { &s.stats, sizeof(float4), true, false, nullptr },
+    }};
+}
+
 // What a pass of the stream pipeline changes before its results are queued; put back when the pass fails, so that a
 // failed push has consumed nothing (include/wifirx.h, WIFIRX_P_STREAM_BATCH: ERRORS) and can simply be repeated.
 struct StreamRollback {
@@ -110,214 +131,172 @@ struct StreamRollback {
     }
 };
 
-}  // namespace
-
-// One pass of the stream pipeline over `n` more samples (what every push was before the staging ring existed).
-// All or nothing: on an error return the handle's stream state is what it was before the call.
-static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on_device, bool flush)
-{
-    static const bool trace = std::getenv("WIFIRX_TRACE") != nullptr;      // stage times of every push on stderr
-    auto t_prev = std::chrono::steady_clock::now();
-    auto stage = [&](const char* what) {
+// WIFIRX_TRACE: stage times of every push on stderr
+struct StageClock {
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    void operator()(const char* what)
+    {
+        static const bool trace = std::getenv("WIFIRX_TRACE") != nullptr;
         if (!trace) return;
         auto t = std::chrono::steady_clock::now();
         std::fprintf(stderr, "[wifirx_push] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
         t_prev = t;
-    };
+    }
+};
+
+// What the frames phase hands to the queue step: per pending trigger its record and whether no more samples can come
+struct FramePass { std::vector<wifirx_frame> fr; std::vector<char> final_; std::shared_ptr<const StreamBatch> batch; };
+
+}  // namespace
+
+// Detect: (1) detection over the tiles with not yet scanned samples (plus one tile of mask history); (2) the sync_short state
+// machine appends to st.pending: a trigger needs min_plateau+1 samples above the threshold in a row and > MIN_GAP since the last
+static int stream_detect(wifirx_handle* h, StageClock& stage)
+{
     StreamState& st = h->st;
-    {
-        std::string dead;
-        { std::lock_guard<std::mutex> lk(h->w.mu); if (st.dead) dead = st.dead_msg; }
-        if (!dead.empty()) return fail(h, WIFIRX_EDEAD, dead);       // (nothing is consumed, and repeating the push will not help)
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = stream_reserve(h, st.sfill + (int64_t)n + 64);
-    if (rc) return rc;
-    StreamRollback undo(h);
-    if (n) {
-        HIP_TRY(h, hipMemcpyAsync(st.sbuf.as<float2>() + st.sfill, iq, n * sizeof(float2),
-                                  iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        st.sfill += (int64_t)n;
-        { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.samples_in += n; }
-    }
-    stage("reserve + enqueue input copy");
-    if (!flush && h->tune.stream_batch > 0 && st.sbase + st.sfill - st.sprocessed < h->tune.stream_batch) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));         // the caller may reuse its buffer
-        undo.armed = false;
-        return WIFIRX_OK;                                       // keep collecting
-    }
-    st.sprocessed = st.sbase + st.sfill;
     const int64_t end_abs = st.sbase + st.sfill;
-    const int mp = h->cfg.min_plateau;
-
-    // (1) detection over the tiles that hold not yet scanned samples (plus one tile of mask history)
-    if (end_abs > st.sdetected) {
-        int64_t t_first = (st.sdetected - st.sbase) / 64;
-        if (t_first > 0) t_first -= 1;
-        const int64_t t_end = (st.sfill + 63) / 64;
-        const int64_t n_tiles = t_end - t_first;
-        HIP_TRY(h, wr_launch_stream_detect(h->stream, st.sbuf.as<float2>(), st.sfill, t_first, n_tiles, h->cfg.sensitivity,
-                                           st.above.as<uint64_t>(), st.A.as<float2>()));
-        std::vector<uint64_t> masks((size_t)n_tiles);
-        HIP_TRY(h, hipMemcpyAsync(masks.data(), st.above.as<uint64_t>() + t_first,
-                                  (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        stage("input copy + detect + masks");
-        // (2) sync_short state machine: a trigger needs min_plateau+1 consecutive samples above the
-        //     threshold and, after a previous trigger, more than MIN_GAP copied samples
-        uint64_t n_new_trig = 0;
-        for (int64_t tl = 0; tl < n_tiles; tl++) {
-            uint64_t m = masks[(size_t)tl], prev = tl > 0 ? masks[(size_t)tl - 1] : 0;
-            if (!m) continue;               // no sample of the tile above the threshold: no plateau can end in it (most tiles: 0.17 -> 0.03 ms per 4 M samples)
-            uint64_t hit = m;
-            for (int j = 1; j <= mp; j++) hit &= (m << j) | (j < 64 ? (prev >> (64 - j)) : 0);
-            const int64_t tile_abs = st.sbase + (t_first + tl) * 64;
-            while (hit) {
-                int l = __builtin_ctzll(hit);
-                hit &= hit - 1;
-                int64_t pos = tile_abs + l;
-                if (pos < st.sdetected || pos >= end_abs) continue;
-                if (pos - st.last_trig <= WIFIRX_MIN_GAP) continue;
-                st.pending.push_back({ pos, 0.0f, false });
-                st.last_trig = pos;
-                n_new_trig++;
-            }
+    if (end_abs <= st.sdetected) return WIFIRX_OK;
+    int64_t t_first = (st.sdetected - st.sbase) / 64;
+    if (t_first > 0) t_first -= 1;
+    const int64_t n_tiles = (st.sfill + 63) / 64 - t_first;
+    HIP_TRY(h, wr_launch_stream_detect(h->stream, st.sbuf.as<float2>(), st.sfill, t_first, n_tiles, h->cfg.sensitivity,
+                                       st.above.as<uint64_t>(), st.A.as<float2>()));
+    std::vector<uint64_t> masks((size_t)n_tiles);
+    HIP_TRY(h, hipMemcpyAsync(masks.data(), st.above.as<uint64_t>() + t_first,
+                              (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    stage("input copy + detect + masks");
+    uint64_t n_new_trig = 0;
+    for (int64_t tl = 0; tl < n_tiles; tl++) {
+        uint64_t m = masks[(size_t)tl], prev = tl > 0 ? masks[(size_t)tl - 1] : 0;
+        if (!m) continue;               // no sample of the tile above the threshold: no plateau can end in it (most tiles: 0.17 -> 0.03 ms per 4 M samples)
+        uint64_t hit = m;
+        for (int j = 1; j <= h->cfg.min_plateau; j++) hit &= (m << j) | (j < 64 ? (prev >> (64 - j)) : 0);
+        const int64_t tile_abs = st.sbase + (t_first + tl) * 64;
+        while (hit) {
+            int l = __builtin_ctzll(hit);
+            hit &= hit - 1;
+            int64_t pos = tile_abs + l;
+            if (pos < st.sdetected || pos >= end_abs) continue;
+            if (pos - st.last_trig <= WIFIRX_MIN_GAP) continue;
+            st.pending.push_back({ pos, 0.0f, false });
+            st.last_trig = pos;
+            n_new_trig++;
         }
-        st.sdetected = end_abs;
-        { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.frames_detected += n_new_trig; }
-        stage("host state machine");
     }
+    st.sdetected = end_abs;
+    { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.frames_detected += n_new_trig; }
+    stage("host state machine");
+    return WIFIRX_OK;
+}
 
-    // (3) every pending trigger whose samples are (partly) here
+// Frames: (3) the frame kernel + decode_mac over every pending trigger whose samples are (partly) here; records, outputs
+static int stream_frames(wifirx_handle* h, bool flush, StageClock& stage, FramePass& p)
+{
+    StreamState& st = h->st;
     const uint32_t np = (uint32_t)st.pending.size();
-    if (np) {
-        if ((rc = stream_out_reserve(h, np))) return rc;
-        const bool soft = h->tune.stream_soft != 0;
-        if (soft && (rc = stream_llr_reserve(h))) return rc;
-        std::vector<wr::StreamTrig> trig(np);
-        std::vector<char> final_(np);
-        for (uint32_t k = 0; k < np; k++) {
-            const int64_t pos = st.pending[k].pos;
-            int64_t L = end_abs - (pos - 16);
-            bool fin = flush;
-            if (k + 1 < np && st.pending[k + 1].pos - pos <= L) { L = st.pending[k + 1].pos - pos; fin = true; }
-            if (L >= WIFIRX_MAX_SAMPLES) { L = WIFIRX_MAX_SAMPLES; fin = true; }
-            trig[k].pos = pos - st.sbase;
-            trig[k].usable = L;
-            trig[k].cfo = st.pending[k].cfo;        // A[] of an earlier push is gone: reuse the value
-            trig[k].pad = st.pending[k].have_cfo;   // the device computed when it first saw the trigger
-            final_[k] = fin;
-        }
-        wr::DemodParams prm = params_of(h);
-        if (soft) prm.llr_bits = 6;                 // the stream's own LLR rows: every rate fits, whatever cfg.llr_bits says
-        const size_t per = (size_t)h->cfg.max_sym * 48;
-        HIP_TRY(h, hipMemcpyAsync(st.trig.p, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
-        // hard decisions as bytes only when the caller polls them (WIFIRX_P_STREAM_IDX); decode_mac reads the bit planes
-        uint8_t* d_idx = h->tune.stream_want_idx ? st.idx.as<uint8_t>() : nullptr;
-        if (d_idx) HIP_TRY(h, hipMemsetAsync(d_idx, 0, np * per, h->stream));
-        HIP_TRY(h, hipMemsetAsync(st.csi.p, 0, (size_t)np * 52 * sizeof(float2), h->stream));
-        if (st.car.p) HIP_TRY(h, hipMemsetAsync(st.car.p, 0, np * per * sizeof(float2), h->stream));
-        const wr::DemodOut dout = { st.frames.as<wifirx_frame>(), d_idx, soft ? st.llr.as<float>() : nullptr,
-                                    st.car.as<float2>(), st.csi.as<float2>(),
-                                    st.stats.as<float4>(), st.hbits.as<uint32_t>() };
-        HIP_TRY(h, wr_launch_demod_stream(h->stream, st.sbuf.as<float2>(), st.sfill, st.trig.as<wr::StreamTrig>(), np,
-                                          &prm, st.A.as<float2>(), &dout));
-        wifirx_out o{};
-        o.frames = st.frames.as<wifirx_frame>();
-        o.idx = d_idx;
-        o.hbits = st.hbits.as<uint32_t>();
-        o.psdu = st.psdu.as<uint8_t>();
-        o.psdu_stride = 2048;
-        o.on_device = 1;
-        o.llr = soft ? st.llr.as<float>() : nullptr;
-        stage("enqueue frame kernel");
-        if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
-        stage("frame kernel + decode_mac");
-        // the frame records first: they say how much of every output row is worth bringing back (rows are max_sym
-        // symbols and 2048 bytes wide on the device, a frame usually fills a fraction of that)
-        std::vector<wifirx_frame> fr(np);
-        HIP_TRY(h, hipMemcpyAsync(fr.data(), st.frames.p, np * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        size_t w_sym = 0, w_psdu = 0;
-        for (uint32_t k = 0; k < np; k++) {
-            w_sym = std::max<size_t>(w_sym, (size_t)fr[k].n_sym_out * 48);
-            if (fr[k].flags & WIFIRX_F_DECODED) w_psdu = std::max<size_t>(w_psdu, std::min<size_t>(fr[k].psdu_len, 2048));
-        }
-        // rows cut to their filled width are packed on the device (2-D copies device -> device), then leave in one
-        // piece for a pinned host buffer: a 2-D copy to pageable memory goes row by row and costs milliseconds.
-        // Hard decisions travel only when the stream wants them (WIFIRX_P_STREAM_IDX), equalised points only for
-        // handles created with want_carrier.
-        auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-        const size_t w_idx = h->tune.stream_want_idx ? w_sym : 0;
-        const size_t w_car = st.car.p ? w_sym * 2 * sizeof(float) : 0;
-        const size_t o_psdu = 0, b_psdu = up16((size_t)np * w_psdu);
-        const size_t o_idx = o_psdu + b_psdu, b_idx = up16((size_t)np * w_idx);
-        const size_t o_car = o_idx + b_idx, b_car = up16((size_t)np * w_car);
-        const size_t o_csi = o_car + b_car, b_csi = up16((size_t)np * 52 * sizeof(float2));
-        const size_t o_stats = o_csi + b_csi, b_stats = up16((size_t)np * sizeof(float4));
-        const size_t b_all = o_stats + b_stats;
-        if ((rc = st.pack.reserve(h, b_all))) return rc;
-        if ((rc = st.host.reserve(h, b_all))) return rc;
-        uint8_t* pk = st.pack.as<uint8_t>();
-        if (w_psdu)
-            HIP_TRY(h, hipMemcpy2DAsync(pk + o_psdu, w_psdu, st.psdu.p, 2048, w_psdu, np, hipMemcpyDeviceToDevice, h->stream));
-        if (w_idx)
-            HIP_TRY(h, hipMemcpy2DAsync(pk + o_idx, w_idx, st.idx.p, per, w_idx, np, hipMemcpyDeviceToDevice, h->stream));
-        if (w_car)
-            HIP_TRY(h, hipMemcpy2DAsync(pk + o_car, w_car, st.car.p, per * 2 * sizeof(float), w_car, np, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(pk + o_csi, st.csi.p, (size_t)np * 52 * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(pk + o_stats, st.stats.p, (size_t)np * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(st.host.p, st.pack.p, b_all, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        stage("outputs to host");
-        // one heap copy of the batch's outputs, shared by its frames (no per-frame allocations)
-        auto blob = std::make_shared<std::vector<uint8_t>>(st.host.as<const uint8_t>(), st.host.as<const uint8_t>() + b_all);
-        std::vector<PendingTrig> keep;
-        undo.armed = false;                                 // nothing below can fail: the pass is committed
-        std::lock_guard<std::mutex> lk(h->w.mu);            // queue + statistics
-        for (uint32_t k = 0; k < np; k++) {
-            wifirx_frame f = fr[k];
-            const bool complete = (f.flags & WIFIRX_F_COMPLETE) != 0;
-            const bool truncated = (f.flags & WIFIRX_F_TRUNCATED) != 0;
-            // a frame is settled when it is complete, when it failed for a reason more samples cannot
-            // cure, or when no more samples can come (next trigger / MAX_SAMPLES / flush)
-            if (!(complete || !truncated || final_[k])) {
-                PendingTrig pt = st.pending[k];
-                pt.cfo = f.cfo_coarse;
-                pt.have_cfo = true;
-                keep.push_back(pt);
-                continue;
-            }
-            f.trigger = (int32_t)(st.pending[k].pos & 0x7fffffff);
-            PolledFrame pf;
-            pf.fr = f;
-            pf.blob = blob;
-            pf.n_psdu = (f.flags & WIFIRX_F_DECODED) ? (uint32_t)std::min<size_t>(f.psdu_len, 2048) : 0;
-            pf.o_psdu = o_psdu + (size_t)k * w_psdu;
-            pf.n_idx = w_idx ? (uint32_t)f.n_sym_out * 48 : 0;
-            pf.o_idx = o_idx + (size_t)k * w_idx;
-            pf.n_car = w_car ? (uint32_t)f.n_sym_out * 96 : 0;
-            pf.o_car = o_car + (size_t)k * w_car;
-            pf.o_csi = o_csi + (size_t)k * 52 * sizeof(float2);
-            pf.o_stats = o_stats + (size_t)k * sizeof(float4);
-            h->stats.frames_signal_ok += (f.flags & WIFIRX_F_SIGNAL) != 0;
-            h->stats.frames_complete += complete;
-            h->stats.frames_crc_ok += (f.flags & WIFIRX_F_CRC_OK) != 0;
-            h->stats.frames_dropped += (f.flags & WIFIRX_F_CRC_OK) == 0;
-            st.queue.push_back(std::move(pf));
-        }
-        st.n_queued.store((uint32_t)st.queue.size(), std::memory_order_release);
-        st.pending.swap(keep);
-        stage("queue frames");
+    if (!np) return WIFIRX_OK;
+    int rc;
+    if ((rc = stream_out_reserve(h, np))) return rc;
+    const bool soft = h->tune.stream_soft != 0;
+    if (soft && (rc = stream_llr_reserve(h))) return rc;
+    const int64_t end_abs = st.sbase + st.sfill;
+    std::vector<wr::StreamTrig> trig(np);
+    for (uint32_t k = 0; k < np; k++) {
+        const int64_t pos = st.pending[k].pos;
+        int64_t L = end_abs - (pos - 16);
+        bool fin = flush;
+        if (k + 1 < np && st.pending[k + 1].pos - pos <= L) { L = st.pending[k + 1].pos - pos; fin = true; }
+        if (L >= WIFIRX_MAX_SAMPLES) { L = WIFIRX_MAX_SAMPLES; fin = true; }
+        trig[k].pos = pos - st.sbase;
+        trig[k].usable = L;
+        trig[k].cfo = st.pending[k].cfo;        // A[] of an earlier push is gone: reuse the value
+        trig[k].pad = st.pending[k].have_cfo;   // the device computed when it first saw the trigger
+        p.final_.push_back(fin);
     }
+    wr::DemodParams prm = params_of(h);
+    if (soft) prm.llr_bits = 6;                 // the stream's own LLR rows: every rate fits, whatever cfg.llr_bits says
+    HIP_TRY(h, hipMemcpyAsync(st.trig.p, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
+    const std::array<StreamOut, SO_N> outs = stream_outs(h);
+    for (const StreamOut& so : outs)
+        if (so.produced && so.zero) HIP_TRY(h, hipMemsetAsync(so.dev->p, 0, np * so.pitch, h->stream));
+    // hard decisions as bytes only when the caller polls them (WIFIRX_P_STREAM_IDX); decode_mac reads the bit planes
+    uint8_t* d_idx = outs[SO_IDX].produced ? st.idx.as<uint8_t>() : nullptr;
+    float* d_llr = soft ? st.llr.as<float>() : nullptr;
+    const wr::DemodOut dout = { st.frames.as<wifirx_frame>(), d_idx, d_llr, st.car.as<float2>(), st.csi.as<float2>(),
+                                st.stats.as<float4>(), st.hbits.as<uint32_t>() };
+    HIP_TRY(h, wr_launch_demod_stream(h->stream, st.sbuf.as<float2>(), st.sfill, st.trig.as<wr::StreamTrig>(), np,
+                                      &prm, st.A.as<float2>(), &dout));
+    const wifirx_out o = { st.frames.as<wifirx_frame>(), d_idx, d_llr, nullptr, st.psdu.as<uint8_t>(), 2048, 1,
+                           nullptr, nullptr, st.hbits.as<uint32_t>() };
+    stage("enqueue frame kernel");
+    if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
+    stage("frame kernel + decode_mac");
+    // the frame records first: they say how much of every output row (max_sym symbols, 2048 bytes) is worth bringing back.
+    // Each output's rows are cut to the batch's widest filled row and packed on the device, then leave in one piece for a
+    // pinned host buffer: a 2-D copy to pageable memory goes row by row and costs milliseconds.
+    p.fr.resize(np);
+    HIP_TRY(h, hipMemcpyAsync(p.fr.data(), st.frames.p, np * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    auto b = std::make_shared<StreamBatch>();
+    size_t total = 0;
+    for (int i = 0; i < SO_N; i++) {         // (widths start at 0: make_shared value-initialises)
+        for (uint32_t k = 0; outs[i].produced && k < np; k++) b->width[i] = std::max(b->width[i], outs[i].bytes(p.fr[k]));
+        b->off[i] = total;
+        total += (np * b->width[i] + 15) / 16 * 16;
+    }
+    if ((rc = st.pack.reserve(h, total)) || (rc = st.host.reserve(h, total))) return rc;
+    for (int i = 0; i < SO_N; i++) {
+        const size_t w = b->width[i];
+        uint8_t* dst = st.pack.as<uint8_t>() + b->off[i];
+        if (w && outs[i].filled) HIP_TRY(h, hipMemcpy2DAsync(dst, w, outs[i].dev->p, outs[i].pitch, w, np, hipMemcpyDeviceToDevice, h->stream));
+        else if (w) HIP_TRY(h, hipMemcpyAsync(dst, outs[i].dev->p, np * w, hipMemcpyDeviceToDevice, h->stream));     // fixed rows: packed already
+    }
+    HIP_TRY(h, hipMemcpyAsync(st.host.p, st.pack.p, total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    stage("outputs to host");
+    b->blob.assign(st.host.as<const uint8_t>(), st.host.as<const uint8_t>() + total);     // shared by the batch's frames
+    p.batch = std::move(b);
+    return WIFIRX_OK;
+}
 
-    // (4) carry: samples a pending trigger still needs + the detection history.  The pass is COMMITTED here (frames queued,
-    //     fill and frontier advanced): nothing below may come back as an error, which every caller reads as "nothing was
-    //     consumed, hand the samples in again" -- that would double them (include/wifirx.h, WIFIRX_P_STREAM_BATCH: ERRORS).
-    //     A failure before the buffer has been touched leaves base and fill as they are (the buffer keeps more than it
-    //     must; the next pass moves it); one after the move began leaves a buffer that cannot be trusted: the stream is
-    //     marked dead and every later push says so (WIFIRX_EDEAD, never "retry").
-    undo.armed = false;
+// Queue: the settled frames go to wifirx_poll, the others stay pending with the coarse CFO the device found (cannot fail)
+static void stream_queue(wifirx_handle* h, const FramePass& p, StageClock& stage)
+{
+    StreamState& st = h->st;
+    if (p.fr.empty()) return;
+    std::vector<PendingTrig> keep;
+    std::lock_guard<std::mutex> lk(h->w.mu);            // queue + statistics
+    for (uint32_t k = 0; k < p.fr.size(); k++) {
+        wifirx_frame f = p.fr[k];
+        const bool complete = (f.flags & WIFIRX_F_COMPLETE) != 0;
+        const bool truncated = (f.flags & WIFIRX_F_TRUNCATED) != 0;
+        // a frame is settled when it is complete, when it failed for a reason more samples cannot
+        // cure, or when no more samples can come (next trigger / MAX_SAMPLES / flush)
+        if (!(complete || !truncated || p.final_[k])) {
+            keep.push_back({ st.pending[k].pos, f.cfo_coarse, true });
+            continue;
+        }
+        f.trigger = (int32_t)(st.pending[k].pos & 0x7fffffff);
+        h->stats.frames_signal_ok += (f.flags & WIFIRX_F_SIGNAL) != 0;
+        h->stats.frames_complete += complete;
+        h->stats.frames_crc_ok += (f.flags & WIFIRX_F_CRC_OK) != 0;
+        h->stats.frames_dropped += (f.flags & WIFIRX_F_CRC_OK) == 0;
+        st.queue.push_back(PolledFrame{ f, p.batch, k });
+    }
+    st.n_queued.store((uint32_t)st.queue.size(), std::memory_order_release);
+    st.pending.swap(keep);
+    stage("queue frames");
+}
+
+// Carry: (4) samples a pending trigger still needs + the detection history.  It runs behind the commit (frames queued, fill
+// and frontier advanced) and reports no error, which every caller reads as "nothing was consumed, hand the samples in
+// again" -- that would double them (include/wifirx.h, WIFIRX_P_STREAM_BATCH: ERRORS).  A failure before the buffer has
+// been touched leaves base and fill as they are (the next pass moves it); one after the move began leaves a buffer that
+// cannot be trusted: the stream is marked dead and every later push says so (WIFIRX_EDEAD, never "retry").
+static void stream_carry(wifirx_handle* h, StageClock& stage)
+{
+    StreamState& st = h->st;
     int64_t keep_from = st.sdetected - kHistory;
     if (!st.pending.empty()) keep_from = std::min(keep_from, st.pending.front().pos - 16);
     if (keep_from < st.sbase) keep_from = st.sbase;
@@ -353,6 +332,37 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
         }
     }
     stage("carry");
+}
+
+// One pass of the stream pipeline over `n` more samples (what every push was before the staging ring existed).
+// All or nothing: on an error return the handle's stream state is what it was before the call.
+static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on_device, bool flush)
+{
+    StageClock stage;
+    StreamState& st = h->st;
+    { std::lock_guard<std::mutex> lk(h->w.mu); if (st.dead) return fail(h, WIFIRX_EDEAD, st.dead_msg); }   // (repeating will not help)
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = stream_reserve(h, st.sfill + (int64_t)n + 64);
+    if (rc) return rc;
+    StreamRollback undo(h);
+    if (n) {
+        HIP_TRY(h, hipMemcpyAsync(st.sbuf.as<float2>() + st.sfill, iq, n * sizeof(float2),
+                                  iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        st.sfill += (int64_t)n;
+        { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.samples_in += n; }
+    }
+    stage("reserve + enqueue input copy");
+    const bool run = flush || h->tune.stream_batch <= 0 || st.sbase + st.sfill - st.sprocessed >= h->tune.stream_batch;
+    if (!run) HIP_TRY(h, hipStreamSynchronize(h->stream));     // keep collecting (WIFIRX_P_STREAM_BATCH); the caller may reuse its buffer
+    else st.sprocessed = st.sbase + st.sfill;
+    FramePass pass;
+    if (run && (rc = stream_detect(h, stage))) return rc;
+    if (run && (rc = stream_frames(h, flush, stage, pass))) return rc;
+    undo.armed = false;                 // the commit: the samples are consumed and the frames queued below; nothing after it fails
+    if (run) {
+        stream_queue(h, pass, stage);
+        stream_carry(h, stage);
+    }
     return WIFIRX_OK;
 }
 
@@ -589,33 +599,22 @@ extern "C" int wifirx_poll_ex(wifirx_handle* h, const wifirx_poll_out* out, uint
     if (!h || !n_out || !out) return WIFIRX_EINVAL;
     *n_out = 0;
     if (cap && !out->frames) return fail(h, WIFIRX_EINVAL, "frames is null");
-    wifirx_frame* frames = out->frames;
-    uint8_t* psdu = out->psdu;
-    const uint32_t psdu_stride = out->psdu_stride;
-    uint8_t* idx = out->idx;
-    float* carrier = out->carrier;
-    float* csi = out->csi;
-    const size_t per = (size_t)h->cfg.max_sym * 48;
+    uint8_t* const dst[SO_N] = { out->psdu, out->idx, reinterpret_cast<uint8_t*>(out->carrier),
+                                 reinterpret_cast<uint8_t*>(out->csi), reinterpret_cast<uint8_t*>(out->sym_stats) };
+    const std::array<StreamOut, SO_N> outs = stream_outs(h);
     uint32_t n = 0;
     std::lock_guard<std::mutex> lk(h->w.mu);
     while (n < cap && !h->st.queue.empty()) {
-        PolledFrame& pf = h->st.queue.front();
-        const uint8_t* bl = pf.blob->data();
-        frames[n] = pf.fr;
-        if (psdu && psdu_stride) {
-            const size_t c = std::min<size_t>(pf.n_psdu, psdu_stride);
-            if (c) std::memcpy(psdu + (size_t)n * psdu_stride, bl + pf.o_psdu, c);
-            std::memset(psdu + (size_t)n * psdu_stride + c, 0, psdu_stride - c);
-        }
-        if (idx) {
-            if (pf.n_idx) std::memcpy(idx + n * per, bl + pf.o_idx, pf.n_idx);
-            std::memset(idx + n * per + pf.n_idx, 0, per - pf.n_idx);
-        }
-        if (csi) std::memcpy(csi + (size_t)n * 104, bl + pf.o_csi, 104 * sizeof(float));
-        if (out->sym_stats) std::memcpy(out->sym_stats + (size_t)n * 4, bl + pf.o_stats, 4 * sizeof(float));
-        if (carrier) {
-            if (pf.n_car) std::memcpy(carrier + n * per * 2, bl + pf.o_car, (size_t)pf.n_car * sizeof(float));
-            std::memset(carrier + n * per * 2 + pf.n_car, 0, (per * 2 - pf.n_car) * sizeof(float));
+        const PolledFrame& pf = h->st.queue.front();
+        const StreamBatch& b = *pf.batch;
+        out->frames[n] = pf.fr;
+        // the caller's row: what the frame filled, as far as its batch brought it back; zeros behind it
+        for (int o = 0; o < SO_N; o++) {
+            if (!dst[o]) continue;
+            const size_t row = o == SO_PSDU ? out->psdu_stride : outs[o].pitch;
+            const size_t c = std::min({ outs[o].bytes(pf.fr), b.width[o], row });
+            if (c) std::memcpy(dst[o] + n * row, b.blob.data() + b.off[o] + pf.k * b.width[o], c);
+            std::memset(dst[o] + n * row + c, 0, row - c);
         }
         h->st.queue.pop_front();
         n++;

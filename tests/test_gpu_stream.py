@@ -428,7 +428,12 @@ def test_block_ends_on_a_dead_stream(monkeypatch):
         assert blk.stream_dead and "lost" in blk.last_error
         n_calls, n_err = len(calls), blk.push_errors
         assert n_err == 1                            # one failed push, not a spin of them
-        assert blk.work([x[:4096]], []) == -1 if not raise_on_error else True
+        if raise_on_error:
+            with pytest.raises(capi.WifiRxError) as ei:
+                blk.work([x[:4096]], [])
+            assert ei.value.code == capi.EDEAD
+        else:
+            assert blk.work([x[:4096]], []) == -1
         blk.stop()                                   # no flush attempts on a dead stream
         assert blk.push_errors <= n_err + 1
         assert 1 <= len(got) <= len(psdus)           # what was finished before the failure was published
