@@ -25,6 +25,7 @@
 #include "wifirx.h"
 #include "wr_kernels.h"
 #include "wr_tx.h"
+#include "wr_channel.h"
 
 // The stream's per-frame outputs (stream_outs, wifirx_api_stream.inc) and the host copy of a batch of them, shared by its
 // frames: output o of frame k is the width[o] bytes at blob[off[o] + k * width[o]] (width 0: the handle did not produce o).
@@ -112,6 +113,7 @@ struct Staging {
     DevBuf iq, frames, idx, llr, car, csi, stats, hbits;
     DevBuf off;                     // slot offsets of wifirx_demod_batch_v
     DevBuf tx_psdu, tx_meta;        // wifirx_tx_batch: host PSDUs; lengths, seeds, row offsets
+    DevBuf ch_meta;                 // wifirx_channel: host taps, phase increments, row offsets, tile bases
 };
 
 // decode workspace
@@ -588,3 +590,4 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_decode.inc"
 #include "wifirx_api_stream.inc"
 #include "wifirx_api_tx.inc"
+#include "wifirx_api_channel.inc"

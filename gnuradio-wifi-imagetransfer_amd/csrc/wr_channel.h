@@ -1,0 +1,30 @@
+// wr_channel.h -- launch interface of the channel kernel (wr_channel.hip; internal, not the C ABI)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace wr {
+
+// one wifirx_channel call, every pointer on the device.  Sample g of the buffers lies at in[g] / out[g].  Tiles are cut per
+// row on pair-aligned output indices: tile k of row r covers [a_r + k CH_TILE, a_r + (k+1) CH_TILE) clipped to the row, with
+// a_r = the row start rounded down so that (a_r + shift) is even (shift = 1 when `out` is 8 but not 16 bytes aligned).
+struct ChanArgs {
+    const float2*   in;
+    float2*         out;
+    const float2*   taps;         // [n_tap_sets][n_taps]; row r uses set r % n_tap_sets
+    const float*    cfo;          // [n_rows] rad/sample, or null: 0
+    const uint64_t* row_off;      // [n_rows + 1] or null: row r = [r row_len, (r+1) row_len)
+    const uint64_t* tile_base;    // row_off form: [n_rows + 1] first tile of every row (tiles of row r: [tile_base[r], tile_base[r+1]))
+    uint64_t        row_len, tiles_per_row;       // fixed-row form
+    uint64_t        phase0, seed, sample0;
+    uint32_t        n_rows, n_taps, n_tap_sets;
+    int32_t         shift;
+    float           gain, noise;
+};
+
+}  // namespace wr
+
+extern "C" {
+hipError_t wr_launch_channel(hipStream_t st, const wr::ChanArgs* args, uint64_t n_tiles);
+uint32_t   wr_channel_tile_samples(void);
+}

@@ -1,0 +1,178 @@
+// wr_channel.hip -- GNU Radio's channels.channel_model on the device (the block between TX and RX of the reference's
+// loop-back, gnu_radio/IRS_tranceiver.py:282-288): per row, the multipath FIR, then the frequency-offset mixer, then the
+// noise adder, in the float32 arithmetic of NUMERICS.md rule 17.
+//
+// Work split (the shape of wr_tx.hip): the output of every row is cut into tiles of CH_TILE consecutive samples on
+// pair-aligned indices; one workgroup owns one tile.  With more than one tap it first stages the tile's input and the
+// n_taps - 1 samples before it (zeros before the row start: every row is its own burst) in LDS; then every lane produces
+// CH_TILE / 512 pairs of consecutive samples and writes each with one 16-byte store.  The phase is fixed point (a uint64
+// in 2^-64 turns: exact for any row length), the noise is wr_synth.hip's Philox4x32-10 + Box-Muller on the counter
+// (pair index of the sample, row).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "wr_device.h"     // sp_sincos (rule 1)
+#include "wr_rng.h"        // philox4x32_10, u01
+#include "wr_channel.h"
+
+namespace wr {
+
+#define CH_TILE     2048     // samples per workgroup: four pairs per lane of a 256-lane group
+#define CH_MAX_TAPS 64
+
+constexpr float CH_PHASE_SCALE = (float)(6.283185307179586 / 4294967296.0);      // 2 pi / 2^32: radians per unit of P >> 32
+
+// rule 17: plain float32 products and sums, no fma (-ffp-contract=off keeps them apart)
+__device__ __forceinline__ float2 ch_mul(float2 a, float2 b)
+{
+    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+
+__device__ __forceinline__ float2 ch_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+
+// sample n of the row after the FIR: gain * (s * exp(j phi(n)))
+__device__ __forceinline__ float2 ch_rotate(float2 s, uint64_t P, float gain)
+{
+    float sn, cs;
+    sp_sincos((float)(int32_t)(uint32_t)(P >> 32) * CH_PHASE_SCALE, sn, cs);
+    const float2 y = ch_mul(s, make_float2(cs, sn));
+    return make_float2(gain * y.x, gain * y.y);
+}
+
+// rad/sample -> phase increment in 2^-64 turns: llround(cfo / (2 pi) * 2^64) as a uint64, the turns reduced to [-1/2, 1/2]
+// first (exact), so that any finite cfo has one (+-1/2 turn = 2^63).  IEEE double, once per workgroup.
+__device__ __forceinline__ uint64_t ch_phase_inc(float cfo)
+{
+    double f = (double)cfo / 6.283185307179586;
+    f -= __builtin_rint(f);
+    const double v = f * 0x1p64;
+    if (v >= 0x1p63 || v <= -0x1p63) return 1ull << 63;
+    return (uint64_t)(int64_t)__builtin_round(v);          // round: half away from zero, as llround
+}
+
+// one Box-Muller sample of wr_synth.hip: radius from ua, angle from ub, each component h * r * (cos | sin)
+__device__ __forceinline__ float2 ch_noise(uint32_t ua, uint32_t ub, float h)
+{
+    const float r = sqrtf(-2.0f * logf(u01(ua)));
+    float s, c;
+    sincosf(6.283185307179586f * u01(ub), &s, &c);
+    return make_float2(h * r * c, h * r * s);
+}
+
+__device__ __forceinline__ uint4 ch_draw(uint64_t pair, uint32_t row, uint2 key)
+{
+    return philox4x32_10(make_uint4((uint32_t)pair, row, (uint32_t)(pair >> 32), 0u), key);
+}
+
+template <bool STAGE>     // STAGE: n_taps > 1, the input tile and its halo go through LDS
+__global__ __launch_bounds__(256)
+void channel_kernel(const ChanArgs a)
+{
+    __shared__ float2 xs[STAGE ? CH_TILE + CH_MAX_TAPS - 1 : 1];
+    __shared__ float2 tp[CH_MAX_TAPS];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t tile = blockIdx.x;
+
+    // ---- the tile's row and its place in it (uniform: scalar loads) ----
+    uint32_t r;
+    uint64_t k;
+    if (a.row_off) {
+        uint32_t lo = 0, hi = a.n_rows;              // the last row whose first tile is <= tile: it has tiles, so it owns it
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (a.tile_base[mid] <= tile) lo = mid; else hi = mid;
+        }
+        r = lo;
+        k = tile - a.tile_base[r];
+    } else {
+        r = (uint32_t)(tile / a.tiles_per_row);
+        k = tile - (uint64_t)r * a.tiles_per_row;
+    }
+    const int64_t rs = a.row_off ? (int64_t)a.row_off[r] : (int64_t)r * (int64_t)a.row_len;
+    const int64_t re = a.row_off ? (int64_t)a.row_off[r + 1] : rs + (int64_t)a.row_len;
+    const int64_t gt = (((rs + a.shift) & ~(int64_t)1) - a.shift) + (int64_t)k * CH_TILE;      // first sample of the tile
+    const uint32_t L = a.n_taps;
+
+    if (tid < L) tp[tid] = a.taps[(size_t)(r % a.n_tap_sets) * L + tid];
+    if constexpr (STAGE) {
+        const int64_t s0 = gt - (int64_t)(L - 1);
+        for (uint32_t i = tid; i < CH_TILE + L - 1; i += 256) {
+            const int64_t g = s0 + (int64_t)i;
+            xs[i] = (g >= rs && g < re) ? a.in[g] : make_float2(0.0f, 0.0f);
+        }
+    }
+    __syncthreads();
+
+    const uint64_t inc = a.cfo ? ch_phase_inc(a.cfo[r]) : 0;
+    const uint2 key = make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    const float h = 0.70710678118654752f * a.noise;
+    float4* out4 = reinterpret_cast<float4*>(a.out - a.shift);
+#pragma unroll
+    for (int u = 0; u < CH_TILE / 512; u++) {
+        const int32_t j = 2 * (256 * u + (int32_t)tid);           // tile offset of the lane's first sample
+        const int64_t g = gt + j;
+        const bool in0 = g >= rs && g < re, in1 = g + 1 >= rs && g + 1 < re;
+        if (!in0 && !in1) continue;
+
+        // FIR, ascending k from the k = 0 product
+        float2 s0, s1;
+        if constexpr (STAGE) {
+            const int32_t b = j + (int32_t)L - 1;                  // xs index of the input at g
+            float2 prev = xs[b + 1];
+            float2 cur = xs[b];
+            s0 = ch_mul(tp[0], cur);
+            s1 = ch_mul(tp[0], prev);
+            for (uint32_t q = 1; q < L; q++) {
+                prev = cur;
+                cur = xs[b - (int32_t)q];
+                s0 = ch_add(s0, ch_mul(tp[q], cur));
+                s1 = ch_add(s1, ch_mul(tp[q], prev));
+            }
+        } else {
+            float2 x0 = make_float2(0.0f, 0.0f), x1 = x0;
+            if (in0 && in1 && ((reinterpret_cast<uintptr_t>(a.in + g) & 15) == 0)) {
+                const float4 v = *reinterpret_cast<const float4*>(a.in + g);
+                x0 = make_float2(v.x, v.y);
+                x1 = make_float2(v.z, v.w);
+            } else {
+                if (in0) x0 = a.in[g];
+                if (in1) x1 = a.in[g + 1];
+            }
+            s0 = ch_mul(tp[0], x0);
+            s1 = ch_mul(tp[0], x1);
+        }
+
+        // mixer: P(n) = phase0 + inc n mod 2^64, n = sample index in the row
+        const uint64_t n0 = (uint64_t)(g - rs);
+        const uint64_t P0 = a.phase0 + inc * n0;
+        float2 y0 = ch_rotate(s0, P0, a.gain);
+        float2 y1 = ch_rotate(s1, P0 + inc, a.gain);
+
+        // noise adder: sample m = sample0 + n draws from the counter (m >> 1, row), first or second pair by m & 1
+        if (a.noise != 0.0f) {                                     // not 0 * w: a Box-Muller radius of inf would give NaN
+            const uint64_t m0 = a.sample0 + n0, m1 = m0 + 1;
+            const bool odd = (m0 & 1) != 0;                        // the same in every lane of the tile
+            const uint4 d0 = ch_draw(m0 >> 1, r, key);
+            const uint4 d1 = odd ? ch_draw(m1 >> 1, r, key) : d0;
+            y0 = ch_add(y0, ch_noise(odd ? d0.z : d0.x, odd ? d0.w : d0.y, h));
+            y1 = ch_add(y1, ch_noise(odd ? d1.x : d0.z, odd ? d1.y : d0.w, h));
+        }
+
+        if (in0 && in1) out4[(g + a.shift) >> 1] = make_float4(y0.x, y0.y, y1.x, y1.y);
+        else if (in0) a.out[g] = y0;
+        else a.out[g + 1] = y1;
+    }
+}
+
+}  // namespace wr
+
+extern "C" hipError_t wr_launch_channel(hipStream_t st, const wr::ChanArgs* args, uint64_t n_tiles)
+{
+    if (n_tiles == 0) return hipSuccess;
+    const dim3 grid((unsigned)n_tiles), block(256);
+    if (args->n_taps > 1) hipLaunchKernelGGL(wr::channel_kernel<true>, grid, block, 0, st, *args);
+    else hipLaunchKernelGGL(wr::channel_kernel<false>, grid, block, 0, st, *args);
+    return hipGetLastError();
+}
+
+extern "C" uint32_t wr_channel_tile_samples(void) { return CH_TILE; }

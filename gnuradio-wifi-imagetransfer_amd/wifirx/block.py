@@ -328,3 +328,95 @@ class wifi_phy_tx(grshim.sync_block):
     def close(self):
         """Release the library handle."""
         self._rx.close()
+
+
+class channel_model(grshim.sync_block):
+    """Drop-in for GNU Radio's ``channels.channel_model`` (the loop-back channel of gnu_radio/IRS_tranceiver.py:282-288) on the
+    device: multipath FIR (``taps``), frequency offset (``frequency_offset`` in cycles/sample, as the flowgraph's
+    ``epsilon*freq/10e6``) and complex Gaussian noise of variance ``noise_voltage**2``, in that order; ``samp_in`` ->
+    ``samp_out``.  Arithmetic: NUMERICS.md rule 17 (wifirx_channel).
+
+    Every ``work()`` is one wifirx_channel call on one row: the last ``len(taps) - 1`` input samples kept from before, then the
+    new chunk.  The row's ``sample0`` is its stream index and its ``phase0`` the phase carried from the previous call (a uint64
+    in 2^-64 turns), so the output does not depend on how the stream is cut into calls; the outputs of the kept samples are
+    dropped.  A setter takes effect at the next ``work()``; a new frequency keeps the phase continuous.
+    ``epsilon`` (the sample-rate offset) must be 1.0: the fractional resampler is not implemented."""
+
+    MAX_TAPS = 64
+
+    def __init__(self, noise_voltage=1.0, frequency_offset=0.0, epsilon=1.0, taps=(1.0,), noise_seed=0, block_tags=False,
+                 device=0):
+        grshim.sync_block.__init__(self, name="channel_model", in_sig=[np.complex64], out_sig=[np.complex64])
+        self.set_timing_offset(epsilon)
+        self.set_noise_voltage(noise_voltage)
+        self.set_frequency_offset(frequency_offset)
+        self.set_taps(taps)
+        self.noise_seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
+        self.block_tags = bool(block_tags)          # tags are not propagated by the shim; accepted for the signature
+        self._rx = capi.WifiRx(max_sym=1, device=device)         # the handle's receive side stays unused
+        self._hist = np.zeros(0, dtype=np.complex64)             # the last (up to MAX_TAPS - 1) input samples
+        self._pos = 0                                            # stream index of the next input sample
+        self._phase = 0                                          # phase of the next input sample, 2^-64 turns
+
+    # ---- GNU Radio's setters and getters ----
+    def set_noise_voltage(self, noise_voltage):
+        v = float(noise_voltage)
+        if not math.isfinite(v):
+            raise ValueError("noise_voltage must be finite")
+        self._noise_voltage = v
+
+    def noise_voltage(self):
+        return self._noise_voltage
+
+    def set_frequency_offset(self, frequency_offset):
+        f = float(frequency_offset)
+        if not math.isfinite(f):
+            raise ValueError("frequency_offset must be finite")
+        self._frequency_offset = f
+
+    def frequency_offset(self):
+        return self._frequency_offset
+
+    def set_taps(self, taps):
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.complex64).reshape(-1))
+        if not 1 <= t.size <= self.MAX_TAPS:
+            raise ValueError("taps must hold 1..%d values" % self.MAX_TAPS)
+        self._taps = t
+
+    def taps(self):
+        return self._taps.copy()
+
+    def set_timing_offset(self, epsilon):
+        if float(epsilon) != 1.0:
+            raise ValueError("sample-rate offset is not supported")
+        self._epsilon = 1.0
+
+    def timing_offset(self):
+        return self._epsilon
+
+    # ---- stream interface ----
+    def work(self, input_items, output_items):
+        x = input_items[0]
+        out = output_items[0]
+        n = min(len(x), len(out))
+        if n == 0:
+            return 0
+        x = np.asarray(x[:n], dtype=np.complex64)
+        L = self._taps.size
+        h = min(L - 1, self._hist.size)
+        row = np.concatenate([self._hist[self._hist.size - h:], x]) if h else x
+        cfo = np.float32(2.0 * math.pi * self._frequency_offset)
+        inc = capi.phase_inc(cfo)
+        m64 = 0xFFFFFFFFFFFFFFFF
+        y = self._rx.channel(row, taps=self._taps, cfo=cfo, phase0=(self._phase - inc * h) & m64, gain=1.0,
+                             noise_voltage=self._noise_voltage, seed=self.noise_seed, sample0=self._pos - h)
+        out[:n] = y[h:]
+        keep = self.MAX_TAPS - 1
+        self._hist = np.concatenate([self._hist, x])[-keep:] if n < keep else x[n - keep:].copy()
+        self._pos += n
+        self._phase = (self._phase + inc * n) & m64
+        return n
+
+    def close(self):
+        """Release the library handle."""
+        self._rx.close()

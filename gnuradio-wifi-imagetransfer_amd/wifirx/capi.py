@@ -39,7 +39,7 @@ EXPORTS = [
     "wifirx_get_stats", "wifirx_demod_batch", "wifirx_decode_batch", "wifirx_push", "wifirx_poll", "wifirx_poll_csi",
     "wifirx_sync", "wifirx_stream", "wifirx_synth_slots", "wifirx_dev_alloc", "wifirx_dev_free",
     "wifirx_memcpy_h2d", "wifirx_memcpy_d2h", "wifirx_time_demod", "wifirx_poll_ex", "wifirx_demod_batch_v",
-    "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft", "wifirx_tx_batch",
+    "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft", "wifirx_tx_batch", "wifirx_channel",
 ]
 
 
@@ -48,6 +48,20 @@ def bf16_to_f32(bits) -> np.ndarray:
     stand for: exact, the 16 bits become the upper half of the float32 word"""
     b = np.asarray(bits, dtype=np.uint16)
     return (b.astype(np.uint32) << 16).view(np.float32)
+
+
+def phase_inc(cfo) -> int:
+    """The uint64 phase increment wifirx_channel derives from `cfo` rad/sample (taken as float32): llround(cfo / (2 pi) * 2^64)
+    with the turns reduced to [-1/2, 1/2] first (+-1/2 turn = 2^63).  A caller that cuts a stream into calls advances its
+    phase0 by phase_inc(cfo) * samples, mod 2^64."""
+    f = float(np.float32(cfo)) / 6.283185307179586
+    f -= float(np.rint(f))
+    v = f * 2.0 ** 64
+    if v >= 2.0 ** 63 or v <= -2.0 ** 63:
+        return 1 << 63
+    a = abs(v)
+    k = int(a) if a >= 2.0 ** 52 else int(np.floor(a + 0.5))      # llround: half away from zero (a + 0.5 is exact below 2^52)
+    return (-k if v < 0 else k) & 0xFFFFFFFFFFFFFFFF
 
 
 class WifiRxError(RuntimeError):
@@ -112,6 +126,9 @@ _lib.wifirx_synth_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32,
                                     C.c_void_p]
 _lib.wifirx_tx_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p,
                                  C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32]
+_lib.wifirx_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_float, C.c_float,
+                                C.c_uint64, C.c_uint64]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -414,6 +431,66 @@ class WifiRx:
         if row_off is not None:
             return out[int(row_off[0]):]
         return out.reshape(n, int(row_len))
+
+    # -- channel (wifirx_channel) --
+    @staticmethod
+    def _channel_taps(taps):
+        """1-D set or 2-D [n_tap_sets, L] array -> (complex64 [n_tap_sets, L], n_tap_sets, L)"""
+        t = np.asarray(taps, dtype=np.complex64)
+        if t.ndim == 1:
+            t = t[None]
+        if t.ndim != 2:
+            raise ValueError("taps must be a 1-D set or a 2-D [n_tap_sets, L] array")
+        return np.ascontiguousarray(t), t.shape[0], t.shape[1]
+
+    def channel_dev(self, in_ptr, out_ptr, samples_cap, n_rows, *, row_len=None, row_off=None, taps=(1.0,), cfo=None,
+                    phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, n_taps=None, n_tap_sets=1):
+        """wifirx_channel over device samples: rows of row_len, or row_off ([n_rows + 1] sample offsets).  taps: a 1-D set, a
+        2-D [n_tap_sets, L] array, or an int device pointer (then n_taps and n_tap_sets say its shape).  cfo: rad/sample per
+        row (scalar or [n_rows]), None = 0.  phase0: uint64 phase in 2^-64 turns.  Asynchronous on the handle's stream."""
+        if isinstance(taps, int):
+            if n_taps is None:
+                raise ValueError("device taps need n_taps")
+            t_ptr, t_dev, L, n_sets, keep = taps, 1, int(n_taps), int(n_tap_sets), None
+        else:
+            keep, n_sets, L = self._channel_taps(taps)
+            t_ptr, t_dev = _np_ptr(keep), 0
+        c = None
+        if cfo is not None:
+            c = np.ascontiguousarray(np.broadcast_to(np.asarray(cfo, dtype=np.float32), (int(n_rows),)))
+        ro = None if row_off is None else np.ascontiguousarray(row_off, dtype=np.uint64)
+        if ro is not None and ro.size != int(n_rows) + 1:
+            raise ValueError("row_off needs n_rows + 1 entries")
+        self._check(_lib.wifirx_channel(self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0),
+                                        int(n_rows), t_ptr, t_dev, L, n_sets, _np_ptr(c), int(phase0) & 0xFFFFFFFFFFFFFFFF,
+                                        float(gain), float(noise_voltage), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        int(sample0) & 0xFFFFFFFFFFFFFFFF))
+
+    def channel(self, x, *, row_off=None, taps=(1.0,), cfo=None, phase0=0, gain=1.0, noise_voltage=0.0, seed=0,
+                sample0=0):
+        """channel_dev on host samples: x [n_rows, row_len] (fixed rows; 1-D = one row) or, with row_off, the 1-D buffer the
+        offsets index.  Returns the output in x's shape; samples outside the rows are 0."""
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        if row_off is not None:
+            if x.ndim != 1:
+                raise ValueError("with row_off, x is the 1-D sample buffer")
+            n_rows, row_len = len(row_off) - 1, None
+        else:
+            xr = x.reshape(1, -1) if x.ndim == 1 else x
+            n_rows, row_len = xr.shape
+        n = x.size
+        d_in = self.alloc(max(n, 1) * 8)
+        d_out = self.alloc(max(n, 1) * 8)
+        try:
+            d_in.upload(x)
+            d_out.upload(np.zeros(n, np.complex64))
+            self.channel_dev(d_in.ptr, d_out.ptr, n, n_rows, row_len=row_len, row_off=row_off, taps=taps, cfo=cfo,
+                             phase0=phase0, gain=gain, noise_voltage=noise_voltage, seed=seed, sample0=sample0)
+            y = d_out.download(np.complex64, n)      # ordered behind the kernel on the handle's stream
+        finally:
+            d_in.free()
+            d_out.free()
+        return y.reshape(x.shape)
 
     # -- stream mode --
     def push(self, iq: np.ndarray):

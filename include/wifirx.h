@@ -342,6 +342,39 @@ int  wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* psdu, int ps
                      const uint32_t* psdu_len, const uint8_t* seeds, uint32_t n_frames, float* samples, uint64_t samples_cap,
                      const uint64_t* row_off, uint64_t row_len, uint32_t lead);
 
+/* GNU Radio's channels.channel_model(noise_voltage, frequency_offset, epsilon = 1, taps, noise_seed), the block between TX
+ * and RX of the reference's loop-back (gnu_radio/IRS_tranceiver.py:282-288), over n_rows rows of device samples; arithmetic =
+ * NUMERICS.md rule 17.  Sample n of row r (x: the input row, y: the output row):
+ *     s      = sum_{k=0}^{L-1} t_{r,k} x[n-k]              x[m] = 0 for m < 0: every row is its own burst
+ *     y[n]   = gain * (s * exp(j phi_r(n))) + noise_voltage * w(sample0 + n, r)
+ *   taps      n_tap_sets sets of n_taps (L, 1..64) complex64 taps; row r uses set r % n_tap_sets.  Device memory when
+ *             taps_on_device.  One set {1} is the flat channel.
+ *   cfo       HOST [n_rows] rad/sample (the unit of wifirx_synth_slots and wifirx_frame.cfo_*); NULL = 0.  The phase is fixed
+ *             point: inc_r = llround(cfo_r / (2 pi) * 2^64) as a uint64, P = phase0 + inc_r n mod 2^64 (phase0 in 2^-64
+ *             turns), phi = (float)(int32_t)(P >> 32) * (float)(2 pi / 2^32): a stream cut into calls keeps its phase
+ *             exactly when each call passes on phase0 + inc * (samples it advanced).
+ *   noise     complex Gaussian of variance noise_voltage^2 (each component noise_voltage / sqrt(2)): Philox4x32-10 keyed by
+ *             `seed` on the counter ((sample0 + n) >> 1, r), Box-Muller as wifirx_synth_slots -- zero input through one flat
+ *             set with gain 1, noise_voltage 1, sample0 = 0 and fixed rows of even length reproduces its noise bit for bit.
+ *             noise_voltage = 0 adds nothing.
+ *   in, out   DEVICE complex64 (8-byte aligned), samples_cap samples long, rows at the same places in both.  In place
+ *             (in == out) only with n_taps = 1; any other overlap of the rows' samples is refused.
+ *   rows      row r = samples [row_off[r], row_off[r+1]) when row_off (HOST [n_rows + 1], non-decreasing) is given,
+ *             [r row_len, (r+1) row_len) otherwise: wifirx_tx_batch's convention.  Every sample of every row is written;
+ *             samples outside the rows are not touched.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for NULL in / out / taps, misaligned buffers, n_taps outside
+ * 1..64, n_tap_sets = 0, a non-finite gain / noise_voltage / cfo, a decreasing row_off and the overlap above; WIFIRX_ERANGE
+ * when the rows end behind samples_cap.  n_rows = 0 does nothing and returns WIFIRX_OK.  One kernel launch per call, after
+ * one upload of the host arrays (taps, cfo, row_off).
+ * ORDER: as wifirx_tx_batch -- the call waits until its host inputs are copied, so they may be reused when it returns; the
+ * kernel then runs asynchronously on the handle's stream, behind the handle's earlier calls.  `in`, `out` and device taps must
+ * stay valid until it has run. */
+int  wifirx_channel(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
+                    const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
+                    const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
+                    const float* cfo, uint64_t phase0, float gain, float noise_voltage,
+                    uint64_t seed, uint64_t sample0);
+
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);
 int  wifirx_dev_free(wifirx_handle* h, void* p);
