@@ -26,6 +26,7 @@
 #include "wr_kernels.h"
 #include "wr_tx.h"
 #include "wr_channel.h"
+#include "wr_link.h"
 
 // The stream's per-frame outputs (stream_outs, wifirx_api_stream.inc) and the host copy of a batch of them, shared by its
 // frames: output o of frame k is the width[o] bytes at blob[off[o] + k * width[o]] (width 0: the handle did not produce o).
@@ -114,6 +115,8 @@ struct Staging {
     DevBuf off;                     // slot offsets of wifirx_demod_batch_v
     DevBuf tx_psdu, tx_meta;        // wifirx_tx_batch: host PSDUs; lengths, seeds, row offsets
     DevBuf ch_meta;                 // wifirx_channel: host taps, phase increments, row offsets, tile bases
+    DevBuf link_meta, link_payload; // wifirx_mac_batch: payload lengths; host payloads
+    DevBuf link_counts;             // wifirx_link_stats: the nine counters
 };
 
 // decode workspace
@@ -591,3 +594,4 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_stream.inc"
 #include "wifirx_api_tx.inc"
 #include "wifirx_api_channel.inc"
+#include "wifirx_api_link.inc"

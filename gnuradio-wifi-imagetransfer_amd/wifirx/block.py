@@ -330,6 +330,43 @@ class wifi_phy_tx(grshim.sync_block):
         self._rx.close()
 
 
+class mac(grshim.basic_block):
+    """Drop-in for ``ieee802_11.mac(src_mac, dst_mac, bss_mac)`` (gnu_radio/IRS_user.py:192, IRS_tranceiver.py:271): the
+    message block in front of the PHY.  ``app in`` takes a PDU ``(meta, u8vector)`` with the payload, ``phy out`` sends
+    ``(meta, u8vector)`` with the PSDU -- 24-byte data header, payload, FCS -- which ``wifi_phy_tx``'s ``mac_in`` takes as it
+    is (port names: IRS_user.py:204-205).  The sequence number counts up from 0, one per frame.
+
+    The block frames on the host (txgen.mac_frame): one message is one frame, there is nothing to batch.  A sweep that
+    frames many payloads at once calls wifirx_mac_batch (capi.WifiRx.mac_batch_dev) instead."""
+
+    MAX_PAYLOAD = capi.MAX_PAYLOAD
+
+    def __init__(self, src_mac=(0x23,) * 6, dst_mac=(0x42,) * 6, bss_mac=(0xFF,) * 6):
+        grshim.basic_block.__init__(self, name="mac", in_sig=None, out_sig=None)
+        self.src_mac, self.dst_mac, self.bss_mac = (self._addr(a) for a in (src_mac, dst_mac, bss_mac))
+        self._seq = 0
+        self._p_out = grshim.intern("phy out")
+        self.message_port_register_out(self._p_out)
+        self.message_port_register_in(grshim.intern("app in"))
+        self.set_msg_handler(grshim.intern("app in"), self._on_app)
+
+    @staticmethod
+    def _addr(a):
+        a = bytes(bytearray(a))
+        if len(a) != 6:
+            raise ValueError("a MAC address has 6 bytes")
+        return a
+
+    def _on_app(self, msg):
+        meta, vec = grshim.to_python(msg)
+        payload = np.asarray(vec, dtype=np.uint8).tobytes()
+        if len(payload) > self.MAX_PAYLOAD:
+            raise ValueError("payload longer than %d bytes" % self.MAX_PAYLOAD)
+        psdu = txgen.mac_frame(payload, seq=self._seq, src=self.src_mac, dst=self.dst_mac, bss=self.bss_mac)
+        self._seq = (self._seq + 1) & 0xFFF
+        self.message_port_pub(self._p_out, grshim.make_pdu(dict(meta or {}), np.frombuffer(psdu, dtype=np.uint8)))
+
+
 class channel_model(grshim.sync_block):
     """Drop-in for GNU Radio's ``channels.channel_model`` (the loop-back channel of gnu_radio/IRS_tranceiver.py:282-288) on the
     device: multipath FIR (``taps``), frequency offset (``frequency_offset`` in cycles/sample, as the flowgraph's

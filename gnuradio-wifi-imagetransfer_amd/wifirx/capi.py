@@ -40,7 +40,9 @@ EXPORTS = [
     "wifirx_sync", "wifirx_stream", "wifirx_synth_slots", "wifirx_dev_alloc", "wifirx_dev_free",
     "wifirx_memcpy_h2d", "wifirx_memcpy_d2h", "wifirx_time_demod", "wifirx_poll_ex", "wifirx_demod_batch_v",
     "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft", "wifirx_tx_batch", "wifirx_channel",
+    "wifirx_mac_batch", "wifirx_link_stats",
 ]
+MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
 
 def bf16_to_f32(bits) -> np.ndarray:
@@ -62,6 +64,20 @@ def phase_inc(cfo) -> int:
     a = abs(v)
     k = int(a) if a >= 2.0 ** 52 else int(np.floor(a + 0.5))      # llround: half away from zero (a + 0.5 is exact below 2^52)
     return (-k if v < 0 else k) & 0xFFFFFFFFFFFFFFFF
+
+
+def link_rates(c) -> dict:
+    """fer, coded_ber and coded_ber_se (float64) from the counters of wifirx_link_counts.  coded_ber_se is the standard error
+    of the mean of the per-frame BER e_f / b over the good frames, b = coded_bits / frames_good bits per frame (frames of
+    one length): sqrt(E[e^2] - E[e]^2) / b / sqrt(frames_good)."""
+    nan = float("nan")
+    g, bits = c["frames_good"], c["coded_bits"]
+    out = {"fer": 1.0 - c["frames_psdu_ok"] / c["frames_ref"] if c["frames_ref"] else nan,
+           "coded_ber": c["coded_bit_errors"] / bits if bits else nan, "coded_ber_se": nan}
+    if g and bits:
+        m1, m2 = c["coded_bit_errors"] / g, c["coded_bit_errors_sq"] / g
+        out["coded_ber_se"] = float(np.sqrt(max(m2 - m1 * m1, 0.0)) / (bits / g) / np.sqrt(g))
+    return out
 
 
 class WifiRxError(RuntimeError):
@@ -91,6 +107,12 @@ class PollOut(C.Structure):
 class Stats(C.Structure):
     _fields_ = [("samples_in", C.c_uint64), ("frames_detected", C.c_uint64), ("frames_signal_ok", C.c_uint64),
                 ("frames_complete", C.c_uint64), ("frames_crc_ok", C.c_uint64), ("frames_dropped", C.c_uint64)]
+
+
+class LinkCounts(C.Structure):
+    """wifirx_link_counts: what wifirx_link_stats counts"""
+    _fields_ = [(k, C.c_uint64) for k in ("frames", "frames_ref", "frames_good", "frames_crc_ok", "frames_psdu_ok",
+                                          "frames_crc_ok_wrong", "coded_bits", "coded_bit_errors", "coded_bit_errors_sq")]
 
 
 if not os.path.exists(LIB_PATH):
@@ -129,6 +151,10 @@ _lib.wifirx_tx_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_u
 _lib.wifirx_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                 C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_float, C.c_float,
                                 C.c_uint64, C.c_uint64]
+_lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                  C.c_uint64, C.c_void_p, C.c_uint32]
+_lib.wifirx_link_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.POINTER(Out), C.c_void_p, C.c_void_p,
+                                   C.POINTER(LinkCounts)]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -491,6 +517,96 @@ class WifiRx:
             d_in.free()
             d_out.free()
         return y.reshape(x.shape)
+
+    # -- the ends of the loop-back (wifirx_mac_batch, wifirx_link_stats) --
+    def mac_batch_dev(self, psdu_ptr, psdu_stride, n_frames, payload=None, payload_len=None, seq0=0, addr=None,
+                      payload_seed=0, payload_stride=None):
+        """wifirx_mac_batch into device memory (n_frames rows of psdu_stride bytes at psdu_ptr): ieee802_11.mac's PSDUs.
+        payload: None (Philox bytes keyed by payload_seed, made on the device), a 2-D uint8 array [n_frames, stride] or a list of
+        bytes (host payloads), or an int device pointer (with payload_stride).  payload_len: one length for all, or
+        [n_frames]; default the row width of `payload` (required for Philox payloads).  addr: (dst, src, bss), 6 bytes each.
+        Asynchronous on the handle's stream.  Returns the payload lengths used (uint32 [n_frames])."""
+        n = int(n_frames)
+        keep, ptr, on_dev = None, None, 0
+        if isinstance(payload, int):
+            if payload_stride is None:
+                raise ValueError("a device payload needs payload_stride")
+            ptr, on_dev, stride = payload, 1, int(payload_stride)
+        elif payload is not None:
+            if isinstance(payload, np.ndarray):
+                keep = np.ascontiguousarray(payload, dtype=np.uint8)
+                if keep.ndim != 2:
+                    raise ValueError("payload must be a 2-D uint8 array, a list of bytes, a device pointer or None")
+            else:
+                keep, lens = self._tx_psdus(payload)
+                if payload_len is None:
+                    payload_len = lens
+            if keep.shape[0] != n:
+                raise ValueError("payload needs n_frames rows")
+            ptr, stride = _np_ptr(keep), keep.shape[1]
+        else:
+            if payload_len is None:
+                raise ValueError("Philox payloads need payload_len")
+            stride = int(np.max(payload_len, initial=0)) if np.ndim(payload_len) else int(payload_len)
+        if payload_len is None:
+            lens = np.full(n, stride, np.uint32)
+        else:
+            lens = np.ascontiguousarray(np.broadcast_to(np.asarray(payload_len, np.uint32), (n,)))
+        # one length for all that is also the stride: no array to upload (payload_len = NULL)
+        uniform = payload_len is None or (np.ndim(payload_len) == 0 and int(payload_len) == stride)
+        a = None
+        if addr is not None:
+            a = np.ascontiguousarray(np.concatenate([np.frombuffer(bytes(x), np.uint8) for x in addr]))
+            if a.size != 18:
+                raise ValueError("addr = (dst, src, bss), 6 bytes each")
+        self._check(_lib.wifirx_mac_batch(self._h, ptr, on_dev, stride, None if uniform else _np_ptr(lens), n, _np_ptr(a), int(seq0) & 0xFFFFFFFF,
+                                          int(payload_seed) & 0xFFFFFFFFFFFFFFFF, psdu_ptr, int(psdu_stride)))
+        return lens
+
+    def mac_batch(self, n_frames, payload=None, payload_len=None, seq0=0, addr=None, payload_seed=0):
+        """Host convenience of mac_batch_dev: returns [n_frames, 28 + longest payload] uint8, PSDU i in row i (zeros behind
+        a shorter one)."""
+        n = int(n_frames)
+        if payload is None and payload_len is None:
+            raise ValueError("Philox payloads need payload_len")
+        if payload_len is not None:
+            width = int(np.max(payload_len, initial=0))
+        elif isinstance(payload, np.ndarray):
+            width = payload.shape[1]
+        else:
+            width = max((len(p) for p in payload), default=0)
+        stride = width + 28
+        buf = self.alloc(max(n, 1) * stride).upload(np.zeros(max(n, 1) * stride, np.uint8))
+        try:
+            self.mac_batch_dev(buf.ptr, stride, n, payload, payload_len, seq0, addr, payload_seed)
+            return buf.download(np.uint8, n * stride).reshape(n, stride)
+        finally:
+            buf.free()
+
+    def link_stats(self, n_slots, dev, ref, per_frame=False) -> dict:
+        """wifirx_link_stats: scores the decoded batch `dev` (an alloc_out dict after demod + decode) against `ref`, a dict with
+        the DevBufs of what was sent: "frames" (required), "psdu" + "psdu_stride", "hbits" / "idx".  Returns the counters of
+        wifirx_link_counts and, derived from them in float64, fer, coded_ber and coded_ber_se (the standard error of the mean
+        of the per-frame BER, for frames of one length); per_frame=True adds "frame_err" (uint32) and "frame_class" (uint8)
+        as DevBufs the caller frees.  Waits for the result."""
+        n = int(n_slots)
+        o_rx, o_ref = self._out_struct(dev), self._out_struct(ref)
+        d_err = self.alloc(4 * max(n, 1)) if per_frame else None
+        d_cls = self.alloc(max(n, 1)) if per_frame else None
+        cnt = LinkCounts()
+        try:
+            self._check(_lib.wifirx_link_stats(self._h, n, C.byref(o_rx), C.byref(o_ref), d_err.ptr if per_frame else None,
+                                               d_cls.ptr if per_frame else None, C.byref(cnt)))
+        except Exception:
+            if per_frame:
+                d_err.free()
+                d_cls.free()
+            raise
+        r = {k: int(getattr(cnt, k)) for k, _ in LinkCounts._fields_}
+        r.update(link_rates(r))
+        if per_frame:
+            r["frame_err"], r["frame_class"] = d_err, d_cls
+        return r
 
     # -- stream mode --
     def push(self, iq: np.ndarray):

@@ -375,6 +375,66 @@ int  wifirx_channel(wifirx_handle* h, const float* in, float* out, uint64_t samp
                     const float* cfo, uint64_t phase0, float gain, float noise_voltage,
                     uint64_t seed, uint64_t sample0);
 
+/* ieee802_11.mac (gnu_radio/IRS_user.py:192,204-205; IRS_tranceiver.py:271,313-314) for a batch: PSDU i, at
+ * psdu + i * psdu_stride, is the 24 + payload_len[i] + 4 bytes
+ *     08 00 | 00 00 | addr1 = dst | addr2 = src | addr3 = bss | ((seq0 + i) & 0xFFF) << 4, little endian | payload i | FCS
+ * with FCS = CRC-32 (reflected 0xEDB88320, little endian) over everything before it.  Bytes of a row behind the PSDU are not
+ * touched.  One kernel launch per call.
+ *   payload      frame i at payload + i * payload_stride; device memory when payload_on_device.  NULL: the payload is made on
+ *                the device -- bytes 16 j .. 16 j + 15 of frame i are the four output words (x, y, z, w, each little endian)
+ *                of Philox4x32-10 on the counter (j, i, 0, 0) with the key (payload_seed & 0xffffffff, payload_seed >> 32);
+ *                payload_stride then only gives the default length
+ *   payload_len  HOST [n_frames], 0..1500 (WIFIRX_MAX_PSDU - 28, upstream's MAX_PAYLOAD); NULL = payload_stride for all
+ *   addr         HOST [18]: dst, src, bss (addr1..3); NULL = 42.. (dst), 23.. (src), ff.. (bss), the reference's flowgraphs
+ *   psdu         DEVICE
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for NULL psdu, a payload_len above 1500 or (with a payload
+ * buffer) above payload_stride; WIFIRX_ERANGE when psdu_stride is smaller than a PSDU.  n_frames = 0 does nothing and returns
+ * WIFIRX_OK.
+ * ORDER: as wifirx_tx_batch -- the call waits until its host inputs (payload_len, host payloads) are copied, so they may be
+ * reused when it returns; the kernel then runs asynchronously on the handle's stream, so wifirx_tx_batch(psdu_on_device = 1)
+ * can follow directly.  Device payloads and `psdu` must stay valid until it has run. */
+int  wifirx_mac_batch(wifirx_handle* h, const uint8_t* payload, int payload_on_device, uint32_t payload_stride,
+                      const uint32_t* payload_len, uint32_t n_frames, const uint8_t* addr, uint32_t seq0,
+                      uint64_t payload_seed, uint8_t* psdu, uint32_t psdu_stride);
+
+/* What wifirx_link_stats counts.  Every counter from frames_good down counts only frames whose reference record is complete;
+ * fer = 1 - frames_psdu_ok / frames_ref, coded_ber = coded_bit_errors / coded_bits. */
+typedef struct wifirx_link_counts {
+    uint64_t frames;               /* n_slots */
+    uint64_t frames_ref;           /* reference records with WIFIRX_F_COMPLETE; only these are scored below */
+    uint64_t frames_good;          /* rx COMPLETE and encoding, psdu_len, n_sym equal to the reference record's */
+    uint64_t frames_crc_ok;        /* rx WIFIRX_F_CRC_OK */
+    uint64_t frames_psdu_ok;       /* CRC_OK, psdu_len equal, and bytes 0 .. psdu_len - 1 equal to the reference PSDU */
+    uint64_t frames_crc_ok_wrong;  /* CRC_OK and not psdu_ok */
+    uint64_t coded_bits;           /* sum over good frames of n_sym * 48 * n_bpsc */
+    uint64_t coded_bit_errors;     /* sum over good frames of e_f */
+    uint64_t coded_bit_errors_sq;  /* sum over good frames of e_f^2 (for the standard error of the mean BER) */
+} wifirx_link_counts;              /* 72 bytes */
+
+/* Scores a decoded batch against what was sent, on the device: the back end of the loop-back (what a host would do with the
+ * records, PSDUs and decisions of gnu_radio/IRS_tranceiver.py's RX side).  `rx` is what wifirx_demod_batch +
+ * wifirx_decode_batch[_soft] left; `ref` describes what was sent, in the same struct: ref->frames (required: e.g. the records
+ * of a demod of the clean TX rows), ref->psdu / ref->psdu_stride (the transmitted PSDUs, e.g. wifirx_mac_batch's output) and
+ * ref->hbits or ref->idx (the transmitted decisions).  Both are device buffers with the row layout of this handle (max_sym
+ * of its config; the psdu strides may differ); idx / hbits 16-byte aligned.  Of `rx` and `ref` only frames, psdu,
+ * psdu_stride, idx, hbits and on_device are read.
+ *   PSDUs      when rx->psdu or ref->psdu is NULL, frames_crc_ok, frames_psdu_ok and frames_crc_ok_wrong stay 0 (and bits 1, 2
+ *              of frame_class).  A frame whose psdu_len exceeds one of the strides is not psdu_ok.
+ *   decisions  e_f = the differing coded bits of frame f over its n_sym data symbols: from hbits (popcount of the XOR of the
+ *              first 2 * n_bpsc * n_sym words) when both sides give hbits, else from idx (popcount of the XOR of the 48 * n_sym
+ *              bytes) when both give idx; the two forms give the same number.  With neither, coded_bits, coded_bit_errors and
+ *              coded_bit_errors_sq stay 0 and frame_err is 0xFFFFFFFF throughout.  n_bpsc is that of the record's encoding; a
+ *              record with an encoding above 7 or n_sym above max_sym is not good.
+ *   frame_err  DEVICE [n_slots], optional: e_f for good frames, 0xFFFFFFFF otherwise
+ *   frame_class DEVICE [n_slots], optional: bit 0 good, bit 1 crc_ok, bit 2 psdu_ok, bit 3 reference complete
+ *   counts     HOST
+ * All sums are integers: the result does not depend on the order of reduction.  WIFIRX_EINVAL for NULL rx / ref / counts /
+ * rx->frames / ref->frames, host buffers (on_device = 0) or misaligned idx / hbits / frame_err.
+ * ORDER: the call zeroes a small device buffer of the handle, runs one kernel behind the handle's earlier calls, copies the
+ * 72 bytes back and WAITS for them: when it returns, everything queued on the handle's stream before it has finished. */
+int  wifirx_link_stats(wifirx_handle* h, uint32_t n_slots, const wifirx_out* rx, const wifirx_out* ref,
+                       uint32_t* frame_err, uint8_t* frame_class, wifirx_link_counts* counts);
+
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);
 int  wifirx_dev_free(wifirx_handle* h, void* p);
