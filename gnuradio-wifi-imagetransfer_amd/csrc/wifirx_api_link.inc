@@ -62,11 +62,12 @@ extern "C" int wifirx_mac_batch(wifirx_handle* h, const uint8_t* payload, int pa
     return WIFIRX_OK;
 }
 
-extern "C" int wifirx_link_stats(wifirx_handle* h, uint32_t n_slots, const wifirx_out* rx, const wifirx_out* ref,
-                                 uint32_t* frame_err, uint8_t* frame_class, wifirx_link_counts* counts)
+namespace {
+
+// both scoring entry points: the totals into `counts` (if given), the counters per reference encoding into by_rate[8] (if given)
+int link_stats_impl(wifirx_handle* h, uint32_t n_slots, const wifirx_out* rx, const wifirx_out* ref, uint32_t* frame_err,
+                    uint8_t* frame_class, wifirx_link_counts* counts, wifirx_link_counts* by_rate)
 {
-    if (!h) return WIFIRX_EINVAL;
-    if (!rx || !ref || !counts) return fail(h, WIFIRX_EINVAL, "rx, ref and counts are required");
     if (!rx->frames || !ref->frames) return fail(h, WIFIRX_EINVAL, "rx->frames and ref->frames are required");
     if (!rx->on_device || !ref->on_device) return fail(h, WIFIRX_EINVAL, "rx and ref must be device buffers");
     if (reinterpret_cast<uintptr_t>(frame_err) & 3) return fail(h, WIFIRX_EINVAL, "frame_err must be 4-byte aligned");
@@ -98,11 +99,36 @@ extern "C" int wifirx_link_stats(wifirx_handle* h, uint32_t n_slots, const wifir
     a.frame_class = frame_class;
     stream_worker_wait_idle(h);
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = h->stage.link_counts.reserve(h, sizeof(wifirx_link_counts))) return rc;
+    // totals | by_rate[8] in one device buffer: one zeroing, one copy back
+    const size_t n_sets = by_rate ? 9 : 1;
+    wifirx_link_counts got[9];
+    if (int rc = h->stage.link_counts.reserve(h, n_sets * sizeof(wifirx_link_counts))) return rc;
     a.counts = h->stage.link_counts.as<unsigned long long>();
-    HIP_TRY(h, hipMemsetAsync(h->stage.link_counts.p, 0, sizeof(wifirx_link_counts), h->stream));
+    a.by_rate = by_rate ? 1 : 0;
+    HIP_TRY(h, hipMemsetAsync(h->stage.link_counts.p, 0, n_sets * sizeof(wifirx_link_counts), h->stream));
     HIP_TRY(h, wr_launch_link_stats(h->stream, &a, h->n_simd));
-    HIP_TRY(h, hipMemcpyAsync(counts, h->stage.link_counts.p, sizeof(wifirx_link_counts), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(got, h->stage.link_counts.p, n_sets * sizeof(wifirx_link_counts), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (counts) *counts = got[0];
+    if (by_rate) std::memcpy(by_rate, got + 1, 8 * sizeof(wifirx_link_counts));
     return WIFIRX_OK;
+}
+
+}  // namespace
+
+extern "C" int wifirx_link_stats(wifirx_handle* h, uint32_t n_slots, const wifirx_out* rx, const wifirx_out* ref,
+                                 uint32_t* frame_err, uint8_t* frame_class, wifirx_link_counts* counts)
+{
+    if (!h) return WIFIRX_EINVAL;
+    if (!rx || !ref || !counts) return fail(h, WIFIRX_EINVAL, "rx, ref and counts are required");
+    return link_stats_impl(h, n_slots, rx, ref, frame_err, frame_class, counts, nullptr);
+}
+
+extern "C" int wifirx_link_stats_by_rate(wifirx_handle* h, uint32_t n_slots, const wifirx_out* rx, const wifirx_out* ref,
+                                         uint32_t* frame_err, uint8_t* frame_class, wifirx_link_counts* total,
+                                         wifirx_link_counts* by_rate)
+{
+    if (!h) return WIFIRX_EINVAL;
+    if (!rx || !ref || !by_rate) return fail(h, WIFIRX_EINVAL, "rx, ref and by_rate are required");
+    return link_stats_impl(h, n_slots, rx, ref, frame_err, frame_class, total, by_rate);
 }

@@ -10,12 +10,13 @@ constexpr TxRate kTxRates[8] = {
 
 }  // namespace
 
-extern "C" int wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* psdu, int psdu_on_device, uint32_t psdu_stride,
-                               const uint32_t* psdu_len, const uint8_t* seeds, uint32_t n_frames, float* samples,
-                               uint64_t samples_cap, const uint64_t* row_off, uint64_t row_len, uint32_t lead)
+namespace {
+
+// both transmitter entry points: every frame at `encoding`, or (enc_v != null) frame i at enc_v[i], checked by the caller
+int tx_batch_impl(wifirx_handle* h, int encoding, const uint8_t* enc_v, const uint8_t* psdu, int psdu_on_device,
+                  uint32_t psdu_stride, const uint32_t* psdu_len, const uint8_t* seeds, uint32_t n_frames, float* samples,
+                  uint64_t samples_cap, const uint64_t* row_off, uint64_t row_len, uint32_t lead)
 {
-    if (!h) return WIFIRX_EINVAL;
-    if (encoding < WIFIRX_BPSK_1_2 || encoding > WIFIRX_64QAM_3_4) return fail(h, WIFIRX_EINVAL, "unknown encoding");
     if (n_frames == 0) return WIFIRX_OK;
     if (!psdu || !psdu_len || !samples) return fail(h, WIFIRX_EINVAL, "psdu, psdu_len and samples are required");
     if (reinterpret_cast<uintptr_t>(samples) & 7) return fail(h, WIFIRX_EINVAL, "samples must be 8-byte aligned (complex64)");
@@ -30,12 +31,13 @@ extern "C" int wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* ps
     if (row_off)
         for (uint32_t i = 0; i < n_frames; i++)
             if (row_off[i + 1] < row_off[i]) return fail(h, WIFIRX_EINVAL, "row_off must not decrease");
-    auto frame_len = [&](uint32_t len) -> uint64_t {
-        return (5ull + (16ull + 8ull * len + 6 + rt.n_dbps - 1) / rt.n_dbps) * 80 + 1;
+    auto frame_len = [&](uint32_t len, uint32_t n_dbps) -> uint64_t {
+        return (5ull + (16ull + 8ull * len + 6 + n_dbps - 1) / n_dbps) * 80 + 1;
     };
     for (uint32_t i = 0; i < n_frames; i++) {
         const uint64_t have = row_off ? row_off[i + 1] - row_off[i] : row_len;
-        if (have < (uint64_t)lead + frame_len(psdu_len[i])) return fail(h, WIFIRX_ERANGE, "a frame plus lead does not fit its row");
+        const uint32_t n_dbps = enc_v ? kTxRates[enc_v[i]].n_dbps : rt.n_dbps;
+        if (have < (uint64_t)lead + frame_len(psdu_len[i], n_dbps)) return fail(h, WIFIRX_ERANGE, "a frame plus lead does not fit its row");
     }
     const uint64_t g0 = row_off ? row_off[0] : 0;
     if (!row_off && row_len > samples_cap / n_frames) return fail(h, WIFIRX_ERANGE, "rows exceed samples_cap");
@@ -53,13 +55,15 @@ extern "C" int wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* ps
     const uint64_t n_tiles = ((uint64_t)(a.g1 + a.shift - a.v0) + tile - 1) / tile;
     if (n_tiles > 0x7fffffffull) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 tiles of output");
 
-    // one upload of what the host holds: lengths | seeds | row offsets | first row of every tile (row_off form)
-    const size_t o_len = 0, o_seed = o_len + 4ull * n_frames, o_row = (o_seed + n_frames + 7) & ~size_t(7);
+    // one upload of what the host holds: lengths | seeds | encodings | row offsets | first row of every tile (row_off form)
+    const size_t o_len = 0, o_seed = o_len + 4ull * n_frames, o_enc = o_seed + n_frames;
+    const size_t o_row = (o_enc + (enc_v ? n_frames : 0) + 7) & ~size_t(7);
     const size_t o_tile = o_row + (row_off ? 8ull * (n_frames + 1) : 0);
     const size_t meta_bytes = o_tile + (row_off ? 4ull * n_tiles : 0);
     std::vector<uint8_t> meta(meta_bytes);
     std::memcpy(meta.data() + o_len, psdu_len, 4ull * n_frames);
     if (seeds) std::memcpy(meta.data() + o_seed, seeds, n_frames);
+    if (enc_v) std::memcpy(meta.data() + o_enc, enc_v, n_frames);
     if (row_off) {
         std::memcpy(meta.data() + o_row, row_off, 8ull * (n_frames + 1));
         uint32_t* tr = reinterpret_cast<uint32_t*>(meta.data() + o_tile);
@@ -98,6 +102,37 @@ extern "C" int wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* ps
     a.n_dbps = rt.n_dbps;
     a.enc = (uint32_t)encoding;
     a.rate_field = rt.rate_field;
+    a.enc_v = enc_v ? dm + o_enc : nullptr;
     HIP_TRY(h, wr_launch_tx(h->stream, &a));
     return WIFIRX_OK;
+}
+
+}  // namespace
+
+extern "C" int wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* psdu, int psdu_on_device, uint32_t psdu_stride,
+                               const uint32_t* psdu_len, const uint8_t* seeds, uint32_t n_frames, float* samples,
+                               uint64_t samples_cap, const uint64_t* row_off, uint64_t row_len, uint32_t lead)
+{
+    if (!h) return WIFIRX_EINVAL;
+    if (encoding < WIFIRX_BPSK_1_2 || encoding > WIFIRX_64QAM_3_4) return fail(h, WIFIRX_EINVAL, "unknown encoding");
+    return tx_batch_impl(h, encoding, nullptr, psdu, psdu_on_device, psdu_stride, psdu_len, seeds, n_frames, samples,
+                         samples_cap, row_off, row_len, lead);
+}
+
+extern "C" int wifirx_tx_batch_rates(wifirx_handle* h, const uint8_t* encoding, const uint8_t* psdu, int psdu_on_device,
+                                     uint32_t psdu_stride, const uint32_t* psdu_len, const uint8_t* seeds, uint32_t n_frames,
+                                     float* samples, uint64_t samples_cap, const uint64_t* row_off, uint64_t row_len,
+                                     uint32_t lead)
+{
+    if (!h) return WIFIRX_EINVAL;
+    if (n_frames == 0) return WIFIRX_OK;
+    if (!encoding) return fail(h, WIFIRX_EINVAL, "encoding is required");
+    bool uniform = true;
+    for (uint32_t i = 0; i < n_frames; i++) {
+        if (encoding[i] > WIFIRX_64QAM_3_4) return fail(h, WIFIRX_EINVAL, "unknown encoding");
+        uniform &= encoding[i] == encoding[0];
+    }
+    // one encoding for all: the single-encoding instance, which keeps that encoding's tables in LDS
+    return tx_batch_impl(h, encoding[0], uniform ? nullptr : encoding, psdu, psdu_on_device, psdu_stride, psdu_len, seeds,
+                         n_frames, samples, samples_cap, row_off, row_len, lead);
 }

@@ -21,7 +21,7 @@ struct MacArgs {
     uint32_t        hdr[6];       // the 24 bytes of the MAC header with sequence number 0, little endian words
 };
 
-// one wifirx_link_stats call, every pointer on the device.  Decision rows are compared as dwords: the first 2 n_bpsc n_sym
+// one wifirx_link_stats or wifirx_link_stats_by_rate call, every pointer on the device.  Decision rows are compared as dwords: the first 2 n_bpsc n_sym
 // of a frame's row for hbits (two words per coded bit of a carrier and symbol), the first 12 n_sym for idx (48 bytes per
 // symbol, whatever the rate).
 struct LinkArgs {
@@ -33,11 +33,13 @@ struct LinkArgs {
     const uint32_t*     ref_dec;
     uint32_t*           frame_err;    // [n_slots] or null
     uint8_t*            frame_class;  // [n_slots] or null
-    unsigned long long* counts;       // [9], zeroed by the caller: the fields of wifirx_link_counts in order
+    unsigned long long* counts;       // [9], zeroed by the caller: the fields of wifirx_link_counts in order; by_rate: [9 * 9],
+                                      // the totals and behind them the same nine per encoding 0..7 of the reference record
     uint32_t            rx_psdu_stride, ref_psdu_stride;
     uint32_t            dec_row_words;    // dwords per frame row of rx_dec / ref_dec (max_sym * 12)
     uint32_t            dec_is_hbits;
     uint32_t            max_sym, n_slots;
+    uint32_t            by_rate;
 };
 
 }  // namespace wr

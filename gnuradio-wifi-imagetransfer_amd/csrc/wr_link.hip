@@ -193,13 +193,18 @@ enum { LC_FRAMES, LC_REF, LC_GOOD, LC_CRC, LC_PSDU_OK, LC_CRC_WRONG, LC_BITS, LC
 // the first 64 loads of every row are issued together with the record loads and masked afterwards (a frame of config 3
 // has 33 of decisions and 74 of PSDU), so that a wave waits for memory once per frame, not twice.  Counters are kept per
 // wave, added per workgroup in LDS, then one 64-bit atomic add per counter and workgroup.
+// BY_RATE (wifirx_link_stats_by_rate): the same counters once more per encoding of the reference record, behind the totals
+// (a.counts[LC_N (1 + e) + i]).  A frame's nine contributions go from lanes 0..8 of its wave into the workgroup's LDS row of
+// its rate with one atomic instruction per frame -- eight more sets of per-wave counters would not fit the registers --, and
+// the rows into global memory at the end like the totals.
+template <bool BY_RATE>
 __global__ __launch_bounds__(LINK_THREADS)
 void link_stats_kernel(const LinkArgs a)
 {
-    __shared__ unsigned long long s_cnt[LC_N];
+    __shared__ unsigned long long s_cnt[BY_RATE ? 9 * LC_N : LC_N];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (tid < LC_N) s_cnt[tid] = 0;
+    if (tid < (BY_RATE ? 9 * LC_N : LC_N)) s_cnt[tid] = 0;
     __syncthreads();
 
     unsigned long long c[LC_N] = {};
@@ -233,6 +238,7 @@ void link_stats_kernel(const LinkArgs a)
             psdu_ok = __ballot(diff) == 0;
         }
         uint32_t e = 0xffffffffu;
+        unsigned long long f_bits = 0;
         if (good && have_dec) {
             const uint32_t nb = (uint32_t)nbpsc_of(rx.encoding);
             const uint32_t n_words = (a.dec_is_hbits ? 2 * nb : 12u) * n_sym, n_quads = n_words >> 2;
@@ -246,7 +252,8 @@ void link_stats_kernel(const LinkArgs a)
             const uint32_t t = (n_words & ~3u) + lane;
             if (lane < 3 && t < n_words) s += __popc(p[t] ^ q[t]);
             e = wave_sum(s);
-            c[LC_BITS] += (unsigned long long)n_sym * 48u * nb;
+            f_bits = (unsigned long long)n_sym * 48u * nb;
+            c[LC_BITS] += f_bits;
             c[LC_ERR] += e;
             c[LC_ERR_SQ] += (unsigned long long)e * e;
         }
@@ -256,6 +263,16 @@ void link_stats_kernel(const LinkArgs a)
         c[LC_CRC] += crc_ok;
         c[LC_PSDU_OK] += psdu_ok;
         c[LC_CRC_WRONG] += crc_ok && !psdu_ok;
+        if constexpr (BY_RATE) {
+            if (ref_c && rf.encoding < 8 && lane < LC_N) {      // (a reference record that is not complete lands in no rate)
+                const bool scored = f_bits != 0;
+                const unsigned long long v = lane == LC_FRAMES || lane == LC_REF ? 1ull : lane == LC_GOOD ? (unsigned long long)good
+                    : lane == LC_CRC ? (unsigned long long)crc_ok : lane == LC_PSDU_OK ? (unsigned long long)psdu_ok
+                    : lane == LC_CRC_WRONG ? (unsigned long long)(crc_ok && !psdu_ok) : lane == LC_BITS ? f_bits
+                    : !scored ? 0ull : lane == LC_ERR ? (unsigned long long)e : (unsigned long long)e * e;
+                if (v) atomicAdd(&s_cnt[LC_N * (1 + rf.encoding) + lane], v);
+            }
+        }
         if (lane == 0) {
             if (a.frame_err) a.frame_err[f] = e;
             if (a.frame_class) a.frame_class[f] = (uint8_t)((good ? 1 : 0) | (crc_ok ? 2 : 0) | (psdu_ok ? 4 : 0) | (ref_c ? 8 : 0));
@@ -266,7 +283,7 @@ void link_stats_kernel(const LinkArgs a)
         for (int i = 0; i < LC_N; i++)
             if (c[i]) atomicAdd(&s_cnt[i], c[i]);
     __syncthreads();
-    if (tid < LC_N && s_cnt[tid]) atomicAdd(&a.counts[tid], s_cnt[tid]);
+    if (tid < (BY_RATE ? 9 * LC_N : LC_N) && s_cnt[tid]) atomicAdd(&a.counts[tid], s_cnt[tid]);
 }
 
 }  // namespace wr
@@ -294,6 +311,7 @@ extern "C" hipError_t wr_launch_link_stats(hipStream_t st, const wr::LinkArgs* a
     const uint32_t per = wr::LINK_THREADS / 64;
     const uint32_t want = (args->n_slots + per - 1) / per, cap = 2 * (n_simd ? n_simd : 1024u);      // 8 waves per SIMD
     const dim3 grid(want < cap ? want : cap), block(wr::LINK_THREADS);
-    hipLaunchKernelGGL(wr::link_stats_kernel, grid, block, 0, st, *args);
+    if (args->by_rate) hipLaunchKernelGGL(wr::link_stats_kernel<true>, grid, block, 0, st, *args);
+    else hipLaunchKernelGGL(wr::link_stats_kernel<false>, grid, block, 0, st, *args);
     return hipGetLastError();
 }

@@ -5,7 +5,7 @@
 
 namespace wr {
 
-// one wifirx_tx_batch call, every pointer on the device.  Output sample g lies at out[g]; the kernel writes the samples
+// one wifirx_tx_batch or wifirx_tx_batch_rates call, every pointer on the device.  Output sample g lies at out[g]; the kernel writes the samples
 // [g0, g1) -- the rows, back to back -- and nothing else.  shift = 1 when `out` is 8 but not 16 bytes aligned: the 16-byte
 // stores then cover the samples (2 k - 1, 2 k).  v0 = the first such pair's index + shift, rounded down to even.
 struct TxArgs {
@@ -19,7 +19,9 @@ struct TxArgs {
     int64_t         g0, g1, v0, shift;
     uint32_t        n_frames, lead;
     uint32_t        enc, n_bpsc, n_cbps, n_dbps, rate_field;
-};
+    const uint8_t*  enc_v;      // [n_frames] one encoding per frame (wifirx_tx_batch_rates), or null: `enc` .. `rate_field`
+};                              // hold for every frame.  With enc_v those five are not read
+
 
 }  // namespace wr
 

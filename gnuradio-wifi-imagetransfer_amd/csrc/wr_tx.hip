@@ -9,8 +9,14 @@
 // the scrambler bit of position t is bit t mod 127 of the seed's period --, builds each in 16 lanes (lane r holds the FFT
 // inputs r + 16 j, the layout of the receive kernels' FFT, wr_quad.h) into LDS, and then writes the tile with one 16-byte
 // store per lane and pair of samples, zeros included.
+//
+// Two kinds of instance.  tx_kernel<NB, false>: every frame at the call's encoding (NB its bits per carrier), that
+// encoding's row of the bit map and its constellation axis in LDS.  tx_kernel<6, true>: one encoding per frame
+// (TxArgs::enc_v); the rate is a property of the row (TxRowMix), the bit loops run at the widest symbol with the guards the
+// SIGNAL symbol already needs, and the bit map is read from constant memory (see the kernel's comment).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "wr_quad.h"      // bfly4_reg, the twiddle table and the spec's complex product (rule 4)
 #include "wr_tx.h"
@@ -22,6 +28,11 @@ namespace wr {
                            // (k - 2) 481 < TX_TILE, so at most 6
 #define TX_SLOTS  38       // symbols one tile needs: <= TX_TILE / 80 + 2 per row touched = 25.6 + 12 (6 rows at most)
 #define TX_PBUF   1040     // PSDU bytes they read: <= (37 * 216 + 6 * 6) / 8 + 2 * 6 = 1016 (6 rows at most)
+// With one encoding per frame the three bounds stand as they are.  TX_ROWS: the shortest frame of any encoding is one data
+// symbol, 6 * 80 + 1 = 481 samples (1..23 bytes at 64-QAM 3/4; every other encoding needs more symbols for the same bytes),
+// so a mix cannot put more rows into a tile than a batch of such frames.  TX_SLOTS counts symbols by the 80 samples each
+// takes, whatever it carries.  TX_PBUF: the symbols a tile needs of one row are consecutive and read N_DBPS + 6 bits each
+// behind one another, rounded outwards to bytes once per row; 216 is the largest N_DBPS, so rows at other encodings read less.
 #define TX_NTW    46       // twiddles the FFT uses: W64^e, e = q r (stage 1) and 4 q (r & 3) (stage 2) <= 45
 
 // scrambler x^7 + x^4 + 1: period of the state 0x7F (bits 0..126, then repeated so that any 32 consecutive bits are one
@@ -80,6 +91,10 @@ struct TxRow {             // one row the tile touches
     int32_t  rs_rel, fs_rel, sbase;      // rs, fs relative to the tile's first sample (clamped to +-2^30); slot - s_lo
 };
 
+struct TxRowMix : TxRow {  // ... and its rate, where every frame has its own
+    uint32_t enc, n_bpsc, n_dbps, rate_field;
+};
+
 __device__ __forceinline__ uint32_t parity7(uint32_t v) { return __builtin_popcount(v) & 1u; }
 
 // Where coded bit `pos` (interleaved order) of an OFDM symbol comes from: de-interleave (802.11 17.3.5.7), de-puncture ->
@@ -112,20 +127,28 @@ __constant__ TxBitMap kTxMap = make_tx_bitmap();
 
 
 // NB = bits per sub-carrier of the call's encoding: the bit loops unroll, so that a symbol's table and window reads go
-// out together instead of one LDS round trip after the other
-template <int NB>
+// out together instead of one LDS round trip after the other.
+// MIX (NB = 6): one encoding per frame.  LDS is full (seven workgroups per CU leave 23 405 bytes each) and the nine rows of
+// kTxMap are 5 184 bytes, so this instance reads the map where it lies, in constant memory: the index is per lane, so these
+// are vector loads, and the whole table stays in the CU's cache (it is read by every workgroup).  Its LDS copy (672 bytes) goes
+// and the three constellation axes (14 floats: 2 | 4 | 8, at axis + 0, 2 and 6) and four words per row come, so the seven
+// workgroups per CU stay.  A wave builds four symbols at once, one per group of 16 lanes, and with rows of different
+// encodings in a tile it runs the unrolled bit loops at the width of the widest, the others masked by `b < n_bpsc`.
+template <int NB, bool MIX>
 __global__ __launch_bounds__(256, 7)     // 7 waves per SIMD (72 registers): seven workgroups per CU, as the LDS allows
 void tx_kernel(TxArgs a)
 {
+    static_assert(!MIX || NB == 6, "the mixed instance runs at the widest symbol");
+    using Row = typename std::conditional<MIX, TxRowMix, TxRow>::type;
     __shared__ float2   sym[TX_SLOTS][64];     // time-domain symbols (also the FFT's transpose space)
     __shared__ uint32_t win[16][8];            // data-bit window of the symbol each group of 16 lanes builds
-    __shared__ uint16_t bmap[288 + 48];        // kTxMap rows of the call's encoding and of SIGNAL
-    __shared__ float    axis[8];               // one axis of the call's constellation
+    __shared__ uint16_t bmap[MIX ? 2 : 288 + 48];      // kTxMap rows of the call's encoding and of SIGNAL (MIX: not used)
+    __shared__ float    axis[MIX ? 14 : 8];    // one axis of the call's constellation; MIX: of the three
     __shared__ float2   twd[TX_NTW];
     __shared__ uint32_t scr_pp[6];
     __shared__ uint8_t  scr_off[128];
     __shared__ uint8_t  pbuf[TX_PBUF];         // the PSDU bytes of the tile's data symbols
-    __shared__ TxRow    rows[TX_ROWS];
+    __shared__ Row      rows[TX_ROWS];
     __shared__ uint32_t n_rows_s, n_tasks_s;
 
     const int tid = threadIdx.x;
@@ -134,18 +157,25 @@ void tx_kernel(TxArgs a)
     const int64_t g_lo = v_lo - a.shift < a.g0 ? a.g0 : v_lo - a.shift;
     const int64_t g_hi = v_lo + TX_TILE - a.shift > a.g1 ? a.g1 : v_lo + TX_TILE - a.shift;
 
-    for (uint32_t i = tid; i < a.n_cbps; i += 256) bmap[i] = kTxMap.m[a.enc][i];
-    if (tid < 48) bmap[288 + tid] = kTxMap.m[8][tid];
+    if constexpr (!MIX) {
+        for (uint32_t i = tid; i < a.n_cbps; i += 256) bmap[i] = kTxMap.m[a.enc][i];
+        if (tid < 48) bmap[288 + tid] = kTxMap.m[8][tid];
+    }
     if (tid < TX_NTW) twd[tid] = make_float2(WR_TWIDDLE64[2 * tid], WR_TWIDDLE64[2 * tid + 1]);
     if (tid < 6) scr_pp[tid] = kTxScr.pp[tid];
     if (tid < 128) scr_off[tid] = kTxScr.off[tid];
-    if (tid < (1 << (a.n_bpsc >> 1)) && a.n_bpsc > 1) axis[tid] = a.n_bpsc == 2 ? kAxis2[tid] : a.n_bpsc == 4 ? kAxis4[tid] : kAxis6[tid];
+    if constexpr (MIX) {
+        if (tid < 14) axis[tid] = tid < 2 ? kAxis2[tid] : tid < 6 ? kAxis4[tid - 2] : kAxis6[tid - 6];
+    } else {
+        if (tid < (1 << (a.n_bpsc >> 1)) && a.n_bpsc > 1) axis[tid] = a.n_bpsc == 2 ? kAxis2[tid] : a.n_bpsc == 4 ? kAxis4[tid] : kAxis6[tid];
+    }
 
     // ---- the rows of the tile and the symbols it needs of each (lanes 0..7 of wave 0, one row each) ----
     if (tid < 64) {
         const uint32_t r0 = a.row_off ? a.tile_row[tile] : (uint32_t)((uint64_t)g_lo / a.row_len);
         const uint32_t r = r0 + (uint32_t)tid;
-        TxRow e{};
+        Row e{};
+        uint32_t n_dbps = a.n_dbps;
         bool in = tid < TX_ROWS && r < a.n_frames;
         if (in) {
             e.rs = a.row_off ? (int64_t)a.row_off[r] : (int64_t)r * (int64_t)a.row_len;
@@ -155,7 +185,16 @@ void tx_kernel(TxArgs a)
             e.frame = r;
             e.len = a.len[r];
             e.seed = a.seeds ? a.seeds[r] : r % 127u + 1u;
-            e.n_tot = 5 + (16 + 8 * e.len + 6 + a.n_dbps - 1) / a.n_dbps;
+            if constexpr (MIX) {
+                // the rate of the row from its encoding (the host has checked enc <= 7): N_BPSC 1 1 2 2 4 4 6 6; N_DBPS =
+                // 48 N_BPSC times 1/2 (even), 3/4 (odd) or 2/3 (64-QAM 2/3); RATE 0xD 0xF 0x5 0x7 0x9 0xB 0x1 0x3
+                e.enc = a.enc_v[r] & 7u;
+                e.n_bpsc = e.enc >= 6 ? 6u : 1u << (e.enc >> 1);
+                e.n_dbps = e.enc == 6 ? 192u : (e.enc & 1) ? 36u * e.n_bpsc : 24u * e.n_bpsc;
+                e.rate_field = (0x31B975FDu >> (4 * e.enc)) & 0xFu;
+                n_dbps = e.n_dbps;
+            }
+            e.n_tot = 5 + (16 + 8 * e.len + 6 + n_dbps - 1) / n_dbps;
             e.flen = e.n_tot * 80 + 1;
             e.fs = e.rs + a.lead;
             const int64_t lo = g_lo > e.fs ? g_lo : e.fs, hi = g_hi < e.fs + e.flen ? g_hi : e.fs + e.flen;
@@ -166,8 +205,8 @@ void tx_kernel(TxArgs a)
                 e.cnt = s_hi - e.s_lo + 1;
                 if (s_hi >= 5) {                                           // data symbols d_lo .. d_hi read data bits
                     const int32_t d_lo = (int32_t)max(e.s_lo, 5u) - 5, d_hi = (int32_t)s_hi - 5;   // d N_DBPS - 6 ..
-                    const int32_t q_lo = max(0, (d_lo * (int32_t)a.n_dbps - 22) >> 3);              // (d + 1) N_DBPS - 1
-                    const int32_t q_hi = min((int32_t)e.len, (((d_hi + 1) * (int32_t)a.n_dbps - 17) >> 3) + 1);
+                    const int32_t q_lo = max(0, (d_lo * (int32_t)n_dbps - 22) >> 3);                // (d + 1) N_DBPS - 1
+                    const int32_t q_hi = min((int32_t)e.len, (((d_hi + 1) * (int32_t)n_dbps - 17) >> 3) + 1);
                     e.b_lo = (uint32_t)q_lo;
                     e.b_n = q_hi > q_lo ? (uint32_t)(q_hi - q_lo) : 0;
                 }
@@ -196,7 +235,7 @@ void tx_kernel(TxArgs a)
     __syncthreads();
     const uint32_t n_rows = n_rows_s, n_tasks = n_tasks_s;
     for (uint32_t ei = 0; ei < n_rows; ei++) {                          // the PSDU bytes, row by row
-        const TxRow& e = rows[ei];
+        const Row& e = rows[ei];
         const uint8_t* p = a.psdu + (uint64_t)e.frame * a.psdu_stride + e.b_lo;
         for (uint32_t k = tid; k < e.b_n; k += 256) pbuf[e.boff + k] = p[k];
     }
@@ -217,22 +256,36 @@ void tx_kernel(TxArgs a)
         if (task < n_tasks) {
             uint32_t ei = 0;
             while (ei + 1 < n_rows && rows[ei + 1].slot <= task) ei++;
-            const TxRow e = rows[ei];                            // (a copy: one set of LDS reads)
+            const Row e = rows[ei];                              // (a copy: one set of LDS reads)
             const uint32_t s = e.s_lo + task - e.slot;
             const bool sig = s == 4;
-            const uint32_t n_bpsc = sig ? 1 : NB;
-            const uint16_t* bm = sig ? bmap + 288 : bmap;
+            uint32_t n_bpsc, n_dbps, rate_field;
+            const uint16_t* bm;
+            const float* ax;
+            if constexpr (MIX) {
+                n_bpsc = sig ? 1 : e.n_bpsc;
+                n_dbps = e.n_dbps;
+                rate_field = e.rate_field;
+                bm = kTxMap.m[sig ? 8 : e.enc];
+                ax = axis + (e.n_bpsc == 6 ? 6 : e.n_bpsc == 4 ? 2 : 0);
+            } else {
+                n_bpsc = sig ? 1 : NB;
+                n_dbps = a.n_dbps;
+                rate_field = a.rate_field;
+                bm = sig ? bmap + 288 : bmap;
+                ax = axis;
+            }
             uint32_t* w = win[grp];
             if (s >= 4 && r < 8) {                                       // the symbol's data-bit window, word r
                 uint32_t word = 0;
                 if (sig) {
                     // SIGNAL: RATE (4 bits, MSB first) | 0 | LENGTH (12 bits, LSB first) | even parity | 6 zero tail bits
-                    const uint32_t rf = a.rate_field;
+                    const uint32_t rf = rate_field;
                     uint32_t b = ((rf >> 3) & 1) | ((rf >> 2) & 1) << 1 | ((rf >> 1) & 1) << 2 | (rf & 1) << 3 | e.len << 5;
                     b |= (uint32_t)(__builtin_popcount(b) & 1) << 17;
                     word = r == 0 ? b << 6 : 0;
                 } else {
-                    const int32_t t0 = (int32_t)((s - 5) * a.n_dbps) - 6 + 32 * r;     // data bit of bit 0 of the word
+                    const int32_t t0 = (int32_t)((s - 5) * n_dbps) - 6 + 32 * r;       // data bit of bit 0 of the word
                     // PSDU bits (LSB first) behind the 16 SERVICE bits; bytes outside the PSDU read as 0
                     const int32_t bq = (t0 - 16) >> 3, sh = (t0 - 16) - 8 * bq;
                     uint64_t raw = 0;                                    // (bytes outside b_lo .. read as 0: such bits
@@ -296,7 +349,7 @@ void tx_kernel(TxArgs a)
                     X = { neg ? -1.0f : 1.0f, 0.0f };
                 } else if (dj[j]) {
                     if (n_bpsc == 1) X = { idx[j] ? 1.0f : -1.0f, 0.0f };
-                    else X = { axis[idx[j] & hmask], axis[idx[j] >> half] };
+                    else X = { ax[idx[j] & hmask], ax[idx[j] >> half] };
                 }
                 v[j] = { X.re, -X.im };                          // the IFFT as conj(FFT(conj(.)))
             }
@@ -339,7 +392,7 @@ void tx_kernel(TxArgs a)
     auto sample = [&](int32_t x) -> float2 {
         uint32_t ei = 0;
         while (ei + 1 < n_rows && rows[ei + 1].rs_rel <= x) ei++;
-        const TxRow& e = rows[ei];
+        const Row& e = rows[ei];
         const int32_t m = x - e.fs_rel;
         const bool in = n_rows != 0 && m >= 0 && m < (int32_t)e.flen;
         const uint32_t mu = in ? (uint32_t)m : 0, s = mu / 80, j = mu - 80 * s;
@@ -379,11 +432,15 @@ extern "C" hipError_t wr_launch_tx(hipStream_t st, const wr::TxArgs* args)
     if (args->g1 <= args->g0) return hipSuccess;
     const uint64_t n_tiles = ((uint64_t)(args->g1 + args->shift - args->v0) + TX_TILE - 1) / TX_TILE;
     const dim3 grid((unsigned)n_tiles), block(256);
+    if (args->enc_v) {
+        hipLaunchKernelGGL((wr::tx_kernel<6, true>), grid, block, 0, st, *args);
+        return hipGetLastError();
+    }
     switch (args->n_bpsc) {
-    case 1: hipLaunchKernelGGL(wr::tx_kernel<1>, grid, block, 0, st, *args); break;
-    case 2: hipLaunchKernelGGL(wr::tx_kernel<2>, grid, block, 0, st, *args); break;
-    case 4: hipLaunchKernelGGL(wr::tx_kernel<4>, grid, block, 0, st, *args); break;
-    default: hipLaunchKernelGGL(wr::tx_kernel<6>, grid, block, 0, st, *args); break;
+    case 1: hipLaunchKernelGGL((wr::tx_kernel<1, false>), grid, block, 0, st, *args); break;
+    case 2: hipLaunchKernelGGL((wr::tx_kernel<2, false>), grid, block, 0, st, *args); break;
+    case 4: hipLaunchKernelGGL((wr::tx_kernel<4, false>), grid, block, 0, st, *args); break;
+    default: hipLaunchKernelGGL((wr::tx_kernel<6, false>), grid, block, 0, st, *args); break;
     }
     return hipGetLastError();
 }

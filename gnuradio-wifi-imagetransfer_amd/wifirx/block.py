@@ -271,18 +271,21 @@ class wifi_phy_tx(grshim.sync_block):
     * ``samp_out``: the frames back to back in arrival order, each ``pad_front`` zeros + frame + ``pad_tail`` zeros.
 
     The scrambler seed runs 1..127 from frame to frame across ``work()`` calls, as the mapper's does.  Every ``work()``
-    builds all PDUs queued since the last one in one device call (wifirx_tx_batch); what does not fit ``output_items[0]``
-    is handed out by the following calls.  The block emits base-band at the hier block's level: IRS_user's x0.5 gain
-    stays in the flowgraph."""
+    builds all PDUs queued since the last one in one device call (wifirx_tx_batch, or wifirx_tx_batch_rates when
+    ``set_encoding`` came between them: a PDU is built at the encoding in force when it arrived, as the mapper does -- the
+    block notes at which position of its queue each setting took effect); what does not fit ``output_items[0]`` is handed
+    out by the following calls.  The block emits base-band at the hier block's level: IRS_user's x0.5 gain stays in the
+    flowgraph."""
 
     def __init__(self, encoding=0, pad_front=0, pad_tail=0, device=0):
         grshim.sync_block.__init__(self, name="wifi_phy_tx", in_sig=None, out_sig=[np.complex64])
+        self._queue = []                                            # PSDUs (bytes) waiting for work()
+        self._enc_from = []                                         # (position in the queue, encoding in force from there on)
         self.set_encoding(encoding)
         self.pad_front, self.pad_tail = int(pad_front), int(pad_tail)
         if self.pad_front < 0 or self.pad_tail < 0:
             raise ValueError("pad_front and pad_tail must be >= 0")
         self._rx = capi.WifiRx(max_sym=1, device=device)          # the handle's receive side stays unused
-        self._queue = []                                            # PSDUs (bytes) waiting for work()
         self._carry = np.zeros(0, dtype=np.complex64)               # built samples not yet handed out
         self._n_frames = 0                                          # frames built so far: the next seed
         self.message_port_register_in(grshim.intern("mac_in"))
@@ -296,6 +299,9 @@ class wifi_phy_tx(grshim.sync_block):
         if not 0 <= encoding <= 7:
             raise ValueError("encoding must be 0..7")
         self.encoding = encoding
+        if self._enc_from and self._enc_from[-1][0] == len(self._queue):
+            self._enc_from.pop()                                    # no PDU arrived under the previous setting
+        self._enc_from.append((len(self._queue), encoding))
 
     def _on_pdu(self, msg):
         vec = grshim.to_python(msg)[1]
@@ -304,11 +310,14 @@ class wifi_phy_tx(grshim.sync_block):
     def _build(self):
         psdus, self._queue = self._queue, []
         n = len(psdus)
+        marks, self._enc_from = self._enc_from + [(n, None)], [(0, self.encoding)]
+        encs = [e for (lo, e), (hi, _) in zip(marks[:-1], marks[1:]) for _ in range(hi - lo)]     # one per PDU
         seeds = (np.arange(self._n_frames, self._n_frames + n) % 127) + 1
-        rows = [self.pad_front + txgen.frame_samples(len(p), self.encoding) + self.pad_tail for p in psdus]
+        rows = [self.pad_front + txgen.frame_samples(len(p), e) + self.pad_tail for p, e in zip(psdus, encs)]
         row_off = np.zeros(n + 1, dtype=np.uint64)
         row_off[1:] = np.cumsum(rows)
-        x = self._rx.tx_batch(psdus, self.encoding, seeds=seeds, lead=self.pad_front, row_off=row_off)
+        encoding = encs[0] if len(set(encs)) == 1 else np.array(encs, np.uint8)
+        x = self._rx.tx_batch(psdus, encoding, seeds=seeds, lead=self.pad_front, row_off=row_off)
         self._n_frames += n
         self._carry = np.concatenate([self._carry, x]) if self._carry.size else x
 

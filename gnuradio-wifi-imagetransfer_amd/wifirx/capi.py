@@ -40,7 +40,7 @@ EXPORTS = [
     "wifirx_sync", "wifirx_stream", "wifirx_synth_slots", "wifirx_dev_alloc", "wifirx_dev_free",
     "wifirx_memcpy_h2d", "wifirx_memcpy_d2h", "wifirx_time_demod", "wifirx_poll_ex", "wifirx_demod_batch_v",
     "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft", "wifirx_tx_batch", "wifirx_channel",
-    "wifirx_mac_batch", "wifirx_link_stats",
+    "wifirx_mac_batch", "wifirx_link_stats", "wifirx_tx_batch_rates", "wifirx_link_stats_by_rate",
 ]
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
@@ -148,6 +148,8 @@ _lib.wifirx_synth_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32,
                                     C.c_void_p]
 _lib.wifirx_tx_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p,
                                  C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32]
+_lib.wifirx_tx_batch_rates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32]
 _lib.wifirx_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                 C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_float, C.c_float,
                                 C.c_uint64, C.c_uint64]
@@ -155,6 +157,8 @@ _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C
                                   C.c_uint64, C.c_void_p, C.c_uint32]
 _lib.wifirx_link_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.POINTER(Out), C.c_void_p, C.c_void_p,
                                    C.POINTER(LinkCounts)]
+_lib.wifirx_link_stats_by_rate.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.POINTER(Out), C.c_void_p, C.c_void_p,
+                                           C.POINTER(LinkCounts), C.POINTER(LinkCounts)]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -322,6 +326,16 @@ class WifiRx:
         self._check(_lib.wifirx_demod_batch_v(self._h, _np_ptr(iq), 0, _np_ptr(off), n_slots, C.byref(out)))
         return dict(frames=frames, idx=idx, llr=llr, carrier=car)
 
+    def demod_batch_var_dev(self, iq_ptr, slot_off, dev):
+        """wifirx_demod_batch_v over device samples at iq_ptr: slot k = samples [slot_off[k], slot_off[k+1]) (host offsets,
+        [n_slots + 1]), into the device buffers of `dev` (alloc_out)"""
+        off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError("slot_off needs n_slots + 1 entries")
+        out = self._out_struct(dev)
+        self._slot_off = off        # the library queues the copy of the offsets: they stay alive until the next call
+        self._check(_lib.wifirx_demod_batch_v(self._h, iq_ptr, 1, _np_ptr(off), off.size - 1, C.byref(out)))
+
     # -- batch mode, device buffers (the measured path) --
     def alloc_out(self, n_slots, psdu_stride=0, want_csi=False, want_stats=False, want_hbits=False, want_idx=True) -> dict:
         ms = self.cfg.max_sym
@@ -420,8 +434,9 @@ class WifiRx:
     def tx_batch_dev(self, samples_ptr, samples_cap, psdus, encoding, seeds=None, lead=0, row_len=None, row_off=None,
                      psdu_len=None, psdu_stride=None):
         """wifirx_tx_batch into device memory (samples_cap complex64 samples at samples_ptr).  psdus: host PSDUs (see
-        tx_batch), or an int device pointer with psdu_len (host lengths) and psdu_stride.  Asynchronous on the handle's
-        stream.  Returns the lengths used."""
+        tx_batch), or an int device pointer with psdu_len (host lengths) and psdu_stride.  encoding: an int, or an array-like
+        of n_frames values (wifirx_tx_batch_rates: frame i at encoding[i]).  Asynchronous on the handle's stream.  Returns
+        the lengths used."""
         if isinstance(psdus, int):
             lens = np.ascontiguousarray(psdu_len, dtype=np.uint32)
             ptr, on_dev, stride, keep = psdus, 1, int(psdu_stride), None
@@ -433,20 +448,34 @@ class WifiRx:
         ro = None if row_off is None else np.ascontiguousarray(row_off, dtype=np.uint64)
         if ro is not None and ro.size != n + 1:
             raise ValueError("row_off needs n_frames + 1 entries")
-        self._check(_lib.wifirx_tx_batch(self._h, int(encoding), ptr, on_dev, stride, _np_ptr(lens), _np_ptr(sd), n,
-                                         samples_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0), int(lead)))
+        if np.ndim(encoding) == 0:
+            self._check(_lib.wifirx_tx_batch(self._h, int(encoding), ptr, on_dev, stride, _np_ptr(lens), _np_ptr(sd), n,
+                                             samples_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0), int(lead)))
+            return lens
+        enc = self._tx_encodings(encoding, n)
+        self._check(_lib.wifirx_tx_batch_rates(self._h, _np_ptr(enc), ptr, on_dev, stride, _np_ptr(lens), _np_ptr(sd), n,
+                                               samples_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0), int(lead)))
         return lens
 
+    @staticmethod
+    def _tx_encodings(encoding, n):
+        """array-like of n encodings -> contiguous uint8 (values outside 0..255 become 255, which the library refuses)"""
+        e = np.asarray(encoding)
+        if e.shape != (n,):
+            raise ValueError("encoding needs n_frames entries")
+        return np.ascontiguousarray(np.where((e < 0) | (e > 255), 255, e).astype(np.uint8))
+
     def tx_batch(self, psdus, encoding, seeds=None, lead=0, row_len=None, row_off=None, psdu_len=None):
-        """Base-band frames of `psdus` (list of bytes, or a 2-D uint8 array with optional psdu_len) at one encoding, built on
-        the device.  Fixed rows (row_len; default lead + the longest frame): returns [n, row_len] complex64, frame i at
+        """Base-band frames of `psdus` (list of bytes, or a 2-D uint8 array with optional psdu_len) at one encoding (an int) or
+        at one encoding per frame (an array-like of n values), built on the device.  Fixed rows (row_len; default lead + the longest frame): returns [n, row_len] complex64, frame i at
         [i, lead:lead + frame].  row_off ([n + 1] sample offsets): returns the packed 1-D stream of samples
         [row_off[0], row_off[n]), frame i `lead` samples into its row."""
         from . import txgen
         arr, lens = self._tx_psdus(psdus, psdu_len)
         n = lens.size
         if row_off is None and row_len is None:
-            row_len = lead + max((txgen.frame_samples(int(l), encoding) for l in lens), default=0)
+            encs = np.broadcast_to(np.asarray(encoding), (n,))
+            row_len = lead + max((txgen.frame_samples(int(l), int(e)) for l, e in zip(lens, encs)), default=0)
         total = int(row_off[-1]) if row_off is not None else n * int(row_len)
         buf = self.alloc(max(total, 1) * 8)
         try:
@@ -583,20 +612,27 @@ class WifiRx:
         finally:
             buf.free()
 
-    def link_stats(self, n_slots, dev, ref, per_frame=False) -> dict:
+    def link_stats(self, n_slots, dev, ref, per_frame=False, by_rate=False) -> dict:
         """wifirx_link_stats: scores the decoded batch `dev` (an alloc_out dict after demod + decode) against `ref`, a dict with
         the DevBufs of what was sent: "frames" (required), "psdu" + "psdu_stride", "hbits" / "idx".  Returns the counters of
         wifirx_link_counts and, derived from them in float64, fer, coded_ber and coded_ber_se (the standard error of the mean
         of the per-frame BER, for frames of one length); per_frame=True adds "frame_err" (uint32) and "frame_class" (uint8)
-        as DevBufs the caller frees.  Waits for the result."""
+        as DevBufs the caller frees.  by_rate=True (wifirx_link_stats_by_rate) adds "by_rate": a list of eight dicts, the same
+        counters and derived values over the slots whose reference record has encoding e.  Waits for the result."""
         n = int(n_slots)
         o_rx, o_ref = self._out_struct(dev), self._out_struct(ref)
         d_err = self.alloc(4 * max(n, 1)) if per_frame else None
         d_cls = self.alloc(max(n, 1)) if per_frame else None
         cnt = LinkCounts()
+        rates = (LinkCounts * 8)()
         try:
-            self._check(_lib.wifirx_link_stats(self._h, n, C.byref(o_rx), C.byref(o_ref), d_err.ptr if per_frame else None,
-                                               d_cls.ptr if per_frame else None, C.byref(cnt)))
+            if by_rate:
+                self._check(_lib.wifirx_link_stats_by_rate(self._h, n, C.byref(o_rx), C.byref(o_ref),
+                                                           d_err.ptr if per_frame else None, d_cls.ptr if per_frame else None,
+                                                           C.byref(cnt), rates))
+            else:
+                self._check(_lib.wifirx_link_stats(self._h, n, C.byref(o_rx), C.byref(o_ref), d_err.ptr if per_frame else None,
+                                                   d_cls.ptr if per_frame else None, C.byref(cnt)))
         except Exception:
             if per_frame:
                 d_err.free()
@@ -604,6 +640,12 @@ class WifiRx:
             raise
         r = {k: int(getattr(cnt, k)) for k, _ in LinkCounts._fields_}
         r.update(link_rates(r))
+        if by_rate:
+            r["by_rate"] = []
+            for e in range(8):
+                d = {k: int(getattr(rates[e], k)) for k, _ in LinkCounts._fields_}
+                d.update(link_rates(d))
+                r["by_rate"].append(d)
         if per_frame:
             r["frame_err"], r["frame_class"] = d_err, d_cls
         return r

@@ -342,6 +342,19 @@ int  wifirx_tx_batch(wifirx_handle* h, int encoding, const uint8_t* psdu, int ps
                      const uint32_t* psdu_len, const uint8_t* seeds, uint32_t n_frames, float* samples, uint64_t samples_cap,
                      const uint64_t* row_off, uint64_t row_len, uint32_t lead);
 
+/* wifirx_tx_batch with one encoding per frame: frame i is built at encoding[i] -- its SIGNAL RATE field, its N_DBPS / N_CBPS,
+ * its n_sym = ceil((16 + 8 L_i + 6) / N_DBPS_i) and so its length (5 + n_sym) * 80 + 1 -- as upstream's mapper applies the rate in
+ * force when it handles each PDU.  Row i is, value for value, what wifirx_tx_batch writes for frame i alone at encoding[i] with
+ * the same seed (NUMERICS.md rule 16 holds per frame).  One kernel launch per call.
+ *   encoding  HOST [n_frames], WIFIRX_BPSK_1_2 .. WIFIRX_64QAM_3_4; it travels in the same upload as psdu_len, seeds, row_off.
+ *             When all entries are equal the call is wifirx_tx_batch at that encoding (the same kernel instance).
+ * Everything else -- psdu, psdu_len, seeds, samples, rows, lead, ORDER -- as wifirx_tx_batch, and so are the checks on the host
+ * before anything is queued: WIFIRX_EINVAL also for NULL encoding or an entry above 7; WIFIRX_ERANGE when a frame plus lead, at
+ * the frame's own encoding, does not fit its row.  n_frames = 0 does nothing and returns WIFIRX_OK. */
+int  wifirx_tx_batch_rates(wifirx_handle* h, const uint8_t* encoding, const uint8_t* psdu, int psdu_on_device,
+                           uint32_t psdu_stride, const uint32_t* psdu_len, const uint8_t* seeds, uint32_t n_frames,
+                           float* samples, uint64_t samples_cap, const uint64_t* row_off, uint64_t row_len, uint32_t lead);
+
 /* GNU Radio's channels.channel_model(noise_voltage, frequency_offset, epsilon = 1, taps, noise_seed), the block between TX
  * and RX of the reference's loop-back (gnu_radio/IRS_tranceiver.py:282-288), over n_rows rows of device samples; arithmetic =
  * NUMERICS.md rule 17.  Sample n of row r (x: the input row, y: the output row):
@@ -434,6 +447,17 @@ typedef struct wifirx_link_counts {
  * 72 bytes back and WAITS for them: when it returns, everything queued on the handle's stream before it has finished. */
 int  wifirx_link_stats(wifirx_handle* h, uint32_t n_slots, const wifirx_out* rx, const wifirx_out* ref,
                        uint32_t* frame_err, uint8_t* frame_class, wifirx_link_counts* counts);
+
+/* wifirx_link_stats with the counters split by rate: for a batch that mixes encodings (wifirx_tx_batch_rates).  Same inputs,
+ * same per-frame rules, same checks and ORDER (one kernel, one zeroing, one copy back of 9 * 72 bytes).
+ *   total     HOST, may be NULL: exactly what wifirx_link_stats returns in `counts`
+ *   by_rate   HOST [8]: by_rate[e] counts the slots whose REFERENCE record is WIFIRX_F_COMPLETE with encoding == e, so in it
+ *             frames == frames_ref.  A slot whose reference record is not complete lands in no rate.
+ * For every counter X except frames: sum over e of by_rate[e].X == total.X; sum over e of by_rate[e].frames == total.frames_ref.
+ * WIFIRX_EINVAL also for NULL by_rate. */
+int  wifirx_link_stats_by_rate(wifirx_handle* h, uint32_t n_slots, const wifirx_out* rx, const wifirx_out* ref,
+                               uint32_t* frame_err, uint8_t* frame_class, wifirx_link_counts* total,
+                               wifirx_link_counts* by_rate);
 
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);

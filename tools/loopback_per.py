@@ -7,7 +7,15 @@ decoders and the coded BER of the hard decisions, the quantities of tests/golden
 oracle), and the raw counters.  --host-stats also downloads the buffers, keeps the books in NumPy and asserts that both agree.
 Prints one JSON line, writes it to --out when given.
 
-    python tools/loopback_per.py [--frames 1000000] [--snr 5 10 15 20 25 30] [--host-stats] [--out profiles/loopback_per_config3_device_stats.json]"""
+    python tools/loopback_per.py [--frames 1000000] [--snr 5 10 15 20 25 30] [--host-stats] [--out profiles/loopback_per_config3_device_stats.json]
+
+--rates answers the rate question in one pass per SNR point: the same loop-back over a batch with the eight encodings cycling
+(frame i at encoding i % 8; wifirx_tx_batch_rates), in row_off rows of lead 160 + frame + 32 rounded up to even (wifirx_channel
+and wifirx_demod_batch_v take them), scored by wifirx_link_stats_by_rate.  Per point and rate: the counters, FER hard and soft,
+coded BER, and the goodput = delivered payload bits per sample of air time.  max_sym is 99 for this mix and the soft decoder
+needs 6 LLRs per carrier, so the LLR rows are bf16 (WIFIRX_LLR_BF16, 57 kB per frame); the default is 131 072 frames.
+
+    python tools/loopback_per.py --rates [--frames 131072] [--host-stats] [--out profiles/loopback_rates.json]"""
 import argparse
 import json
 import math
@@ -53,13 +61,16 @@ def check_host(r, hs, what):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=1_000_000)
+    ap.add_argument("--frames", type=int, default=None, help="default 1 000 000; with --rates 131 072")
+    ap.add_argument("--rates", action="store_true", help="the eight encodings cycling in one batch, statistics by rate")
     ap.add_argument("--snr", type=float, nargs="+", default=[5, 10, 15, 20, 25, 30])
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--host-stats", action="store_true", help="also keep the books in NumPy and assert they agree")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    n = a.frames
+    if a.rates:
+        return rates_main(a)
+    n = a.frames or 1_000_000
     n_sym = txgen.n_sym_for(PSDU_LEN, ENC)
     nb = txgen.RATE_TABLE[ENC][0]
     taps = np.load(os.path.join(ROOT, "tests", "golden", "sv_taps.npy")).astype(np.complex64)
@@ -109,6 +120,125 @@ def main():
                        "lead 160, sv_taps.npy sets cycling, CFO uniform in +-20 ppm, LS; hard and soft decode_mac" % n,
            "stats": "wifirx_link_stats on the device" + (", checked against the NumPy bookkeeping" if a.host_stats else ""),
            "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def host_stats_by_rate(rx, dev, n, max_sym, enc, p, fr_tx, idx_tx):
+    """the bookkeeping of wifirx_link_stats_by_rate on the host, from the downloaded records, PSDU rows and decisions"""
+    fr = dev["frames"].download(capi.FRAME_DTYPE, n)
+    got = dev["psdu"].download(np.uint8, n * 304).reshape(n, 304)[:, :PSDU_LEN]
+    idx = dev["idx"].download(np.uint8, n * max_sym * 48).reshape(n, -1)
+    out = []
+    for e in range(8):
+        sel = np.nonzero(enc == e)[0]
+        f, ft = fr[sel], fr_tx[sel]
+        n_sym, nb = txgen.n_sym_for(PSDU_LEN, e), txgen.RATE_TABLE[e][0]
+        crc = (f["flags"] & capi.F_CRC_OK) != 0
+        ok = crc & (f["psdu_len"] == PSDU_LEN) & (got[sel] == p[sel]).all(axis=1)
+        good = (((f["flags"] & capi.F_COMPLETE) != 0) & (f["encoding"] == ft["encoding"]) & (f["psdu_len"] == ft["psdu_len"])
+                & (f["n_sym"] == ft["n_sym"]))
+        err = POPCOUNT6[idx[sel][good][:, :n_sym * 48] ^ idx_tx[sel][good][:, :n_sym * 48]].sum(axis=1, dtype=np.int64)
+        out.append(dict(frames=sel.size, frames_ref=sel.size, frames_good=int(good.sum()), frames_crc_ok=int(crc.sum()),
+                        frames_psdu_ok=int(ok.sum()), frames_crc_ok_wrong=int((crc & ~ok).sum()),
+                        coded_bits=int(good.sum()) * n_sym * 48 * nb, coded_bit_errors=int(err.sum()),
+                        coded_bit_errors_sq=int((err * err).sum())))
+    return out
+
+
+def rates_main(a):
+    n = a.frames or 131072
+    n -= n % 8
+    enc = (np.arange(n) % 8).astype(np.uint8)
+    flen = np.array([txgen.frame_samples(PSDU_LEN, e) for e in range(8)])
+    max_sym = txgen.n_sym_for(PSDU_LEN, 0)
+    tail = 32
+    row_of = LEAD + flen + tail
+    row_of += row_of & 1
+    row_off = np.concatenate([[0], np.cumsum(row_of[enc])]).astype(np.uint64)
+    total = int(row_off[-1])
+    taps = np.load(os.path.join(ROOT, "tests", "golden", "sv_taps.npy")).astype(np.complex64)
+    rx = capi.WifiRx(max_sym=max_sym, llr_bits=6, chan_est=capi.EQ_LS, device=0)
+    rx.set_llr_format("bf16")
+    t_all = time.perf_counter()
+    d_psdu, rows, iq = rx.alloc(n * PSDU_LEN), rx.alloc(total * 8), rx.alloc(total * 8)
+    rx.mac_batch_dev(d_psdu.ptr, PSDU_LEN, n, None, payload_len=PSDU_LEN - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, total, d_psdu.ptr, enc, psdu_len=np.full(n, PSDU_LEN, np.uint32), psdu_stride=PSDU_LEN,
+                    lead=LEAD, row_off=row_off)
+    dev = rx.alloc_out(n, psdu_stride=304, want_hbits=True)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * max_sym * 48),
+               hbits=rx.alloc(n * max_sym * 48), psdu=d_psdu, psdu_stride=PSDU_LEN)
+    rx.demod_batch_var_dev(rows.ptr, row_off, ref)
+    clean = rx.link_stats(n, ref, ref, by_rate=True)
+    assert clean["frames_ref"] == n and all(b["frames_good"] == n // 8 for b in clean["by_rate"]), "a clean frame was not demodulated"
+    if a.host_stats:
+        p = d_psdu.download(np.uint8, n * PSDU_LEN).reshape(n, PSDU_LEN)
+        fr_tx = ref["frames"].download(capi.FRAME_DTYPE, n)
+        idx_tx = ref["idx"].download(np.uint8, n * max_sym * 48).reshape(n, -1)
+    payload_bits = 8 * (PSDU_LEN - 28)
+    points = []
+    for snr in a.snr:
+        t0 = time.perf_counter()
+        cfo = np.random.default_rng(int(1000 * snr) + a.seed).uniform(-CFO_20PPM, CFO_20PPM, n).astype(np.float32)
+        rx.channel_dev(rows.ptr, iq.ptr, total, n, row_off=row_off, taps=taps, cfo=cfo, gain=math.sqrt(10 ** (snr / 10)),
+                       noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32))
+        rx.demod_batch_var_dev(iq.ptr, row_off, dev)
+        both = []
+        for soft in (False, True):
+            (rx.decode_batch_soft_dev if soft else rx.decode_batch_dev)(n, dev)
+            r = rx.link_stats(n, dev, ref, by_rate=True)
+            assert {k: r[k] for k in COUNTERS} == {k: rx.link_stats(n, dev, ref)[k] for k in COUNTERS}
+            if a.host_stats:
+                hs = host_stats_by_rate(rx, dev, n, max_sym, enc, p, fr_tx, idx_tx)
+                for e in range(8):
+                    assert {k: r["by_rate"][e][k] for k in COUNTERS} == hs[e], ("soft" if soft else "hard", e, r["by_rate"][e], hs[e])
+            both.append(r)
+        hard, soft = both
+        rates = []
+        for e in range(8):
+            h, s = hard["by_rate"][e], soft["by_rate"][e]
+            rates.append({"encoding": e, "frame_samples": int(flen[e]), "fer": h["fer"], "fer_soft": s["fer"],
+                          "coded_ber": h["coded_ber"], "coded_ber_se": h["coded_ber_se"],
+                          "goodput_bits_per_sample": h["frames_psdu_ok"] * payload_bits / (h["frames_ref"] * float(flen[e])),
+                          "goodput_bits_per_sample_soft": s["frames_psdu_ok"] * payload_bits / (s["frames_ref"] * float(flen[e])),
+                          "counts": {k: h[k] for k in COUNTERS}, "counts_soft": {k: s[k] for k in COUNTERS}})
+        best = max(rates, key=lambda q: q["goodput_bits_per_sample_soft"])
+        points.append({"snr_db": snr, "frames": n, "seconds": time.perf_counter() - t0, "best_encoding_soft": best["encoding"],
+                       "counts": {k: hard[k] for k in COUNTERS}, "counts_soft": {k: soft[k] for k in COUNTERS}, "rates": rates})
+        print(json.dumps({"snr_db": snr, "seconds": points[-1]["seconds"],
+                          "fer": [q["fer"] for q in rates], "fer_soft": [q["fer_soft"] for q in rates],
+                          "goodput_soft": [round(q["goodput_bits_per_sample_soft"], 4) for q in rates]}), file=sys.stderr)
+    seconds_total = time.perf_counter() - t_all
+    rx.free_out(ref)
+    rx.free_out(dev)
+    rows.free(); iq.free(); rx.close()
+    # the encoding-7 column is config 3's experiment with other noise: both FERs side by side, with the binomial standard
+    # error of each; nothing is asserted
+    side, c3 = [], os.path.join(ROOT, "profiles", "loopback_per_config3_device_stats.json")
+    if os.path.exists(c3):
+        with open(c3) as f:
+            rec = json.load(f)
+        old = {q["snr_db"]: q for q in rec.get("record", rec).get("points", [])}
+        se = lambda f_, m: math.sqrt(max(f_ * (1.0 - f_), 0.0) / m)
+        for q in points:
+            o = old.get(q["snr_db"])
+            if o is None:
+                continue
+            r7 = q["rates"][7]
+            for key in ("fer", "fer_soft"):
+                side.append({"snr_db": q["snr_db"], "what": key, "here": r7[key], "here_se": se(r7[key], n // 8),
+                             "config3": o[key], "config3_se": se(o[key], o["frames"])})
+                print("encoding 7, %g dB, %s: %.5f +- %.5f here, %.5f +- %.5f in config 3's sweep"
+                      % (q["snr_db"], key, r7[key], side[-1]["here_se"], o[key], side[-1]["config3_se"]), file=sys.stderr)
+    res = {"workload": "loop-back on the device, the eight encodings cycling: %d distinct frames per point (%d per rate; wifirx_mac_batch, "
+                       "Philox payloads), PSDU 294 B, row_off rows of lead 160 + frame + %d rounded up to even, sv_taps.npy sets cycling, "
+                       "CFO uniform in +-20 ppm, LS; hard and soft decode_mac" % (n, n // 8, tail),
+           "llr": "bf16 (WIFIRX_LLR_BF16), 6 per carrier, max_sym %d: %d bytes per frame" % (max_sym, max_sym * 48 * 6 * 2),
+           "stats": "wifirx_link_stats_by_rate on the device" + (", checked against the NumPy bookkeeping" if a.host_stats else ""),
+           "goodput": "frames_psdu_ok * %d payload bits / (frames_ref * frame_samples)" % payload_bits,
+           "seconds_total": seconds_total, "points": points, "encoding_7_against_config3": side}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
