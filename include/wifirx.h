@@ -146,6 +146,8 @@ typedef struct wifirx_config {
 /* stream mode: 1 = decode_mac runs on LLRs (wifirx_decode_batch_soft, NUMERICS.md rule 14) instead of the hard decisions.
  * The frame kernel then writes LLRs with 6 bits per carrier reserved into rows the handle owns (max_sym * 48 * 6 floats
  * per trigger, allocated once the mode is on), whatever cfg.llr_bits is; WIFIRX_P_LLR_CSI weights them as in batch mode.
+ * The frame records of such a batch are those of a handle created with llr_bits = 6: WIFIRX_F_LLR is set for every frame
+ * whose symbols were demodulated, also on a handle with llr_bits = 0 (wifirx_poll* still has no LLR output).
  * Default 0 (the upstream hard-decision decoder); other values are WIFIRX_EINVAL.  Batches run after the call use it. */
 #define WIFIRX_P_STREAM_SOFT 9
 /* LLR format of the batch calls made after it is set (NUMERICS.md rule 15): WIFIRX_LLR_F32 (default) = float32 values;

@@ -12,7 +12,12 @@ Test infrastructure only: the package never imports it.  It restates the contrac
 * add-compare-select: m0 = pm[p0] + bm0, m1 = pm[p1] + bm1, m1 taken only if m1 < m0 (survivor bit = m1 < m0);
 * start: state 0 at 0, the other states at +inf; before every step t > 0 with t % NORM_STEPS == 0 the minimum of
   the 64 metrics is subtracted from all of them;
-* end: smallest metric, lowest state on ties; trace back over the hard path's trellis length, descramble, CRC-32.
+* end: smallest metric, lowest state on ties; trace back over the hard path's trellis length, descramble, CRC-32;
+* overflow: plain IEEE float32, nothing clamped.  Metrics may reach +inf; when all 64 are +inf at a normalisation
+  (LLR magnitudes around 1e37 and above) inf - inf makes all 64 NaN, no comparison is true from then on, and the
+  survivor bits and the end state are 0.  A frame's metrics are NaN in none or in all 64 states (asserted below at
+  every normalisation and at the end): that is what makes min / argmin here and fminf / the `<` scan of the kernel
+  interchangeable.
 """
 from __future__ import annotations
 
@@ -99,9 +104,17 @@ def _scrambler_table(n_bits: int) -> np.ndarray:
 _SCR = None
 
 
-def viterbi_soft(coded: np.ndarray) -> np.ndarray:
+def _none_or_all_nan(pm: np.ndarray) -> np.ndarray:
+    """[F] bool: the frames whose metrics are NaN; a frame with some but not all 64 NaN is outside the contract"""
+    n_nan = np.isnan(pm).sum(axis=1)
+    assert np.all((n_nan == 0) | (n_nan == 64)), "a frame's 64 metrics are partly NaN"
+    return n_nan == 64
+
+
+def viterbi_soft(coded: np.ndarray, nan_frames: list | None = None) -> np.ndarray:
     """coded: float32 [F][2 n] -- the sanitised LLR of every de-punctured coded bit (0 = no information).
-    Returns the decoded bits uint8 [F][n]."""
+    Returns the decoded bits uint8 [F][n].  nan_frames (a list): gets one bool array [F], the frames that ended in the
+    all-NaN regime."""
     coded = np.asarray(coded, dtype=np.float32)
     F, n2 = coded.shape
     n = n2 // 2
@@ -109,10 +122,11 @@ def viterbi_soft(coded: np.ndarray) -> np.ndarray:
     pm = np.full((F, 64), np.inf, dtype=np.float32)
     pm[:, 0] = 0
     surv = np.empty((n, F, 8), dtype=np.uint8)
-    with np.errstate(invalid="raise", over="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
         for t in range(n):
             if t and t % NORM_STEPS == 0:
-                pm = pm - pm.min(axis=1, keepdims=True)
+                pm = pm - pm.min(axis=1, keepdims=True)          # inf - inf = NaN: the overflow regime
+                _none_or_all_nan(pm)
             la, lb = coded[:, 2 * t], coded[:, 2 * t + 1]
             ca = np.stack([np.maximum(la, zero), np.maximum(-la, zero)], axis=1)      # cost of expecting 0 / 1
             cb = np.stack([np.maximum(lb, zero), np.maximum(-lb, zero)], axis=1)
@@ -122,7 +136,10 @@ def viterbi_soft(coded: np.ndarray) -> np.ndarray:
             take = m1 < m0
             pm = np.where(take, m1, m0)
             surv[t] = np.packbits(take, axis=1, bitorder="little")
-    s = np.argmin(pm, axis=1)                   # first minimum = lowest state
+    is_nan = _none_or_all_nan(pm)
+    if nan_frames is not None:
+        nan_frames.append(is_nan)
+    s = np.where(is_nan, 0, np.argmin(pm, axis=1))          # first minimum = lowest state; no `<` is true among NaNs
     out = np.empty((F, n), dtype=np.uint8)
     rows = np.arange(F)
     for t in range(n - 1, -1, -1):
@@ -159,13 +176,16 @@ def finish(dec: np.ndarray, psdu_len: int):
     return by, ok
 
 
-def decode_batch(frames: np.ndarray, llr: np.ndarray, max_sym: int, psdu_stride: int = 2048, chunk: int = 1024):
+def decode_batch(frames: np.ndarray, llr: np.ndarray, max_sym: int, psdu_stride: int = 2048, chunk: int = 1024,
+                 llr_bits: int = 6, nan_out: np.ndarray | None = None):
     """The contract over a batch.  frames: FRAME_DTYPE [n]; llr: float32 [n][max_sym*48*llr_bits].
-    Returns (frames with F_DECODED / F_CRC_OK updated, psdu uint8 [n][psdu_stride])."""
+    Returns (frames with F_DECODED / F_CRC_OK updated, psdu uint8 [n][psdu_stride]).  llr_bits: frames of a rate with more
+    bits per carrier have no LLRs in the row and are left alone.  nan_out (bool [n]): set where a frame ended all-NaN."""
     frames = frames.copy()
     n = frames.shape[0]
     psdu = np.zeros((n, psdu_stride), dtype=np.uint8)
-    sel = np.nonzero(decodable(frames, max_sym, psdu_stride))[0]
+    fits = np.array(N_BPSC)[frames["encoding"].astype(np.int64) & 7] <= llr_bits
+    sel = np.nonzero(decodable(frames, max_sym, psdu_stride) & fits)[0]
     if sel.size == 0:
         return frames, psdu
     key = (frames["encoding"][sel].astype(np.int64) & 7) * 65536 + frames["psdu_len"][sel]
@@ -174,7 +194,10 @@ def decode_batch(frames: np.ndarray, llr: np.ndarray, max_sym: int, psdu_stride:
         enc, ln = int(k) >> 16, int(k) & 0xFFFF
         for c0 in range(0, grp.size, chunk):
             g = grp[c0:c0 + chunk]
-            dec = viterbi_soft(coded_llrs(llr[g], enc, ln))
+            nf = []
+            dec = viterbi_soft(coded_llrs(llr[g], enc, ln), nf)
+            if nan_out is not None:
+                nan_out[g] = nf[0]
             by, ok = finish(dec, ln)
             psdu[g, :ln] = by
             fl = frames["flags"][g] | F_DECODED

@@ -7,18 +7,21 @@ from wifirx import txgen
 pytestmark = pytest.mark.gpu
 
 
-def build_stream(seed=3, noise=True):
+def build_stream(seed=3, noise=True, snr_db=24):
     """A stream like the one IRS_user sends (frames with 100 front / 1000 tail padding,
-    gnu_radio/IRS_user.py:193), mixed rates and lengths, per-frame CFO, unit-variance noise."""
+    gnu_radio/IRS_user.py:193), mixed rates and lengths, per-frame CFO, unit-variance noise.
+    snr_db: one value for all ten frames, or one per frame."""
     rng = np.random.default_rng(seed)
     parts, psdus = [], []
     specs = [(0, 60), (2, 294), (4, 500), (7, 1000), (2, 294), (5, 120), (3, 294), (6, 64), (1, 200), (2, 294)]
+    snrs = [snr_db] * len(specs) if np.ndim(snr_db) == 0 else list(snr_db)
+    assert len(snrs) == len(specs)
     for k, (enc, plen) in enumerate(specs):
         psdu = txgen.make_psdus(1, plen, seed=seed * 100 + k, seq0=k)
         tx = txgen.encode_psdus(psdu, enc, seeds=[(k % 127) + 1])
         n = tx.samples.shape[1]
         cfo = rng.uniform(-0.03, 0.03)
-        sig = tx.samples[0] * np.exp(1j * cfo * np.arange(n)) * np.sqrt(10 ** (24 / 10))
+        sig = tx.samples[0] * np.exp(1j * cfo * np.arange(n)) * np.sqrt(10 ** (snrs[k] / 10))
         gap_front, gap_tail = 100, (1000 if k != 4 else 200)
         parts += [np.zeros(gap_front, np.complex64), sig.astype(np.complex64), np.zeros(gap_tail, np.complex64)]
         psdus.append(psdu[0])
