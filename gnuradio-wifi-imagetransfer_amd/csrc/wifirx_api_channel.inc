@@ -1,10 +1,11 @@
-// channel entry point: channels.channel_model over rows of device samples (wr_channel.hip)
+// channel entry points: channels.channel_model over rows of device samples (wr_channel.hip)
 
-extern "C" int wifirx_channel(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
-                              const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
-                              const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
-                              const float* cfo, uint64_t phase0, float gain, float noise_voltage,
-                              uint64_t seed, uint64_t sample0)
+// wifirx_channel (sro == NULL: drift0 is not looked at) and wifirx_channel_sro
+static int channel_call(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
+                        const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
+                        const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
+                        const float* cfo, uint64_t phase0, const float* sro, int64_t drift0, float gain, float noise_voltage,
+                        uint64_t seed, uint64_t sample0)
 {
     if (!h) return WIFIRX_EINVAL;
     if (!in || !out || !taps) return fail(h, WIFIRX_EINVAL, "in, out and taps are required");
@@ -18,6 +19,10 @@ extern "C" int wifirx_channel(wifirx_handle* h, const float* in, float* out, uin
     if (cfo)
         for (uint32_t r = 0; r < n_rows; r++)
             if (!std::isfinite(cfo[r])) return fail(h, WIFIRX_EINVAL, "cfo must be finite");
+    if (sro)
+        for (uint32_t r = 0; r < n_rows; r++)
+            if (!(std::fabs(sro[r]) <= 0x1p-8f)) return fail(h, WIFIRX_EINVAL, "sro must be finite and at most 2^-8 in magnitude");
+    if (sro && in == out) return fail(h, WIFIRX_EINVAL, "in place is not possible with a sample-rate offset");
     if (row_off)
         for (uint32_t r = 0; r < n_rows; r++)
             if (row_off[r + 1] < row_off[r]) return fail(h, WIFIRX_EINVAL, "row_off must not decrease");
@@ -30,6 +35,21 @@ extern "C" int wifirx_channel(wifirx_handle* h, const float* in, float* out, uin
         const uintptr_t o0 = reinterpret_cast<uintptr_t>(out) + 8 * g0, o1 = reinterpret_cast<uintptr_t>(out) + 8 * g1;
         if (i0 < o1 && o0 < i1 && !(n_taps == 1 && in == out))
             return fail(h, WIFIRX_EINVAL, "in and out overlap: only in == out with one tap is allowed");
+    }
+    // rule 18: dinc_r = llround(sro_r 2^40) (exact in double: a float32 times a power of two), |dinc| <= 2^32; the drift
+    // D(n) = drift0 + dinc n of every sample of every row must stay below 2^62 in magnitude
+    std::vector<int64_t> dinc;
+    if (sro) {
+        dinc.resize(n_rows);
+        uint64_t longest = row_off ? 0 : row_len, worst = 0;
+        for (uint32_t r = 0; r < n_rows; r++) {
+            dinc[r] = std::llround((double)sro[r] * 0x1p40);
+            worst = std::max<uint64_t>(worst, (uint64_t)std::llabs(dinc[r]));
+            if (row_off) longest = std::max(longest, row_off[r + 1] - row_off[r]);
+        }
+        const unsigned __int128 reach = (unsigned __int128)(drift0 < 0 ? 0 - (uint64_t)drift0 : (uint64_t)drift0) +
+                                        (unsigned __int128)worst * longest;
+        if (reach >= ((unsigned __int128)1 << 62)) return fail(h, WIFIRX_ERANGE, "|drift0| + |dinc| * (longest row) must stay below 2^62");
     }
 
     wr::ChanArgs a{};
@@ -55,12 +75,13 @@ extern "C" int wifirx_channel(wifirx_handle* h, const float* in, float* out, uin
     stream_worker_wait_idle(h);
     HIP_TRY(h, hipSetDevice(h->device));
 
-    // one upload of what the host holds: taps | cfo | row offsets | tile bases (row_off form)
+    // one upload of what the host holds: taps | cfo | row offsets | tile bases (row_off form) | drift increments (sro)
     const size_t taps_bytes = 8ull * n_taps * n_tap_sets;
     const size_t o_taps = 0, o_cfo = o_taps + (taps_on_device ? 0 : taps_bytes);
     const size_t o_row = o_cfo + (cfo ? (4ull * n_rows + 7) & ~7ull : 0);
     const size_t o_tile = o_row + (row_off ? 8ull * (n_rows + 1) : 0);
-    const size_t meta_bytes = o_tile + (row_off ? 8ull * (n_rows + 1) : 0);
+    const size_t o_dinc = o_tile + (row_off ? 8ull * (n_rows + 1) : 0);
+    const size_t meta_bytes = o_dinc + (sro ? 8ull * n_rows : 0);
     uint8_t* dm = nullptr;
     if (meta_bytes) {
         std::vector<uint8_t> meta(meta_bytes);      // (the phase increments are derived on the device: wr_channel.hip)
@@ -70,6 +91,7 @@ extern "C" int wifirx_channel(wifirx_handle* h, const float* in, float* out, uin
             std::memcpy(meta.data() + o_row, row_off, 8ull * (n_rows + 1));
             std::memcpy(meta.data() + o_tile, tile_base.data(), 8ull * (n_rows + 1));
         }
+        if (sro) std::memcpy(meta.data() + o_dinc, dinc.data(), 8ull * n_rows);
         int rc = h->stage.ch_meta.reserve(h, meta_bytes);
         if (rc) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->stage.ch_meta.p, meta.data(), meta_bytes, hipMemcpyHostToDevice, h->stream));
@@ -93,6 +115,38 @@ extern "C" int wifirx_channel(wifirx_handle* h, const float* in, float* out, uin
     a.n_tap_sets = n_tap_sets;
     a.gain = gain;
     a.noise = noise_voltage;
+    a.dinc = sro ? reinterpret_cast<const int64_t*>(dm + o_dinc) : nullptr;
+    a.drift0 = sro ? drift0 : 0;
     HIP_TRY(h, wr_launch_channel(h->stream, &a, n_tiles));
+    return WIFIRX_OK;
+}
+
+extern "C" int wifirx_channel(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
+                              const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
+                              const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
+                              const float* cfo, uint64_t phase0, float gain, float noise_voltage,
+                              uint64_t seed, uint64_t sample0)
+{
+    return channel_call(h, in, out, samples_cap, row_off, row_len, n_rows, taps, taps_on_device, n_taps, n_tap_sets, cfo, phase0,
+                        nullptr, 0, gain, noise_voltage, seed, sample0);
+}
+
+extern "C" int wifirx_channel_sro(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
+                                  const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
+                                  const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
+                                  const float* cfo, uint64_t phase0, const float* sro, int64_t drift0,
+                                  float gain, float noise_voltage, uint64_t seed, uint64_t sample0)
+{
+    return channel_call(h, in, out, samples_cap, row_off, row_len, n_rows, taps, taps_on_device, n_taps, n_tap_sets, cfo, phase0,
+                        sro, drift0, gain, noise_voltage, seed, sample0);
+}
+
+extern "C" int wifirx_resampler_table(const float** taps, uint32_t* n_phases, uint32_t* n_taps)
+{
+    uint32_t phases, width;
+    const float* table = wr_resample_table(&phases, &width);
+    if (taps) *taps = table;
+    if (n_phases) *n_phases = phases;
+    if (n_taps) *n_taps = width;
     return WIFIRX_OK;
 }

@@ -20,6 +20,8 @@ struct ChanArgs {
     uint32_t        n_rows, n_taps, n_tap_sets;
     int32_t         shift;
     float           gain, noise;
+    const int64_t*  dinc;         // [n_rows] drift per sample in 2^-40 samples (NUMERICS.md rule 18), or null: no resampler
+    int64_t         drift0;       // drift of every row's first output sample, 2^-40 samples
 };
 
 }  // namespace wr
@@ -27,4 +29,5 @@ struct ChanArgs {
 extern "C" {
 hipError_t wr_launch_channel(hipStream_t st, const wr::ChanArgs* args, uint64_t n_tiles);
 uint32_t   wr_channel_tile_samples(void);
+const float* wr_resample_table(uint32_t* n_phases, uint32_t* n_taps);      // host copy of the rule-18 table, [n_phases + 1][n_taps]
 }

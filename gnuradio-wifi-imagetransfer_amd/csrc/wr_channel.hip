@@ -8,17 +8,29 @@
 // CH_TILE / 512 pairs of consecutive samples and writes each with one 16-byte store.  The phase is fixed point (a uint64
 // in 2^-64 turns: exact for any row length), the noise is wr_synth.hip's Philox4x32-10 + Box-Muller on the counter
 // (pair index of the sample, row).
+//
+// With a sample-rate offset (wifirx_channel_sro, NUMERICS.md rule 18) a further kind of instance puts the polyphase
+// resampler in front of the FIR inside the same launch: the workgroup stages the raw input window of its tile (the tile,
+// the FIR halo, the resampler's 31 neighbours and the drift spread over the tile) and the table in LDS, forms the resampled
+// samples u of the tile and its FIR halo into the array the FIR reads, and goes on as the other instances do.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "wr_device.h"     // sp_sincos (rule 1)
 #include "wr_rng.h"        // philox4x32_10, u01
 #include "wr_channel.h"
+#include "wr_resample_table.h"
 
 namespace wr {
 
 #define CH_TILE     2048     // samples per workgroup: four pairs per lane of a 256-lane group
 #define CH_MAX_TAPS 64
+// raw input window of a resampling tile: the CH_TILE + CH_MAX_TAPS - 1 outputs u it forms read input positions that spread
+// over at most that many samples plus ceil((CH_TILE + CH_MAX_TAPS - 2) / 256) = 9 of drift (|sro| <= 2^-8), plus the
+// resampler's WR_RS_TAPS - 1 neighbours
+#define CH_RAW      (CH_TILE + CH_MAX_TAPS - 1 + 9 + WR_RS_TAPS - 1)
+
+__device__ const float rs_table[(WR_RS_PHASES + 1) * WR_RS_TAPS] = WR_RS_TABLE_INIT;
 
 constexpr float CH_PHASE_SCALE = (float)(6.283185307179586 / 4294967296.0);      // 2 pi / 2^32: radians per unit of P >> 32
 
@@ -64,12 +76,19 @@ __device__ __forceinline__ uint4 ch_draw(uint64_t pair, uint32_t row, uint2 key)
     return philox4x32_10(make_uint4((uint32_t)pair, row, (uint32_t)(pair >> 32), 0u), key);
 }
 
-template <bool STAGE>     // STAGE: n_taps > 1, the input tile and its halo go through LDS
+// rule 18: output n of a row whose drift is D = drift0 + dinc n (2^-40 samples) reads the input around i = n + (D >> 40)
+__device__ __forceinline__ int64_t rs_pos(int64_t n, int64_t D) { return n + (D >> 40); }
+
+// STAGE: the FIR reads its input from LDS (n_taps > 1, or SRO); SRO: that input is the resampled row (rule 18), any n_taps
+template <bool STAGE, bool SRO>
 __global__ __launch_bounds__(256)
 void channel_kernel(const ChanArgs a)
 {
+    static_assert(STAGE || !SRO, "the resampler writes the array the FIR reads");
     __shared__ float2 xs[STAGE ? CH_TILE + CH_MAX_TAPS - 1 : 1];
     __shared__ float2 tp[CH_MAX_TAPS];
+    __shared__ float2 raw[SRO ? CH_RAW : 1];
+    __shared__ __attribute__((aligned(16))) float tab[SRO ? (WR_RS_PHASES + 1) * WR_RS_TAPS : 1];
     const uint32_t tid = threadIdx.x;
     const uint64_t tile = blockIdx.x;
 
@@ -94,7 +113,41 @@ void channel_kernel(const ChanArgs a)
     const uint32_t L = a.n_taps;
 
     if (tid < L) tp[tid] = a.taps[(size_t)(r % a.n_tap_sets) * L + tid];
-    if constexpr (STAGE) {
+    if constexpr (SRO) {
+        const int64_t len = re - rs;
+        const int64_t dinc = a.dinc[r];
+        const int64_t n0 = gt - rs - (int64_t)(L - 1);            // row index of xs[0]; may be negative
+        // the outputs this tile forms, [nA, nB], and the input window they read (i is non-decreasing in n)
+        const int64_t nA = n0 > 0 ? n0 : 0;
+        const int64_t nB = (n0 + CH_TILE + (int64_t)L - 2 < len - 1) ? n0 + CH_TILE + (int64_t)L - 2 : len - 1;
+        const int64_t lo = rs_pos(nA, a.drift0 + dinc * nA) - WR_RS_CENTER;
+        int64_t W = rs_pos(nB, a.drift0 + dinc * nB) + (WR_RS_TAPS - WR_RS_CENTER) - lo;      // nB < nA: nothing to form
+        if (W > CH_RAW) W = CH_RAW;                               // (cannot bind: see CH_RAW)
+        for (uint32_t i = tid; i < (WR_RS_PHASES + 1) * WR_RS_TAPS; i += 256) tab[i] = rs_table[i];
+        for (int64_t i = tid; i < W; i += 256) {
+            const int64_t m = lo + i;
+            raw[i] = (m >= 0 && m < len) ? a.in[rs + m] : make_float2(0.0f, 0.0f);
+        }
+        __syncthreads();
+        for (uint32_t t = tid; t < CH_TILE + L - 1; t += 256) {
+            const int64_t n = n0 + (int64_t)t;
+            float2 u = make_float2(0.0f, 0.0f);
+            if (n >= 0 && n < len) {
+                const int64_t D = a.drift0 + dinc * n;
+                const uint64_t mu = (uint64_t)D & ((1ull << 40) - 1);
+                const float frac = (float)(uint32_t)((mu >> 9) & 0xFFFFFFu) * 0x1p-24f;
+                const float* t0 = tab + (uint32_t)(mu >> 33) * WR_RS_TAPS;
+                const float2* x = raw + (rs_pos(n, D) - WR_RS_CENTER - lo);
+#pragma unroll
+                for (int q = 0; q < WR_RS_TAPS; q++) {
+                    const float c = t0[q] + frac * (t0[WR_RS_TAPS + q] - t0[q]);
+                    const float2 v = x[q];
+                    u = q == 0 ? make_float2(c * v.x, c * v.y) : make_float2(u.x + c * v.x, u.y + c * v.y);
+                }
+            }
+            xs[t] = u;
+        }
+    } else if constexpr (STAGE) {
         const int64_t s0 = gt - (int64_t)(L - 1);
         for (uint32_t i = tid; i < CH_TILE + L - 1; i += 256) {
             const int64_t g = s0 + (int64_t)i;
@@ -170,9 +223,18 @@ extern "C" hipError_t wr_launch_channel(hipStream_t st, const wr::ChanArgs* args
 {
     if (n_tiles == 0) return hipSuccess;
     const dim3 grid((unsigned)n_tiles), block(256);
-    if (args->n_taps > 1) hipLaunchKernelGGL(wr::channel_kernel<true>, grid, block, 0, st, *args);
-    else hipLaunchKernelGGL(wr::channel_kernel<false>, grid, block, 0, st, *args);
+    if (args->dinc) hipLaunchKernelGGL((wr::channel_kernel<true, true>), grid, block, 0, st, *args);
+    else if (args->n_taps > 1) hipLaunchKernelGGL((wr::channel_kernel<true, false>), grid, block, 0, st, *args);
+    else hipLaunchKernelGGL((wr::channel_kernel<false, false>), grid, block, 0, st, *args);
     return hipGetLastError();
 }
 
 extern "C" uint32_t wr_channel_tile_samples(void) { return CH_TILE; }
+
+extern "C" const float* wr_resample_table(uint32_t* n_phases, uint32_t* n_taps)
+{
+    static const float table[(WR_RS_PHASES + 1) * WR_RS_TAPS] = WR_RS_TABLE_INIT;
+    *n_phases = WR_RS_PHASES;
+    *n_taps = WR_RS_TAPS;
+    return table;
+}

@@ -386,7 +386,8 @@ class channel_model(grshim.sync_block):
     new chunk.  The row's ``sample0`` is its stream index and its ``phase0`` the phase carried from the previous call (a uint64
     in 2^-64 turns), so the output does not depend on how the stream is cut into calls; the outputs of the kept samples are
     dropped.  A setter takes effect at the next ``work()``; a new frequency keeps the phase continuous.
-    ``epsilon`` (the sample-rate offset) must be 1.0: the fractional resampler is not implemented."""
+    ``epsilon`` (the sample-rate offset) must be 1.0: the fractional resampler exists for rows (``WifiRx.channel(sro=...)``,
+    wifirx_channel_sro), not for this stream block, whose output rate would differ from its input rate."""
 
     MAX_TAPS = 64
 

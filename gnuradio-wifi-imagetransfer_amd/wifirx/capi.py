@@ -41,6 +41,7 @@ EXPORTS = [
     "wifirx_memcpy_h2d", "wifirx_memcpy_d2h", "wifirx_time_demod", "wifirx_poll_ex", "wifirx_demod_batch_v",
     "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft", "wifirx_tx_batch", "wifirx_channel",
     "wifirx_mac_batch", "wifirx_link_stats", "wifirx_tx_batch_rates", "wifirx_link_stats_by_rate",
+    "wifirx_channel_sro", "wifirx_resampler_table",
 ]
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
@@ -64,6 +65,34 @@ def phase_inc(cfo) -> int:
     a = abs(v)
     k = int(a) if a >= 2.0 ** 52 else int(np.floor(a + 0.5))      # llround: half away from zero (a + 0.5 is exact below 2^52)
     return (-k if v < 0 else k) & 0xFFFFFFFFFFFFFFFF
+
+
+SRO_MAX = 2.0 ** -8                 # the largest |sro| wifirx_channel_sro takes
+
+
+def drift_inc(sro) -> int:
+    """The int64 drift increment wifirx_channel_sro derives from `sro` = epsilon - 1 (taken as float32): llround(sro * 2^40),
+    in 2^-40 samples per sample (NUMERICS.md rule 18).  A caller that cuts a stream into calls advances its drift0 by
+    drift_inc(sro) * samples."""
+    v = float(np.float32(sro)) * 2.0 ** 40      # exact: a float32 times a power of two
+    a = abs(v)
+    k = int(a) if a >= 2.0 ** 52 else int(np.floor(a + 0.5))      # llround: half away from zero
+    return -k if v < 0 else k
+
+
+def locked_sro(cfo, bandwidth=20e6, frequency=5.89e9):
+    """sro of a sample clock locked to the carrier, for `cfo` rad/sample as wifirx_channel applies it (exp(+j cfo n)):
+    epsilon - 1 = -cfo * bw / (2 pi fc), the offset the receiver's frame_equalizer compensates (float32 array or scalar)"""
+    return (-np.asarray(cfo, dtype=np.float64) * bandwidth / (2 * np.pi * frequency)).astype(np.float32)
+
+
+def resampler_table() -> np.ndarray:
+    """wifirx_resampler_table: the rule-18 table as float32 [n_phases + 1, n_taps] (a copy; no handle, no device)"""
+    p, n_ph, n_t = C.POINTER(C.c_float)(), C.c_uint32(), C.c_uint32()
+    rc = _lib.wifirx_resampler_table(C.byref(p), C.byref(n_ph), C.byref(n_t))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_resampler_table")
+    return np.ctypeslib.as_array(p, shape=(n_ph.value + 1, n_t.value)).copy()
 
 
 def link_rates(c) -> dict:
@@ -153,6 +182,10 @@ _lib.wifirx_tx_batch_rates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_i
 _lib.wifirx_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                 C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_float, C.c_float,
                                 C.c_uint64, C.c_uint64]
+_lib.wifirx_channel_sro.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                    C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64,
+                                    C.c_float, C.c_float, C.c_uint64, C.c_uint64]
+_lib.wifirx_resampler_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                   C.c_uint64, C.c_void_p, C.c_uint32]
 _lib.wifirx_link_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.POINTER(Out), C.c_void_p, C.c_void_p,
@@ -499,10 +532,12 @@ class WifiRx:
         return np.ascontiguousarray(t), t.shape[0], t.shape[1]
 
     def channel_dev(self, in_ptr, out_ptr, samples_cap, n_rows, *, row_len=None, row_off=None, taps=(1.0,), cfo=None,
-                    phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, n_taps=None, n_tap_sets=1):
+                    phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, n_taps=None, n_tap_sets=1, sro=None, drift0=0):
         """wifirx_channel over device samples: rows of row_len, or row_off ([n_rows + 1] sample offsets).  taps: a 1-D set, a
         2-D [n_tap_sets, L] array, or an int device pointer (then n_taps and n_tap_sets say its shape).  cfo: rad/sample per
-        row (scalar or [n_rows]), None = 0.  phase0: uint64 phase in 2^-64 turns.  Asynchronous on the handle's stream."""
+        row (scalar or [n_rows]), None = 0.  phase0: uint64 phase in 2^-64 turns.  sro: epsilon - 1 per row (scalar or
+        [n_rows]; wifirx_channel_sro, never in place), None = no resampler; drift0: int64 drift of the rows' first output
+        sample in 2^-40 samples.  Asynchronous on the handle's stream."""
         if isinstance(taps, int):
             if n_taps is None:
                 raise ValueError("device taps need n_taps")
@@ -516,13 +551,21 @@ class WifiRx:
         ro = None if row_off is None else np.ascontiguousarray(row_off, dtype=np.uint64)
         if ro is not None and ro.size != int(n_rows) + 1:
             raise ValueError("row_off needs n_rows + 1 entries")
+        if sro is not None:
+            s = np.ascontiguousarray(np.broadcast_to(np.asarray(sro, dtype=np.float32), (int(n_rows),)))
+            self._check(_lib.wifirx_channel_sro(self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0),
+                                                int(n_rows), t_ptr, t_dev, L, n_sets, _np_ptr(c),
+                                                int(phase0) & 0xFFFFFFFFFFFFFFFF, _np_ptr(s), int(drift0), float(gain),
+                                                float(noise_voltage), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                int(sample0) & 0xFFFFFFFFFFFFFFFF))
+            return
         self._check(_lib.wifirx_channel(self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0),
                                         int(n_rows), t_ptr, t_dev, L, n_sets, _np_ptr(c), int(phase0) & 0xFFFFFFFFFFFFFFFF,
                                         float(gain), float(noise_voltage), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                         int(sample0) & 0xFFFFFFFFFFFFFFFF))
 
     def channel(self, x, *, row_off=None, taps=(1.0,), cfo=None, phase0=0, gain=1.0, noise_voltage=0.0, seed=0,
-                sample0=0):
+                sample0=0, sro=None, drift0=0):
         """channel_dev on host samples: x [n_rows, row_len] (fixed rows; 1-D = one row) or, with row_off, the 1-D buffer the
         offsets index.  Returns the output in x's shape; samples outside the rows are 0."""
         x = np.ascontiguousarray(x, dtype=np.complex64)
@@ -540,7 +583,8 @@ class WifiRx:
             d_in.upload(x)
             d_out.upload(np.zeros(n, np.complex64))
             self.channel_dev(d_in.ptr, d_out.ptr, n, n_rows, row_len=row_len, row_off=row_off, taps=taps, cfo=cfo,
-                             phase0=phase0, gain=gain, noise_voltage=noise_voltage, seed=seed, sample0=sample0)
+                             phase0=phase0, gain=gain, noise_voltage=noise_voltage, seed=seed, sample0=sample0, sro=sro,
+                             drift0=drift0)
             y = d_out.download(np.complex64, n)      # ordered behind the kernel on the handle's stream
         finally:
             d_in.free()

@@ -390,6 +390,36 @@ int  wifirx_channel(wifirx_handle* h, const float* in, float* out, uint64_t samp
                     const float* cfo, uint64_t phase0, float gain, float noise_voltage,
                     uint64_t seed, uint64_t sample0);
 
+/* wifirx_channel with channel_model's fourth argument, the sample-rate offset epsilon: a fractional resampler in front of the
+ * FIR (GNU Radio's order: resampler -> taps -> mixer -> noise), in the same single launch; arithmetic = NUMERICS.md rule 18.
+ * Output n of row r reads its input at the position n + D_r(n) / 2^40:
+ *     u[n]   = sum_{k=0}^{31} c_k(n) x[i + k - 15]         i = n + floor(D / 2^40), c = the table's taps for frac(D / 2^40)
+ *     D_r(n) = drift0 + dinc_r n                           dinc_r = llround((double)sro_r * 2^40), exact int64
+ * (x[m] = 0 outside the row), and wifirx_channel's chain then runs on u; the mixer and the noise count output samples.
+ *   sro       HOST [n_rows] epsilon - 1 per row (y[n] = x(n epsilon)), e.g. -20e-6f; |sro| <= 2^-8.  NULL = no resampler: the
+ *             call then IS wifirx_channel (the same kernel instances, drift0 is not looked at).  A sample clock locked to
+ *             the carrier, which the receiver's frame_equalizer assumes, is sro_r = -cfo_r * bw / (2 pi fc) for the cfo_r
+ *             rad/sample of this call (20 ppm at 5.89 GHz and 20 MS/s: cfo = +0.037, sro = -20e-6).
+ *   drift0    the drift of every row's first output sample, in 2^-40 samples: what phase0 is to the mixer.  A stream cut
+ *             into calls stays exact when each call passes on drift0 + dinc * (samples it advanced) -- apart from the
+ *             samples within the resampler's and the FIR's reach of the cut, which see zeros across it.
+ *   in, out   as wifirx_channel, but never in place, whatever n_taps: every overlap of the rows' samples is refused.
+ * All-zero sro with drift0 = 0 gives wifirx_channel's bytes on finite input (table rows 0 and 128 are unit impulses).
+ * Checked on the host before anything is queued, beside wifirx_channel's checks: WIFIRX_EINVAL for an sro that is not finite
+ * or above 2^-8 in magnitude, and for in == out; WIFIRX_ERANGE when |drift0| + |dinc| * (longest row) >= 2^62, |dinc| the
+ * largest of the call (so every D(n), and every input position, is an exact int64).  One kernel launch per call, after one
+ * upload of the host arrays (taps, cfo, row_off, the drift increments).  ORDER: as wifirx_channel. */
+int  wifirx_channel_sro(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
+                        const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
+                        const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
+                        const float* cfo, uint64_t phase0, const float* sro, int64_t drift0,
+                        float gain, float noise_voltage, uint64_t seed, uint64_t sample0);
+
+/* The resampler's table (NUMERICS.md rule 18; tools/gen_resample_table.py): *taps = (n_phases + 1) rows of n_taps float32,
+ * row p = the fractional delay p / n_phases, tap k weighing x[i + k - 15]; n_phases = 128, n_taps = 32.  Host memory owned by
+ * the library.  Needs no handle and no device; any argument may be NULL.  Returns WIFIRX_OK. */
+int  wifirx_resampler_table(const float** taps, uint32_t* n_phases, uint32_t* n_taps);
+
 /* ieee802_11.mac (gnu_radio/IRS_user.py:192,204-205; IRS_tranceiver.py:271,313-314) for a batch: PSDU i, at
  * psdu + i * psdu_stride, is the 24 + payload_len[i] + 4 bytes
  *     08 00 | 00 00 | addr1 = dst | addr2 = src | addr3 = bss | ((seq0 + i) & 0xFFF) << 4, little endian | payload i | FCS

@@ -3,7 +3,11 @@ handle's stream after a warm-up: one tap and the 8-tap sets of tests/golden/sv_t
 process, against a device-to-device hipMemcpyAsync of the same bytes and wifirx_synth_slots on the same geometry (which only
 writes).  Prints one JSON line, writes it to --out when given.
 
-    python tools/channel_bench.py [--iters 3] [--out profiles/channel_config2.json]"""
+--sro adds wifirx_channel_sro on the same rows with the sample clock locked to the carrier, sro = -cfo bw / (2 pi fc) per
+row (NUMERICS.md rule 18), one tap and 8 taps, and a hipMemsetAsync of the output bytes, beside the calls without sro.
+
+    python tools/channel_bench.py [--iters 3] [--out profiles/channel_config2.json]
+    python tools/channel_bench.py --sro [--out profiles/channel_sro_config2.json]"""
 import argparse
 import ctypes as C
 import json
@@ -25,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--rows", type=int, default=N)
+    ap.add_argument("--sro", action="store_true", help="also time wifirx_channel_sro (locked sample clock) and a memset")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     n = a.rows
@@ -34,6 +39,7 @@ def main():
     ev0, ev1 = C.c_void_p(), C.c_void_p()
     assert hip.hipEventCreate(C.byref(ev0)) == 0 and hip.hipEventCreate(C.byref(ev1)) == 0
     hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
     hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
     hip.hipEventSynchronize.argtypes = [C.c_void_p]
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
@@ -74,6 +80,15 @@ def main():
         "memcpy_d2d": lambda: hip.hipMemcpyAsync(d_out.ptr, d_in.ptr, nbytes, 3, st),
         "synth_slots": lambda: rx.synth_slots(tmpl, d_out.ptr, ROW, n, 160, 20.0, 0.037, 7),
     }
+    if a.sro:
+        sro = capi.locked_sro(cfo)
+        runs.update({
+            "channel_sro_L1": lambda: rx.channel_dev(d_in.ptr, d_out.ptr, n * ROW, n, row_len=ROW, taps=(1.0,), cfo=cfo, sro=sro,
+                                                     gain=gain, noise_voltage=1.0, seed=7),
+            "channel_sro_L8": lambda: rx.channel_dev(d_in.ptr, d_out.ptr, n * ROW, n, row_len=ROW, taps=taps8, cfo=cfo, sro=sro,
+                                                     gain=gain, noise_voltage=1.0, seed=7),
+            "memset": lambda: hip.hipMemsetAsync(d_out.ptr, 0, nbytes, st),
+        })
     rx.synth_slots(tmpl, d_in.ptr, ROW, n, 160, 20.0, 0.037, 3)        # the input: config 2's slots
     for fn in runs.values():                                            # warm-up of each
         fn()
@@ -93,6 +108,14 @@ def main():
                aim_ratio_L8=1.25,
                note="channel_* cover the whole call on the handle's stream: the upload of the host arrays (4 MB of CFO; "
                     "64 KB of taps for L8), then the kernel; kernel_* pass device taps and no CFO array (no upload)")
+    if a.sro:
+        res["sro"] = dict(what="wifirx_channel_sro, sro = -cfo * 20e6 / (2 pi 5.89e9) per row, drift0 = 0; the whole call "
+                               "(upload of 4 MB of CFO and 8 MB of drift increments, then the kernel)",
+                          ms_median={k: med[k] for k in ("channel_sro_L1", "channel_sro_L8", "memset")},
+                          ratio_to_channel_without_sro={"L1": med["channel_sro_L1"] / med["channel_L1"],
+                                                        "L8": med["channel_sro_L8"] / med["channel_L8"]},
+                          Gsamples_per_s={k: n * ROW / med[k] / 1e6 for k in ("channel_sro_L1", "channel_sro_L8")},
+                          memset_GBps_written=nbytes / med["memset"] / 1e6)
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:

@@ -15,7 +15,13 @@ and wifirx_demod_batch_v take them), scored by wifirx_link_stats_by_rate.  Per p
 coded BER, and the goodput = delivered payload bits per sample of air time.  max_sym is 99 for this mix and the soft decoder
 needs 6 LLRs per carrier, so the LLR rows are bf16 (WIFIRX_LLR_BF16, 57 kB per frame); the default is 131 072 frames.
 
-    python tools/loopback_per.py --rates [--frames 131072] [--host-stats] [--out profiles/loopback_rates.json]"""
+    python tools/loopback_per.py --rates [--frames 131072] [--host-stats] [--out profiles/loopback_rates.json]
+
+--locked-clock (both modes) locks the channel's sample clock to its carrier, as a real radio's is and as the receiver's
+frame_equalizer assumes: wifirx_channel_sro with sro = -cfo bw / (2 pi fc) per row (NUMERICS.md rule 18) in place of
+wifirx_channel.  Everything else, the seeds included, stays, so a sweep with the switch stands beside one without.
+
+    python tools/loopback_per.py --locked-clock [--out profiles/loopback_per_config3_locked.json]"""
 import argparse
 import json
 import math
@@ -66,6 +72,7 @@ def main():
     ap.add_argument("--snr", type=float, nargs="+", default=[5, 10, 15, 20, 25, 30])
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--host-stats", action="store_true", help="also keep the books in NumPy and assert they agree")
+    ap.add_argument("--locked-clock", action="store_true", help="sample clock locked to the carrier: sro = -cfo bw / (2 pi fc)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.rates:
@@ -96,7 +103,8 @@ def main():
         t0 = time.perf_counter()
         cfo = np.random.default_rng(int(1000 * snr) + a.seed).uniform(-CFO_20PPM, CFO_20PPM, n).astype(np.float32)
         rx.channel_dev(rows.ptr, iq.ptr, n * SLOT, n, row_len=SLOT, taps=taps, cfo=cfo, gain=math.sqrt(10 ** (snr / 10)),
-                       noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32))
+                       noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32),
+                       sro=capi.locked_sro(cfo) if a.locked_clock else None)
         rx.demod_batch_dev(iq.ptr, SLOT, n, dev)
         rx.decode_batch_dev(n, dev)
         hard = rx.link_stats(n, dev, ref)
@@ -117,7 +125,8 @@ def main():
     rx.free_out(dev)
     rows.free(); iq.free(); rx.close()
     res = {"workload": "loop-back on the device, config 3: %d distinct frames per point (wifirx_mac_batch, Philox payloads), 64-QAM 3/4, PSDU 294 B, rows of 1472, "
-                       "lead 160, sv_taps.npy sets cycling, CFO uniform in +-20 ppm, LS; hard and soft decode_mac" % n,
+                       "lead 160, sv_taps.npy sets cycling, CFO uniform in +-20 ppm, LS; hard and soft decode_mac" % n
+                       + ("; sample clock locked to the carrier (wifirx_channel_sro, sro = -cfo bw / (2 pi fc))" if a.locked_clock else ""),
            "stats": "wifirx_link_stats on the device" + (", checked against the NumPy bookkeeping" if a.host_stats else ""),
            "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
@@ -183,7 +192,8 @@ def rates_main(a):
         t0 = time.perf_counter()
         cfo = np.random.default_rng(int(1000 * snr) + a.seed).uniform(-CFO_20PPM, CFO_20PPM, n).astype(np.float32)
         rx.channel_dev(rows.ptr, iq.ptr, total, n, row_off=row_off, taps=taps, cfo=cfo, gain=math.sqrt(10 ** (snr / 10)),
-                       noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32))
+                       noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32),
+                       sro=capi.locked_sro(cfo) if a.locked_clock else None)
         rx.demod_batch_var_dev(iq.ptr, row_off, dev)
         both = []
         for soft in (False, True):
@@ -234,7 +244,8 @@ def rates_main(a):
                       % (q["snr_db"], key, r7[key], side[-1]["here_se"], o[key], side[-1]["config3_se"]), file=sys.stderr)
     res = {"workload": "loop-back on the device, the eight encodings cycling: %d distinct frames per point (%d per rate; wifirx_mac_batch, "
                        "Philox payloads), PSDU 294 B, row_off rows of lead 160 + frame + %d rounded up to even, sv_taps.npy sets cycling, "
-                       "CFO uniform in +-20 ppm, LS; hard and soft decode_mac" % (n, n // 8, tail),
+                       "CFO uniform in +-20 ppm, LS; hard and soft decode_mac" % (n, n // 8, tail)
+                       + ("; sample clock locked to the carrier (wifirx_channel_sro, sro = -cfo bw / (2 pi fc))" if a.locked_clock else ""),
            "llr": "bf16 (WIFIRX_LLR_BF16), 6 per carrier, max_sym %d: %d bytes per frame" % (max_sym, max_sym * 48 * 6 * 2),
            "stats": "wifirx_link_stats_by_rate on the device" + (", checked against the NumPy bookkeeping" if a.host_stats else ""),
            "goodput": "frames_psdu_ok * %d payload bits / (frames_ref * frame_samples)" % payload_bits,
