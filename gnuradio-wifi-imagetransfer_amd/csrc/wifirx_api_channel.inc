@@ -1,11 +1,13 @@
 // channel entry points: channels.channel_model over rows of device samples (wr_channel.hip)
 
-// wifirx_channel (sro == NULL: drift0 is not looked at) and wifirx_channel_sro
+// wifirx_channel (sro == NULL: drift0 is not looked at), wifirx_channel_sro and wifirx_channel_fading (doppler == NULL:
+// k_factor, fade_seed and time0 are not looked at)
 static int channel_call(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
                         const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
                         const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
                         const float* cfo, uint64_t phase0, const float* sro, int64_t drift0, float gain, float noise_voltage,
-                        uint64_t seed, uint64_t sample0)
+                        uint64_t seed, uint64_t sample0,
+                        const float* doppler = nullptr, float k_factor = 0.0f, uint64_t fade_seed = 0, uint64_t time0 = 0)
 {
     if (!h) return WIFIRX_EINVAL;
     if (!in || !out || !taps) return fail(h, WIFIRX_EINVAL, "in, out and taps are required");
@@ -23,6 +25,15 @@ static int channel_call(wifirx_handle* h, const float* in, float* out, uint64_t 
         for (uint32_t r = 0; r < n_rows; r++)
             if (!(std::fabs(sro[r]) <= 0x1p-8f)) return fail(h, WIFIRX_EINVAL, "sro must be finite and at most 2^-8 in magnitude");
     if (sro && in == out) return fail(h, WIFIRX_EINVAL, "in place is not possible with a sample-rate offset");
+    if (doppler) {
+        // rule 19: the interpolation of the gains between grid points is good to sqrt(8) (2 pi fd 32)^2 / 8, 1.4e-2 at 2^-10
+        for (uint32_t r = 0; r < n_rows; r++)
+            if (!(doppler[r] >= 0.0f && doppler[r] <= 0x1p-10f))
+                return fail(h, WIFIRX_EINVAL, "doppler must be finite, not negative and at most 2^-10 cycles per sample");
+        if (!(std::isfinite(k_factor) && k_factor >= 0.0f)) return fail(h, WIFIRX_EINVAL, "k_factor must be finite and not negative");
+        if (n_taps > wr_channel_fade_taps()) return fail(h, WIFIRX_EINVAL, "n_taps must be 1..16 with fading");
+        if (in == out) return fail(h, WIFIRX_EINVAL, "in place is not possible with fading");
+    }
     if (row_off)
         for (uint32_t r = 0; r < n_rows; r++)
             if (row_off[r + 1] < row_off[r]) return fail(h, WIFIRX_EINVAL, "row_off must not decrease");
@@ -75,13 +86,15 @@ static int channel_call(wifirx_handle* h, const float* in, float* out, uint64_t 
     stream_worker_wait_idle(h);
     HIP_TRY(h, hipSetDevice(h->device));
 
-    // one upload of what the host holds: taps | cfo | row offsets | tile bases (row_off form) | drift increments (sro)
+    // one upload of what the host holds: taps | cfo | row offsets | tile bases (row_off form) | drift increments (sro) |
+    // Doppler (fading)
     const size_t taps_bytes = 8ull * n_taps * n_tap_sets;
     const size_t o_taps = 0, o_cfo = o_taps + (taps_on_device ? 0 : taps_bytes);
     const size_t o_row = o_cfo + (cfo ? (4ull * n_rows + 7) & ~7ull : 0);
     const size_t o_tile = o_row + (row_off ? 8ull * (n_rows + 1) : 0);
     const size_t o_dinc = o_tile + (row_off ? 8ull * (n_rows + 1) : 0);
-    const size_t meta_bytes = o_dinc + (sro ? 8ull * n_rows : 0);
+    const size_t o_dop = o_dinc + (sro ? 8ull * n_rows : 0);
+    const size_t meta_bytes = o_dop + (doppler ? 4ull * n_rows : 0);
     uint8_t* dm = nullptr;
     if (meta_bytes) {
         std::vector<uint8_t> meta(meta_bytes);      // (the phase increments are derived on the device: wr_channel.hip)
@@ -92,6 +105,7 @@ static int channel_call(wifirx_handle* h, const float* in, float* out, uint64_t 
             std::memcpy(meta.data() + o_tile, tile_base.data(), 8ull * (n_rows + 1));
         }
         if (sro) std::memcpy(meta.data() + o_dinc, dinc.data(), 8ull * n_rows);
+        if (doppler) std::memcpy(meta.data() + o_dop, doppler, 4ull * n_rows);
         int rc = h->stage.ch_meta.reserve(h, meta_bytes);
         if (rc) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->stage.ch_meta.p, meta.data(), meta_bytes, hipMemcpyHostToDevice, h->stream));
@@ -117,6 +131,15 @@ static int channel_call(wifirx_handle* h, const float* in, float* out, uint64_t 
     a.noise = noise_voltage;
     a.dinc = sro ? reinterpret_cast<const int64_t*>(dm + o_dinc) : nullptr;
     a.drift0 = sro ? drift0 : 0;
+    if (doppler) {
+        a.doppler = reinterpret_cast<const float*>(dm + o_dop);
+        a.fade_seed = fade_seed;
+        a.time0 = time0;
+        if (k_factor > 0.0f) {                      // formed in double; k_factor = 0: neither is applied (a_los = 0 says so)
+            a.a_los = (float)std::sqrt((double)k_factor / ((double)k_factor + 1.0));
+            a.a_nlos = (float)std::sqrt(1.0 / ((double)k_factor + 1.0));
+        }
+    }
     HIP_TRY(h, wr_launch_channel(h->stream, &a, n_tiles));
     return WIFIRX_OK;
 }
@@ -139,6 +162,17 @@ extern "C" int wifirx_channel_sro(wifirx_handle* h, const float* in, float* out,
 {
     return channel_call(h, in, out, samples_cap, row_off, row_len, n_rows, taps, taps_on_device, n_taps, n_tap_sets, cfo, phase0,
                         sro, drift0, gain, noise_voltage, seed, sample0);
+}
+
+extern "C" int wifirx_channel_fading(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
+                                     const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
+                                     const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
+                                     const float* cfo, uint64_t phase0, const float* sro, int64_t drift0,
+                                     float gain, float noise_voltage, uint64_t seed, uint64_t sample0,
+                                     const float* doppler, float k_factor, uint64_t fade_seed, uint64_t time0)
+{
+    return channel_call(h, in, out, samples_cap, row_off, row_len, n_rows, taps, taps_on_device, n_taps, n_tap_sets, cfo, phase0,
+                        sro, drift0, gain, noise_voltage, seed, sample0, doppler, k_factor, fade_seed, time0);
 }
 
 extern "C" int wifirx_resampler_table(const float** taps, uint32_t* n_phases, uint32_t* n_taps)

@@ -22,6 +22,10 @@ struct ChanArgs {
     float           gain, noise;
     const int64_t*  dinc;         // [n_rows] drift per sample in 2^-40 samples (NUMERICS.md rule 18), or null: no resampler
     int64_t         drift0;       // drift of every row's first output sample, 2^-40 samples
+    const float*    doppler;      // [n_rows] Doppler in cycles per sample (NUMERICS.md rule 19), or null: no fading
+    uint64_t        fade_seed;    // key of the fader's draws
+    uint64_t        time0;        // stream time of every row's first output sample: the gains' grid lies on time0 + n
+    float           a_los, a_nlos;      // sqrt(K / (K + 1)), sqrt(1 / (K + 1)); a_los = 0: k_factor = 0, neither is applied
 };
 
 }  // namespace wr
@@ -29,5 +33,6 @@ struct ChanArgs {
 extern "C" {
 hipError_t wr_launch_channel(hipStream_t st, const wr::ChanArgs* args, uint64_t n_tiles);
 uint32_t   wr_channel_tile_samples(void);
+uint32_t   wr_channel_fade_taps(void);             // the most taps with fading
 const float* wr_resample_table(uint32_t* n_phases, uint32_t* n_taps);      // host copy of the rule-18 table, [n_phases + 1][n_taps]
 }

@@ -13,6 +13,11 @@
 // resampler in front of the FIR inside the same launch: the workgroup stages the raw input window of its tile (the tile,
 // the FIR halo, the resampler's 31 neighbours and the drift spread over the tile) and the table in LDS, forms the resampled
 // samples u of the tile and its FIR halo into the array the FIR reads, and goes on as the other instances do.
+//
+// With Doppler fading (wifirx_channel_fading, NUMERICS.md rule 19) two more instances, with and without the resampler, make
+// the FIR's taps functions of time: the workgroup derives its row's oscillators (8 per tap and the line-of-sight one: a
+// Philox draw, one sp_sincos and one double product each), fills an LDS array with the gains of every tap on the 32-sample
+// grid of the stream time that covers the tile, and the FIR loop interpolates between two grid points per sample and tap.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,6 +30,11 @@ namespace wr {
 
 #define CH_TILE     2048     // samples per workgroup: four pairs per lane of a 256-lane group
 #define CH_MAX_TAPS 64
+#define CH_FADE_TAPS 16      // the most taps with fading: the grid gains of 64 would leave one workgroup per CU
+#define CH_FADE_SINES 8      // sinusoids per tap
+#define CH_FADE_STEP 32      // samples between two grid points of the gains: a power of two
+#define CH_FADE_GRID (CH_TILE / CH_FADE_STEP + 2)      // grid points a tile touches: it may start anywhere between two
+#define CH_FADE_LOS  (CH_FADE_TAPS * CH_FADE_SINES)    // counter index (and slot) of tap 0's line-of-sight oscillator
 // raw input window of a resampling tile: the CH_TILE + CH_MAX_TAPS - 1 outputs u it forms read input positions that spread
 // over at most that many samples plus ceil((CH_TILE + CH_MAX_TAPS - 2) / 256) = 9 of drift (|sro| <= 2^-8), plus the
 // resampler's WR_RS_TAPS - 1 neighbours
@@ -76,15 +86,33 @@ __device__ __forceinline__ uint4 ch_draw(uint64_t pair, uint32_t row, uint2 key)
     return philox4x32_10(make_uint4((uint32_t)pair, row, (uint32_t)(pair >> 32), 0u), key);
 }
 
+// rule 19: oscillator with start phase phi and increment inc (2^-64 turns) at stream time t: (cos, sin) of P = phi + inc t
+__device__ __forceinline__ float2 fade_osc(uint64_t phi, uint64_t inc, uint64_t t)
+{
+    float sn, cs;
+    sp_sincos((float)(int32_t)(uint32_t)((phi + inc * t) >> 32) * CH_PHASE_SCALE, sn, cs);
+    return make_float2(cs, sn);
+}
+
+// rule 19: the gain between the grid points G0 (at or before the sample) and G1 (32 samples later), w = (t & 31) / 32
+__device__ __forceinline__ float2 fade_lerp(float2 G0, float2 G1, float w)
+{
+    return make_float2(G0.x + w * (G1.x - G0.x), G0.y + w * (G1.y - G0.y));
+}
+
 // rule 18: output n of a row whose drift is D = drift0 + dinc n (2^-40 samples) reads the input around i = n + (D >> 40)
 __device__ __forceinline__ int64_t rs_pos(int64_t n, int64_t D) { return n + (D >> 40); }
 
-// STAGE: the FIR reads its input from LDS (n_taps > 1, or SRO); SRO: that input is the resampled row (rule 18), any n_taps
-template <bool STAGE, bool SRO>
+// STAGE: the FIR reads its input from LDS (n_taps > 1, SRO or FADE); SRO: that input is the resampled row (rule 18), any
+// n_taps; FADE: the taps are multiplied by gains that vary with the stream time (rule 19), n_taps <= CH_FADE_TAPS
+template <bool STAGE, bool SRO, bool FADE>
 __global__ __launch_bounds__(256)
 void channel_kernel(const ChanArgs a)
 {
     static_assert(STAGE || !SRO, "the resampler writes the array the FIR reads");
+    static_assert(STAGE || !FADE, "the fading FIR reads its input from LDS");
+    __shared__ uint64_t osc_phi[FADE ? CH_FADE_LOS + 1 : 1], osc_inc[FADE ? CH_FADE_LOS + 1 : 1];
+    __shared__ float2 gg[FADE ? CH_FADE_GRID * CH_FADE_TAPS : 1];      // [grid point][tap], n_taps apart
     __shared__ float2 xs[STAGE ? CH_TILE + CH_MAX_TAPS - 1 : 1];
     __shared__ float2 tp[CH_MAX_TAPS];
     __shared__ float2 raw[SRO ? CH_RAW : 1];
@@ -113,6 +141,18 @@ void channel_kernel(const ChanArgs a)
     const uint32_t L = a.n_taps;
 
     if (tid < L) tp[tid] = a.taps[(size_t)(r % a.n_tap_sets) * L + tid];
+    uint64_t q0 = 0;                                   // FADE: stream time of the tile's first grid point
+    if constexpr (FADE) {
+        q0 = (a.time0 + (uint64_t)(gt - rs)) & ~(uint64_t)(CH_FADE_STEP - 1);
+        // the row's oscillators: slot 8 l + k for sinusoid k of tap l, slot CH_FADE_LOS for the line of sight
+        if (tid < CH_FADE_SINES * L || tid == CH_FADE_LOS) {
+            const uint4 d = philox4x32_10(make_uint4(tid, r, 0u, 1u), make_uint2((uint32_t)a.fade_seed, (uint32_t)(a.fade_seed >> 32)));
+            float sn, cs;
+            sp_sincos((float)(int32_t)d.x * CH_PHASE_SCALE, sn, cs);
+            osc_inc[tid] = (uint64_t)(int64_t)__builtin_round((double)a.doppler[r] * (double)cs * 0x1p64);      // |.| <= 2^54
+            osc_phi[tid] = ((uint64_t)d.y << 32) | d.z;
+        }
+    }
     if constexpr (SRO) {
         const int64_t len = re - rs;
         const int64_t dinc = a.dinc[r];
@@ -154,6 +194,24 @@ void channel_kernel(const ChanArgs a)
             xs[i] = (g >= rs && g < re) ? a.in[g] : make_float2(0.0f, 0.0f);
         }
     }
+    if constexpr (FADE) {
+        __syncthreads();                               // the oscillators
+        const bool los = a.a_los != 0.0f;              // k_factor > 0
+        for (uint32_t e = tid; e < CH_FADE_GRID * L; e += 256) {
+            const uint32_t i = e / L, l = e - i * L;
+            const uint64_t t = q0 + (uint64_t)i * CH_FADE_STEP;
+            float2 G = fade_osc(osc_phi[CH_FADE_SINES * l], osc_inc[CH_FADE_SINES * l], t);
+#pragma unroll
+            for (uint32_t k = 1; k < CH_FADE_SINES; k++)
+                G = ch_add(G, fade_osc(osc_phi[CH_FADE_SINES * l + k], osc_inc[CH_FADE_SINES * l + k], t));
+            G = make_float2(0.35355339f * G.x, 0.35355339f * G.y);
+            if (los && l == 0) {
+                const float2 o = fade_osc(osc_phi[CH_FADE_LOS], osc_inc[CH_FADE_LOS], t);
+                G = make_float2(a.a_los * o.x + a.a_nlos * G.x, a.a_los * o.y + a.a_nlos * G.y);
+            }
+            gg[e] = G;
+        }
+    }
     __syncthreads();
 
     const uint64_t inc = a.cfo ? ch_phase_inc(a.cfo[r]) : 0;
@@ -169,7 +227,25 @@ void channel_kernel(const ChanArgs a)
 
         // FIR, ascending k from the k = 0 product
         float2 s0, s1;
-        if constexpr (STAGE) {
+        if constexpr (FADE) {
+            // the gains of both samples at their own output times t and t + 1, for every tap
+            const uint64_t t0 = a.time0 + (uint64_t)(g - rs), t1 = t0 + 1;
+            const float2* g0 = gg + (uint32_t)((t0 - q0) / CH_FADE_STEP) * L;
+            const float2* g1 = gg + (uint32_t)((t1 - q0) / CH_FADE_STEP) * L;
+            const float w0 = (float)(uint32_t)(t0 & (CH_FADE_STEP - 1)) * (1.0f / CH_FADE_STEP);
+            const float w1 = (float)(uint32_t)(t1 & (CH_FADE_STEP - 1)) * (1.0f / CH_FADE_STEP);
+            const int32_t b = j + (int32_t)L - 1;                  // xs index of the input at g
+            float2 prev = xs[b + 1];
+            float2 cur = xs[b];
+            s0 = ch_mul(ch_mul(fade_lerp(g0[0], g0[L], w0), tp[0]), cur);
+            s1 = ch_mul(ch_mul(fade_lerp(g1[0], g1[L], w1), tp[0]), prev);
+            for (uint32_t q = 1; q < L; q++) {
+                prev = cur;
+                cur = xs[b - (int32_t)q];
+                s0 = ch_add(s0, ch_mul(ch_mul(fade_lerp(g0[q], g0[L + q], w0), tp[q]), cur));
+                s1 = ch_add(s1, ch_mul(ch_mul(fade_lerp(g1[q], g1[L + q], w1), tp[q]), prev));
+            }
+        } else if constexpr (STAGE) {
             const int32_t b = j + (int32_t)L - 1;                  // xs index of the input at g
             float2 prev = xs[b + 1];
             float2 cur = xs[b];
@@ -223,13 +299,17 @@ extern "C" hipError_t wr_launch_channel(hipStream_t st, const wr::ChanArgs* args
 {
     if (n_tiles == 0) return hipSuccess;
     const dim3 grid((unsigned)n_tiles), block(256);
-    if (args->dinc) hipLaunchKernelGGL((wr::channel_kernel<true, true>), grid, block, 0, st, *args);
-    else if (args->n_taps > 1) hipLaunchKernelGGL((wr::channel_kernel<true, false>), grid, block, 0, st, *args);
-    else hipLaunchKernelGGL((wr::channel_kernel<false, false>), grid, block, 0, st, *args);
+    if (args->doppler && args->n_taps > CH_FADE_TAPS) return hipErrorInvalidValue;      // (the entry point refuses it first)
+    if (args->doppler && args->dinc) hipLaunchKernelGGL((wr::channel_kernel<true, true, true>), grid, block, 0, st, *args);
+    else if (args->doppler) hipLaunchKernelGGL((wr::channel_kernel<true, false, true>), grid, block, 0, st, *args);
+    else if (args->dinc) hipLaunchKernelGGL((wr::channel_kernel<true, true, false>), grid, block, 0, st, *args);
+    else if (args->n_taps > 1) hipLaunchKernelGGL((wr::channel_kernel<true, false, false>), grid, block, 0, st, *args);
+    else hipLaunchKernelGGL((wr::channel_kernel<false, false, false>), grid, block, 0, st, *args);
     return hipGetLastError();
 }
 
 extern "C" uint32_t wr_channel_tile_samples(void) { return CH_TILE; }
+extern "C" uint32_t wr_channel_fade_taps(void) { return CH_FADE_TAPS; }
 
 extern "C" const float* wr_resample_table(uint32_t* n_phases, uint32_t* n_taps)
 {

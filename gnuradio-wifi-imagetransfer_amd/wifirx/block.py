@@ -387,17 +387,27 @@ class channel_model(grshim.sync_block):
     in 2^-64 turns), so the output does not depend on how the stream is cut into calls; the outputs of the kept samples are
     dropped.  A setter takes effect at the next ``work()``; a new frequency keeps the phase continuous.
     ``epsilon`` (the sample-rate offset) must be 1.0: the fractional resampler exists for rows (``WifiRx.channel(sro=...)``,
-    wifirx_channel_sro), not for this stream block, whose output rate would differ from its input rate."""
+    wifirx_channel_sro), not for this stream block, whose output rate would differ from its input rate.
+
+    ``doppler`` (cycles per sample, 0 .. 2^-10; None = static taps, the default) turns on the Doppler fader of NUMERICS.md
+    rule 19 (wifirx_channel_fading): every tap is multiplied by a time-varying gain of mean power 1, Rician on tap 0 with
+    ``k_factor`` > 0, drawn from ``fade_seed``; at most 16 taps then.  The gains are functions of the stream index (the call's
+    ``time0``), carried across ``work()`` calls like the phase, so the output does not depend on the cut here either.
+    ``doppler=0`` is not "off": it is one static random gain per tap."""
 
     MAX_TAPS = 64
 
     def __init__(self, noise_voltage=1.0, frequency_offset=0.0, epsilon=1.0, taps=(1.0,), noise_seed=0, block_tags=False,
-                 device=0):
+                 device=0, doppler=None, k_factor=0.0, fade_seed=0):
         grshim.sync_block.__init__(self, name="channel_model", in_sig=[np.complex64], out_sig=[np.complex64])
+        self._doppler = None
+        self.set_k_factor(k_factor)
+        self.fade_seed = int(fade_seed) & 0xFFFFFFFFFFFFFFFF
         self.set_timing_offset(epsilon)
         self.set_noise_voltage(noise_voltage)
         self.set_frequency_offset(frequency_offset)
         self.set_taps(taps)
+        self.set_doppler(doppler)
         self.noise_seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
         self.block_tags = bool(block_tags)          # tags are not propagated by the shim; accepted for the signature
         self._rx = capi.WifiRx(max_sym=1, device=device)         # the handle's receive side stays unused
@@ -428,10 +438,35 @@ class channel_model(grshim.sync_block):
         t = np.ascontiguousarray(np.asarray(taps, dtype=np.complex64).reshape(-1))
         if not 1 <= t.size <= self.MAX_TAPS:
             raise ValueError("taps must hold 1..%d values" % self.MAX_TAPS)
+        if self._doppler is not None and t.size > capi.FADE_MAX_TAPS:
+            raise ValueError("taps must hold 1..%d values with fading" % capi.FADE_MAX_TAPS)
         self._taps = t
 
     def taps(self):
         return self._taps.copy()
+
+    def set_doppler(self, doppler):
+        """maximum Doppler shift in cycles per sample, or None for static taps"""
+        if doppler is not None:
+            d = float(np.float32(doppler))
+            if not 0.0 <= d <= capi.DOPPLER_MAX:
+                raise ValueError("doppler must be 0 .. 2^-10 cycles per sample")
+            if self._taps.size > capi.FADE_MAX_TAPS:
+                raise ValueError("fading takes at most %d taps" % capi.FADE_MAX_TAPS)
+            doppler = d
+        self._doppler = doppler
+
+    def doppler(self):
+        return self._doppler
+
+    def set_k_factor(self, k_factor):
+        k = float(k_factor)
+        if not (math.isfinite(k) and k >= 0.0):
+            raise ValueError("k_factor must be finite and not negative")
+        self._k_factor = k
+
+    def k_factor(self):
+        return self._k_factor
 
     def set_timing_offset(self, epsilon):
         if float(epsilon) != 1.0:
@@ -455,8 +490,11 @@ class channel_model(grshim.sync_block):
         cfo = np.float32(2.0 * math.pi * self._frequency_offset)
         inc = capi.phase_inc(cfo)
         m64 = 0xFFFFFFFFFFFFFFFF
+        fade = {}                                                # without Doppler the call is the one it was
+        if self._doppler is not None:
+            fade = dict(doppler=self._doppler, k_factor=self._k_factor, fade_seed=self.fade_seed, time0=self._pos - h)
         y = self._rx.channel(row, taps=self._taps, cfo=cfo, phase0=(self._phase - inc * h) & m64, gain=1.0,
-                             noise_voltage=self._noise_voltage, seed=self.noise_seed, sample0=self._pos - h)
+                             noise_voltage=self._noise_voltage, seed=self.noise_seed, sample0=self._pos - h, **fade)
         out[:n] = y[h:]
         keep = self.MAX_TAPS - 1
         self._hist = np.concatenate([self._hist, x])[-keep:] if n < keep else x[n - keep:].copy()

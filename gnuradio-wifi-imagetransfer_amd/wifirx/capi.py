@@ -41,7 +41,7 @@ EXPORTS = [
     "wifirx_memcpy_h2d", "wifirx_memcpy_d2h", "wifirx_time_demod", "wifirx_poll_ex", "wifirx_demod_batch_v",
     "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft", "wifirx_tx_batch", "wifirx_channel",
     "wifirx_mac_batch", "wifirx_link_stats", "wifirx_tx_batch_rates", "wifirx_link_stats_by_rate",
-    "wifirx_channel_sro", "wifirx_resampler_table",
+    "wifirx_channel_sro", "wifirx_resampler_table", "wifirx_channel_fading",
 ]
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
@@ -84,6 +84,10 @@ def locked_sro(cfo, bandwidth=20e6, frequency=5.89e9):
     """sro of a sample clock locked to the carrier, for `cfo` rad/sample as wifirx_channel applies it (exp(+j cfo n)):
     epsilon - 1 = -cfo * bw / (2 pi fc), the offset the receiver's frame_equalizer compensates (float32 array or scalar)"""
     return (-np.asarray(cfo, dtype=np.float64) * bandwidth / (2 * np.pi * frequency)).astype(np.float32)
+
+
+DOPPLER_MAX = 2.0 ** -10            # the largest doppler (cycles per sample) wifirx_channel_fading takes
+FADE_MAX_TAPS = 16                  # the most taps with fading
 
 
 def resampler_table() -> np.ndarray:
@@ -185,6 +189,7 @@ _lib.wifirx_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, 
 _lib.wifirx_channel_sro.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                     C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64,
                                     C.c_float, C.c_float, C.c_uint64, C.c_uint64]
+_lib.wifirx_channel_fading.argtypes = _lib.wifirx_channel_sro.argtypes + [C.c_void_p, C.c_float, C.c_uint64, C.c_uint64]
 _lib.wifirx_resampler_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                   C.c_uint64, C.c_void_p, C.c_uint32]
@@ -532,12 +537,16 @@ class WifiRx:
         return np.ascontiguousarray(t), t.shape[0], t.shape[1]
 
     def channel_dev(self, in_ptr, out_ptr, samples_cap, n_rows, *, row_len=None, row_off=None, taps=(1.0,), cfo=None,
-                    phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, n_taps=None, n_tap_sets=1, sro=None, drift0=0):
+                    phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, n_taps=None, n_tap_sets=1, sro=None, drift0=0,
+                    doppler=None, k_factor=0.0, fade_seed=0, time0=0):
         """wifirx_channel over device samples: rows of row_len, or row_off ([n_rows + 1] sample offsets).  taps: a 1-D set, a
         2-D [n_tap_sets, L] array, or an int device pointer (then n_taps and n_tap_sets say its shape).  cfo: rad/sample per
         row (scalar or [n_rows]), None = 0.  phase0: uint64 phase in 2^-64 turns.  sro: epsilon - 1 per row (scalar or
         [n_rows]; wifirx_channel_sro, never in place), None = no resampler; drift0: int64 drift of the rows' first output
-        sample in 2^-40 samples.  Asynchronous on the handle's stream."""
+        sample in 2^-40 samples.  doppler: maximum Doppler shift per row in cycles per sample (scalar or [n_rows], 0 ..
+        2^-10; wifirx_channel_fading, NUMERICS.md rule 19: never in place, at most 16 taps), None = static taps; 0 is a
+        static random gain per row and tap.  k_factor: Rician K of tap 0 (0 = Rayleigh); fade_seed: key of the fader's draws;
+        time0: uint64 stream time of the rows' first output sample.  Asynchronous on the handle's stream."""
         if isinstance(taps, int):
             if n_taps is None:
                 raise ValueError("device taps need n_taps")
@@ -551,6 +560,16 @@ class WifiRx:
         ro = None if row_off is None else np.ascontiguousarray(row_off, dtype=np.uint64)
         if ro is not None and ro.size != int(n_rows) + 1:
             raise ValueError("row_off needs n_rows + 1 entries")
+        if doppler is not None:
+            s = None if sro is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sro, dtype=np.float32), (int(n_rows),)))
+            fd = np.ascontiguousarray(np.broadcast_to(np.asarray(doppler, dtype=np.float32), (int(n_rows),)))
+            self._check(_lib.wifirx_channel_fading(self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0),
+                                                   int(n_rows), t_ptr, t_dev, L, n_sets, _np_ptr(c),
+                                                   int(phase0) & 0xFFFFFFFFFFFFFFFF, _np_ptr(s), int(drift0), float(gain),
+                                                   float(noise_voltage), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                   int(sample0) & 0xFFFFFFFFFFFFFFFF, _np_ptr(fd), float(k_factor),
+                                                   int(fade_seed) & 0xFFFFFFFFFFFFFFFF, int(time0) & 0xFFFFFFFFFFFFFFFF))
+            return
         if sro is not None:
             s = np.ascontiguousarray(np.broadcast_to(np.asarray(sro, dtype=np.float32), (int(n_rows),)))
             self._check(_lib.wifirx_channel_sro(self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0),
@@ -565,7 +584,7 @@ class WifiRx:
                                         int(sample0) & 0xFFFFFFFFFFFFFFFF))
 
     def channel(self, x, *, row_off=None, taps=(1.0,), cfo=None, phase0=0, gain=1.0, noise_voltage=0.0, seed=0,
-                sample0=0, sro=None, drift0=0):
+                sample0=0, sro=None, drift0=0, doppler=None, k_factor=0.0, fade_seed=0, time0=0):
         """channel_dev on host samples: x [n_rows, row_len] (fixed rows; 1-D = one row) or, with row_off, the 1-D buffer the
         offsets index.  Returns the output in x's shape; samples outside the rows are 0."""
         x = np.ascontiguousarray(x, dtype=np.complex64)
@@ -584,7 +603,7 @@ class WifiRx:
             d_out.upload(np.zeros(n, np.complex64))
             self.channel_dev(d_in.ptr, d_out.ptr, n, n_rows, row_len=row_len, row_off=row_off, taps=taps, cfo=cfo,
                              phase0=phase0, gain=gain, noise_voltage=noise_voltage, seed=seed, sample0=sample0, sro=sro,
-                             drift0=drift0)
+                             drift0=drift0, doppler=doppler, k_factor=k_factor, fade_seed=fade_seed, time0=time0)
             y = d_out.download(np.complex64, n)      # ordered behind the kernel on the handle's stream
         finally:
             d_in.free()

@@ -415,6 +415,37 @@ int  wifirx_channel_sro(wifirx_handle* h, const float* in, float* out, uint64_t 
                         const float* cfo, uint64_t phase0, const float* sro, int64_t drift0,
                         float gain, float noise_voltage, uint64_t seed, uint64_t sample0);
 
+/* wifirx_channel_sro with taps that vary in time: a Doppler fader (Rayleigh, or Rician on tap 0) between the resampler and the
+ * rest of wifirx_channel's chain, in the same single launch; arithmetic = NUMERICS.md rule 19.  Every tap l of row r is
+ * multiplied by a gain of mean power 1, a sum of 8 sinusoids whose arrival angles and start phases are Philox draws:
+ *     s[n]     = sum_{l=0}^{L-1} (g_{r,l}(n) t_{r,l}) u[n-l]      the gain at the output time n for every tap
+ *     g_l      = the linear interpolation, on the 32-sample grid of t = time0 + n, of
+ *     G_l(t)   = sqrt(1/8) sum_{k=0}^{7} exp(j 2 pi (phi_{l,k} + inc_{l,k} t) / 2^64),    inc = llround(fd_r cos(a_{l,k}) 2^64)
+ * and with k_factor = K > 0 tap 0 is sqrt(K / (K+1)) e_los(t) + sqrt(1 / (K+1)) G_0(t), e_los one more such oscillator.
+ *   doppler    HOST [n_rows] maximum Doppler shift fd_r in cycles per sample (1e-4 = 1 kHz at 10 MS/s), 0 <= fd_r <= 2^-10: the
+ *              interpolation is then within sqrt(8) (2 pi fd 32)^2 / 8 = 1.4e-2 of the sinusoids (1.4e-4 at 1e-4).  fd_r = 0
+ *              is not "no fading": it is one static random gain per row and tap.  NULL = no fading: the call then IS
+ *              wifirx_channel_sro (the same kernel instances; k_factor, fade_seed and time0 are not looked at).
+ *   k_factor   Rician K of tap 0 (power of the line of sight over the scattered power); 0 = Rayleigh on every tap.
+ *   fade_seed  key of the fader's draws, on the counter (8 l + k, r, 0, 1) (the line of sight: 128): word 3 keeps them apart
+ *              from the noise's, which has 0 there, so one value may serve as seed and fade_seed.
+ *   time0      the stream time of every row's first output sample.  The grid lies on time0 + n, so a stream cut into calls
+ *              stays exact when each call passes on time0 + (samples it advanced), apart from the FIR's n_taps - 1 samples
+ *              behind the cut; any uint64 is taken, the time wraps.
+ *   sro        as wifirx_channel_sro; may be NULL (no resampler) with or without fading.
+ *   n_taps     1..16 with fading (the gains of a tile live in LDS beside the resampler's arrays).
+ *   in, out    never in place with fading, not even with one tap: every overlap of the rows' samples is refused.
+ * Checked on the host before anything is queued, beside wifirx_channel_sro's checks: WIFIRX_EINVAL for a doppler that is not
+ * finite, negative or above 2^-10, for a k_factor that is not finite or negative, for n_taps > 16 with fading, and for
+ * in == out with fading.  One kernel launch per call, after one upload of the host arrays (taps, cfo, row_off, the drift
+ * increments, doppler).  ORDER: as wifirx_channel. */
+int  wifirx_channel_fading(wifirx_handle* h, const float* in, float* out, uint64_t samples_cap,
+                           const uint64_t* row_off, uint64_t row_len, uint32_t n_rows,
+                           const float* taps, int taps_on_device, uint32_t n_taps, uint32_t n_tap_sets,
+                           const float* cfo, uint64_t phase0, const float* sro, int64_t drift0,
+                           float gain, float noise_voltage, uint64_t seed, uint64_t sample0,
+                           const float* doppler, float k_factor, uint64_t fade_seed, uint64_t time0);
+
 /* The resampler's table (NUMERICS.md rule 18; tools/gen_resample_table.py): *taps = (n_phases + 1) rows of n_taps float32,
  * row p = the fractional delay p / n_phases, tap k weighing x[i + k - 15]; n_phases = 128, n_taps = 32.  Host memory owned by
  * the library.  Needs no handle and no device; any argument may be NULL.  Returns WIFIRX_OK. */

@@ -6,8 +6,12 @@ writes).  Prints one JSON line, writes it to --out when given.
 --sro adds wifirx_channel_sro on the same rows with the sample clock locked to the carrier, sro = -cfo bw / (2 pi fc) per
 row (NUMERICS.md rule 18), one tap and 8 taps, and a hipMemsetAsync of the output bytes, beside the calls without sro.
 
+--fading adds wifirx_channel_fading on the same rows with the same 8-tap sets, a Doppler of 1e-4 cycles per sample on every
+row and K = 10 (NUMERICS.md rule 19), and -- to say where its time goes -- the static and the fading 8-tap call without noise.
+
     python tools/channel_bench.py [--iters 3] [--out profiles/channel_config2.json]
-    python tools/channel_bench.py --sro [--out profiles/channel_sro_config2.json]"""
+    python tools/channel_bench.py --sro [--out profiles/channel_sro_config2.json]
+    python tools/channel_bench.py --fading [--out profiles/channel_fading_config2.json]"""
 import argparse
 import ctypes as C
 import json
@@ -30,6 +34,7 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--rows", type=int, default=N)
     ap.add_argument("--sro", action="store_true", help="also time wifirx_channel_sro (locked sample clock) and a memset")
+    ap.add_argument("--fading", action="store_true", help="also time wifirx_channel_fading (8 taps, Doppler 1e-4, K = 10)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     n = a.rows
@@ -89,6 +94,17 @@ def main():
                                                      gain=gain, noise_voltage=1.0, seed=7),
             "memset": lambda: hip.hipMemsetAsync(d_out.ptr, 0, nbytes, st),
         })
+    if a.fading:
+        fd = np.full(n, 1e-4, np.float32)
+        fade = dict(doppler=fd, k_factor=10.0, fade_seed=19)
+        runs.update({
+            "channel_fading_L8": lambda: rx.channel_dev(d_in.ptr, d_out.ptr, n * ROW, n, row_len=ROW, taps=taps8, cfo=cfo, gain=gain,
+                                                        noise_voltage=1.0, seed=7, **fade),
+            "channel_L8_quiet": lambda: rx.channel_dev(d_in.ptr, d_out.ptr, n * ROW, n, row_len=ROW, taps=taps8, cfo=cfo, gain=gain,
+                                                       noise_voltage=0.0),
+            "channel_fading_L8_quiet": lambda: rx.channel_dev(d_in.ptr, d_out.ptr, n * ROW, n, row_len=ROW, taps=taps8, cfo=cfo,
+                                                              gain=gain, noise_voltage=0.0, **fade),
+        })
     rx.synth_slots(tmpl, d_in.ptr, ROW, n, 160, 20.0, 0.037, 3)        # the input: config 2's slots
     for fn in runs.values():                                            # warm-up of each
         fn()
@@ -116,6 +132,17 @@ def main():
                                                         "L8": med["channel_sro_L8"] / med["channel_L8"]},
                           Gsamples_per_s={k: n * ROW / med[k] / 1e6 for k in ("channel_sro_L1", "channel_sro_L8")},
                           memset_GBps_written=nbytes / med["memset"] / 1e6)
+    if a.fading:
+        res["fading"] = dict(what="wifirx_channel_fading, 8 taps (sv_taps.npy sets), doppler 1e-4 cycles per sample on every row, "
+                                  "k_factor 10, time0 0; the whole call (upload of 4 MB of CFO and 4 MB of Doppler, then the kernel)",
+                             ms_median={k: med[k] for k in ("channel_fading_L8", "channel_L8", "memcpy_d2d", "channel_fading_L8_quiet",
+                                                            "channel_L8_quiet")},
+                             ratio_to_static_L8=med["channel_fading_L8"] / med["channel_L8"],
+                             ratio_to_memcpy=med["channel_fading_L8"] / med["memcpy_d2d"],
+                             ratio_to_static_L8_without_noise=med["channel_fading_L8_quiet"] / med["channel_L8_quiet"],
+                             ms_added_by_fading={"with_noise": med["channel_fading_L8"] - med["channel_L8"],
+                                                 "without_noise": med["channel_fading_L8_quiet"] - med["channel_L8_quiet"]},
+                             Gsamples_per_s=n * ROW / med["channel_fading_L8"] / 1e6)
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:

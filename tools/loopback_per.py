@@ -21,7 +21,16 @@ needs 6 LLRs per carrier, so the LLR rows are bf16 (WIFIRX_LLR_BF16, 57 kB per f
 frame_equalizer assumes: wifirx_channel_sro with sro = -cfo bw / (2 pi fc) per row (NUMERICS.md rule 18) in place of
 wifirx_channel.  Everything else, the seeds included, stays, so a sweep with the switch stands beside one without.
 
-    python tools/loopback_per.py --locked-clock [--out profiles/loopback_per_config3_locked.json]"""
+    python tools/loopback_per.py --locked-clock [--out profiles/loopback_per_config3_locked.json]
+
+--doppler asks which equaliser follows a channel that changes within the frame: the loop-back through wifirx_channel_fading
+(NUMERICS.md rule 19) at every Doppler given (cycles per sample; 1e-4 = 1 kHz at 10 MS/s), Rician on tap 0 with --k-factor, and
+per channel realisation the demodulator with each equaliser of --eq (all four by default) and the hard decode_mac.  The frames
+are --psdu-len bytes at --encoding (default 1528 bytes of 64-QAM 2/3: 64 symbols) in fixed rows of lead 160 + frame + 79, the
+channel is flat (--multipath: the 8-tap sets of sv_taps.npy cycling, every tap fading) and has no carrier offset.  Per SNR,
+Doppler and equaliser: the FER and the counters of wifirx_link_stats.
+
+    python tools/loopback_per.py --doppler 0 3e-5 1e-4 2e-4 --k-factor 10 --snr 25 30 [--frames 1000000] [--out profiles/loopback_fading.json]"""
 import argparse
 import json
 import math
@@ -40,6 +49,9 @@ SLOT, LEAD, ENC, PSDU_LEN = 1472, 160, 7, 294
 CFO_20PPM = 2 * np.pi * 20e-6 * 5.89e9 / 20e6
 POPCOUNT6 = np.array([bin(v).count("1") for v in range(256)], np.uint8)
 COUNTERS = [k for k, _ in capi.LinkCounts._fields_]
+
+
+EQUALISERS = {"ls": capi.EQ_LS, "lms": capi.EQ_LMS, "comb": capi.EQ_COMB, "sta": capi.EQ_STA}
 
 
 def host_stats(rx, dev, n, n_sym, nb, p, idx_tx):
@@ -73,8 +85,17 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--host-stats", action="store_true", help="also keep the books in NumPy and assert they agree")
     ap.add_argument("--locked-clock", action="store_true", help="sample clock locked to the carrier: sro = -cfo bw / (2 pi fc)")
+    ap.add_argument("--doppler", type=float, nargs="+", default=None, help="Doppler fading at these values, cycles per sample")
+    ap.add_argument("--k-factor", type=float, default=0.0, help="with --doppler: Rician K of tap 0 (0 = Rayleigh)")
+    ap.add_argument("--eq", nargs="+", choices=sorted(EQUALISERS, key=EQUALISERS.get), default=None,
+                    help="with --doppler: the equalisers to compare (default all four)")
+    ap.add_argument("--psdu-len", type=int, default=1528, help="with --doppler: PSDU bytes, 28 .. 1528")
+    ap.add_argument("--encoding", type=int, default=6, help="with --doppler: 0 .. 7")
+    ap.add_argument("--multipath", action="store_true", help="with --doppler: the sv_taps.npy sets in place of the flat channel")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.doppler is not None:
+        return fading_main(a)
     if a.rates:
         return rates_main(a)
     n = a.frames or 1_000_000
@@ -129,6 +150,66 @@ def main():
                        + ("; sample clock locked to the carrier (wifirx_channel_sro, sro = -cfo bw / (2 pi fc))" if a.locked_clock else ""),
            "stats": "wifirx_link_stats on the device" + (", checked against the NumPy bookkeeping" if a.host_stats else ""),
            "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def fading_main(a):
+    if a.rates or a.host_stats or a.locked_clock:
+        raise SystemExit("--doppler stands alone: not with --rates, --host-stats or --locked-clock")
+    n = a.frames or 1_000_000
+    plen, enc = a.psdu_len, a.encoding
+    if not (28 <= plen <= 1528 and 0 <= enc <= 7):
+        raise SystemExit("--psdu-len 28 .. 1528, --encoding 0 .. 7")
+    eqs = a.eq or ["ls", "lms", "comb", "sta"]
+    n_sym = txgen.n_sym_for(plen, enc)
+    slot = LEAD + txgen.frame_samples(plen, enc) + 79
+    slot += slot & 1
+    stride = (plen + 15) // 16 * 16
+    taps = np.load(os.path.join(ROOT, "tests", "golden", "sv_taps.npy")).astype(np.complex64) if a.multipath else (1.0,)
+    rx = capi.WifiRx(max_sym=n_sym, llr_bits=0, chan_est=capi.EQ_LS, device=0)
+    t_all = time.perf_counter()
+    d_psdu, rows, iq = rx.alloc(n * plen), rx.alloc(n * slot * 8), rx.alloc(n * slot * 8)
+    rx.mac_batch_dev(d_psdu.ptr, plen, n, None, payload_len=plen - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, n * slot, d_psdu.ptr, enc, psdu_len=np.full(n, plen, np.uint32), psdu_stride=plen, lead=LEAD,
+                    row_len=slot)
+    dev = rx.alloc_out(n, psdu_stride=stride, want_hbits=True)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * n_sym * 48), hbits=rx.alloc(n * n_sym * 48),
+               psdu=d_psdu, psdu_stride=plen)
+    rx.demod_batch_dev(rows.ptr, slot, n, ref)
+    assert rx.link_stats(n, ref, ref)["frames_ref"] == n, "a clean frame was not demodulated"
+    points = []
+    for snr in a.snr:
+        for i, fd in enumerate(a.doppler):
+            t0 = time.perf_counter()
+            # one channel realisation per (SNR, Doppler); every equaliser sees the same samples
+            rx.channel_dev(rows.ptr, iq.ptr, n * slot, n, row_len=slot, taps=taps, gain=math.sqrt(10 ** (snr / 10)), noise_voltage=1.0,
+                           seed=9000 + int(snr) + (a.seed << 32), doppler=fd, k_factor=a.k_factor, fade_seed=100 * a.seed + i)
+            by_eq = {}
+            for name in eqs:
+                rx.set_param(capi.P_CHAN_EST, EQUALISERS[name])
+                rx.demod_batch_dev(iq.ptr, slot, n, dev)
+                rx.decode_batch_dev(n, dev)
+                r = rx.link_stats(n, dev, ref)
+                by_eq[name] = {"fer": r["fer"], "coded_ber": r["coded_ber"], "coded_ber_se": r["coded_ber_se"],
+                               "counts": {k: r[k] for k in COUNTERS}}
+            rx.set_param(capi.P_CHAN_EST, capi.EQ_LS)
+            points.append({"snr_db": snr, "doppler": fd, "frames": n, "seconds": time.perf_counter() - t0,
+                           "fer": {k: v["fer"] for k, v in by_eq.items()}, "by_equaliser": by_eq})
+            print(json.dumps({k: points[-1][k] for k in ("snr_db", "doppler", "seconds", "fer")}), file=sys.stderr)
+    seconds_total = time.perf_counter() - t_all
+    rx.free_out(ref)
+    rx.free_out(dev)
+    rows.free(); iq.free(); rx.close()
+    res = {"workload": "loop-back on the device through wifirx_channel_fading: %d distinct frames per point (wifirx_mac_batch, Philox "
+                       "payloads), encoding %d, PSDU %d B (%d symbols), rows of %d, lead 160, %s, k_factor %g, no carrier offset; hard "
+                       "decode_mac; every equaliser on the same channel output"
+                       % (n, enc, plen, n_sym, slot, "sv_taps.npy sets cycling, every tap fading" if a.multipath else "flat channel",
+                          a.k_factor),
+           "doppler_unit": "cycles per sample (1e-4 = 1 kHz at 10 MS/s)", "equalisers": eqs,
+           "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
