@@ -3,21 +3,20 @@
 // noise adder, in the float32 arithmetic of NUMERICS.md rule 17.
 //
 // Work split (the shape of wr_tx.hip): the output of every row is cut into tiles of CH_TILE consecutive samples on
-// pair-aligned indices; one workgroup owns one tile.  With more than one tap it first stages the tile's input and the
-// n_taps - 1 samples before it (zeros before the row start: every row is its own burst) in LDS; then every lane produces
-// CH_TILE / 512 pairs of consecutive samples and writes each with one 16-byte store.  The phase is fixed point (a uint64
-// in 2^-64 turns: exact for any row length), the noise is wr_synth.hip's Philox4x32-10 + Box-Muller on the counter
-// (pair index of the sample, row).
-//
-// With a sample-rate offset (wifirx_channel_sro, NUMERICS.md rule 18) a further kind of instance puts the polyphase
-// resampler in front of the FIR inside the same launch: the workgroup stages the raw input window of its tile (the tile,
-// the FIR halo, the resampler's 31 neighbours and the drift spread over the tile) and the table in LDS, forms the resampled
-// samples u of the tile and its FIR halo into the array the FIR reads, and goes on as the other instances do.
-//
-// With Doppler fading (wifirx_channel_fading, NUMERICS.md rule 19) two more instances, with and without the resampler, make
-// the FIR's taps functions of time: the workgroup derives its row's oscillators (8 per tap and the line-of-sight one: a
-// Philox draw, one sp_sincos and one double product each), fills an LDS array with the gains of every tap on the 32-sample
-// grid of the stream time that covers the tile, and the FIR loop interpolates between two grid points per sample and tap.
+// pair-aligned indices; one workgroup owns one tile.  channel_kernel, in this order:
+//   place    ch_place: the tile's row and its place in it, for fixed rows and for row_off rows;
+//   stage    with more than one tap, the tile's input and the n_taps - 1 samples before it (zeros before the row start: every
+//            row is its own burst) into the LDS array xs.  With a sample-rate offset (wifirx_channel_sro, NUMERICS.md rule 18)
+//            the raw input window (the tile, the FIR halo, the resampler's 31 neighbours, the drift spread over the tile) and
+//            the table go into LDS, and xs takes the resampled samples u of the tile and its FIR halo;
+//   fade     with Doppler fading (wifirx_channel_fading, rule 19) the row's oscillators (8 per tap and the line-of-sight one: a
+//            Philox draw, one sp_sincos and one double product each), set up in front of the staging, and behind it the gains
+//            of every tap on the 32-sample grid of the stream time that covers the tile, in LDS;
+//   FIR      every lane forms CH_TILE / 512 pairs of consecutive samples in one loop over xs, whose coefficient (ch_coef) is
+//            the tap or, with fading, the tap times the gain interpolated between two grid points; one tap reads its pair
+//            from global memory instead;
+//   mix, noise, store   the phase is fixed point (a uint64 in 2^-64 turns: exact for any row length), the noise is
+//            wr_synth.hip's Philox4x32-10 + Box-Muller on the counter (pair index of the sample, row), one 16-byte store a pair.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -103,24 +102,11 @@ __device__ __forceinline__ float2 fade_lerp(float2 G0, float2 G1, float w)
 // rule 18: output n of a row whose drift is D = drift0 + dinc n (2^-40 samples) reads the input around i = n + (D >> 40)
 __device__ __forceinline__ int64_t rs_pos(int64_t n, int64_t D) { return n + (D >> 40); }
 
-// STAGE: the FIR reads its input from LDS (n_taps > 1, SRO or FADE); SRO: that input is the resampled row (rule 18), any
-// n_taps; FADE: the taps are multiplied by gains that vary with the stream time (rule 19), n_taps <= CH_FADE_TAPS
-template <bool STAGE, bool SRO, bool FADE>
-__global__ __launch_bounds__(256)
-void channel_kernel(const ChanArgs a)
-{
-    static_assert(STAGE || !SRO, "the resampler writes the array the FIR reads");
-    static_assert(STAGE || !FADE, "the fading FIR reads its input from LDS");
-    __shared__ uint64_t osc_phi[FADE ? CH_FADE_LOS + 1 : 1], osc_inc[FADE ? CH_FADE_LOS + 1 : 1];
-    __shared__ float2 gg[FADE ? CH_FADE_GRID * CH_FADE_TAPS : 1];      // [grid point][tap], n_taps apart
-    __shared__ float2 xs[STAGE ? CH_TILE + CH_MAX_TAPS - 1 : 1];
-    __shared__ float2 tp[CH_MAX_TAPS];
-    __shared__ float2 raw[SRO ? CH_RAW : 1];
-    __shared__ __attribute__((aligned(16))) float tab[SRO ? (WR_RS_PHASES + 1) * WR_RS_TAPS : 1];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t tile = blockIdx.x;
+struct ChanTile { uint32_t r; uint64_t k; int64_t rs, re; };      // row, tile of the row, row start and end
 
-    // ---- the tile's row and its place in it (uniform: scalar loads) ----
+// the tile's row and its place in it (uniform: scalar loads)
+__device__ __forceinline__ ChanTile ch_place(const ChanArgs& a, uint64_t tile)
+{
     uint32_t r;
     uint64_t k;
     if (a.row_off) {
@@ -137,14 +123,41 @@ void channel_kernel(const ChanArgs a)
     }
     const int64_t rs = a.row_off ? (int64_t)a.row_off[r] : (int64_t)r * (int64_t)a.row_len;
     const int64_t re = a.row_off ? (int64_t)a.row_off[r + 1] : rs + (int64_t)a.row_len;
-    const int64_t gt = (((rs + a.shift) & ~(int64_t)1) - a.shift) + (int64_t)k * CH_TILE;      // first sample of the tile
-    const uint32_t L = a.n_taps;
+    return {r, k, rs, re};
+}
 
+// coefficient of tap q: the tap; with FADE the gain interpolated between the grid rows g and g + L, times the tap
+template <bool FADE>
+__device__ __forceinline__ float2 ch_coef(const float2* tp, const float2* g, float w, uint32_t L, uint32_t q)
+{
+    if constexpr (FADE) return ch_mul(fade_lerp(g[q], g[L + q], w), tp[q]);
+    else return tp[q];
+}
+
+// STAGE: the FIR reads its input from LDS (n_taps > 1, SRO or FADE); SRO: that input is the resampled row (rule 18), any
+// n_taps; FADE: the taps are multiplied by gains that vary with the stream time (rule 19), n_taps <= CH_FADE_TAPS
+template <bool STAGE, bool SRO, bool FADE>
+__global__ __launch_bounds__(256)
+void channel_kernel(const ChanArgs a)
+{
+    static_assert(STAGE || !SRO, "the resampler writes the array the FIR reads");
+    static_assert(STAGE || !FADE, "the fading FIR reads its input from LDS");
+    __shared__ uint64_t osc_phi[FADE ? CH_FADE_LOS + 1 : 1], osc_inc[FADE ? CH_FADE_LOS + 1 : 1];
+    __shared__ float2 gg[FADE ? CH_FADE_GRID * CH_FADE_TAPS : 1];      // [grid point][tap], n_taps apart
+    __shared__ float2 xs[STAGE ? CH_TILE + CH_MAX_TAPS - 1 : 1];
+    __shared__ float2 tp[CH_MAX_TAPS];
+    __shared__ float2 raw[SRO ? CH_RAW : 1];
+    __shared__ __attribute__((aligned(16))) float tab[SRO ? (WR_RS_PHASES + 1) * WR_RS_TAPS : 1];
+    const uint32_t tid = threadIdx.x;
+    const ChanTile p = ch_place(a, blockIdx.x);
+    const uint32_t r = p.r, L = a.n_taps;
+    const int64_t rs = p.rs, re = p.re, gt = (((rs + a.shift) & ~(int64_t)1) - a.shift) + (int64_t)p.k * CH_TILE;
+
+    // ---- stage: the taps, the input window, the gains on the grid ----
     if (tid < L) tp[tid] = a.taps[(size_t)(r % a.n_tap_sets) * L + tid];
     uint64_t q0 = 0;                                   // FADE: stream time of the tile's first grid point
     if constexpr (FADE) {
         q0 = (a.time0 + (uint64_t)(gt - rs)) & ~(uint64_t)(CH_FADE_STEP - 1);
-        // the row's oscillators: slot 8 l + k for sinusoid k of tap l, slot CH_FADE_LOS for the line of sight
         if (tid < CH_FADE_SINES * L || tid == CH_FADE_LOS) {
             const uint4 d = philox4x32_10(make_uint4(tid, r, 0u, 1u), make_uint2((uint32_t)a.fade_seed, (uint32_t)(a.fade_seed >> 32)));
             float sn, cs;
@@ -196,7 +209,7 @@ void channel_kernel(const ChanArgs a)
     }
     if constexpr (FADE) {
         __syncthreads();                               // the oscillators
-        const bool los = a.a_los != 0.0f;              // k_factor > 0
+        const bool los = a.a_los != 0.0f;                  // k_factor > 0
         for (uint32_t e = tid; e < CH_FADE_GRID * L; e += 256) {
             const uint32_t i = e / L, l = e - i * L;
             const uint64_t t = q0 + (uint64_t)i * CH_FADE_STEP;
@@ -214,6 +227,7 @@ void channel_kernel(const ChanArgs a)
     }
     __syncthreads();
 
+    // ---- per pair of samples: FIR, mixer, noise, store ----
     const uint64_t inc = a.cfo ? ch_phase_inc(a.cfo[r]) : 0;
     const uint2 key = make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
     const float h = 0.70710678118654752f * a.noise;
@@ -225,37 +239,24 @@ void channel_kernel(const ChanArgs a)
         const bool in0 = g >= rs && g < re, in1 = g + 1 >= rs && g + 1 < re;
         if (!in0 && !in1) continue;
 
-        // FIR, ascending k from the k = 0 product
         float2 s0, s1;
-        if constexpr (FADE) {
+        if constexpr (STAGE) {
             // the gains of both samples at their own output times t and t + 1, for every tap
             const uint64_t t0 = a.time0 + (uint64_t)(g - rs), t1 = t0 + 1;
-            const float2* g0 = gg + (uint32_t)((t0 - q0) / CH_FADE_STEP) * L;
-            const float2* g1 = gg + (uint32_t)((t1 - q0) / CH_FADE_STEP) * L;
+            const float2* g0 = gg + (FADE ? (uint32_t)((t0 - q0) / CH_FADE_STEP) * L : 0);
+            const float2* g1 = gg + (FADE ? (uint32_t)((t1 - q0) / CH_FADE_STEP) * L : 0);
             const float w0 = (float)(uint32_t)(t0 & (CH_FADE_STEP - 1)) * (1.0f / CH_FADE_STEP);
             const float w1 = (float)(uint32_t)(t1 & (CH_FADE_STEP - 1)) * (1.0f / CH_FADE_STEP);
             const int32_t b = j + (int32_t)L - 1;                  // xs index of the input at g
             float2 prev = xs[b + 1];
             float2 cur = xs[b];
-            s0 = ch_mul(ch_mul(fade_lerp(g0[0], g0[L], w0), tp[0]), cur);
-            s1 = ch_mul(ch_mul(fade_lerp(g1[0], g1[L], w1), tp[0]), prev);
+            s0 = ch_mul(ch_coef<FADE>(tp, g0, w0, L, 0), cur);
+            s1 = ch_mul(ch_coef<FADE>(tp, g1, w1, L, 0), prev);
             for (uint32_t q = 1; q < L; q++) {
                 prev = cur;
                 cur = xs[b - (int32_t)q];
-                s0 = ch_add(s0, ch_mul(ch_mul(fade_lerp(g0[q], g0[L + q], w0), tp[q]), cur));
-                s1 = ch_add(s1, ch_mul(ch_mul(fade_lerp(g1[q], g1[L + q], w1), tp[q]), prev));
-            }
-        } else if constexpr (STAGE) {
-            const int32_t b = j + (int32_t)L - 1;                  // xs index of the input at g
-            float2 prev = xs[b + 1];
-            float2 cur = xs[b];
-            s0 = ch_mul(tp[0], cur);
-            s1 = ch_mul(tp[0], prev);
-            for (uint32_t q = 1; q < L; q++) {
-                prev = cur;
-                cur = xs[b - (int32_t)q];
-                s0 = ch_add(s0, ch_mul(tp[q], cur));
-                s1 = ch_add(s1, ch_mul(tp[q], prev));
+                s0 = ch_add(s0, ch_mul(ch_coef<FADE>(tp, g0, w0, L, q), cur));
+                s1 = ch_add(s1, ch_mul(ch_coef<FADE>(tp, g1, w1, L, q), prev));
             }
         } else {
             float2 x0 = make_float2(0.0f, 0.0f), x1 = x0;
@@ -276,8 +277,6 @@ void channel_kernel(const ChanArgs a)
         const uint64_t P0 = a.phase0 + inc * n0;
         float2 y0 = ch_rotate(s0, P0, a.gain);
         float2 y1 = ch_rotate(s1, P0 + inc, a.gain);
-
-        // noise adder: sample m = sample0 + n draws from the counter (m >> 1, row), first or second pair by m & 1
         if (a.noise != 0.0f) {                                     // not 0 * w: a Box-Muller radius of inf would give NaN
             const uint64_t m0 = a.sample0 + n0, m1 = m0 + 1;
             const bool odd = (m0 & 1) != 0;                        // the same in every lane of the tile

@@ -547,6 +547,9 @@ class WifiRx:
         2^-10; wifirx_channel_fading, NUMERICS.md rule 19: never in place, at most 16 taps), None = static taps; 0 is a
         static random gain per row and tap.  k_factor: Rician K of tap 0 (0 = Rayleigh); fade_seed: key of the fader's draws;
         time0: uint64 stream time of the rows' first output sample.  Asynchronous on the handle's stream."""
+        n, u64 = int(n_rows), lambda v: int(v) & 0xFFFFFFFFFFFFFFFF
+        # scalar or [n_rows] -> contiguous float32 [n_rows]; None stays None
+        per_row = lambda v: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (n,)))
         if isinstance(taps, int):
             if n_taps is None:
                 raise ValueError("device taps need n_taps")
@@ -554,34 +557,19 @@ class WifiRx:
         else:
             keep, n_sets, L = self._channel_taps(taps)
             t_ptr, t_dev = _np_ptr(keep), 0
-        c = None
-        if cfo is not None:
-            c = np.ascontiguousarray(np.broadcast_to(np.asarray(cfo, dtype=np.float32), (int(n_rows),)))
+        c, s, fd = per_row(cfo), per_row(sro), per_row(doppler)
         ro = None if row_off is None else np.ascontiguousarray(row_off, dtype=np.uint64)
-        if ro is not None and ro.size != int(n_rows) + 1:
+        if ro is not None and ro.size != n + 1:
             raise ValueError("row_off needs n_rows + 1 entries")
-        if doppler is not None:
-            s = None if sro is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sro, dtype=np.float32), (int(n_rows),)))
-            fd = np.ascontiguousarray(np.broadcast_to(np.asarray(doppler, dtype=np.float32), (int(n_rows),)))
-            self._check(_lib.wifirx_channel_fading(self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0),
-                                                   int(n_rows), t_ptr, t_dev, L, n_sets, _np_ptr(c),
-                                                   int(phase0) & 0xFFFFFFFFFFFFFFFF, _np_ptr(s), int(drift0), float(gain),
-                                                   float(noise_voltage), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                   int(sample0) & 0xFFFFFFFFFFFFFFFF, _np_ptr(fd), float(k_factor),
-                                                   int(fade_seed) & 0xFFFFFFFFFFFFFFFF, int(time0) & 0xFFFFFFFFFFFFFFFF))
-            return
-        if sro is not None:
-            s = np.ascontiguousarray(np.broadcast_to(np.asarray(sro, dtype=np.float32), (int(n_rows),)))
-            self._check(_lib.wifirx_channel_sro(self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0),
-                                                int(n_rows), t_ptr, t_dev, L, n_sets, _np_ptr(c),
-                                                int(phase0) & 0xFFFFFFFFFFFFFFFF, _np_ptr(s), int(drift0), float(gain),
-                                                float(noise_voltage), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                int(sample0) & 0xFFFFFFFFFFFFFFFF))
-            return
-        self._check(_lib.wifirx_channel(self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0),
-                                        int(n_rows), t_ptr, t_dev, L, n_sets, _np_ptr(c), int(phase0) & 0xFFFFFFFFFFFFFFFF,
-                                        float(gain), float(noise_voltage), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                        int(sample0) & 0xFFFFFFFFFFFFFFFF))
+        head = (self._h, in_ptr, out_ptr, int(samples_cap), _np_ptr(ro), int(row_len or 0), n, t_ptr, t_dev, L, n_sets, _np_ptr(c), u64(phase0))
+        noise = (float(gain), float(noise_voltage), u64(seed), u64(sample0))
+        if fd is not None:                          # the narrowest entry point that takes the call
+            rc = _lib.wifirx_channel_fading(*head, _np_ptr(s), int(drift0), *noise, _np_ptr(fd), float(k_factor), u64(fade_seed), u64(time0))
+        elif s is not None:
+            rc = _lib.wifirx_channel_sro(*head, _np_ptr(s), int(drift0), *noise)
+        else:
+            rc = _lib.wifirx_channel(*head, *noise)
+        self._check(rc)
 
     def channel(self, x, *, row_off=None, taps=(1.0,), cfo=None, phase0=0, gain=1.0, noise_voltage=0.0, seed=0,
                 sample0=0, sro=None, drift0=0, doppler=None, k_factor=0.0, fade_seed=0, time0=0):

@@ -3,7 +3,10 @@
 Per row: the FIR in float32 (plain products and sums, ascending k from the k = 0 product), the mixer with the fixed-point
 phase P = phase0 + inc n mod 2^64 and the oracle's sincos (rule 1), one float32 multiply by the gain per part, then -- when
 noise_voltage != 0 -- Philox4x32-10 + Box-Muller noise on the counter ((sample0 + n) >> 1, row), key = seed.  The noiseless
-path is bit-exact; the noise uses NumPy's float32 log / sqrt / sin / cos where the device has its own, so it agrees to ulps."""
+path is bit-exact; the noise uses NumPy's float32 log / sqrt / sin / cos where the device has its own, so it agrees to ulps.
+
+channel() composes rules 17 to 19: the row layout, the per-row arguments and the choice of the tap set are written here once,
+the resampler's stages are resample_ref.py's and the fader's fading_ref.py's; fir() and mix() serve static and fading taps."""
 import math
 
 import numpy as np
@@ -68,31 +71,37 @@ def noise(m, row, seed, noise_voltage):
     return (h * r) * np.cos(ang), (h * r) * np.sin(ang)
 
 
-def channel_row(x, taps, inc=0, phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, row=0):
-    """one row: x complex64 [n], taps complex64 [L] -> complex64 [n]"""
+def angle(P):
+    """uint64 phases in 2^-64 turns -> the float32 angle the mixer forms"""
+    return (P >> np.uint64(32)).astype(np.uint32).view(np.int32).astype(F32) * PHASE_SCALE
+
+
+def fir(x, coef):
+    """s[n] = sum_k c_k[n] x[n - k], x = 0 before the row: plain float32 products and sums per part, from the k = 0 product in
+    ascending k.  x complex64 [n]; coef: per tap its (real, imaginary) parts, float32 scalars (a tap set) or arrays [n] (taps
+    that vary per sample).  Returns the parts (real, imaginary) float32 [n]"""
     x = np.asarray(x, dtype=np.complex64)
     n = x.size
     xr, xi = x.real.astype(F32), x.imag.astype(F32)
-    t = np.asarray(taps, dtype=np.complex64).reshape(-1)
     sr = np.zeros(n, F32)
     si = np.zeros(n, F32)
-    for k in range(t.size):
-        ar, ai = F32(t[k].real), F32(t[k].imag)
+    for k, (ar, ai) in enumerate(coef):
         br = np.zeros(n, F32)
         bi = np.zeros(n, F32)
-        br[k:] = xr[:n - k] if k < n else br[k:]
-        bi[k:] = xi[:n - k] if k < n else bi[k:]
+        if k < n:
+            br[k:], bi[k:] = xr[:n - k], xi[:n - k]
         pr = ar * br - ai * bi
         pi = ar * bi + ai * br
-        if k == 0:
-            sr, si = pr, pi
-        else:
-            sr, si = sr + pr, si + pi
-    idx = np.arange(n, dtype=np.uint64)
+        sr, si = (pr, pi) if k == 0 else (sr + pr, si + pi)
+    return sr, si
+
+
+def mix(sr, si, inc=0, phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, row=0):
+    """rule 17 after the FIR: the mixer, the gain and the noise on the parts (sr, si) float32 [n] -> complex64 [n]"""
+    idx = np.arange(sr.size, dtype=np.uint64)
     with np.errstate(over="ignore"):
         P = np.uint64(phase0 & M64) + np.uint64(inc & M64) * idx
-    ang = (P >> np.uint64(32)).astype(np.uint32).view(np.int32).astype(F32) * PHASE_SCALE
-    sn, cs = orc.sincos(ang)
+    sn, cs = orc.sincos(angle(P))
     yr = sr * cs - si * sn
     yi = sr * sn + si * cs
     g = F32(gain)
@@ -102,14 +111,24 @@ def channel_row(x, taps, inc=0, phase0=0, gain=1.0, noise_voltage=0.0, seed=0, s
             m = np.uint64(sample0 & M64) + idx
         wr_, wi_ = noise(m, row, seed, noise_voltage)
         yr, yi = yr + wr_, yi + wi_
-    out = np.empty(n, np.complex64)
+    out = np.empty(sr.size, np.complex64)
     out.real, out.imag = yr, yi
     return out
 
 
-def channel(x, row_off=None, taps=(1.0,), cfo=None, phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0):
-    """WifiRx.channel restated: x [n_rows, row_len] (1-D = one row) or, with row_off, the 1-D buffer; taps 1-D or
-    [n_tap_sets, L]; cfo scalar or per row (rad/sample, taken as float32).  Samples outside the rows are 0."""
+def channel_row(x, taps, inc=0, phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, row=0):
+    """one row: x complex64 [n], taps complex64 [L] -> complex64 [n]"""
+    t = np.asarray(taps, dtype=np.complex64).reshape(-1)
+    return mix(*fir(x, [(F32(c.real), F32(c.imag)) for c in t]), inc, phase0, gain, noise_voltage, seed, sample0, row)
+
+
+def channel(x, row_off=None, taps=(1.0,), cfo=None, phase0=0, gain=1.0, noise_voltage=0.0, seed=0, sample0=0, *, sro=None,
+            drift0=0, doppler=None, k_factor=0.0, fade_seed=0, time0=0):
+    """WifiRx.channel restated, rules 17 to 19 composed: x [n_rows, row_len] (1-D = one row) or, with row_off, the 1-D buffer;
+    taps 1-D or [n_tap_sets, L]; cfo, sro and doppler scalar or per row (taken as float32).  sro=None: no resampler
+    (resample_ref.py), doppler=None: static taps (fading_ref.py).  Samples outside the rows are 0."""
+    import fading_ref          # (both import this module)
+    import resample_ref
     x = np.asarray(x, dtype=np.complex64)
     t = np.asarray(taps, dtype=np.complex64)
     t = t[None] if t.ndim == 1 else t
@@ -121,11 +140,17 @@ def channel(x, row_off=None, taps=(1.0,), cfo=None, phase0=0, gain=1.0, noise_vo
         off = np.asarray(row_off, dtype=np.uint64)
         flat = x
     n_rows = off.size - 1
-    c = np.zeros(n_rows, F32) if cfo is None else np.broadcast_to(np.asarray(cfo, dtype=F32), (n_rows,))
+    per_row = lambda v: None if v is None else np.broadcast_to(np.asarray(v, dtype=F32), (n_rows,))
+    c, s, fd = per_row(0.0 if cfo is None else cfo), per_row(sro), per_row(doppler)
+    assert s is None or (np.abs(s) <= resample_ref.SRO_MAX).all()
     out = np.zeros(flat.size, np.complex64)
     for r in range(n_rows):
         a, b = int(off[r]), int(off[r + 1])
         if b > a:
-            out[a:b] = channel_row(flat[a:b], t[r % t.shape[0]], phase_inc(c[r]), phase0, gain, noise_voltage, seed,
-                                   sample0, r)
+            u = flat[a:b] if s is None else resample_ref.resample_row(flat[a:b], resample_ref.drift_inc(s[r]), drift0)
+            tail = (phase_inc(c[r]), phase0, gain, noise_voltage, seed, sample0, r)
+            if fd is None:
+                out[a:b] = channel_row(u, t[r % t.shape[0]], *tail)
+            else:
+                out[a:b] = fading_ref.fading_row(u, t[r % t.shape[0]], fd[r], k_factor, fade_seed, time0, *tail)
     return out.reshape(x.shape)

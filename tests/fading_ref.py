@@ -12,8 +12,7 @@ import math
 import numpy as np
 
 import channel_ref
-import resample_ref
-from channel_ref import F32, M64, PHASE_SCALE, philox4x32_10
+from channel_ref import F32, M64, PHASE_SCALE, philox4x32_10, angle
 from oracle import oracle as orc
 from wifirx import capi
 
@@ -26,11 +25,6 @@ U64 = np.uint64
 # 64-QAM 2/3, 1528 bytes, a flat Rician channel at 30 dB without carrier offset; arms (name, doppler, equaliser)
 E2E = dict(n=48, enc=6, plen=1528, lead=160, k_factor=10.0, snr_db=30.0, seed=30, fade_seed=4, psdu_seed=19)
 ARMS = (("fd 1e-4, LS", 1e-4, capi.EQ_LS), ("fd 1e-4, STA", 1e-4, capi.EQ_STA), ("fd 0, LS", 0.0, capi.EQ_LS))
-
-
-def _angle(P):
-    """uint64 phases in 2^-64 turns -> the float32 angle the mixer forms"""
-    return (P >> U64(32)).astype(np.uint32).view(np.int32).astype(F32) * PHASE_SCALE
 
 
 def oscillators(row, n_taps, fd, fade_seed):
@@ -61,7 +55,7 @@ def osc(inc, phi, t):
     """(cos, sin) float32 of oscillators at the times t: uint64 arrays that broadcast"""
     with np.errstate(over="ignore"):
         P = np.asarray(phi, dtype=U64) + np.asarray(inc, dtype=U64) * np.asarray(t, dtype=U64)
-    sn, cs = orc.sincos(_angle(P))
+    sn, cs = orc.sincos(angle(P))
     return cs, sn
 
 
@@ -105,68 +99,17 @@ def fading_row(x, taps, fd, k_factor=0.0, fade_seed=0, time0=0, inc=0, phase0=0,
     n = x.size
     t = np.asarray(taps, dtype=np.complex64).reshape(-1)
     assert 1 <= t.size <= MAX_TAPS and 0.0 <= float(F32(fd)) <= DOPPLER_MAX
-    xr, xi = x.real.astype(F32), x.imag.astype(F32)
-    idx = np.arange(n, dtype=U64)
     with np.errstate(over="ignore"):
-        tt = U64(time0 & M64) + idx
-    o_inc, o_phi = oscillators(row, t.size, fd, fade_seed)
-    gr, gi = gains(tt, o_inc, o_phi, t.size, *rice(k_factor))
-    sr = np.zeros(n, F32)
-    si = np.zeros(n, F32)
-    for l in range(t.size):
-        ar, ai = F32(t[l].real), F32(t[l].imag)
-        cr = gr[:, l] * ar - gi[:, l] * ai
-        ci = gr[:, l] * ai + gi[:, l] * ar
-        br = np.zeros(n, F32)
-        bi = np.zeros(n, F32)
-        if l < n:
-            br[l:], bi[l:] = xr[:n - l], xi[:n - l]
-        pr = cr * br - ci * bi
-        pi = cr * bi + ci * br
-        sr, si = (pr, pi) if l == 0 else (sr + pr, si + pi)
-    # rule 17 from the mixer on (channel_ref.channel_row)
-    with np.errstate(over="ignore"):
-        P = U64(phase0 & M64) + U64(inc & M64) * idx
-    sn, cs = orc.sincos(_angle(P))
-    yr = sr * cs - si * sn
-    yi = sr * sn + si * cs
-    g = F32(gain)
-    yr, yi = g * yr, g * yi
-    if noise_voltage != 0.0:
-        with np.errstate(over="ignore"):
-            m = U64(sample0 & M64) + idx
-        wr_, wi_ = channel_ref.noise(m, row, seed, noise_voltage)
-        yr, yi = yr + wr_, yi + wi_
-    out = np.empty(n, np.complex64)
-    out.real, out.imag = yr, yi
-    return out
+        tt = U64(time0 & M64) + np.arange(n, dtype=U64)
+    gr, gi = gains(tt, *oscillators(row, t.size, fd, fade_seed), t.size, *rice(k_factor))
+    coef = [(gr[:, l] * F32(t[l].real) - gi[:, l] * F32(t[l].imag), gr[:, l] * F32(t[l].imag) + gi[:, l] * F32(t[l].real))
+            for l in range(t.size)]
+    return channel_ref.mix(*channel_ref.fir(x, coef), inc, phase0, gain, noise_voltage, seed, sample0, row)
 
 
 def channel(x, row_off=None, taps=(1.0,), cfo=None, phase0=0, sro=None, drift0=0, gain=1.0, noise_voltage=0.0, seed=0,
             sample0=0, doppler=None, k_factor=0.0, fade_seed=0, time0=0):
     """WifiRx.channel(..., doppler=, k_factor=, fade_seed=, time0=) restated.  doppler: scalar or per row (taken as float32),
-    None = rules 17 and 18 alone (resample_ref.channel)."""
-    if doppler is None:
-        return resample_ref.channel(x, row_off, taps, cfo, phase0, sro, drift0, gain, noise_voltage, seed, sample0)
-    x = np.asarray(x, dtype=np.complex64)
-    t = np.asarray(taps, dtype=np.complex64)
-    t = t[None] if t.ndim == 1 else t
-    if row_off is None:
-        rows = x.reshape(1, -1) if x.ndim == 1 else x
-        off = np.arange(rows.shape[0] + 1, dtype=U64) * rows.shape[1]
-        flat = rows.reshape(-1)
-    else:
-        off = np.asarray(row_off, dtype=U64)
-        flat = x
-    n_rows = off.size - 1
-    c = np.zeros(n_rows, F32) if cfo is None else np.broadcast_to(np.asarray(cfo, dtype=F32), (n_rows,))
-    fd = np.broadcast_to(np.asarray(doppler, dtype=F32), (n_rows,))
-    s = None if sro is None else np.broadcast_to(np.asarray(sro, dtype=F32), (n_rows,))
-    out = np.zeros(flat.size, np.complex64)
-    for r in range(n_rows):
-        a, b = int(off[r]), int(off[r + 1])
-        if b > a:
-            u = flat[a:b] if s is None else resample_ref.resample_row(flat[a:b], resample_ref.drift_inc(s[r]), drift0)
-            out[a:b] = fading_row(u, t[r % t.shape[0]], fd[r], k_factor, fade_seed, time0, channel_ref.phase_inc(c[r]), phase0,
-                                  gain, noise_voltage, seed, sample0, r)
-    return out.reshape(x.shape)
+    None = rules 17 and 18 alone."""
+    return channel_ref.channel(x, row_off, taps, cfo, phase0, gain, noise_voltage, seed, sample0, sro=sro, drift0=drift0,
+                               doppler=doppler, k_factor=k_factor, fade_seed=fade_seed, time0=time0)

@@ -83,21 +83,4 @@ def channel(x, row_off=None, taps=(1.0,), cfo=None, phase0=0, sro=None, drift0=0
             sample0=0):
     """WifiRx.channel(..., sro=, drift0=) restated: channel_ref.channel with every row resampled first.  sro: scalar or per
     row (taken as float32), None = rule 17 alone."""
-    if sro is None:
-        return channel_ref.channel(x, row_off, taps, cfo, phase0, gain, noise_voltage, seed, sample0)
-    x = np.asarray(x, dtype=np.complex64)
-    if row_off is None:
-        rows = x.reshape(1, -1) if x.ndim == 1 else x
-        off = np.arange(rows.shape[0] + 1, dtype=np.uint64) * rows.shape[1]
-        flat = rows.reshape(-1)
-    else:
-        off = np.asarray(row_off, dtype=np.uint64)
-        flat = x
-    n_rows = off.size - 1
-    s = np.broadcast_to(np.asarray(sro, dtype=F32), (n_rows,))
-    assert (np.abs(s) <= SRO_MAX).all()
-    u = np.zeros(flat.size, np.complex64)
-    for r in range(n_rows):
-        a, b = int(off[r]), int(off[r + 1])
-        u[a:b] = resample_row(flat[a:b], drift_inc(s[r]), drift0)
-    return channel_ref.channel(u.reshape(x.shape), row_off, taps, cfo, phase0, gain, noise_voltage, seed, sample0)
+    return channel_ref.channel(x, row_off, taps, cfo, phase0, gain, noise_voltage, seed, sample0, sro=sro, drift0=drift0)

@@ -5,7 +5,6 @@
   * in place with one tap; argument errors refused on the host, before any launch;
   * config 3 through TX -> channel -> demod -> decode_mac on the device against the CPU oracle's table;
   * IRS_tranceiver's loop-back through wifi_phy_tx -> x gain -> channel_model -> wifi_phy_rx."""
-import ctypes as C
 import math
 import os
 
@@ -13,51 +12,13 @@ import numpy as np
 import pytest
 
 import channel_ref
+from channel_helpers import NAN_WORD, P, assert_oracle_records, cnoise, loopback, run, rx, tap_sets  # noqa: F401 (rx: fixture)
 from wifirx import capi, txgen
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NAN_WORD = np.uint32(0x7FC0DEAD)
 CFO_20PPM = 2 * np.pi * 20e-6 * 5.89e9 / 20e6
-
-
-@pytest.fixture(scope="module")
-def rx():
-    r = capi.WifiRx(max_sym=1, device=0)
-    yield r
-    r.close()
-
-
-def cnoise(rng, n):
-    return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.5).astype(np.complex64)
-
-
-def run(rx, x, cap, n_rows, out_shift=0, taps=(1.0,), taps_dev=False, **kw):
-    """wifirx_channel from a device copy of x into a NaN-filled buffer (out_shift = 1: 8 bytes past a 16-byte boundary)"""
-    d_in = rx.alloc(max(cap, 1) * 8).upload(x)
-    d_out = rx.alloc((cap + 1) * 8).upload(np.full(2 * (cap + 1), NAN_WORD, np.uint32))
-    t = np.asarray(taps, np.complex64)
-    t = t[None] if t.ndim == 1 else t
-    d_t = None
-    try:
-        if taps_dev:
-            d_t = rx.alloc(t.nbytes).upload(t)
-            rx.channel_dev(d_in.ptr, d_out.ptr + 8 * out_shift, cap, n_rows, taps=d_t.ptr, n_taps=t.shape[1],
-                           n_tap_sets=t.shape[0], **kw)
-        else:
-            rx.channel_dev(d_in.ptr, d_out.ptr + 8 * out_shift, cap, n_rows, taps=t, **kw)
-        y = d_out.download(np.complex64, cap + 1)[out_shift:out_shift + cap]
-    finally:
-        d_in.free()
-        d_out.free()
-        if d_t is not None:
-            d_t.free()
-    return y
-
-
-def tap_sets(rng, n_sets, L):
-    return ((rng.standard_normal((n_sets, L)) + 1j * rng.standard_normal((n_sets, L))) / np.sqrt(2 * L)).astype(np.complex64)
 
 
 @pytest.mark.parametrize("L", [1, 2, 8, 64])
@@ -159,7 +120,6 @@ def test_argument_errors_launch_nothing(rx):
     canary = out.download(np.uint8, cap * 8)
     taps = np.ones((2, 4), np.complex64)
     cfo = np.zeros(n_rows, np.float32)
-    P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
 
     def call(i=-1, o=-1, cap=cap, row_off=None, row_len=row_len, n=n_rows, t=taps, L=4, sets=2, c=cfo, gain=1.0, nv=1.0):
         return lib.wifirx_channel(rx._h, d_in.ptr if i == -1 else i, out.ptr if o == -1 else o, cap, P(row_off), row_len, n,
@@ -197,46 +157,19 @@ def test_argument_errors_launch_nothing(rx):
 C3_SLOT, C3_LEAD, C3_ENC, C3_LEN, C3_FRAMES = 1472, 160, 7, 294, 30000
 
 
-def _config3_run(snr, n, seed):
-    """n distinct config-3 frames through the device chain; returns (frames, psdu rows, psdus, iq of 256 picks, picks)"""
-    psdus = txgen.make_psdus(n, C3_LEN, seed=seed)
-    taps = np.load(os.path.join(GOLD, "sv_taps.npy")).astype(np.complex64)
-    n_sym = txgen.n_sym_for(C3_LEN, C3_ENC)
-    rx = capi.WifiRx(max_sym=n_sym, llr_bits=0, chan_est=capi.EQ_LS, device=0)
-    try:
-        rows = rx.alloc(n * C3_SLOT * 8)
-        rx.tx_batch_dev(rows.ptr, n * C3_SLOT, psdus, C3_ENC, lead=C3_LEAD, row_len=C3_SLOT)
-        iq = rx.alloc(n * C3_SLOT * 8)
-        cfo = np.random.default_rng(seed).uniform(-CFO_20PPM, CFO_20PPM, n).astype(np.float32)
-        rx.channel_dev(rows.ptr, iq.ptr, n * C3_SLOT, n, row_len=C3_SLOT, taps=taps, cfo=cfo,
-                       gain=math.sqrt(10 ** (snr / 10)), noise_voltage=1.0, seed=seed)
-        rows.free()
-        dev = rx.alloc_out(n, psdu_stride=304, want_hbits=True)
-        rx.demod_batch_dev(iq.ptr, C3_SLOT, n, dev)
-        rx.decode_batch_dev(n, dev)
-        rx.sync()
-        r = rx.download_out(dev, n)
-        rx.free_out(dev)
-        pick = np.sort(np.random.default_rng(seed + 1).choice(n, 256, replace=False))
-        x = np.empty((256, C3_SLOT), np.complex64)
-        for i, f in enumerate(pick):
-            rx._check(capi.lib().wifirx_memcpy_d2h(rx._h, x[i].ctypes.data_as(C.c_void_p), iq.ptr + int(f) * C3_SLOT * 8,
-                                                   C3_SLOT * 8))
-        iq.free()
-    finally:
-        rx.close()
-    return r, psdus, x, pick
-
-
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("snr", [25, 30])
 def test_config3_fer_against_the_oracle_table(orc, snr):
     import json
     table = {p["snr_db"]: p for p in json.load(open(os.path.join(GOLD, "config3_ber_table.json")))["points"]}
-    n = C3_FRAMES
-    r, psdus, x, pick = _config3_run(snr, n, 5000 + snr)
-    fr = r["frames"]
-    crc = (fr["flags"] & capi.F_CRC_OK) != 0
+    n, seed = C3_FRAMES, 5000 + snr
+    psdus = txgen.make_psdus(n, C3_LEN, seed=seed)                   # n distinct config-3 frames through the device chain
+    taps = np.load(os.path.join(GOLD, "sv_taps.npy")).astype(np.complex64)
+    cfo = np.random.default_rng(seed).uniform(-CFO_20PPM, CFO_20PPM, n).astype(np.float32)
+    pick = np.sort(np.random.default_rng(seed + 1).choice(n, 256, replace=False))
+    kw = dict(taps=taps, cfo=cfo, gain=math.sqrt(10 ** (snr / 10)), noise_voltage=1.0, seed=seed)
+    (r, x), = loopback(psdus, C3_ENC, C3_LEAD, C3_SLOT, capi.EQ_LS, [kw], psdu_stride=304, pick=pick)
+    crc = (r["frames"]["flags"] & capi.F_CRC_OK) != 0
     own = (r["psdu"][:, :C3_LEN] == psdus).all(axis=1)
     assert own[crc].all(), "a CRC-ok frame carries another PSDU"
     fer = 1.0 - float((crc & own).mean())
@@ -244,12 +177,7 @@ def test_config3_fer_against_the_oracle_table(orc, snr):
     se = math.sqrt(fer * (1 - fer) / n + ref * (1 - ref) / table[snr]["frames"])
     assert abs(fer - ref) <= 4 * se, (snr, fer, ref, se)
     # the records and decisions of a subset against the oracle on the channel's own output
-    n_sym = txgen.n_sym_for(C3_LEN, C3_ENC)
-    o = orc.demod_batch(x.reshape(-1), C3_SLOT, orc.make_params(max_sym=n_sym), n_threads=min(os.cpu_count() or 1, 16))
-    rec = fr[pick].copy()
-    rec["flags"] &= ~np.uint32(capi.F_DECODED | capi.F_CRC_OK)
-    assert np.array_equal(rec, o["frames"])
-    assert np.array_equal(r["idx"][pick], o["idx"])
+    assert_oracle_records(orc, r, x, C3_SLOT, pick, max_sym=txgen.n_sym_for(C3_LEN, C3_ENC))
 
 
 # ---- IRS_tranceiver's loop-back through the blocks ----

@@ -6,55 +6,19 @@
   * the host checks, before anything is queued; the stream block fed in uneven chunks;
   * 64-QAM 2/3 frames of 64 symbols through TX -> channel -> demod -> decode: at 1e-4 cycles per sample the LS equaliser loses
     the link and the STA equaliser keeps it."""
-import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 
 import fading_ref
+from channel_helpers import NAN_WORD, ONE, M64, P, assert_oracle_records, cnoise, loopback, run, rx, same, tap_sets  # noqa: F401 (rx: fixture)
 from wifirx import block, capi, txgen
 
 pytestmark = pytest.mark.gpu
 
-NAN_WORD = np.uint32(0x7FC0DEAD)
-ONE = 1 << 40
 FDS = np.array([0.0, 1e-5, 1e-4, 2.0 ** -10, 3e-4], np.float32)
 TIMES = [0, (1 << 40) + 12345]
-M64 = 0xFFFFFFFFFFFFFFFF
-
-
-@pytest.fixture(scope="module")
-def rx():
-    r = capi.WifiRx(max_sym=1, device=0)
-    yield r
-    r.close()
-
-
-def cnoise(rng, n):
-    return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.5).astype(np.complex64)
-
-
-def tap_sets(rng, n_sets, L):
-    return ((rng.standard_normal((n_sets, L)) + 1j * rng.standard_normal((n_sets, L))) / np.sqrt(2 * L)).astype(np.complex64)
-
-
-def run(rx, x, cap, n_rows, out_shift=0, **kw):
-    """channel_dev from a device copy of x into a NaN-filled buffer (out_shift = 1: 8 bytes past a 16-byte boundary);
-    returns the cap samples at the output pointer"""
-    d_in = rx.alloc(max(cap, 1) * 8).upload(x)
-    d_out = rx.alloc((cap + 1) * 8).upload(np.full(2 * (cap + 1), NAN_WORD, np.uint32))
-    try:
-        rx.channel_dev(d_in.ptr, d_out.ptr + 8 * out_shift, cap, n_rows, **kw)
-        return d_out.download(np.complex64, cap + 1)[out_shift:out_shift + cap]
-    finally:
-        d_in.free()
-        d_out.free()
-
-
-def same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 # ---- 1. noiseless, value for value ----
@@ -122,7 +86,6 @@ def test_null_doppler_is_wifirx_channel_sro(rx, with_sro):
     t = np.ascontiguousarray(tap_sets(rng, 2, L))
     c = rng.uniform(-0.05, 0.05, n_rows).astype(np.float32)
     s = np.array([20e-6, -20e-6, 2.0 ** -8, 0.0, -2.0 ** -8], np.float32) if with_sro else None
-    P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
     lib = capi.lib()
     d_in = rx.alloc(x.nbytes).upload(x)
     outs = []
@@ -177,7 +140,6 @@ def test_host_checks_queue_nothing(rx):
     out = rx.alloc(cap * 8).upload(np.full(2 * cap, NAN_WORD, np.uint32))
     canary = out.download(np.uint8, cap * 8)
     taps = np.full((1, 17), 0.25, np.complex64)
-    P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
 
     def call(fd, k_factor=0.0, n_taps=1, i=None, o=None, sro=None):
         t = np.ascontiguousarray(taps[:, :n_taps])
@@ -252,43 +214,18 @@ def test_block_in_uneven_chunks_equals_one_call(rx):
 def test_doppler_breaks_ls_and_not_sta_on_the_device(orc):
     e = fading_ref.E2E
     n, enc, plen, lead = e["n"], e["enc"], e["plen"], e["lead"]
-    n_sym = txgen.n_sym_for(plen, enc)
     slot = lead + txgen.frame_samples(plen, enc) + 79
     psdus = txgen.make_psdus(n, plen, seed=e["psdu_seed"])
-    good, rows_out, recs = {}, {}, {}
+    res = {}
     for name, fd, eq in fading_ref.ARMS:
-        rx = capi.WifiRx(max_sym=n_sym, llr_bits=0, chan_est=eq, device=0)
-        try:
-            rows = rx.alloc(n * slot * 8)
-            rx.tx_batch_dev(rows.ptr, n * slot, psdus, enc, lead=lead, row_len=slot)
-            iq = rx.alloc(n * slot * 8)
-            rx.channel_dev(rows.ptr, iq.ptr, n * slot, n, row_len=slot, gain=math.sqrt(10 ** (e["snr_db"] / 10)), noise_voltage=1.0,
-                           seed=e["seed"], doppler=fd, k_factor=e["k_factor"], fade_seed=e["fade_seed"])
-            dev = rx.alloc_out(n, psdu_stride=1536, want_hbits=True)
-            rx.demod_batch_dev(iq.ptr, slot, n, dev)
-            rx.decode_batch_dev(n, dev)
-            rx.sync()
-            r = rx.download_out(dev, n)
-            rx.free_out(dev)
-            fr = r["frames"]
-            crc = (fr["flags"] & capi.F_CRC_OK) != 0
-            assert (r["psdu"][crc][:, :plen] == psdus[crc]).all(), "an FCS-good frame carries another PSDU"
-            good[name] = int(crc.sum())
-            rows_out[name] = iq.download(np.complex64, n * slot)
-            recs[name] = (fr.copy(), r["idx"].copy())
-            rows.free()
-            iq.free()
-        finally:
-            rx.close()
+        kw = dict(gain=math.sqrt(10 ** (e["snr_db"] / 10)), noise_voltage=1.0, seed=e["seed"], doppler=fd, k_factor=e["k_factor"],
+                  fade_seed=e["fade_seed"])
+        res[name], = loopback(psdus, enc, lead, slot, eq, [kw], psdu_stride=1536)
+    good = {name: int(((r["frames"]["flags"] & capi.F_CRC_OK) != 0).sum()) for name, (r, _) in res.items()}
     print("FCS-good of %d: %r" % (n, good))
     assert good["fd 1e-4, LS"] <= 15
     assert good["fd 1e-4, STA"] >= 40
     assert good["fd 0, LS"] >= 40
     # the records and decisions of the downloaded rows equal the oracle's
     for name, fd, eq in fading_ref.ARMS:
-        prm = orc.make_params(max_sym=n_sym, chan_est=eq)
-        o = orc.demod_batch(rows_out[name], slot, prm, n_threads=min(os.cpu_count() or 1, 16))
-        rec = recs[name][0].copy()
-        rec["flags"] &= ~np.uint32(capi.F_DECODED | capi.F_CRC_OK)
-        assert np.array_equal(rec, o["frames"]), name
-        assert np.array_equal(recs[name][1], o["idx"]), name
+        assert_oracle_records(orc, *res[name], slot, msg=name, max_sym=txgen.n_sym_for(plen, enc), chan_est=eq)

@@ -6,51 +6,19 @@
   * the host checks, before anything is queued; a row cut into two calls;
   * 64-QAM 3/4 frames of 57 symbols at +-20 ppm through TX -> channel -> demod -> decode with the LS equaliser: they
     decode with the sample clock locked to the carrier and not without."""
-import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 
-import channel_ref
 import resample_ref
+from channel_helpers import NAN_WORD, ONE, M64, P, assert_oracle_records, cnoise, loopback, run, rx, tap_sets  # noqa: F401 (rx: fixture)
 from wifirx import capi, txgen
 
 pytestmark = pytest.mark.gpu
 
-NAN_WORD = np.uint32(0x7FC0DEAD)
-ONE = 1 << 40
 SROS = np.array([0.0, 20e-6, -20e-6, 2.0 ** -8, -2.0 ** -8], np.float32)
 DRIFTS = [0, int(0.37 * ONE) + 12345, -(3 * ONE + ONE // 4)]
-
-
-@pytest.fixture(scope="module")
-def rx():
-    r = capi.WifiRx(max_sym=1, device=0)
-    yield r
-    r.close()
-
-
-def cnoise(rng, n):
-    return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.5).astype(np.complex64)
-
-
-def tap_sets(rng, n_sets, L):
-    return ((rng.standard_normal((n_sets, L)) + 1j * rng.standard_normal((n_sets, L))) / np.sqrt(2 * L)).astype(np.complex64)
-
-
-def run(rx, x, cap, n_rows, out_shift=0, **kw):
-    """channel_dev from a device copy of x into a NaN-filled buffer (out_shift = 1: 8 bytes past a 16-byte boundary);
-    returns the cap samples at the output pointer"""
-    d_in = rx.alloc(max(cap, 1) * 8).upload(x)
-    d_out = rx.alloc((cap + 1) * 8).upload(np.full(2 * (cap + 1), NAN_WORD, np.uint32))
-    try:
-        rx.channel_dev(d_in.ptr, d_out.ptr + 8 * out_shift, cap, n_rows, **kw)
-        return d_out.download(np.complex64, cap + 1)[out_shift:out_shift + cap]
-    finally:
-        d_in.free()
-        d_out.free()
 
 
 @pytest.fixture(scope="module")
@@ -130,8 +98,8 @@ def test_no_resampling_is_wifirx_channel(rx, L):
     d_in = rx.alloc(x.nbytes).upload(x)
     d_out = rx.alloc(x.nbytes).upload(np.full(2 * x.size, NAN_WORD, np.uint32))
     t, c = np.ascontiguousarray(kw["taps"]), kw["cfo"]
-    rc = capi.lib().wifirx_channel_sro(rx._h, d_in.ptr, d_out.ptr, x.size, None, row_len, n_rows, t.ctypes.data_as(C.c_void_p), 0,
-                                       L, 2, c.ctypes.data_as(C.c_void_p), 99, None, 123456789, 1.7, 0.4, 3, 5)
+    rc = capi.lib().wifirx_channel_sro(rx._h, d_in.ptr, d_out.ptr, x.size, None, row_len, n_rows, P(t), 0, L, 2, P(c), 99, None,
+                                       123456789, 1.7, 0.4, 3, 5)
     assert rc == capi.OK
     null = d_out.download(np.complex64, x.size)
     d_in.free()
@@ -147,7 +115,6 @@ def test_host_checks_queue_nothing(rx):
     out = rx.alloc(cap * 8).upload(np.full(2 * cap, NAN_WORD, np.uint32))
     canary = out.download(np.uint8, cap * 8)
     taps = np.ones((1, 1), np.complex64)
-    P = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
 
     def call(sro, i=None, o=None, drift0=0, row_off=None):
         return lib.wifirx_channel_sro(rx._h, d_in.ptr if i is None else i, out.ptr if o is None else o, cap, P(row_off), row_len,
@@ -201,7 +168,7 @@ def test_cut_invariance_on_the_device(rx, n_taps):
         dinc = capi.drift_inc(s)
         kw = dict(taps=taps, cfo=cfo, sro=s, gain=1.5, noise_voltage=0.3, seed=5)
         one = run(rx, x, n, 1, row_len=n, phase0=7, drift0=d0, **kw)
-        part = run(rx, x[k:], n - k, 1, row_len=n - k, phase0=(7 + inc * k) & 0xFFFFFFFFFFFFFFFF, drift0=d0 + dinc * k,
+        part = run(rx, x[k:], n - k, 1, row_len=n - k, phase0=(7 + inc * k) & M64, drift0=d0 + dinc * k,
                    sample0=k, **kw)
         assert part[halo:].tobytes() == one[k + halo:].tobytes(), float(s)
 
@@ -210,43 +177,16 @@ def test_cut_invariance_on_the_device(rx, n_taps):
 
 def test_long_frames_decode_with_the_locked_clock_only(orc):
     n, enc, plen, lead = 48, 7, 1528, 160
-    n_sym = txgen.n_sym_for(plen, enc)
     slot = lead + txgen.frame_samples(plen, enc) + 79
     psdus = txgen.make_psdus(n, plen, seed=18)
     cfo = np.where(np.arange(n) % 2 == 0, 0.037, -0.037).astype(np.float32)
-    rx = capi.WifiRx(max_sym=n_sym, llr_bits=0, chan_est=capi.EQ_LS, device=0)
-    good, rows_out, recs = {}, {}, {}
-    try:
-        rows = rx.alloc(n * slot * 8)
-        rx.tx_batch_dev(rows.ptr, n * slot, psdus, enc, lead=lead, row_len=slot)
-        iq = rx.alloc(n * slot * 8)
-        for name, sro in (("locked", capi.locked_sro(cfo)), ("unlocked", None)):
-            rx.channel_dev(rows.ptr, iq.ptr, n * slot, n, row_len=slot, cfo=cfo, sro=sro, gain=math.sqrt(10 ** 3.2),
-                           noise_voltage=1.0, seed=32)
-            dev = rx.alloc_out(n, psdu_stride=1536, want_hbits=True)
-            rx.demod_batch_dev(iq.ptr, slot, n, dev)
-            rx.decode_batch_dev(n, dev)
-            rx.sync()
-            r = rx.download_out(dev, n)
-            rx.free_out(dev)
-            fr = r["frames"]
-            crc = (fr["flags"] & capi.F_CRC_OK) != 0
-            assert (r["psdu"][crc][:, :plen] == psdus[crc]).all(), "an FCS-good frame carries another PSDU"
-            good[name] = int(crc.sum())
-            rows_out[name] = iq.download(np.complex64, n * slot)
-            recs[name] = (fr.copy(), r["idx"].copy())
-        rows.free()
-        iq.free()
-    finally:
-        rx.close()
+    arms = {"locked": capi.locked_sro(cfo), "unlocked": None}
+    res = loopback(psdus, enc, lead, slot, capi.EQ_LS, psdu_stride=1536, channels=[
+        dict(cfo=cfo, sro=sro, gain=math.sqrt(10 ** 3.2), noise_voltage=1.0, seed=32) for sro in arms.values()])
+    good = {name: int(((r["frames"]["flags"] & capi.F_CRC_OK) != 0).sum()) for name, (r, _) in zip(arms, res)}
     print("FCS-good of %d: %r" % (n, good))
     assert good["locked"] >= 45
     assert good["unlocked"] <= 3
     # the records of the downloaded rows equal the oracle's
-    prm = orc.make_params(max_sym=n_sym, chan_est=capi.EQ_LS)
-    for name in ("locked", "unlocked"):
-        o = orc.demod_batch(rows_out[name], slot, prm, n_threads=min(os.cpu_count() or 1, 16))
-        rec = recs[name][0].copy()
-        rec["flags"] &= ~np.uint32(capi.F_DECODED | capi.F_CRC_OK)
-        assert np.array_equal(rec, o["frames"]), name
-        assert np.array_equal(recs[name][1], o["idx"]), name
+    for name, (r, x) in zip(arms, res):
+        assert_oracle_records(orc, r, x, slot, msg=name, max_sym=txgen.n_sym_for(plen, enc), chan_est=capi.EQ_LS)
