@@ -5,6 +5,11 @@
 driven by the scheduler stand-in of wifirx.grshim.
 
     python examples/irs_ap_file_rx.py in.c64 out.png [--bandwidth 20e6] [--chan-est 0]
+    python examples/irs_ap_file_rx.py in.sc8 out.png --format sc8 [--scale S]
+
+--format sc16 / sc8: the file holds int16 / int8 pairs (a UHD sc16 recording, hackrf_transfer's output).  It is read in
+its own dtype and handed to the block as it is -- no float copy is built on the host; the samples are widened on the
+device (value = integer * scale; default 2^-15 / 2^-7).
 """
 import argparse
 import os
@@ -25,8 +30,14 @@ def main():
     ap.add_argument("--frequency", type=float, default=5.89e9)
     ap.add_argument("--chan-est", type=int, default=block.LS)
     ap.add_argument("--chunk", type=int, default=1 << 20)
+    ap.add_argument("--format", choices=("fc32", "sc16", "sc8"), default="fc32")
+    ap.add_argument("--scale", type=float, default=None, help="integer formats: value of one integer step")
     a = ap.parse_args()
-    x = np.fromfile(a.iq, dtype=np.complex64)
+    if a.format == "fc32":
+        x = np.fromfile(a.iq, dtype=np.complex64)
+    else:
+        x = np.fromfile(a.iq, dtype=np.int16 if a.format == "sc16" else np.int8)
+        x = x[:x.size // 2 * 2].reshape(-1, 2)
     img = np.zeros((300, 300, 3), np.uint8)
     n = [0]
 
@@ -34,7 +45,8 @@ def main():
         app.redraw_image(app.load_piece(data), img)
         n[0] += 1
 
-    rx = block.wifi_phy_rx(bandwidth=a.bandwidth, frequency=a.frequency, chan_est=a.chan_est, publish_carrier=False)
+    rx = block.wifi_phy_rx(bandwidth=a.bandwidth, frequency=a.frequency, chan_est=a.chan_est, publish_carrier=False,
+                           sample_format=a.format, sample_scale=a.scale)
     pics = app.extract_pics(sink=on_piece)
     grshim.msg_connect(rx, "mac_out", pics, "MAC")
     grshim.run_stream(rx, x, chunk=a.chunk)

@@ -2,9 +2,12 @@
 """TX side of BASELINE.json config 1 without an SDR: image -> pieces in the reference's wire format
 (upload_image_udp.py:19-34) -> ieee802_11.mac framing -> 802.11a frames (wifirx.txgen, CPU) -> x0.5 gain and
 packet_pad2(100, 1000) as in gnu_radio/IRS_user.py:193-196 -> unit-variance AWGN at the given SNR ->
-interleaved float32 I/Q file (GNU Radio file_sink format) that examples/irs_ap_file_rx.py receives.
+interleaved float32 I/Q file (GNU Radio file_sink format) that examples/irs_ap_file_rx.py receives.  With --format sc16 / sc8
+the samples are quantised on the host (NUMERICS.md rule 20) with full scale --backoff-db above their RMS and written as
+int16 / int8 pairs: a UHD sc16 recording, or what hackrf_transfer writes; the scale that widens them again is printed.
 
     python examples/make_iq_file.py image.png out.c64 [--encoding 0] [--snr 20] [--pieces 1000]
+    python examples/make_iq_file.py kodim01 out.sc8 --format sc8 --backoff-db 12
 """
 import argparse
 import os
@@ -24,6 +27,8 @@ def main():
     ap.add_argument("--encoding", type=int, default=0)
     ap.add_argument("--snr", type=float, default=20.0)
     ap.add_argument("--pieces", type=int, default=0, help="first N pieces only (0 = all 2700)")
+    ap.add_argument("--format", choices=("fc32", "sc16", "sc8"), default="fc32")
+    ap.add_argument("--backoff-db", type=float, default=12.0, help="integer formats: full scale above the RMS of the samples")
     a = ap.parse_args()
     gold = os.path.join(ROOT, "tests", "golden", "kodim_300.npz")
     if os.path.exists(a.image):
@@ -48,8 +53,16 @@ def main():
     x = np.concatenate([np.concatenate([np.zeros(100, np.complex64), b, np.zeros(1000, np.complex64)]) for b in bursts])
     rng = np.random.default_rng(0)
     x = (x + (rng.standard_normal(x.size) + 1j * rng.standard_normal(x.size)) * np.sqrt(0.5)).astype(np.complex64)
-    x.tofile(a.out)
-    print("%d frames, %d samples (%.1f MB) -> %s" % (len(bursts), x.size, x.nbytes / 1e6, a.out))
+    if a.format != "fc32":
+        scale = txgen.iq_full_scale(x, a.backoff_db, a.format)
+        q, clipped = txgen.quantise_iq(x, a.format, scale)
+        q.tofile(a.out)
+        print("%s, full scale %.1f dB above the RMS: %d of %d components clipped; receive with --format %s --scale %.9g"
+              % (a.format, a.backoff_db, clipped, q.size, a.format, 1.0 / float(scale)))
+        x = q
+    else:
+        x.tofile(a.out)
+    print("%d frames, %d samples (%.1f MB) -> %s" % (len(bursts), len(x), x.nbytes / 1e6, a.out))
 
 
 if __name__ == "__main__":

@@ -27,6 +27,7 @@
 #include "wr_tx.h"
 #include "wr_channel.h"
 #include "wr_link.h"
+#include "wr_convert.h"
 
 // The stream's per-frame outputs (stream_outs, wifirx_api_stream.inc) and the host copy of a batch of them, shared by its
 // frames: output o of frame k is the width[o] bytes at blob[off[o] + k * width[o]] (width 0: the handle did not produce o).
@@ -117,6 +118,7 @@ struct Staging {
     DevBuf ch_meta;                 // wifirx_channel: host taps, phase increments, row offsets, tile bases
     DevBuf link_meta, link_payload; // wifirx_mac_batch: payload lengths; host payloads
     DevBuf link_counts;             // wifirx_link_stats: the nine counters
+    DevBuf iq_clipped;              // wifirx_iq_from_f32: the counter of clipped components
 };
 
 // decode workspace
@@ -129,6 +131,7 @@ struct DecodeWork {
 // stream mode (wifirx_api_stream.inc)
 struct StreamState {
     DevBuf   sbuf;                  // device sample buffer of sbuf_cap samples
+    DevBuf   native;                // wifirx_push_iq: a pass's host samples in their integer format, widened from here into sbuf
     DevBuf   above, A;              // the detection side buffers, sized by sbuf_cap too
     int64_t  sbuf_cap = 0;
     int64_t  sbase = 0;             // absolute index of sbuf[0] (multiple of 64)
@@ -149,8 +152,9 @@ struct StreamState {
     size_t   push_consumed = 0;     // wifirx_push_consumed
 };
 
-// A batch handed to the worker: `n` samples at `ptr` (a ring buffer), and whether it ends with a flush
-struct Job { const float* ptr; size_t n; bool flush; };
+// A batch handed to the worker: `n` samples of format `fmt` (WIFIRX_IQ_*; `scale` widens the integer ones) at `ptr` (a ring
+// buffer), and whether it ends with a flush
+struct Job { const void* ptr; size_t n; bool flush; int fmt; float scale; };
 
 // Host-buffer stream path (what a GNU Radio work() drives; wifirx_api_stream.inc): pushes are copied into one of two
 // pinned staging buffers of one batch each; a full one is handed to the worker thread, which runs the device pipeline
@@ -166,6 +170,7 @@ struct Worker {
     int     rc = 0;                     std::string err;     // first failure of a batch, reported by the next call
     std::string err_local;              // the worker's own error text (only the worker writes it; h->err belongs to the caller's thread)
     PinnedBuf ring[2];                  size_t ring_cap = 0, ring_fill = 0;   int ring_cur = 0;
+    int     ring_fmt = WIFIRX_IQ_FC32;  float ring_scale = 1.0f;            // format of the samples staged in ring[ring_cur]
 };
 
 }  // namespace
@@ -178,6 +183,7 @@ struct wifirx_handle {
     Environment   env;
     int           device = 0;
     uint32_t      n_simd = 1024;    // SIMDs of the device (4 per CU): sizes the speculative trace-back's launch
+    uint32_t      n_cu = 256;       // CUs of the device: sizes the grids of the format converters
     hipStream_t   stream = nullptr;
     std::string   err;
     wifirx_stats  stats{};
@@ -288,6 +294,7 @@ int wifirx_create(const wifirx_config* cfg, wifirx_handle** out)
     h->cfg = *cfg;
     h->device = cfg->device;
     h->n_simd = 4u * (uint32_t)prop.multiProcessorCount;
+    h->n_cu = (uint32_t)prop.multiProcessorCount;
     const int prio = read_environment(h);
     if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio) != hipSuccess) {
         delete h;
@@ -595,3 +602,4 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_tx.inc"
 #include "wifirx_api_channel.inc"
 #include "wifirx_api_link.inc"
+#include "wifirx_api_convert.inc"

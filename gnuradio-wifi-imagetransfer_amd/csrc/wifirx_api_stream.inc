@@ -43,6 +43,13 @@ int stream_reserve(wifirx_handle* h, int64_t need)
     return WIFIRX_OK;
 }
 
+// wifirx_push_iq, host input: room for a pass's samples in their integer format (grows like the sample buffer)
+int stream_native_reserve(wifirx_handle* h, size_t need)
+{
+    if (h->st.native.bytes >= need) return WIFIRX_OK;
+    return stream_alloc(h, h->st.native, need + need / 2, "hipMalloc(stream native samples)");
+}
+
 // Output rows of the frame kernel + decode_mac for up to `n` triggers.  The capacity is zero while the buffers are
 // being replaced, so a failed allocation leaves "no buffers, capacity 0" and the next push allocates again.
 int stream_out_reserve(wifirx_handle* h, uint32_t n)
@@ -334,9 +341,11 @@ static void stream_carry(wifirx_handle* h, StageClock& stage)
     stage("carry");
 }
 
-// One pass of the stream pipeline over `n` more samples (what every push was before the staging ring existed).
+// One pass of the stream pipeline over `n` more samples of format `fmt` (what every push was before the staging ring existed).
+// Integer samples (NUMERICS.md rule 20) are widened into the sample buffer by a launch in front of the detection: from the
+// caller's device buffer, or from the handle's scratch buffer, which host samples cross the bus into in their native format.
 // All or nothing: on an error return the handle's stream state is what it was before the call.
-static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on_device, bool flush)
+static int stream_process(wifirx_handle* h, const void* iq, size_t n, int iq_on_device, bool flush, int fmt, float scale)
 {
     StageClock stage;
     StreamState& st = h->st;
@@ -344,10 +353,23 @@ static int stream_process(wifirx_handle* h, const float* iq, size_t n, int iq_on
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = stream_reserve(h, st.sfill + (int64_t)n + 64);
     if (rc) return rc;
+    const uint32_t bps = wr_iq_sample_bytes(fmt);       // 0: float pairs
+    // the scratch copy starts where its first whole 16-byte piece, behind the widen kernel's head sample, is 16-byte aligned
+    const size_t native_off = bps ? (16 - (size_t)(st.sfill & 1) * bps) & 15 : 0;
+    if (n && bps && !iq_on_device && (rc = stream_native_reserve(h, native_off + n * bps))) return rc;
     StreamRollback undo(h);
-    if (n) {
+    if (n && bps) {
+        const void* d_native = iq;
+        if (!iq_on_device) {
+            d_native = st.native.as<uint8_t>() + native_off;
+            HIP_TRY(h, hipMemcpyAsync(st.native.as<uint8_t>() + native_off, iq, n * bps, hipMemcpyHostToDevice, h->stream));
+        }
+        HIP_TRY(h, wr_launch_iq_widen(h->stream, d_native, fmt, n, scale, st.sbuf.as<float2>() + st.sfill, h->n_cu));
+    } else if (n) {
         HIP_TRY(h, hipMemcpyAsync(st.sbuf.as<float2>() + st.sfill, iq, n * sizeof(float2),
                                   iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    }
+    if (n) {
         st.sfill += (int64_t)n;
         { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.samples_in += n; }
     }
@@ -380,7 +402,7 @@ static void stream_worker_main(wifirx_handle* h)
         lk.unlock();
         int rc;
         try {
-            rc = stream_process(h, job.ptr, job.n, 0, job.flush);
+            rc = stream_process(h, job.ptr, job.n, 0, job.flush, job.fmt, job.scale);
         } catch (const std::exception& e) {          // nothing may escape a thread (or the C boundary)
             rc = WIFIRX_ENOMEM;
             w.err_local = std::string("stream worker: ") + e.what();
@@ -451,7 +473,7 @@ static int stream_submit(wifirx_handle* h, bool flush)
     {
         std::unique_lock<std::mutex> lk(w.mu);
         w.cv.wait(lk, [&] { return !w.busy; });
-        w.job = Job{ w.ring[w.ring_cur].as<const float>(), w.ring_fill, flush };
+        w.job = Job{ w.ring[w.ring_cur].p, w.ring_fill, flush, w.ring_fmt, w.ring_scale };
         w.busy = true;
         w.cv.notify_all();
     }
@@ -501,9 +523,9 @@ static int stream_drain_staged(wifirx_handle* h)
     return stream_worker_take_error(h);
 }
 
-extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_on_device)
+// wifirx_push and wifirx_push_iq behind their checks: `n` samples of format `fmt` (n = 0: flush)
+static int stream_push(wifirx_handle* h, const void* iq, size_t n, int fmt, float scale, int iq_on_device)
 {
-    if (!h) return WIFIRX_EINVAL;
     h->st.push_consumed = 0;
     if (n > 0 && !iq) return fail(h, WIFIRX_EINVAL, "iq is null");
     const bool flush = (n == 0);
@@ -512,7 +534,7 @@ extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_o
         const int drc = stream_drain_staged(h);                   // samples staged before the mode changed
         if (drc) return drc;
         try {
-            const int rc = stream_process(h, iq, n, iq_on_device, flush);
+            const int rc = stream_process(h, iq, n, iq_on_device, flush, fmt, scale);
             if (rc == WIFIRX_OK) h->st.push_consumed = n;
             return rc;
         } catch (const std::exception& e) {
@@ -542,6 +564,14 @@ extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_o
         w.ring_cap = cap;
         w.ring_cur = 0;
     }
+    // one format and scale per staged batch: what is staged in another runs first, as a short batch (the ring's bytes were
+    // sized for float pairs, the widest format)
+    const uint32_t bps = fmt == WIFIRX_IQ_FC32 ? (uint32_t)sizeof(float2) : wr_iq_sample_bytes(fmt);
+    if (n && (w.ring_fmt != fmt || (fmt != WIFIRX_IQ_FC32 && w.ring_scale != scale))) {
+        if (w.ring_fill && (rc = stream_drain_staged(h))) return rc;
+        w.ring_fmt = fmt;
+        w.ring_scale = scale;
+    }
     if (!w.thread.joinable()) {
         w.stop = false;
         try {
@@ -550,7 +580,7 @@ extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_o
             return fail(h, WIFIRX_ENOMEM, std::string("cannot start the stream worker thread: ") + e.what());
         }
     }
-    const float2* src = reinterpret_cast<const float2*>(iq);
+    const uint8_t* src = static_cast<const uint8_t*>(iq);
     for (;;) {
         if (w.ring_fill == cap) {
             // hand-over.  The batch before this one must be through first (the worker takes one at a time); if it failed
@@ -562,10 +592,10 @@ extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_o
         }
         if (!n) break;
         const size_t take = std::min(n, cap - w.ring_fill);
-        stage_copy(w.ring[w.ring_cur].as<float2>() + w.ring_fill, src, take * sizeof(float2));
+        stage_copy(w.ring[w.ring_cur].as<uint8_t>() + w.ring_fill * bps, src, take * bps);
         w.ring_fill += take;
         h->st.push_consumed += take;
-        src += take;
+        src += take * bps;
         n -= take;
     }
     if (flush) {
@@ -574,6 +604,12 @@ extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_o
         return stream_worker_take_error(h);     // on a failure the flush batch stays staged (retry slot): flush again
     }
     return WIFIRX_OK;
+}
+
+extern "C" int wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_on_device)
+{
+    if (!h) return WIFIRX_EINVAL;
+    return stream_push(h, iq, n, WIFIRX_IQ_FC32, 1.0f, iq_on_device);
 }
 
 extern "C" uint32_t wifirx_queued(const wifirx_handle* h) { return h ? h->st.n_queued.load(std::memory_order_acquire) : 0; }

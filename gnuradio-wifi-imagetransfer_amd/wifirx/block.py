@@ -36,8 +36,17 @@ LINKTYPE_IEEE802_11 = 105
 class wifi_phy_rx(grshim.sync_block):
     def __init__(self, bandwidth=10e6, chan_est=LS, encoding=0, frequency=5.89e9, sensitivity=0.56,
                  max_sym=511, publish_carrier=True, device=0, batch_samples=None, publish_csi=False, snr_probe=None,
-                 soft_decision=False):
-        grshim.sync_block.__init__(self, name="wifi_phy_rx", in_sig=[np.complex64], out_sig=None)
+                 soft_decision=False, sample_format="fc32", sample_scale=None):
+        # sample_format: "fc32" (complex64 items, the default), or "sc16" / "sc8": items of two int16 / int8 (I, Q), the form
+        # a UHD source with an sc16 CPU format delivers; they cross the bus as they are and are widened on the device
+        # (value = integer * sample_scale, default 2^-15 / 2^-7; wifirx_push_iq, NUMERICS.md rule 20)
+        self.sample_format = capi.iq_format(sample_format)
+        if self.sample_format not in capi.IQ_DTYPE:
+            raise ValueError("sample_format must be 'fc32', 'sc16' or 'sc8'")
+        self.sample_scale = float(capi.IQ_SCALE[self.sample_format] if sample_scale is None else sample_scale)
+        self._item = capi.IQ_DTYPE[self.sample_format]
+        in_sig = [np.complex64] if self.sample_format == capi.IQ_FC32 else [(self._item.type, 2)]
+        grshim.sync_block.__init__(self, name="wifi_phy_rx", in_sig=in_sig, out_sig=None)
         self.bandwidth = float(bandwidth)
         self.chan_est = int(chan_est)
         self.encoding = encoding            # TX-side parameter of the hier block: accepted, unused on RX
@@ -74,6 +83,9 @@ class wifi_phy_rx(grshim.sync_block):
         if soft_decision:
             self.set_soft_decision(True)
         self._push = capi.lib().wifirx_push
+        if self.sample_format != capi.IQ_FC32:
+            push_iq, fmt, scale = capi.lib().wifirx_push_iq, self.sample_format, self.sample_scale
+            self._push = lambda h, buf, n, on_device: push_iq(h, buf, n, fmt, scale, on_device)
         self._queued = capi.lib().wifirx_queued
         self._h = self._rx._h
         self._p_mac = grshim.intern("mac_out")
@@ -140,8 +152,8 @@ class wifi_phy_rx(grshim.sync_block):
         x = input_items[0]
         n = len(x)
         if n:
-            if x.dtype != _C64 or not x.flags.c_contiguous:
-                x = np.ascontiguousarray(x, dtype=np.complex64)
+            if x.dtype != self._item or not x.flags.c_contiguous:
+                x = np.ascontiguousarray(x, dtype=self._item)
             try:
                 buf = _ANCHOR.from_buffer(x)                 # the address of x's data, without building a dict
             except (TypeError, ValueError):                  # read-only input: the slower route

@@ -24,6 +24,11 @@ P_STREAM_SOFT = 9                   # stream mode: decode_mac on LLRs (wifirx_de
 P_LLR_FORMAT = 10                   # LLR format of the batch calls (NUMERICS.md rule 15); stream mode keeps float32
 LLR_F32, LLR_BF16 = 0, 1            # WIFIRX_LLR_*
 _LLR_FORMATS = {"f32": LLR_F32, "bf16": LLR_BF16}
+IQ_FC32, IQ_SC16, IQ_SC8 = 0, 1, 2  # WIFIRX_IQ_*: sample formats (NUMERICS.md rule 20)
+IQ_FORMATS = {"fc32": IQ_FC32, "sc16": IQ_SC16, "sc8": IQ_SC8}
+IQ_DTYPE = {IQ_FC32: np.dtype(np.complex64), IQ_SC16: np.dtype(np.int16), IQ_SC8: np.dtype(np.int8)}     # sc16 / sc8: two items per sample
+IQ_SCALE = {IQ_FC32: 1.0, IQ_SC16: 2.0 ** -15, IQ_SC8: 2.0 ** -7}      # the conventional widening scales
+IQ_MAX_BITS = {IQ_SC16: 16, IQ_SC8: 8}
 F_DETECTED, F_SYNC, F_SIGNAL, F_COMPLETE, F_LLR, F_DECODED, F_CRC_OK = 1, 2, 4, 8, 16, 32, 64
 
 FRAME_DTYPE = np.dtype([
@@ -42,6 +47,7 @@ EXPORTS = [
     "wifirx_push_consumed", "wifirx_queued", "wifirx_decode_batch_soft", "wifirx_tx_batch", "wifirx_channel",
     "wifirx_mac_batch", "wifirx_link_stats", "wifirx_tx_batch_rates", "wifirx_link_stats_by_rate",
     "wifirx_channel_sro", "wifirx_resampler_table", "wifirx_channel_fading",
+    "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
 ]
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
@@ -197,6 +203,10 @@ _lib.wifirx_link_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.POI
                                    C.POINTER(LinkCounts)]
 _lib.wifirx_link_stats_by_rate.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.POINTER(Out), C.c_void_p, C.c_void_p,
                                            C.POINTER(LinkCounts), C.POINTER(LinkCounts)]
+_lib.wifirx_iq_to_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_float, C.c_void_p]
+_lib.wifirx_iq_from_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.c_uint32, C.c_void_p,
+                                    C.POINTER(C.c_uint64)]
+_lib.wifirx_push_iq.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -207,6 +217,15 @@ _lib.wifirx_time_demod.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint3
 
 def lib():
     return _lib
+
+
+def iq_format(fmt) -> int:
+    """"fc32" / "sc16" / "sc8" or IQ_FC32 / IQ_SC16 / IQ_SC8 -> the WIFIRX_IQ_* value"""
+    if isinstance(fmt, str):
+        if fmt not in IQ_FORMATS:
+            raise ValueError("sample format must be 'fc32', 'sc16' or 'sc8'")
+        return IQ_FORMATS[fmt]
+    return int(fmt)
 
 
 def _np_ptr(a):
@@ -701,10 +720,88 @@ class WifiRx:
             r["frame_err"], r["frame_class"] = d_err, d_cls
         return r
 
+    # -- sample formats (wifirx_iq_to_f32, wifirx_iq_from_f32; NUMERICS.md rule 20) --
+    def iq_to_f32_dev(self, src_ptr, fmt, n, dst_ptr, scale=None):
+        """wifirx_iq_to_f32 on device pointers: n samples of `fmt` at src_ptr -> complex64 at dst_ptr.  Asynchronous on the
+        handle's stream."""
+        fmt = iq_format(fmt)
+        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
+        self._check(_lib.wifirx_iq_to_f32(self._h, src_ptr, fmt, int(n), float(scale), dst_ptr))
+
+    def iq_from_f32_dev(self, src_ptr, n, fmt, dst_ptr, scale=None, bits=None, count=False):
+        """wifirx_iq_from_f32 on device pointers: n complex64 samples at src_ptr -> samples of `fmt` at dst_ptr, quantised to
+        `bits` bits (default: the container's).  scale defaults to the inverse of the conventional widening scale.
+        count=True waits and returns the number of clipped components; otherwise asynchronous, returns None."""
+        fmt = iq_format(fmt)
+        scale = 1.0 / IQ_SCALE.get(fmt, 1.0) if scale is None else scale
+        bits = IQ_MAX_BITS.get(fmt, 0) if bits is None else bits
+        c = C.c_uint64(0)
+        self._check(_lib.wifirx_iq_from_f32(self._h, src_ptr, int(n), float(scale), fmt, int(bits), dst_ptr,
+                                            C.byref(c) if count else None))
+        return int(c.value) if count else None
+
+    @staticmethod
+    def _iq_array(x, fmt=None):
+        """int16 / int8 samples as [n, 2] or flat [2 n] -> (contiguous flat array, format, n)"""
+        x = np.asarray(x)
+        if fmt is None:
+            fmt = {np.dtype(np.int16): IQ_SC16, np.dtype(np.int8): IQ_SC8}.get(x.dtype)
+            if fmt is None:
+                raise ValueError("the sample format is taken from int16 or int8 arrays only")
+        fmt = iq_format(fmt)
+        if fmt in IQ_MAX_BITS:
+            if x.dtype != IQ_DTYPE[fmt]:
+                raise ValueError("%s samples must be %s" % ({IQ_SC16: "sc16", IQ_SC8: "sc8"}[fmt], IQ_DTYPE[fmt]))
+            if not (x.ndim == 1 or (x.ndim == 2 and x.shape[1] == 2)) or x.size % 2:
+                raise ValueError("integer samples come as [n, 2] or flat [2 n]")
+        x = np.ascontiguousarray(x).reshape(-1)
+        return x, fmt, x.size // 2 if fmt in IQ_MAX_BITS else x.size
+
+    def iq_to_f32(self, q, fmt=None, scale=None) -> np.ndarray:
+        """iq_to_f32_dev on a NumPy array of int16 / int8 samples ([n, 2] or flat [2 n]): returns complex64 [n]"""
+        q, fmt, n = self._iq_array(q, fmt)
+        d_in, d_out = self.alloc(max(q.nbytes, 1)), self.alloc(max(n, 1) * 8)
+        try:
+            d_in.upload(q)
+            self.iq_to_f32_dev(d_in.ptr, fmt, n, d_out.ptr, scale)
+            return d_out.download(np.complex64, n)       # ordered behind the kernel on the handle's stream
+        finally:
+            d_in.free()
+            d_out.free()
+
+    def iq_from_f32(self, x, fmt, scale=None, bits=None):
+        """iq_from_f32_dev on complex64 samples: returns (int16 / int8 array [n, 2], clipped components)"""
+        x = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1)
+        fmt = iq_format(fmt)
+        dt = IQ_DTYPE[fmt]
+        d_in, d_out = self.alloc(max(x.nbytes, 1)), self.alloc(max(x.size, 1) * 2 * dt.itemsize)
+        try:
+            d_in.upload(x)
+            clipped = self.iq_from_f32_dev(d_in.ptr, x.size, fmt, d_out.ptr, scale, bits, count=True)
+            return d_out.download(dt, 2 * x.size).reshape(-1, 2), clipped
+        finally:
+            d_in.free()
+            d_out.free()
+
     # -- stream mode --
     def push(self, iq: np.ndarray):
         iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
         self._check(_lib.wifirx_push(self._h, _np_ptr(iq), iq.size, 0))
+
+    def push_iq(self, x, fmt=None, scale=None):
+        """wifirx_push_iq: samples in their native format.  fmt None: taken from an int16 (sc16) / int8 (sc8) array of shape
+        [n, 2] or flat [2 n]; "fc32" (complex64) is push().  scale None: 2^-15 for sc16, 2^-7 for sc8."""
+        if fmt is not None and iq_format(fmt) == IQ_FC32:
+            x = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1)
+            self._check(_lib.wifirx_push_iq(self._h, _np_ptr(x), x.size, IQ_FC32, float(1.0 if scale is None else scale), 0))
+            return
+        x, fmt, n = self._iq_array(x, fmt)
+        self._check(_lib.wifirx_push_iq(self._h, _np_ptr(x), n, fmt, float(IQ_SCALE.get(fmt, 1.0) if scale is None else scale), 0))
+
+    def push_iq_dev(self, ptr, n, fmt, scale=None):
+        """wifirx_push_iq on n samples of `fmt` in device memory at ptr"""
+        fmt = iq_format(fmt)
+        self._check(_lib.wifirx_push_iq(self._h, ptr, int(n), fmt, float(IQ_SCALE.get(fmt, 1.0) if scale is None else scale), 1))
 
     def flush(self):
         self._check(_lib.wifirx_push(self._h, None, 0, 0))

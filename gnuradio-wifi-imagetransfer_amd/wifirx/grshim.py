@@ -116,10 +116,15 @@ def msg_connect(src, sport, dst, dport):
 
 def run_stream(block, samples: np.ndarray, chunk: int = 8192, finish: bool = True) -> int:
     """Drive ``block.work()`` the way the GNU Radio scheduler would: successive chunks of the input
-    stream, each call consuming what ``work`` returns."""
-    samples = np.ascontiguousarray(samples, dtype=np.complex64)
+    stream, each call consuming what ``work`` returns.  ``samples``: complex64 items, or -- for a block whose ``in_sig`` is
+    ``(np.int16, 2)`` / ``(np.int8, 2)`` -- an int16 / int8 array of shape [n, 2], one row per item."""
+    samples = np.asarray(samples)
+    if samples.dtype in (np.dtype(np.int16), np.dtype(np.int8)) and samples.ndim == 2:
+        samples = np.ascontiguousarray(samples)
+    else:
+        samples = np.ascontiguousarray(samples, dtype=np.complex64)
     pos = stalls = 0
-    while pos < samples.size:
+    while pos < len(samples):
         n = block.work([samples[pos:pos + chunk]], [])
         if n == -1:                     # WORK_DONE: the block has ended the flowgraph (a dead stream, wifirx/block.py)
             break

@@ -316,3 +316,39 @@ def impair(frames: np.ndarray, snr_db: float | None, cfo: np.ndarray | float = 0
     slot[:] = noise
     slot[:, lead:lead + m] += g * x[:, :m]
     return slot.astype(np.complex64)
+
+
+# ---- sample formats on the host (NUMERICS.md rule 20; what wifirx_iq_from_f32 / wifirx_iq_to_f32 compute on the device) ----
+IQ_DTYPE = {"sc16": np.int16, "sc8": np.int8}
+IQ_BITS = {"sc16": 16, "sc8": 8}
+
+
+def iq_full_scale(x: np.ndarray, backoff_db: float, fmt: str, bits: int | None = None) -> np.float32:
+    """The quantiser scale that puts full scale, 2^(bits-1), `backoff_db` dB above the RMS of a component of the complex
+    samples x (|x|_rms / sqrt(2))"""
+    bits = IQ_BITS[fmt] if bits is None else bits
+    rms = math.sqrt(float(np.mean(np.abs(np.asarray(x).astype(np.complex128)) ** 2)) / 2.0)
+    return np.float32(2.0 ** (bits - 1) / (rms * 10.0 ** (backoff_db / 20.0)))
+
+
+def quantise_iq(x: np.ndarray, fmt: str, scale, bits: int | None = None):
+    """complex64 [n] -> (int16 / int8 [n, 2], clipped components): t = x * scale in float32, rint (ties to even), clamp to
+    [-2^(bits-1), 2^(bits-1) - 1], NaN gives 0"""
+    bits = IQ_BITS[fmt] if bits is None else bits
+    if not 2 <= bits <= IQ_BITS[fmt]:
+        raise ValueError("bits must be 2..%d for %s" % (IQ_BITS[fmt], fmt))
+    v = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1).view(np.float32).reshape(-1, 2)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = v * np.float32(scale)
+        r = np.rint(t)
+    lo, hi = np.float32(-(2 ** (bits - 1))), np.float32(2 ** (bits - 1) - 1)
+    nan = np.isnan(t)
+    clipped = int(np.count_nonzero(nan | (r < lo) | (r > hi)))
+    q = np.where(nan, np.float32(0), np.clip(r, lo, hi)).astype(np.int32).astype(IQ_DTYPE[fmt])
+    return q, clipped
+
+
+def widen_iq(q: np.ndarray, scale) -> np.ndarray:
+    """int16 / int8 [n, 2] -> complex64 [n]: each component (float)q * scale, one float32 multiply"""
+    v = np.ascontiguousarray(np.asarray(q).reshape(-1, 2).astype(np.float32) * np.float32(scale))
+    return v.view(np.complex64).reshape(-1)

@@ -522,6 +522,51 @@ int  wifirx_link_stats_by_rate(wifirx_handle* h, uint32_t n_slots, const wifirx_
                                uint32_t* frame_err, uint8_t* frame_class, wifirx_link_counts* total,
                                wifirx_link_counts* by_rate);
 
+/* Sample formats of the radios (NUMERICS.md rule 20).  The library computes in WIFIRX_IQ_FC32, interleaved float32 (re, im);
+ * the integer formats are what a USRP (sc16: int16 I, int16 Q, native endian -- UHD's wire and file format) and a HackRF
+ * (sc8: int8 I, int8 Q -- what hackrf_transfer writes) deliver.
+ *   widen     each component is (float)q * scale, one float32 multiply of the exactly converted integer; `scale` is a finite
+ *             float32 > 0, by convention 2^-15 (sc16) and 2^-7 (sc8); exact whenever scale is a power of two
+ *   quantise  to `bits` bits inside the container (2..16 for sc16, 2..8 for sc8), per component: t = x * scale (one float32
+ *             multiply), r = rintf(t) (ties to even), lo = -2^(bits-1), hi = 2^(bits-1) - 1, q = r < lo ? lo : r > hi ? hi :
+ *             (int)r; NaN gives 0, +-inf saturate.  A component is CLIPPED when it was NaN or r lay outside [lo, hi]. */
+#define WIFIRX_IQ_FC32 0
+#define WIFIRX_IQ_SC16 1
+#define WIFIRX_IQ_SC8  2
+
+/* Widen n samples of `fmt` (WIFIRX_IQ_SC16 / WIFIRX_IQ_SC8) at src into float pairs at dst.  DEVICE buffers: src at its natural
+ * alignment (4 bytes sc16, 2 bytes sc8), dst 8-byte aligned; n * 4 or n * 2 bytes are read, n * 8 written.  What the batch
+ * calls take a recording through: wifirx_iq_to_f32 into the float buffer wifirx_demod_batch reads.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for NULL src / dst, an unknown format or WIFIRX_IQ_FC32 (there
+ * is nothing to convert), a scale that is not finite or <= 0, misaligned buffers, and any overlap of the source and
+ * destination bytes.  n = 0 does nothing and returns WIFIRX_OK.  One kernel launch per call.
+ * ORDER: as wifirx_channel -- the kernel runs asynchronously on the handle's stream, behind the handle's earlier calls; src and
+ * dst must stay valid until it has run (wifirx_sync(), or an event recorded on wifirx_stream()). */
+int  wifirx_iq_to_f32(wifirx_handle* h, const void* src, int fmt, uint64_t n, float scale, float* dst);
+
+/* Quantise n float pairs at src to `bits` bits in samples of `fmt` at dst: the converter in front of a receiver (the loop-back
+ * runs it between wifirx_channel and the demod, then widens again).  DEVICE buffers, aligned as above.
+ *   clipped   HOST, may be NULL: the number of clipped components of the call, I and Q each counted on their own (0 .. 2 n).
+ * Checked on the host before anything is queued: wifirx_iq_to_f32's checks, and WIFIRX_EINVAL for bits outside 2..16 (sc16) /
+ * 2..8 (sc8).  n = 0 does nothing and returns WIFIRX_OK (*clipped = 0).  One kernel launch per call.
+ * ORDER: with clipped == NULL as wifirx_iq_to_f32: nothing is counted and nothing waits.  With clipped != NULL as
+ * wifirx_link_stats: the call zeroes a small device counter of the handle, runs the kernel behind the handle's earlier calls,
+ * copies the 8 bytes back and WAITS for them. */
+int  wifirx_iq_from_f32(wifirx_handle* h, const float* src, uint64_t n, float scale, int fmt, uint32_t bits,
+                        void* dst, uint64_t* clipped);
+
+/* wifirx_push for a stream whose samples arrive in `fmt`: n samples (not bytes) at iq, host or device memory, at the format's
+ * natural alignment.  The stream it produces is, byte for byte in every record and output, the stream wifirx_push produces
+ * from the rule-20 widened samples.  WIFIRX_IQ_FC32 IS wifirx_push (the same code path; scale is not looked at).
+ * Host input with WIFIRX_P_STREAM_BATCH is staged and crosses the bus in its native format (a half or a quarter of the float32
+ * bytes) and is widened on the device, into the stream's sample buffer; device input is widened straight from the caller's buffer.
+ * Formats and scales may alternate freely between pushes: a push whose format or scale differs from that of samples still
+ * staged first runs those samples as a (short) batch, the rule a change of WIFIRX_P_STREAM_BATCH follows.  n = 0 flushes.
+ * wifirx_push_consumed, the ERRORS contract of WIFIRX_P_STREAM_BATCH, WIFIRX_EDEAD and wifirx_stats.samples_in keep their
+ * meaning, in samples.  WIFIRX_EINVAL, with wifirx_push_consumed() = 0 and the stream untouched, for an unknown format, a scale
+ * that is not finite or <= 0 (integer formats), NULL iq with n > 0, or a misaligned iq. */
+int  wifirx_push_iq(wifirx_handle* h, const void* iq, size_t n, int fmt, float scale, int iq_on_device);
+
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);
 int  wifirx_dev_free(wifirx_handle* h, void* p);

@@ -5,7 +5,14 @@
 
 Two streams: config-2-like (QPSK-1/2, 294 B, one frame per 4608 samples) and config-1-like (BPSK-1/2, 294 B,
 packet_pad2 gaps: 9420 samples per frame); work() chunk sizes 8192 / 32768 / 131072 items; batch sizes 2^20 / 2^22.
-Prints one JSON line per case: Gsample/s through work() incl. PDU construction and a list-append consumer."""
+Prints one JSON line per case: Gsample/s through work() incl. PDU construction and a list-append consumer.
+
+    python tools/host_path_bench.py --format [frames=6000] [--out profiles/host_path_formats.json]
+
+--format: the same work() loop with fc32, sc16 and sc8 items (wifi_phy_rx(sample_format=...); the integer streams are the
+float stream quantised on the host with full scale 12 dB above its RMS, NUMERICS.md rule 20), on the config-2-like stream with
+batch 2^22 and chunks of 131072 items: three blocks in one process, five rounds alternating between them, the median of each
+and its ratio to fc32."""
 import json
 import os
 import sys
@@ -31,7 +38,51 @@ def make_stream(enc, n_frames, period, lead, snr_db=20.0, seed=3):
     return x, tx.n_sym
 
 
+def formats_main(argv):
+    out = None
+    if "--out" in argv:
+        out = argv[argv.index("--out") + 1]
+        argv = [v for i, v in enumerate(argv) if v != "--out" and (i == 0 or argv[i - 1] != "--out")]
+    n_frames = int(argv[0]) if argv else 6000
+    period, chunk, batch, rounds = 4608, 131072, 1 << 22, 5
+    x, n_sym = make_stream(2, n_frames, period, 160)
+    streams = {"fc32": (x, None)}
+    for fmt in ("sc16", "sc8"):
+        scale = txgen.iq_full_scale(x, 12.0, fmt)
+        streams[fmt] = (txgen.quantise_iq(x, fmt, scale)[0], 1.0 / float(scale))
+    blocks, got = {}, {}
+    for fmt, (samples, scale) in streams.items():
+        blocks[fmt] = block.wifi_phy_rx(bandwidth=20e6, frequency=5.89e9, max_sym=n_sym, publish_carrier=False, batch_samples=batch,
+                                        sample_format=fmt, sample_scale=scale)
+        got[fmt] = []
+        grshim.msg_connect(blocks[fmt], "mac_out", grshim.sink_block(got[fmt].append), "in")
+        grshim.run_stream(blocks[fmt], samples[:period * 300], chunk=chunk)           # warm-up
+    n0 = {fmt: len(g) for fmt, g in got.items()}
+    rate = {fmt: [] for fmt in streams}
+    for _ in range(rounds):
+        for fmt, (samples, _) in streams.items():
+            t = time.perf_counter()
+            grshim.run_stream(blocks[fmt], samples, chunk=chunk)
+            rate[fmt].append(len(samples) / (time.perf_counter() - t) / 1e9)
+    med = {fmt: float(np.median(v)) for fmt, v in rate.items()}
+    res = {"workload": "wifi_phy_rx.work() on the config-2-like stream (QPSK 1/2, 294 B, one frame per 4608 samples, %d frames, 20 dB), "
+                       "batch_samples 2^22, work() chunks of %d items; PDU construction and a list-append consumer included" % (n_frames, chunk),
+           "method": "three blocks (fc32, sc16, sc8 items) in one process, %d rounds alternating between them, medians; the integer "
+                     "streams are the float stream quantised on the host, full scale 12 dB above its RMS" % rounds,
+           "host_bytes_per_sample": {"fc32": 8, "sc16": 4, "sc8": 2},
+           "gsamples_per_s": med, "gsamples_per_s_rounds": rate, "ratio_to_fc32": {fmt: med[fmt] / med["fc32"] for fmt in med},
+           "pdus_per_round": {fmt: (len(got[fmt]) - n0[fmt]) // rounds for fmt in got}, "frames": n_frames}
+    print(json.dumps(res), flush=True)
+    if out:
+        with open(out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    for b in blocks.values():
+        b.close()
+
+
 def main():
+    if "--format" in sys.argv[1:]:
+        return formats_main([v for v in sys.argv[1:] if v != "--format"])
     n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 6000
     for name, enc, period, lead in (("config-2-like", 2, 4608, 160), ("config-1-like", 0, 9420, 100)):
         x, n_sym = make_stream(enc, n_frames, period, lead)

@@ -30,7 +30,15 @@ are --psdu-len bytes at --encoding (default 1528 bytes of 64-QAM 2/3: 64 symbols
 channel is flat (--multipath: the 8-tap sets of sv_taps.npy cycling, every tap fading) and has no carrier offset.  Per SNR,
 Doppler and equaliser: the FER and the counters of wifirx_link_stats.
 
-    python tools/loopback_per.py --doppler 0 3e-5 1e-4 2e-4 --k-factor 10 --snr 25 30 [--frames 1000000] [--out profiles/loopback_fading.json]"""
+    python tools/loopback_per.py --doppler 0 3e-5 1e-4 2e-4 --k-factor 10 --snr 25 30 [--frames 1000000] [--out profiles/loopback_fading.json]
+
+--adc-bits asks what the converter in front of the receiver costs: config 3's loop-back with, between wifirx_channel and the
+demod, wifirx_iq_from_f32 to B bits in --adc-format (default: sc8 up to 8 bits, sc16 above) and wifirx_iq_to_f32 back (NUMERICS.md
+rule 20), on the device.  Full scale, 2^(B-1), is set --backoff-db above the RMS of a component of the channel output (measured on
+its first 256 rows, which are downloaded for it).  Per SNR point: the float32 loop-back without a converter, then per B the FER
+hard and soft and the share of clipped components, every B on the same channel output.
+
+    python tools/loopback_per.py --adc-bits 8 6 4 12 16 --backoff-db 12 --snr 20 25 30 [--frames 262144] [--out profiles/loopback_adc.json]"""
 import argparse
 import json
 import math
@@ -92,8 +100,13 @@ def main():
     ap.add_argument("--psdu-len", type=int, default=1528, help="with --doppler: PSDU bytes, 28 .. 1528")
     ap.add_argument("--encoding", type=int, default=6, help="with --doppler: 0 .. 7")
     ap.add_argument("--multipath", action="store_true", help="with --doppler: the sv_taps.npy sets in place of the flat channel")
+    ap.add_argument("--adc-bits", type=int, nargs="+", default=None, help="a converter of these many bits in front of the receiver")
+    ap.add_argument("--adc-format", choices=("auto", "sc16", "sc8"), default="auto", help="with --adc-bits: the container (auto: sc8 up to 8 bits)")
+    ap.add_argument("--backoff-db", type=float, default=12.0, help="with --adc-bits: full scale above the RMS of the channel output")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.adc_bits is not None:
+        return adc_main(a)
     if a.doppler is not None:
         return fading_main(a)
     if a.rates:
@@ -150,6 +163,75 @@ def main():
                        + ("; sample clock locked to the carrier (wifirx_channel_sro, sro = -cfo bw / (2 pi fc))" if a.locked_clock else ""),
            "stats": "wifirx_link_stats on the device" + (", checked against the NumPy bookkeeping" if a.host_stats else ""),
            "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def adc_main(a):
+    if a.rates or a.host_stats or a.locked_clock or a.doppler is not None:
+        raise SystemExit("--adc-bits stands alone: not with --rates, --host-stats, --locked-clock or --doppler")
+    n = a.frames or 262144
+    fmt_of = lambda b: a.adc_format if a.adc_format != "auto" else ("sc8" if b <= 8 else "sc16")
+    for b in a.adc_bits:
+        if not 2 <= b <= capi.IQ_MAX_BITS[capi.IQ_FORMATS[fmt_of(b)]]:
+            raise SystemExit("--adc-bits %d does not fit %s" % (b, fmt_of(b)))
+    n_sym, nb = txgen.n_sym_for(PSDU_LEN, ENC), txgen.RATE_TABLE[ENC][0]
+    taps = np.load(os.path.join(ROOT, "tests", "golden", "sv_taps.npy")).astype(np.complex64)
+    rx = capi.WifiRx(max_sym=n_sym, llr_bits=nb, chan_est=capi.EQ_LS, device=0)
+    t_all = time.perf_counter()
+    d_psdu, rows, iq, iq_adc, d_int = rx.alloc(n * PSDU_LEN), rx.alloc(n * SLOT * 8), rx.alloc(n * SLOT * 8), rx.alloc(n * SLOT * 8), rx.alloc(n * SLOT * 4)
+    rx.mac_batch_dev(d_psdu.ptr, PSDU_LEN, n, None, payload_len=PSDU_LEN - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, n * SLOT, d_psdu.ptr, ENC, psdu_len=np.full(n, PSDU_LEN, np.uint32), psdu_stride=PSDU_LEN, lead=LEAD, row_len=SLOT)
+    dev = rx.alloc_out(n, psdu_stride=304, want_hbits=True)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * n_sym * 48), hbits=rx.alloc(n * n_sym * 48), psdu=d_psdu,
+               psdu_stride=PSDU_LEN)
+    rx.demod_batch_dev(rows.ptr, SLOT, n, ref)
+    assert rx.link_stats(n, ref, ref)["frames_ref"] == n, "a clean frame was not demodulated"
+
+    def receive(ptr):
+        rx.demod_batch_dev(ptr, SLOT, n, dev)
+        rx.decode_batch_dev(n, dev)
+        hard = rx.link_stats(n, dev, ref)
+        rx.decode_batch_soft_dev(n, dev)
+        soft = rx.link_stats(n, dev, ref)
+        return {"fer": hard["fer"], "fer_soft": soft["fer"], "coded_ber": hard["coded_ber"], "counts": {k: hard[k] for k in COUNTERS},
+                "counts_soft": {k: soft[k] for k in COUNTERS}}
+
+    points = []
+    for snr in a.snr:
+        t0 = time.perf_counter()
+        cfo = np.random.default_rng(int(1000 * snr) + a.seed).uniform(-CFO_20PPM, CFO_20PPM, n).astype(np.float32)
+        rx.channel_dev(rows.ptr, iq.ptr, n * SLOT, n, row_len=SLOT, taps=taps, cfo=cfo, gain=math.sqrt(10 ** (snr / 10)),
+                       noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32))
+        head = iq.download(np.complex64, min(n, 256) * SLOT)
+        rms = math.sqrt(float(np.mean(np.abs(head.astype(np.complex128)) ** 2)) / 2.0)          # of a component
+        pt = {"snr_db": snr, "frames": n, "rms_component": rms, "float32": receive(iq.ptr), "adc": []}
+        for b in a.adc_bits:
+            fmt = fmt_of(b)
+            scale_q = float(np.float32(2.0 ** (b - 1) / (rms * 10.0 ** (a.backoff_db / 20.0))))
+            clipped = rx.iq_from_f32_dev(iq.ptr, n * SLOT, fmt, d_int.ptr, scale_q, b, count=True)
+            rx.iq_to_f32_dev(d_int.ptr, fmt, n * SLOT, iq_adc.ptr, float(np.float32(1.0 / scale_q)))
+            r = receive(iq_adc.ptr)
+            r.update(bits=b, format=fmt, scale=scale_q, clipped_share=clipped / (2.0 * n * SLOT))
+            pt["adc"].append(r)
+        pt["seconds"] = time.perf_counter() - t0
+        points.append(pt)
+        print(json.dumps({"snr_db": snr, "float32": [pt["float32"]["fer"], pt["float32"]["fer_soft"]],
+                          "adc": [[r["bits"], r["format"], r["fer"], r["fer_soft"], r["clipped_share"]] for r in pt["adc"]]}), file=sys.stderr)
+    seconds_total = time.perf_counter() - t_all
+    rx.free_out(ref)
+    rx.free_out(dev)
+    for d in (rows, iq, iq_adc, d_int):
+        d.free()
+    rx.close()
+    res = {"workload": "loop-back on the device, config 3 (%d distinct frames per point, 64-QAM 3/4, PSDU 294 B, rows of 1472, lead 160, "
+                       "sv_taps.npy sets cycling, CFO uniform in +-20 ppm, LS; hard and soft decode_mac) with a converter between channel and "
+                       "receiver: wifirx_iq_from_f32 to B bits, wifirx_iq_to_f32 back; full scale %.1f dB above the RMS of a component of the "
+                       "channel output (its first 256 rows)" % (n, a.backoff_db),
+           "columns": "per SNR: float32 = no converter; adc = one entry per B: fer (hard), fer_soft, clipped_share of the components",
+           "backoff_db": a.backoff_db, "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
