@@ -8,6 +8,12 @@ int16 / int8 pairs: a UHD sc16 recording, or what hackrf_transfer writes; the sc
 
     python examples/make_iq_file.py image.png out.c64 [--encoding 0] [--snr 20] [--pieces 1000]
     python examples/make_iq_file.py kodim01 out.sc8 --format sc8 --backoff-db 12
+    python examples/make_iq_file.py kodim01 wide.sc16 --format sc16 --channels 4 [--stacking 1]
+
+--channels M (2, 4 or 8): a wideband capture at M times the channel rate for examples/wideband_file_rx.py.  The frames are
+dealt round-robin to M streams (frame k goes to channel k mod M), every stream is up-sampled by M with a float64 FFT, shifted
+to its channel's centre and the streams are summed (txgen.synthesise_wideband, NUMERICS.md rule 21); the noise then has unit
+variance per channel bandwidth, so --snr means per channel what it means without --channels.
 """
 import argparse
 import os
@@ -29,6 +35,9 @@ def main():
     ap.add_argument("--pieces", type=int, default=0, help="first N pieces only (0 = all 2700)")
     ap.add_argument("--format", choices=("fc32", "sc16", "sc8"), default="fc32")
     ap.add_argument("--backoff-db", type=float, default=12.0, help="integer formats: full scale above the RMS of the samples")
+    ap.add_argument("--channels", type=int, choices=(1, 2, 4, 8), default=1, help="adjacent channels in one wideband capture")
+    ap.add_argument("--stacking", type=int, choices=(0, 1), default=1, help="--channels: 1 = centres at odd multiples of half the "
+                    "channel width, 0 = at whole multiples")
     a = ap.parse_args()
     gold = os.path.join(ROOT, "tests", "golden", "kodim_300.npz")
     if os.path.exists(a.image):
@@ -50,9 +59,16 @@ def main():
         tx = txgen.encode_psdus(psdus, a.encoding, seeds=[(k % 127) + 1 for k in ks])
         for row, k in enumerate(ks):
             bursts[k] = tx.samples[row] * g
-    x = np.concatenate([np.concatenate([np.zeros(100, np.complex64), b, np.zeros(1000, np.complex64)]) for b in bursts])
+    M = a.channels
+    padded = [np.concatenate([np.zeros(100, np.complex64), b, np.zeros(1000, np.complex64)]) for b in bursts]
     rng = np.random.default_rng(0)
-    x = (x + (rng.standard_normal(x.size) + 1j * rng.standard_normal(x.size)) * np.sqrt(0.5)).astype(np.complex64)
+    if M == 1:
+        x = np.concatenate(padded)
+    else:
+        streams = [np.concatenate(padded[k::M] or [np.zeros(0, np.complex64)]) for k in range(M)]
+        n = max(len(v) for v in streams)
+        x = txgen.synthesise_wideband([np.concatenate([v, np.zeros(n - len(v), np.complex64)]) for v in streams], M, a.stacking)
+    x = (x + (rng.standard_normal(x.size) + 1j * rng.standard_normal(x.size)) * np.sqrt(0.5 * M)).astype(np.complex64)
     if a.format != "fc32":
         scale = txgen.iq_full_scale(x, a.backoff_db, a.format)
         q, clipped = txgen.quantise_iq(x, a.format, scale)

@@ -274,6 +274,158 @@ class wifi_phy_rx(grshim.sync_block):
         self._rx.close()
 
 
+class _channel_rx(wifi_phy_rx):
+    """One channel of ``wifi_phy_rx_wideband``: a ``wifi_phy_rx`` whose PDUs leave on the owner's ports, with ``channel`` (and
+    on ``mac_out`` the ``freq`` it already carries: the channel's own centre) in their dictionaries."""
+
+    def __init__(self, owner, channel, **kw):
+        self._owner, self._channel = owner, int(channel)
+        wifi_phy_rx.__init__(self, **kw)
+
+    def message_port_pub(self, port, msg):
+        meta, vec = grshim.to_python(msg)
+        meta = dict(meta or {})
+        meta["channel"] = self._channel
+        self._owner.message_port_pub(port, grshim.make_pdu(meta, vec) if grshim.HAVE_GNURADIO else (meta, vec))
+
+
+class wifi_phy_rx_wideband(grshim.sync_block):
+    """``wifi_phy_rx`` for a front end that covers ``n_channels`` = 2, 4 or 8 adjacent channels in one stream: ``samp_in`` at
+    ``n_channels * bandwidth``, split on the device by wifirx_channelize (NUMERICS.md rule 21) into ``n_channels`` streams
+    that never leave it, each received by a ``wifi_phy_rx`` chain of its own.  ``stacking`` = 1: the channels' centres lie at
+    ``center_frequency`` -+ bandwidth/2, -+ 3 bandwidth/2, ... (5180 / 5200 / 5220 / 5240 MHz around 5210 MHz); 0: at
+    ``center_frequency + (k - n_channels/2) * bandwidth``.  ``sample_format`` / ``sample_scale`` as ``wifi_phy_rx``; every
+    other keyword goes to the channels' ``wifi_phy_rx``.
+
+    ``mac_out`` and ``carrier`` carry what ``wifi_phy_rx`` publishes, with ``channel`` (k) added to the dictionaries;
+    ``freq`` is the channel's own centre.  Per channel the PDUs, in order, are those of a ``wifi_phy_rx`` fed that channel's
+    samples; between channels they come in the order the chains finish them.
+
+    ``work()`` uploads its items behind the up to ``n_channels - 1`` items the call before left over, runs one
+    wifirx_channelize on the block's own handle (the 23 * n_channels samples of history stay on the device, in two buffers
+    used in turn), WAITS for that handle (the channels' handles read the rows on their own streams, which nothing else orders
+    behind it: include/wifirx.h, wifirx_push, DEVICE INPUT) and pushes row k to channel k as device input.  All handles live
+    on the one device, in this process."""
+
+    def __init__(self, n_channels=4, stacking=1, center_frequency=5.21e9, bandwidth=20e6, sample_format="fc32",
+                 sample_scale=None, device=0, **rx_kwargs):
+        self.n_channels, self.stacking = int(n_channels), int(stacking)
+        if self.n_channels not in capi.CHANNELIZER_CHANNELS:
+            raise ValueError("n_channels must be 2, 4 or 8")
+        if self.stacking not in (0, 1):
+            raise ValueError("stacking must be 0 or 1")
+        self.sample_format = capi.iq_format(sample_format)
+        if self.sample_format not in capi.IQ_DTYPE:
+            raise ValueError("sample_format must be 'fc32', 'sc16' or 'sc8'")
+        self.sample_scale = float(capi.IQ_SCALE[self.sample_format] if sample_scale is None else sample_scale)
+        self._item = capi.IQ_DTYPE[self.sample_format]
+        in_sig = [np.complex64] if self.sample_format == capi.IQ_FC32 else [(self._item.type, 2)]
+        grshim.sync_block.__init__(self, name="wifi_phy_rx_wideband", in_sig=in_sig, out_sig=None)
+        self.bandwidth, self.center_frequency = float(bandwidth), float(center_frequency)
+        M = self.n_channels
+        self.frequencies = [self.center_frequency + capi.channel_centre(k, M, self.stacking) * M * self.bandwidth for k in range(M)]
+        self.message_port_register_out(grshim.intern("mac_out"))
+        self.message_port_register_out(grshim.intern("carrier"))
+        self._bps = 8 if self.sample_format == capi.IQ_FC32 else 2 * self._item.itemsize        # bytes per sample
+        self._cz = capi.WifiRx(max_sym=1, device=device)           # the channelising handle: its receive side stays unused
+        self._rx = []
+        try:
+            for k in range(M):
+                self._rx.append(_channel_rx(self, k, bandwidth=self.bandwidth, frequency=self.frequencies[k], device=device,
+                                            **rx_kwargs))
+        except Exception:
+            self.close()
+            raise
+        self._rem = np.zeros(0, dtype=np.uint8)                     # bytes of the fewer than M samples not yet channelised
+        self._m0 = 0                                                # stream index of the next output
+        self._hist = [self._cz.alloc(capi.CHANNELIZER_HIST * M * self._bps) for _ in range(2)]
+        self._hist_cur = None                                       # index of the buffer that holds the history; None: a new stream
+        self._d_in = self._d_out = None
+        self._cap = 0                                               # outputs per channel the two buffers hold
+        self._push = capi.lib().wifirx_push
+        self.raise_on_error = True
+
+    def _reserve(self, n_out):
+        if n_out <= self._cap:
+            return
+        for b in (self._d_in, self._d_out):
+            if b is not None:
+                b.free()
+        M = self.n_channels
+        self._cap = (n_out + n_out // 2 + 1) & ~1                   # even: every row starts on 16 bytes
+        self._d_in = self._cz.alloc((self._cap + 1) * M * self._bps)
+        self._d_out = self._cz.alloc(self._cap * M * 8)
+
+    def work(self, input_items, output_items):
+        x = input_items[0]
+        n = len(x)
+        if n == 0:
+            return 0
+        if x.dtype != self._item or not x.flags.c_contiguous:
+            x = np.ascontiguousarray(x, dtype=self._item)
+        M, bps = self.n_channels, self._bps
+        raw = x.reshape(-1).view(np.uint8)
+        n_rem = self._rem.size // bps
+        n_out = (n_rem + n) // M
+        if n_out == 0:
+            self._rem = np.concatenate([self._rem, raw])
+            return n
+        self._reserve(n_out)
+        cz, d_in = self._cz, self._d_in
+        if n_rem:
+            d_in.upload(self._rem)
+        used = (n_out * M - n_rem) * bps                            # bytes of x this call channelises
+        cz._check(capi.lib().wifirx_memcpy_h2d(cz._h, d_in.ptr + n_rem * bps, raw.ctypes.data, used))
+        nxt = 1 if self._hist_cur == 0 else 0
+        cz.channelize_dev(d_in.ptr, self.sample_format, n_out, M, self.stacking, self._d_out.ptr, self._cap,
+                          hist_ptr=None if self._hist_cur is None else self._hist[self._hist_cur].ptr,
+                          hist_out_ptr=self._hist[nxt].ptr, m0=self._m0, scale=self.sample_scale)
+        cz.sync()                                                   # the rows are read on the channels' own streams
+        self._hist_cur, self._m0 = nxt, self._m0 + n_out
+        self._rem = raw[used:].copy()
+        for k, rx in enumerate(self._rx):
+            rc = self._push(rx._h, self._d_out.ptr + 8 * k * self._cap, n_out, 1)
+            if rc:
+                rx.push_errors += 1
+                rx.last_error = capi.lib().wifirx_last_error(rx._h).decode()
+                if self.raise_on_error:
+                    rx._rx._check(rc)
+            if rx._queued(rx._h):
+                rx._publish()
+        return n
+
+    def stop(self):
+        """End of stream: settle every channel's pending frames.  The fewer than n_channels samples left over make no output."""
+        for rx in self._rx:
+            rx.stop()
+        return True
+
+    @property
+    def frames_ok(self):
+        return sum(rx.frames_ok for rx in self._rx)
+
+    @property
+    def frames_dropped(self):
+        return sum(rx.frames_dropped for rx in self._rx)
+
+    def stats(self):
+        """the channels' wifirx_stats, channel 0 first"""
+        return [rx.stats() for rx in self._rx]
+
+    def close(self):
+        """Release the device buffers and every handle."""
+        for b in list(getattr(self, "_hist", [])) + [getattr(self, "_d_in", None), getattr(self, "_d_out", None)]:
+            if b is not None:
+                b.free()
+        self._hist, self._d_in, self._d_out, self._cap = [], None, None, 0
+        for rx in getattr(self, "_rx", []):
+            rx.close()
+        self._rx = []
+        if getattr(self, "_cz", None) is not None:
+            self._cz.close()
+            self._cz = None
+
+
 class wifi_phy_tx(grshim.sync_block):
     """Drop-in for the TX half of ``wifi_phy_hier`` (mapper, SIGNAL, chunks->symbols, carrier allocator, IFFT, cyclic
     prefixer; gnu_radio/wifi_phy_hier.grc:279-479,570-586), optionally with ``foo.packet_pad2``'s zeros folded in

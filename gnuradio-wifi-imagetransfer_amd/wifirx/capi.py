@@ -48,7 +48,10 @@ EXPORTS = [
     "wifirx_mac_batch", "wifirx_link_stats", "wifirx_tx_batch_rates", "wifirx_link_stats_by_rate",
     "wifirx_channel_sro", "wifirx_resampler_table", "wifirx_channel_fading",
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
+    "wifirx_channelize", "wifirx_channelizer_table",
 ]
+CHANNELIZER_CHANNELS = (2, 4, 8)    # wifirx_channelize: n_channels (NUMERICS.md rule 21)
+CHANNELIZER_HIST = 23               # input blocks of n_channels samples that a call takes from before its input
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
 
@@ -103,6 +106,20 @@ def resampler_table() -> np.ndarray:
     if rc != OK:
         raise WifiRxError(rc, "wifirx_resampler_table")
     return np.ctypeslib.as_array(p, shape=(n_ph.value + 1, n_t.value)).copy()
+
+
+def channelizer_table(n_channels) -> np.ndarray:
+    """wifirx_channelizer_table: the rule-21 prototype as float32 [24 * n_channels] (a copy; no handle, no device)"""
+    p, n = C.POINTER(C.c_float)(), C.c_uint32()
+    rc = _lib.wifirx_channelizer_table(int(n_channels), C.byref(p), C.byref(n))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_channelizer_table: n_channels must be 2, 4 or 8")
+    return np.ctypeslib.as_array(p, shape=(n.value,)).copy()
+
+
+def channel_centre(k, n_channels, stacking) -> float:
+    """f_k of wifirx_channelize in cycles per input sample; times n_channels * bandwidth it is the channel's offset in Hz"""
+    return (k + stacking / 2.0 - n_channels / 2.0) / n_channels
 
 
 def link_rates(c) -> dict:
@@ -207,6 +224,9 @@ _lib.wifirx_iq_to_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C
 _lib.wifirx_iq_from_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.c_uint32, C.c_void_p,
                                     C.POINTER(C.c_uint64)]
 _lib.wifirx_push_iq.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int]
+_lib.wifirx_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                   C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
+_lib.wifirx_channelizer_table.argtypes = [C.c_uint32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -782,6 +802,19 @@ class WifiRx:
         finally:
             d_in.free()
             d_out.free()
+
+    # -- wideband ingest (wifirx_channelize; NUMERICS.md rule 21) --
+    def channelize_dev(self, in_ptr, fmt, n_out, n_channels, stacking, out_ptr, out_stride=None, hist_ptr=None,
+                       hist_out_ptr=None, m0=0, scale=None):
+        """wifirx_channelize on device pointers: n_out * n_channels samples of `fmt` at in_ptr -> n_channels rows of n_out
+        complex64 at out_ptr, row k at out_ptr + 8 * k * out_stride bytes (out_stride None: n_out).  hist_ptr: the
+        23 * n_channels samples in front (None: zeros); hist_out_ptr: where the next call's hist goes (None: nowhere).
+        Asynchronous on the handle's stream: sync() before another handle reads the rows."""
+        fmt = iq_format(fmt)
+        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
+        self._check(_lib.wifirx_channelize(self._h, in_ptr, fmt, float(scale), hist_ptr, hist_out_ptr, int(n_channels),
+                                           int(stacking), int(n_out), int(m0) & 0xFFFFFFFFFFFFFFFF, out_ptr,
+                                           int(n_out if out_stride is None else out_stride)))
 
     # -- stream mode --
     def push(self, iq: np.ndarray):

@@ -352,3 +352,26 @@ def widen_iq(q: np.ndarray, scale) -> np.ndarray:
     """int16 / int8 [n, 2] -> complex64 [n]: each component (float)q * scale, one float32 multiply"""
     v = np.ascontiguousarray(np.asarray(q).reshape(-1, 2).astype(np.float32) * np.float32(scale))
     return v.view(np.complex64).reshape(-1)
+
+
+def synthesise_wideband(streams, n_channels: int, stacking: int, gains=None) -> np.ndarray:
+    """The host synthesis of a wideband capture, the counterpart of wifirx_channelize (NUMERICS.md rule 21): `n_channels`
+    complex streams at fs (equal lengths n) -> complex128 [n * n_channels] at n_channels * fs, stream k centred at
+    f_k = (k + stacking/2 - n_channels/2) / n_channels cycles per sample.  float64: FFT up-sampling by n_channels (each
+    stream's spectrum placed in the middle of an n_channels times wider band, amplitudes kept), a shift to f_k, and a sum.
+    The FFT makes each stream periodic: a capture starts and ends in silence."""
+    M = int(n_channels)
+    streams = [np.asarray(v, dtype=np.complex128).reshape(-1) for v in streams]
+    if len(streams) != M or len({len(v) for v in streams}) != 1:
+        raise ValueError("n_channels streams of one length are required")
+    n = len(streams[0])
+    t = np.arange(n * M)
+    out = np.zeros(n * M, np.complex128)
+    lo = (n * M) // 2 - n // 2
+    for k, v in enumerate(streams):
+        W = np.zeros(n * M, np.complex128)
+        W[lo:lo + n] = np.fft.fftshift(np.fft.fft(v))
+        up = np.fft.ifft(np.fft.ifftshift(W)) * M
+        f_k = (k + stacking / 2.0 - M / 2.0) / M
+        out += (1.0 if gains is None else gains[k]) * up * np.exp(2j * np.pi * f_k * t)
+    return out

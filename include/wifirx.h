@@ -272,7 +272,17 @@ int  wifirx_decode_batch_soft(wifirx_handle* h, uint32_t n_slots, const wifirx_o
 
 /* Stream mode (what the GNU Radio block's work() calls): append `n` samples of the continuous
  * input stream (host or device memory; the library copies).  Frames that completed inside the
- * samples seen so far are demodulated + decoded and queued for wifirx_poll. */
+ * samples seen so far are demodulated + decoded and queued for wifirx_poll.
+ *
+ * DEVICE INPUT (iq_on_device = 1), what the call guarantees.  The samples are read by work queued on the handle's own stream,
+ * wifirx_stream(h): a device-to-device copy (wifirx_push), or the widening kernel (wifirx_push_iq), into the library's sample
+ * buffer.  Before the call returns WIFIRX_OK it has waited for that stream at least once behind this read -- when it only
+ * collects (WIFIRX_P_STREAM_BATCH not reached) it waits for the copy, otherwise for the detection behind it -- so the caller may
+ * overwrite or free the buffer as soon as the call has returned; after an error return the library reads it no more either.
+ * The handle's stream is created with hipStreamNonBlocking: it is ordered against NO other stream, the legacy default stream
+ * included.  Whoever produced the samples on another stream -- a kernel of the caller, a torch stream, another handle's
+ * wifirx_channelize -- must therefore have finished before wifirx_push is called: wifirx_sync() on the producing handle, or
+ * an event recorded on the producer's stream and waited for (by the host, or by a hipStreamWaitEvent on wifirx_stream(h)). */
 int  wifirx_push(wifirx_handle* h, const float* iq, size_t n, int iq_on_device);
 
 /* How many leading samples of the last wifirx_push call the stream has taken over: n after WIFIRX_OK; after an error
@@ -566,6 +576,39 @@ int  wifirx_iq_from_f32(wifirx_handle* h, const float* src, uint64_t n, float sc
  * meaning, in samples.  WIFIRX_EINVAL, with wifirx_push_consumed() = 0 and the stream untouched, for an unknown format, a scale
  * that is not finite or <= 0 (integer formats), NULL iq with n > 0, or a misaligned iq. */
 int  wifirx_push_iq(wifirx_handle* h, const void* iq, size_t n, int fmt, float scale, int iq_on_device);
+
+/* Wideband ingest (NUMERICS.md rule 21): split one stream sampled at M * fs, M = n_channels in {2, 4, 8} adjacent channels of
+ * width fs, into M streams at fs -- a critically sampled polyphase analysis bank, 24 taps per branch, on the device.  Channel k
+ * (0 .. M-1) is centred at f_k = (k + stacking/2 - M/2) / M cycles per input sample: stacking = 1 puts the centres at -+fs/2,
+ * -+3fs/2, ... around the tuned frequency (four 5 GHz channels around their common centre), stacking = 0 at k * fs - M/2 * fs
+ * (channel 0 then straddles the band edge; it is still produced).  With z_k[n] = x[n] exp(-j 2 pi f_k n), n the stream's input
+ * index, and h the prototype of wifirx_channelizer_table:  y_k[m] = sum_{i < 24 M} h[i] z_k[m M + M - 1 - i].
+ * n_out outputs per channel consume exactly n_out * M input samples.
+ *   in          DEVICE, n_out * M samples of `fmt` (WIFIRX_IQ_FC32 / SC16 / SC8) at the format's natural alignment (8 / 4 / 2
+ *               bytes).  Integer samples are widened by rule 20 with `scale` inside the kernel; for FC32 scale is not looked at.
+ *   hist        DEVICE, the 23 * M samples in front of in[0], same format; NULL = zeros (the start of a stream).
+ *   hist_out    DEVICE, may be NULL: receives the last 23 * M samples of (hist || in), in the input format, by copies queued
+ *               behind the kernel.  Passed on as the next call's hist, with m0 + n_out, it makes a stream cut into calls
+ *               byte-identical to the uncut one from the first output on.  It must not overlap hist, in or out: a caller
+ *               alternates between two buffers.
+ *   m0          the stream index of the call's first output (its parity enters for stacking = 1).
+ *   out         DEVICE, 8-byte aligned float pairs: channel k occupies out + 2 * k * out_stride floats, n_out samples; nothing
+ *               else is written.  Each row is what wifirx_push(iq_on_device = 1) of channel k's handle takes.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for NULL in / out with n_out > 0, an unknown fmt, a scale that
+ * is not finite or <= 0 (integer formats), n_channels outside {2, 4, 8}, stacking outside {0, 1}, misaligned buffers, and any
+ * overlap among in, hist, hist_out and the M rows of out (taken as one range, first row to last); WIFIRX_ERANGE for
+ * out_stride < n_out, out_stride > 2^44 or n_out > 2^40.  n_out = 0 returns WIFIRX_OK and still produces hist_out (= hist, or
+ * zeros) when asked.  One kernel launch per call, and at most two copies for hist_out.
+ * ORDER: as wifirx_iq_to_f32 -- asynchronous on the handle's stream, behind the handle's earlier calls; every buffer must stay
+ * valid until the work has run.  The rows are usually consumed by OTHER handles, each on its own stream: see wifirx_push,
+ * DEVICE INPUT -- wifirx_sync() on this handle (or an event on wifirx_stream()) comes between this call and their pushes. */
+int  wifirx_channelize(wifirx_handle* h, const void* in, int fmt, float scale, const void* hist, void* hist_out,
+                       uint32_t n_channels, int stacking, uint64_t n_out, uint64_t m0, float* out, uint64_t out_stride);
+
+/* The bank's prototype (NUMERICS.md rule 21; tools/gen_channelizer_table.py): *taps = the 24 * n_channels float32 taps h for
+ * n_channels in {2, 4, 8}, symmetric, sum 1; *n_taps = their number.  Host memory owned by the library.  Needs no handle and
+ * no device.  WIFIRX_EINVAL for another n_channels or a NULL argument. */
+int  wifirx_channelizer_table(uint32_t n_channels, const float** taps, uint32_t* n_taps);
 
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);

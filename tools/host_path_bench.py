@@ -12,7 +12,13 @@ Prints one JSON line per case: Gsample/s through work() incl. PDU construction a
 --format: the same work() loop with fc32, sc16 and sc8 items (wifi_phy_rx(sample_format=...); the integer streams are the
 float stream quantised on the host with full scale 12 dB above its RMS, NUMERICS.md rule 20), on the config-2-like stream with
 batch 2^22 and chunks of 131072 items: three blocks in one process, five rounds alternating between them, the median of each
-and its ratio to fc32."""
+and its ratio to fc32.
+
+    python tools/host_path_bench.py --wideband M [frames=600] [--format sc16] [--out profiles/host_path_wideband.json]
+
+--wideband M: wifi_phy_rx_wideband.work() on a capture of M config-2-like streams synthesised on the host (float64 FFT
+up-sampling, NUMERICS.md rule 21) and quantised to the format, in chunks of 524288 wideband items: wideband samples per second,
+the median of five rounds, beside M times the single-channel figure recorded in profiles/host_path_formats.json."""
 import json
 import os
 import sys
@@ -26,14 +32,17 @@ from wifirx import block, grshim, txgen  # noqa: E402
 
 
 def make_stream(enc, n_frames, period, lead, snr_db=20.0, seed=3):
+    """snr_db None: the frames at unit power without noise (the wideband synthesis adds its own)"""
     tx = txgen.encode_psdus(txgen.make_psdus(64, 294, seed=seed), enc)
     flen = tx.samples.shape[1]
     assert lead + flen <= period
-    g = np.float32(np.sqrt(10 ** (snr_db / 10)))
+    g = np.float32(1.0 if snr_db is None else np.sqrt(10 ** (snr_db / 10)))
     x = np.zeros((n_frames, period), np.complex64)
     x[:, lead:lead + flen] = tx.samples[np.arange(n_frames) % 64] * g
     rng = np.random.default_rng(seed)
     x = x.reshape(-1)
+    if snr_db is None:
+        return x, tx.n_sym
     x += ((rng.standard_normal(x.size) + 1j * rng.standard_normal(x.size)) * np.sqrt(0.5)).astype(np.complex64)
     return x, tx.n_sym
 
@@ -80,7 +89,69 @@ def formats_main(argv):
         b.close()
 
 
+def wideband_main(argv):
+    def option(name, default):
+        if name in argv:
+            i = argv.index(name)
+            value = argv[i + 1]
+            del argv[i:i + 2]
+            return value
+        return default
+    M = int(option("--wideband", "4"))
+    out, fmt = option("--out", None), option("--format", "sc16")
+    n_frames = int(argv[0]) if argv else 600
+    period, chunk, batch, rounds, stacking = 4608, 524288, 1 << 22, 5, 1
+    streams, n_sym = [], 0
+    for k in range(M):
+        v, n_sym = make_stream(2, n_frames, period, 96 + 8 * k, snr_db=None, seed=3 + k)
+        streams.append(v)
+    wide = txgen.synthesise_wideband(streams, M, stacking) * np.sqrt(10 ** (20.0 / 10))
+    del streams
+    rng = np.random.default_rng(9)
+    x = wide.astype(np.complex64)
+    del wide
+    x += ((rng.standard_normal(x.size) + 1j * rng.standard_normal(x.size)) * np.sqrt(0.5 * M)).astype(np.complex64)
+    scale = None
+    if fmt != "fc32":
+        scale_q = txgen.iq_full_scale(x, 12.0, fmt)
+        x, scale = txgen.quantise_iq(x, fmt, scale_q)[0], 1.0 / float(scale_q)
+    blk = block.wifi_phy_rx_wideband(M, stacking, 5.21e9, bandwidth=20e6, sample_format=fmt, sample_scale=scale, max_sym=n_sym,
+                                     publish_carrier=False, batch_samples=batch)
+    got = []
+    grshim.msg_connect(blk, "mac_out", grshim.sink_block(got.append), "in")
+    grshim.run_stream(blk, x[:period * M * 100], chunk=chunk)                 # warm-up
+    n0, rate = len(got), []
+    for _ in range(rounds):
+        t = time.perf_counter()
+        grshim.run_stream(blk, x, chunk=chunk)
+        rate.append(len(x) / (time.perf_counter() - t) / 1e9)
+    single = None
+    try:
+        with open(os.path.join(ROOT, "profiles", "host_path_formats.json")) as f:
+            single = json.load(f)["gsamples_per_s"]["fc32"]
+    except (OSError, KeyError, ValueError):
+        pass
+    med = float(np.median(rate))
+    res = {"workload": "wifi_phy_rx_wideband.work(): %d channels (stacking 1), each the config-2-like stream (QPSK 1/2, 294 B, one frame "
+                       "per 4608 channel samples, %d frames, 20 dB), %s items, batch_samples 2^22 per channel, work() chunks of %d wideband "
+                       "items; PDU construction and a list-append consumer included" % (M, n_frames, fmt, chunk),
+           "method": "one block, %d rounds over the capture, the median; the figure beside it is the fc32 work() rate of the "
+                     "single-channel block recorded in profiles/host_path_formats.json (the channels' streams arrive as float32 on the "
+                     "device), times the number of channels" % rounds,
+           "n_channels": M, "format": fmt, "wideband_gsamples_per_s": med, "wideband_gsamples_per_s_rounds": rate,
+           "single_channel_fc32_gsamples_per_s": single, "n_channels_times_single": None if single is None else M * single,
+           "ratio_to_n_channels_times_single": None if single is None else med / (M * single),
+           "pdus_per_round": (len(got) - n0) // rounds, "frames_per_channel": n_frames}
+    print(json.dumps(res), flush=True)
+    if out:
+        with open(out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    blk.close()
+
+
 def main():
+    if "--wideband" in sys.argv[1:]:
+        return wideband_main(list(sys.argv[1:]))
     if "--format" in sys.argv[1:]:
         return formats_main([v for v in sys.argv[1:] if v != "--format"])
     n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 6000
