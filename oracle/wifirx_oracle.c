@@ -1291,6 +1291,10 @@ int orc_decode_batch(uint32_t n_slots, const orc_params* prm, wifirx_frame* fram
         wifirx_frame* fr = frames + i;
         if (!(fr->flags & WIFIRX_F_COMPLETE)) continue;
         if (fr->psdu_len > psdu_stride) continue;
+        /* a frame whose symbols do not fit the row of decisions is left alone (frame_steps of csrc/wr_decode.h); a
+         * demodulation never marks one complete, host-made records may (tests/hard_rows.py) */
+        int n_dbps = N_DBPS[fr->encoding & 7];
+        if ((16 + 8 * (int)fr->psdu_len + 6 + n_dbps - 1) / n_dbps > prm->max_sym) continue;
         int r = orc_decode_mac(idx + i * idx_stride, fr->encoding, fr->psdu_len, psdu + (size_t)i * psdu_stride);
         if (r < 0) continue;
         fr->flags |= WIFIRX_F_DECODED;

@@ -6,35 +6,15 @@ frame's last symbol; decode_mac from planes alone == the oracle's PSDUs, uniform
 import numpy as np
 import pytest
 
-from helpers import make_slots
+from helpers import make_slots, planes_of
 
 pytestmark = pytest.mark.gpu
-
-DATA_BINS = np.array([i for i in range(6, 59) if i not in (11, 25, 32, 39, 53)])       # data carrier c -> FFT bin (shifted)
-N_BPSC = np.array([1, 1, 2, 2, 4, 4, 6, 6])
 
 
 @pytest.fixture(scope="module")
 def capi():
     from wifirx import capi
     return capi
-
-
-def planes_of(frames, idx, max_sym):
-    """numpy statement of the layout in include/wifirx.h: word 2 b + h of symbol q = bit b of bins 32 h .. 32 h + 31"""
-    n = len(frames)
-    out = np.zeros((n, max_sym * 12), np.uint32)
-    for f in range(n):
-        nb = int(N_BPSC[frames["encoding"][f] & 7]) if frames["n_bpsc"][f] else 0
-        for q in range(int(frames["n_sym_out"][f])):
-            dec = idx[f, q].astype(np.uint32)
-            for b in range(nb):
-                bits = np.zeros(64, np.uint64)
-                bits[DATA_BINS] = (dec >> b) & 1
-                w = int((bits << np.arange(64, dtype=np.uint64)).sum())
-                out[f, q * 2 * nb + 2 * b] = w & 0xffffffff
-                out[f, q * 2 * nb + 2 * b + 1] = w >> 32
-    return out
 
 
 @pytest.mark.parametrize("encoding", range(8))

@@ -16,42 +16,16 @@ import pytest
 
 import soft_rows as sr
 import soft_viterbi_ref as ref
+from helpers import Fenced
 from llr_bf16_ref import bf16_to_f32
 
 pytestmark = pytest.mark.gpu
-
-FENCE = 4096
 
 
 @pytest.fixture(scope="module")
 def capi():
     from wifirx import capi
     return capi
-
-
-class Fenced:
-    """a PSDU buffer of n rows, `off` bytes behind a 16-byte boundary, between two fences, all of it FILL"""
-
-    def __init__(self, rx, n, stride, off=0):
-        self.n, self.stride, self.at = n, stride, FENCE + off
-        self.total = FENCE + 16 + n * stride + FENCE
-        self.buf = rx.alloc(self.total).upload(np.full(self.total, sr.FILL, np.uint8))
-        assert self.buf.ptr % 16 == 0
-        self.ptr = self.buf.ptr + self.at
-
-    def refill(self):
-        self.buf.upload(np.full(self.total, sr.FILL, np.uint8))
-
-    def expected(self, rows):
-        e = np.full(self.total, sr.FILL, np.uint8)
-        e[self.at:self.at + self.n * self.stride] = rows.reshape(-1)
-        return e
-
-    def download(self):
-        return self.buf.download(np.uint8, self.total)
-
-    def free(self):
-        self.buf.free()
 
 
 def soft_decode(capi, rx, d_frames, d_llr, ps, n):
