@@ -12,6 +12,14 @@ trigger of sync_short counts.
 
     rx = IndependentRx()                       # constants from tests/golden/grc_constants.json
     out = rx.receive(slots)                    # slots: [F, S] complex; dict of per-frame arrays
+
+The other three equalisers (`chan_est` 1 = LMS, 2 = COMB, 3 = STA) are written from the TEXT of NUMERICS.md rule 11, the
+soft outputs from rules 7, 12 and 13 -- in float64, with complex division, np.interp and np.convolve, not from either
+implementation.  Besides the hard decisions `receive` returns the equalised points (`eq`, and `eq_signal` for the SIGNAL
+symbol), the LS estimate on the 52 used bins (`csi`), the LLRs (`llr`, `[F, max_sym, 48, n_bpsc]`, the bits of the real
+axis first), the channel-state weight per data carrier (`weight`) with the weighted LLRs (`llr_w`), and the per-frame
+sums of |y|, |y|^2, |y|^4 (`sym_stats`).  `margin` is the distance of a point's components to the nearest slicer
+threshold: what decides where a float32 and a float64 slicer may legitimately differ.
 """
 import json
 import os
@@ -24,6 +32,14 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 RATE_FIELD = {0b1011: (0, 1, 24), 0b1111: (1, 1, 36), 0b1010: (2, 2, 48), 0b1110: (3, 2, 72),
               0b1001: (4, 4, 96), 0b1101: (5, 4, 144), 0b1000: (6, 6, 192), 0b1100: (7, 6, 216)}
 MIN_GAP, MAX_SAMPLES, SYNC_LENGTH = 480, 540 * 80, 320
+LS, LMS, COMB, STA = 0, 1, 2, 3                       # chan_est, in the order of the reference's Equalizer enum
+# NUMERICS.md rule 11, the table of constants
+LMS_STEP = 0.5                                        # H <- (1 - step) H + step X/point
+COMB_ALPHA = 0.2                                      # d_H <- (1 - alpha) d_H + alpha H
+COMB_NODES = (0, 11, 25, 39, 53, 64)                  # band edge, the four pilots, band edge
+STA_ALPHA, STA_BETA = 0.5, 2                          # time constant, half-width in bins
+# the amplitude unit a of a constellation (802.11 Table 18-7 .. 18-10: K_mod), per n_bpsc
+UNIT = {1: 1.0, 2: np.sqrt(0.5), 4: np.sqrt(0.1), 6: np.sqrt(1.0 / 42.0)}
 
 
 def _conv_outputs():
@@ -164,8 +180,80 @@ class IndependentRx:
         return ((re > 0) | ((ar < 4 * a) << 1) | (((ar > 2 * a) & (ar < 6 * a)) << 2) |
                 ((im > 0) << 3) | ((ai < 4 * a) << 4) | (((ai > 2 * a) & (ai < 6 * a)) << 5)).astype(np.uint8)
 
+    @staticmethod
+    def _axis_level(pos, inner, mid, n_axis):
+        """the level (in units of a) of one axis from the bits decide() states: pos = (u > 0); for 16-QAM inner = (|u| < 2a);
+        for 64-QAM inner = (|u| < 4a), mid = (2a < |u| < 6a)"""
+        if n_axis == 1:
+            mag = np.ones(pos.shape)
+        elif n_axis == 2:
+            mag = np.where(inner, 1.0, 3.0)
+        else:
+            mag = np.where(inner, np.where(mid, 3.0, 1.0), np.where(mid, 5.0, 7.0))
+        return np.where(pos, mag, -mag)
+
+    @classmethod
+    def points(cls, idx, n_bpsc):
+        """the constellation point of a decision, from the bit order of decide()"""
+        i = np.asarray(idx).astype(np.int64)
+        if n_bpsc == 1:
+            return np.where(i & 1, 1.0, -1.0).astype(np.complex128)
+        h = n_bpsc // 2
+        re = cls._axis_level((i & 1) != 0, (i >> 1) & 1 != 0, (i >> 2) & 1 != 0, h)
+        j = i >> h
+        im = cls._axis_level((j & 1) != 0, (j >> 1) & 1 != 0, (j >> 2) & 1 != 0, h)
+        return UNIT[n_bpsc] * (re + 1j * im)
+
+    @staticmethod
+    def llr(y, n_bpsc):
+        """rule 7: per axis u, L0 = u; 16-QAM L1 = 2a - |u|; 64-QAM L1 = 4a - |u|, L2 = 2a - ||u| - 4a|; positive = bit 1;
+        [..., n_bpsc], the bits of the real axis first"""
+        a = UNIT[n_bpsc]
+        if n_bpsc == 1:
+            return y.real[..., None].copy()
+
+        def axis(u):
+            if n_bpsc == 2:
+                return [u]
+            if n_bpsc == 4:
+                return [u, 2 * a - np.abs(u)]
+            return [u, 4 * a - np.abs(u), 2 * a - np.abs(np.abs(u) - 4 * a)]
+        return np.stack(axis(y.real) + axis(y.imag), axis=-1)
+
+    @staticmethod
+    def margin(y, n_bpsc):
+        """[..., 2]: distance of the real and the imaginary part to the nearest threshold of decide(); BPSK has none on the
+        imaginary axis"""
+        a = UNIT[n_bpsc]
+        thr = {1: [0.0], 2: [0.0], 4: [0.0, 2 * a], 6: [0.0, 2 * a, 4 * a, 6 * a]}[n_bpsc]
+        u = np.stack([np.abs(y.real), np.abs(y.imag)], axis=-1)
+        m = np.min(np.stack([np.abs(u - t) for t in thr], axis=0), axis=0)
+        if n_bpsc == 1:
+            m[..., 1] = np.inf
+        return m
+
+    def _comb_estimate(self, X, s):
+        """rule 11, COMB: the channel of ONE symbol from its four pilots (after the common-phase rotation), polarity removed;
+        bins 0 and 64 take their mean; linear in between"""
+        if s < 2:
+            nodes = np.stack([X[:, 11], -X[:, 25], X[:, 39], X[:, 53]], axis=1)
+        else:
+            nodes = self.polarity[(s - 2) % 127] * np.stack([X[:, 11], X[:, 25], X[:, 39], -X[:, 53]], axis=1)
+        lo_edge = hi_edge = nodes.mean(axis=1)
+        v = np.concatenate([lo_edge[:, None], nodes, hi_edge[:, None]], axis=1)
+        i = np.arange(64)
+        return np.stack([np.interp(i, COMB_NODES, r.real) + 1j * np.interp(i, COMB_NODES, r.imag) for r in v], axis=0)
+
+    def _sta_average(self, HU):
+        """rule 11, STA: the mean of the per-bin estimates over the used bins within +-STA_BETA (3, 4 or 5 of them)"""
+        box = np.ones(2 * STA_BETA + 1)
+        cnt = np.convolve(self.used.astype(np.float64), box, mode="same")
+        tot = np.stack([np.convolve(r, box, mode="same") for r in np.where(self.used[None, :], HU, 0.0)], axis=0)
+        avg = tot / np.maximum(cnt, 1.0)[None, :]
+        return avg
+
     # ---- the chain ------------------------------------------------------------------------------------------
-    def receive(self, slots, max_sym=64):
+    def receive(self, slots, max_sym=64, chan_est=LS):
         x = np.asarray(slots, dtype=np.complex128)
         F, S = x.shape
         t, cfo_c = self.detect(x)
@@ -190,6 +278,13 @@ class IndependentRx:
         idx = np.zeros((F, max_sym, 48), np.uint8)
         n_out = np.zeros(F, np.int64)
         k64 = np.arange(64) - 32
+        db = self.data_bins
+        H_ls = np.ones((F, 64), np.complex128)                                   # the LS estimate: CSI export, rule 12
+        DH = np.ones((F, 64), np.complex128)                                     # the running estimate of COMB / STA
+        eq = np.zeros((F, max_sym, 48), np.complex128)
+        eq_signal = np.zeros((F, 48), np.complex128)
+        llr = np.zeros((F, max_sym, 48, 6))
+        stats = np.zeros((F, 3))
         s = 0
         while True:
             act = alive & (s <= n_sym + 2)
@@ -219,6 +314,9 @@ class IndependentRx:
             X = X * np.exp(-1j * beta)[:, None]                                                             # (4)
             if s >= 2:
                 d_er = np.where(act, 0.9 * d_er + 0.1 * er_new, d_er)                                       # (5)
+            if chan_est == COMB:                                                 # rule 11: every symbol, the two LTS included
+                Hc = self._comb_estimate(X, s)
+                DH = np.where(act[:, None], Hc if s == 0 else (1 - COMB_ALPHA) * DH + COMB_ALPHA * Hc, DH)
             if s == 0:                                                                                      # (6)
                 H = np.where(act[:, None], X, H)
             elif s == 1:
@@ -228,11 +326,35 @@ class IndependentRx:
                 Hn = np.ones_like(H)
                 Hn[:, u] = (H[:, u] + X[:, u]) / (2.0 * self.lts_f[u])[None, :]
                 H = np.where(act[:, None], Hn, H)
+                H_ls = H.copy()
+                if chan_est == STA:
+                    DH = H_ls.copy()                                             # STA starts from the LS estimate
                 with np.errstate(divide="ignore", invalid="ignore"):
                     snr = np.where(act, 10 * np.log10(signal / noise / 2), snr)
             else:
-                Y = X[:, self.data_bins] / H[:, self.data_bins]
+                nbs = np.ones(F, np.int64) if s == 2 else n_bpsc                 # rule 11: BPSK decisions on the SIGNAL symbol
+                H_run = DH if chan_est in (COMB, STA) else H                     # COMB: this symbol's update is already in
+                Y = X[:, db] / H_run[:, db]
+                if chan_est in (LMS, STA):
+                    pt = np.ones((F, 48), np.complex128)
+                    for nb in (1, 2, 4, 6):
+                        sel = act & (nbs == nb)
+                        if sel.any():
+                            pt[sel] = self.points(self.decide(Y[sel], nb), nb)
+                    if chan_est == LMS:                                          # after the bin is equalised with the old H
+                        Hn = H.copy()
+                        Hn[:, db] = (1 - LMS_STEP) * H[:, db] + LMS_STEP * (X[:, db] / pt)
+                        H = np.where(act[:, None], Hn, H)
+                    else:                                                        # after the whole symbol is equalised with the old d_H
+                        HU = np.zeros((F, 64), np.complex128)
+                        HU[:, db] = X[:, db] / pt
+                        HU[:, self.pilot_bins] = X[:, self.pilot_bins] * (p * np.array([1.0, 1.0, 1.0, -1.0]))[None, :]
+                        DH_new = np.where(self.used[None, :], (1 - STA_ALPHA) * DH + STA_ALPHA * self._sta_average(HU), DH)
+                        H_used = DH                                              # ... the new one serves the next symbol
+                        Y = X[:, db] / H_used[:, db]
+                        DH = np.where(act[:, None], DH_new, DH)
                 if s == 2:                                                                                  # (7)
+                    eq_signal = np.where(act[:, None], Y, eq_signal)
                     rxb = (Y.real > 0).astype(np.int64)
                     i48 = np.arange(48)
                     deint = rxb[:, 3 * (i48 % 16) + i48 // 16]
@@ -256,9 +378,19 @@ class IndependentRx:
                         sel = act & (n_bpsc == nb)
                         if sel.any():
                             idx[sel, q, :] = self.decide(Y[sel], nb)
+                            llr[sel, q, :, :nb] = self.llr(Y[sel], nb)
+                    eq[act, q, :] = Y[act]
+                    ay = np.abs(Y)
+                    stats += np.where(act[:, None], np.stack([ay.sum(axis=1), (ay ** 2).sum(axis=1), (ay ** 4).sum(axis=1)], axis=1), 0.0)
                     n_out = np.where(act, q + 1, n_out)
             s += 1
         complete = signal_ok & (n_out == n_sym) & ~truncated
-        return dict(trigger=t, cfo_coarse=cfo_c, frame_start=np.where(sync, fs, 0), cfo_fine=np.where(sync, cfo_f, 0.0),
+        wH = H_ls                                                                # rule 12: the LS estimate, whatever the equaliser
+        weight = np.abs(wH[:, db]) ** 2
+        nb_max = int(n_bpsc[signal_ok].max()) if signal_ok.any() else 1
+        llr = llr[..., :nb_max]
+        soft = dict(eq=eq, eq_signal=eq_signal, csi=H_ls[:, self.used], llr=llr, weight=weight,
+                    llr_w=llr * weight[:, None, :, None], sym_stats=stats, n_bpsc=n_bpsc)
+        return dict(soft, trigger=t, cfo_coarse=cfo_c, frame_start=np.where(sync, fs, 0), cfo_fine=np.where(sync, cfo_f, 0.0),
                     detected=det, sync=sync, found=found, top4=top, signal_ok=signal_ok, encoding=enc, psdu_len=length,
                     n_sym=n_sym, n_sym_out=n_out, complete=complete, snr_db=snr, idx=idx)

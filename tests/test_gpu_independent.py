@@ -5,7 +5,9 @@ HIP chain through the C ABI on the same random frames: same trigger, frame start
 accuracy; hard decisions equal but for points within float32 noise of a decision boundary (counted, bounded, recorded in
 gpurun_out/r04_gpu_vs_independent.json).  This is not bit parity -- the kernels run the float32 SPEC arithmetic, the
 independent receiver float64 -- it is the check that what the kernels compute IS the chain of the reference's flowgraph
-(`gnu_radio/IRS_AP.py:268-285`) as the survey's appendix describes it, made by code that was not derived from the oracle."""
+(`gnu_radio/IRS_AP.py:268-285`) as the survey's appendix describes it, made by code that was not derived from the oracle.
+The soft values (points, LLRs, CSI, moments), LMS / COMB / STA and the other operating points: tests/test_independent_eq.py,
+tests/test_gpu_independent_eq.py."""
 import json
 import os
 

@@ -9,7 +9,9 @@ float32 and a float64 evaluation of the same formulas is counted and bounded; a 
 modes (a sign, an index, a cadence, a constant) would show as a gross disagreement.
 
 Runs on the CPU (`-m "not gpu"`); the GPU is tied to the oracle's SPEC mode bit for bit by the `-m gpu` suite, and SPEC to
-LIBM by tests/test_spec_math.py and the measured distances of DESIGN.md section 2."""
+LIBM by tests/test_spec_math.py and the measured distances of DESIGN.md section 2.
+The soft values (points, LLRs, CSI, moments), LMS / COMB / STA and the other operating points: tests/test_independent_eq.py,
+tests/test_gpu_independent_eq.py."""
 import json
 import os
 
