@@ -669,3 +669,77 @@ class channel_model(grshim.sync_block):
     def close(self):
         """Release the library handle."""
         self._rx.close()
+
+
+class wideband_combiner(grshim.sync_interpolator):
+    """The transmit counterpart of ``wifi_phy_rx_wideband`` (GNU Radio's ``pfb_synthesizer_ccf``): ``n_channels`` = 2, 4 or
+    8 ``complex64`` inputs at ``bandwidth``, one per adjacent channel, joined on the device by wifirx_combine (NUMERICS.md
+    rule 22) into one ``complex64`` output at ``n_channels`` times the rate; input k lands at the centre that
+    ``wifi_phy_rx_wideband`` gives channel k for the same ``stacking``.  ``gains``: one real factor per input, or None.
+
+    ``work()`` consumes n = min(len of every input, len(output_items[0]) // n_channels) items of each input, writes
+    n * n_channels items and returns that number.  The 23 samples of history per channel stay on the device, in two buffers
+    used in turn, and so does the stream index: the output does not depend on how the scheduler cuts the stream."""
+
+    def __init__(self, n_channels=4, stacking=1, gains=None, device=0):
+        self.n_channels, self.stacking = int(n_channels), int(stacking)
+        if self.n_channels not in capi.CHANNELIZER_CHANNELS:
+            raise ValueError("n_channels must be 2, 4 or 8")
+        if self.stacking not in (0, 1):
+            raise ValueError("stacking must be 0 or 1")
+        M = self.n_channels
+        grshim.sync_interpolator.__init__(self, "wideband_combiner", [np.complex64] * M, [np.complex64], M)
+        self.gains = None
+        self.set_gains(gains)
+        self._rx = capi.WifiRx(max_sym=1, device=device)           # the handle's receive side stays unused
+        self._m0 = 0                                                # stream index of the next input sample
+        self._hist = [self._rx.alloc(capi.CHANNELIZER_HIST * M * 8) for _ in range(2)]
+        self._hist_cur = None                                       # index of the buffer that holds the history; None: a new stream
+        self._d_in = self._d_out = None
+        self._cap = 0                                               # samples per channel the two buffers hold
+
+    def set_gains(self, gains):
+        """one finite real factor per input from the next ``work()`` on; None: no multiply"""
+        if gains is not None:
+            gains = np.array(gains, dtype=np.float32).reshape(-1)
+            if gains.size != self.n_channels or not np.isfinite(gains).all():
+                raise ValueError("gains: one finite value per channel")
+        self.gains = gains
+
+    def _reserve(self, n):
+        if n <= self._cap:
+            return
+        for b in (self._d_in, self._d_out):
+            if b is not None:
+                b.free()
+        self._cap = (n + n // 2 + 1) & ~1                           # even: every row starts on 16 bytes
+        self._d_in = self._rx.alloc(self._cap * self.n_channels * 8)
+        self._d_out = self._rx.alloc(self._cap * self.n_channels * 8)
+
+    def work(self, input_items, output_items):
+        M, out = self.n_channels, output_items[0]
+        n = min(min(len(x) for x in input_items[:M]), len(out) // M)
+        if n <= 0:
+            return 0
+        self._reserve(n)
+        rx = self._rx
+        for k in range(M):
+            x = np.ascontiguousarray(input_items[k][:n], dtype=np.complex64)
+            rx._check(capi.lib().wifirx_memcpy_h2d(rx._h, self._d_in.ptr + 8 * k * self._cap, x.ctypes.data, 8 * n))
+        nxt = 1 if self._hist_cur == 0 else 0
+        rx.combine_dev(self._d_in.ptr, self._cap, n, M, self.stacking, self._d_out.ptr, gains=self.gains,
+                       hist_ptr=None if self._hist_cur is None else self._hist[self._hist_cur].ptr,
+                       hist_out_ptr=self._hist[nxt].ptr, m0=self._m0)
+        out[:n * M] = self._d_out.download(np.complex64, n * M)    # ordered behind the kernel on the handle's stream
+        self._hist_cur, self._m0 = nxt, self._m0 + n
+        return n * M
+
+    def close(self):
+        """Release the device buffers and the handle."""
+        for b in list(getattr(self, "_hist", [])) + [getattr(self, "_d_in", None), getattr(self, "_d_out", None)]:
+            if b is not None:
+                b.free()
+        self._hist, self._d_in, self._d_out, self._cap = [], None, None, 0
+        if getattr(self, "_rx", None) is not None:
+            self._rx.close()
+            self._rx = None

@@ -48,7 +48,7 @@ EXPORTS = [
     "wifirx_mac_batch", "wifirx_link_stats", "wifirx_tx_batch_rates", "wifirx_link_stats_by_rate",
     "wifirx_channel_sro", "wifirx_resampler_table", "wifirx_channel_fading",
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
-    "wifirx_channelize", "wifirx_channelizer_table",
+    "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine",
 ]
 CHANNELIZER_CHANNELS = (2, 4, 8)    # wifirx_channelize: n_channels (NUMERICS.md rule 21)
 CHANNELIZER_HIST = 23               # input blocks of n_channels samples that a call takes from before its input
@@ -227,6 +227,8 @@ _lib.wifirx_push_iq.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c
 _lib.wifirx_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                    C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
 _lib.wifirx_channelizer_table.argtypes = [C.c_uint32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
+_lib.wifirx_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_uint32,
+                                C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -815,6 +817,38 @@ class WifiRx:
         self._check(_lib.wifirx_channelize(self._h, in_ptr, fmt, float(scale), hist_ptr, hist_out_ptr, int(n_channels),
                                            int(stacking), int(n_out), int(m0) & 0xFFFFFFFFFFFFFFFF, out_ptr,
                                            int(n_out if out_stride is None else out_stride)))
+
+    # -- wideband transmit (wifirx_combine; NUMERICS.md rule 22) --
+    def combine_dev(self, in_ptr, in_stride, n_in, n_channels, stacking, out_ptr, gains=None, hist_ptr=None, hist_out_ptr=None,
+                    m0=0):
+        """wifirx_combine on device pointers: n_channels rows of n_in complex64 at in_ptr, row k at in_ptr + 8 * k * in_stride
+        bytes -> n_in * n_channels complex64 at out_ptr.  gains: n_channels finite floats (host; None: no multiply).
+        hist_ptr: n_channels rows of 23 samples in front (None: zeros); hist_out_ptr: where the next call's hist goes
+        (None: nowhere).  Asynchronous on the handle's stream: sync() before another handle reads the output."""
+        g = None
+        if gains is not None:
+            g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+            if g.size != int(n_channels):
+                raise ValueError("one gain per channel is required")
+            g = g.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(_lib.wifirx_combine(self._h, in_ptr, int(in_stride), g, hist_ptr, hist_out_ptr, int(n_channels),
+                                        int(stacking), int(n_in), int(m0) & 0xFFFFFFFFFFFFFFFF, out_ptr))
+
+    def combine(self, streams, stacking, gains=None) -> np.ndarray:
+        """combine_dev on host arrays: n_channels complex streams of one length n from the start of a stream -> complex64
+        [n * n_channels] (PCIe-bound convenience)"""
+        u = np.ascontiguousarray(np.asarray(streams, dtype=np.complex64))
+        if u.ndim != 2:
+            raise ValueError("streams of one length are required")
+        M, n = u.shape
+        d_in, d_out = self.alloc(max(u.nbytes, 1)), self.alloc(max(n * M, 1) * 8)
+        try:
+            d_in.upload(u)
+            self.combine_dev(d_in.ptr, n, n, M, stacking, d_out.ptr, gains)
+            return d_out.download(np.complex64, n * M)       # ordered behind the kernel on the handle's stream
+        finally:
+            d_in.free()
+            d_out.free()
 
     # -- stream mode --
     def push(self, iq: np.ndarray):

@@ -40,6 +40,7 @@ def to_python(msg):
 
 if HAVE_GNURADIO:  # pragma: no cover
     sync_block = _gr.sync_block
+    sync_interpolator = _gr.sync_interpolator
     basic_block = _gr.basic_block
 else:
     class basic_block:
@@ -76,6 +77,17 @@ else:
         def work(self, input_items, output_items):  # pragma: no cover - overridden
             raise NotImplementedError
 
+    class sync_interpolator(sync_block):
+        """gr.sync_interpolator: ``work()`` writes ``interp`` output items per input item it consumes and returns the
+        number of output items; ``len(output_items[0])`` bounds the call."""
+
+        def __init__(self, name="", in_sig=None, out_sig=None, interp=1):
+            sync_block.__init__(self, name=name, in_sig=in_sig, out_sig=out_sig)
+            self._interp = int(interp)
+
+        def interpolation(self):
+            return self._interp
+
 
 class sink_block(basic_block if not HAVE_GNURADIO else object):
     """Message sink with one input port ``in`` that hands every PDU (as Python) to ``fn`` -- what
@@ -104,8 +116,9 @@ class pmt_shim:
 
 
 class gr_shim:
-    """``from gnuradio import gr`` for the shim: the two block classes."""
+    """``from gnuradio import gr`` for the shim: the block classes."""
     sync_block = sync_block
+    sync_interpolator = sync_interpolator
     basic_block = basic_block
 
 

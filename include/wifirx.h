@@ -610,6 +610,37 @@ int  wifirx_channelize(wifirx_handle* h, const void* in, int fmt, float scale, c
  * no device.  WIFIRX_EINVAL for another n_channels or a NULL argument. */
 int  wifirx_channelizer_table(uint32_t n_channels, const float** taps, uint32_t* n_taps);
 
+/* Wideband transmit (NUMERICS.md rule 22): join M = n_channels in {2, 4, 8} streams at fs, one per adjacent channel of width
+ * fs, into one stream sampled at M * fs -- the critically sampled polyphase synthesis bank that mirrors wifirx_channelize, 24
+ * taps per branch, on the device (GNU Radio's pfb_synthesizer_ccf).  Stream k lands at wifirx_channelize's centre
+ * f_k = (k + stacking/2 - M/2) / M cycles per output sample.  With h the prototype of wifirx_channelizer_table and n the
+ * stream's output index:  x[n] = sum_k g_k exp(j 2 pi f_k n) sum_m u_k[m] M h[n - m M].  Amplitudes are kept (a unit-power
+ * stream gives unit power in its channel); the filter delays by (24 M - 1) / 2 output samples, and through
+ * wifirx_channelize every stream comes back delayed by exactly 23 channel samples.  n_in samples per channel give exactly
+ * n_in * M output samples.
+ *   in          DEVICE, 8-byte aligned float pairs: channel k's n_in samples start at in + 2 * k * in_stride floats -- the layout
+ *               of wifirx_channelize's out, and of M wifirx_tx_batch sample buffers laid side by side.
+ *   gains       HOST, M finite floats g_k (one real multiply per component), or NULL for no multiply.  They travel as kernel
+ *               arguments: nothing is uploaded, and the array may be reused as soon as the call returns.
+ *   hist        DEVICE, M rows of 23 float pairs, row k at hist + 2 * 23 * k floats: the 23 samples of every channel in front
+ *               of in; NULL = zeros (the start of a stream).
+ *   hist_out    DEVICE, may be NULL: receives the last 23 samples of (hist || in) of every channel, same layout, by a copy
+ *               queued behind the kernel.  Passed on as the next call's hist, with m0 + n_in, it makes a stream cut into calls
+ *               byte-identical to the uncut one.  It must not overlap hist, in or out: a caller alternates between two buffers.
+ *   m0          the stream index of the call's first input sample (its parity enters for stacking = 1).
+ *   out         DEVICE, 8-byte aligned, n_in * M float pairs; nothing else is written.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for NULL in / out with n_in > 0, n_channels outside {2, 4, 8},
+ * stacking outside {0, 1}, a gain that is not finite, misaligned buffers, and any overlap among the M rows of in (taken as
+ * one range, first row to last), hist, hist_out and out; WIFIRX_ERANGE for in_stride < n_in, in_stride > 2^44 or
+ * n_in > 2^40.  n_in = 0 returns WIFIRX_OK and still produces hist_out (= hist, or zeros) when asked.  One kernel launch per
+ * call, and one small copy kernel for hist_out.
+ * ORDER: as wifirx_iq_to_f32 -- asynchronous on the handle's stream, behind the handle's earlier calls; every buffer must stay
+ * valid until the work has run.  The rows are usually produced by OTHER handles (wifirx_tx_batch, wifirx_channel), each on its
+ * own stream, and out may be consumed by another: wifirx_sync() on the producing handle (or an event on wifirx_stream())
+ * comes between their calls and this one, and between this one and the consumer's. */
+int  wifirx_combine(wifirx_handle* h, const float* in, uint64_t in_stride, const float* gains, const float* hist,
+                    float* hist_out, uint32_t n_channels, int stacking, uint64_t n_in, uint64_t m0, float* out);
+
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);
 int  wifirx_dev_free(wifirx_handle* h, void* p);

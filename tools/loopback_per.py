@@ -38,7 +38,18 @@ rule 20), on the device.  Full scale, 2^(B-1), is set --backoff-db above the RMS
 its first 256 rows, which are downloaded for it).  Per SNR point: the float32 loop-back without a converter, then per B the FER
 hard and soft and the share of clipped components, every B on the same channel output.
 
-    python tools/loopback_per.py --adc-bits 8 6 4 12 16 --backoff-db 12 --snr 20 25 30 [--frames 262144] [--out profiles/loopback_adc.json]"""
+    python tools/loopback_per.py --adc-bits 8 6 4 12 16 --backoff-db 12 --snr 20 25 30 [--frames 262144] [--out profiles/loopback_adc.json]
+
+--wideband M asks what a channel loses when its neighbours are loud: M = 2, 4 or 8 adjacent channels, the victim (--victim K)
+carrying config 3's frames in their rows (flat channel, or --multipath; CFO uniform in +-20 ppm) and every other channel frames
+of the same kind back to back, A dB above the victim for every A of --neighbour-db (and, first, silent).  Per point: the M rows
+-> wifirx_combine with the gains (NUMERICS.md rule 22) -> wideband AWGN (wifirx_channel, one tap, in place, noise_voltage
+sqrt(M): unit variance per channel bandwidth) -> with --adc-bits B, wifirx_iq_from_f32 to B bits at --backoff-db over the wide
+stream's RMS -> wifirx_channelize (rule 21; the victim comes back 23 samples later in its rows) -> demod with each equaliser of
+--eq (default ls) and both decoders -> wifirx_link_stats on the victim.  Beside it, per SNR, the same victim rows through the
+single-channel path without either bank.
+
+    python tools/loopback_per.py --wideband 4 --victim 1 --neighbour-db 0 10 20 25 30 35 40 50 --snr 25 30 [--frames 262144] [--out profiles/loopback_wideband.json]"""
 import argparse
 import json
 import math
@@ -103,8 +114,14 @@ def main():
     ap.add_argument("--adc-bits", type=int, nargs="+", default=None, help="a converter of these many bits in front of the receiver")
     ap.add_argument("--adc-format", choices=("auto", "sc16", "sc8"), default="auto", help="with --adc-bits: the container (auto: sc8 up to 8 bits)")
     ap.add_argument("--backoff-db", type=float, default=12.0, help="with --adc-bits: full scale above the RMS of the channel output")
+    ap.add_argument("--wideband", type=int, default=None, choices=(2, 4, 8), help="M adjacent channels through both banks")
+    ap.add_argument("--victim", type=int, default=1, help="with --wideband: the channel that is scored, 0 .. M - 1")
+    ap.add_argument("--stacking", type=int, default=1, choices=(0, 1), help="with --wideband")
+    ap.add_argument("--neighbour-db", type=float, nargs="+", default=[0, 20, 30, 40], help="with --wideband: the other channels' power above the victim's")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.wideband is not None:
+        return wideband_main(a)
     if a.adc_bits is not None:
         return adc_main(a)
     if a.doppler is not None:
@@ -232,6 +249,113 @@ def adc_main(a):
                        "channel output (its first 256 rows)" % (n, a.backoff_db),
            "columns": "per SNR: float32 = no converter; adc = one entry per B: fer (hard), fer_soft, clipped_share of the components",
            "backoff_db": a.backoff_db, "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def wideband_main(a):
+    if a.rates or a.host_stats or a.locked_clock or a.doppler is not None:
+        raise SystemExit("--wideband stands alone: not with --rates, --host-stats, --locked-clock or --doppler")
+    M, s, victim = a.wideband, a.stacking, a.victim
+    if not 0 <= victim < M:
+        raise SystemExit("--victim 0 .. M - 1")
+    if a.adc_bits is not None and (len(a.adc_bits) != 1 or not 2 <= a.adc_bits[0] <= 16):
+        raise SystemExit("--wideband takes one --adc-bits value, 2 .. 16")
+    n = a.frames or 262144
+    eqs = a.eq or ["ls"]
+    n_sym, nb = txgen.n_sym_for(PSDU_LEN, ENC), txgen.RATE_TABLE[ENC][0]
+    taps = np.load(os.path.join(ROOT, "tests", "golden", "sv_taps.npy")).astype(np.complex64) if a.multipath else (1.0,)
+    row = n * SLOT                                            # samples per channel
+    back = txgen.frame_samples(PSDU_LEN, ENC)
+    back += back & 1                                          # the neighbours' frames back to back, in rows of even length
+    n_nb = row // back
+    rx = capi.WifiRx(max_sym=n_sym, llr_bits=nb, chan_est=capi.EQ_LS, device=0)
+    t_all = time.perf_counter()
+    d_psdu, d_psdu_nb = rx.alloc(n * PSDU_LEN), rx.alloc(n_nb * PSDU_LEN)
+    rows, iq = rx.alloc(row * 8), rx.alloc(row * 8)
+    chans, wide, split = rx.alloc(M * row * 8), rx.alloc(M * row * 8), rx.alloc(M * row * 8)
+    d_int = rx.alloc(M * row * 4) if a.adc_bits else None
+    rx.mac_batch_dev(d_psdu.ptr, PSDU_LEN, n, None, payload_len=PSDU_LEN - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, row, d_psdu.ptr, ENC, psdu_len=np.full(n, PSDU_LEN, np.uint32), psdu_stride=PSDU_LEN, lead=LEAD, row_len=SLOT)
+    dev = rx.alloc_out(n, psdu_stride=304, want_hbits=True)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * n_sym * 48), hbits=rx.alloc(n * n_sym * 48), psdu=d_psdu,
+               psdu_stride=PSDU_LEN)
+    rx.demod_batch_dev(rows.ptr, SLOT, n, ref)
+    assert rx.link_stats(n, ref, ref)["frames_ref"] == n, "a clean frame was not demodulated"
+    # the M channel rows, unit power: the victim's frames through their channel without noise, the others back to back
+    cfo = np.random.default_rng(a.seed).uniform(-CFO_20PPM, CFO_20PPM, n).astype(np.float32)
+    rx.channel_dev(rows.ptr, chans.ptr + 8 * victim * row, row, n, row_len=SLOT, taps=taps, cfo=cfo, gain=1.0, noise_voltage=0.0)
+    nb_off = np.arange(n_nb + 1, dtype=np.uint64) * back
+    nb_off[-1] = row                                          # the last row takes the rest: zeros
+    for k in range(M):
+        if k != victim:
+            rx.mac_batch_dev(d_psdu_nb.ptr, PSDU_LEN, n_nb, None, payload_len=PSDU_LEN - 28, payload_seed=a.seed + 100 * (k + 1))
+            rx.tx_batch_dev(chans.ptr + 8 * k * row, row, d_psdu_nb.ptr, ENC, psdu_len=np.full(n_nb, PSDU_LEN, np.uint32),
+                            psdu_stride=PSDU_LEN, lead=0, row_off=nb_off)
+
+    def receive(ptr):
+        by_eq = {}
+        for name in eqs:
+            rx.set_param(capi.P_CHAN_EST, EQUALISERS[name])
+            rx.demod_batch_dev(ptr, SLOT, n, dev)
+            rx.decode_batch_dev(n, dev)
+            hard = rx.link_stats(n, dev, ref)
+            rx.decode_batch_soft_dev(n, dev)
+            soft = rx.link_stats(n, dev, ref)
+            by_eq[name] = {"fer": hard["fer"], "fer_soft": soft["fer"], "coded_ber": hard["coded_ber"],
+                           "counts": {k: hard[k] for k in COUNTERS}, "counts_soft": {k: soft[k] for k in COUNTERS}}
+        rx.set_param(capi.P_CHAN_EST, capi.EQ_LS)
+        return by_eq
+
+    points = []
+    for snr in a.snr:
+        g = math.sqrt(10 ** (snr / 10))
+        seed = 9000 + int(snr) + (a.seed << 32)
+        t0 = time.perf_counter()
+        rx.channel_dev(chans.ptr + 8 * victim * row, iq.ptr, row, n, row_len=SLOT, taps=(1.0,), gain=g, noise_voltage=1.0, seed=seed)
+        pt = {"snr_db": snr, "frames": n, "single_channel": receive(iq.ptr), "seconds_single_channel": time.perf_counter() - t0, "wideband": []}
+        for above in [None] + list(a.neighbour_db):
+            t0 = time.perf_counter()
+            gains = np.full(M, 0.0 if above is None else g * 10 ** (above / 20), np.float32)
+            gains[victim] = g
+            rx.combine_dev(chans.ptr, row, row, M, s, wide.ptr, gains=gains)
+            rx.channel_dev(wide.ptr, wide.ptr, M * row, n, row_len=M * SLOT, taps=(1.0,), gain=1.0, noise_voltage=math.sqrt(M), seed=seed + 1)
+            r = {"neighbour_db": above}
+            if a.adc_bits:
+                b = a.adc_bits[0]
+                fmt = a.adc_format if a.adc_format != "auto" else ("sc8" if b <= 8 else "sc16")
+                head = wide.download(np.complex64, min(n, 256) * M * SLOT)
+                rms = math.sqrt(float(np.mean(np.abs(head.astype(np.complex128)) ** 2)) / 2.0)      # of a component
+                scale_q = float(np.float32(2.0 ** (b - 1) / (rms * 10.0 ** (a.backoff_db / 20.0))))
+                clipped = rx.iq_from_f32_dev(wide.ptr, M * row, fmt, d_int.ptr, scale_q, b, count=True)
+                rx.channelize_dev(d_int.ptr, fmt, row, M, s, split.ptr, row, scale=float(np.float32(1.0 / scale_q)))
+                r.update(bits=b, format=fmt, scale=scale_q, clipped_share=clipped / (2.0 * M * row))
+            else:
+                rx.channelize_dev(wide.ptr, "fc32", row, M, s, split.ptr, row)
+            r["by_equaliser"] = receive(split.ptr + 8 * victim * row)
+            r["fer"] = {k: v["fer"] for k, v in r["by_equaliser"].items()}
+            r["fer_soft"] = {k: v["fer_soft"] for k, v in r["by_equaliser"].items()}
+            r["seconds"] = time.perf_counter() - t0
+            pt["wideband"].append(r)
+            print(json.dumps({"snr_db": snr, "neighbour_db": above, "fer": r["fer"], "fer_soft": r["fer_soft"], "seconds": r["seconds"]}), file=sys.stderr)
+        points.append(pt)
+    seconds_total = time.perf_counter() - t_all
+    rx.free_out(ref)
+    rx.free_out(dev)
+    for d in (d_psdu_nb, rows, iq, chans, wide, split, d_int):
+        if d is not None:
+            d.free()
+    rx.close()
+    res = {"workload": "wideband loop-back on the device: M = %d channels, stacking %d, victim %d with %d distinct frames per point (64-QAM 3/4, PSDU "
+                       "294 B, rows of 1472, lead 160, %s, CFO uniform in +-20 ppm), every other channel the same kind of frames back to back at "
+                       "neighbour_db above the victim (null: silent); wifirx_combine -> AWGN of unit variance per channel bandwidth -> %s"
+                       "wifirx_channelize -> demod, hard and soft decode_mac" % (
+                           M, s, victim, n, "sv_taps.npy sets cycling" if a.multipath else "flat channel",
+                           "a converter of %d bits, %.1f dB back-off -> " % (a.adc_bits[0], a.backoff_db) if a.adc_bits else ""),
+           "columns": "per SNR: single_channel = the victim's rows without either bank; wideband = one entry per neighbour power",
+           "equalisers": eqs, "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
