@@ -283,6 +283,8 @@ int wifirx_create(const wifirx_config* cfg, wifirx_handle** out)
         return fail(nullptr, WIFIRX_EINVAL, "chan_est must be one of WIFIRX_EQ_LS, LMS, COMB, STA");
     if (!(cfg->bandwidth > 0) || !(cfg->frequency > 0)) return fail(nullptr, WIFIRX_EINVAL, "bandwidth/frequency must be > 0");
     if (cfg->min_plateau < 0 || cfg->min_plateau > 32) return fail(nullptr, WIFIRX_EINVAL, "min_plateau out of range");
+    // the detect phase compares squares (NUMERICS.md rule 3): a negative threshold would act as its magnitude
+    if (!(cfg->sensitivity >= 0)) return fail(nullptr, WIFIRX_EINVAL, "sensitivity must be >= 0");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, WIFIRX_ENODEV, "no HIP device: libwifirx has no CPU fallback");
@@ -333,6 +335,7 @@ int wifirx_set_param(wifirx_handle* h, int id, double value)
         h->cfg.frequency = value;
         return WIFIRX_OK;
     case WIFIRX_P_SENSITIVITY:
+        if (!(value >= 0)) return fail(h, WIFIRX_EINVAL, "sensitivity must be >= 0");      // squared comparison, NUMERICS.md rule 3
         h->cfg.sensitivity = (float)value;
         return WIFIRX_OK;
     case WIFIRX_P_CHAN_EST:

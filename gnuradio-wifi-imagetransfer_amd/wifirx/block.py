@@ -126,8 +126,8 @@ class wifi_phy_rx(grshim.sync_block):
         return self.sensitivity
 
     def set_sensitivity(self, sensitivity):
+        self._rx.set_param(capi.P_SENSITIVITY, float(sensitivity))      # refuses a negative value or a NaN: the old one stays
         self.sensitivity = float(sensitivity)
-        self._rx.set_param(capi.P_SENSITIVITY, self.sensitivity)
 
     def get_soft_decision(self):
         return self.soft_decision

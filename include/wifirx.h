@@ -99,7 +99,11 @@ typedef struct wifirx_config {
     int32_t  device;       /* HIP device ordinal */
     double   bandwidth;    /* sample rate in Hz: wifi_phy_hier `bandwidth` (grc:83-92) */
     double   frequency;    /* carrier in Hz:    wifi_phy_hier `frequency` (grc:501-510) */
-    float    sensitivity;  /* sync_short threshold: wifi_phy_hier `sensitivity` (grc:681-690), 0.56 */
+    float    sensitivity;  /* sync_short threshold: wifi_phy_hier `sensitivity` (grc:681-690), 0.56.  Must be >= 0: the
+                              detect phase compares |A|^2 > (sensitivity * P)^2 (NUMERICS.md rule 3), under which a
+                              negative value would act as its magnitude, whereas upstream's |A| / P > sensitivity is then
+                              true wherever P > 0.  A negative value or a NaN is WIFIRX_EINVAL, here and in
+                              wifirx_set_param. */
     int32_t  min_plateau;  /* sync_short min_plateau, 2 (gnu_radio/IRS_AP.py:268) */
     int32_t  chan_est;     /* WIFIRX_EQ_*: wifi_phy_hier `chan_est` (grc:299-308, IRS_AP.py:139-141) */
     uint32_t max_sym;      /* output capacity per frame in data symbols (<= WIFIRX_MAX_SYM) */
@@ -113,6 +117,9 @@ typedef struct wifirx_config {
  * (gnu_radio/IRS_user.py:229,265,273; gnu_radio/IRS_AP.py:348,373,382) */
 #define WIFIRX_P_BANDWIDTH   1
 #define WIFIRX_P_FREQUENCY   2
+/* >= 0 (see wifirx_config.sensitivity); a refused value leaves the handle's value as it was.  In stream mode the new value
+ * acts on every sample the detection has not yet run over: the samples of later pushes and, with WIFIRX_P_STREAM_BATCH,
+ * the samples already pushed that are still staged for their batch.  Samples already detected keep their triggers. */
 #define WIFIRX_P_SENSITIVITY 3
 #define WIFIRX_P_CHAN_EST    4
 /* stream mode: wifirx_push only collects samples until this many are waiting, then detects / demodulates /

@@ -60,12 +60,30 @@ def test_create_argument_checks():
     bad = capi.Config(99, 0, 20e6, 5.89e9, 0.56, 2, 0, 64, 0, 0, 0, 0)
     assert capi.lib().wifirx_create(ctypes.byref(bad), ctypes.byref(h)) == -1
     for kw in (dict(max_sym=0), dict(max_sym=512), dict(llr_bits=3), dict(chan_est=4), dict(chan_est=-1), dict(bandwidth=0.0)):
-        vals = dict(abi_version=2, device=0, bandwidth=20e6, frequency=5.89e9, sensitivity=0.56, min_plateau=2,
+        vals = dict(abi_version=capi.ABI_VERSION, device=0, bandwidth=20e6, frequency=5.89e9, sensitivity=0.56, min_plateau=2,
                     chan_est=0, max_sym=64, llr_bits=0, want_carrier=0, max_batch=0, max_slot_len=0)
         vals.update(kw)
         cfg = capi.Config(*[vals[f] for f, _ in capi.Config._fields_])
         assert capi.lib().wifirx_create(ctypes.byref(cfg), ctypes.byref(h)) == -1, kw
-        assert b"" != capi.lib().wifirx_last_error(None)
+        assert capi.lib().wifirx_last_error(None) not in (b"", b"abi_version mismatch"), kw     # refused for ITS field
+
+
+def test_create_refuses_a_sensitivity_the_squared_comparison_cannot_honour():
+    """negative or NaN (NUMERICS.md rule 3): refused before the device is looked at, with a text that names the field
+    (that 0 is accepted is asserted where a device is: tests/test_gpu_detect_rows.py)"""
+    from wifirx import capi
+
+    def create(sens):
+        h = ctypes.c_void_p()
+        cfg = capi.Config(capi.ABI_VERSION, 0, 20e6, 5.89e9, sens, 2, 0, 64, 0, 0, 0, 0)
+        rc = capi.lib().wifirx_create(ctypes.byref(cfg), ctypes.byref(h))
+        return rc, capi.lib().wifirx_last_error(None)
+    for sens in (-0.5, -1e-30, float("-inf"), float("nan")):
+        rc, msg = create(sens)
+        assert rc == capi.EINVAL and b"sensitivity" in msg, sens
+        with pytest.raises(capi.WifiRxError) as e:
+            capi.WifiRx(sensitivity=sens)
+        assert e.value.code == capi.EINVAL
 
 
 def test_tools_and_examples_do_not_touch_the_oracle():
