@@ -30,6 +30,7 @@
 #include "wr_convert.h"
 #include "wr_channelizer.h"
 #include "wr_combiner.h"
+#include "wr_diversity.h"
 
 // The stream's per-frame outputs (stream_outs, wifirx_api_stream.inc) and the host copy of a batch of them, shared by its
 // frames: output o of frame k is the width[o] bytes at blob[off[o] + k * width[o]] (width 0: the handle did not produce o).
@@ -610,3 +611,4 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_convert.inc"
 #include "wifirx_api_channelizer.inc"
 #include "wifirx_api_combiner.inc"
+#include "wifirx_api_diversity.inc"

@@ -48,8 +48,11 @@ EXPORTS = [
     "wifirx_mac_batch", "wifirx_link_stats", "wifirx_tx_batch_rates", "wifirx_link_stats_by_rate",
     "wifirx_channel_sro", "wifirx_resampler_table", "wifirx_channel_fading",
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
-    "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine",
+    "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine", "wifirx_diversity_combine",
 ]
+DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
+DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
+DIV_MAX_ANT = 8
 CHANNELIZER_CHANNELS = (2, 4, 8)    # wifirx_channelize: n_channels (NUMERICS.md rule 21)
 CHANNELIZER_HIST = 23               # input blocks of n_channels samples that a call takes from before its input
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
@@ -229,6 +232,8 @@ _lib.wifirx_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C
 _lib.wifirx_channelizer_table.argtypes = [C.c_uint32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
 _lib.wifirx_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_uint32,
                                 C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+_lib.wifirx_diversity_combine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.c_uint32, C.c_int, C.POINTER(C.c_float),
+                                          C.POINTER(Out), C.c_void_p]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -849,6 +854,61 @@ class WifiRx:
         finally:
             d_in.free()
             d_out.free()
+
+    # -- receive diversity (wifirx_diversity_combine; NUMERICS.md rule 23) --
+    def diversity_combine_dev(self, ins, n_slots, out, mode=DIV_MRC, ant_gain=None, used_mask_ptr=None):
+        """wifirx_diversity_combine on device buffers: ins = one alloc_out dict per antenna after its demod (frames, carrier and
+        csi are read; they may belong to other handles with the same max_sym, synchronised first), out = an alloc_out dict
+        without hbits that receives frames and, where allocated, idx, llr and carrier.  mode: DIV_MRC / DIV_SELECT (or "mrc" /
+        "select").  ant_gain: one finite float >= 0 per antenna, the inverse noise power (None: equal noise).  used_mask_ptr:
+        n_slots device bytes (None: not wanted).  Asynchronous on the handle's stream, behind its earlier calls."""
+        mode = DIV_MODES[mode] if isinstance(mode, str) else int(mode)
+        arr = (Out * max(len(ins), 1))(*[self._out_struct(d) for d in ins])
+        g = None
+        if ant_gain is not None:
+            g = np.ascontiguousarray(ant_gain, dtype=np.float32).reshape(-1)
+            if g.size != len(ins):
+                raise ValueError("one gain per antenna is required")
+            g = g.ctypes.data_as(C.POINTER(C.c_float))
+        o = self._out_struct(out)
+        self._check(_lib.wifirx_diversity_combine(self._h, len(ins), arr, int(n_slots), mode, g, C.byref(o), used_mask_ptr))
+
+    def demod_diversity(self, iqs, slot_len, mode=DIV_MRC, ant_gain=None, soft=False, psdu_stride=2048) -> dict:
+        """Host convenience (PCIe-bound): iqs = one complex64 array per antenna, slot i of each the same transmission.  Every
+        array is demodulated, the batches are combined (diversity_combine_dev) and the result is decoded (soft=True: on the
+        LLRs).  The handle needs want_carrier (and llr_bits > 0 for soft).  Returns the combined batch -- frames, psdu, idx,
+        llr, carrier -- and used_mask (uint8 [n_slots], bit a = antenna a contributed)."""
+        if not self.cfg.want_carrier:
+            raise ValueError("demod_diversity needs a handle created with want_carrier=True")
+        iqs = [np.ascontiguousarray(x, dtype=np.complex64).reshape(-1) for x in iqs]
+        if not iqs or any(x.size != iqs[0].size for x in iqs) or iqs[0].size % slot_len:
+            raise ValueError("one array of n_slots * slot_len samples per antenna is required")
+        n = iqs[0].size // slot_len
+        d_iq, ins, out, d_mask = self.alloc(max(iqs[0].nbytes, 1)), [], None, None
+        try:
+            for x in iqs:
+                ins.append(self.alloc_out(n, want_csi=True))
+                d_iq.upload(x)                                  # ordered behind the previous antenna's demod on the stream
+                self.demod_batch_dev(d_iq.ptr, slot_len, n, ins[-1])
+            out = self.alloc_out(n, psdu_stride=psdu_stride)
+            d_mask = self.alloc(max(n, 1)).upload(np.zeros(max(n, 1), np.uint8))
+            self.diversity_combine_dev(ins, n, out, mode, ant_gain, d_mask.ptr)
+            if soft:
+                self.decode_batch_soft_dev(n, out)
+            else:
+                self.decode_batch_dev(n, out)
+            self.sync()
+            r = self.download_out(out, n)
+            r["used_mask"] = d_mask.download(np.uint8, n)
+            return r
+        finally:
+            d_iq.free()
+            for d in ins:
+                self.free_out(d)
+            if out is not None:
+                self.free_out(out)
+            if d_mask is not None:
+                d_mask.free()
 
     # -- stream mode --
     def push(self, iq: np.ndarray):

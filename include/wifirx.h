@@ -648,6 +648,40 @@ int  wifirx_channelizer_table(uint32_t n_channels, const float** taps, uint32_t*
 int  wifirx_combine(wifirx_handle* h, const float* in, uint64_t in_stride, const float* gains, const float* hist,
                     float* hist_out, uint32_t n_channels, int stacking, uint64_t n_in, uint64_t m0, float* out);
 
+/* Receive diversity (NUMERICS.md rule 23): combine the equalised points of n_ant antennas' demodulated batches into one batch
+ * to decode.  Slot i of every in[a] is the same transmission, demodulated from antenna a's samples by wifirx_demod_batch with
+ * `carrier` and `csi` outputs (by this handle one after the other, or by other handles with the same max_sym).  Per slot: the
+ * antennas whose record has WIFIRX_F_SIGNAL and WIFIRX_F_COMPLETE are usable; the reference antenna r is the usable one with
+ * the greatest snr_db (the lowest index on ties); those usable antennas whose encoding and psdu_len equal r's contribute.
+ *   WIFIRX_DIV_MRC     maximal-ratio combining after equalisation: per data carrier Y = sum_a u_a Y_a with u_a = w_a / sum w,
+ *                      w_a = |H_a|^2 of antenna a's LS estimate (the weight of WIFIRX_P_LLR_CSI) times ant_gain[a]; a carrier
+ *                      whose weights sum to 0 or to nothing finite takes the reference antenna's point as it is
+ *   WIFIRX_DIV_SELECT  selection: only r contributes -- every output is a copy of antenna r's
+ *   in         HOST [n_ant], n_ant = 1 .. 8; of in[a] only frames, carrier, csi and on_device are read: DEVICE buffers,
+ *              16-byte aligned, in the row layout of this handle's max_sym
+ *   ant_gain   HOST [n_ant], finite and >= 0: the inverse noise power of each antenna's receiver; NULL = equal noise (no
+ *              multiply)
+ *   out        DEVICE, 16-byte aligned.  frames (required) receives r's record with WIFIRX_F_DECODED / WIFIRX_F_CRC_OK cleared
+ *              and WIFIRX_F_LLR set exactly when LLRs were written.  idx, llr, carrier are each optional (a decoder afterwards
+ *              needs idx or llr) and are written for the record's n_sym symbols only; llr as wifirx_demod_batch writes it: when
+ *              n_bpsc <= llr_bits, times the summed weight under WIFIRX_P_LLR_CSI, in the handle's WIFIRX_P_LLR_FORMAT.  A slot
+ *              without a usable antenna gets antenna 0's record with COMPLETE, LLR, DECODED and CRC_OK cleared and nothing else.
+ *              hbits must be NULL: the planes are not produced here (wifirx_decode_batch then packs them from idx); psdu,
+ *              csi and sym_stats are not looked at.
+ *   used_mask  DEVICE [n_slots], may be NULL: bit a = antenna a contributed to the slot (0: no usable antenna)
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for NULL in / out / out->frames, n_ant outside 1 .. 8, an
+ * unknown mode, host buffers (on_device = 0), misaligned buffers, an antenna without frames, carrier or csi, an ant_gain that
+ * is not finite or is negative, out->llr on a handle with llr_bits = 0, out->hbits != NULL, and an output pointer equal to an
+ * input pointer; WIFIRX_ERANGE for n_slots above the handle's max_batch.  n_slots = 0 does nothing and returns WIFIRX_OK.
+ * One kernel launch per call.
+ * ORDER: as wifirx_channel -- `in` and ant_gain travel as kernel arguments, so they may be reused when the call returns; the
+ * kernel runs asynchronously on the handle's stream, behind the handle's earlier calls: demod, combine, decode on one handle
+ * need no wifirx_sync in between.  Batches demodulated by OTHER handles must have finished first (wifirx_sync on them). */
+#define WIFIRX_DIV_MRC    0
+#define WIFIRX_DIV_SELECT 1
+int  wifirx_diversity_combine(wifirx_handle* h, uint32_t n_ant, const wifirx_out* in, uint32_t n_slots, int mode,
+                              const float* ant_gain, const wifirx_out* out, uint8_t* used_mask);
+
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);
 int  wifirx_dev_free(wifirx_handle* h, void* p);

@@ -49,7 +49,16 @@ stream's RMS -> wifirx_channelize (rule 21; the victim comes back 23 samples lat
 --eq (default ls) and both decoders -> wifirx_link_stats on the victim.  Beside it, per SNR, the same victim rows through the
 single-channel path without either bank.
 
-    python tools/loopback_per.py --wideband 4 --victim 1 --neighbour-db 0 10 20 25 30 35 40 50 --snr 25 30 [--frames 262144] [--out profiles/loopback_wideband.json]"""
+    python tools/loopback_per.py --wideband 4 --victim 1 --neighbour-db 0 10 20 25 30 35 40 50 --snr 25 30 [--frames 262144] [--out profiles/loopback_wideband.json]
+
+--antennas asks what receive diversity buys in fading: the same TX rows (--psdu-len bytes at --encoding, fixed rows of lead 160 +
+frame + 79) go through one wifirx_channel_fading call per antenna -- flat Rayleigh (Rician with --k-factor), Doppler the first
+value of --doppler (default 0: one static gain per row and antenna), a fade_seed and a noise seed of its own per antenna, no
+carrier offset --, then one demod per antenna, wifirx_diversity_combine (NUMERICS.md rule 23) in every mode of --diversity,
+decode_mac hard and soft, and wifirx_link_stats.  Per SNR: the FER of every antenna count given (1 = antenna 0 alone, without
+the combiner) and mode.  The counts nest: A antennas are the first A of the largest count, so the columns share their channels.
+
+    python tools/loopback_per.py --antennas 1 2 4 --diversity mrc select --psdu-len 294 --encoding 2 --snr 5 10 15 20 25 [--frames 65536] [--out profiles/loopback_diversity.json]"""
 import argparse
 import json
 import math
@@ -118,8 +127,13 @@ def main():
     ap.add_argument("--victim", type=int, default=1, help="with --wideband: the channel that is scored, 0 .. M - 1")
     ap.add_argument("--stacking", type=int, default=1, choices=(0, 1), help="with --wideband")
     ap.add_argument("--neighbour-db", type=float, nargs="+", default=[0, 20, 30, 40], help="with --wideband: the other channels' power above the victim's")
+    ap.add_argument("--antennas", type=int, nargs="+", default=None, help="receive diversity: these antenna counts, 1 .. 8")
+    ap.add_argument("--diversity", nargs="+", choices=sorted(capi.DIV_MODES, key=capi.DIV_MODES.get), default=None,
+                    help="with --antennas: the combiner's modes (default both)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.antennas is not None:
+        return diversity_main(a)
     if a.wideband is not None:
         return wideband_main(a)
     if a.adc_bits is not None:
@@ -356,6 +370,77 @@ def wideband_main(a):
                            "a converter of %d bits, %.1f dB back-off -> " % (a.adc_bits[0], a.backoff_db) if a.adc_bits else ""),
            "columns": "per SNR: single_channel = the victim's rows without either bank; wideband = one entry per neighbour power",
            "equalisers": eqs, "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def diversity_main(a):
+    if a.rates or a.host_stats or a.locked_clock or a.adc_bits is not None or a.wideband is not None:
+        raise SystemExit("--antennas stands alone: not with --rates, --host-stats, --locked-clock, --adc-bits or --wideband")
+    counts = sorted(set(a.antennas))
+    if counts[0] < 1 or counts[-1] > capi.DIV_MAX_ANT:
+        raise SystemExit("--antennas 1 .. %d" % capi.DIV_MAX_ANT)
+    modes = a.diversity or ["mrc", "select"]
+    n = a.frames or 65536
+    plen, enc = a.psdu_len, a.encoding
+    if not (28 <= plen <= 1528 and 0 <= enc <= 7):
+        raise SystemExit("--psdu-len 28 .. 1528, --encoding 0 .. 7")
+    fd = a.doppler[0] if a.doppler else 0.0
+    n_sym, nb = txgen.n_sym_for(plen, enc), txgen.RATE_TABLE[enc][0]
+    slot = LEAD + txgen.frame_samples(plen, enc) + 79
+    slot += slot & 1
+    stride = (plen + 15) // 16 * 16
+    rx = capi.WifiRx(max_sym=n_sym, llr_bits=nb, want_carrier=True, chan_est=capi.EQ_LS, device=0)
+    t_all = time.perf_counter()
+    d_psdu, rows, iq = rx.alloc(n * plen), rx.alloc(n * slot * 8), rx.alloc(n * slot * 8)
+    rx.mac_batch_dev(d_psdu.ptr, plen, n, None, payload_len=plen - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, n * slot, d_psdu.ptr, enc, psdu_len=np.full(n, plen, np.uint32), psdu_stride=plen, lead=LEAD, row_len=slot)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * n_sym * 48), psdu=d_psdu, psdu_stride=plen)
+    rx.demod_batch_dev(rows.ptr, slot, n, ref)
+    assert rx.link_stats(n, ref, ref)["frames_ref"] == n, "a clean frame was not demodulated"
+    ins = [rx.alloc_out(n, psdu_stride=stride, want_csi=True) for _ in range(counts[-1])]
+    out = rx.alloc_out(n, psdu_stride=stride)
+
+    def score(dev):
+        rx.decode_batch_dev(n, dev)
+        hard = rx.link_stats(n, dev, ref)
+        rx.decode_batch_soft_dev(n, dev)
+        soft = rx.link_stats(n, dev, ref)
+        return {"fer": hard["fer"], "fer_soft": soft["fer"], "counts": {k: hard[k] for k in COUNTERS}, "counts_soft": {k: soft[k] for k in COUNTERS}}
+
+    points = []
+    for snr in a.snr:
+        t0 = time.perf_counter()
+        for ant, dev in enumerate(ins):
+            rx.channel_dev(rows.ptr, iq.ptr, n * slot, n, row_len=slot, gain=math.sqrt(10 ** (snr / 10)), noise_voltage=1.0,
+                           seed=9000 + int(snr) + (a.seed << 32) + (ant << 16), doppler=fd, k_factor=a.k_factor,
+                           fade_seed=100 * a.seed + ant)
+            rx.demod_batch_dev(iq.ptr, slot, n, dev)
+        res = {}
+        for A in counts:
+            if A == 1:
+                res["1"] = score(ins[0])          # (decode_mac marks the records DECODED / CRC_OK: the combiner clears that)
+                continue
+            for m in modes:
+                rx.diversity_combine_dev(ins[:A], n, out, m)
+                res["%d_%s" % (A, m)] = score(out)
+        points.append({"snr_db": snr, "frames": n, "seconds": time.perf_counter() - t0, "fer": {k: v["fer"] for k, v in res.items()},
+                       "fer_soft": {k: v["fer_soft"] for k, v in res.items()}, "by_antennas_and_mode": res})
+        print(json.dumps({k: points[-1][k] for k in ("snr_db", "seconds", "fer", "fer_soft")}), file=sys.stderr)
+    seconds_total = time.perf_counter() - t_all
+    for d in ins + [out]:
+        rx.free_out(d)
+    rx.free_out(ref)
+    rows.free(); iq.free(); rx.close()
+    res = {"workload": "receive diversity on the device: %d distinct frames per point (wifirx_mac_batch, Philox payloads), encoding %d, PSDU %d B "
+                       "(%d symbols), rows of %d, lead 160, per antenna one wifirx_channel_fading call (flat, doppler %g cycles per sample, "
+                       "k_factor %g, its own fade_seed and noise seed, no carrier offset) and one LS demod; wifirx_diversity_combine; hard and "
+                       "soft decode_mac" % (n, enc, plen, n_sym, slot, fd, a.k_factor),
+           "columns": "fer / fer_soft per SNR: '1' = antenna 0 alone (no combiner), 'A_mode' = the first A antennas combined in that mode",
+           "antennas": counts, "modes": modes, "stats": "wifirx_link_stats on the device; reported, not asserted",
+           "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
