@@ -609,6 +609,5 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_channel.inc"
 #include "wifirx_api_link.inc"
 #include "wifirx_api_convert.inc"
-#include "wifirx_api_channelizer.inc"
-#include "wifirx_api_combiner.inc"
+#include "wifirx_api_bank.inc"
 #include "wifirx_api_diversity.inc"

@@ -1,6 +1,6 @@
 // wr_combiner.hip -- the synthesis bank of NUMERICS.md rule 22: M streams at fs, one per adjacent 20 MHz channel, into one
 // wideband stream sampled at M fs.  An M-point inverse DFT across the channels per input block and a polyphase filter
-// (24 taps per branch) per output: the mirror of wr_channelizer.hip, with the same prototype.
+// (24 taps per branch) per output: the mirror of wr_channelizer.hip, with the same prototype; what the two share is wr_bank.h.
 //
 // One workgroup turns a tile of WR_CB_TILE input blocks (one sample of every channel) into WR_CB_TILE * M outputs.  A lane
 // reads two adjacent samples of every row as one 16-byte piece, applies the gains and the inverse DFT in registers and
@@ -11,49 +11,11 @@
 #include <stdint.h>
 
 #include "wr_combiner.h"
-#include "wr_channelizer_table.h"
+#include "wr_bank.h"
 
 namespace wr {
 
-namespace {
-
-constexpr uint32_t CB_THREADS = WR_CB_TILE / 2;
-constexpr uint32_t CB_P = WR_CZ_TAPS_PER_BRANCH;
-constexpr uint32_t CB_PLANE = WR_CB_TILE + WR_CB_HIST + 1;          // float2 per plane; even, so every plane starts on 16 bytes
-static_assert(CB_P == WR_CB_HIST + 1 && CB_PLANE % 2 == 0 && WR_CB_HIST <= CB_THREADS, "tile geometry");
-
-// rule 21's tables; rule 22 uses the taps times M and the complex conjugates of the constants
-template <int M> struct Tables;
-#define WR_CB_TABLES(M_)                                                                      \
-    __device__ const float cb_taps##M_[CB_P * M_] = WR_CZ_TAPS##M_##_INIT;                    \
-    __device__ const float cb_branch##M_[2 * M_] = WR_CZ_BRANCH##M_##_INIT;                   \
-    __device__ const float cb_twiddle##M_[M_] = WR_CZ_TWIDDLE##M_##_INIT;                     \
-    template <> struct Tables<M_> {                                                           \
-        static __device__ __forceinline__ float tap(int i) { return (float)M_ * cb_taps##M_[i]; } \
-        static __device__ __forceinline__ float2 branch(int r) { return make_float2(cb_branch##M_[2 * r], -cb_branch##M_[2 * r + 1]); } \
-        static __device__ __forceinline__ float2 twiddle(int t) { return make_float2(cb_twiddle##M_[2 * t], -cb_twiddle##M_[2 * t + 1]); } \
-    };
-WR_CB_TABLES(2)
-WR_CB_TABLES(4)
-WR_CB_TABLES(8)
-#undef WR_CB_TABLES
-
-// Two float pairs as one 16-byte access, declared at the 8 bytes that a row or `out` promises (wr_convert.hip's Piece: one
-// instruction, taken by the hardware at any such address).
-struct __attribute__((packed, aligned(8))) Pair2 { float v[4]; };
-
-// rule 17's plain complex product
-__device__ __forceinline__ float2 cb_mul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-constexpr int cb_bitrev(int j, int bits)
-{
-    int r = 0;
-    for (int i = 0; i < bits; i++) r |= ((j >> i) & 1) << (bits - 1 - i);
-    return r;
-}
-constexpr int cb_log2(int m) { return m == 2 ? 1 : m == 4 ? 2 : 3; }
-
-}  // namespace
+static_assert(WR_CB_TILE == BANK_TILE && WR_CB_HIST == BANK_HIST && WR_CB_HIST <= BANK_THREADS, "tile geometry");
 
 // the gains travel as kernel arguments
 struct CombineGains { float g[8]; };
@@ -67,24 +29,10 @@ __device__ __forceinline__ void cb_spread(float2 (&u)[M], const CombineGains& gn
     float2 a[M];
 #pragma unroll
     for (int j = 0; j < M; j++) {
-        const int k = cb_bitrev(j, cb_log2(M));
+        const int k = bank_bitrev(j, bank_log2(M));
         a[j] = has_gains ? make_float2(u[k].x * gn.g[k], u[k].y * gn.g[k]) : u[k];
     }
-#pragma unroll
-    for (int len = 2; len <= M; len *= 2) {
-#pragma unroll
-        for (int base = 0; base < M; base += len) {
-#pragma unroll
-            for (int t = 0; t < len / 2; t++) {
-                const int e = t * (M / len);
-                const float2 b = a[base + t + len / 2];
-                const float2 x = e == 0 ? b : 4 * e == M ? make_float2(-b.y, b.x) : cb_mul(Tables<M>::twiddle(e), b);
-                const float2 lo = a[base + t];
-                a[base + t] = make_float2(lo.x + x.x, lo.y + x.y);
-                a[base + t + len / 2] = make_float2(lo.x - x.x, lo.y - x.y);
-            }
-        }
-    }
+    radix2<M, true>(a);
 #pragma unroll
     for (int r = 0; r < M; r++) u[r] = a[r];
 }
@@ -95,18 +43,18 @@ __device__ __forceinline__ float2 cb_rotate(float2 v, int r, bool negate)
 {
     float2 x;
     if (S == 0) x = (r & 1) ? make_float2(-v.x, -v.y) : v;
-    else x = r == 0 ? v : cb_mul(Tables<M>::branch(r), v);
+    else x = r == 0 ? v : bank_mul(bank_conj(Tables<M>::branch(r)), v);
     return negate ? make_float2(-x.x, -x.y) : x;
 }
 
 }  // namespace
 
 template <int M, int S>
-__global__ __launch_bounds__(CB_THREADS)
+__global__ __launch_bounds__(BANK_THREADS)
 void combine_kernel(const float2* __restrict__ in, uint64_t in_stride, const float2* __restrict__ hist, CombineGains gn,
                     int has_gains, uint64_t n_in, uint64_t m0, float2* __restrict__ out)
 {
-    __shared__ __attribute__((aligned(16))) float2 plane[M * CB_PLANE];          // [r][block - first + 23]
+    __shared__ __attribute__((aligned(16))) float2 plane[M * BANK_PLANE];        // [r][block - first + 23]
     const uint32_t tid = threadIdx.x;
     const uint64_t first = (uint64_t)blockIdx.x * WR_CB_TILE;                    // the tile's first block
     const uint32_t count = n_in - first < WR_CB_TILE ? (uint32_t)(n_in - first) : WR_CB_TILE;        // its blocks, >= 1
@@ -123,7 +71,7 @@ void combine_kernel(const float2* __restrict__ in, uint64_t in_stride, const flo
         }
         cb_spread<M>(u, gn, has_gains);
 #pragma unroll
-        for (int r = 0; r < M; r++) plane[r * CB_PLANE + tid] = u[r];
+        for (int r = 0; r < M; r++) plane[r * BANK_PLANE + tid] = u[r];
     }
     // the tile's own blocks, two per lane in 16-byte pieces; a last odd block sample by sample
     if (a_blk + 1 < count) {
@@ -138,8 +86,8 @@ void combine_kernel(const float2* __restrict__ in, uint64_t in_stride, const flo
         cb_spread<M>(ub, gn, has_gains);
 #pragma unroll
         for (int r = 0; r < M; r++) {
-            plane[r * CB_PLANE + WR_CB_HIST + a_blk] = ua[r];
-            plane[r * CB_PLANE + WR_CB_HIST + a_blk + 1] = ub[r];
+            plane[r * BANK_PLANE + WR_CB_HIST + a_blk] = ua[r];
+            plane[r * BANK_PLANE + WR_CB_HIST + a_blk + 1] = ub[r];
         }
     } else if (a_blk < count) {
         float2 ua[M];
@@ -147,7 +95,7 @@ void combine_kernel(const float2* __restrict__ in, uint64_t in_stride, const flo
         for (int k = 0; k < M; k++) ua[k] = in[(uint64_t)k * in_stride + first + a_blk];
         cb_spread<M>(ua, gn, has_gains);
 #pragma unroll
-        for (int r = 0; r < M; r++) plane[r * CB_PLANE + WR_CB_HIST + a_blk] = ua[r];
+        for (int r = 0; r < M; r++) plane[r * BANK_PLANE + WR_CB_HIST + a_blk] = ua[r];
     }
     __syncthreads();
 
@@ -155,30 +103,10 @@ void combine_kernel(const float2* __restrict__ in, uint64_t in_stride, const flo
     float2 va[M], vb[M];
 #pragma unroll
     for (int r = 0; r < M; r++) {
-        // blocks a_blk - 23 .. a_blk + 1 of plane r: w[j] = block a_blk - 23 + j
-        float2 w[CB_P + 1];
-        const float4* p4 = reinterpret_cast<const float4*>(&plane[r * CB_PLANE + a_blk]);
+        float tap[BANK_P];
 #pragma unroll
-        for (uint32_t j = 0; j < CB_P / 2; j++) {
-            const float4 t = p4[j];
-            w[2 * j] = make_float2(t.x, t.y);
-            w[2 * j + 1] = make_float2(t.z, t.w);
-        }
-        w[CB_P] = plane[r * CB_PLANE + a_blk + CB_P];
-        float2 sa, sb;
-#pragma unroll
-        for (uint32_t p = 0; p < CB_P; p++) {
-            const float g = Tables<M>::tap(p * M + r);
-            const float2 xa = w[CB_P - 1 - p], xb = w[CB_P - p];
-            const float2 ta = make_float2(g * xa.x, g * xa.y), tb = make_float2(g * xb.x, g * xb.y);
-            sa = p == 0 ? ta : make_float2(sa.x + ta.x, sa.y + ta.y);
-            sb = p == 0 ? tb : make_float2(sb.x + tb.x, sb.y + tb.y);
-        }
-        // as in channelize_kernel: keep both sums here, so that only one branch's window is in registers at a time
-        asm volatile("" : "+v"(sa.x), "+v"(sa.y), "+v"(sb.x), "+v"(sb.y));
-        __builtin_amdgcn_sched_barrier(0);
-        va[r] = sa;
-        vb[r] = sb;
+        for (uint32_t p = 0; p < BANK_P; p++) tap[p] = (float)M * Tables<M>::tap(p * M + r);
+        window_sums(&plane[r * BANK_PLANE + a_blk], tap, va[r], vb[r]);
     }
     const uint64_t ma = first + a_blk;
     const bool nega = S && ((m0 + ma) & 1), negb = S && ((m0 + ma + 1) & 1);
@@ -217,7 +145,7 @@ template <int M>
 hipError_t launch_combine(hipStream_t st, const float2* in, uint64_t in_stride, const CombineGains& gn, int has_gains,
                           const float2* hist, int stacking, uint64_t n_in, uint64_t m0, float2* out)
 {
-    const dim3 grid((uint32_t)((n_in + WR_CB_TILE - 1) / WR_CB_TILE)), block(CB_THREADS);
+    const dim3 grid((uint32_t)((n_in + WR_CB_TILE - 1) / WR_CB_TILE)), block(BANK_THREADS);
     if (stacking) hipLaunchKernelGGL((combine_kernel<M, 1>), grid, block, 0, st, in, in_stride, hist, gn, has_gains, n_in, m0, out);
     else hipLaunchKernelGGL((combine_kernel<M, 0>), grid, block, 0, st, in, in_stride, hist, gn, has_gains, n_in, m0, out);
     return hipGetLastError();

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "wr_convert.h"
+#include "wr_iq.h"
 
 namespace wr {
 
@@ -14,35 +15,12 @@ namespace {
 constexpr uint32_t CONV_THREADS = 256;
 constexpr uint32_t CONV_BLOCKS_PER_CU = 8;
 
-// A lane's piece is 16 bytes of integers: 4 samples of sc16, 8 of sc8, and so 2 or 4 16-byte pieces of float pairs.
-template <int FMT> struct Format;
-template <> struct Format<WIFIRX_IQ_SC16> { static constexpr uint32_t G = 4, BYTES = 4; };
-template <> struct Format<WIFIRX_IQ_SC8>  { static constexpr uint32_t G = 8, BYTES = 2; };
-
-// the two components of sample s of an integer buffer, exactly converted; natural alignment
-template <int FMT>
-__device__ __forceinline__ float2 load_sample(const void* p, uint64_t s)
-{
-    if constexpr (FMT == WIFIRX_IQ_SC16) {
-        const uint32_t w = static_cast<const uint32_t*>(p)[s];
-        return make_float2((float)(int16_t)(w & 0xffffu), (float)(int16_t)(w >> 16));
-    } else {
-        const uint32_t w = static_cast<const uint16_t*>(p)[s];
-        return make_float2((float)(int8_t)(w & 0xffu), (float)(int8_t)(w >> 8));
-    }
-}
-
 template <int FMT>
 __device__ __forceinline__ void store_sample(void* p, uint64_t s, int i, int q)
 {
     if constexpr (FMT == WIFIRX_IQ_SC16) static_cast<uint32_t*>(p)[s] = ((uint32_t)i & 0xffffu) | ((uint32_t)q << 16);
     else static_cast<uint16_t*>(p)[s] = (uint16_t)(((uint32_t)i & 0xffu) | (((uint32_t)q & 0xffu) << 8));
 }
-
-// The 16 bytes of a lane's piece, declared at the format's natural alignment, which is all a caller's buffer promises: the
-// compiler still moves it with one 16-byte instruction, and the hardware takes that at any such address.  (The stream places
-// its own scratch copy so that the pieces lie on 16-byte boundaries, wifirx_api_stream.inc.)
-template <int FMT> struct __attribute__((packed, aligned(Format<FMT>::BYTES))) Piece { uint32_t w[4]; };
 
 template <int FMT>
 __device__ __forceinline__ Piece<FMT>* piece_at(void* p, uint64_t first)
@@ -112,8 +90,7 @@ void iq_widen_kernel(const void* __restrict__ src, float2* __restrict__ dst, uin
     const uint64_t n_edge = cut.head + (n - cut.rest_from);       // at most 1 + G - 1 samples
     if (blockIdx.x == 0 && threadIdx.x < n_edge) {
         const uint64_t s = threadIdx.x < cut.head ? threadIdx.x : cut.rest_from + (threadIdx.x - cut.head);
-        const float2 q = load_sample<FMT>(src, s);
-        dst[s] = make_float2(q.x * scale, q.y * scale);
+        dst[s] = load_sample<FMT>(src, s, scale);
     }
 }
 

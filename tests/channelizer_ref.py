@@ -30,15 +30,17 @@ def _snap32(z):
     return re.astype(np.float32), im.astype(np.float32)
 
 
-def branch_constants(M):
-    """c_q of stacking 1, float32 (re, im), rounded once from float64"""
+def branch_constants(M, conj=False):
+    """c_q of stacking 1, float32 (re, im), rounded once from float64; conj: rule 22's, the imaginary part's sign flipped"""
     q = np.arange(M)
-    return _snap32((-1.0) ** q * np.exp(-1j * np.pi * q / M))
+    re, im = _snap32((-1.0) ** q * np.exp(-1j * np.pi * q / M))
+    return re, -im if conj else im
 
 
-def twiddles(M):
-    """exp(-j 2 pi t / M), t < M/2, float32 (re, im), rounded once from float64"""
-    return _snap32(np.exp(-2j * np.pi * np.arange(M // 2) / M))
+def twiddles(M, conj=False):
+    """exp(-j 2 pi t / M), t < M/2, float32 (re, im), rounded once from float64; conj: the imaginary part's sign flipped"""
+    re, im = _snap32(np.exp(-2j * np.pi * np.arange(M // 2) / M))
+    return re, -im if conj else im
 
 
 def _mul(ar, ai, br, bi):
@@ -52,6 +54,33 @@ def _bitrev(j, bits):
         r = (r << 1) | (j & 1)
         j >>= 1
     return r
+
+
+def radix2(xr, xi, M, inverse=False):
+    """the M-point DFT (inverse: sum_k x_k exp(+j 2 pi k r / M), the conjugate twiddles) down axis 0 of float32 arrays
+    [M, n]: radix 2, decimation in time on the bit-reversed input; W = 1 is not multiplied, W = -+j is a swap and a sign"""
+    bits = M.bit_length() - 1
+    order = [_bitrev(j, bits) for j in range(M)]
+    ar, ai = np.ascontiguousarray(xr[order]), np.ascontiguousarray(xi[order])
+    tw_r, tw_i = twiddles(M, conj=inverse)
+    length = 2
+    while length <= M:                                        # wr_bank.h: for (len = 2; len <= M; len *= 2)
+        half = length // 2
+        for base in range(0, M, length):
+            for t in range(half):
+                i0, i1 = base + t, base + t + half
+                e = t * (M // length)
+                br, bi = ar[i1].copy(), ai[i1].copy()
+                if e == 0:
+                    tr, ti = br, bi
+                elif 4 * e == M:
+                    tr, ti = (-bi, br) if inverse else (bi, -br)
+                else:
+                    tr, ti = _mul(tw_r[e], tw_i[e], br, bi)
+                ar[i0], ar[i1] = ar[i0] + tr, ar[i0] - tr
+                ai[i0], ai[i1] = ai[i0] + ti, ai[i0] - ti
+        length *= 2
+    return ar, ai
 
 
 def history(x, hist, M):
@@ -88,34 +117,13 @@ def analyse(x, M, s, hist=None, m0=0, taps=None, outputs=None):
         cr_, ci_ = branch_constants(M)
         wr_, wi_ = vr.copy(), vi.copy()
         wr_[:, 1:], wi_[:, 1:] = _mul(cr_[None, 1:], ci_[None, 1:], vr[:, 1:], vi[:, 1:])     # c_0 = 1 is not multiplied
-    # DFT: radix-2 decimation in time on bit-reversed q
-    bits = M.bit_length() - 1
-    order = [_bitrev(j, bits) for j in range(M)]
-    ar, ai = np.ascontiguousarray(wr_[:, order]), np.ascontiguousarray(wi_[:, order])
-    tw_r, tw_i = twiddles(M)
-    length = 2
-    while length <= M:
-        half = length // 2
-        for base in range(0, M, length):
-            for t in range(half):
-                i0, i1 = base + t, base + t + half
-                e = t * (M // length)
-                br, bi = ar[:, i1], ai[:, i1]
-                if e == 0:
-                    tr, ti = br, bi
-                elif 4 * e == M:
-                    tr, ti = bi, -br                          # W = -j: swap and negate
-                else:
-                    tr, ti = _mul(tw_r[e], tw_i[e], br, bi)
-                ar[:, i0], ar[:, i1] = ar[:, i0] + tr, ar[:, i0] - tr
-                ai[:, i0], ai[:, i1] = ai[:, i0] + ti, ai[:, i0] - ti
-        length *= 2
+    ar, ai = radix2(wr_.T, wi_.T, M)                          # [k, m]
     if s:
         neg = ((int(m0) + ms) & 1).astype(bool)
-        ar[neg], ai[neg] = -ar[neg], -ai[neg]
+        ar[:, neg], ai[:, neg] = -ar[:, neg], -ai[:, neg]
     assert ar.dtype == np.float32 and ai.dtype == np.float32
     out = np.empty((M, len(ms)), np.complex64)
-    out.real, out.imag = ar.T, ai.T
+    out.real, out.imag = ar, ai
     return out
 
 

@@ -12,15 +12,13 @@ CHANNELS = zr.CHANNELS
 
 
 def branch_constants(M):
-    """c'_r of stacking 1: the complex conjugate of rule 21's float32 constants (the imaginary part's sign flipped)"""
-    re, im = zr.branch_constants(M)
-    return re, -im
+    """c'_r of stacking 1: the complex conjugate of rule 21's float32 constants"""
+    return zr.branch_constants(M, conj=True)
 
 
 def twiddles(M):
-    """exp(+j 2 pi t / M), t < M/2: rule 21's float32 twiddles with the imaginary part's sign flipped"""
-    re, im = zr.twiddles(M)
-    return re, -im
+    """exp(+j 2 pi t / M), t < M/2: the complex conjugate of rule 21's float32 twiddles"""
+    return zr.twiddles(M, conj=True)
 
 
 def rows(streams, M):
@@ -43,30 +41,9 @@ def next_history(streams, hist, M):
 
 
 def inverse_dft(ur, ui, M):
-    """V_r = sum_k u_k exp(+j 2 pi k r / M) down axis 0 of float32 arrays [M, n]: rule 21's radix-2 network, decimation in
-    time on bit-reversed k, with the conjugate twiddles"""
-    bits = M.bit_length() - 1
-    order = [zr._bitrev(j, bits) for j in range(M)]
-    ar, ai = np.ascontiguousarray(ur[order]), np.ascontiguousarray(ui[order])
-    tw_r, tw_i = twiddles(M)
-    length = 2
-    while length <= M:
-        half = length // 2
-        for base in range(0, M, length):
-            for t in range(half):
-                i0, i1 = base + t, base + t + half
-                e = t * (M // length)
-                br, bi = ar[i1].copy(), ai[i1].copy()
-                if e == 0:
-                    tr, ti = br, bi
-                elif 4 * e == M:
-                    tr, ti = -bi, br                          # W = +j: swap and negate
-                else:
-                    tr, ti = zr._mul(tw_r[e], tw_i[e], br, bi)
-                ar[i0], ar[i1] = ar[i0] + tr, ar[i0] - tr
-                ai[i0], ai[i1] = ai[i0] + ti, ai[i0] - ti
-        length *= 2
-    return ar, ai
+    """V_r = sum_k u_k exp(+j 2 pi k r / M) down axis 0 of float32 arrays [M, n]: rule 21's radix-2 network with the
+    conjugate twiddles"""
+    return zr.radix2(ur, ui, M, inverse=True)
 
 
 def combine(streams, M, s, gains=None, hist=None, m0=0, taps=None):

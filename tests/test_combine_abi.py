@@ -3,29 +3,12 @@ arguments.  wifirx_combine refuses a NULL handle first and a handle needs a devi
 exercised where a handle exists, in tests/test_gpu_combine.py."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_raw():
-    return open(os.path.join(ROOT, "include", "wifirx.h")).read()
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", _header_raw(), flags=re.S)
-
-
-def _decl(txt, name):
-    return re.search(r"\b%s\s*\((.*?)\)\s*;" % name, txt, flags=re.S).group(1)
-
-
-def _norm(decl):
-    return [re.sub(r"\s+", " ", a).strip() for a in decl.split(",")]
+from abi_helpers import _decl, _header, _header_raw, _norm
 
 
 def test_declared_exported_and_bound():

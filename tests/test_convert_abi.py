@@ -1,27 +1,10 @@
 """The sample-format entry points in the C ABI and the Python surface, on a box without a GPU."""
 import inspect
-import os
 import re
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_raw():
-    return open(os.path.join(ROOT, "include", "wifirx.h")).read()
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", _header_raw(), flags=re.S)
-
-
-def _decl(txt, name):
-    return re.search(r"\b%s\s*\((.*?)\)\s*;" % name, txt, flags=re.S).group(1)
-
-
-def _norm(decl):
-    return [re.sub(r"\s+", " ", a).strip() for a in decl.split(",")]
+from abi_helpers import _decl, _header, _header_raw, _norm
 
 
 def test_declared_exported_and_bound():

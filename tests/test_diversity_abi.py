@@ -3,26 +3,9 @@ constants.  The call refuses a NULL handle first and a handle needs a device, so
 where a handle exists, in tests/test_gpu_diversity.py."""
 import ctypes as C
 import inspect
-import os
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_raw():
-    return open(os.path.join(ROOT, "include", "wifirx.h")).read()
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", _header_raw(), flags=re.S)
-
-
-def _decl(txt, name):
-    return re.search(r"\b%s\s*\((.*?)\)\s*;" % name, txt, flags=re.S).group(1)
-
-
-def _norm(decl):
-    return [re.sub(r"\s+", " ", a).strip() for a in decl.split(",")]
+from abi_helpers import _decl, _header, _header_raw, _norm
 
 
 def test_declared_exported_and_bound():

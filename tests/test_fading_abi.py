@@ -1,18 +1,8 @@
 """wifirx_channel_fading in the C ABI and the Python surface, on a box without a GPU."""
 import inspect
-import os
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header():
-    txt = open(os.path.join(ROOT, "include", "wifirx.h")).read()
-    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-
-
-def _decl(txt, name):
-    return re.search(r"\b%s\s*\((.*?)\)\s*;" % name, txt, flags=re.S).group(1)
+from abi_helpers import _decl, _header
 
 
 def test_symbol_declared_exported_and_listed():

@@ -1,25 +1,19 @@
 """wifirx_channelize (wr_channelizer.hip) against tests/channelizer_ref.py, bit for bit: every size around the 24-tap window
 and the kernel's tile, every channel count, stacking and sample format, both input offsets, rows between canaries, hist and
 hist_out, a stream cut into calls, the parity of m0, one large call, and the refused arguments."""
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
 import channelizer_ref as zr
 import convert_ref as cr
+from bank_helpers import CANARY, alloc_bufs, bits_of, download_fenced, fill, open_rx, same_bits, tile
 from wifirx import capi
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-T = int(re.search(r"#define\s+WR_CZ_TILE\s+(\d+)", open(os.path.join(
-    ROOT, "gnuradio-wifi-imagetransfer_amd", "csrc", "wr_channelizer.h")).read()).group(1))
+T = tile("wr_channelizer.h", "WR_CZ_TILE")
 SIZES = (0, 1, 2, 23, 24, 25, T - 1, T, T + 1, 2 * T + 3, 1031)
 N_MAX = max(SIZES)
-CANARY = 0xA5
 BPS = {cr.FC32: 8, cr.SC16: 4, cr.SC8: 2}
 FORMATS = [cr.FC32, cr.SC16, cr.SC8]
 FMT_ID = {cr.FC32: "fc32", cr.SC16: "sc16", cr.SC8: "sc8"}
@@ -31,18 +25,12 @@ OUT_ROOM = 16 + 8 + (8 * (N_MAX + 5)) * 8 + 64          # bytes: the lead, 8 row
 
 @pytest.fixture(scope="module")
 def rx():
-    r = capi.WifiRx(max_sym=1, device=0)
-    yield r
-    r.close()
+    yield from open_rx()
 
 
 @pytest.fixture(scope="module")
 def bufs(rx):
-    b = dict(inp=rx.alloc((N_MAX * 8 + 1) * 8 + 16), hist=rx.alloc(23 * 8 * 8), hout=rx.alloc(23 * 8 * 8 + 32), hout2=rx.alloc(23 * 8 * 8),
-             out=rx.alloc(OUT_ROOM))
-    yield b
-    for d in b.values():
-        d.free()
+    yield from alloc_bufs(rx, inp=(N_MAX * 8 + 1) * 8 + 16, hist=23 * 8 * 8, hout=23 * 8 * 8 + 32, hout2=23 * 8 * 8, out=OUT_ROOM)
 
 
 def samples(rng, n, fmt):
@@ -51,10 +39,6 @@ def samples(rng, n, fmt):
         return rng.standard_normal((n, 2)).astype(np.float32)
     info = np.iinfo(cr.DTYPE[fmt])
     return rng.integers(info.min, info.max + 1, (n, 2)).astype(cr.DTYPE[fmt])
-
-
-def bits_of(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
 def scale_of(fmt, scale):
@@ -71,29 +55,18 @@ def run_dev(rx, bufs, x, fmt, M, s, hist, m0, scale, in_off=0, want_hist_out=Tru
     bufs["inp"].upload(np.concatenate([np.full(in_off * bps, 0x5A, np.uint8), bits_of(x), np.full(16, 0x5A, np.uint8)]))
     if hist is not None:
         bufs["hist"].upload(bits_of(hist))
-    bufs["out"].upload(np.full(OUT_ROOM, CANARY, np.uint8))
-    bufs["hout"].upload(np.full(23 * 8 * 8 + 32, CANARY, np.uint8))
+    fill(bufs["out"])
+    fill(bufs["hout"])
     out_ptr = bufs["out"].ptr + 24                            # 8 bytes past a 16-byte boundary
     assert bufs["out"].ptr % 16 == 0
     rx.channelize_dev(bufs["inp"].ptr + in_off * bps, fmt, n_out, M, s, out_ptr, stride, hist_ptr=None if hist is None else bufs["hist"].ptr,
                       hist_out_ptr=bufs["hout"].ptr if want_hist_out else None, m0=m0, scale=scale_of(fmt, scale))
-    raw = bufs["out"].download(np.uint8, OUT_ROOM)
-    rows = np.empty((M, n_out), np.complex64)
-    mask = np.ones(OUT_ROOM, bool)
-    for k in range(M):
-        a = 24 + k * stride * 8
-        rows[k] = raw[a:a + n_out * 8].view(np.complex64)
-        mask[a:a + n_out * 8] = False
-    assert (raw[mask] == CANARY).all(), "wrote outside its rows"
-    hraw = bufs["hout"].download(np.uint8, 23 * 8 * 8 + 32)
+    raw = download_fenced(bufs["out"], [(24 + k * stride * 8, n_out * 8) for k in range(M)], "its rows")
+    rows = np.stack([raw[24 + k * stride * 8:][:n_out * 8].view(np.complex64) for k in range(M)])
     nh = 23 * M * bps if want_hist_out else 0
-    assert (hraw[nh:] == CANARY).all(), "wrote behind hist_out"
+    hraw = download_fenced(bufs["hout"], [(0, nh)], "hist_out")
     dt = np.float32 if fmt == cr.FC32 else cr.DTYPE[fmt]
     return rows, hraw[:nh].view(dt).reshape(-1, 2)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
 @pytest.mark.parametrize("M,s,fmt", CASES)
@@ -201,10 +174,8 @@ def test_refused_arguments_leave_every_buffer_alone(rx, bufs):
         (i, 0, 1.0, hi, ho, 8, 1, (1 << 64) - 1, 0, o, (1 << 64) - 1),
     ]
     try:
-        fills = {k: np.full(d.nbytes, CANARY, np.uint8) for k, d in bufs.items()}
-        for k, d in bufs.items():
-            d.upload(fills[k])
-        big.upload(np.full(1 << 16, CANARY, np.uint8))
+        fills = {k: fill(d) for k, d in bufs.items()}
+        fill(big)
         for a in einval:
             assert lib.wifirx_channelize(h, *a) == capi.EINVAL, a
         for a in erange:

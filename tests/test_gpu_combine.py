@@ -3,24 +3,21 @@ kernel's tile, every channel count and stacking, hist and hist_out, both paritie
 gains, buffers at 8 but not 16 bytes, out and hist_out between fences, a stream cut into calls, the block, and the refused
 arguments."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import combine_ref as cb
+from bank_helpers import CANARY, alloc_bufs, bits_of, download_fenced, fill, open_rx, same_bits, tile
 from wifirx import block, capi
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-T = int(re.search(r"#define\s+WR_CB_TILE\s+(\d+)", open(os.path.join(
-    ROOT, "gnuradio-wifi-imagetransfer_amd", "csrc", "wr_combiner.h")).read()).group(1))
+T = tile("wr_combiner.h", "WR_CB_TILE")
 assert T == 512
 SIZES = (1, 2, 23, 24, 25, T - 1, T, T + 1, 2 * T + 1, 3 * T + 7)
 N_MAX = max(SIZES)
-FENCE, CANARY = 4096, 0xA5
+FENCE = 4096
 CASES = [pytest.param(M, s, id="M%d-s%d" % (M, s)) for M in (2, 4, 8) for s in (0, 1)]
 # (hist given, m0, in_stride - n_in, gains given, input offset in bytes, output offset in bytes)
 COMBOS = ((False, 0, 0, False, 0, 0), (True, 7, 3, True, 8, 8), (True, 1 << 40, 4, False, 8, 0), (False, 11, 1, True, 0, 8))
@@ -31,17 +28,12 @@ HIST_ROOM = FENCE + 23 * 8 * 8 + FENCE
 
 @pytest.fixture(scope="module")
 def rx():
-    r = capi.WifiRx(max_sym=1, device=0)
-    yield r
-    r.close()
+    yield from open_rx()
 
 
 @pytest.fixture(scope="module")
 def bufs(rx):
-    b = dict(inp=rx.alloc(IN_ROOM), hist=rx.alloc(23 * 8 * 8), hout=rx.alloc(HIST_ROOM), hout2=rx.alloc(HIST_ROOM), out=rx.alloc(OUT_ROOM))
-    yield b
-    for d in b.values():
-        d.free()
+    yield from alloc_bufs(rx, inp=IN_ROOM, hist=23 * 8 * 8, hout=HIST_ROOM, hout2=HIST_ROOM, out=OUT_ROOM)
 
 
 def streams(rng, M, n):
@@ -53,14 +45,6 @@ def gains_of(M):
     g = (0.5 + 0.375 * np.arange(M)).astype(np.float32)
     g[0], g[M - 1] = -0.75, 0.0
     return g
-
-
-def bits_of(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits_of(a), bits_of(b))
 
 
 def run_dev(rx, bufs, u, M, s, hist=None, m0=0, extra=0, gains=None, in_off=0, out_off=0, hout="hout", want_hist_out=True):
@@ -75,18 +59,16 @@ def run_dev(rx, bufs, u, M, s, hist=None, m0=0, extra=0, gains=None, in_off=0, o
     bufs["inp"].upload(raw)
     if hist is not None:
         bufs["hist"].upload(bits_of(hist))
-    bufs["out"].upload(np.full(OUT_ROOM, CANARY, np.uint8))
-    bufs[hout].upload(np.full(HIST_ROOM, CANARY, np.uint8))
+    fill(bufs["out"])
+    fill(bufs[hout])
     assert bufs["out"].ptr % 16 == 0 and bufs["inp"].ptr % 16 == 0
     rx.combine_dev(bufs["inp"].ptr + in_off, stride, n, M, s, bufs["out"].ptr + FENCE + out_off, gains=gains,
                    hist_ptr=None if hist is None else bufs["hist"].ptr,
                    hist_out_ptr=bufs[hout].ptr + FENCE if want_hist_out else None, m0=m0)
-    got = bufs["out"].download(np.uint8, OUT_ROOM)
     a = FENCE + out_off
-    assert (got[:a] == CANARY).all() and (got[a + n * M * 8:] == CANARY).all(), "wrote outside out"
-    hraw = bufs[hout].download(np.uint8, HIST_ROOM)
+    got = download_fenced(bufs["out"], [(a, n * M * 8)], "out")
     nh = 23 * M * 8 if want_hist_out else 0
-    assert (hraw[:FENCE] == CANARY).all() and (hraw[FENCE + nh:] == CANARY).all(), "wrote outside hist_out"
+    hraw = download_fenced(bufs[hout], [(FENCE, nh)], "hist_out")
     return got[a:a + n * M * 8].view(np.complex64), hraw[FENCE:FENCE + nh].view(np.complex64).reshape(-1, 23)
 
 
@@ -205,10 +187,8 @@ def test_refused_arguments_leave_every_buffer_alone(rx, bufs):
         (i, 1 << 41, ok, hi, ho, 4, 1, (1 << 40) + 1, 0, o), (i, (1 << 64) - 1, ok, hi, ho, 8, 1, (1 << 64) - 1, 0, o),
     ]
     try:
-        fills = {k: np.full(d.nbytes, CANARY, np.uint8) for k, d in bufs.items()}
-        for k, d in bufs.items():
-            d.upload(fills[k])
-        big.upload(np.full(1 << 16, CANARY, np.uint8))
+        fills = {k: fill(d) for k, d in bufs.items()}
+        fill(big)
         for a in einval:
             assert lib.wifirx_combine(h, *a) == capi.EINVAL, a
         for a in erange:
