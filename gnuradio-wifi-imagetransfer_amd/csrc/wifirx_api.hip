@@ -31,12 +31,18 @@
 #include "wr_channelizer.h"
 #include "wr_combiner.h"
 #include "wr_diversity.h"
+#include "wr_detect_multi.h"
 
 // The stream's per-frame outputs (stream_outs, wifirx_api_stream.inc) and the host copy of a batch of them, shared by its
 // frames: output o of frame k is the width[o] bytes at blob[off[o] + k * width[o]] (width 0: the handle did not produce o).
 // A PolledFrame is a finished frame of the stream: its record and its row k of the batch it came with.
 enum StreamOutput { SO_PSDU, SO_IDX, SO_CAR, SO_CSI, SO_STATS, SO_N };
-struct StreamBatch { std::vector<uint8_t> blob; size_t off[SO_N], width[SO_N]; };
+// A batch of the diversity stream also carries, per frame k, used[k] = the contributing antennas and ant[k * n_ant + a] =
+// antenna a's own record (n_ant = 0: a batch of the single stream).
+struct StreamBatch {
+    std::vector<uint8_t> blob; size_t off[SO_N], width[SO_N];
+    uint32_t n_ant; std::vector<uint8_t> used; std::vector<wifirx_frame> ant;
+};
 struct PolledFrame { wifirx_frame fr; std::shared_ptr<const StreamBatch> batch; uint32_t k; };
 
 struct PendingTrig {
@@ -153,6 +159,18 @@ struct StreamState {
     bool     dead = false;          // the carry step failed after it had begun to move the sample buffer
     std::string dead_msg;
     size_t   push_consumed = 0;     // wifirx_push_consumed
+    bool     single = false;        // wifirx_push / wifirx_push_iq has handed in samples: no wifirx_push_diversity on this handle
+};
+
+// the diversity stream (wifirx_api_stream_div.inc): what it keeps beside the StreamState it shares with the single stream.
+// There st.sbuf holds the n_ant sample planes, plane a at sbuf + a * sbuf_cap samples, and the st.* output rows are the
+// combined set.
+struct DivStream {
+    uint32_t n_ant = 0;             // fixed by the handle's first wifirx_push_diversity; 0: none yet
+    uint32_t cap = 0;               // triggers the per-antenna rows hold
+    DevBuf   frames, car, csi, stats;   // n_ant sets of frame-kernel rows, set a at cap rows times a
+    DevBuf   used, src;             // per trigger: the contributing antennas (the combiner's), the antenna of the csi / sym_stats rows
+    DevBuf   native;                // host input in an integer format: the n_ant chunks of a pass, widened from here
 };
 
 // A batch handed to the worker: `n` samples of format `fmt` (WIFIRX_IQ_*; `scale` widens the integer ones) at `ptr` (a ring
@@ -193,6 +211,7 @@ struct wifirx_handle {
     Staging       stage;
     DecodeWork    dec;
     StreamState   st;
+    DivStream     div;
     Worker        w;
 };
 
@@ -611,3 +630,4 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_convert.inc"
 #include "wifirx_api_bank.inc"
 #include "wifirx_api_diversity.inc"
+#include "wifirx_api_stream_div.inc"

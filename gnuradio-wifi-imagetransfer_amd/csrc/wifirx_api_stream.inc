@@ -152,27 +152,23 @@ struct StageClock {
 };
 
 // What the frames phase hands to the queue step: per pending trigger its record and whether no more samples can come
-struct FramePass { std::vector<wifirx_frame> fr; std::vector<char> final_; std::shared_ptr<const StreamBatch> batch; };
+// (a diversity pass, wifirx_api_stream_div.inc, adds: hold[k] = an antenna's record of trigger k still waits for samples;
+// per frame the contributing antennas and the n_ant antennas' own records, which travel with the batch)
+struct FramePass {
+    std::vector<wifirx_frame> fr; std::vector<char> final_; std::shared_ptr<const StreamBatch> batch;
+    std::vector<char> hold; std::vector<uint8_t> used; std::vector<wifirx_frame> ant; uint32_t n_ant = 0;
+};
 
 }  // namespace
 
-// Detect: (1) detection over the tiles with not yet scanned samples (plus one tile of mask history); (2) the sync_short state
-// machine appends to st.pending: a trigger needs min_plateau+1 samples above the threshold in a row and > MIN_GAP since the last
-static int stream_detect(wifirx_handle* h, StageClock& stage)
+// The sync_short state machine over the plateau masks of the tiles from t_first on (the first one is mask history when
+// t_first > 0): appends to st.pending and moves the detection frontier to the end of the buffer.  A trigger needs
+// min_plateau+1 samples above the threshold in a row and > MIN_GAP since the last.  Shared by the single stream and the
+// diversity stream, whose masks come from the joint detection.
+static void stream_select_triggers(wifirx_handle* h, const std::vector<uint64_t>& masks, int64_t t_first, StageClock& stage)
 {
     StreamState& st = h->st;
-    const int64_t end_abs = st.sbase + st.sfill;
-    if (end_abs <= st.sdetected) return WIFIRX_OK;
-    int64_t t_first = (st.sdetected - st.sbase) / 64;
-    if (t_first > 0) t_first -= 1;
-    const int64_t n_tiles = (st.sfill + 63) / 64 - t_first;
-    HIP_TRY(h, wr_launch_stream_detect(h->stream, st.sbuf.as<float2>(), st.sfill, t_first, n_tiles, h->cfg.sensitivity,
-                                       st.above.as<uint64_t>(), st.A.as<float2>()));
-    std::vector<uint64_t> masks((size_t)n_tiles);
-    HIP_TRY(h, hipMemcpyAsync(masks.data(), st.above.as<uint64_t>() + t_first,
-                              (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    stage("input copy + detect + masks");
+    const int64_t end_abs = st.sbase + st.sfill, n_tiles = (int64_t)masks.size();
     uint64_t n_new_trig = 0;
     for (int64_t tl = 0; tl < n_tiles; tl++) {
         uint64_t m = masks[(size_t)tl], prev = tl > 0 ? masks[(size_t)tl - 1] : 0;
@@ -194,19 +190,35 @@ static int stream_detect(wifirx_handle* h, StageClock& stage)
     st.sdetected = end_abs;
     { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.frames_detected += n_new_trig; }
     stage("host state machine");
+}
+
+// Detect: (1) detection over the tiles with not yet scanned samples (plus one tile of mask history); (2) the sync_short state
+// machine (stream_select_triggers) appends to st.pending
+static int stream_detect(wifirx_handle* h, StageClock& stage)
+{
+    StreamState& st = h->st;
+    const int64_t end_abs = st.sbase + st.sfill;
+    if (end_abs <= st.sdetected) return WIFIRX_OK;
+    int64_t t_first = (st.sdetected - st.sbase) / 64;
+    if (t_first > 0) t_first -= 1;
+    const int64_t n_tiles = (st.sfill + 63) / 64 - t_first;
+    HIP_TRY(h, wr_launch_stream_detect(h->stream, st.sbuf.as<float2>(), st.sfill, t_first, n_tiles, h->cfg.sensitivity,
+                                       st.above.as<uint64_t>(), st.A.as<float2>()));
+    std::vector<uint64_t> masks((size_t)n_tiles);
+    HIP_TRY(h, hipMemcpyAsync(masks.data(), st.above.as<uint64_t>() + t_first,
+                              (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    stage("input copy + detect + masks");
+    stream_select_triggers(h, masks, t_first, stage);
     return WIFIRX_OK;
 }
 
-// Frames: (3) the frame kernel + decode_mac over every pending trigger whose samples are (partly) here; records, outputs
-static int stream_frames(wifirx_handle* h, bool flush, StageClock& stage, FramePass& p)
+// The triggers of a pass as the frame kernel takes them: position in the buffer, the samples that belong to the trigger, the
+// coarse CFO of an earlier pass; p.final_[k] = no more samples can come for trigger k (next trigger / MAX_SAMPLES / flush)
+static std::vector<wr::StreamTrig> stream_trig_rows(wifirx_handle* h, bool flush, FramePass& p)
 {
     StreamState& st = h->st;
     const uint32_t np = (uint32_t)st.pending.size();
-    if (!np) return WIFIRX_OK;
-    int rc;
-    if ((rc = stream_out_reserve(h, np))) return rc;
-    const bool soft = h->tune.stream_soft != 0;
-    if (soft && (rc = stream_llr_reserve(h))) return rc;
     const int64_t end_abs = st.sbase + st.sfill;
     std::vector<wr::StreamTrig> trig(np);
     for (uint32_t k = 0; k < np; k++) {
@@ -221,30 +233,17 @@ static int stream_frames(wifirx_handle* h, bool flush, StageClock& stage, FrameP
         trig[k].pad = st.pending[k].have_cfo;   // the device computed when it first saw the trigger
         p.final_.push_back(fin);
     }
-    wr::DemodParams prm = params_of(h);
-    if (soft) prm.llr_bits = 6;                 // the stream's own LLR rows: every rate fits, whatever cfg.llr_bits says
-    HIP_TRY(h, hipMemcpyAsync(st.trig.p, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
-    const std::array<StreamOut, SO_N> outs = stream_outs(h);
-    for (const StreamOut& so : outs)
-        if (so.produced && so.zero) HIP_TRY(h, hipMemsetAsync(so.dev->p, 0, np * so.pitch, h->stream));
-    // hard decisions as bytes only when the caller polls them (WIFIRX_P_STREAM_IDX); decode_mac reads the bit planes
-    uint8_t* d_idx = outs[SO_IDX].produced ? st.idx.as<uint8_t>() : nullptr;
-    float* d_llr = soft ? st.llr.as<float>() : nullptr;
-    const wr::DemodOut dout = { st.frames.as<wifirx_frame>(), d_idx, d_llr, st.car.as<float2>(), st.csi.as<float2>(),
-                                st.stats.as<float4>(), st.hbits.as<uint32_t>() };
-    HIP_TRY(h, wr_launch_demod_stream(h->stream, st.sbuf.as<float2>(), st.sfill, st.trig.as<wr::StreamTrig>(), np,
-                                      &prm, st.A.as<float2>(), &dout));
-    const wifirx_out o = { st.frames.as<wifirx_frame>(), d_idx, d_llr, nullptr, st.psdu.as<uint8_t>(), 2048, 1,
-                           nullptr, nullptr, st.hbits.as<uint32_t>() };
-    stage("enqueue frame kernel");
-    if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
-    stage("frame kernel + decode_mac");
-    // the frame records first: they say how much of every output row (max_sym symbols, 2048 bytes) is worth bringing back.
-    // Each output's rows are cut to the batch's widest filled row and packed on the device, then leave in one piece for a
-    // pinned host buffer: a 2-D copy to pageable memory goes row by row and costs milliseconds.
-    p.fr.resize(np);
-    HIP_TRY(h, hipMemcpyAsync(p.fr.data(), st.frames.p, np * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return trig;
+}
+
+// The outputs of a pass to the host, p.fr (the records, already here) saying how much of every output row (max_sym symbols,
+// 2048 bytes) is worth bringing back.  Each output's rows are cut to the batch's widest filled row and packed on the device,
+// then leave in one piece for a pinned host buffer: a 2-D copy to pageable memory goes row by row and costs milliseconds.
+static int stream_pack_outputs(wifirx_handle* h, const std::array<StreamOut, SO_N>& outs, StageClock& stage, FramePass& p)
+{
+    StreamState& st = h->st;
+    const uint32_t np = (uint32_t)p.fr.size();
+    int rc;
     auto b = std::make_shared<StreamBatch>();
     size_t total = 0;
     for (int i = 0; i < SO_N; i++) {         // (widths start at 0: make_shared value-initialises)
@@ -263,8 +262,47 @@ static int stream_frames(wifirx_handle* h, bool flush, StageClock& stage, FrameP
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     stage("outputs to host");
     b->blob.assign(st.host.as<const uint8_t>(), st.host.as<const uint8_t>() + total);     // shared by the batch's frames
+    b->n_ant = p.n_ant;
+    b->used = std::move(p.used);
+    b->ant = std::move(p.ant);
     p.batch = std::move(b);
     return WIFIRX_OK;
+}
+
+// Frames: (3) the frame kernel + decode_mac over every pending trigger whose samples are (partly) here; records, outputs
+static int stream_frames(wifirx_handle* h, bool flush, StageClock& stage, FramePass& p)
+{
+    StreamState& st = h->st;
+    const uint32_t np = (uint32_t)st.pending.size();
+    if (!np) return WIFIRX_OK;
+    int rc;
+    if ((rc = stream_out_reserve(h, np))) return rc;
+    const bool soft = h->tune.stream_soft != 0;
+    if (soft && (rc = stream_llr_reserve(h))) return rc;
+    const std::vector<wr::StreamTrig> trig = stream_trig_rows(h, flush, p);
+    wr::DemodParams prm = params_of(h);
+    if (soft) prm.llr_bits = 6;                 // the stream's own LLR rows: every rate fits, whatever cfg.llr_bits says
+    HIP_TRY(h, hipMemcpyAsync(st.trig.p, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
+    const std::array<StreamOut, SO_N> outs = stream_outs(h);
+    for (const StreamOut& so : outs)
+        if (so.produced && so.zero) HIP_TRY(h, hipMemsetAsync(so.dev->p, 0, np * so.pitch, h->stream));
+    // hard decisions as bytes only when the caller polls them (WIFIRX_P_STREAM_IDX); decode_mac reads the bit planes
+    uint8_t* d_idx = outs[SO_IDX].produced ? st.idx.as<uint8_t>() : nullptr;
+    float* d_llr = soft ? st.llr.as<float>() : nullptr;
+    const wr::DemodOut dout = { st.frames.as<wifirx_frame>(), d_idx, d_llr, st.car.as<float2>(), st.csi.as<float2>(),
+                                st.stats.as<float4>(), st.hbits.as<uint32_t>() };
+    HIP_TRY(h, wr_launch_demod_stream(h->stream, st.sbuf.as<float2>(), st.sfill, st.trig.as<wr::StreamTrig>(), np,
+                                      &prm, st.A.as<float2>(), &dout));
+    const wifirx_out o = { st.frames.as<wifirx_frame>(), d_idx, d_llr, nullptr, st.psdu.as<uint8_t>(), 2048, 1,
+                           nullptr, nullptr, st.hbits.as<uint32_t>() };
+    stage("enqueue frame kernel");
+    if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
+    stage("frame kernel + decode_mac");
+    // the frame records first: they say how much of every output row is worth bringing back (stream_pack_outputs)
+    p.fr.resize(np);
+    HIP_TRY(h, hipMemcpyAsync(p.fr.data(), st.frames.p, np * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return stream_pack_outputs(h, outs, stage, p);
 }
 
 // Queue: the settled frames go to wifirx_poll, the others stay pending with the coarse CFO the device found (cannot fail)
@@ -280,7 +318,9 @@ static void stream_queue(wifirx_handle* h, const FramePass& p, StageClock& stage
         const bool truncated = (f.flags & WIFIRX_F_TRUNCATED) != 0;
         // a frame is settled when it is complete, when it failed for a reason more samples cannot
         // cure, or when no more samples can come (next trigger / MAX_SAMPLES / flush)
-        if (!(complete || !truncated || p.final_[k])) {
+        // (a diversity pass: when every antenna's record is complete or failed so -- p.hold)
+        const bool waits = p.hold.empty() ? !(complete || !truncated) : p.hold[k] != 0;
+        if (waits && !p.final_[k]) {
             keep.push_back({ st.pending[k].pos, f.cfo_coarse, true });
             continue;
         }
@@ -528,6 +568,9 @@ static int stream_push(wifirx_handle* h, const void* iq, size_t n, int fmt, floa
 {
     h->st.push_consumed = 0;
     if (n > 0 && !iq) return fail(h, WIFIRX_EINVAL, "iq is null");
+    // the two kinds of stream share the queue and the absolute sample index: one handle cannot mix them
+    if (h->div.n_ant) return fail(h, WIFIRX_EINVAL, "the handle's stream is a diversity stream (wifirx_push_diversity)");
+    if (n > 0) h->st.single = true;
     const bool flush = (n == 0);
     // Device input, or no batching: the pipeline runs in the caller's thread, as one pass per push.
     if (iq_on_device || h->tune.stream_batch <= 0) {
@@ -630,7 +673,10 @@ extern "C" int wifirx_poll_csi(wifirx_handle* h, wifirx_frame* frames, uint8_t* 
     return wifirx_poll_ex(h, &o, cap, n_out);
 }
 
-extern "C" int wifirx_poll_ex(wifirx_handle* h, const wifirx_poll_out* out, uint32_t cap, uint32_t* n_out)
+// wifirx_poll_ex and wifirx_poll_diversity: the latter also delivers, per frame, the contributing antennas and the antennas' own
+// records (zeros for the frames of a single stream)
+static int stream_poll(wifirx_handle* h, const wifirx_poll_out* out, uint8_t* used_mask, wifirx_frame* ant_frames,
+                       uint32_t n_ant, uint32_t cap, uint32_t* n_out)
 {
     if (!h || !n_out || !out) return WIFIRX_EINVAL;
     *n_out = 0;
@@ -652,10 +698,20 @@ extern "C" int wifirx_poll_ex(wifirx_handle* h, const wifirx_poll_out* out, uint
             if (c) std::memcpy(dst[o] + n * row, b.blob.data() + b.off[o] + pf.k * b.width[o], c);
             std::memset(dst[o] + n * row + c, 0, row - c);
         }
+        if (used_mask) used_mask[n] = pf.k < b.used.size() ? b.used[pf.k] : 0;
+        for (uint32_t a = 0; ant_frames && a < n_ant; a++) {
+            if (a < b.n_ant) ant_frames[(size_t)n * n_ant + a] = b.ant[(size_t)pf.k * b.n_ant + a];
+            else std::memset(&ant_frames[(size_t)n * n_ant + a], 0, sizeof(wifirx_frame));
+        }
         h->st.queue.pop_front();
         n++;
     }
     h->st.n_queued.store((uint32_t)h->st.queue.size(), std::memory_order_release);
     *n_out = n;
     return WIFIRX_OK;
+}
+
+extern "C" int wifirx_poll_ex(wifirx_handle* h, const wifirx_poll_out* out, uint32_t cap, uint32_t* n_out)
+{
+    return stream_poll(h, out, nullptr, nullptr, 0, cap, n_out);
 }

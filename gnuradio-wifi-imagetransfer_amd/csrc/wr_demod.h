@@ -30,10 +30,20 @@ struct DetectState {       // what a tile needs from the tile before it
 
 __device__ __forceinline__ DetectState detect_state_zero() { return { 0, 0, 0, 0, 0, 0 }; }
 
-// Processes tile [n0, n0+64) given this lane's sample xn = x[n0 + lane] and xd = x[n0 + lane - 16] (zero outside the
-// stream).  Returns the ballot of c[n] > thr; Ar/Ai = A[n] of this lane's sample.
-__device__ __forceinline__ uint64_t detect_tile_core(c32 xn, c32 xd, long n_samp, long n0, float thr,
-                                                     int lane, DetectState& ps, float& Ar, float& Ai)
+// The summand part of a tile: rule 3's a[n] = x[n] conj(x[n - 16]) and |x[n]|^2 of this lane's sample xn = x[n0 + lane] and
+// xd = x[n0 + lane - 16] (zero outside the stream).
+__device__ __forceinline__ void detect_summands(c32 xn, c32 xd, float& ar, float& ai, float& pw)
+{
+    ar = fma_(xn.im, xd.im, xn.re * xd.re);
+    ai = fma_(xn.im, xd.re, -(xn.re * xd.im));
+    pw = fma_(xn.im, xn.im, xn.re * xn.re);
+}
+
+// The window part of tile [n0, n0+64): rule 3's blocked window sums and threshold comparison over this lane's summands (one
+// antenna's, or rule 24's sums over the antennas: wr_detect_multi.hip).  Returns the ballot of c[n] > thr; Ar/Ai = A[n] and
+// P = P[n] of this lane's sample.
+__device__ __forceinline__ uint64_t detect_tile_windows(float ar, float ai, float pw, long n_samp, long n0, float thr,
+                                                        int lane, DetectState& ps, float& Ar, float& Ai, float& P)
 {
     const int q = lane >> 4;
     const int l16 = (lane + 16) & 63;              // lane that holds index lane-48 (mod 64)
@@ -41,9 +51,6 @@ __device__ __forceinline__ uint64_t detect_tile_core(c32 xn, c32 xd, long n_samp
     const int b2 = (((q - 2) & 3) << 4) | 15;
     const int b3 = (((q - 3) & 3) << 4) | 15;
     const long n = n0 + lane;
-    float ar = fma_(xn.im, xd.im, xn.re * xd.re);
-    float ai = fma_(xn.im, xd.re, -(xn.re * xd.im));
-    float pw = fma_(xn.im, xn.im, xn.re * xn.re);
     float Hr = row_prefix16(ar), Hi = row_prefix16(ai), Hp = row_prefix16(pw);
     float Tr = dpp_zero<0x101>(row_suffix16(ar));
     float Ti = dpp_zero<0x101>(row_suffix16(ai));
@@ -67,12 +74,22 @@ __device__ __forceinline__ uint64_t detect_tile_core(c32 xn, c32 xd, long n_samp
     float B1p = (q >= 1) ? cB1p : oB1p;
     Ar = ((t3r + B2r) + B1r) + Hr;
     Ai = ((t3i + B2i) + B1i) + Hi;
-    float P  = (((ps.Tp + B3p) + B2p) + B1p) + Hp; // tail of block m-4: same lane, previous tile
+    P  = (((ps.Tp + B3p) + B2p) + B1p) + Hp;       // tail of block m-4: same lane, previous tile
     float m2 = fma_(Ai, Ai, Ar * Ar);
     float tp = thr * P;
     bool above = (m2 > tp * tp) && (n < n_samp);
     ps = { Hr, Hi, Hp, Tr, Ti, Tp };
     return __ballot(above);
+}
+
+// Processes tile [n0, n0+64) given this lane's sample xn and xd: the summand part, then the window part.  Returns the ballot
+// of c[n] > thr; Ar/Ai = A[n] of this lane's sample.
+__device__ __forceinline__ uint64_t detect_tile_core(c32 xn, c32 xd, long n_samp, long n0, float thr,
+                                                     int lane, DetectState& ps, float& Ar, float& Ai)
+{
+    float ar, ai, pw, P;
+    detect_summands(xn, xd, ar, ai, pw);
+    return detect_tile_windows(ar, ai, pw, n_samp, n0, thr, lane, ps, Ar, Ai, P);
 }
 
 __device__ __forceinline__ uint64_t detect_tile(const float2* __restrict__ x, long n_samp, long n0, float thr,

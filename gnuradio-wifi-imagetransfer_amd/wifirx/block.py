@@ -36,7 +36,7 @@ LINKTYPE_IEEE802_11 = 105
 class wifi_phy_rx(grshim.sync_block):
     def __init__(self, bandwidth=10e6, chan_est=LS, encoding=0, frequency=5.89e9, sensitivity=0.56,
                  max_sym=511, publish_carrier=True, device=0, batch_samples=None, publish_csi=False, snr_probe=None,
-                 soft_decision=False, sample_format="fc32", sample_scale=None):
+                 soft_decision=False, sample_format="fc32", sample_scale=None, antennas=1, diversity="mrc", ant_gain=None):
         # sample_format: "fc32" (complex64 items, the default), or "sc16" / "sc8": items of two int16 / int8 (I, Q), the form
         # a UHD source with an sc16 CPU format delivers; they cross the bus as they are and are widened on the device
         # (value = integer * sample_scale, default 2^-15 / 2^-7; wifirx_push_iq, NUMERICS.md rule 20)
@@ -46,7 +46,23 @@ class wifi_phy_rx(grshim.sync_block):
         self.sample_scale = float(capi.IQ_SCALE[self.sample_format] if sample_scale is None else sample_scale)
         self._item = capi.IQ_DTYPE[self.sample_format]
         in_sig = [np.complex64] if self.sample_format == capi.IQ_FC32 else [(self._item.type, 2)]
-        grshim.sync_block.__init__(self, name="wifi_phy_rx", in_sig=in_sig, out_sig=None)
+        # antennas = A > 1: A `samp_in` ports of the item type, the sample-synchronous channels of ONE radio (a two-channel
+        # uhd.usrp_source).  Detection runs once, on all of them (NUMERICS.md rule 24), the antennas' equalised points are
+        # combined (`diversity`: "mrc" or "select"; ant_gain: the inverse noise power per antenna, None = equal; rule 23) and
+        # decoded once; `mac_out` and `carrier` are as with one antenna, with `antennas_used` (bit a = antenna a contributed)
+        # added to the PDU's dictionary.  antennas = 1 is the single-stream path, untouched.
+        self.antennas = int(antennas)
+        if not 1 <= self.antennas <= capi.DIV_MAX_ANT:
+            raise ValueError("antennas must be 1 .. %d" % capi.DIV_MAX_ANT)
+        if diversity not in capi.DIV_MODES:
+            raise ValueError("diversity must be 'mrc' or 'select'")
+        self.diversity = diversity
+        self.ant_gain = None
+        if ant_gain is not None:
+            self.ant_gain = np.array(ant_gain, dtype=np.float32).reshape(-1)
+            if self.ant_gain.size != self.antennas or not (np.isfinite(self.ant_gain).all() and (self.ant_gain >= 0).all()):
+                raise ValueError("ant_gain: one finite value >= 0 per antenna")
+        grshim.sync_block.__init__(self, name="wifi_phy_rx", in_sig=in_sig * self.antennas, out_sig=None)
         self.bandwidth = float(bandwidth)
         self.chan_est = int(chan_est)
         self.encoding = encoding            # TX-side parameter of the hier block: accepted, unused on RX
@@ -148,7 +164,34 @@ class wifi_phy_rx(grshim.sync_block):
         self.encoding = encoding
 
     # ---- stream interface ----
+    def _work_diversity(self, input_items):
+        """work() with antennas > 1: the common length of the ports is pushed and consumed on every port.  A failed push has
+        taken nothing (it is all or nothing): with raise_on_error it raises, otherwise 0 items are consumed and the scheduler
+        hands them in again; a dead stream ends the block."""
+        n = min(len(x) for x in input_items[:self.antennas])
+        if n:
+            xs = [x[:n] for x in input_items[:self.antennas]]
+            try:
+                self._rx.push_diversity(xs, self.diversity, self.ant_gain, self.sample_format, self.sample_scale)
+            except capi.WifiRxError as e:
+                self.push_errors += 1
+                self.last_error = str(e)
+                if e.code == capi.EDEAD:
+                    self.stream_dead = True
+                    self._publish()
+                    if self.raise_on_error:
+                        raise
+                    return -1
+                if self.raise_on_error:
+                    raise
+                n = 0
+            if self._queued(self._h):
+                self._publish()
+        return n
+
     def work(self, input_items, output_items):
+        if self.antennas > 1:
+            return self._work_diversity(input_items)
         x = input_items[0]
         n = len(x)
         if n:
@@ -186,6 +229,19 @@ class wifi_phy_rx(grshim.sync_block):
         """End of stream: settle the frames still waiting for samples.  A batch that failed on the library's worker thread is
         reported by the first flush (once, before it does anything) and run again by the second: flush until it goes through
         (at most three times), publish whatever is finished in any case, and only then -- with raise_on_error -- raise."""
+        if self.antennas > 1:
+            try:
+                if not self.stream_dead:
+                    self._rx.flush_diversity(self.diversity, self.ant_gain, self.antennas)
+            except capi.WifiRxError as e:
+                self.push_errors += 1
+                self.last_error = str(e)
+                self.stream_dead = self.stream_dead or e.code == capi.EDEAD
+                if self.raise_on_error:
+                    raise
+            finally:
+                self._publish()
+            return True
         rc = 0
         try:
             for _ in range(3):
@@ -210,8 +266,9 @@ class wifi_phy_rx(grshim.sync_block):
         pub, make = self.message_port_pub, grshim.make_pdu
         want_car = self.publish_carrier
         while True:
-            r = self._rx.poll(cap=1024, psdu_stride=2048, want_csi=self.publish_csi, want_stats=self.snr_probe is not None,
-                              trim_psdu=True)
+            poll = self._rx.poll if self.antennas == 1 else self._rx.poll_diversity
+            r = poll(cap=1024, psdu_stride=2048, want_csi=self.publish_csi, want_stats=self.snr_probe is not None, trim_psdu=True)
+            used = r.get("used_mask")           # diversity: which antennas contributed to every frame
             fr = r["frames"]
             nf = len(fr)
             if nf == 0:
@@ -249,7 +306,7 @@ class wifi_phy_rx(grshim.sync_block):
             freq = self.frequency
             csi = r["csi"] if self.publish_csi else None
             p_mac = self._p_mac
-            if csi is None and not grshim.HAVE_GNURADIO:
+            if csi is None and used is None and not grshim.HAVE_GNURADIO:
                 # the common case on the shim, kept tight: a PDU is (dict, row view) -- poll() handed out its own copy of the rows
                 for i in ok:
                     pub(p_mac, ({"frame_bytes": plen[i], "encoding": enc[i], "snr": snr[i], "freq": freq,
@@ -260,6 +317,8 @@ class wifi_phy_rx(grshim.sync_block):
                         "freq_offset": foff[i], "dlt": LINKTYPE_IEEE802_11}
                 if csi is not None:
                     meta["csi"] = csi[i]
+                if used is not None:
+                    meta["antennas_used"] = int(used[i])
                 pub(p_mac, make(meta, psdu[i, :plen[i] - 4]))
 
     def get_probe_snr(self):

@@ -49,6 +49,7 @@ EXPORTS = [
     "wifirx_channel_sro", "wifirx_resampler_table", "wifirx_channel_fading",
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
     "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine", "wifirx_diversity_combine",
+    "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi",
 ]
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
@@ -163,6 +164,12 @@ class PollOut(C.Structure):
                 ("idx", C.c_void_p), ("carrier", C.c_void_p), ("csi", C.c_void_p), ("sym_stats", C.c_void_p)]
 
 
+class DivStream(C.Structure):
+    """wifirx_div_stream: what a wifirx_push_diversity call says about its antennas"""
+    _fields_ = [("n_ant", C.c_uint32), ("mode", C.c_int), ("ant_gain", C.POINTER(C.c_float)), ("fmt", C.c_int),
+                ("scale", C.c_float), ("iq_on_device", C.c_int)]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_in", C.c_uint64), ("frames_detected", C.c_uint64), ("frames_signal_ok", C.c_uint64),
                 ("frames_complete", C.c_uint64), ("frames_crc_ok", C.c_uint64), ("frames_dropped", C.c_uint64)]
@@ -234,6 +241,10 @@ _lib.wifirx_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.
                                 C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
 _lib.wifirx_diversity_combine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.c_uint32, C.c_int, C.POINTER(C.c_float),
                                           C.POINTER(Out), C.c_void_p]
+_lib.wifirx_push_diversity.argtypes = [C.c_void_p, C.POINTER(DivStream), C.POINTER(C.c_void_p), C.c_size_t]
+_lib.wifirx_poll_diversity.argtypes = [C.c_void_p, C.POINTER(PollOut), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+_lib.wifirx_detect_multi.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint64, C.c_float, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
 _lib.wifirx_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.wifirx_dev_free.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -932,6 +943,81 @@ class WifiRx:
 
     def flush(self):
         self._check(_lib.wifirx_push(self._h, None, 0, 0))
+
+    # -- stream-mode receive diversity (wifirx_push_diversity; NUMERICS.md rules 24 and 23) --
+    def _push_diversity(self, ptrs, n, mode, ant_gain, fmt, scale, on_device):
+        mode = DIV_MODES[mode] if isinstance(mode, str) else int(mode)
+        n_ant = len(ptrs)
+        g = None
+        if ant_gain is not None:
+            g = np.ascontiguousarray(ant_gain, dtype=np.float32).reshape(-1)
+            if g.size != n_ant:
+                raise ValueError("one gain per antenna is required")
+        cfg = DivStream(n_ant, mode, None if g is None else g.ctypes.data_as(C.POINTER(C.c_float)), fmt,
+                        float(IQ_SCALE.get(fmt, 1.0) if scale is None else scale), int(on_device))
+        arr = (C.c_void_p * max(n_ant, 1))(*ptrs)
+        self._check(_lib.wifirx_push_diversity(self._h, C.byref(cfg), arr, int(n)))
+        self._div_n_ant = n_ant
+
+    def push_diversity(self, iqs, mode=DIV_MRC, ant_gain=None, fmt=None, scale=None):
+        """wifirx_push_diversity on host arrays: iqs = one array per antenna of ONE radio (sample-synchronous, one length), the
+        next samples of each.  fmt None: complex64, or taken from int16 (sc16) / int8 (sc8) arrays of shape [n, 2] or flat
+        [2 n]; scale None: the format's conventional one.  mode: DIV_MRC / DIV_SELECT (or "mrc" / "select"); ant_gain: one
+        finite float >= 0 per antenna, the inverse noise power (None: equal noise).  The number of antennas is fixed by the
+        handle's first call, and a handle that has taken samples through push() takes none here."""
+        if fmt is None and np.asarray(iqs[0]).dtype.kind != "i":
+            fmt = IQ_FC32
+        if fmt is not None and iq_format(fmt) == IQ_FC32:
+            keep, fmt = [np.ascontiguousarray(x, dtype=np.complex64).reshape(-1) for x in iqs], IQ_FC32
+            ns = [x.size for x in keep]
+        else:
+            conv = [self._iq_array(x, fmt) for x in iqs]
+            keep, fmt, ns = [c[0] for c in conv], conv[0][1], [c[2] for c in conv]
+            if any(c[1] != fmt for c in conv):
+                raise ValueError("one sample format for all antennas")
+        if len(set(ns)) != 1:
+            raise ValueError("the antennas of one radio deliver the same number of samples")
+        self._push_diversity([x.ctypes.data for x in keep], ns[0], mode, ant_gain, fmt, scale, 0)
+
+    def push_diversity_dev(self, ptrs, n, mode=DIV_MRC, ant_gain=None, fmt="fc32", scale=None):
+        """wifirx_push_diversity on device memory: ptrs = one pointer per antenna to its next n samples of `fmt`"""
+        self._push_diversity([int(p) for p in ptrs], n, mode, ant_gain, iq_format(fmt), scale, 1)
+
+    def flush_diversity(self, mode=DIV_MRC, ant_gain=None, n_ant=None):
+        """end of the diversity stream: settles the frames still waiting for samples (n_ant: that of the pushes before)"""
+        n_ant = getattr(self, "_div_n_ant", 1) if n_ant is None else int(n_ant)
+        self._push_diversity([None] * n_ant, 0, mode, ant_gain, IQ_FC32, None, 0)
+
+    def poll_diversity(self, cap=256, psdu_stride=2048, want_idx=False, want_csi=False, want_stats=False, trim_psdu=False,
+                       n_ant=None):
+        """poll() for a diversity stream: the same dict plus used_mask (uint8 [n], bit a = antenna a contributed to the
+        frame) and ant_frames (records [n, n_ant]: every antenna's own record of the frame, with the joint trigger)."""
+        ms = self.cfg.max_sym
+        n_ant = getattr(self, "_div_n_ant", 1) if n_ant is None else int(n_ant)
+        frames, psdu = np.zeros(cap, dtype=FRAME_DTYPE), np.zeros((cap, psdu_stride), dtype=np.uint8)
+        idx = np.zeros((cap, ms, 48), dtype=np.uint8) if want_idx else None
+        car = np.zeros((cap, ms, 48), dtype=np.complex64) if self.cfg.want_carrier else None
+        csi = np.zeros((cap, 52), dtype=np.complex64) if want_csi else None
+        stats = np.zeros((cap, 4), dtype=np.float32) if want_stats else None
+        used, ant = np.zeros(cap, dtype=np.uint8), np.zeros((cap, n_ant), dtype=FRAME_DTYPE)
+        out = PollOut(_np_ptr(frames), _np_ptr(psdu), psdu_stride, 0, _np_ptr(idx), _np_ptr(car), _np_ptr(csi), _np_ptr(stats))
+        n = C.c_uint32(0)
+        self._check(_lib.wifirx_poll_diversity(self._h, C.byref(out), _np_ptr(used), _np_ptr(ant), cap, C.byref(n)))
+        n = n.value
+        w = psdu_stride
+        if trim_psdu and n:
+            w = min(max(int(frames["psdu_len"][:n].max()), 1), psdu_stride)
+        return dict(frames=frames[:n].copy(), psdu=psdu[:n, :w].copy(), idx=None if idx is None else idx[:n].copy(),
+                    carrier=None if car is None else car[:n].copy(), csi=None if csi is None else csi[:n].copy(),
+                    sym_stats=None if stats is None else stats[:n].copy(), used_mask=used[:n].copy(), ant_frames=ant[:n].copy())
+
+    def detect_multi_dev(self, iq_ptrs, n, threshold, masks_ptr, A_ptr, P_ptr=None):
+        """wifirx_detect_multi: NUMERICS.md rule 24 over n samples of every antenna at the device pointers iq_ptrs, from the
+        capture's origin: masks (uint64 [ceil(n / 64)]) at masks_ptr, A (complex64 [n]) at A_ptr, P (float32 [n]) at P_ptr
+        or None.  One antenna is the stream detector's metric.  Asynchronous on the handle's stream."""
+        ptrs = [int(p) if p is not None else None for p in iq_ptrs]
+        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        self._check(_lib.wifirx_detect_multi(self._h, len(ptrs), arr, int(n), float(threshold), masks_ptr, A_ptr, P_ptr))
 
     def queued(self) -> int:
         """finished frames waiting for poll()"""

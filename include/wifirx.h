@@ -682,6 +682,57 @@ int  wifirx_combine(wifirx_handle* h, const float* in, uint64_t in_stride, const
 int  wifirx_diversity_combine(wifirx_handle* h, uint32_t n_ant, const wifirx_out* in, uint32_t n_slots, int mode,
                               const float* ant_gain, const wifirx_out* out, uint8_t* used_mask);
 
+/* Stream-mode receive diversity (NUMERICS.md rules 24 and 23): wifirx_push for the n_ant sample-synchronous antennas of ONE
+ * radio (a multi-channel USRP).  Detection runs once, on the sum of the antennas' autocorrelations and powers (rule 24), so
+ * every antenna gets the same triggers and the same coarse CFO, and slot i of every antenna is the same transmission by
+ * construction; per trigger every antenna's samples go through the frame kernel, the combiner of wifirx_diversity_combine
+ * joins the n_ant rows, and decode_mac runs once, on the combined rows (on LLRs under WIFIRX_P_STREAM_SOFT).  Antennas that
+ * are not sample-synchronous (several radios) are not what this takes: that needs the triggers of independent streams
+ * associated, which is not built.
+ *   cfg->n_ant      1 .. 8, fixed by the handle's first call.  One antenna gives, byte for byte, the stream of wifirx_push.
+ *   cfg->mode       WIFIRX_DIV_MRC / WIFIRX_DIV_SELECT, cfg->ant_gain HOST [n_ant] or NULL: as wifirx_diversity_combine
+ *   cfg->fmt, scale the sample format of every iq[a] (WIFIRX_IQ_*; scale widens the integer ones, rule 20)
+ *   iq              HOST [n_ant] pointers, iq[a] = n samples of antenna a, host or device memory (cfg->iq_on_device), at the
+ *                   format's natural alignment; n = 0 flushes.  DEVICE INPUT: what wifirx_push guarantees.
+ * Everything runs in the caller's thread on the handle's stream: the pinned staging ring and the worker thread of wifirx_push
+ * are not built for n_ant host streams.  WIFIRX_P_STREAM_BATCH > 0 keeps its meaning for device input: the call only collects
+ * until that many samples wait.  A trigger settles when it is final (next trigger, WIFIRX_MAX_SAMPLES, flush) or when every
+ * antenna's record is complete or failed for a reason more samples cannot cure.  All or nothing: after an error return the
+ * stream is what it was before the call, and the call can be repeated as it was (wifirx_push_consumed is not involved).
+ * DELIVERY: frames go to the handle's queue; wifirx_poll, wifirx_poll_csi, wifirx_poll_ex, wifirx_queued and wifirx_get_stats
+ * work unchanged, and the statistics count a combined frame once.  The delivered record is the combiner's -- the reference
+ * antenna's, then decoded --, idx / carrier / psdu are those of the combined points; the csi and sym_stats rows are the
+ * reference antenna's own: the lowest usable antenna whose snr_db equals the combined record's (antenna 0 where no antenna is
+ * usable).  A frame without a usable antenna is delivered as antenna 0's record with WIFIRX_F_COMPLETE cleared and zero rows.
+ * WIFIRX_EINVAL, checked on the host before anything is queued and with the stream untouched: a NULL handle, cfg or iq, a NULL
+ * iq[a] with n > 0, n_ant outside 1 .. 8 or different from the handle's first call, an unknown mode or fmt, a scale that is not
+ * finite or <= 0 (integer formats), an ant_gain that is not finite or is negative, misaligned buffers, and a handle whose stream
+ * has already taken samples through wifirx_push / wifirx_push_iq -- as those two refuse a handle that wifirx_push_diversity
+ * has been called on: the two kinds of stream share the queue and the absolute sample index.  WIFIRX_EDEAD as for wifirx_push. */
+typedef struct {
+    uint32_t n_ant;          /* 1 .. 8, fixed by the handle's first call */
+    int      mode;           /* WIFIRX_DIV_MRC / WIFIRX_DIV_SELECT */
+    const float* ant_gain;   /* HOST [n_ant] or NULL, as wifirx_diversity_combine */
+    int      fmt;            /* WIFIRX_IQ_* */
+    float    scale;
+    int      iq_on_device;
+} wifirx_div_stream;
+
+/* n samples of EVERY antenna (sample-synchronous); n = 0 flushes */
+int  wifirx_push_diversity(wifirx_handle* h, const wifirx_div_stream* cfg, const void* const* iq, size_t n);
+
+/* wifirx_poll_ex plus, per frame, which antennas contributed and every antenna's own record
+ * (used_mask [cap], ant_frames [cap][n_ant]; either may be NULL).  Every antenna's record carries the joint trigger. */
+int  wifirx_poll_diversity(wifirx_handle* h, const wifirx_poll_out* out, uint8_t* used_mask,
+                           wifirx_frame* ant_frames, uint32_t cap, uint32_t* n_out);
+
+/* Rule 24 over a device-resident capture from its origin: masks [ceil(n/64)] (bit l of word t = c[64 t + l] > threshold),
+ * A [n] float pairs, P [n] or NULL; nothing is written behind them.  n_ant = 1 is the stream detector's metric (what the
+ * reference plots on its correlation sink).  iq_dev: HOST [n_ant] device pointers, 8-byte aligned.  WIFIRX_EINVAL for NULL
+ * arguments, n_ant outside 1 .. 8, a negative or NaN threshold and misaligned buffers.  Asynchronous on the handle's stream. */
+int  wifirx_detect_multi(wifirx_handle* h, uint32_t n_ant, const float* const* iq_dev, uint64_t n,
+                         float threshold, uint64_t* masks_dev, float* A_dev, float* P_dev);
+
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);
 int  wifirx_dev_free(wifirx_handle* h, void* p);
