@@ -26,6 +26,7 @@
 #include "wr_kernels.h"
 #include "wr_tx.h"
 #include "wr_channel.h"
+#include "wr_irs.h"
 #include "wr_link.h"
 #include "wr_convert.h"
 #include "wr_channelizer.h"
@@ -125,6 +126,7 @@ struct Staging {
     DevBuf off;                     // slot offsets of wifirx_demod_batch_v
     DevBuf tx_psdu, tx_meta;        // wifirx_tx_batch: host PSDUs; lengths, seeds, row offsets
     DevBuf ch_meta;                 // wifirx_channel: host taps, phase increments, row offsets, tile bases
+    DevBuf irs_meta;                // wifirx_irs_taps: line-of-sight vectors, tap scales, host psi
     DevBuf link_meta, link_payload; // wifirx_mac_batch: payload lengths; host payloads
     DevBuf link_counts;             // wifirx_link_stats: the nine counters
     DevBuf iq_clipped;              // wifirx_iq_from_f32: the counter of clipped components
@@ -626,6 +628,7 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_stream.inc"
 #include "wifirx_api_tx.inc"
 #include "wifirx_api_channel.inc"
+#include "wifirx_api_irs.inc"
 #include "wifirx_api_link.inc"
 #include "wifirx_api_convert.inc"
 #include "wifirx_api_bank.inc"

@@ -1,0 +1,84 @@
+// IRS entry point: the tap sets of a reflecting surface's cascade channel, made on the device (wr_irs.hip, NUMERICS.md rule 25)
+
+extern "C" int wifirx_irs_taps(wifirx_handle* h, float* taps_out, uint32_t n_sets, uint32_t n_taps, const float* pdp, float gain,
+                               uint32_t n_elems, const float* los_b2r, const float* los_r2u, const float* los_b2u,
+                               float k_factor, float direct_gain,
+                               const float* psi, int psi_on_device, uint32_t n_psi_sets, uint32_t align_bits,
+                               const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
+                               float* elems_out, uint8_t* codes_out)
+{
+    if (!h) return WIFIRX_EINVAL;
+    // ---- the argument checks, before anything is queued ----
+    if (!taps_out || !pdp || !los_b2r || !los_r2u) return fail(h, WIFIRX_EINVAL, "taps_out, pdp, los_b2r and los_r2u are required");
+    if (n_elems < 1 || n_elems > wr_irs_max_elems()) return fail(h, WIFIRX_EINVAL, "n_elems must be 1..4096");
+    if (n_taps < 1 || n_taps > wr_irs_max_taps()) return fail(h, WIFIRX_EINVAL, "n_taps must be 1..16");
+    if (align_bits > 3) return fail(h, WIFIRX_EINVAL, "align_bits must be 0..3");
+    if (!std::isfinite(gain) || !std::isfinite(direct_gain)) return fail(h, WIFIRX_EINVAL, "gain and direct_gain must be finite");
+    if (!(std::isfinite(k_factor) && k_factor >= 0.0f)) return fail(h, WIFIRX_EINVAL, "k_factor must be finite and not negative");
+    if (direct_gain != 0.0f && !los_b2u) return fail(h, WIFIRX_EINVAL, "los_b2u is required with a direct path");
+    if (align_bits == 0 && !psi) return fail(h, WIFIRX_EINVAL, "psi is required when align_bits is 0");
+    if (align_bits == 0 && n_psi_sets == 0) return fail(h, WIFIRX_EINVAL, "n_psi_sets must be >= 1 when align_bits is 0");
+    if (align_bits == 0 && codes_out) return fail(h, WIFIRX_EINVAL, "codes_out needs align_bits 1..3");
+    if (scatter && n_scatter == 0) return fail(h, WIFIRX_EINVAL, "n_scatter must be >= 1 with scatter");
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    const bool psi_read = align_bits == 0;
+    if ((addr(taps_out) | addr(scatter) | addr(elems_out) | (psi_read && psi_on_device ? addr(psi) : 0)) & 7)
+        return fail(h, WIFIRX_EINVAL, "taps_out, scatter, elems_out and device psi must be 8-byte aligned (complex64)");
+    if ((addr(pdp) | addr(los_b2r) | addr(los_r2u) | addr(los_b2u) | (psi_read && !psi_on_device ? addr(psi) : 0)) & 3)
+        return fail(h, WIFIRX_EINVAL, "the host arrays must be 4-byte aligned (float32)");
+    for (uint32_t l = 0; l < n_taps; l++)
+        if (!(std::isfinite(pdp[l]) && pdp[l] >= 0.0f)) return fail(h, WIFIRX_EINVAL, "pdp must be finite and not negative");
+    if (n_sets == 0) return WIFIRX_OK;
+    if (n_sets > 0x7fffffffu) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 tap sets");
+    const bool host_psi = psi_read && !psi_on_device;
+    if (host_psi && (uint64_t)n_psi_sets * n_elems * 8 > (1ull << 31)) return fail(h, WIFIRX_ERANGE, "host psi above 2 GiB");
+
+    stream_worker_wait_idle(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    wr::IrsArgs a{};
+    // one upload of what the host holds, as channel_call does it: add() appends an array to `meta` at 8-byte alignment and
+    // notes which device pointer of `a` is to name it once the copy has its place
+    std::vector<uint8_t> meta;
+    std::vector<std::pair<void*, size_t>> named;
+    auto add = [&](void* dev_ptr, const void* host, size_t bytes) {
+        const size_t off = (meta.size() + 7) & ~(size_t)7;
+        meta.resize(off + bytes);
+        std::memcpy(meta.data() + off, host, bytes);
+        named.emplace_back(dev_ptr, off);
+    };
+    std::vector<float> scale(n_taps);                  // s_l = (float)(sqrt(pdp_l) gain), formed in double
+    for (uint32_t l = 0; l < n_taps; l++) scale[l] = (float)(std::sqrt((double)pdp[l]) * (double)gain);
+    add(&a.los_a, los_b2r, 8ull * n_elems);
+    add(&a.los_b, los_r2u, 8ull * n_elems);
+    add(&a.scale, scale.data(), 4ull * n_taps);
+    a.psi = reinterpret_cast<const float2*>(psi);
+    if (host_psi) add(&a.psi, psi, 8ull * n_psi_sets * n_elems);
+    int rc;
+    if ((rc = h->stage.irs_meta.reserve(h, meta.size()))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->stage.irs_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, h->stream));
+    // the host arrays (the caller's and `meta`) may go once this returns: wait for the copy, not for the kernel
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (const auto& n : named) {
+        const uint8_t* dev = h->stage.irs_meta.as<uint8_t>() + n.second;
+        std::memcpy(n.first, &dev, sizeof dev);
+    }
+    a.taps_out = reinterpret_cast<float2*>(taps_out);
+    a.scatter = reinterpret_cast<const float2*>(scatter);
+    a.elems_out = reinterpret_cast<float2*>(elems_out);
+    a.codes_out = codes_out;
+    if (direct_gain != 0.0f) a.los_d = make_float2(los_b2u[0], los_b2u[1]);
+    a.seed = irs_seed;
+    a.n_sets = n_sets;
+    a.n_taps = n_taps;
+    a.n_elems = n_elems;
+    a.n_psi_sets = psi_read ? n_psi_sets : 1;
+    a.n_scatter = scatter ? n_scatter : 1;
+    a.align_bits = align_bits;
+    if (k_factor > 0.0f) {                              // formed in double; k_factor = 0: neither is applied (a_los = 0 says so)
+        a.a_los = (float)std::sqrt((double)k_factor / ((double)k_factor + 1.0));
+        a.a_nlos = (float)std::sqrt(1.0 / ((double)k_factor + 1.0));
+    }
+    a.direct_gain = direct_gain;
+    HIP_TRY(h, wr_launch_irs(h->stream, &a));
+    return WIFIRX_OK;
+}

@@ -28,6 +28,16 @@ struct ChanArgs {
     float           a_los, a_nlos;      // sqrt(K / (K + 1)), sqrt(1 / (K + 1)); a_los = 0: k_factor = 0, neither is applied
 };
 
+#ifdef __HIPCC__
+// rule 17: plain float32 products and sums, no fma (-ffp-contract=off keeps them apart)
+__device__ __forceinline__ float2 ch_mul(float2 a, float2 b)
+{
+    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+
+__device__ __forceinline__ float2 ch_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+#endif
+
 }  // namespace wr
 
 extern "C" {

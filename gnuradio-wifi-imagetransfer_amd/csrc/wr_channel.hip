@@ -21,8 +21,8 @@
 #include <stdint.h>
 
 #include "wr_device.h"     // sp_sincos (rule 1)
-#include "wr_rng.h"        // philox4x32_10, u01
-#include "wr_channel.h"
+#include "wr_rng.h"        // philox4x32_10, u01, ch_noise
+#include "wr_channel.h"    // ch_mul, ch_add
 #include "wr_resample_table.h"
 
 namespace wr {
@@ -43,14 +43,6 @@ __device__ const float rs_table[(WR_RS_PHASES + 1) * WR_RS_TAPS] = WR_RS_TABLE_I
 
 constexpr float CH_PHASE_SCALE = (float)(6.283185307179586 / 4294967296.0);      // 2 pi / 2^32: radians per unit of P >> 32
 
-// rule 17: plain float32 products and sums, no fma (-ffp-contract=off keeps them apart)
-__device__ __forceinline__ float2 ch_mul(float2 a, float2 b)
-{
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-__device__ __forceinline__ float2 ch_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-
 // sample n of the row after the FIR: gain * (s * exp(j phi(n)))
 __device__ __forceinline__ float2 ch_rotate(float2 s, uint64_t P, float gain)
 {
@@ -69,15 +61,6 @@ __device__ __forceinline__ uint64_t ch_phase_inc(float cfo)
     const double v = f * 0x1p64;
     if (v >= 0x1p63 || v <= -0x1p63) return 1ull << 63;
     return (uint64_t)(int64_t)__builtin_round(v);          // round: half away from zero, as llround
-}
-
-// one Box-Muller sample of wr_synth.hip: radius from ua, angle from ub, each component h * r * (cos | sin)
-__device__ __forceinline__ float2 ch_noise(uint32_t ua, uint32_t ub, float h)
-{
-    const float r = sqrtf(-2.0f * logf(u01(ua)));
-    float s, c;
-    sincosf(6.283185307179586f * u01(ub), &s, &c);
-    return make_float2(h * r * c, h * r * s);
 }
 
 __device__ __forceinline__ uint4 ch_draw(uint64_t pair, uint32_t row, uint2 key)

@@ -1,0 +1,155 @@
+// wr_irs.hip -- the cascade channel of an intelligent reflecting surface on the device (the model of the reference's
+// utils/SV_channel.py and utils/channel.py, H = H_B2R diag(psi) H_R2U + H_B2U, for one AP antenna and one user), in the
+// float32 arithmetic of NUMERICS.md rule 25: per tap set r and tap l the Rician mix of N element pairs and of the direct
+// path, the surface's phases (given, or aligned per draw to B bits), the sum over the surface and the tap's scale.
+//
+// Work split: one workgroup of four waves owns one tap set; its waves walk the set's taps (wave w: l = w, w + 4, ...).
+// Lane i of the wave that owns tap l forms the elements n = i, i + 64, ... in ascending n and sums their products; the 64
+// partial sums are folded by a __shfl_xor butterfly (no LDS, no barrier), so every lane holds the sum, and lane 0 stores the
+// tap.  The generator is compute-bound (a Philox draw and two Box-Mullers per element against 8 bytes out per N elements).
+//   aligned mode   the codes are decided on tap 0 and serve every tap of the set: the workgroup's 256 lanes form tap 0's
+//                  elements once, lane t the elements t, t + 256, ..., and leave the codes in LDS (N bytes) behind the kernel's
+//                  one barrier.  The other choice, every wave forming tap 0 again beside its own tap, doubles the Philox work
+//                  of every tap; this one adds 1 / L of it (the wave that owns tap 0 forms those elements a second time).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "wr_rng.h"        // philox4x32_10, ch_noise
+#include "wr_channel.h"    // ch_mul, ch_add
+#include "wr_irs.h"
+
+namespace wr {
+
+#define IRS_MAX_ELEMS 4096
+#define IRS_MAX_TAPS  16
+#define IRS_WAVES     4
+#define IRS_DIRECT    0xFFFFFFFFu      // counter word 0 of the direct path's draw (an element has n < 4096)
+
+// C_k = exp(j 2 pi k / 8); code c of a B-bit surface is C_{c << (3 - B)}
+__device__ const float2 irs_phase[8] = {
+    {1.0f, 0.0f}, {0.70710678118654752f, 0.70710678118654752f}, {0.0f, 1.0f}, {-0.70710678118654752f, 0.70710678118654752f},
+    {-1.0f, 0.0f}, {-0.70710678118654752f, -0.70710678118654752f}, {0.0f, -1.0f}, {0.70710678118654752f, -0.70710678118654752f}};
+
+// the Rician mix of one coefficient: a_los * los + a_nlos * w per part; k_factor = 0: w itself
+__device__ __forceinline__ float2 irs_mix(const IrsArgs& a, float2 los, float2 w)
+{
+    if (a.a_los == 0.0f) return w;
+    return make_float2(a.a_los * los.x + a.a_nlos * w.x, a.a_los * los.y + a.a_nlos * w.y);
+}
+
+// row of `scatter` that the pair (r, l) reads
+__device__ __forceinline__ const float2* irs_row(const IrsArgs& a, uint32_t r, uint32_t l)
+{
+    return a.scatter + (((uint64_t)r * a.n_taps + l) % a.n_scatter) * (2ull * a.n_elems + 1);
+}
+
+struct IrsElem { float2 a, b; };
+
+// element n of tap l of set r: the two legs after the mix
+__device__ __forceinline__ IrsElem irs_elem(const IrsArgs& a, uint32_t r, uint32_t l, uint32_t n, uint2 key)
+{
+    float2 wa, wb;
+    if (a.scatter) {
+        const float2* row = irs_row(a, r, l);
+        wa = row[n];
+        wb = row[a.n_elems + n];
+    } else {
+        const uint4 d = philox4x32_10(make_uint4(n, r, l, 2u), key);
+        wa = ch_noise(d.x, d.y, 0.70710678118654752f);
+        wb = ch_noise(d.z, d.w, 0.70710678118654752f);
+    }
+    const bool los = a.a_los != 0.0f;
+    const float2 zero = make_float2(0.0f, 0.0f);
+    return {irs_mix(a, los ? a.los_a[n] : zero, wa), irs_mix(a, los ? a.los_b[n] : zero, wb)};
+}
+
+// the direct path of tap l of set r (the same value in every lane)
+__device__ __forceinline__ float2 irs_direct(const IrsArgs& a, uint32_t r, uint32_t l, uint2 key)
+{
+    if (a.direct_gain == 0.0f) return make_float2(0.0f, 0.0f);
+    float2 w;
+    if (a.scatter) {
+        w = irs_row(a, r, l)[2 * a.n_elems];
+    } else {
+        const uint4 d = philox4x32_10(make_uint4(IRS_DIRECT, r, l, 2u), key);
+        w = ch_noise(d.x, d.y, 0.70710678118654752f);
+    }
+    const float2 v = irs_mix(a, a.los_d, w);
+    return make_float2(a.direct_gain * v.x, a.direct_gain * v.y);
+}
+
+// ALIGN: the phases are the B-bit codes decided on tap 0 (rule 25, genie bound), not a.psi
+template <bool ALIGN>
+__global__ __launch_bounds__(64 * IRS_WAVES)
+void irs_kernel(const IrsArgs a)
+{
+    __shared__ uint8_t codes[ALIGN ? IRS_MAX_ELEMS : 1];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t r = blockIdx.x, N = a.n_elems, L = a.n_taps;
+    const uint2 key = make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    const uint32_t up = 3 - a.align_bits;               // ALIGN: code c is irs_phase[c << up]
+
+    if constexpr (ALIGN) {
+        const float2 hd = irs_direct(a, r, 0, key);
+        const bool axis = hd.x == 0.0f && hd.y == 0.0f;     // no direct path to align to: the positive real axis
+        const float2 hc = make_float2(hd.x, -hd.y);
+        const uint32_t n_codes = 1u << a.align_bits;
+        for (uint32_t n = tid; n < N; n += 64 * IRS_WAVES) {
+            const IrsElem e = irs_elem(a, r, 0, n, key);
+            float2 g = ch_mul(e.a, e.b);
+            if (!axis) g = ch_mul(hc, g);
+            uint32_t best = 0;
+            float top = ch_mul(g, irs_phase[0]).x;
+            for (uint32_t c = 1; c < n_codes; c++) {
+                const float m = ch_mul(g, irs_phase[c << up]).x;
+                if (m > top) { top = m; best = c; }        // the lowest c wins a tie
+            }
+            codes[n] = (uint8_t)best;
+            if (a.codes_out) a.codes_out[(uint64_t)r * N + n] = (uint8_t)best;
+        }
+        __syncthreads();
+    }
+
+    const float2* psi = ALIGN ? nullptr : a.psi + (uint64_t)(r % a.n_psi_sets) * N;
+    for (uint32_t l = wave; l < L; l += IRS_WAVES) {
+        float2 acc = make_float2(0.0f, 0.0f);               // a lane without an element holds +0
+        float2* eo = a.elems_out ? a.elems_out + ((uint64_t)r * L + l) * 2ull * N : nullptr;
+        for (uint32_t n = lane; n < N; n += 64) {
+            const IrsElem e = irs_elem(a, r, l, n, key);
+            if (eo) {
+                eo[n] = e.a;
+                eo[N + n] = e.b;
+            }
+            float2 ph;
+            if constexpr (ALIGN) ph = irs_phase[(uint32_t)codes[n] << up];
+            else ph = psi[n];
+            const float2 p = ch_mul(ch_mul(e.a, ph), e.b);
+            acc = n == lane ? p : ch_add(acc, p);           // ascending n, from the lane's first product
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {                 // symmetric: every lane ends with the same bits
+            const float ox = __shfl_xor(acc.x, m), oy = __shfl_xor(acc.y, m);
+            acc = make_float2(acc.x + ox, acc.y + oy);
+        }
+        const float2 h = ch_add(irs_direct(a, r, l, key), acc);
+        const float s = a.scale[l];
+        if (lane == 0) a.taps_out[(uint64_t)r * L + l] = make_float2(h.x * s, h.y * s);
+    }
+}
+
+}  // namespace wr
+
+extern "C" hipError_t wr_launch_irs(hipStream_t st, const wr::IrsArgs* args)
+{
+    if (args->n_sets == 0) return hipSuccess;
+    if (args->n_elems < 1 || args->n_elems > IRS_MAX_ELEMS || args->n_taps < 1 || args->n_taps > IRS_MAX_TAPS ||
+        args->align_bits > 3 || args->n_sets > 0x7fffffffu)
+        return hipErrorInvalidValue;                        // (the entry point refuses these first)
+    const dim3 grid(args->n_sets), block(64 * IRS_WAVES);
+    if (args->align_bits) hipLaunchKernelGGL((wr::irs_kernel<true>), grid, block, 0, st, *args);
+    else hipLaunchKernelGGL((wr::irs_kernel<false>), grid, block, 0, st, *args);
+    return hipGetLastError();
+}
+
+extern "C" uint32_t wr_irs_max_elems(void) { return IRS_MAX_ELEMS; }
+extern "C" uint32_t wr_irs_max_taps(void) { return IRS_MAX_TAPS; }

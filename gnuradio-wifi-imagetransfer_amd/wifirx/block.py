@@ -26,6 +26,7 @@ import math
 import numpy as np
 
 from . import capi, grshim, probe, txgen
+from . import irs as irs_mod
 
 LS, LMS, COMB, STA = 0, 1, 2, 3
 _C64 = np.dtype(np.complex64)
@@ -616,14 +617,27 @@ class channel_model(grshim.sync_block):
     rule 19 (wifirx_channel_fading): every tap is multiplied by a time-varying gain of mean power 1, Rician on tap 0 with
     ``k_factor`` > 0, drawn from ``fade_seed``; at most 16 taps then.  The gains are functions of the stream index (the call's
     ``time0``), carried across ``work()`` calls like the phase, so the output does not depend on the cut here either.
-    ``doppler=0`` is not "off": it is one static random gain per tap."""
+    ``doppler=0`` is not "off": it is one static random gain per tap.
+
+    ``irs`` (an ``irs.IrsConfig``; None = the block as it is without it) takes the taps from a reflecting surface instead
+    (wifirx_irs_taps, NUMERICS.md rule 25): output sample n of the stream runs through tap set ``n // irs.refresh`` of the
+    configuration's draws, made on the device and handed to wifirx_channel there.  ``taps`` must then stay at its default and
+    ``doppler`` at None; ``set_psi`` loads another phase configuration, which holds from the next ``work()`` on."""
 
     MAX_TAPS = 64
 
     def __init__(self, noise_voltage=1.0, frequency_offset=0.0, epsilon=1.0, taps=(1.0,), noise_seed=0, block_tags=False,
-                 device=0, doppler=None, k_factor=0.0, fade_seed=0):
+                 device=0, doppler=None, k_factor=0.0, fade_seed=0, irs=None):
         grshim.sync_block.__init__(self, name="channel_model", in_sig=[np.complex64], out_sig=[np.complex64])
         self._doppler = None
+        self._irs = None
+        if irs is not None:
+            if not isinstance(irs, irs_mod.IrsConfig):
+                raise TypeError("irs must be an irs.IrsConfig")
+            if doppler is not None or np.asarray(taps).size != 1 or complex(np.asarray(taps).reshape(-1)[0]) != 1.0:
+                raise ValueError("with irs the taps are the surface's: leave taps and doppler at their defaults")
+        self._irs_sets = None                                    # device buffer of the surface's tap sets 0 .. _irs_n - 1
+        self._irs_n = 0
         self.set_k_factor(k_factor)
         self.fade_seed = int(fade_seed) & 0xFFFFFFFFFFFFFFFF
         self.set_timing_offset(epsilon)
@@ -637,6 +651,58 @@ class channel_model(grshim.sync_block):
         self._hist = np.zeros(0, dtype=np.complex64)             # the last (up to MAX_TAPS - 1) input samples
         self._pos = 0                                            # stream index of the next input sample
         self._phase = 0                                          # phase of the next input sample, 2^-64 turns
+        self._irs = irs
+
+    # ---- the reflecting surface ----
+    def set_psi(self, psi):
+        """another phase configuration of the surface ([N] complex), from the next work() on"""
+        if self._irs is None or self._irs.align_bits:
+            raise ValueError("set_psi needs irs with given phases (align_bits = 0)")
+        self._irs.set_psi(psi)
+        self._irs_n = 0                                          # the sets are made again when they are next needed
+
+    def _irs_set(self, s):
+        """device pointer of the surface's tap set s: the sets 0 .. s are made in one wifirx_irs_taps call (set r depends on r
+        alone), twice as many each time the stream outgrows them"""
+        c = self._irs
+        if s >= self._irs_n:
+            n = max(16, 2 * (s + 1))
+            if self._irs_sets is not None:
+                self._irs_sets.free()
+            self._irs_sets = self._rx.alloc(n * c.pdp.size * 8)
+            self._rx.irs_taps_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, gain=c.gain, k_factor=c.k_factor,
+                                  direct_gain=c.direct_gain, psi=c.psi if c.align_bits == 0 else None,
+                                  align_bits=c.align_bits, seed=c.seed)
+            self._irs_n = n
+        return self._irs_sets.ptr + 8 * c.pdp.size * s
+
+    def _irs_work(self, x, out, n):
+        """work() with the surface's taps: the chunk is cut where the set index changes, every piece one wifirx_channel call
+        on device taps with the L - 1 samples before it in front"""
+        c, L, rx = self._irs, self._irs.pdp.size, self._rx
+        cfo = np.float32(2.0 * math.pi * self._frequency_offset)
+        inc, m64 = capi.phase_inc(cfo), 0xFFFFFFFFFFFFFFFF
+        at = 0
+        while at < n:
+            s = self._pos // c.refresh
+            m = min(n - at, (s + 1) * c.refresh - self._pos)
+            h = min(L - 1, self._hist.size)
+            row = np.ascontiguousarray(np.concatenate([self._hist[self._hist.size - h:], x[at:at + m]]) if h else x[at:at + m])
+            d_in, d_out = rx.alloc(row.size * 8).upload(row), rx.alloc(row.size * 8)
+            try:
+                rx.channel_dev(d_in.ptr, d_out.ptr, row.size, 1, row_len=row.size, taps=self._irs_set(s), n_taps=L, n_tap_sets=1,
+                               cfo=cfo, phase0=(self._phase - inc * h) & m64, gain=1.0, noise_voltage=self._noise_voltage,
+                               seed=self.noise_seed, sample0=self._pos - h)
+                out[at:at + m] = d_out.download(np.complex64, row.size)[h:]
+            finally:
+                d_in.free()
+                d_out.free()
+            keep = self.MAX_TAPS - 1
+            self._hist = np.concatenate([self._hist, x[at:at + m]])[-keep:]
+            self._pos += m
+            self._phase = (self._phase + inc * m) & m64
+            at += m
+        return n
 
     # ---- GNU Radio's setters and getters ----
     def set_noise_voltage(self, noise_voltage):
@@ -707,6 +773,8 @@ class channel_model(grshim.sync_block):
         if n == 0:
             return 0
         x = np.asarray(x[:n], dtype=np.complex64)
+        if self._irs is not None:
+            return self._irs_work(x, out, n)
         L = self._taps.size
         h = min(L - 1, self._hist.size)
         row = np.concatenate([self._hist[self._hist.size - h:], x]) if h else x
@@ -727,6 +795,9 @@ class channel_model(grshim.sync_block):
 
     def close(self):
         """Release the library handle."""
+        if self._irs_sets is not None:
+            self._irs_sets.free()
+            self._irs_sets = None
         self._rx.close()
 
 

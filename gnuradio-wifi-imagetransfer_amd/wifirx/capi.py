@@ -49,7 +49,7 @@ EXPORTS = [
     "wifirx_channel_sro", "wifirx_resampler_table", "wifirx_channel_fading",
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
     "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine", "wifirx_diversity_combine",
-    "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi",
+    "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi", "wifirx_irs_taps",
 ]
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
@@ -101,6 +101,7 @@ def locked_sro(cfo, bandwidth=20e6, frequency=5.89e9):
 
 DOPPLER_MAX = 2.0 ** -10            # the largest doppler (cycles per sample) wifirx_channel_fading takes
 FADE_MAX_TAPS = 16                  # the most taps with fading
+IRS_MAX_ELEMS, IRS_MAX_TAPS = 4096, 16      # wifirx_irs_taps: the most surface elements and taps (NUMERICS.md rule 25)
 
 
 def resampler_table() -> np.ndarray:
@@ -223,6 +224,9 @@ _lib.wifirx_channel_sro.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint
                                     C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64,
                                     C.c_float, C.c_float, C.c_uint64, C.c_uint64]
 _lib.wifirx_channel_fading.argtypes = _lib.wifirx_channel_sro.argtypes + [C.c_void_p, C.c_float, C.c_uint64, C.c_uint64]
+_lib.wifirx_irs_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32,
+                                 C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
 _lib.wifirx_resampler_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                   C.c_uint64, C.c_void_p, C.c_uint32]
@@ -654,6 +658,71 @@ class WifiRx:
             d_in.free()
             d_out.free()
         return y.reshape(x.shape)
+
+    # -- reflecting surface (wifirx_irs_taps; NUMERICS.md rule 25) --
+    def irs_taps_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, gain=1.0, k_factor=0.0, direct_gain=1.0,
+                     psi=None, n_psi_sets=None, align_bits=0, scatter=None, n_scatter=None, seed=0, elems_ptr=None,
+                     codes_ptr=None):
+        """wifirx_irs_taps into device memory: n_sets sets of len(pdp) complex64 taps at taps_ptr (an int device pointer or a
+        DevBuf, as every *_ptr here), what channel_dev takes as taps=ptr, n_taps=len(pdp), n_tap_sets=n_sets.  los_b2r, los_r2u:
+        the N line-of-sight coefficients of the two legs, los_b2u the direct path's (irs.los gives all three).  psi: a host
+        array [N] or [n_psi_sets, N], or a device pointer (then n_psi_sets says its rows); align_bits = 1..3 aligns the phases
+        per draw instead and psi is not read.  scatter: None = Philox draws keyed by `seed`, or a device pointer to n_scatter
+        rows of 2 N + 1 complex64.  elems_ptr / codes_ptr: optional device outputs [n_sets, L, 2, N] complex64 / [n_sets, N]
+        uint8.  Asynchronous on the handle's stream."""
+        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
+        c64 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.complex64).reshape(-1))
+        p = np.ascontiguousarray(np.asarray(pdp, dtype=np.float32).reshape(-1))
+        a, b = c64(los_b2r), c64(los_r2u)
+        if a.size != b.size:
+            raise ValueError("los_b2r and los_r2u must have one length, the number of elements")
+        d = None if los_b2u is None else c64(los_b2u)
+        if d is not None and d.size != 1:
+            raise ValueError("los_b2u is one complex value")
+        keep, psi_ptr, psi_dev, n_psi = None, None, 0, 0
+        if isinstance(psi, (int, DevBuf)):
+            psi_ptr, psi_dev, n_psi = ptr(psi), 1, int(n_psi_sets or 1)
+        elif psi is not None:
+            keep = np.asarray(psi, dtype=np.complex64)
+            keep = np.ascontiguousarray(keep[None] if keep.ndim == 1 else keep)
+            if keep.ndim != 2 or keep.shape[1] != a.size:
+                raise ValueError("psi must be [N] or [n_psi_sets, N]")
+            psi_ptr, n_psi = _np_ptr(keep), keep.shape[0]
+        if scatter is not None and n_scatter is None:
+            raise ValueError("device scatter needs n_scatter")
+        self._check(_lib.wifirx_irs_taps(self._h, ptr(taps_ptr), int(n_sets), p.size, _np_ptr(p), float(gain), a.size, _np_ptr(a),
+                                         _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain), psi_ptr, psi_dev, n_psi,
+                                         int(align_bits), ptr(scatter), int(n_scatter or 0), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                         ptr(elems_ptr), ptr(codes_ptr)))
+
+    def irs_taps(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, scatter=None, want_elems=False, want_codes=False, **kw):
+        """irs_taps_dev with host arrays: returns the taps as complex64 [n_sets, L], or a dict with them under "taps" and the
+        elements [n_sets, L, 2, N] under "elems" / the codes [n_sets, N] under "codes" when asked for.  scatter: None or a host
+        array [n_scatter, 2 N + 1].  psi and the other keywords as irs_taps_dev."""
+        n_sets, L, N = int(n_sets), np.asarray(pdp).size, np.asarray(los_b2r).size
+        bufs = {"taps": self.alloc(max(n_sets * L, 1) * 8)}
+        try:
+            if scatter is not None:
+                s = np.ascontiguousarray(scatter, dtype=np.complex64)
+                if s.ndim != 2 or s.shape[1] != 2 * N + 1:
+                    raise ValueError("scatter must be [n_scatter, 2 N + 1]")
+                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
+                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
+            if want_elems:
+                bufs["elems"] = self.alloc(max(n_sets * L * 2 * N, 1) * 8)
+            if want_codes:
+                bufs["codes"] = self.alloc(max(n_sets * N, 1))
+            self.irs_taps_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, elems_ptr=bufs.get("elems"),
+                              codes_ptr=bufs.get("codes"), **kw)
+            out = {"taps": bufs["taps"].download(np.complex64, n_sets * L).reshape(n_sets, L)}
+            if want_elems:
+                out["elems"] = bufs["elems"].download(np.complex64, n_sets * L * 2 * N).reshape(n_sets, L, 2, N)
+            if want_codes:
+                out["codes"] = bufs["codes"].download(np.uint8, n_sets * N).reshape(n_sets, N)
+        finally:
+            for b in bufs.values():
+                b.free()
+        return out if (want_elems or want_codes) else out["taps"]
 
     # -- the ends of the loop-back (wifirx_mac_batch, wifirx_link_stats) --
     def mac_batch_dev(self, psdu_ptr, psdu_stride, n_frames, payload=None, payload_len=None, seq0=0, addr=None,

@@ -468,6 +468,48 @@ int  wifirx_channel_fading(wifirx_handle* h, const float* in, float* out, uint64
  * the library.  Needs no handle and no device; any argument may be NULL.  Returns WIFIRX_OK. */
 int  wifirx_resampler_table(const float** taps, uint32_t* n_phases, uint32_t* n_taps);
 
+/* The tap sets of a link that runs over an intelligent reflecting surface, made on the device: the cascade model of the
+ * reference's utils/SV_channel.py and utils/channel.py (Channel.getChnl: H = H_B2R diag(psi) H_R2U + H_B2U) for one AP antenna,
+ * one user and N = n_elems surface elements; arithmetic = NUMERICS.md rule 25.  Tap l (0 <= l < L = n_taps) of set r:
+ *     a_n      = a_los A_n + a_nlos w_a(n,r,l)        b_n = a_los B_n + a_nlos w_b(n,r,l)          0 <= n < N
+ *     h_d      = direct_gain (a_los D + a_nlos w_d(r,l))
+ *     t_{r,l}  = s_l (h_d + sum_n a_n psi_n b_n)      s_l = (float)(sqrt(pdp_l) gain)
+ * with a_los = sqrt(K / (K+1)), a_nlos = sqrt(1 / (K+1)), K = k_factor (0 = Rayleigh: a_n = w_a, b_n = w_b, h_d = direct_gain
+ * w_d), and w complex Gaussians of variance 1.  The sum runs in the order of a 64-wide wave: lane i adds its elements n = i,
+ * i + 64, ... in ascending n, and the 64 partial sums are folded by a butterfly over lane xor 32, 16, 8, 4, 2, 1.
+ *   taps_out     DEVICE complex64 [n_sets][n_taps] (8-byte aligned): the layout wifirx_channel* reads with taps_on_device = 1,
+ *                n_tap_sets = n_sets.
+ *   pdp, gain    HOST float32 [n_taps], each >= 0: the power delay profile; gain scales every tap.
+ *   los_b2r, los_r2u, los_b2u   HOST complex64 [N], [N], [1]: the line-of-sight vectors A, B and the scalar D (Python:
+ *                wifirx.irs.los, the steering vectors of genLoS).  Not looked at when k_factor = 0; los_b2u may be NULL when
+ *                direct_gain = 0.
+ *   direct_gain  scales the direct path; 0 is a blocked direct path (h_d = +0, nothing of it is drawn or read).
+ *   psi          align_bits = 0: complex64 [n_psi_sets][N], HOST or (psi_on_device) DEVICE; set r uses row r % n_psi_sets.  Any
+ *                complex value is taken, an amplitude below 1 is a lossy element.  Not looked at when align_bits > 0.
+ *   align_bits   B in {1, 2, 3}: the genie bound of a B-bit surface.  The codes are decided on tap 0 of every set and applied
+ *                to all its taps: with e_n = a_{0,n} b_{0,n}, code c_n = the c in 0 .. 2^B - 1 that maximises
+ *                Re(conj(h_{d,0}) e_n C_c), C_c = exp(j 2 pi c / 2^B) from a float32 table, the lowest c at a tie; with
+ *                h_{d,0} = 0 the surface aligns to the positive real axis (conj(h_d) -> 1).  psi_n = C_{c_n}.
+ *   scatter      NULL: the w are Philox4x32-10 draws keyed by irs_seed on the counter (n, r, l, 2) -- (x, y) -> w_a, (z, w) ->
+ *                w_b by wifirx_channel's Box-Muller with h = sqrt(1/2); w_d from (x, y) of the counter (0xFFFFFFFF, r, l, 2).
+ *                Word 3 keeps them apart from the noise (0) and the fader (1), so one value may serve as every seed.
+ *                Else DEVICE complex64 [n_scatter][2 N + 1], each row w_a[N], w_b[N], w_d; the pair (r, l) reads row
+ *                (r L + l) % n_scatter and nothing is drawn.
+ *   elems_out    DEVICE complex64 [n_sets][n_taps][2][N] or NULL: the realised a_n, b_n (the surface's CSI).
+ *   codes_out    DEVICE uint8 [n_sets][N] or NULL: the codes of the aligned mode.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for a NULL taps_out / pdp / los_b2r / los_r2u, a NULL los_b2u
+ * with direct_gain != 0, a NULL psi or n_psi_sets = 0 with align_bits = 0, n_scatter = 0 with scatter, n_elems outside 1..4096,
+ * n_taps outside 1..16, align_bits > 3, codes_out with align_bits = 0, a k_factor that is not finite or negative, a pdp entry
+ * that is not finite or negative, a non-finite gain / direct_gain, and misaligned pointers (device complex64: 8 bytes, host
+ * float32: 4); WIFIRX_ERANGE for more than 2^31 - 1 sets.  n_sets = 0 does nothing and returns WIFIRX_OK.  One kernel launch
+ * per call, after one upload of the host arrays (the line-of-sight vectors, the scales, host psi).  ORDER: as wifirx_channel. */
+int  wifirx_irs_taps(wifirx_handle* h, float* taps_out, uint32_t n_sets, uint32_t n_taps, const float* pdp, float gain,
+                     uint32_t n_elems, const float* los_b2r, const float* los_r2u, const float* los_b2u,
+                     float k_factor, float direct_gain,
+                     const float* psi, int psi_on_device, uint32_t n_psi_sets, uint32_t align_bits,
+                     const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
+                     float* elems_out, uint8_t* codes_out);
+
 /* ieee802_11.mac (gnu_radio/IRS_user.py:192,204-205; IRS_tranceiver.py:271,313-314) for a batch: PSDU i, at
  * psdu + i * psdu_stride, is the 24 + payload_len[i] + 4 bytes
  *     08 00 | 00 00 | addr1 = dst | addr2 = src | addr3 = bss | ((seq0 + i) & 0xFFF) << 4, little endian | payload i | FCS

@@ -58,7 +58,14 @@ carrier offset --, then one demod per antenna, wifirx_diversity_combine (NUMERIC
 decode_mac hard and soft, and wifirx_link_stats.  Per SNR: the FER of every antenna count given (1 = antenna 0 alone, without
 the combiner) and mode.  The counts nest: A antennas are the first A of the largest count, so the columns share their channels.
 
-    python tools/loopback_per.py --antennas 1 2 4 --diversity mrc select --psdu-len 294 --encoding 2 --snr 5 10 15 20 25 [--frames 65536] [--out profiles/loopback_diversity.json]"""
+    python tools/loopback_per.py --antennas 1 2 4 --diversity mrc select --psdu-len 294 --encoding 2 --snr 5 10 15 20 25 [--frames 65536] [--out profiles/loopback_diversity.json]
+
+--irs: the link over a reflecting surface of N elements with B-bit phases (wifirx_irs_taps, NUMERICS.md rule 25): one tap set of 8
+taps per frame, made on the device and read there by wifirx_channel; FER against the surface size at SNRs of one unit-power path.
+--irs-mode: random phases, the one configuration aligned to the geometry, the genie aligned per draw.  --irs 0 is the direct
+path alone.
+
+    python tools/loopback_per.py --irs 0 16 64 256 --irs-bits 2 --irs-mode random los genie --k-factor 3 --direct-db -inf --psdu-len 294 --encoding 2 --snr -20 -10 0 [--frames 65536] [--out profiles/loopback_irs.json]"""
 import argparse
 import json
 import math
@@ -130,8 +137,15 @@ def main():
     ap.add_argument("--antennas", type=int, nargs="+", default=None, help="receive diversity: these antenna counts, 1 .. 8")
     ap.add_argument("--diversity", nargs="+", choices=sorted(capi.DIV_MODES, key=capi.DIV_MODES.get), default=None,
                     help="with --antennas: the combiner's modes (default both)")
+    ap.add_argument("--irs", type=int, nargs="+", default=None, help="a reflecting surface of these many elements (squares; 0 = the direct path alone)")
+    ap.add_argument("--irs-bits", type=int, default=2, choices=(1, 2, 3), help="with --irs: the phase resolution")
+    ap.add_argument("--irs-mode", nargs="+", choices=("random", "los", "genie"), default=["genie"],
+                    help="with --irs: random phases, the one configuration aligned to the geometry, or aligned per draw")
+    ap.add_argument("--direct-db", type=float, default=float("-inf"), help="with --irs: gain of the direct path in dB (-inf: blocked)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.irs is not None:
+        return irs_main(a)
     if a.antennas is not None:
         return diversity_main(a)
     if a.wideband is not None:
@@ -500,6 +514,83 @@ def fading_main(a):
                        % (n, enc, plen, n_sym, slot, "sv_taps.npy sets cycling, every tap fading" if a.multipath else "flat channel",
                           a.k_factor),
            "doppler_unit": "cycles per sample (1e-4 = 1 kHz at 10 MS/s)", "equalisers": eqs,
+           "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def irs_main(a):
+    if a.rates or a.host_stats or a.locked_clock or a.doppler is not None:
+        raise SystemExit("--irs stands alone: not with --rates, --host-stats, --locked-clock or --doppler")
+    from wifirx import irs
+    n = a.frames or 65536
+    plen, enc, bits = a.psdu_len, a.encoding, a.irs_bits
+    if not (28 <= plen <= 1528 and 0 <= enc <= 7):
+        raise SystemExit("--psdu-len 28 .. 1528, --encoding 0 .. 7")
+    for N in a.irs:
+        if N < 0 or N > capi.IRS_MAX_ELEMS or int(round(N ** 0.5)) ** 2 != N:
+            raise SystemExit("--irs takes square surfaces of 0 .. 4096 elements")
+    direct_gain = 0.0 if a.direct_db == float("-inf") else 10 ** (a.direct_db / 20)
+    n_sym = txgen.n_sym_for(plen, enc)
+    slot = LEAD + txgen.frame_samples(plen, enc) + 79
+    slot += slot & 1
+    stride = (plen + 15) // 16 * 16
+    L = 8
+    pdp = np.exp(-np.arange(L) / 2.0)
+    pdp = (pdp / pdp.sum()).astype(np.float32)
+    rx = capi.WifiRx(max_sym=n_sym, llr_bits=0, chan_est=capi.EQ_LS, device=0)
+    t_all = time.perf_counter()
+    d_psdu, rows, iq, d_taps = rx.alloc(n * plen), rx.alloc(n * slot * 8), rx.alloc(n * slot * 8), rx.alloc(n * L * 8)
+    rx.mac_batch_dev(d_psdu.ptr, plen, n, None, payload_len=plen - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, n * slot, d_psdu.ptr, enc, psdu_len=np.full(n, plen, np.uint32), psdu_stride=plen, lead=LEAD,
+                    row_len=slot)
+    dev = rx.alloc_out(n, psdu_stride=stride, want_hbits=True)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * n_sym * 48), hbits=rx.alloc(n * n_sym * 48),
+               psdu=d_psdu, psdu_stride=plen)
+    rx.demod_batch_dev(rows.ptr, slot, n, ref)
+    assert rx.link_stats(n, ref, ref)["frames_ref"] == n, "a clean frame was not demodulated"
+    points = []
+    for N in a.irs:
+        # the surface in front of the AP as in the reference's scenes; --irs 0: one element that reflects nothing
+        S = max(1, int(round(N ** 0.5)))
+        b2r, r2u, b2u = irs.los(S, [0.015, 0.015, 0], [S * 0.015, S * 0.015, 4.5], [S * 0.015 + 0.3, S * 0.015 - 0.2, 1.0])
+        for mode in (a.irs_mode if N else ["none"]):
+            kw = dict(k_factor=a.k_factor, direct_gain=direct_gain if N else (direct_gain or 1.0), seed=(a.seed << 32) + N)
+            if mode == "genie":
+                kw["align_bits"] = bits
+            elif mode == "los":
+                kw["psi"] = irs.align(b2r, r2u, b2u if direct_gain else 0.0, bits)[1]
+            elif mode == "random":
+                kw["psi"] = irs.random_psi(N, bits, a.seed)
+            else:
+                kw["psi"] = np.zeros(1, np.complex64)
+            # one tap set per frame, made on the device and read there by the channel
+            rx.irs_taps_dev(d_taps, n, pdp, b2r, r2u, b2u, **kw)
+            mean_power = float((np.abs(d_taps.download(np.complex64, min(n, 65536) * L).astype(np.complex128)) ** 2).sum() / min(n, 65536))
+            for snr in a.snr:
+                t0 = time.perf_counter()
+                rx.channel_dev(rows.ptr, iq.ptr, n * slot, n, row_len=slot, taps=d_taps.ptr, n_taps=L, n_tap_sets=n,
+                               gain=math.sqrt(10 ** (snr / 10)), noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32))
+                rx.demod_batch_dev(iq.ptr, slot, n, dev)
+                rx.decode_batch_dev(n, dev)
+                r = rx.link_stats(n, dev, ref)
+                points.append({"n_elems": N, "mode": mode, "snr_db": snr, "frames": n, "fer": r["fer"], "coded_ber": r["coded_ber"],
+                               "mean_channel_power": mean_power, "seconds": time.perf_counter() - t0,
+                               "counts": {k: r[k] for k in COUNTERS}})
+                print(json.dumps({k: points[-1][k] for k in ("n_elems", "mode", "snr_db", "fer", "mean_channel_power")}), file=sys.stderr)
+    seconds_total = time.perf_counter() - t_all
+    rx.free_out(ref)
+    rx.free_out(dev)
+    rows.free(); iq.free(); d_taps.free(); rx.close()
+    res = {"workload": "loop-back on the device over a reflecting surface (wifirx_irs_taps -> wifirx_channel, tap sets never leave the "
+                       "device): %d distinct frames per point, one tap set per frame, encoding %d, PSDU %d B (%d symbols), rows of %d, "
+                       "lead 160, 8 taps (pdp exp(-l/2), sum 1), k_factor %g, direct path %s, %d-bit phases, LS, hard decode_mac"
+                       % (n, enc, plen, n_sym, slot, a.k_factor, "blocked" if direct_gain == 0 else "%g dB" % a.direct_db, bits),
+           "snr": "of one unit-power path (an element's leg, or the unattenuated direct path); n_elems 0 is the direct path alone at 0 dB",
+           "modes": {"random": "one random configuration", "los": "the one configuration aligned to the geometry (irs.align)",
+                     "genie": "aligned per draw on tap 0 (align_bits)"},
            "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
