@@ -82,3 +82,82 @@ extern "C" int wifirx_irs_taps(wifirx_handle* h, float* taps_out, uint32_t n_set
     HIP_TRY(h, wr_launch_irs(h->stream, &a));
     return WIFIRX_OK;
 }
+
+// beam training over a codebook: the same scene, K configurations, the best one per set (wr_irs_sweep.hip, NUMERICS.md rule 26)
+extern "C" int wifirx_irs_sweep(wifirx_handle* h, float* taps_out, uint32_t n_sets, uint32_t n_taps, const float* pdp, float gain,
+                                uint32_t n_elems, const float* los_b2r, const float* los_r2u, const float* los_b2u,
+                                float k_factor, float direct_gain,
+                                const float* codebook, int codebook_on_device, uint32_t n_codes,
+                                const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
+                                uint16_t* best_out, float* power_out)
+{
+    if (!h) return WIFIRX_EINVAL;
+    // ---- the argument checks, before anything is queued ----
+    if (!pdp || !los_b2r || !los_r2u || !codebook) return fail(h, WIFIRX_EINVAL, "pdp, los_b2r, los_r2u and codebook are required");
+    if (!taps_out && !best_out && !power_out) return fail(h, WIFIRX_EINVAL, "one of taps_out, best_out and power_out is required");
+    if (n_elems < 1 || n_elems > wr_irs_max_elems()) return fail(h, WIFIRX_EINVAL, "n_elems must be 1..4096");
+    if (n_taps < 1 || n_taps > wr_irs_max_taps()) return fail(h, WIFIRX_EINVAL, "n_taps must be 1..16");
+    if (n_codes < 1 || n_codes > wr_irs_max_codes()) return fail(h, WIFIRX_EINVAL, "n_codes must be 1..1024");
+    if (!std::isfinite(gain) || !std::isfinite(direct_gain)) return fail(h, WIFIRX_EINVAL, "gain and direct_gain must be finite");
+    if (!(std::isfinite(k_factor) && k_factor >= 0.0f)) return fail(h, WIFIRX_EINVAL, "k_factor must be finite and not negative");
+    if (direct_gain != 0.0f && !los_b2u) return fail(h, WIFIRX_EINVAL, "los_b2u is required with a direct path");
+    if (scatter && n_scatter == 0) return fail(h, WIFIRX_EINVAL, "n_scatter must be >= 1 with scatter");
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((addr(taps_out) | addr(scatter) | (codebook_on_device ? addr(codebook) : 0)) & 7)
+        return fail(h, WIFIRX_EINVAL, "taps_out, scatter and a device codebook must be 8-byte aligned (complex64)");
+    if ((addr(pdp) | addr(los_b2r) | addr(los_r2u) | addr(los_b2u) | addr(power_out) | (codebook_on_device ? 0 : addr(codebook))) & 3)
+        return fail(h, WIFIRX_EINVAL, "the host arrays and power_out must be 4-byte aligned (float32)");
+    if (addr(best_out) & 1) return fail(h, WIFIRX_EINVAL, "best_out must be 2-byte aligned (uint16)");
+    for (uint32_t l = 0; l < n_taps; l++)
+        if (!(std::isfinite(pdp[l]) && pdp[l] >= 0.0f)) return fail(h, WIFIRX_EINVAL, "pdp must be finite and not negative");
+    if (n_sets == 0) return WIFIRX_OK;
+    if (n_sets > 0x7fffffffu) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 tap sets");
+
+    stream_worker_wait_idle(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    wr::IrsSweepArgs a{};
+    // one upload of what the host holds, as wifirx_irs_taps does it
+    std::vector<uint8_t> meta;
+    std::vector<std::pair<void*, size_t>> named;
+    auto add = [&](void* dev_ptr, const void* host, size_t bytes) {
+        const size_t off = (meta.size() + 7) & ~(size_t)7;
+        meta.resize(off + bytes);
+        std::memcpy(meta.data() + off, host, bytes);
+        named.emplace_back(dev_ptr, off);
+    };
+    std::vector<float> scale(n_taps);                  // s_l = (float)(sqrt(pdp_l) gain), formed in double
+    for (uint32_t l = 0; l < n_taps; l++) scale[l] = (float)(std::sqrt((double)pdp[l]) * (double)gain);
+    add(&a.s.los_a, los_b2r, 8ull * n_elems);
+    add(&a.s.los_b, los_r2u, 8ull * n_elems);
+    add(&a.s.scale, scale.data(), 4ull * n_taps);
+    a.codebook = reinterpret_cast<const float2*>(codebook);
+    if (!codebook_on_device) add(&a.codebook, codebook, 8ull * n_codes * n_elems);
+    int rc;
+    if ((rc = h->stage.irs_meta.reserve(h, meta.size()))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->stage.irs_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, h->stream));
+    // the host arrays (the caller's and `meta`) may go once this returns: wait for the copy, not for the kernel
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (const auto& n : named) {
+        const uint8_t* dev = h->stage.irs_meta.as<uint8_t>() + n.second;
+        std::memcpy(n.first, &dev, sizeof dev);
+    }
+    a.s.taps_out = reinterpret_cast<float2*>(taps_out);
+    a.s.scatter = reinterpret_cast<const float2*>(scatter);
+    if (direct_gain != 0.0f) a.s.los_d = make_float2(los_b2u[0], los_b2u[1]);
+    a.s.seed = irs_seed;
+    a.s.n_sets = n_sets;
+    a.s.n_taps = n_taps;
+    a.s.n_elems = n_elems;
+    a.s.n_psi_sets = 1;
+    a.s.n_scatter = scatter ? n_scatter : 1;
+    if (k_factor > 0.0f) {                              // formed in double; k_factor = 0: neither is applied (a_los = 0 says so)
+        a.s.a_los = (float)std::sqrt((double)k_factor / ((double)k_factor + 1.0));
+        a.s.a_nlos = (float)std::sqrt(1.0 / ((double)k_factor + 1.0));
+    }
+    a.s.direct_gain = direct_gain;
+    a.best_out = best_out;
+    a.power_out = power_out;
+    a.n_codes = n_codes;
+    HIP_TRY(h, wr_launch_irs_sweep(h->stream, &a));
+    return WIFIRX_OK;
+}

@@ -622,7 +622,9 @@ class channel_model(grshim.sync_block):
     ``irs`` (an ``irs.IrsConfig``; None = the block as it is without it) takes the taps from a reflecting surface instead
     (wifirx_irs_taps, NUMERICS.md rule 25): output sample n of the stream runs through tap set ``n // irs.refresh`` of the
     configuration's draws, made on the device and handed to wifirx_channel there.  ``taps`` must then stay at its default and
-    ``doppler`` at None; ``set_psi`` loads another phase configuration, which holds from the next ``work()`` on."""
+    ``doppler`` at None; ``set_psi`` loads another phase configuration, which holds from the next ``work()`` on.  With
+    ``IrsConfig(codebook=...)`` every tap set is the winner of a beam-training sweep over the codebook (wifirx_irs_sweep,
+    NUMERICS.md rule 26), and ``irs_best`` holds the winning entries of the sets drawn so far."""
 
     MAX_TAPS = 64
 
@@ -638,6 +640,7 @@ class channel_model(grshim.sync_block):
                 raise ValueError("with irs the taps are the surface's: leave taps and doppler at their defaults")
         self._irs_sets = None                                    # device buffer of the surface's tap sets 0 .. _irs_n - 1
         self._irs_n = 0
+        self._irs_best = None                                    # device buffer of the winning entries (codebook mode)
         self.set_k_factor(k_factor)
         self.fade_seed = int(fade_seed) & 0xFFFFFFFFFFFFFFFF
         self.set_timing_offset(epsilon)
@@ -656,8 +659,8 @@ class channel_model(grshim.sync_block):
     # ---- the reflecting surface ----
     def set_psi(self, psi):
         """another phase configuration of the surface ([N] complex), from the next work() on"""
-        if self._irs is None or self._irs.align_bits:
-            raise ValueError("set_psi needs irs with given phases (align_bits = 0)")
+        if self._irs is None or self._irs.align_bits or self._irs.codebook is not None:
+            raise ValueError("set_psi needs irs with given phases (align_bits = 0, no codebook)")
         self._irs.set_psi(psi)
         self._irs_n = 0                                          # the sets are made again when they are next needed
 
@@ -670,11 +673,28 @@ class channel_model(grshim.sync_block):
             if self._irs_sets is not None:
                 self._irs_sets.free()
             self._irs_sets = self._rx.alloc(n * c.pdp.size * 8)
+            if c.codebook is not None:
+                if self._irs_best is not None:
+                    self._irs_best.free()
+                self._irs_best = self._rx.alloc(n * 2)
+                self._rx.irs_sweep_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, codebook=c.codebook, gain=c.gain,
+                                       k_factor=c.k_factor, direct_gain=c.direct_gain, seed=c.seed, best_ptr=self._irs_best)
+                self._irs_n = n
+                return self._irs_sets.ptr + 8 * c.pdp.size * s
             self._rx.irs_taps_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, gain=c.gain, k_factor=c.k_factor,
                                   direct_gain=c.direct_gain, psi=c.psi if c.align_bits == 0 else None,
                                   align_bits=c.align_bits, seed=c.seed)
             self._irs_n = n
         return self._irs_sets.ptr + 8 * c.pdp.size * s
+
+    @property
+    def irs_best(self):
+        """codebook mode: the winning entries of the tap sets drawn so far (uint16; set s is entry s)"""
+        if self._irs is None or self._irs.codebook is None:
+            raise ValueError("irs_best needs irs with a codebook")
+        if self._irs_n == 0:
+            return np.zeros(0, np.uint16)
+        return self._irs_best.download(np.uint16, self._irs_n)
 
     def _irs_work(self, x, out, n):
         """work() with the surface's taps: the chunk is cut where the set index changes, every piece one wifirx_channel call
@@ -798,6 +818,9 @@ class channel_model(grshim.sync_block):
         if self._irs_sets is not None:
             self._irs_sets.free()
             self._irs_sets = None
+        if self._irs_best is not None:
+            self._irs_best.free()
+            self._irs_best = None
         self._rx.close()
 
 

@@ -49,7 +49,7 @@ EXPORTS = [
     "wifirx_channel_sro", "wifirx_resampler_table", "wifirx_channel_fading",
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
     "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine", "wifirx_diversity_combine",
-    "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi", "wifirx_irs_taps",
+    "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi", "wifirx_irs_taps", "wifirx_irs_sweep",
 ]
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
@@ -102,6 +102,7 @@ def locked_sro(cfo, bandwidth=20e6, frequency=5.89e9):
 DOPPLER_MAX = 2.0 ** -10            # the largest doppler (cycles per sample) wifirx_channel_fading takes
 FADE_MAX_TAPS = 16                  # the most taps with fading
 IRS_MAX_ELEMS, IRS_MAX_TAPS = 4096, 16      # wifirx_irs_taps: the most surface elements and taps (NUMERICS.md rule 25)
+IRS_MAX_CODES = 1024                        # wifirx_irs_sweep: the most codebook entries (NUMERICS.md rule 26)
 
 
 def resampler_table() -> np.ndarray:
@@ -227,6 +228,9 @@ _lib.wifirx_channel_fading.argtypes = _lib.wifirx_channel_sro.argtypes + [C.c_vo
 _lib.wifirx_irs_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32,
                                  C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+_lib.wifirx_irs_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_uint32,
+                                  C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
 _lib.wifirx_resampler_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                   C.c_uint64, C.c_void_p, C.c_uint32]
@@ -723,6 +727,62 @@ class WifiRx:
             for b in bufs.values():
                 b.free()
         return out if (want_elems or want_codes) else out["taps"]
+
+    # -- beam training of the surface (wifirx_irs_sweep; NUMERICS.md rule 26) --
+    def irs_sweep_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, codebook, n_codes=None, gain=1.0,
+                      k_factor=0.0, direct_gain=1.0, scatter=None, n_scatter=None, seed=0, best_ptr=None, power_ptr=None):
+        """wifirx_irs_sweep into device memory: for each of n_sets tap sets the elements of irs_taps_dev (the same seed gives
+        the same elements) run against every entry of `codebook`; the winner's len(pdp) taps go to taps_ptr (what channel_dev
+        takes as taps=ptr), the winning entry to best_ptr (uint16 [n_sets]) and every entry's power to power_ptr (float32
+        [n_sets, K]).  Each of the three is an int device pointer, a DevBuf or None; one at least is required.  codebook: a host
+        array [K, N] complex, or a device pointer (then n_codes says its rows); K <= 1024.  The other arguments as
+        irs_taps_dev.  Asynchronous on the handle's stream."""
+        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
+        c64 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.complex64).reshape(-1))
+        p = np.ascontiguousarray(np.asarray(pdp, dtype=np.float32).reshape(-1))
+        a, b = c64(los_b2r), c64(los_r2u)
+        if a.size != b.size:
+            raise ValueError("los_b2r and los_r2u must have one length, the number of elements")
+        d = None if los_b2u is None else c64(los_b2u)
+        if d is not None and d.size != 1:
+            raise ValueError("los_b2u is one complex value")
+        if isinstance(codebook, (int, DevBuf)):
+            keep, cb_ptr, cb_dev, n_cb = None, ptr(codebook), 1, int(n_codes or 0)
+        else:
+            keep = np.ascontiguousarray(np.asarray(codebook, dtype=np.complex64))
+            if keep.ndim != 2 or keep.shape[1] != a.size:
+                raise ValueError("codebook must be [K, N]")
+            cb_ptr, cb_dev, n_cb = _np_ptr(keep), 0, keep.shape[0]
+        if scatter is not None and n_scatter is None:
+            raise ValueError("device scatter needs n_scatter")
+        self._check(_lib.wifirx_irs_sweep(self._h, ptr(taps_ptr), int(n_sets), p.size, _np_ptr(p), float(gain), a.size, _np_ptr(a),
+                                          _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain), cb_ptr, cb_dev, n_cb,
+                                          ptr(scatter), int(n_scatter or 0), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          ptr(best_ptr), ptr(power_ptr)))
+
+    def irs_sweep(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, codebook, scatter=None, **kw):
+        """irs_sweep_dev with host arrays: returns {"taps": complex64 [n_sets, L], "best": uint16 [n_sets], "power": float32
+        [n_sets, K]}.  codebook: a host array [K, N] or a device pointer with n_codes=K; scatter: None or a host array
+        [n_scatter, 2 N + 1].  The other keywords as irs_sweep_dev."""
+        n_sets, L, N = int(n_sets), np.asarray(pdp).size, np.asarray(los_b2r).size
+        K = int(kw.get("n_codes") or 0) if isinstance(codebook, (int, DevBuf)) else np.asarray(codebook).shape[0]
+        bufs = {"taps": self.alloc(max(n_sets * L, 1) * 8), "best": self.alloc(max(n_sets, 1) * 2),
+                "power": self.alloc(max(n_sets * K, 1) * 4)}
+        try:
+            if scatter is not None:
+                s = np.ascontiguousarray(scatter, dtype=np.complex64)
+                if s.ndim != 2 or s.shape[1] != 2 * N + 1:
+                    raise ValueError("scatter must be [n_scatter, 2 N + 1]")
+                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
+                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
+            self.irs_sweep_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook=codebook, best_ptr=bufs["best"],
+                               power_ptr=bufs["power"], **kw)
+            return {"taps": bufs["taps"].download(np.complex64, n_sets * L).reshape(n_sets, L),
+                    "best": bufs["best"].download(np.uint16, n_sets),
+                    "power": bufs["power"].download(np.float32, n_sets * K).reshape(n_sets, K)}
+        finally:
+            for b in bufs.values():
+                b.free()
 
     # -- the ends of the loop-back (wifirx_mac_batch, wifirx_link_stats) --
     def mac_batch_dev(self, psdu_ptr, psdu_stride, n_frames, payload=None, payload_len=None, seq0=0, addr=None,

@@ -1,5 +1,6 @@
-"""The host side of the reflecting-surface channel (wifirx_irs_taps, NUMERICS.md rule 25): the line-of-sight geometry the call
-takes as input, fixed phase configurations for it, and the configuration object of ``block.channel_model(irs=...)``.
+"""The host side of the reflecting-surface channel (wifirx_irs_taps, NUMERICS.md rule 25; wifirx_irs_sweep, rule 26): the
+line-of-sight geometry the calls take as input, fixed phase configurations and beam-training codebooks for them, and the
+configuration object of ``block.channel_model(irs=...)``.
 
 The model is the reference's (utils/SV_channel.py, utils/channel.py) for one AP antenna and one user: a square surface of
 S x S elements half a wavelength apart in the x-y plane, far-field steering vectors, H = H_B2R diag(psi) H_R2U + H_B2U.
@@ -87,12 +88,71 @@ def random_psi(n, bits, seed):
     return PHASES[codes << (3 - bits)]
 
 
+def quantize(psi, bits):
+    """Every phase of `psi` (complex, any shape) moved to the nearest of the 2^B table phases: rule 25's argmax on conj(psi)
+    (code c maximises Re(conj(psi) C_c), the lowest c at a tie), so the result is exact and needs no atan2.  complex64."""
+    p = np.asarray(psi, dtype=np.complex64)
+    codes = align_codes(p.real, -p.imag, 0, 0, bits)
+    return PHASES[codes.astype(np.intp) << (3 - bits)]
+
+
+def dft_codebook(scale, los_b2r=None, over=1, bits=0):
+    """A beam-training codebook of M^2 steering patterns for the scale x scale surface, M = over * scale beams per axis: entry
+    k = i M + j points at the direction cosines (u_i, u_j), u_i = -1 + 2 i / M, after undoing the AP -> surface leg:
+    psi_{k,n} = conj(A_n) / |A_n| exp(-j pi (u_i ix + u_j iy)) for element n = ix * scale + iy (the order of :func:`los`),
+    A = los_b2r (None: 1).  over = 1 is the orthogonal DFT grid; over = 2 halves the scalloping loss between beams.
+    bits > 0: quantised to a B-bit surface by :func:`quantize`.  complex64 [M^2, N]."""
+    s, o = int(scale), int(over)
+    if s < 1 or o < 1:
+        raise ValueError("scale and over must be >= 1")
+    m = o * s
+    ix, iy = np.divmod(np.arange(s * s), s)
+    u = -1.0 + 2.0 * np.arange(m) / m
+    ui, uj = np.repeat(u, m), np.tile(u, m)
+    cb = np.exp(-1j * math.pi * (ui[:, None] * ix[None, :] + uj[:, None] * iy[None, :]))
+    if los_b2r is not None:
+        a = np.asarray(los_b2r, dtype=np.complex128).reshape(-1)
+        if a.size != s * s or not (np.abs(a) > 0).all():
+            raise ValueError("los_b2r must hold scale^2 values that are not zero")
+        cb = cb * (np.conj(a) / np.abs(a))[None, :]
+    cb = cb.astype(np.complex64)
+    return quantize(cb, bits) if bits else cb
+
+
+def traverse_codebook(scale, interval, irs_pos, ap_pos, accuracy=10, freq=5e9, bits=0):
+    """The grid of the reference's controller ("IRS Traverse" in gnu_radio/IRS_tranceiver.grc, the phase formula also in
+    gnu_radio/IRS_AP.grc), written from the formula: theta_i, phi_j = linspace(-pi/2, pi/2, accuracy), entry k = i * accuracy + j,
+    element n = ix * scale + iy at (x, y) = (irs_pos[0] + ix * interval, irs_pos[1] + iy * interval), D_n its distance to the
+    AP, and psi_{k,n} = exp(j (2 pi freq / 3e8) (D_n - sin(theta) cos(phi) y_n - sin(theta) sin(phi) x_n)); at theta = 0 the
+    formula's other branch, D_n - sin(phi) x_n.  bits > 0: quantised by :func:`quantize`.  complex64 [accuracy^2, N]."""
+    s, acc = int(scale), int(accuracy)
+    if s < 1 or acc < 1:
+        raise ValueError("scale and accuracy must be >= 1")
+    ix, iy = np.divmod(np.arange(s * s), s)
+    x = float(irs_pos[0]) + ix * float(interval)
+    y = float(irs_pos[1]) + iy * float(interval)
+    dist = np.sqrt((x - float(ap_pos[0])) ** 2 + (y - float(ap_pos[1])) ** 2 + (float(irs_pos[2]) - float(ap_pos[2])) ** 2)
+    wave = 2.0 * math.pi * float(freq) / 3e8
+    grid = np.linspace(-math.pi / 2, math.pi / 2, acc)
+    cb = np.empty((acc * acc, s * s), np.complex128)
+    for i, th in enumerate(grid):
+        for j, ph in enumerate(grid):
+            if th != 0:
+                pha = wave * (dist - math.sin(th) * math.cos(ph) * y - math.sin(th) * math.sin(ph) * x)
+            else:
+                pha = wave * (dist - math.sin(ph) * x)
+            cb[i * acc + j] = np.exp(1j * pha)
+    cb = cb.astype(np.complex64)
+    return quantize(cb, bits) if bits else cb
+
+
 @dataclass
 class IrsConfig:
     """What ``block.channel_model(irs=...)`` needs to draw its taps from wifirx_irs_taps.  The surface is given either by its
     geometry (``scale`` and the three positions, through :func:`los`) or by the line-of-sight vectors themselves; the phases
-    either by ``psi`` ([N] complex) or by ``align_bits`` = 1..3 (aligned per draw).  ``refresh``: the number of samples after
-    which a new tap set is drawn (set index = stream time // refresh)."""
+    either by ``psi`` ([N] complex), by ``align_bits`` = 1..3 (aligned per draw), or by ``codebook`` ([K, N] complex, K <= 1024:
+    trained per draw by wifirx_irs_sweep, NUMERICS.md rule 26; excludes the other two).  ``refresh``: the number of samples
+    after which a new tap set is drawn (set index = stream time // refresh)."""
     scale: int | None = None
     irs_pos: tuple | None = None
     ap_pos: tuple | None = None
@@ -108,6 +168,7 @@ class IrsConfig:
     align_bits: int = 0
     seed: int = 0
     refresh: int = 1 << 16
+    codebook: np.ndarray | None = None
     n_elems: int = field(init=False, default=0)
 
     def __post_init__(self):
@@ -136,7 +197,14 @@ class IrsConfig:
         self.align_bits = int(self.align_bits)
         if self.align_bits not in (0, 1, 2, 3):
             raise ValueError("align_bits must be 0..3")
-        if self.align_bits == 0:
+        if self.codebook is not None:
+            if self.psi is not None or self.align_bits:
+                raise ValueError("codebook excludes psi and align_bits")
+            cb = np.ascontiguousarray(np.asarray(self.codebook, dtype=np.complex64))
+            if cb.ndim != 2 or cb.shape[1] != self.n_elems or not 1 <= cb.shape[0] <= 1024:
+                raise ValueError("codebook must be [K, N] with 1 <= K <= 1024")
+            self.codebook = cb
+        elif self.align_bits == 0:
             self.set_psi(self.psi)
         self.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
         self.refresh = int(self.refresh)

@@ -510,6 +510,39 @@ int  wifirx_irs_taps(wifirx_handle* h, float* taps_out, uint32_t n_sets, uint32_
                      const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
                      float* elems_out, uint8_t* codes_out);
 
+/* Beam training of the same surface: the purpose of the reference's "IRS Traverse" block (gnu_radio/IRS_tranceiver.grc), which
+ * steps the surface through a codebook of configurations and keeps the one with the best link.  For every tap set the elements
+ * are drawn once and run against all K = n_codes entries; arithmetic = NUMERICS.md rule 26.  With a_n, b_n, h_d and s_l exactly
+ * wifirx_irs_taps' (the same irs_seed gives the same element bits: counters (n, r, l, 2) and (0xFFFFFFFF, r, l, 2), scatter row
+ * (r L + l) % n_scatter) and e_n = a_n b_n:
+ *     y_{l,k}  = sum_n e_n psi_{k,n}      one fma chain per part over the 2 N floats e_0.re, e_0.im, e_1.re, ... in ascending
+ *                                         order from +0, filled with zero terms up to a multiple of 4: the order in which
+ *                                         consecutive v_mfma_f32_16x16x4_f32 instructions accumulate
+ *     t_{l,k}  = s_l (h_d + y_{l,k})
+ *     P_{r,k}  = sum_l |t_{l,k}|^2        ascending l; |t|^2 = re re + im im without fma
+ *     best_r   = the k with the greatest P_{r,k}: scan k ascending from top = -1, replace on a strict >, so the lowest k wins a
+ *                tie, a NaN power never wins, and all powers NaN give 0
+ * The reference's block never updates its running maximum and so settles on the last entry; this call implements the stated
+ * purpose.  Selection is by channel power (the measured SNR up to noise); selection from noisy estimates is not modelled.
+ *   taps_out     DEVICE complex64 [n_sets][n_taps] (8-byte aligned) or NULL: the winner's taps t_{l,best}, the layout
+ *                wifirx_channel* reads with taps_on_device = 1, n_tap_sets = n_sets.  Within rule 26's bound of wifirx_irs_taps
+ *                with psi = codebook[best] (the same value rounded in another order).
+ *   best_out     DEVICE uint16 [n_sets] (2-byte aligned) or NULL: the winning entry.
+ *   power_out    DEVICE float32 [n_sets][n_codes] (4-byte aligned) or NULL: P_{r,k}.
+ *   codebook     complex64 [n_codes][N], HOST or (codebook_on_device) DEVICE; 1 <= n_codes <= 1024.  Any complex value is taken
+ *                (Python: wifirx.irs.dft_codebook, traverse_codebook, quantize).
+ *   the other arguments   as wifirx_irs_taps, refused on the same grounds.
+ * Checked on the host before anything is queued: wifirx_irs_taps' WIFIRX_EINVAL cases for the shared arguments, and WIFIRX_EINVAL
+ * for a NULL codebook, n_codes outside 1..1024, all three outputs NULL, and misaligned pointers (complex64: 8 bytes, power_out
+ * and the host arrays: 4, best_out: 2); WIFIRX_ERANGE for more than 2^31 - 1 sets.  n_sets = 0 does nothing and returns
+ * WIFIRX_OK.  One kernel launch per call, after one upload of the host arrays.  ORDER: as wifirx_channel. */
+int  wifirx_irs_sweep(wifirx_handle* h, float* taps_out, uint32_t n_sets, uint32_t n_taps, const float* pdp, float gain,
+                      uint32_t n_elems, const float* los_b2r, const float* los_r2u, const float* los_b2u,
+                      float k_factor, float direct_gain,
+                      const float* codebook, int codebook_on_device, uint32_t n_codes,
+                      const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
+                      uint16_t* best_out, float* power_out);
+
 /* ieee802_11.mac (gnu_radio/IRS_user.py:192,204-205; IRS_tranceiver.py:271,313-314) for a batch: PSDU i, at
  * psdu + i * psdu_stride, is the 24 + payload_len[i] + 4 bytes
  *     08 00 | 00 00 | addr1 = dst | addr2 = src | addr3 = bss | ((seq0 + i) & 0xFFF) << 4, little endian | payload i | FCS

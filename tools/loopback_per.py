@@ -62,10 +62,12 @@ the combiner) and mode.  The counts nest: A antennas are the first A of the larg
 
 --irs: the link over a reflecting surface of N elements with B-bit phases (wifirx_irs_taps, NUMERICS.md rule 25): one tap set of 8
 taps per frame, made on the device and read there by wifirx_channel; FER against the surface size at SNRs of one unit-power path.
---irs-mode: random phases, the one configuration aligned to the geometry, the genie aligned per draw.  --irs 0 is the direct
-path alone.
+--irs-mode: random phases, the one configuration aligned to the geometry, the genie aligned per draw, or `sweep`: a surface
+trained per draw by a codebook sweep (wifirx_irs_sweep, rule 26; --irs-codebook dft / dft2 / traverse, quantised to --irs-bits).
+--irs 0 is the direct path alone.
 
-    python tools/loopback_per.py --irs 0 16 64 256 --irs-bits 2 --irs-mode random los genie --k-factor 3 --direct-db -inf --psdu-len 294 --encoding 2 --snr -20 -10 0 [--frames 65536] [--out profiles/loopback_irs.json]"""
+    python tools/loopback_per.py --irs 0 16 64 256 --irs-bits 2 --irs-mode random los genie --k-factor 3 --direct-db -inf --psdu-len 294 --encoding 2 --snr -20 -10 0 [--frames 65536] [--out profiles/loopback_irs.json]
+    python tools/loopback_per.py --irs 64 256 --irs-bits 2 --irs-mode random los genie sweep --irs-codebook dft2 --k-factor 3 --psdu-len 294 --encoding 2 --snr -30 -20 -10 [--out profiles/loopback_irs_sweep.json]"""
 import argparse
 import json
 import math
@@ -139,8 +141,12 @@ def main():
                     help="with --antennas: the combiner's modes (default both)")
     ap.add_argument("--irs", type=int, nargs="+", default=None, help="a reflecting surface of these many elements (squares; 0 = the direct path alone)")
     ap.add_argument("--irs-bits", type=int, default=2, choices=(1, 2, 3), help="with --irs: the phase resolution")
-    ap.add_argument("--irs-mode", nargs="+", choices=("random", "los", "genie"), default=["genie"],
-                    help="with --irs: random phases, the one configuration aligned to the geometry, or aligned per draw")
+    ap.add_argument("--irs-mode", nargs="+", choices=("random", "los", "genie", "sweep"), default=["genie"],
+                    help="with --irs: random phases, the one configuration aligned to the geometry, aligned per draw, or trained "
+                         "per draw by a codebook sweep (wifirx_irs_sweep)")
+    ap.add_argument("--irs-codebook", choices=("dft", "dft2", "traverse"), default="dft2",
+                    help="with --irs-mode sweep: irs.dft_codebook at over = 1 / 2, or the reference controller's 10 x 10 grid "
+                         "(irs.traverse_codebook), quantised to --irs-bits")
     ap.add_argument("--direct-db", type=float, default=float("-inf"), help="with --irs: gain of the direct path in dB (-inf: blocked)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -543,6 +549,7 @@ def irs_main(a):
     rx = capi.WifiRx(max_sym=n_sym, llr_bits=0, chan_est=capi.EQ_LS, device=0)
     t_all = time.perf_counter()
     d_psdu, rows, iq, d_taps = rx.alloc(n * plen), rx.alloc(n * slot * 8), rx.alloc(n * slot * 8), rx.alloc(n * L * 8)
+    d_best = rx.alloc(n * 2)
     rx.mac_batch_dev(d_psdu.ptr, plen, n, None, payload_len=plen - 28, payload_seed=a.seed)
     rx.tx_batch_dev(rows.ptr, n * slot, d_psdu.ptr, enc, psdu_len=np.full(n, plen, np.uint32), psdu_stride=plen, lead=LEAD,
                     row_len=slot)
@@ -555,10 +562,17 @@ def irs_main(a):
     for N in a.irs:
         # the surface in front of the AP as in the reference's scenes; --irs 0: one element that reflects nothing
         S = max(1, int(round(N ** 0.5)))
-        b2r, r2u, b2u = irs.los(S, [0.015, 0.015, 0], [S * 0.015, S * 0.015, 4.5], [S * 0.015 + 0.3, S * 0.015 - 0.2, 1.0])
+        irs_pos, ap_pos = [0.015, 0.015, 0], [S * 0.015, S * 0.015, 4.5]
+        b2r, r2u, b2u = irs.los(S, irs_pos, ap_pos, [S * 0.015 + 0.3, S * 0.015 - 0.2, 1.0])
         for mode in (a.irs_mode if N else ["none"]):
             kw = dict(k_factor=a.k_factor, direct_gain=direct_gain if N else (direct_gain or 1.0), seed=(a.seed << 32) + N)
-            if mode == "genie":
+            winners = None
+            if mode == "sweep":
+                if a.irs_codebook == "traverse":
+                    kw["codebook"] = irs.traverse_codebook(S, 0.03, irs_pos, ap_pos, accuracy=10, bits=bits)
+                else:
+                    kw["codebook"] = irs.dft_codebook(S, b2r, over=min(2 if a.irs_codebook == "dft2" else 1, max(1, 32 // S)), bits=bits)
+            elif mode == "genie":
                 kw["align_bits"] = bits
             elif mode == "los":
                 kw["psi"] = irs.align(b2r, r2u, b2u if direct_gain else 0.0, bits)[1]
@@ -567,7 +581,13 @@ def irs_main(a):
             else:
                 kw["psi"] = np.zeros(1, np.complex64)
             # one tap set per frame, made on the device and read there by the channel
-            rx.irs_taps_dev(d_taps, n, pdp, b2r, r2u, b2u, **kw)
+            if mode == "sweep":
+                rx.irs_sweep_dev(d_taps, n, pdp, b2r, r2u, b2u, best_ptr=d_best, **kw)
+                hist = np.bincount(d_best.download(np.uint16, n), minlength=kw["codebook"].shape[0])
+                winners = {"entries": int(kw["codebook"].shape[0]), "distinct": int((hist > 0).sum()),
+                           "histogram": {str(k): int(hist[k]) for k in np.nonzero(hist)[0]}}
+            else:
+                rx.irs_taps_dev(d_taps, n, pdp, b2r, r2u, b2u, **kw)
             mean_power = float((np.abs(d_taps.download(np.complex64, min(n, 65536) * L).astype(np.complex128)) ** 2).sum() / min(n, 65536))
             for snr in a.snr:
                 t0 = time.perf_counter()
@@ -579,18 +599,22 @@ def irs_main(a):
                 points.append({"n_elems": N, "mode": mode, "snr_db": snr, "frames": n, "fer": r["fer"], "coded_ber": r["coded_ber"],
                                "mean_channel_power": mean_power, "seconds": time.perf_counter() - t0,
                                "counts": {k: r[k] for k in COUNTERS}})
+                if winners is not None:
+                    points[-1]["winners"] = winners
                 print(json.dumps({k: points[-1][k] for k in ("n_elems", "mode", "snr_db", "fer", "mean_channel_power")}), file=sys.stderr)
     seconds_total = time.perf_counter() - t_all
     rx.free_out(ref)
     rx.free_out(dev)
-    rows.free(); iq.free(); d_taps.free(); rx.close()
-    res = {"workload": "loop-back on the device over a reflecting surface (wifirx_irs_taps -> wifirx_channel, tap sets never leave the "
+    rows.free(); iq.free(); d_taps.free(); d_best.free(); rx.close()
+    res = {"workload": "loop-back on the device over a reflecting surface (wifirx_irs_taps / wifirx_irs_sweep -> wifirx_channel, tap sets never leave the "
                        "device): %d distinct frames per point, one tap set per frame, encoding %d, PSDU %d B (%d symbols), rows of %d, "
                        "lead 160, 8 taps (pdp exp(-l/2), sum 1), k_factor %g, direct path %s, %d-bit phases, LS, hard decode_mac"
                        % (n, enc, plen, n_sym, slot, a.k_factor, "blocked" if direct_gain == 0 else "%g dB" % a.direct_db, bits),
            "snr": "of one unit-power path (an element's leg, or the unattenuated direct path); n_elems 0 is the direct path alone at 0 dB",
            "modes": {"random": "one random configuration", "los": "the one configuration aligned to the geometry (irs.align)",
-                     "genie": "aligned per draw on tap 0 (align_bits)"},
+                     "genie": "aligned per draw on tap 0 (align_bits)",
+                     "sweep": "trained per draw: the best entry of the %s codebook, quantised to the same bits (wifirx_irs_sweep, "
+                              "NUMERICS.md rule 26); 'winners' holds the histogram of the winning entries" % a.irs_codebook},
            "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
