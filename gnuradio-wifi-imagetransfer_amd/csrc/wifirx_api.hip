@@ -28,6 +28,7 @@
 #include "wr_channel.h"
 #include "wr_irs.h"
 #include "wr_irs_sweep.h"
+#include "wr_irs_multi.h"
 #include "wr_link.h"
 #include "wr_convert.h"
 #include "wr_channelizer.h"

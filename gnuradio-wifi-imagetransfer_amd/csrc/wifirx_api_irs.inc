@@ -161,3 +161,168 @@ extern "C" int wifirx_irs_sweep(wifirx_handle* h, float* taps_out, uint32_t n_se
     HIP_TRY(h, wr_launch_irs_sweep(h->stream, &a));
     return WIFIRX_OK;
 }
+
+// ---- the surface behind an AP of n_ant antennas (wr_irs_multi.hip, NUMERICS.md rules 27 and 28) ----
+
+// the checks of the scene that wifirx_irs_taps_multi and wifirx_irs_sweep_multi share, in wifirx_irs_taps' order and words
+static int irs_multi_check(wifirx_handle* h, uint32_t n_ant, uint32_t n_taps, const float* pdp, float gain, uint32_t n_elems,
+                           const float* los_b2u, float k_factor, float direct_gain, const float* scatter, uint32_t n_scatter)
+{
+    if (n_ant < 1 || n_ant > wr_irs_max_ant()) return fail(h, WIFIRX_EINVAL, "n_ant must be 1..8");
+    if (n_elems < 1 || n_elems > wr_irs_max_elems()) return fail(h, WIFIRX_EINVAL, "n_elems must be 1..4096");
+    if (n_taps < 1 || n_taps > wr_irs_max_taps()) return fail(h, WIFIRX_EINVAL, "n_taps must be 1..16");
+    if (!std::isfinite(gain) || !std::isfinite(direct_gain)) return fail(h, WIFIRX_EINVAL, "gain and direct_gain must be finite");
+    if (!(std::isfinite(k_factor) && k_factor >= 0.0f)) return fail(h, WIFIRX_EINVAL, "k_factor must be finite and not negative");
+    if (direct_gain != 0.0f && !los_b2u) return fail(h, WIFIRX_EINVAL, "los_b2u is required with a direct path");
+    if (scatter && n_scatter == 0) return fail(h, WIFIRX_EINVAL, "n_scatter must be >= 1 with scatter");
+    return WIFIRX_OK;
+}
+
+// one upload of what the host holds, as wifirx_irs_taps does it: add() appends an array at 8-byte alignment and notes which
+// device pointer is to name it; send() copies, waits for the copy (not for a kernel) and sets the pointers
+struct IrsMeta {
+    std::vector<uint8_t> meta;
+    std::vector<std::pair<void*, size_t>> named;
+    void add(void* dev_ptr, const void* host, size_t bytes)
+    {
+        const size_t off = (meta.size() + 7) & ~(size_t)7;
+        meta.resize(off + bytes);
+        std::memcpy(meta.data() + off, host, bytes);
+        named.emplace_back(dev_ptr, off);
+    }
+    int send(wifirx_handle* h)
+    {
+        int rc;
+        if ((rc = h->stage.irs_meta.reserve(h, meta.size()))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->stage.irs_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (const auto& n : named) {
+            const uint8_t* dev = h->stage.irs_meta.as<uint8_t>() + n.second;
+            std::memcpy(n.first, &dev, sizeof dev);
+        }
+        return WIFIRX_OK;
+    }
+};
+
+// the scene's host arrays into `up` and its scalars into `a` (the pointers of `a` are set by up.send())
+static void irs_multi_scene(wr::IrsMultiArgs& a, IrsMeta& up, std::vector<float>& scale, std::vector<float>& los_d, uint32_t n_ant,
+                            uint32_t n_sets, uint32_t n_taps, const float* pdp, float gain, uint32_t n_elems, const float* los_b2r,
+                            const float* los_r2u, const float* los_b2u, float k_factor, float direct_gain, const float* scatter,
+                            uint32_t n_scatter, uint64_t irs_seed)
+{
+    scale.resize(n_taps);                               // s_l = (float)(sqrt(pdp_l) gain), formed in double
+    for (uint32_t l = 0; l < n_taps; l++) scale[l] = (float)(std::sqrt((double)pdp[l]) * (double)gain);
+    los_d.assign(2 * (size_t)n_ant, 0.0f);              // D_m; zeros where nothing of the direct path is read
+    if (direct_gain != 0.0f) std::memcpy(los_d.data(), los_b2u, 8 * (size_t)n_ant);
+    up.add(&a.s.los_a, los_b2r, 8ull * n_ant * n_elems);
+    up.add(&a.s.los_b, los_r2u, 8ull * n_elems);
+    up.add(&a.s.scale, scale.data(), 4ull * n_taps);
+    up.add(&a.los_d, los_d.data(), 8ull * n_ant);
+    a.s.scatter = reinterpret_cast<const float2*>(scatter);
+    a.s.seed = irs_seed;
+    a.s.n_sets = n_sets;
+    a.s.n_taps = n_taps;
+    a.s.n_elems = n_elems;
+    a.s.n_psi_sets = 1;
+    a.s.n_scatter = scatter ? n_scatter : 1;
+    if (k_factor > 0.0f) {                              // formed in double; k_factor = 0: neither is applied (a_los = 0 says so)
+        a.s.a_los = (float)std::sqrt((double)k_factor / ((double)k_factor + 1.0));
+        a.s.a_nlos = (float)std::sqrt(1.0 / ((double)k_factor + 1.0));
+    }
+    a.s.direct_gain = direct_gain;
+    a.n_ant = n_ant;
+}
+
+extern "C" int wifirx_irs_taps_multi(wifirx_handle* h, float* taps_out, uint32_t n_ant, uint32_t n_sets, uint32_t n_taps,
+                                     const float* pdp, float gain, uint32_t n_elems,
+                                     const float* los_b2r, const float* los_r2u, const float* los_b2u,
+                                     float k_factor, float direct_gain,
+                                     const float* psi, int psi_on_device, uint32_t n_psi_sets, uint32_t align_bits,
+                                     const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
+                                     float* elems_out, uint8_t* codes_out)
+{
+    if (!h) return WIFIRX_EINVAL;
+    // ---- the argument checks, before anything is queued ----
+    if (!taps_out || !pdp || !los_b2r || !los_r2u) return fail(h, WIFIRX_EINVAL, "taps_out, pdp, los_b2r and los_r2u are required");
+    if (align_bits > 3) return fail(h, WIFIRX_EINVAL, "align_bits must be 0..3");
+    int rc;
+    if ((rc = irs_multi_check(h, n_ant, n_taps, pdp, gain, n_elems, los_b2u, k_factor, direct_gain, scatter, n_scatter))) return rc;
+    if (align_bits == 0 && !psi) return fail(h, WIFIRX_EINVAL, "psi is required when align_bits is 0");
+    if (align_bits == 0 && n_psi_sets == 0) return fail(h, WIFIRX_EINVAL, "n_psi_sets must be >= 1 when align_bits is 0");
+    if (align_bits == 0 && codes_out) return fail(h, WIFIRX_EINVAL, "codes_out needs align_bits 1..3");
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    const bool psi_read = align_bits == 0;
+    if ((addr(taps_out) | addr(scatter) | addr(elems_out) | (psi_read && psi_on_device ? addr(psi) : 0)) & 7)
+        return fail(h, WIFIRX_EINVAL, "taps_out, scatter, elems_out and device psi must be 8-byte aligned (complex64)");
+    if ((addr(pdp) | addr(los_b2r) | addr(los_r2u) | addr(los_b2u) | (psi_read && !psi_on_device ? addr(psi) : 0)) & 3)
+        return fail(h, WIFIRX_EINVAL, "the host arrays must be 4-byte aligned (float32)");
+    for (uint32_t l = 0; l < n_taps; l++)
+        if (!(std::isfinite(pdp[l]) && pdp[l] >= 0.0f)) return fail(h, WIFIRX_EINVAL, "pdp must be finite and not negative");
+    if (n_sets == 0) return WIFIRX_OK;
+    if (n_sets > 0x7fffffffu) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 tap sets");
+    const bool host_psi = psi_read && !psi_on_device;
+    if (host_psi && (uint64_t)n_psi_sets * n_elems * 8 > (1ull << 31)) return fail(h, WIFIRX_ERANGE, "host psi above 2 GiB");
+
+    stream_worker_wait_idle(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    wr::IrsMultiArgs a{};
+    IrsMeta up;
+    std::vector<float> scale, los_d;
+    irs_multi_scene(a, up, scale, los_d, n_ant, n_sets, n_taps, pdp, gain, n_elems, los_b2r, los_r2u, los_b2u, k_factor, direct_gain,
+                    scatter, n_scatter, irs_seed);
+    a.s.psi = reinterpret_cast<const float2*>(psi);
+    if (host_psi) up.add(&a.s.psi, psi, 8ull * n_psi_sets * n_elems);
+    // the host arrays (the caller's and the staging vectors) may go once this returns
+    if ((rc = up.send(h))) return rc;
+    a.s.taps_out = reinterpret_cast<float2*>(taps_out);
+    a.s.elems_out = reinterpret_cast<float2*>(elems_out);
+    a.s.codes_out = codes_out;
+    a.s.n_psi_sets = psi_read ? n_psi_sets : 1;
+    a.s.align_bits = align_bits;
+    HIP_TRY(h, wr_launch_irs_multi(h->stream, &a));
+    return WIFIRX_OK;
+}
+
+extern "C" int wifirx_irs_sweep_multi(wifirx_handle* h, float* taps_out, uint32_t n_ant, uint32_t n_sets, uint32_t n_taps,
+                                      const float* pdp, float gain, uint32_t n_elems,
+                                      const float* los_b2r, const float* los_r2u, const float* los_b2u,
+                                      float k_factor, float direct_gain,
+                                      const float* codebook, int codebook_on_device, uint32_t n_codes,
+                                      const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
+                                      uint16_t* best_out, float* power_out)
+{
+    if (!h) return WIFIRX_EINVAL;
+    // ---- the argument checks, before anything is queued ----
+    if (!pdp || !los_b2r || !los_r2u || !codebook) return fail(h, WIFIRX_EINVAL, "pdp, los_b2r, los_r2u and codebook are required");
+    if (!taps_out && !best_out && !power_out) return fail(h, WIFIRX_EINVAL, "one of taps_out, best_out and power_out is required");
+    if (n_codes < 1 || n_codes > wr_irs_max_codes()) return fail(h, WIFIRX_EINVAL, "n_codes must be 1..1024");
+    int rc;
+    if ((rc = irs_multi_check(h, n_ant, n_taps, pdp, gain, n_elems, los_b2u, k_factor, direct_gain, scatter, n_scatter))) return rc;
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((addr(taps_out) | addr(scatter) | (codebook_on_device ? addr(codebook) : 0)) & 7)
+        return fail(h, WIFIRX_EINVAL, "taps_out, scatter and a device codebook must be 8-byte aligned (complex64)");
+    if ((addr(pdp) | addr(los_b2r) | addr(los_r2u) | addr(los_b2u) | addr(power_out) | (codebook_on_device ? 0 : addr(codebook))) & 3)
+        return fail(h, WIFIRX_EINVAL, "the host arrays and power_out must be 4-byte aligned (float32)");
+    if (addr(best_out) & 1) return fail(h, WIFIRX_EINVAL, "best_out must be 2-byte aligned (uint16)");
+    for (uint32_t l = 0; l < n_taps; l++)
+        if (!(std::isfinite(pdp[l]) && pdp[l] >= 0.0f)) return fail(h, WIFIRX_EINVAL, "pdp must be finite and not negative");
+    if (n_sets == 0) return WIFIRX_OK;
+    if (n_sets > 0x7fffffffu) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 tap sets");
+
+    stream_worker_wait_idle(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    wr::IrsSweepMultiArgs a{};
+    IrsMeta up;
+    std::vector<float> scale, los_d;
+    irs_multi_scene(a.m, up, scale, los_d, n_ant, n_sets, n_taps, pdp, gain, n_elems, los_b2r, los_r2u, los_b2u, k_factor,
+                    direct_gain, scatter, n_scatter, irs_seed);
+    a.codebook = reinterpret_cast<const float2*>(codebook);
+    if (!codebook_on_device) up.add(&a.codebook, codebook, 8ull * n_codes * n_elems);
+    if ((rc = up.send(h))) return rc;
+    a.m.s.taps_out = reinterpret_cast<float2*>(taps_out);
+    a.best_out = best_out;
+    a.power_out = power_out;
+    a.n_codes = n_codes;
+    HIP_TRY(h, wr_launch_irs_sweep_multi(h->stream, &a));
+    return WIFIRX_OK;
+}

@@ -624,18 +624,25 @@ class channel_model(grshim.sync_block):
     configuration's draws, made on the device and handed to wifirx_channel there.  ``taps`` must then stay at its default and
     ``doppler`` at None; ``set_psi`` loads another phase configuration, which holds from the next ``work()`` on.  With
     ``IrsConfig(codebook=...)`` every tap set is the winner of a beam-training sweep over the codebook (wifirx_irs_sweep,
-    NUMERICS.md rule 26), and ``irs_best`` holds the winning entries of the sets drawn so far."""
+    NUMERICS.md rule 26), and ``irs_best`` holds the winning entries of the sets drawn so far.
+
+    ``IrsConfig(antennas=M)``, M = 2..8, puts an AP of M antennas behind the surface (wifirx_irs_taps_multi /
+    wifirx_irs_sweep_multi, NUMERICS.md rules 27 and 28): the block then has M output ports, port m the input through plane m of
+    the tap set in force.  The ports are the sample-synchronous antennas of one radio (rule 24): they share
+    ``frequency_offset`` and ``epsilon``, and port m draws its noise from ``noise_seed + m``.  ``irs_best`` and ``set_psi`` work
+    as with one antenna; a codebook is trained on the sum of the antennas' channel powers."""
 
     MAX_TAPS = 64
 
     def __init__(self, noise_voltage=1.0, frequency_offset=0.0, epsilon=1.0, taps=(1.0,), noise_seed=0, block_tags=False,
                  device=0, doppler=None, k_factor=0.0, fade_seed=0, irs=None):
-        grshim.sync_block.__init__(self, name="channel_model", in_sig=[np.complex64], out_sig=[np.complex64])
+        if irs is not None and not isinstance(irs, irs_mod.IrsConfig):
+            raise TypeError("irs must be an irs.IrsConfig")
+        self._ports = 1 if irs is None else irs.antennas         # output ports: the AP antennas behind the surface
+        grshim.sync_block.__init__(self, name="channel_model", in_sig=[np.complex64], out_sig=[np.complex64] * self._ports)
         self._doppler = None
         self._irs = None
         if irs is not None:
-            if not isinstance(irs, irs_mod.IrsConfig):
-                raise TypeError("irs must be an irs.IrsConfig")
             if doppler is not None or np.asarray(taps).size != 1 or complex(np.asarray(taps).reshape(-1)[0]) != 1.0:
                 raise ValueError("with irs the taps are the surface's: leave taps and doppler at their defaults")
         self._irs_sets = None                                    # device buffer of the surface's tap sets 0 .. _irs_n - 1
@@ -664,28 +671,30 @@ class channel_model(grshim.sync_block):
         self._irs.set_psi(psi)
         self._irs_n = 0                                          # the sets are made again when they are next needed
 
-    def _irs_set(self, s):
-        """device pointer of the surface's tap set s: the sets 0 .. s are made in one wifirx_irs_taps call (set r depends on r
-        alone), twice as many each time the stream outgrows them"""
+    def _irs_set(self, s, m=0):
+        """device pointer of the surface's tap set s for antenna m: the sets 0 .. s are made in one wifirx_irs_taps call (set r
+        depends on r alone), twice as many each time the stream outgrows them.  With M > 1 antennas the one call is
+        wifirx_irs_taps_multi / wifirx_irs_sweep_multi and the buffer holds its M planes of _irs_n sets."""
         c = self._irs
+        multi = c.antennas > 1
         if s >= self._irs_n:
             n = max(16, 2 * (s + 1))
             if self._irs_sets is not None:
                 self._irs_sets.free()
-            self._irs_sets = self._rx.alloc(n * c.pdp.size * 8)
+            self._irs_sets = self._rx.alloc(c.antennas * n * c.pdp.size * 8)
             if c.codebook is not None:
                 if self._irs_best is not None:
                     self._irs_best.free()
                 self._irs_best = self._rx.alloc(n * 2)
-                self._rx.irs_sweep_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, codebook=c.codebook, gain=c.gain,
-                                       k_factor=c.k_factor, direct_gain=c.direct_gain, seed=c.seed, best_ptr=self._irs_best)
-                self._irs_n = n
-                return self._irs_sets.ptr + 8 * c.pdp.size * s
-            self._rx.irs_taps_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, gain=c.gain, k_factor=c.k_factor,
-                                  direct_gain=c.direct_gain, psi=c.psi if c.align_bits == 0 else None,
-                                  align_bits=c.align_bits, seed=c.seed)
+                sweep = self._rx.irs_sweep_multi_dev if multi else self._rx.irs_sweep_dev
+                sweep(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, codebook=c.codebook, gain=c.gain,
+                      k_factor=c.k_factor, direct_gain=c.direct_gain, seed=c.seed, best_ptr=self._irs_best)
+            else:
+                taps = self._rx.irs_taps_multi_dev if multi else self._rx.irs_taps_dev
+                taps(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, gain=c.gain, k_factor=c.k_factor,
+                     direct_gain=c.direct_gain, psi=c.psi if c.align_bits == 0 else None, align_bits=c.align_bits, seed=c.seed)
             self._irs_n = n
-        return self._irs_sets.ptr + 8 * c.pdp.size * s
+        return self._irs_sets.ptr + 8 * c.pdp.size * (m * self._irs_n + s)
 
     @property
     def irs_best(self):
@@ -696,9 +705,9 @@ class channel_model(grshim.sync_block):
             return np.zeros(0, np.uint16)
         return self._irs_best.download(np.uint16, self._irs_n)
 
-    def _irs_work(self, x, out, n):
+    def _irs_work(self, x, outs, n):
         """work() with the surface's taps: the chunk is cut where the set index changes, every piece one wifirx_channel call
-        on device taps with the L - 1 samples before it in front"""
+        per output port on device taps with the L - 1 samples before it in front"""
         c, L, rx = self._irs, self._irs.pdp.size, self._rx
         cfo = np.float32(2.0 * math.pi * self._frequency_offset)
         inc, m64 = capi.phase_inc(cfo), 0xFFFFFFFFFFFFFFFF
@@ -710,10 +719,11 @@ class channel_model(grshim.sync_block):
             row = np.ascontiguousarray(np.concatenate([self._hist[self._hist.size - h:], x[at:at + m]]) if h else x[at:at + m])
             d_in, d_out = rx.alloc(row.size * 8).upload(row), rx.alloc(row.size * 8)
             try:
-                rx.channel_dev(d_in.ptr, d_out.ptr, row.size, 1, row_len=row.size, taps=self._irs_set(s), n_taps=L, n_tap_sets=1,
-                               cfo=cfo, phase0=(self._phase - inc * h) & m64, gain=1.0, noise_voltage=self._noise_voltage,
-                               seed=self.noise_seed, sample0=self._pos - h)
-                out[at:at + m] = d_out.download(np.complex64, row.size)[h:]
+                for port, out in enumerate(outs):
+                    rx.channel_dev(d_in.ptr, d_out.ptr, row.size, 1, row_len=row.size, taps=self._irs_set(s, port), n_taps=L,
+                                   n_tap_sets=1, cfo=cfo, phase0=(self._phase - inc * h) & m64, gain=1.0,
+                                   noise_voltage=self._noise_voltage, seed=(self.noise_seed + port) & m64, sample0=self._pos - h)
+                    out[at:at + m] = d_out.download(np.complex64, row.size)[h:]
             finally:
                 d_in.free()
                 d_out.free()
@@ -789,12 +799,12 @@ class channel_model(grshim.sync_block):
     def work(self, input_items, output_items):
         x = input_items[0]
         out = output_items[0]
-        n = min(len(x), len(out))
+        n = min([len(x)] + [len(o) for o in output_items[:self._ports]])
         if n == 0:
             return 0
         x = np.asarray(x[:n], dtype=np.complex64)
         if self._irs is not None:
-            return self._irs_work(x, out, n)
+            return self._irs_work(x, output_items[:self._ports], n)
         L = self._taps.size
         h = min(L - 1, self._hist.size)
         row = np.concatenate([self._hist[self._hist.size - h:], x]) if h else x

@@ -50,6 +50,7 @@ EXPORTS = [
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
     "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine", "wifirx_diversity_combine",
     "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi", "wifirx_irs_taps", "wifirx_irs_sweep",
+    "wifirx_irs_taps_multi", "wifirx_irs_sweep_multi",
 ]
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
@@ -103,6 +104,7 @@ DOPPLER_MAX = 2.0 ** -10            # the largest doppler (cycles per sample) wi
 FADE_MAX_TAPS = 16                  # the most taps with fading
 IRS_MAX_ELEMS, IRS_MAX_TAPS = 4096, 16      # wifirx_irs_taps: the most surface elements and taps (NUMERICS.md rule 25)
 IRS_MAX_CODES = 1024                        # wifirx_irs_sweep: the most codebook entries (NUMERICS.md rule 26)
+IRS_MAX_ANT = 8                             # wifirx_irs_taps_multi / _sweep_multi: the most AP antennas (NUMERICS.md rule 27)
 
 
 def resampler_table() -> np.ndarray:
@@ -231,6 +233,8 @@ _lib.wifirx_irs_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
 _lib.wifirx_irs_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_uint32,
                                   C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+_lib.wifirx_irs_taps_multi.argtypes = _lib.wifirx_irs_taps.argtypes[:2] + [C.c_uint32] + _lib.wifirx_irs_taps.argtypes[2:]
+_lib.wifirx_irs_sweep_multi.argtypes = _lib.wifirx_irs_sweep.argtypes[:2] + [C.c_uint32] + _lib.wifirx_irs_sweep.argtypes[2:]
 _lib.wifirx_resampler_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                   C.c_uint64, C.c_void_p, C.c_uint32]
@@ -778,6 +782,127 @@ class WifiRx:
             self.irs_sweep_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook=codebook, best_ptr=bufs["best"],
                                power_ptr=bufs["power"], **kw)
             return {"taps": bufs["taps"].download(np.complex64, n_sets * L).reshape(n_sets, L),
+                    "best": bufs["best"].download(np.uint16, n_sets),
+                    "power": bufs["power"].download(np.float32, n_sets * K).reshape(n_sets, K)}
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    # -- the surface behind an AP of M antennas (wifirx_irs_taps_multi, wifirx_irs_sweep_multi; NUMERICS.md rules 27, 28) --
+    @staticmethod
+    def _irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u):
+        """(pdp [L], A [M, N], B [N], D [M] or None) as contiguous float32 / complex64; a 1-D los_b2r is one antenna"""
+        p = np.ascontiguousarray(np.asarray(pdp, dtype=np.float32).reshape(-1))
+        a = np.asarray(los_b2r, dtype=np.complex64)
+        a = np.ascontiguousarray(a[None] if a.ndim == 1 else a)
+        b = np.ascontiguousarray(np.asarray(los_r2u, dtype=np.complex64).reshape(-1))
+        if a.ndim != 2 or a.shape[1] != b.size:
+            raise ValueError("los_b2r must be [M, N] and los_r2u [N]")
+        d = None if los_b2u is None else np.ascontiguousarray(np.asarray(los_b2u, dtype=np.complex64).reshape(-1))
+        if d is not None and d.size != a.shape[0]:
+            raise ValueError("los_b2u is one complex value per antenna")
+        return p, a, b, d
+
+    def irs_taps_multi_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, gain=1.0, k_factor=0.0,
+                           direct_gain=1.0, psi=None, n_psi_sets=None, align_bits=0, scatter=None, n_scatter=None, seed=0,
+                           elems_ptr=None, codes_ptr=None):
+        """wifirx_irs_taps_multi into device memory: M = len(los_b2r) planes of n_sets sets of len(pdp) complex64 taps at
+        taps_ptr, antenna-major [M, n_sets, L]; plane m (taps_ptr + m * n_sets * L * 8) is what channel_dev takes as taps=ptr,
+        n_taps=L, n_tap_sets=n_sets.  los_b2r [M, N], los_r2u [N], los_b2u [M] (irs.los(antennas=M) gives all three).  The
+        antennas share the surface-to-user leg and the phases; align_bits = 1..3 aligns on antenna 0, tap 0.  scatter: None =
+        Philox draws keyed by `seed`, or a device pointer to n_scatter rows of (M + 1) N + M complex64.  elems_ptr / codes_ptr:
+        optional device outputs [n_sets, L, M + 1, N] complex64 (a_0 .. a_{M-1}, b) / [n_sets, N] uint8.  The other arguments as
+        irs_taps_dev.  Asynchronous on the handle's stream."""
+        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
+        p, a, b, d = self._irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u)
+        keep, psi_ptr, psi_dev, n_psi = None, None, 0, 0
+        if isinstance(psi, (int, DevBuf)):
+            psi_ptr, psi_dev, n_psi = ptr(psi), 1, int(n_psi_sets or 1)
+        elif psi is not None:
+            keep = np.asarray(psi, dtype=np.complex64)
+            keep = np.ascontiguousarray(keep[None] if keep.ndim == 1 else keep)
+            if keep.ndim != 2 or keep.shape[1] != b.size:
+                raise ValueError("psi must be [N] or [n_psi_sets, N]")
+            psi_ptr, n_psi = _np_ptr(keep), keep.shape[0]
+        if scatter is not None and n_scatter is None:
+            raise ValueError("device scatter needs n_scatter")
+        self._check(_lib.wifirx_irs_taps_multi(self._h, ptr(taps_ptr), a.shape[0], int(n_sets), p.size, _np_ptr(p), float(gain),
+                                               b.size, _np_ptr(a), _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain),
+                                               psi_ptr, psi_dev, n_psi, int(align_bits), ptr(scatter), int(n_scatter or 0),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(elems_ptr), ptr(codes_ptr)))
+
+    def irs_taps_multi(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, scatter=None, want_elems=False, want_codes=False,
+                       **kw):
+        """irs_taps_multi_dev with host arrays: returns the taps as complex64 [M, n_sets, L], or a dict with them under "taps"
+        and the elements [n_sets, L, M + 1, N] under "elems" / the codes [n_sets, N] under "codes" when asked for.  scatter:
+        None or a host array [n_scatter, (M + 1) N + M]."""
+        a = np.asarray(los_b2r)
+        n_sets, L, M, N = int(n_sets), np.asarray(pdp).size, (1 if a.ndim == 1 else a.shape[0]), a.shape[-1]
+        bufs = {"taps": self.alloc(max(M * n_sets * L, 1) * 8)}
+        try:
+            if scatter is not None:
+                s = np.ascontiguousarray(scatter, dtype=np.complex64)
+                if s.ndim != 2 or s.shape[1] != (M + 1) * N + M:
+                    raise ValueError("scatter must be [n_scatter, (M + 1) N + M]")
+                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
+                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
+            if want_elems:
+                bufs["elems"] = self.alloc(max(n_sets * L * (M + 1) * N, 1) * 8)
+            if want_codes:
+                bufs["codes"] = self.alloc(max(n_sets * N, 1))
+            self.irs_taps_multi_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, elems_ptr=bufs.get("elems"),
+                                    codes_ptr=bufs.get("codes"), **kw)
+            out = {"taps": bufs["taps"].download(np.complex64, M * n_sets * L).reshape(M, n_sets, L)}
+            if want_elems:
+                out["elems"] = bufs["elems"].download(np.complex64, n_sets * L * (M + 1) * N).reshape(n_sets, L, M + 1, N)
+            if want_codes:
+                out["codes"] = bufs["codes"].download(np.uint8, n_sets * N).reshape(n_sets, N)
+        finally:
+            for b in bufs.values():
+                b.free()
+        return out if (want_elems or want_codes) else out["taps"]
+
+    def irs_sweep_multi_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, codebook, n_codes=None, gain=1.0,
+                            k_factor=0.0, direct_gain=1.0, scatter=None, n_scatter=None, seed=0, best_ptr=None, power_ptr=None):
+        """wifirx_irs_sweep_multi into device memory: irs_sweep_dev for the M = len(los_b2r) antennas of irs_taps_multi_dev, the
+        entries ranked by the sum of the antennas' channel powers (what an MRC receiver collects).  The winner's taps go to
+        taps_ptr as [M, n_sets, L], the winning entry to best_ptr (uint16 [n_sets]), every entry's summed power to power_ptr
+        (float32 [n_sets, K]); one of the three at least.  The other arguments as irs_sweep_dev and irs_taps_multi_dev.
+        Asynchronous on the handle's stream."""
+        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
+        p, a, b, d = self._irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u)
+        if isinstance(codebook, (int, DevBuf)):
+            keep, cb_ptr, cb_dev, n_cb = None, ptr(codebook), 1, int(n_codes or 0)
+        else:
+            keep = np.ascontiguousarray(np.asarray(codebook, dtype=np.complex64))
+            if keep.ndim != 2 or keep.shape[1] != b.size:
+                raise ValueError("codebook must be [K, N]")
+            cb_ptr, cb_dev, n_cb = _np_ptr(keep), 0, keep.shape[0]
+        if scatter is not None and n_scatter is None:
+            raise ValueError("device scatter needs n_scatter")
+        self._check(_lib.wifirx_irs_sweep_multi(self._h, ptr(taps_ptr), a.shape[0], int(n_sets), p.size, _np_ptr(p), float(gain),
+                                                b.size, _np_ptr(a), _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain),
+                                                cb_ptr, cb_dev, n_cb, ptr(scatter), int(n_scatter or 0),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(best_ptr), ptr(power_ptr)))
+
+    def irs_sweep_multi(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, codebook, scatter=None, **kw):
+        """irs_sweep_multi_dev with host arrays: returns {"taps": complex64 [M, n_sets, L], "best": uint16 [n_sets], "power":
+        float32 [n_sets, K]}.  scatter: None or a host array [n_scatter, (M + 1) N + M]."""
+        a = np.asarray(los_b2r)
+        n_sets, L, M, N = int(n_sets), np.asarray(pdp).size, (1 if a.ndim == 1 else a.shape[0]), a.shape[-1]
+        K = int(kw.get("n_codes") or 0) if isinstance(codebook, (int, DevBuf)) else np.asarray(codebook).shape[0]
+        bufs = {"taps": self.alloc(max(M * n_sets * L, 1) * 8), "best": self.alloc(max(n_sets, 1) * 2),
+                "power": self.alloc(max(n_sets * K, 1) * 4)}
+        try:
+            if scatter is not None:
+                s = np.ascontiguousarray(scatter, dtype=np.complex64)
+                if s.ndim != 2 or s.shape[1] != (M + 1) * N + M:
+                    raise ValueError("scatter must be [n_scatter, (M + 1) N + M]")
+                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
+                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
+            self.irs_sweep_multi_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook=codebook,
+                                     best_ptr=bufs["best"], power_ptr=bufs["power"], **kw)
+            return {"taps": bufs["taps"].download(np.complex64, M * n_sets * L).reshape(M, n_sets, L),
                     "best": bufs["best"].download(np.uint16, n_sets),
                     "power": bufs["power"].download(np.float32, n_sets * K).reshape(n_sets, K)}
         finally:

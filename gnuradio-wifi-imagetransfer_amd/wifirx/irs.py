@@ -31,17 +31,28 @@ def _steer(scale, direction):
     return np.exp(1j * math.pi * (direction[0] * ix + direction[1] * iy))
 
 
-def los(irs_scale, irs_pos, ap_pos, user_pos):
+def los(irs_scale, irs_pos, ap_pos, user_pos, antennas=None):
     """The line-of-sight part of the three links for one AP antenna and one user, in float64: (b2r [N], r2u [N], b2u),
     N = irs_scale^2.  The AP and the user are single antennas (steering vector 1), so the AP -> surface link is the conjugate
     of the surface's steering vector towards the AP, the surface -> user link the steering vector of the direction from the
-    user, and the direct link is 1."""
+    user, and the direct link is 1.
+
+    antennas = M (an int, 1..8): the AP is a uniform linear array of M antennas half a wavelength apart along x, the
+    reference's genLoS with antennaNum = M, and the result is (b2r [M, N], r2u [N], b2u [M]):
+    b2r[m, n] = exp(j pi m ux) b2r_single[n] and b2u[m] = exp(j pi m ux'), ux the x direction cosine from the surface to the AP
+    and ux' the one from the user to the AP.  Antenna 0 is the single-antenna result."""
     s = int(irs_scale)
     if s < 1:
         raise ValueError("irs_scale must be >= 1")
     b2r = np.conj(_steer(s, _direction(ap_pos, irs_pos)))
     r2u = _steer(s, _direction(irs_pos, user_pos))
-    return b2r, r2u, complex(1.0)
+    if antennas is None:
+        return b2r, r2u, complex(1.0)
+    m = int(antennas)
+    if not 1 <= m <= 8:
+        raise ValueError("antennas must be 1..8")
+    ula = lambda ux: np.exp(1j * math.pi * ux * np.arange(m))
+    return ula(_direction(ap_pos, irs_pos)[0])[:, None] * b2r[None, :], r2u, ula(_direction(ap_pos, user_pos)[0])
 
 
 def _mul32(ar, ai, br, bi):
@@ -152,7 +163,9 @@ class IrsConfig:
     geometry (``scale`` and the three positions, through :func:`los`) or by the line-of-sight vectors themselves; the phases
     either by ``psi`` ([N] complex), by ``align_bits`` = 1..3 (aligned per draw), or by ``codebook`` ([K, N] complex, K <= 1024:
     trained per draw by wifirx_irs_sweep, NUMERICS.md rule 26; excludes the other two).  ``refresh``: the number of samples
-    after which a new tap set is drawn (set index = stream time // refresh)."""
+    after which a new tap set is drawn (set index = stream time // refresh).  ``antennas`` = M (1..8): the AP is the array of
+    ``los(antennas=M)`` (wifirx_irs_taps_multi / wifirx_irs_sweep_multi, NUMERICS.md rules 27 and 28); the line-of-sight
+    vectors are then [M, N], [N] and [M], and the block has M output ports.  M = 1 is the single-antenna surface."""
     scale: int | None = None
     irs_pos: tuple | None = None
     ap_pos: tuple | None = None
@@ -169,19 +182,34 @@ class IrsConfig:
     seed: int = 0
     refresh: int = 1 << 16
     codebook: np.ndarray | None = None
+    antennas: int = 1
     n_elems: int = field(init=False, default=0)
 
     def __post_init__(self):
         geometry = (self.scale, self.irs_pos, self.ap_pos, self.user_pos)
+        self.antennas = int(self.antennas)
+        if not 1 <= self.antennas <= 8:
+            raise ValueError("antennas must be 1..8")
+        multi = self.antennas > 1
         if self.los_b2r is None and self.los_r2u is None:
             if any(v is None for v in geometry):
                 raise ValueError("give scale and the three positions, or the line-of-sight vectors")
-            self.los_b2r, self.los_r2u, self.los_b2u = los(*geometry)
+            self.los_b2r, self.los_r2u, self.los_b2u = los(*geometry, antennas=self.antennas) if multi else los(*geometry)
         elif self.los_b2r is None or self.los_r2u is None:
             raise ValueError("los_b2r and los_r2u come together")
-        self.los_b2r = np.asarray(self.los_b2r, dtype=np.complex64).reshape(-1)
         self.los_r2u = np.asarray(self.los_r2u, dtype=np.complex64).reshape(-1)
-        self.n_elems = self.los_b2r.size
+        if multi:
+            self.los_b2r = np.ascontiguousarray(np.asarray(self.los_b2r, dtype=np.complex64))
+            if self.los_b2r.ndim != 2 or self.los_b2r.shape[0] != self.antennas:
+                raise ValueError("los_b2r must be [antennas, N]")
+            self.n_elems = self.los_b2r.shape[1]
+            if self.los_b2u is not None:
+                self.los_b2u = np.ascontiguousarray(np.asarray(self.los_b2u, dtype=np.complex64).reshape(-1))
+                if self.los_b2u.size != self.antennas:
+                    raise ValueError("los_b2u must hold one value per antenna")
+        else:
+            self.los_b2r = np.asarray(self.los_b2r, dtype=np.complex64).reshape(-1)
+            self.n_elems = self.los_b2r.size
         if self.los_r2u.size != self.n_elems or not 1 <= self.n_elems <= 4096:
             raise ValueError("los_b2r and los_r2u must have one length of 1..4096 elements")
         self.k_factor, self.direct_gain, self.gain = float(self.k_factor), float(self.direct_gain), float(self.gain)

@@ -543,6 +543,70 @@ int  wifirx_irs_sweep(wifirx_handle* h, float* taps_out, uint32_t n_sets, uint32
                       const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
                       uint16_t* best_out, float* power_out);
 
+/* The same surface behind an AP of M = n_ant antennas, 1 <= M <= 8: the reference's Saleh_Valenzuela_Channel(..., antennaNum = M),
+ * whose H_B2R is [M, N] and H_B2U [M] while every antenna sees ONE surface-to-user leg H_R2U; arithmetic = NUMERICS.md rule 27.
+ * For antenna m < M, set r, tap l and element n, in float32 with wifirx_irs_taps' operations throughout:
+ *     b_n       = mix(B_n, w_b(n,r,l))                      shared by all antennas
+ *     a_{m,n}   = mix(A_{m,n}, w_a(m,n,r,l))
+ *     h_{d,m}   = direct_gain * mix(D_m, w_d(m,r,l))
+ *     t_{m,r,l} = s_l (h_{d,m} + sum_n (a_{m,n} psi_n) b_n)
+ * mix(X, w) = a_los X + a_nlos w (k_factor = 0: w itself), s_l, the order of the sum (per antenna) and the special cases
+ * k_factor = 0 and direct_gain = 0 are wifirx_irs_taps'.  Antenna 0 is wifirx_irs_taps bit for bit, and n_ant = 1 is that call.
+ *   taps_out     DEVICE complex64 [n_ant][n_sets][n_taps] (8-byte aligned): antenna-major, so plane m (at taps_out +
+ *                2 m n_sets n_taps floats) is what wifirx_channel* reads with taps_on_device = 1, n_tap_sets = n_sets.
+ *   los_b2r, los_r2u, los_b2u   HOST complex64 [n_ant][N], [N], [n_ant]: A, B and D (Python: wifirx.irs.los(antennas=M), a
+ *                half-wavelength uniform linear array along x as in genLoS).  los_b2u may be NULL when direct_gain = 0.
+ *   psi          as wifirx_irs_taps: one configuration per set serves every antenna.
+ *   align_bits   B in {1, 2, 3}: the genie of the reference antenna.  The codes are wifirx_irs_taps' argmax on ANTENNA 0, TAP 0
+ *                (e_n = a_{0,n} b_n of tap 0, h_{d,0} of tap 0) and serve every antenna and tap of the set.  A genie for the
+ *                sum of the antennas' powers has no closed form and is not offered; wifirx_irs_sweep_multi trains on that sum.
+ *   scatter      NULL: Philox4x32-10 draws keyed by irs_seed, counter word 3 = 2.  w_a(0) = words (x, y) and w_b = words (z, w)
+ *                of the counter (n, r, l, 2); w_d(0) = words (x, y) of (0xFFFFFFFF, r, l, 2): wifirx_irs_taps' draws.  For
+ *                m >= 1, w_a(m) comes from the counter (n, r, l + 16 ((m + 1) >> 1), 2) and w_d(m) from (0xFFFFFFFF, r,
+ *                l + 16 ((m + 1) >> 1), 2): words (x, y) when m is odd, (z, w) when m is even, so one draw serves two antennas
+ *                and, as l < 16, no counter meets wifirx_irs_taps'.
+ *                Else DEVICE complex64 [n_scatter][(M + 1) N + M], each row w_a[0][N] .. w_a[M-1][N], w_b[N], w_d[M]; the pair
+ *                (r, l) reads row (r L + l) % n_scatter.  At M = 1 this is wifirx_irs_taps' row of 2 N + 1.
+ *   elems_out    DEVICE complex64 [n_sets][n_taps][n_ant + 1][N] or NULL: the realised a_0 .. a_{M-1}, then b.
+ *   codes_out    DEVICE uint8 [n_sets][N] or NULL: the codes of the aligned mode.
+ *   the other arguments   as wifirx_irs_taps.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for n_ant outside 1..8 and for every case of wifirx_irs_taps;
+ * WIFIRX_ERANGE as there.  n_sets = 0 does nothing and returns WIFIRX_OK.  One kernel launch per call, after one upload of the
+ * host arrays.  ORDER: as wifirx_channel. */
+int  wifirx_irs_taps_multi(wifirx_handle* h, float* taps_out, uint32_t n_ant, uint32_t n_sets, uint32_t n_taps,
+                           const float* pdp, float gain, uint32_t n_elems,
+                           const float* los_b2r /*[n_ant][N]*/, const float* los_r2u /*[N]*/, const float* los_b2u /*[n_ant]*/,
+                           float k_factor, float direct_gain,
+                           const float* psi, int psi_on_device, uint32_t n_psi_sets, uint32_t align_bits,
+                           const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
+                           float* elems_out /*[n_sets][L][n_ant+1][N]: a_0..a_{M-1}, b*/, uint8_t* codes_out);
+
+/* Beam training of that surface for a receiver that combines the M antennas (maximum-ratio combining, wifirx_diversity_combine):
+ * arithmetic = NUMERICS.md rule 28.  The elements are wifirx_irs_taps_multi's, drawn once per (set, tap); with
+ * e_{m,n} = ch_mul(a_{m,n}, b_n), row rho = m L + l and entry k:
+ *     y           = wifirx_irs_sweep's chain over e_{m,0}.re, e_{m,0}.im, e_{m,1}.re, ... (zero fill to a multiple of 4, on
+ *                   v_mfma_f32_16x16x4_f32, the same bits as a VALU fmaf chain)
+ *     t_{m,l,k}   = s_l (h_{d,m} + y)          q = re re + im im, without fma
+ *     P_{r,k}     = q_0 + q_1 + ... + q_{ML-1}  in ascending rho, starting from q_0: the channel power behind an MRC receiver
+ *                   with equal noise per antenna
+ *     best_r      = wifirx_irs_sweep's scan: strict >, the lowest k wins a tie, a NaN never wins
+ * Per-antenna noise weights and selection-combining metrics are not offered.  At n_ant = 1 this is wifirx_irs_sweep exactly.
+ *   taps_out     DEVICE complex64 [n_ant][n_sets][n_taps] (8-byte aligned) or NULL: the winner's taps t_{m,l,best}, antenna-major
+ *                as wifirx_irs_taps_multi's.  Within rule 26's bound, per antenna, of wifirx_irs_taps_multi with
+ *                psi = codebook[best].
+ *   best_out, power_out, codebook   as wifirx_irs_sweep.
+ *   the other arguments   as wifirx_irs_taps_multi.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for n_ant outside 1..8 and for every case of wifirx_irs_sweep;
+ * WIFIRX_ERANGE as there.  n_sets = 0 does nothing and returns WIFIRX_OK.  One kernel launch per call, after one upload of the
+ * host arrays.  ORDER: as wifirx_channel. */
+int  wifirx_irs_sweep_multi(wifirx_handle* h, float* taps_out, uint32_t n_ant, uint32_t n_sets, uint32_t n_taps,
+                            const float* pdp, float gain, uint32_t n_elems,
+                            const float* los_b2r, const float* los_r2u, const float* los_b2u,
+                            float k_factor, float direct_gain,
+                            const float* codebook, int codebook_on_device, uint32_t n_codes,
+                            const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
+                            uint16_t* best_out, float* power_out);
+
 /* ieee802_11.mac (gnu_radio/IRS_user.py:192,204-205; IRS_tranceiver.py:271,313-314) for a batch: PSDU i, at
  * psdu + i * psdu_stride, is the 24 + payload_len[i] + 4 bytes
  *     08 00 | 00 00 | addr1 = dst | addr2 = src | addr3 = bss | ((seq0 + i) & 0xFFF) << 4, little endian | payload i | FCS

@@ -1,0 +1,142 @@
+"""The operating point of the end-to-end test of the multi-antenna surface (tests/test_gpu_irs_multi.py::test_antennas_close_a_link_one_antenna_cannot) and the host chain
+that chose it: txgen -> irs_multi_ref.irs_sweep_multi (NUMERICS.md rules 27 and 28) -> channel_ref.channel per antenna -> the
+oracle's demod -> diversity_ref (MRC, rule 23) -> the oracle's decode_mac.
+
+256 QPSK-1/2 frames of 100 bytes, the 8-tap profile of tools/loopback_per.py --irs (pdp exp(-l/2), sum 1), an 8 x 8 surface
+(N = 64) in that tool's geometry in front of an AP of A antennas (irs.los(antennas=A)), Rician scatter with k_factor = 3, the
+direct path blocked, the surface trained per draw on the MRC metric over irs.dft_codebook(8, los_b2r[0], over=2, bits=2) (256
+entries of 2-bit phases), noise_voltage 1 on every antenna (noise seed NOISE_SEED + m) and a transmit gain of sqrt(snr): `snr` is
+the SNR of ONE unit-power path at one antenna.
+
+The point is searched on a 1 dB grid, for A = 2 first and for A = 4 only if A = 2 has none: the host chain must decode at most a
+quarter of the frames (64) on antenna 0 alone and at least three quarters (192) behind the A-antenna MRC, and both must still
+hold 1 dB to either side.  profiles/irs_multi_operating_point.json holds the point, its neighbours and every step looked at.
+
+What the search found: A = 2 has no such step (the batch MRC of two antennas lies about 2 dB left of antenna 0's curve: every
+antenna is detected and estimated on its own, so the window of 2 dB plus the grid does not fit).  A = 4 has one: -23 dB, with
+14 / 249 of 256 there, 3 / 227 at -24 dB and 54 / 255 at -22 dB.  With a single tap (pdp = {1}) neither A has one (the file's
+"single_tap" entry): the channel power then differs more from draw to draw and antenna 0's curve is flatter; the eight taps,
+whose scatter is independent, average that out.
+
+    python tests/irs_multi_point.py [--search] [--out profiles/irs_multi_operating_point.json]"""
+import math
+import os
+import sys
+
+import numpy as np
+
+N_FRAMES, ENC, PLEN, LEAD, TAIL = 256, 2, 100, 160, 79
+N_ANT = 4
+SNR_DB = -23.0
+SCALE, BITS, OVER, K_FACTOR = 8, 2, 2, 3.0
+N_ELEMS = SCALE * SCALE
+PSDU_SEED, NOISE_SEED, IRS_SEED = 33, 9500, 47
+N_TAPS = 8
+PDP = tuple(float(v) for v in (np.exp(-np.arange(N_TAPS) / 2.0) / np.exp(-np.arange(N_TAPS) / 2.0).sum()).astype(np.float32))
+SINGLE_AT_MOST, MRC_AT_LEAST = N_FRAMES // 4, 3 * N_FRAMES // 4
+GRID = range(-32, -20)
+
+
+def geometry():
+    from wifirx import txgen
+    slot = LEAD + txgen.frame_samples(PLEN, ENC) + TAIL
+    return txgen.n_sym_for(PLEN, ENC), slot + (slot & 1)
+
+
+def scene(n_ant=N_ANT):
+    """(los_b2r [A, N], los_r2u [N]) of the surface in front of the AP's array, as tools/loopback_per.py --irs places it"""
+    from wifirx import irs
+    S = SCALE
+    b2r, r2u, _ = irs.los(S, [0.015, 0.015, 0], [S * 0.015, S * 0.015, 4.5], [S * 0.015 + 0.3, S * 0.015 - 0.2, 1.0], antennas=n_ant)
+    return b2r.astype(np.complex64), r2u.astype(np.complex64)
+
+
+def surface(n_ant=N_ANT):
+    """keywords of irs_sweep_multi, restatement and device alike"""
+    from wifirx import irs
+    return dict(k_factor=K_FACTOR, direct_gain=0.0, seed=IRS_SEED, codebook=irs.dft_codebook(SCALE, scene(n_ant)[0][0], over=OVER, bits=BITS))
+
+
+def host_taps(n_ant=N_ANT, n=N_FRAMES, pdp=PDP):
+    import irs_multi_ref
+    b2r, r2u = scene(n_ant)
+    return irs_multi_ref.irs_sweep_multi(n, pdp, b2r, r2u, None, **surface(n_ant))
+
+
+def host_chain(snr_db=SNR_DB, n_ant=N_ANT, n=N_FRAMES, taps=None):
+    """FCS-good frames (of n) on antenna 0 alone and behind the MRC of the n_ant antennas, on the host"""
+    import channel_ref
+    import diversity_ref as dr
+    from oracle import oracle as orc
+    from wifirx import txgen
+    n_sym, slot = geometry()
+    psdus = txgen.make_psdus(n, PLEN, seed=PSDU_SEED)
+    tx = txgen.encode_psdus(psdus, ENC)
+    rows = np.zeros((n, slot), np.complex64)
+    rows[:, LEAD:LEAD + tx.samples.shape[1]] = tx.samples
+    prm = orc.make_params(max_sym=n_sym, llr_bits=2)
+    t = host_taps(n_ant, n) if taps is None else taps
+    ant = []
+    for m in range(n_ant):
+        y = channel_ref.channel(rows, taps=t["taps"][m], gain=math.sqrt(10 ** (snr_db / 10)), noise_voltage=1.0, seed=NOISE_SEED + m)
+        ant.append(orc.demod_batch(y, slot, prm, want_eq=True, want_csi=True, n_threads=8))
+
+    def good(frames, idx):
+        fr = frames.copy()
+        got = orc.decode_batch(fr, idx, prm, psdu_stride=112, n_threads=8)
+        return int((((fr["flags"] & 0x40) != 0) & (fr["psdu_len"] == PLEN) & (got[:, :PLEN] == psdus).all(axis=1)).sum())
+
+    out = dr.new_outputs(n, n_sym, 2, fill=0)
+    dr.combine([o["frames"] for o in ant], [o["eq"] for o in ant], [o["csi"] for o in ant], n_sym, 2, out, mode=dr.MRC)
+    power = np.abs(t["taps"].astype(np.complex128)) ** 2
+    res = {"snr_db": snr_db, "antennas": n_ant, "frames": n, "single": good(ant[0]["frames"], ant[0]["idx"]),
+           "mrc": good(out["frames"], out["idx"]), "mean_power_antenna0": float(power[0].mean()),
+           "mean_power_sum": float(power.sum(axis=0).mean()), "distinct_winners": int(np.unique(t["best"]).size)}
+    res["holds"] = bool(res["single"] <= SINGLE_AT_MOST and res["mrc"] >= MRC_AT_LEAST)
+    return res
+
+
+def search(n_ant, pdp=PDP):
+    """every grid step for n_ant antennas, and the first step that holds together with both neighbours (or None)"""
+    taps = host_taps(n_ant, pdp=pdp)                            # the taps do not depend on the SNR
+    pts = [host_chain(float(s), n_ant, taps=taps) for s in GRID]
+    for i in range(1, len(pts) - 1):
+        if pts[i - 1]["holds"] and pts[i]["holds"] and pts[i + 1]["holds"]:
+            return pts, pts[i]["snr_db"]
+    return pts, None
+
+
+if __name__ == "__main__":
+    import argparse
+    import json
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "gnuradio-wifi-imagetransfer_amd")]
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--search", action="store_true", help="walk the 1 dB grid for A = 2, then A = 4, instead of the chosen point")
+    ap.add_argument("--single-tap", action="store_true", help="with --search: also walk the grid with pdp = {1}, for the record")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rec = {"what": "host chain of tests/irs_multi_point.py: FCS-good frames of %d QPSK-1/2 frames of %d bytes at an SNR per unit-power "
+                   "path and antenna, 8 taps (pdp exp(-l/2), sum 1), over %d elements, k_factor %g, direct path blocked, the surface trained per draw on the MRC "
+                   "metric over a 256-entry 2-bit DFT codebook (NUMERICS.md rules 27 and 28): antenna 0 alone / MRC of A antennas"
+                   % (N_FRAMES, PLEN, N_ELEMS, K_FACTOR),
+           "accept": "single <= %d and mrc >= %d of %d, at the point and 1 dB to either side" % (SINGLE_AT_MOST, MRC_AT_LEAST, N_FRAMES)}
+    if a.search:
+        rec["searched"] = {}
+        for n_ant in (2, 4):
+            pts, found = search(n_ant)
+            rec["searched"]["A=%d" % n_ant] = {"points": pts, "found_snr_db": found}
+            if found is not None:
+                break
+        if a.single_tap:
+            rec["single_tap"] = {}
+            for n_ant in (2, 4):
+                pts, found = search(n_ant, pdp=(1.0,))
+                rec["single_tap"]["A=%d" % n_ant] = {"points": pts, "found_snr_db": found}
+    taps = host_taps()
+    rec.update(chosen_antennas=N_ANT, chosen_snr_db=SNR_DB, points=[host_chain(SNR_DB + s, taps=taps) for s in (-1.0, 0.0, 1.0)])
+    rec["neighbours_hold"] = bool(all(p["holds"] for p in rec["points"]))
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(rec, indent=1) + "\n")

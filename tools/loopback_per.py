@@ -150,6 +150,8 @@ def main():
     ap.add_argument("--direct-db", type=float, default=float("-inf"), help="with --irs: gain of the direct path in dB (-inf: blocked)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.irs is not None and a.antennas is not None:
+        return irs_multi_main(a)
     if a.irs is not None:
         return irs_main(a)
     if a.antennas is not None:
@@ -616,6 +618,115 @@ def irs_main(a):
                      "sweep": "trained per draw: the best entry of the %s codebook, quantised to the same bits (wifirx_irs_sweep, "
                               "NUMERICS.md rule 26); 'winners' holds the histogram of the winning entries" % a.irs_codebook},
            "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def irs_multi_main(a):
+    """--irs with --antennas: the diversity receiver behind the surface.  Per antenna count A the surface is drawn for an AP of A
+    antennas (wifirx_irs_taps_multi, or wifirx_irs_sweep_multi trained on the MRC metric), every antenna gets one wifirx_channel
+    call on its plane with a noise seed of its own, and the A demodulated antennas are combined (wifirx_diversity_combine)."""
+    if a.rates or a.host_stats or a.locked_clock or a.doppler is not None or a.adc_bits is not None or a.wideband is not None:
+        raise SystemExit("--irs with --antennas: not with --rates, --host-stats, --locked-clock, --doppler, --adc-bits or --wideband")
+    from wifirx import irs
+    counts = sorted(set(a.antennas))
+    if counts[0] < 1 or counts[-1] > min(capi.DIV_MAX_ANT, capi.IRS_MAX_ANT):
+        raise SystemExit("--antennas 1 .. %d" % min(capi.DIV_MAX_ANT, capi.IRS_MAX_ANT))
+    div = (a.diversity or ["mrc"])[0]
+    n = a.frames or 65536
+    plen, enc, bits = a.psdu_len, a.encoding, a.irs_bits
+    if not (28 <= plen <= 1528 and 0 <= enc <= 7):
+        raise SystemExit("--psdu-len 28 .. 1528, --encoding 0 .. 7")
+    for N in a.irs:
+        if N < 1 or N > capi.IRS_MAX_ELEMS or int(round(N ** 0.5)) ** 2 != N:
+            raise SystemExit("--irs with --antennas takes square surfaces of 1 .. 4096 elements")
+    modes = [m for m in a.irs_mode if m in ("random", "genie", "sweep")]
+    if len(modes) != len(a.irs_mode):
+        raise SystemExit("--irs with --antennas: --irs-mode random, genie (on antenna 0) or sweep (on the MRC metric)")
+    if a.irs_codebook == "traverse":
+        raise SystemExit("--irs with --antennas: --irs-codebook dft or dft2")
+    direct_gain = 0.0 if a.direct_db == float("-inf") else 10 ** (a.direct_db / 20)
+    n_sym, nb = txgen.n_sym_for(plen, enc), txgen.RATE_TABLE[enc][0]
+    slot = LEAD + txgen.frame_samples(plen, enc) + 79
+    slot += slot & 1
+    stride = (plen + 15) // 16 * 16
+    L = 8
+    pdp = np.exp(-np.arange(L) / 2.0)
+    pdp = (pdp / pdp.sum()).astype(np.float32)
+    rx = capi.WifiRx(max_sym=n_sym, llr_bits=nb, want_carrier=True, chan_est=capi.EQ_LS, device=0)
+    t_all = time.perf_counter()
+    d_psdu, rows, iq = rx.alloc(n * plen), rx.alloc(n * slot * 8), rx.alloc(n * slot * 8)
+    d_taps, d_best = rx.alloc(counts[-1] * n * L * 8), rx.alloc(n * 2)
+    rx.mac_batch_dev(d_psdu.ptr, plen, n, None, payload_len=plen - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, n * slot, d_psdu.ptr, enc, psdu_len=np.full(n, plen, np.uint32), psdu_stride=plen, lead=LEAD, row_len=slot)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * n_sym * 48), psdu=d_psdu, psdu_stride=plen)
+    rx.demod_batch_dev(rows.ptr, slot, n, ref)
+    assert rx.link_stats(n, ref, ref)["frames_ref"] == n, "a clean frame was not demodulated"
+    ins = [rx.alloc_out(n, psdu_stride=stride, want_csi=True) for _ in range(counts[-1])]
+    out = rx.alloc_out(n, psdu_stride=stride)
+    points = []
+    for N in a.irs:
+        S = int(round(N ** 0.5))
+        irs_pos, ap_pos, user_pos = [0.015, 0.015, 0], [S * 0.015, S * 0.015, 4.5], [S * 0.015 + 0.3, S * 0.015 - 0.2, 1.0]
+        for A in counts:
+            b2r, r2u, b2u = irs.los(S, irs_pos, ap_pos, user_pos, antennas=A)
+            for mode in modes:
+                kw = dict(k_factor=a.k_factor, direct_gain=direct_gain, seed=(a.seed << 32) + N)       # irs_main's seeds
+                winners = None
+                if mode == "sweep":
+                    kw["codebook"] = irs.dft_codebook(S, b2r[0], over=min(2 if a.irs_codebook == "dft2" else 1, max(1, 32 // S)), bits=bits)
+                    rx.irs_sweep_multi_dev(d_taps, n, pdp, b2r, r2u, b2u, best_ptr=d_best, **kw)
+                    hist = np.bincount(d_best.download(np.uint16, n), minlength=kw["codebook"].shape[0])
+                    winners = {"entries": int(kw["codebook"].shape[0]), "distinct": int((hist > 0).sum())}
+                elif mode == "genie":
+                    rx.irs_taps_multi_dev(d_taps, n, pdp, b2r, r2u, b2u, align_bits=bits, **kw)
+                else:
+                    rx.irs_taps_multi_dev(d_taps, n, pdp, b2r, r2u, b2u, psi=irs.random_psi(N, bits, a.seed), **kw)
+                k = min(n, 65536)
+                planes = d_taps.download(np.complex64, A * n * L).reshape(A, n, L)[:, :k].astype(np.complex128)
+                power = (np.abs(planes) ** 2).sum(axis=2).mean(axis=1)          # per antenna: the mean over the sets of sum_l |t|^2
+                for snr in a.snr:
+                    t0 = time.perf_counter()
+                    for ant in range(A):
+                        rx.channel_dev(rows.ptr, iq.ptr, n * slot, n, row_len=slot, taps=d_taps.ptr + ant * n * L * 8, n_taps=L,
+                                       n_tap_sets=n, gain=math.sqrt(10 ** (snr / 10)), noise_voltage=1.0,
+                                       seed=9000 + int(snr) + (a.seed << 32) + (ant << 16))
+                        rx.demod_batch_dev(iq.ptr, slot, n, ins[ant])
+                    dev = ins[0]
+                    if A > 1:
+                        rx.diversity_combine_dev(ins[:A], n, out, div)
+                        dev = out
+                    rx.decode_batch_dev(n, dev)
+                    hard = rx.link_stats(n, dev, ref)
+                    rx.decode_batch_soft_dev(n, dev)
+                    soft = rx.link_stats(n, dev, ref)
+                    points.append({"n_elems": N, "antennas": A, "mode": mode, "snr_db": snr, "frames": n, "fer": hard["fer"],
+                                   "fer_soft": soft["fer"], "mean_combined_channel_power": float(power.sum()),
+                                   "mean_channel_power_per_antenna": [float(v) for v in power], "seconds": time.perf_counter() - t0,
+                                   "counts": {c: hard[c] for c in COUNTERS}, "counts_soft": {c: soft[c] for c in COUNTERS}})
+                    if winners is not None:
+                        points[-1]["winners"] = winners
+                    print(json.dumps({c: points[-1][c] for c in ("n_elems", "antennas", "mode", "snr_db", "fer", "fer_soft",
+                                                                 "mean_combined_channel_power")}), file=sys.stderr)
+    seconds_total = time.perf_counter() - t_all
+    for d in ins + [out]:
+        rx.free_out(d)
+    rx.free_out(ref)
+    rows.free(); iq.free(); d_taps.free(); d_best.free(); rx.close()
+    res = {"workload": "the diversity receiver behind a reflecting surface, on the device (wifirx_irs_taps_multi / wifirx_irs_sweep_multi -> one "
+                       "wifirx_channel per antenna on its plane -> LS demod -> wifirx_diversity_combine (%s) -> hard and soft decode_mac; the tap "
+                       "sets never leave the device): %d distinct frames per point, one tap set per frame and antenna, encoding %d, PSDU %d B "
+                       "(%d symbols), rows of %d, lead 160, 8 taps (pdp exp(-l/2), sum 1), k_factor %g, direct path %s, %d-bit phases; the AP a "
+                       "half-wavelength array along x (irs.los(antennas=A))"
+                       % (div, n, enc, plen, n_sym, slot, a.k_factor, "blocked" if direct_gain == 0 else "%g dB" % a.direct_db, bits),
+           "snr": "of one unit-power path at one antenna; every antenna has noise of variance 1 from a seed of its own",
+           "modes": {"random": "one random configuration", "genie": "aligned per draw on antenna 0, tap 0 (align_bits)",
+                     "sweep": "trained per draw on the sum of the antennas' channel powers: the best entry of the %s codebook, quantised to "
+                              "the same bits (wifirx_irs_sweep_multi, NUMERICS.md rule 28)" % a.irs_codebook},
+           "antennas": counts, "stats": "wifirx_link_stats on the device; reported, not asserted",
+           "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
