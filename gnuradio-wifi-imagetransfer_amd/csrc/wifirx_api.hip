@@ -29,6 +29,7 @@
 #include "wr_irs.h"
 #include "wr_irs_sweep.h"
 #include "wr_irs_multi.h"
+#include "wr_irs_estimate.h"
 #include "wr_link.h"
 #include "wr_convert.h"
 #include "wr_channelizer.h"
@@ -129,6 +130,7 @@ struct Staging {
     DevBuf tx_psdu, tx_meta;        // wifirx_tx_batch: host PSDUs; lengths, seeds, row offsets
     DevBuf ch_meta;                 // wifirx_channel: host taps, phase increments, row offsets, tile bases
     DevBuf irs_meta;                // wifirx_irs_taps: line-of-sight vectors, tap scales, host psi
+    DevBuf irs_obs, irs_psi;        // wifirx_irs_estimate: the observations without an obs_out; the decided phases for the taps
     DevBuf link_meta, link_payload; // wifirx_mac_batch: payload lengths; host payloads
     DevBuf link_counts;             // wifirx_link_stats: the nine counters
     DevBuf iq_clipped;              // wifirx_iq_from_f32: the counter of clipped components

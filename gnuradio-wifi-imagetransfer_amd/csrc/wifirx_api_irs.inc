@@ -326,3 +326,91 @@ extern "C" int wifirx_irs_sweep_multi(wifirx_handle* h, float* taps_out, uint32_
     HIP_TRY(h, wr_launch_irs_sweep_multi(h->stream, &a));
     return WIFIRX_OK;
 }
+
+// ---- the surface configured from noisy pilot observations (wr_irs_estimate.hip, NUMERICS.md rule 29) ----
+
+extern "C" int wifirx_irs_estimate(wifirx_handle* h, float* taps_out, uint32_t n_ant, uint32_t n_sets, uint32_t n_taps,
+                                   const float* pdp, float gain, uint32_t n_elems,
+                                   const float* los_b2r, const float* los_r2u, const float* los_b2u, float k_factor, float direct_gain,
+                                   const float* pilot, int pilot_on_device, uint32_t n_pilots, uint32_t n_groups, const uint16_t* group,
+                                   float noise_sigma, float est_scale, uint32_t align_bits,
+                                   const float* scatter, uint32_t n_scatter, const float* noise, uint32_t n_noise, uint64_t irs_seed,
+                                   float* est_out, uint8_t* codes_out, float* obs_out)
+{
+    if (!h) return WIFIRX_EINVAL;
+    // ---- the argument checks, before anything is queued ----
+    if (!pdp || !los_b2r || !los_r2u || !pilot) return fail(h, WIFIRX_EINVAL, "pdp, los_b2r, los_r2u and pilot are required");
+    if (!taps_out && !est_out && !codes_out && !obs_out)
+        return fail(h, WIFIRX_EINVAL, "one of taps_out, est_out, codes_out and obs_out is required");
+    if (align_bits > 3) return fail(h, WIFIRX_EINVAL, "align_bits must be 0..3");
+    if (align_bits == 0 && (taps_out || codes_out)) return fail(h, WIFIRX_EINVAL, "taps_out and codes_out need align_bits 1..3");
+    int rc;
+    if ((rc = irs_multi_check(h, n_ant, n_taps, pdp, gain, n_elems, los_b2u, k_factor, direct_gain, scatter, n_scatter))) return rc;
+    if (n_pilots < 1 || n_pilots > wr_irs_max_pilots()) return fail(h, WIFIRX_EINVAL, "n_pilots must be 1..1024");
+    if (n_groups < 1 || n_groups > std::min(n_elems, wr_irs_max_groups())) return fail(h, WIFIRX_EINVAL, "n_groups must be 1..min(n_elems, 1023)");
+    if (!group && n_groups != n_elems) return fail(h, WIFIRX_EINVAL, "group is required when n_groups differs from n_elems");
+    if (!(std::isfinite(noise_sigma) && noise_sigma >= 0.0f)) return fail(h, WIFIRX_EINVAL, "noise_sigma must be finite and not negative");
+    if (!std::isfinite(est_scale)) return fail(h, WIFIRX_EINVAL, "est_scale must be finite");
+    if (noise && n_noise == 0) return fail(h, WIFIRX_EINVAL, "n_noise must be >= 1 with noise");
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((addr(taps_out) | addr(scatter) | addr(noise) | addr(est_out) | addr(obs_out) | (pilot_on_device ? addr(pilot) : 0)) & 7)
+        return fail(h, WIFIRX_EINVAL, "taps_out, est_out, obs_out, scatter, noise and a device pilot must be 8-byte aligned (complex64)");
+    if ((addr(pdp) | addr(los_b2r) | addr(los_r2u) | addr(los_b2u) | (pilot_on_device ? 0 : addr(pilot))) & 3)
+        return fail(h, WIFIRX_EINVAL, "the host arrays must be 4-byte aligned (float32)");
+    if (addr(group) & 1) return fail(h, WIFIRX_EINVAL, "group must be 2-byte aligned (uint16)");
+    for (uint32_t l = 0; l < n_taps; l++)
+        if (!(std::isfinite(pdp[l]) && pdp[l] >= 0.0f)) return fail(h, WIFIRX_EINVAL, "pdp must be finite and not negative");
+    if (group)
+        for (uint32_t n = 0; n < n_elems; n++)
+            if (group[n] >= n_groups) return fail(h, WIFIRX_EINVAL, "a group value is not below n_groups");
+    if (n_sets == 0) return WIFIRX_OK;
+    if (n_sets > 0x7fffffffu) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 tap sets");
+    const uint64_t rows = (uint64_t)n_sets * n_ant * n_taps;
+    if ((rows + 15) / 16 > 0x7fffffffu) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 tiles of 16 rows");
+
+    stream_worker_wait_idle(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    wr::IrsEstimateArgs a{};
+    IrsMeta up;
+    std::vector<float> scale, los_d;
+    irs_multi_scene(a.m, up, scale, los_d, n_ant, n_sets, n_taps, pdp, gain, n_elems, los_b2r, los_r2u, los_b2u, k_factor,
+                    direct_gain, scatter, n_scatter, irs_seed);
+    a.pilot = reinterpret_cast<const float2*>(pilot);
+    if (!pilot_on_device) up.add(&a.pilot, pilot, 8ull * n_pilots * n_groups);
+    if (group) up.add(&a.group, group, 2ull * n_elems);
+    // the scratch is reserved before the upload is queued: a failed allocation queues nothing
+    a.obs = reinterpret_cast<float2*>(obs_out);
+    if (!obs_out && (taps_out || est_out || codes_out)) {
+        if ((rc = h->stage.irs_obs.reserve(h, rows * n_pilots * 8))) return rc;
+        a.obs = h->stage.irs_obs.as<float2>();
+    }
+    if (taps_out) {
+        if ((rc = h->stage.irs_psi.reserve(h, 8ull * n_sets * n_elems))) return rc;
+        a.psi_out = h->stage.irs_psi.as<float2>();
+    }
+    // the host arrays (the caller's and the staging vectors) may go once this returns
+    if ((rc = up.send(h))) return rc;
+    a.noise = reinterpret_cast<const float2*>(noise);
+    a.est_out = reinterpret_cast<float2*>(est_out);
+    a.m.s.codes_out = codes_out;
+    a.m.s.align_bits = align_bits;
+    a.n_pilots = n_pilots;
+    a.n_groups = n_groups;
+    a.n_noise = noise ? n_noise : 1;
+    a.sigma = noise_sigma;
+    a.kappa = est_scale;
+    HIP_TRY(h, wr_launch_irs_observe(h->stream, &a));
+    if (!taps_out && !est_out && !codes_out) return WIFIRX_OK;
+    HIP_TRY(h, wr_launch_irs_despread(h->stream, &a));
+    if (!taps_out) return WIFIRX_OK;
+    // the taps of the TRUE elements under the decided phases: rule 27's kernel on the phases the decision pass wrote
+    wr::IrsMultiArgs t = a.m;
+    t.s.taps_out = reinterpret_cast<float2*>(taps_out);
+    t.s.psi = a.psi_out;
+    t.s.n_psi_sets = n_sets;
+    t.s.align_bits = 0;
+    t.s.codes_out = nullptr;
+    t.s.elems_out = nullptr;
+    HIP_TRY(h, wr_launch_irs_multi(h->stream, &t));
+    return WIFIRX_OK;
+}

@@ -624,7 +624,9 @@ class channel_model(grshim.sync_block):
     configuration's draws, made on the device and handed to wifirx_channel there.  ``taps`` must then stay at its default and
     ``doppler`` at None; ``set_psi`` loads another phase configuration, which holds from the next ``work()`` on.  With
     ``IrsConfig(codebook=...)`` every tap set is the winner of a beam-training sweep over the codebook (wifirx_irs_sweep,
-    NUMERICS.md rule 26), and ``irs_best`` holds the winning entries of the sets drawn so far.
+    NUMERICS.md rule 26), and ``irs_best`` holds the winning entries of the sets drawn so far.  With ``IrsConfig(pilots=...)``
+    every tap set is trained from a noisy pilot-based estimate of its own (wifirx_irs_estimate, NUMERICS.md rule 29), and
+    ``irs_codes`` holds the decided codes of the sets drawn so far.
 
     ``IrsConfig(antennas=M)``, M = 2..8, puts an AP of M antennas behind the surface (wifirx_irs_taps_multi /
     wifirx_irs_sweep_multi, NUMERICS.md rules 27 and 28): the block then has M output ports, port m the input through plane m of
@@ -648,6 +650,7 @@ class channel_model(grshim.sync_block):
         self._irs_sets = None                                    # device buffer of the surface's tap sets 0 .. _irs_n - 1
         self._irs_n = 0
         self._irs_best = None                                    # device buffer of the winning entries (codebook mode)
+        self._irs_codes = None                                   # device buffer of the decided codes (pilot mode)
         self.set_k_factor(k_factor)
         self.fade_seed = int(fade_seed) & 0xFFFFFFFFFFFFFFFF
         self.set_timing_offset(epsilon)
@@ -666,8 +669,8 @@ class channel_model(grshim.sync_block):
     # ---- the reflecting surface ----
     def set_psi(self, psi):
         """another phase configuration of the surface ([N] complex), from the next work() on"""
-        if self._irs is None or self._irs.align_bits or self._irs.codebook is not None:
-            raise ValueError("set_psi needs irs with given phases (align_bits = 0, no codebook)")
+        if self._irs is None or self._irs.align_bits or self._irs.codebook is not None or self._irs.pilots is not None:
+            raise ValueError("set_psi needs irs with given phases (align_bits = 0, no codebook, no pilots)")
         self._irs.set_psi(psi)
         self._irs_n = 0                                          # the sets are made again when they are next needed
 
@@ -682,7 +685,14 @@ class channel_model(grshim.sync_block):
             if self._irs_sets is not None:
                 self._irs_sets.free()
             self._irs_sets = self._rx.alloc(c.antennas * n * c.pdp.size * 8)
-            if c.codebook is not None:
+            if c.pilots is not None:                             # one call for one antenna and for several (rule 29)
+                if self._irs_codes is not None:
+                    self._irs_codes.free()
+                self._irs_codes = self._rx.alloc(n * c.pilots.shape[1])
+                self._rx.irs_estimate_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, pilots=c.pilots, group=c.group,
+                                          sigma=c.pilot_sigma, est_scale=c.est_scale, align_bits=c.pilot_bits, gain=c.gain,
+                                          k_factor=c.k_factor, direct_gain=c.direct_gain, seed=c.seed, codes_ptr=self._irs_codes)
+            elif c.codebook is not None:
                 if self._irs_best is not None:
                     self._irs_best.free()
                 self._irs_best = self._rx.alloc(n * 2)
@@ -704,6 +714,16 @@ class channel_model(grshim.sync_block):
         if self._irs_n == 0:
             return np.zeros(0, np.uint16)
         return self._irs_best.download(np.uint16, self._irs_n)
+
+    @property
+    def irs_codes(self):
+        """pilot mode: the codes decided for the tap sets drawn so far (uint8 [sets, G]; row s is set s)"""
+        if self._irs is None or self._irs.pilots is None:
+            raise ValueError("irs_codes needs irs with pilots")
+        G = self._irs.pilots.shape[1]
+        if self._irs_n == 0:
+            return np.zeros((0, G), np.uint8)
+        return self._irs_codes.download(np.uint8, self._irs_n * G).reshape(self._irs_n, G)
 
     def _irs_work(self, x, outs, n):
         """work() with the surface's taps: the chunk is cut where the set index changes, every piece one wifirx_channel call
@@ -831,6 +851,9 @@ class channel_model(grshim.sync_block):
         if self._irs_best is not None:
             self._irs_best.free()
             self._irs_best = None
+        if self._irs_codes is not None:
+            self._irs_codes.free()
+            self._irs_codes = None
         self._rx.close()
 
 

@@ -50,7 +50,7 @@ EXPORTS = [
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
     "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine", "wifirx_diversity_combine",
     "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi", "wifirx_irs_taps", "wifirx_irs_sweep",
-    "wifirx_irs_taps_multi", "wifirx_irs_sweep_multi",
+    "wifirx_irs_taps_multi", "wifirx_irs_sweep_multi", "wifirx_irs_estimate",
 ]
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
@@ -105,6 +105,7 @@ FADE_MAX_TAPS = 16                  # the most taps with fading
 IRS_MAX_ELEMS, IRS_MAX_TAPS = 4096, 16      # wifirx_irs_taps: the most surface elements and taps (NUMERICS.md rule 25)
 IRS_MAX_CODES = 1024                        # wifirx_irs_sweep: the most codebook entries (NUMERICS.md rule 26)
 IRS_MAX_ANT = 8                             # wifirx_irs_taps_multi / _sweep_multi: the most AP antennas (NUMERICS.md rule 27)
+IRS_MAX_PILOTS, IRS_MAX_GROUPS = 1024, 1023 # wifirx_irs_estimate: the most pilot slots and element groups (NUMERICS.md rule 29)
 
 
 def resampler_table() -> np.ndarray:
@@ -235,6 +236,9 @@ _lib.wifirx_irs_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32
                                   C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
 _lib.wifirx_irs_taps_multi.argtypes = _lib.wifirx_irs_taps.argtypes[:2] + [C.c_uint32] + _lib.wifirx_irs_taps.argtypes[2:]
 _lib.wifirx_irs_sweep_multi.argtypes = _lib.wifirx_irs_sweep.argtypes[:2] + [C.c_uint32] + _lib.wifirx_irs_sweep.argtypes[2:]
+_lib.wifirx_irs_estimate.argtypes = _lib.wifirx_irs_taps_multi.argtypes[:13] + [
+    C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+    C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.wifirx_resampler_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                   C.c_uint64, C.c_void_p, C.c_uint32]
@@ -905,6 +909,89 @@ class WifiRx:
             return {"taps": bufs["taps"].download(np.complex64, M * n_sets * L).reshape(M, n_sets, L),
                     "best": bufs["best"].download(np.uint16, n_sets),
                     "power": bufs["power"].download(np.float32, n_sets * K).reshape(n_sets, K)}
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    # -- the surface configured from noisy pilot observations (wifirx_irs_estimate; NUMERICS.md rule 29) --
+    def irs_estimate_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, pilots, n_pilots=None, n_groups=None,
+                         group=None, sigma=0.0, est_scale=None, align_bits=0, gain=1.0, k_factor=0.0, direct_gain=1.0,
+                         scatter=None, n_scatter=None, noise=None, n_noise=None, seed=0, est_ptr=None, codes_ptr=None,
+                         obs_ptr=None):
+        """wifirx_irs_estimate into device memory: the surface of irs_taps_multi_dev (M = len(los_b2r) antennas; a 1-D los_b2r
+        is one) stepped through the T pilot configurations `pilots`, observed in noise of standard deviation `sigma`, de-spread
+        into an estimate of the direct path and of every group's cascade coefficient, and configured with the B = align_bits
+        codes decided from that estimate.  The taps of the true channel under those codes go to taps_ptr as [M, n_sets, L]
+        (plane m is what channel_dev takes as taps=ptr), the estimate to est_ptr (complex64 [n_sets, M L, G + 1], column 0 the
+        direct path), the codes to codes_ptr (uint8 [n_sets, G]), the observations to obs_ptr (complex64 [n_sets, M L, T]).
+        Each is an int device pointer, a DevBuf or None; one at least, and taps / codes need align_bits 1..3.  pilots: a host
+        array [T, G] complex (irs.dft_pilots, irs.hadamard_pilots), or a device pointer with n_pilots=T and n_groups=G.
+        group: None (G = N) or uint16 [N] (irs.groups).  est_scale: kappa, default irs.est_scale(T) = 1 / T.  noise: None
+        (Philox draws keyed by `seed`) or a device pointer to n_noise rows of T complex64.  The other arguments as
+        irs_taps_multi_dev.  Asynchronous on the handle's stream."""
+        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
+        p, a, b, d = self._irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u)
+        if isinstance(pilots, (int, DevBuf)):
+            keep, pl_ptr, pl_dev, T, G = None, ptr(pilots), 1, int(n_pilots or 0), int(n_groups or 0)
+        else:
+            keep = np.ascontiguousarray(np.asarray(pilots, dtype=np.complex64))
+            if keep.ndim != 2:
+                raise ValueError("pilots must be [T, G]")
+            pl_ptr, pl_dev, (T, G) = _np_ptr(keep), 0, keep.shape
+        grp = None
+        if group is not None:
+            grp = np.ascontiguousarray(np.asarray(group, dtype=np.uint16).reshape(-1))
+            if grp.size != b.size:
+                raise ValueError("group must hold one value per element")
+        if scatter is not None and n_scatter is None:
+            raise ValueError("device scatter needs n_scatter")
+        if noise is not None and n_noise is None:
+            raise ValueError("device noise needs n_noise")
+        kappa = 1.0 / max(T, 1) if est_scale is None else float(est_scale)
+        self._check(_lib.wifirx_irs_estimate(self._h, ptr(taps_ptr), a.shape[0], int(n_sets), p.size, _np_ptr(p), float(gain),
+                                             b.size, _np_ptr(a), _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain),
+                                             pl_ptr, pl_dev, T, G, _np_ptr(grp), float(sigma), kappa, int(align_bits),
+                                             ptr(scatter), int(n_scatter or 0), ptr(noise), int(n_noise or 0),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(est_ptr), ptr(codes_ptr), ptr(obs_ptr)))
+
+    def irs_estimate(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, pilots, scatter=None, noise=None,
+                     want=("taps", "est", "codes", "obs"), **kw):
+        """irs_estimate_dev with host arrays: returns a dict with the outputs named in `want`: "taps" complex64 [M, n_sets, L],
+        "est" complex64 [n_sets, M L, G + 1], "codes" uint8 [n_sets, G], "obs" complex64 [n_sets, M L, T].  With align_bits = 0
+        "taps" and "codes" are left out.  pilots: a host array [T, G]; scatter: None or a host array [n_scatter, (M + 1) N + M];
+        noise: None or a host array [n_noise, T]."""
+        a = np.asarray(los_b2r)
+        n_sets, L, M, N = int(n_sets), np.asarray(pdp).size, (1 if a.ndim == 1 else a.shape[0]), a.shape[-1]
+        pl = np.asarray(pilots)
+        if pl.ndim != 2:
+            raise ValueError("pilots must be [T, G]")
+        T, G = pl.shape
+        R = M * L
+        want = [w for w in want if kw.get("align_bits", 0) or w in ("est", "obs")]
+        shapes = {"taps": (np.complex64, (M, n_sets, L)), "est": (np.complex64, (n_sets, R, G + 1)),
+                  "codes": (np.uint8, (n_sets, G)), "obs": (np.complex64, (n_sets, R, T))}
+        if not want or any(w not in shapes for w in want):
+            raise ValueError("want names taps, est, codes or obs; taps and codes need align_bits")
+        bufs = {}
+        try:
+            for w in want:
+                dt, sh = shapes[w]
+                bufs[w] = self.alloc(max(int(np.prod(sh)) * np.dtype(dt).itemsize, 8))
+            if scatter is not None:
+                s = np.ascontiguousarray(scatter, dtype=np.complex64)
+                if s.ndim != 2 or s.shape[1] != (M + 1) * N + M:
+                    raise ValueError("scatter must be [n_scatter, (M + 1) N + M]")
+                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
+                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
+            if noise is not None:
+                w = np.ascontiguousarray(noise, dtype=np.complex64)
+                if w.ndim != 2 or w.shape[1] != T:
+                    raise ValueError("noise must be [n_noise, T]")
+                bufs["noise"] = self.alloc(max(w.nbytes, 1)).upload(w)
+                kw.update(noise=bufs["noise"], n_noise=w.shape[0])
+            self.irs_estimate_dev(bufs.get("taps"), n_sets, pdp, los_b2r, los_r2u, los_b2u, pilots=pl, est_ptr=bufs.get("est"),
+                                  codes_ptr=bufs.get("codes"), obs_ptr=bufs.get("obs"), **kw)
+            return {w: bufs[w].download(shapes[w][0], int(np.prod(shapes[w][1]))).reshape(shapes[w][1]) for w in want}
         finally:
             for b in bufs.values():
                 b.free()

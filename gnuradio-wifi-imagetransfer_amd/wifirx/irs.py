@@ -1,6 +1,6 @@
-"""The host side of the reflecting-surface channel (wifirx_irs_taps, NUMERICS.md rule 25; wifirx_irs_sweep, rule 26): the
-line-of-sight geometry the calls take as input, fixed phase configurations and beam-training codebooks for them, and the
-configuration object of ``block.channel_model(irs=...)``.
+"""The host side of the reflecting-surface channel (wifirx_irs_taps, NUMERICS.md rule 25; wifirx_irs_sweep, rule 26;
+wifirx_irs_estimate, rule 29): the line-of-sight geometry the calls take as input, fixed phase configurations, beam-training
+codebooks, pilot configurations and element groups for them, and the configuration object of ``block.channel_model(irs=...)``.
 
 The model is the reference's (utils/SV_channel.py, utils/channel.py) for one AP antenna and one user: a square surface of
 S x S elements half a wavelength apart in the x-y plane, far-field steering vectors, H = H_B2R diag(psi) H_R2U + H_B2U.
@@ -157,6 +157,55 @@ def traverse_codebook(scale, interval, irs_pos, ap_pos, accuracy=10, freq=5e9, b
     return quantize(cb, bits) if bits else cb
 
 
+def dft_pilots(n_groups):
+    """The pilot configurations of a least-squares channel estimate (wifirx_irs_estimate, NUMERICS.md rule 29): T = G + 1 slots
+    for G groups, pilot[t][g] = exp(-2 pi i t (g + 1) / (G + 1)), columns 1..G of the (G + 1)-point DFT matrix (the reference's
+    Channel.DFT_matrix up to its 1 / sqrt(J)); column 0, the constant 1, is the direct path's and stays with the estimator.  The
+    columns are orthogonal: sum_t conj(p_j) p_j' = T delta.  Formed in float64 and rounded once.  complex64 [G + 1, G]."""
+    g = int(n_groups)
+    if not 1 <= g <= 1023:
+        raise ValueError("n_groups must be 1..1023")
+    t, j = np.arange(g + 1)[:, None], np.arange(1, g + 1)[None, :]
+    return np.exp(-2j * math.pi * ((t * j) % (g + 1)) / (g + 1)).astype(np.complex64)
+
+
+def hadamard_pilots(n_groups):
+    """Pilot configurations a 1-bit surface can realise: columns 1..G of the Sylvester-Hadamard matrix of order
+    T = 2^ceil(log2(G + 1)), entries +-1 (column 0, all ones, is the direct path's).  Orthogonal as :func:`dft_pilots`.
+    complex64 [T, G]."""
+    g = int(n_groups)
+    if not 1 <= g <= 1023:
+        raise ValueError("n_groups must be 1..1023")
+    t = 1 << g.bit_length()                                   # 2^ceil(log2(G + 1))
+    i, j = np.arange(t)[:, None], np.arange(1, g + 1)[None, :]
+    bits = i & j
+    par = np.zeros_like(bits)
+    while bits.any():
+        par ^= bits & 1
+        bits = bits >> 1
+    return (1.0 - 2.0 * par).astype(np.complex64)
+
+
+def groups(scale, c):
+    """The reference's clustering (clustered_SV_channel, cluster_cale = c): c x c neighbouring elements of the scale x scale
+    surface share one phase.  Element n = ix * scale + iy belongs to group (ix // c) * (scale // c) + iy // c; c must divide
+    scale.  uint16 [scale^2], with (scale // c)^2 groups."""
+    s, c = int(scale), int(c)
+    if s < 1 or c < 1 or s % c:
+        raise ValueError("c must divide scale")
+    ix, iy = np.divmod(np.arange(s * s), s)
+    return ((ix // c) * (s // c) + iy // c).astype(np.uint16)
+
+
+def est_scale(n_pilots, sigma=0.0, mmse=False):
+    """kappa of wifirx_irs_estimate as float32: 1 / T (least squares), or with mmse 1 / (T + sigma^2), the reference's
+    Channel.CH_est (1 / (1 + sigma2) behind unitary pilots) for coefficients of variance 1."""
+    t = int(n_pilots)
+    if t < 1:
+        raise ValueError("n_pilots must be >= 1")
+    return F32(1.0 / (t + float(sigma) ** 2)) if mmse else F32(1.0 / t)
+
+
 @dataclass
 class IrsConfig:
     """What ``block.channel_model(irs=...)`` needs to draw its taps from wifirx_irs_taps.  The surface is given either by its
@@ -165,7 +214,13 @@ class IrsConfig:
     trained per draw by wifirx_irs_sweep, NUMERICS.md rule 26; excludes the other two).  ``refresh``: the number of samples
     after which a new tap set is drawn (set index = stream time // refresh).  ``antennas`` = M (1..8): the AP is the array of
     ``los(antennas=M)`` (wifirx_irs_taps_multi / wifirx_irs_sweep_multi, NUMERICS.md rules 27 and 28); the line-of-sight
-    vectors are then [M, N], [N] and [M], and the block has M output ports.  M = 1 is the single-antenna surface."""
+    vectors are then [M, N], [N] and [M], and the block has M output ports.  M = 1 is the single-antenna surface.
+
+    ``pilots`` ([T, G] complex, T <= 1024, G <= min(N, 1023): :func:`dft_pilots`, :func:`hadamard_pilots`) trains the surface per
+    draw from noisy channel estimates instead (wifirx_irs_estimate, NUMERICS.md rule 29; excludes ``psi``, ``align_bits`` and
+    ``codebook``): the surface steps through the pilots, is observed in noise of standard deviation ``pilot_sigma``, and loads
+    the ``pilot_bits``-bit codes decided from the de-spread estimate.  ``group`` ([N] uint16, :func:`groups`; None: G = N) puts
+    several elements behind one phase; ``est_scale`` is the estimator's kappa (None: 1 / T, least squares)."""
     scale: int | None = None
     irs_pos: tuple | None = None
     ap_pos: tuple | None = None
@@ -183,6 +238,11 @@ class IrsConfig:
     refresh: int = 1 << 16
     codebook: np.ndarray | None = None
     antennas: int = 1
+    pilots: np.ndarray | None = None
+    pilot_sigma: float = 0.0
+    group: np.ndarray | None = None
+    pilot_bits: int = 2
+    est_scale: float | None = None
     n_elems: int = field(init=False, default=0)
 
     def __post_init__(self):
@@ -225,7 +285,31 @@ class IrsConfig:
         self.align_bits = int(self.align_bits)
         if self.align_bits not in (0, 1, 2, 3):
             raise ValueError("align_bits must be 0..3")
-        if self.codebook is not None:
+        if self.pilots is not None:
+            if self.psi is not None or self.align_bits or self.codebook is not None:
+                raise ValueError("pilots exclude psi, align_bits and codebook")
+            pl = np.ascontiguousarray(np.asarray(self.pilots, dtype=np.complex64))
+            if pl.ndim != 2 or not 1 <= pl.shape[0] <= 1024 or not 1 <= pl.shape[1] <= min(self.n_elems, 1023):
+                raise ValueError("pilots must be [T, G] with 1 <= T <= 1024 and 1 <= G <= min(N, 1023)")
+            if self.group is None:
+                if pl.shape[1] != self.n_elems:
+                    raise ValueError("without a group map the pilots hold one column per element")
+            else:
+                g = np.asarray(self.group).reshape(-1)
+                if g.size != self.n_elems or (g < 0).any() or (g >= pl.shape[1]).any():
+                    raise ValueError("group must hold one value below G per element")
+                self.group = np.ascontiguousarray(g.astype(np.uint16))
+            self.pilots, self.pilot_sigma, self.pilot_bits = pl, float(self.pilot_sigma), int(self.pilot_bits)
+            if not (math.isfinite(self.pilot_sigma) and self.pilot_sigma >= 0.0):
+                raise ValueError("pilot_sigma must be finite and not negative")
+            if self.pilot_bits not in (1, 2, 3):
+                raise ValueError("pilot_bits must be 1, 2 or 3")
+            self.est_scale = float(est_scale(pl.shape[0]) if self.est_scale is None else self.est_scale)
+            if not math.isfinite(self.est_scale):
+                raise ValueError("est_scale must be finite")
+        elif self.group is not None:
+            raise ValueError("group comes with pilots")
+        elif self.codebook is not None:
             if self.psi is not None or self.align_bits:
                 raise ValueError("codebook excludes psi and align_bits")
             cb = np.ascontiguousarray(np.asarray(self.codebook, dtype=np.complex64))

@@ -607,6 +607,53 @@ int  wifirx_irs_sweep_multi(wifirx_handle* h, float* taps_out, uint32_t n_ant, u
                             const float* scatter, uint32_t n_scatter, uint64_t irs_seed,
                             uint16_t* best_out, float* power_out);
 
+/* The surface configured as a real controller can: from noisy channel estimates, one observation per pilot configuration.  The
+ * reference's Channel.CH_est over Channel.DFT_matrix / genDFT pilots (utils/channel.py: H_est = y_rx Pilot^H / (1 + sigma2)), with
+ * clustered_SV_channel's grouping of elements behind one phase; arithmetic = NUMERICS.md rule 29.  The elements a_{m,n}, b_n, the
+ * direct path h_{d,m}, s_l and the cases k_factor = 0 and direct_gain = 0 are wifirx_irs_taps_multi's (the same irs_seed gives the
+ * same element bits, scatter rows of (M + 1) N + M); n_ant = 1 is the surface of wifirx_irs_taps.  Rows rho = m L + l, R = M L,
+ * T = n_pilots, G = n_groups, J = G + 1, e_{rho,n} = a_{m,n} b_n:
+ *     x_{rho,t}    = s_l (h_{d,rho} + y)        y = wifirx_irs_sweep's chain over e.re, e.im in ascending n against
+ *                                               pilot[t][group[n]]: the tap wifirx_irs_sweep_multi forms for entry t
+ *     obs_{rho,t}  = x + sigma w                w of variance 1 from words (x, y) of the Philox counter (t, r, rho, 3) keyed by
+ *                                               irs_seed (wifirx_channel's Box-Muller, h = sqrt(1/2)); sigma = 0: obs = x
+ *     ghat_{rho,j} = kappa sum_t obs_{rho,t} conj(p_{t,j})     p_{t,0} = 1 (the direct path), p_{t,g+1} = pilot[t][g]; per part
+ *                                               one fma chain from +0 over obs.re, obs.im in ascending t, filled with zero terms
+ *                                               up to a multiple of 4 (v_mfma_f32_16x16x4_f32), then one multiply by kappa
+ *     c_g          = wifirx_irs_taps' argmax on row 0 with the estimate: the c that maximises Re(conj(ghat_{0,0}) ghat_{0,g+1} C_c),
+ *                    the lowest c wins a tie, conj(ghat_{0,0}) -> 1 when both of its parts are zero and when direct_gain = 0
+ *                    (a blocked direct path has nothing to align to: the real axis, as there);  psi_n = C_{c_{group[n]}}
+ *     taps         = wifirx_irs_taps_multi of the TRUE elements with that psi given, bit for bit
+ * A joint decision over antennas and taps, an estimate of noise_sigma, per-antenna noise weights, pilots carried through the
+ * TX -> channel -> demod chain and more than 1023 groups are not offered.
+ *   taps_out     DEVICE complex64 [n_ant][n_sets][n_taps] (8-byte aligned) or NULL: antenna-major as wifirx_irs_taps_multi's.
+ *   pilot        complex64 [n_pilots][n_groups], HOST or (pilot_on_device) DEVICE; 1 <= n_pilots <= 1024, 1 <= n_groups <=
+ *                min(N, 1023).  Any complex value is taken (Python: wifirx.irs.dft_pilots, hadamard_pilots).
+ *   group        HOST uint16 [N], every value < n_groups: the group of element n (Python: wifirx.irs.groups); NULL is the
+ *                identity and needs n_groups = N.
+ *   noise_sigma  sigma >= 0.  est_scale: kappa, any finite value; 1 / T is least squares, 1 / (T + sigma^2) the reference's MMSE
+ *                for coefficients of variance 1 (Python: wifirx.irs.est_scale).
+ *   align_bits   B in {1, 2, 3}, or 0 when neither taps_out nor codes_out is given (nothing is decided).
+ *   noise        NULL, or DEVICE complex64 [n_noise][n_pilots]: the pair (r, rho) reads row (r R + rho) % n_noise as w and
+ *                nothing is drawn; sigma still scales it.
+ *   est_out      DEVICE complex64 [n_sets][R][n_groups + 1] or NULL: ghat.   codes_out  DEVICE uint8 [n_sets][n_groups] or NULL.
+ *   obs_out      DEVICE complex64 [n_sets][R][n_pilots] or NULL: obs.  Without it the observations live in a scratch of the handle.
+ *   the other arguments   as wifirx_irs_taps_multi.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for every case of wifirx_irs_taps_multi for the shared arguments, a
+ * NULL pilot, n_pilots outside 1..1024, n_groups outside 1..min(N, 1023), a NULL group with n_groups != N, a group value >=
+ * n_groups, a negative or non-finite noise_sigma, a non-finite est_scale, n_noise = 0 with noise, align_bits > 3, taps_out or
+ * codes_out with align_bits = 0, all four outputs NULL, and misaligned pointers (complex64: 8 bytes, float32: 4, uint16: 2);
+ * WIFIRX_ERANGE for more than 2^31 - 1 sets or tiles of 16 rows.  n_sets = 0 does nothing and returns WIFIRX_OK.  At most three
+ * kernel launches per call, after one upload of the host arrays.  ORDER: as wifirx_channel. */
+int  wifirx_irs_estimate(wifirx_handle* h, float* taps_out, uint32_t n_ant, uint32_t n_sets, uint32_t n_taps,
+                         const float* pdp, float gain, uint32_t n_elems,
+                         const float* los_b2r, const float* los_r2u, const float* los_b2u, float k_factor, float direct_gain,
+                         const float* pilot, int pilot_on_device, uint32_t n_pilots, uint32_t n_groups, const uint16_t* group,
+                         float noise_sigma, float est_scale, uint32_t align_bits,
+                         const float* scatter, uint32_t n_scatter, const float* noise, uint32_t n_noise, uint64_t irs_seed,
+                         float* est_out   /* [n_sets][R][n_groups+1] complex64 */, uint8_t* codes_out /* [n_sets][n_groups] */,
+                         float* obs_out   /* [n_sets][R][n_pilots] complex64 */);
+
 /* ieee802_11.mac (gnu_radio/IRS_user.py:192,204-205; IRS_tranceiver.py:271,313-314) for a batch: PSDU i, at
  * psdu + i * psdu_stride, is the 24 + payload_len[i] + 4 bytes
  *     08 00 | 00 00 | addr1 = dst | addr2 = src | addr3 = bss | ((seq0 + i) & 0xFFF) << 4, little endian | payload i | FCS

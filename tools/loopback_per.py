@@ -62,12 +62,14 @@ the combiner) and mode.  The counts nest: A antennas are the first A of the larg
 
 --irs: the link over a reflecting surface of N elements with B-bit phases (wifirx_irs_taps, NUMERICS.md rule 25): one tap set of 8
 taps per frame, made on the device and read there by wifirx_channel; FER against the surface size at SNRs of one unit-power path.
---irs-mode: random phases, the one configuration aligned to the geometry, the genie aligned per draw, or `sweep`: a surface
+--irs-mode: random phases, the one configuration aligned to the geometry, the genie aligned per draw, `estimate`: a surface
+trained per draw from a noisy pilot-based channel estimate (wifirx_irs_estimate; --irs-pilots, --pilot-snr-db, --irs-group), or `sweep`: a surface
 trained per draw by a codebook sweep (wifirx_irs_sweep, rule 26; --irs-codebook dft / dft2 / traverse, quantised to --irs-bits).
 --irs 0 is the direct path alone.
 
     python tools/loopback_per.py --irs 0 16 64 256 --irs-bits 2 --irs-mode random los genie --k-factor 3 --direct-db -inf --psdu-len 294 --encoding 2 --snr -20 -10 0 [--frames 65536] [--out profiles/loopback_irs.json]
-    python tools/loopback_per.py --irs 64 256 --irs-bits 2 --irs-mode random los genie sweep --irs-codebook dft2 --k-factor 3 --psdu-len 294 --encoding 2 --snr -30 -20 -10 [--out profiles/loopback_irs_sweep.json]"""
+    python tools/loopback_per.py --irs 64 256 --irs-bits 2 --irs-mode random los genie sweep --irs-codebook dft2 --k-factor 3 --psdu-len 294 --encoding 2 --snr -30 -20 -10 [--out profiles/loopback_irs_sweep.json]
+    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode random sweep estimate genie --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_estimate.json]"""
 import argparse
 import json
 import math
@@ -141,9 +143,14 @@ def main():
                     help="with --antennas: the combiner's modes (default both)")
     ap.add_argument("--irs", type=int, nargs="+", default=None, help="a reflecting surface of these many elements (squares; 0 = the direct path alone)")
     ap.add_argument("--irs-bits", type=int, default=2, choices=(1, 2, 3), help="with --irs: the phase resolution")
-    ap.add_argument("--irs-mode", nargs="+", choices=("random", "los", "genie", "sweep"), default=["genie"],
-                    help="with --irs: random phases, the one configuration aligned to the geometry, aligned per draw, or trained "
-                         "per draw by a codebook sweep (wifirx_irs_sweep)")
+    ap.add_argument("--irs-mode", nargs="+", choices=("random", "los", "genie", "sweep", "estimate"), default=["genie"],
+                    help="with --irs: random phases, the one configuration aligned to the geometry, aligned per draw, trained "
+                         "per draw by a codebook sweep (wifirx_irs_sweep), or trained per draw from a noisy pilot-based channel "
+                         "estimate (wifirx_irs_estimate)")
+    ap.add_argument("--irs-pilots", choices=("dft", "hadamard"), default="dft", help="with --irs-mode estimate: irs.dft_pilots or irs.hadamard_pilots")
+    ap.add_argument("--pilot-snr-db", type=float, default=0.0,
+                    help="with --irs-mode estimate: the SNR of one unit-power path in one pilot observation (sigma = 10^(-dB / 20))")
+    ap.add_argument("--irs-group", type=int, default=1, help="with --irs-mode estimate: c x c elements behind one phase (irs.groups)")
     ap.add_argument("--irs-codebook", choices=("dft", "dft2", "traverse"), default="dft2",
                     help="with --irs-mode sweep: irs.dft_codebook at over = 1 / 2, or the reference controller's 10 x 10 grid "
                          "(irs.traverse_codebook), quantised to --irs-bits")
@@ -529,6 +536,21 @@ def fading_main(a):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def estimate_keywords(a, S):
+    """--irs-mode estimate: the keywords of irs_estimate_dev for an S x S surface, and what the result file says about them"""
+    from wifirx import irs
+    c = a.irs_group
+    if c < 1 or S % c:
+        raise SystemExit("--irs-group must divide the surface's side")
+    G = (S // c) ** 2
+    if G > capi.IRS_MAX_GROUPS:
+        raise SystemExit("--irs-mode estimate takes at most %d groups: a larger --irs-group" % capi.IRS_MAX_GROUPS)
+    pl = irs.dft_pilots(G) if a.irs_pilots == "dft" else irs.hadamard_pilots(G)
+    sigma = 10 ** (-a.pilot_snr_db / 20)
+    kw = dict(pilots=pl, group=None if c == 1 else irs.groups(S, c), sigma=sigma, est_scale=irs.est_scale(pl.shape[0]), align_bits=a.irs_bits)
+    return kw, {"pilots": a.irs_pilots, "slots": int(pl.shape[0]), "groups": G, "sigma": sigma, "est_scale": float(kw["est_scale"])}
+
+
 def irs_main(a):
     if a.rates or a.host_stats or a.locked_clock or a.doppler is not None:
         raise SystemExit("--irs stands alone: not with --rates, --host-stats, --locked-clock or --doppler")
@@ -569,7 +591,10 @@ def irs_main(a):
         for mode in (a.irs_mode if N else ["none"]):
             kw = dict(k_factor=a.k_factor, direct_gain=direct_gain if N else (direct_gain or 1.0), seed=(a.seed << 32) + N)
             winners = None
-            if mode == "sweep":
+            if mode == "estimate":
+                est_kw, winners = estimate_keywords(a, S)
+                kw.update(est_kw)
+            elif mode == "sweep":
                 if a.irs_codebook == "traverse":
                     kw["codebook"] = irs.traverse_codebook(S, 0.03, irs_pos, ap_pos, accuracy=10, bits=bits)
                 else:
@@ -583,7 +608,9 @@ def irs_main(a):
             else:
                 kw["psi"] = np.zeros(1, np.complex64)
             # one tap set per frame, made on the device and read there by the channel
-            if mode == "sweep":
+            if mode == "estimate":
+                rx.irs_estimate_dev(d_taps, n, pdp, b2r, r2u, b2u, **kw)
+            elif mode == "sweep":
                 rx.irs_sweep_dev(d_taps, n, pdp, b2r, r2u, b2u, best_ptr=d_best, **kw)
                 hist = np.bincount(d_best.download(np.uint16, n), minlength=kw["codebook"].shape[0])
                 winners = {"entries": int(kw["codebook"].shape[0]), "distinct": int((hist > 0).sum()),
@@ -602,7 +629,7 @@ def irs_main(a):
                                "mean_channel_power": mean_power, "seconds": time.perf_counter() - t0,
                                "counts": {k: r[k] for k in COUNTERS}})
                 if winners is not None:
-                    points[-1]["winners"] = winners
+                    points[-1]["training" if mode == "estimate" else "winners"] = winners
                 print(json.dumps({k: points[-1][k] for k in ("n_elems", "mode", "snr_db", "fer", "mean_channel_power")}), file=sys.stderr)
     seconds_total = time.perf_counter() - t_all
     rx.free_out(ref)
@@ -616,7 +643,10 @@ def irs_main(a):
            "modes": {"random": "one random configuration", "los": "the one configuration aligned to the geometry (irs.align)",
                      "genie": "aligned per draw on tap 0 (align_bits)",
                      "sweep": "trained per draw: the best entry of the %s codebook, quantised to the same bits (wifirx_irs_sweep, "
-                              "NUMERICS.md rule 26); 'winners' holds the histogram of the winning entries" % a.irs_codebook},
+                              "NUMERICS.md rule 26); 'winners' holds the histogram of the winning entries" % a.irs_codebook,
+                     "estimate": "trained per draw from a noisy pilot-based estimate of the direct path and of every group's cascade "
+                                 "coefficient (wifirx_irs_estimate, NUMERICS.md rule 29); 'training' holds the pilots, the groups and "
+                                 "the noise of one pilot observation"},
            "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
@@ -642,9 +672,10 @@ def irs_multi_main(a):
     for N in a.irs:
         if N < 1 or N > capi.IRS_MAX_ELEMS or int(round(N ** 0.5)) ** 2 != N:
             raise SystemExit("--irs with --antennas takes square surfaces of 1 .. 4096 elements")
-    modes = [m for m in a.irs_mode if m in ("random", "genie", "sweep")]
+    modes = [m for m in a.irs_mode if m in ("random", "genie", "sweep", "estimate")]
     if len(modes) != len(a.irs_mode):
-        raise SystemExit("--irs with --antennas: --irs-mode random, genie (on antenna 0) or sweep (on the MRC metric)")
+        raise SystemExit("--irs with --antennas: --irs-mode random, genie (on antenna 0), sweep (on the MRC metric) or estimate "
+                         "(decided on antenna 0)")
     if a.irs_codebook == "traverse":
         raise SystemExit("--irs with --antennas: --irs-codebook dft or dft2")
     direct_gain = 0.0 if a.direct_db == float("-inf") else 10 ** (a.direct_db / 20)
@@ -675,7 +706,10 @@ def irs_multi_main(a):
             for mode in modes:
                 kw = dict(k_factor=a.k_factor, direct_gain=direct_gain, seed=(a.seed << 32) + N)       # irs_main's seeds
                 winners = None
-                if mode == "sweep":
+                if mode == "estimate":
+                    est_kw, winners = estimate_keywords(a, S)
+                    rx.irs_estimate_dev(d_taps, n, pdp, b2r, r2u, b2u, **est_kw, **kw)
+                elif mode == "sweep":
                     kw["codebook"] = irs.dft_codebook(S, b2r[0], over=min(2 if a.irs_codebook == "dft2" else 1, max(1, 32 // S)), bits=bits)
                     rx.irs_sweep_multi_dev(d_taps, n, pdp, b2r, r2u, b2u, best_ptr=d_best, **kw)
                     hist = np.bincount(d_best.download(np.uint16, n), minlength=kw["codebook"].shape[0])
@@ -707,7 +741,7 @@ def irs_multi_main(a):
                                    "mean_channel_power_per_antenna": [float(v) for v in power], "seconds": time.perf_counter() - t0,
                                    "counts": {c: hard[c] for c in COUNTERS}, "counts_soft": {c: soft[c] for c in COUNTERS}})
                     if winners is not None:
-                        points[-1]["winners"] = winners
+                        points[-1]["training" if mode == "estimate" else "winners"] = winners
                     print(json.dumps({c: points[-1][c] for c in ("n_elems", "antennas", "mode", "snr_db", "fer", "fer_soft",
                                                                  "mean_combined_channel_power")}), file=sys.stderr)
     seconds_total = time.perf_counter() - t_all
@@ -724,7 +758,9 @@ def irs_multi_main(a):
            "snr": "of one unit-power path at one antenna; every antenna has noise of variance 1 from a seed of its own",
            "modes": {"random": "one random configuration", "genie": "aligned per draw on antenna 0, tap 0 (align_bits)",
                      "sweep": "trained per draw on the sum of the antennas' channel powers: the best entry of the %s codebook, quantised to "
-                              "the same bits (wifirx_irs_sweep_multi, NUMERICS.md rule 28)" % a.irs_codebook},
+                              "the same bits (wifirx_irs_sweep_multi, NUMERICS.md rule 28)" % a.irs_codebook,
+                     "estimate": "trained per draw from a noisy pilot-based estimate, the codes decided on antenna 0, tap 0 "
+                                 "(wifirx_irs_estimate, NUMERICS.md rule 29)"},
            "antennas": counts, "stats": "wifirx_link_stats on the device; reported, not asserted",
            "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
