@@ -30,6 +30,7 @@
 #include "wr_irs_sweep.h"
 #include "wr_irs_multi.h"
 #include "wr_irs_estimate.h"
+#include "wr_irs_optimize.h"
 #include "wr_link.h"
 #include "wr_convert.h"
 #include "wr_channelizer.h"

@@ -414,3 +414,63 @@ extern "C" int wifirx_irs_estimate(wifirx_handle* h, float* taps_out, uint32_t n
     HIP_TRY(h, wr_launch_irs_multi(h->stream, &t));
     return WIFIRX_OK;
 }
+
+// ---- the joint phase decision over antennas and taps (wr_irs_optimize.hip, NUMERICS.md rule 30) ----
+
+extern "C" int wifirx_irs_optimize(wifirx_handle* h, const float* coef, uint32_t n_sets, uint32_t n_rows, uint32_t n_cols,
+                                   uint32_t bits, uint32_t max_sweeps, int start, int direct_blocked, const uint8_t* codes_in,
+                                   uint32_t n_elems, const uint16_t* group,
+                                   uint8_t* codes_out, float* psi_out, float* power_out, uint8_t* sweeps_out)
+{
+    if (!h) return WIFIRX_EINVAL;
+    // ---- the argument checks, before anything is queued ----
+    if (!coef) return fail(h, WIFIRX_EINVAL, "coef is required");
+    if (!codes_out && !psi_out) return fail(h, WIFIRX_EINVAL, "one of codes_out and psi_out is required");
+    if (n_rows < 1 || n_rows > wr_irs_max_rows()) return fail(h, WIFIRX_EINVAL, "n_rows must be 1..128");
+    if (n_cols < 2 || n_cols > wr_irs_max_groups() + 1) return fail(h, WIFIRX_EINVAL, "n_cols must be 2..1024");
+    if (bits < 1 || bits > 3) return fail(h, WIFIRX_EINVAL, "bits must be 1..3");
+    if (max_sweeps > wr_irs_max_sweeps()) return fail(h, WIFIRX_EINVAL, "max_sweeps must be 0..16");
+    if (start != WIFIRX_IRS_START_REF && start != WIFIRX_IRS_START_GIVEN && start != WIFIRX_IRS_START_ZERO)
+        return fail(h, WIFIRX_EINVAL, "start must be WIFIRX_IRS_START_REF, _GIVEN or _ZERO");
+    if (start == WIFIRX_IRS_START_GIVEN && !codes_in) return fail(h, WIFIRX_EINVAL, "codes_in is required with WIFIRX_IRS_START_GIVEN");
+    const uint32_t n_groups = n_cols - 1;
+    if (psi_out) {
+        if (n_elems < 1 || n_elems > wr_irs_max_elems()) return fail(h, WIFIRX_EINVAL, "n_elems must be 1..4096 with psi_out");
+        if (!group && n_elems != n_groups) return fail(h, WIFIRX_EINVAL, "group is required when n_elems differs from n_cols - 1");
+    }
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((addr(coef) | addr(psi_out)) & 7) return fail(h, WIFIRX_EINVAL, "coef and psi_out must be 8-byte aligned (complex64)");
+    if (addr(power_out) & 3) return fail(h, WIFIRX_EINVAL, "power_out must be 4-byte aligned (float32)");
+    if (psi_out && (addr(group) & 1)) return fail(h, WIFIRX_EINVAL, "group must be 2-byte aligned (uint16)");
+    if (psi_out && group)
+        for (uint32_t n = 0; n < n_elems; n++)
+            if (group[n] >= n_groups) return fail(h, WIFIRX_EINVAL, "a group value is not below n_cols - 1");
+    if (n_sets == 0) return WIFIRX_OK;
+    if (n_sets > 0x7fffffffu) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 sets");
+
+    stream_worker_wait_idle(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    wr::IrsOptimizeArgs a{};
+    if (psi_out && group) {                             // the one upload: the group map, as wifirx_irs_estimate sends it
+        IrsMeta up;
+        int rc;
+        up.add(&a.group, group, 2ull * n_elems);
+        if ((rc = up.send(h))) return rc;
+    }
+    a.coef = reinterpret_cast<const float2*>(coef);
+    a.codes_in = start == WIFIRX_IRS_START_GIVEN ? codes_in : nullptr;
+    a.codes_out = codes_out;
+    a.psi_out = reinterpret_cast<float2*>(psi_out);
+    a.power_out = power_out;
+    a.sweeps_out = sweeps_out;
+    a.n_sets = n_sets;
+    a.n_rows = n_rows;
+    a.n_cols = n_cols;
+    a.n_elems = psi_out ? n_elems : 0;
+    a.bits = bits;
+    a.max_sweeps = max_sweeps;
+    a.start = (uint32_t)start;
+    a.blocked = direct_blocked != 0;
+    HIP_TRY(h, wr_launch_irs_optimize(h->stream, &a));
+    return WIFIRX_OK;
+}

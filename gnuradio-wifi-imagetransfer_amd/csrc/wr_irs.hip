@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "wr_irs_elem.h"   // irs_elem, irs_direct, irs_mix: shared with wr_irs_sweep.hip
+#include "wr_irs_elem.h"   // irs_elem, irs_direct, irs_mix: shared with wr_irs_sweep.hip; irs_argmax, irs_butterfly: with wr_irs_optimize.hip
 
 namespace wr {
 
@@ -45,12 +45,7 @@ void irs_kernel(const IrsArgs a)
             const IrsElem e = irs_elem(a, r, 0, n, key);
             float2 g = ch_mul(e.a, e.b);
             if (!axis) g = ch_mul(hc, g);
-            uint32_t best = 0;
-            float top = ch_mul(g, irs_phase[0]).x;
-            for (uint32_t c = 1; c < n_codes; c++) {
-                const float m = ch_mul(g, irs_phase[c << up]).x;
-                if (m > top) { top = m; best = c; }        // the lowest c wins a tie
-            }
+            const uint32_t best = irs_argmax(g, irs_phase, n_codes, up);
             codes[n] = (uint8_t)best;
             if (a.codes_out) a.codes_out[(uint64_t)r * N + n] = (uint8_t)best;
         }
@@ -73,11 +68,7 @@ void irs_kernel(const IrsArgs a)
             const float2 p = ch_mul(ch_mul(e.a, ph), e.b);
             acc = n == lane ? p : ch_add(acc, p);           // ascending n, from the lane's first product
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {                 // symmetric: every lane ends with the same bits
-            const float ox = __shfl_xor(acc.x, m), oy = __shfl_xor(acc.y, m);
-            acc = make_float2(acc.x + ox, acc.y + oy);
-        }
+        acc = irs_butterfly(acc);                           // symmetric: every lane ends with the same bits
         const float2 h = ch_add(irs_direct(a, r, l, key), acc);
         const float s = a.scale[l];
         if (lane == 0) a.taps_out[(uint64_t)r * L + l] = make_float2(h.x * s, h.y * s);

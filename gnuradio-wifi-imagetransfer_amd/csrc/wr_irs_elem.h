@@ -63,4 +63,29 @@ __device__ __forceinline__ float2 irs_direct(const IrsArgs& a, uint32_t r, uint3
     return make_float2(a.direct_gain * v.x, a.direct_gain * v.y);
 }
 
+// rule 25's argmax: the code c of n_codes that maximises Re(g C_{c << up}), `phase` the table of the C_k.  Ascending c and a strict
+// `>`: the lowest c wins a tie, and a NaN never replaces the running maximum.  One text for wr_irs.hip and wr_irs_optimize.hip
+__device__ __forceinline__ uint32_t irs_argmax(float2 g, const float2* phase, uint32_t n_codes, uint32_t up)
+{
+    uint32_t best = 0;
+    float top = ch_mul(g, phase[0]).x;
+    for (uint32_t c = 1; c < n_codes; c++) {
+        const float m = ch_mul(g, phase[c << up]).x;
+        if (m > top) { top = m; best = c; }            // the lowest c wins a tie
+    }
+    return best;
+}
+
+// rule 25's fold of the 64 lanes' partial sums: lane xor 32, 16, 8, 4, 2, 1, each part apart (no LDS, no barrier).  Symmetric:
+// every lane ends with the same bits
+__device__ __forceinline__ float2 irs_butterfly(float2 acc)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ox = __shfl_xor(acc.x, m), oy = __shfl_xor(acc.y, m);
+        acc = make_float2(acc.x + ox, acc.y + oy);
+    }
+    return acc;
+}
+
 }  // namespace wr

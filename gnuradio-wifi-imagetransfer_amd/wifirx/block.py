@@ -626,7 +626,8 @@ class channel_model(grshim.sync_block):
     ``IrsConfig(codebook=...)`` every tap set is the winner of a beam-training sweep over the codebook (wifirx_irs_sweep,
     NUMERICS.md rule 26), and ``irs_best`` holds the winning entries of the sets drawn so far.  With ``IrsConfig(pilots=...)``
     every tap set is trained from a noisy pilot-based estimate of its own (wifirx_irs_estimate, NUMERICS.md rule 29), and
-    ``irs_codes`` holds the decided codes of the sets drawn so far.
+    ``irs_codes`` holds the decided codes of the sets drawn so far.  ``IrsConfig(pilots=..., decision="joint")`` decides them over
+    every antenna and tap (wifirx_irs_estimate -> wifirx_irs_optimize -> wifirx_irs_taps_multi on one stream, NUMERICS.md rule 30).
 
     ``IrsConfig(antennas=M)``, M = 2..8, puts an AP of M antennas behind the surface (wifirx_irs_taps_multi /
     wifirx_irs_sweep_multi, NUMERICS.md rules 27 and 28): the block then has M output ports, port m the input through plane m of
@@ -689,9 +690,27 @@ class channel_model(grshim.sync_block):
                 if self._irs_codes is not None:
                     self._irs_codes.free()
                 self._irs_codes = self._rx.alloc(n * c.pilots.shape[1])
-                self._rx.irs_estimate_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, pilots=c.pilots, group=c.group,
-                                          sigma=c.pilot_sigma, est_scale=c.est_scale, align_bits=c.pilot_bits, gain=c.gain,
-                                          k_factor=c.k_factor, direct_gain=c.direct_gain, seed=c.seed, codes_ptr=self._irs_codes)
+                scene = dict(gain=c.gain, k_factor=c.k_factor, direct_gain=c.direct_gain, seed=c.seed)
+                est = dict(pilots=c.pilots, group=c.group, sigma=c.pilot_sigma, est_scale=c.est_scale, **scene)
+                if c.decision == "joint":
+                    # estimate -> joint decision -> taps of the true elements, on one stream (NUMERICS.md rule 30); the two
+                    # scratch buffers are freed behind the handle's sync
+                    R, J = c.antennas * c.pdp.size, c.pilots.shape[1] + 1
+                    coef, psi = self._rx.alloc(n * R * J * 8), self._rx.alloc(n * c.n_elems * 8)
+                    try:
+                        self._rx.irs_estimate_dev(None, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, est_ptr=coef, **est)
+                        self._rx.irs_optimize_dev(coef, n, R, J, bits=c.pilot_bits, max_sweeps=c.sweeps, start="ref",
+                                                  direct_blocked=c.direct_gain == 0.0, n_elems=c.n_elems, group=c.group,
+                                                  codes_ptr=self._irs_codes, psi_ptr=psi)
+                        self._rx.irs_taps_multi_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, psi=psi,
+                                                    n_psi_sets=n, **scene)
+                        self._rx.sync()
+                    finally:
+                        coef.free()
+                        psi.free()
+                else:
+                    self._rx.irs_estimate_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, align_bits=c.pilot_bits,
+                                              codes_ptr=self._irs_codes, **est)
             elif c.codebook is not None:
                 if self._irs_best is not None:
                     self._irs_best.free()

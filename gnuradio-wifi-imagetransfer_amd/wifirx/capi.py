@@ -50,7 +50,7 @@ EXPORTS = [
     "wifirx_iq_to_f32", "wifirx_iq_from_f32", "wifirx_push_iq",
     "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine", "wifirx_diversity_combine",
     "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi", "wifirx_irs_taps", "wifirx_irs_sweep",
-    "wifirx_irs_taps_multi", "wifirx_irs_sweep_multi", "wifirx_irs_estimate",
+    "wifirx_irs_taps_multi", "wifirx_irs_sweep_multi", "wifirx_irs_estimate", "wifirx_irs_optimize",
 ]
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
@@ -106,6 +106,9 @@ IRS_MAX_ELEMS, IRS_MAX_TAPS = 4096, 16      # wifirx_irs_taps: the most surface 
 IRS_MAX_CODES = 1024                        # wifirx_irs_sweep: the most codebook entries (NUMERICS.md rule 26)
 IRS_MAX_ANT = 8                             # wifirx_irs_taps_multi / _sweep_multi: the most AP antennas (NUMERICS.md rule 27)
 IRS_MAX_PILOTS, IRS_MAX_GROUPS = 1024, 1023 # wifirx_irs_estimate: the most pilot slots and element groups (NUMERICS.md rule 29)
+IRS_MAX_ROWS, IRS_MAX_SWEEPS = 128, 16      # wifirx_irs_optimize: the most rows of a set and sweeps (NUMERICS.md rule 30)
+IRS_START_REF, IRS_START_GIVEN, IRS_START_ZERO = 0, 1, 2    # WIFIRX_IRS_START_*
+IRS_STARTS = {"ref": IRS_START_REF, "given": IRS_START_GIVEN, "zero": IRS_START_ZERO}
 
 
 def resampler_table() -> np.ndarray:
@@ -239,6 +242,8 @@ _lib.wifirx_irs_sweep_multi.argtypes = _lib.wifirx_irs_sweep.argtypes[:2] + [C.c
 _lib.wifirx_irs_estimate.argtypes = _lib.wifirx_irs_taps_multi.argtypes[:13] + [
     C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
     C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.wifirx_irs_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.wifirx_resampler_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                   C.c_uint64, C.c_void_p, C.c_uint32]
@@ -991,6 +996,69 @@ class WifiRx:
                 kw.update(noise=bufs["noise"], n_noise=w.shape[0])
             self.irs_estimate_dev(bufs.get("taps"), n_sets, pdp, los_b2r, los_r2u, los_b2u, pilots=pl, est_ptr=bufs.get("est"),
                                   codes_ptr=bufs.get("codes"), obs_ptr=bufs.get("obs"), **kw)
+            return {w: bufs[w].download(shapes[w][0], int(np.prod(shapes[w][1]))).reshape(shapes[w][1]) for w in want}
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    # -- the joint phase decision over antennas and taps (wifirx_irs_optimize; NUMERICS.md rule 30) --
+    def irs_optimize_dev(self, coef_ptr, n_sets, n_rows, n_cols, *, bits=2, max_sweeps=4, start="ref", direct_blocked=False,
+                         codes_in=None, n_elems=None, group=None, codes_ptr=None, psi_ptr=None, power_ptr=None, sweeps_ptr=None):
+        """wifirx_irs_optimize on device memory: cyclic coordinate ascent on the power an MRC receiver collects, over the
+        B = bits codes of the G = n_cols - 1 groups, on the coefficient matrix at coef_ptr (complex64 [n_sets, n_rows, n_cols]
+        in the layout of irs_estimate_dev's est_ptr: column 0 the direct term, column g + 1 group g).  start: "ref" (the
+        decision of irs_estimate_dev, row 0 alone), "given" (codes_in, a device pointer to uint8 [n_sets, G]) or "zero".
+        direct_blocked: the direct path is blocked (direct_gain = 0), column 0 is not read.  The final codes go to codes_ptr
+        (uint8 [n_sets, G]), their phases to psi_ptr (complex64 [n_sets, N], N = n_elems, through `group`: None = the identity,
+        N = G; irs_taps_multi_dev reads them as psi=ptr, n_psi_sets=n_sets), the collected power behind the start and behind
+        every sweep to power_ptr (float32 [n_sets, max_sweeps + 1]), the number of sweeps that changed a code to sweeps_ptr
+        (uint8 [n_sets]).  Each is an int device pointer, a DevBuf or None; codes_ptr or psi_ptr at least.  Asynchronous on the
+        handle's stream."""
+        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
+        if start not in IRS_STARTS:
+            raise ValueError("start must be ref, given or zero")
+        grp = None
+        if group is not None:
+            grp = np.ascontiguousarray(np.asarray(group, dtype=np.uint16).reshape(-1))
+            if n_elems is not None and grp.size != int(n_elems):
+                raise ValueError("group must hold one value per element")
+        N = int(n_elems) if n_elems is not None else (grp.size if grp is not None else int(n_cols) - 1)
+        self._check(_lib.wifirx_irs_optimize(self._h, ptr(coef_ptr), int(n_sets), int(n_rows), int(n_cols), int(bits),
+                                             int(max_sweeps), IRS_STARTS[start], int(bool(direct_blocked)), ptr(codes_in), N,
+                                             _np_ptr(grp), ptr(codes_ptr), ptr(psi_ptr), ptr(power_ptr), ptr(sweeps_ptr)))
+
+    def irs_optimize(self, coef, *, bits=2, max_sweeps=4, start="ref", direct_blocked=False, codes_in=None, group=None,
+                     n_elems=None, want=("codes", "psi", "power", "sweeps")):
+        """irs_optimize_dev with host arrays: coef complex64 [n_sets, R, J] (or [R, J]: one set), codes_in uint8 [n_sets, G]
+        with start="given".  Returns a dict with the outputs named in `want`: "codes" uint8 [n_sets, G], "psi" complex64
+        [n_sets, N], "power" float32 [n_sets, max_sweeps + 1], "sweeps" uint8 [n_sets]; codes or psi at least."""
+        q = np.asarray(coef, dtype=np.complex64)
+        q = np.ascontiguousarray(q[None] if q.ndim == 2 else q)
+        if q.ndim != 3:
+            raise ValueError("coef must be [n_sets, R, J]")
+        n_sets, R, J = q.shape
+        G = J - 1
+        N = int(n_elems) if n_elems is not None else (np.asarray(group).size if group is not None else G)
+        shapes = {"codes": (np.uint8, (n_sets, G)), "psi": (np.complex64, (n_sets, N)),
+                  "power": (np.float32, (n_sets, int(max_sweeps) + 1)), "sweeps": (np.uint8, (n_sets,))}
+        want = list(want)
+        if any(w not in shapes for w in want) or not ("codes" in want or "psi" in want):
+            raise ValueError("want names codes, psi, power or sweeps; codes or psi at least")
+        bufs = {}
+        try:
+            bufs["coef"] = self.alloc(max(q.nbytes, 8)).upload(q)
+            for w in want:
+                dt, sh = shapes[w]
+                bufs[w] = self.alloc(max(int(np.prod(sh)) * np.dtype(dt).itemsize, 8))
+            if codes_in is not None:
+                ci = np.ascontiguousarray(np.asarray(codes_in, dtype=np.uint8))
+                if ci.shape != (n_sets, G):
+                    raise ValueError("codes_in must be [n_sets, G]")
+                bufs["codes_in"] = self.alloc(max(ci.nbytes, 8)).upload(ci)
+            self.irs_optimize_dev(bufs["coef"], n_sets, R, J, bits=bits, max_sweeps=max_sweeps, start=start,
+                                  direct_blocked=direct_blocked, codes_in=bufs.get("codes_in"), n_elems=N, group=group,
+                                  codes_ptr=bufs.get("codes"), psi_ptr=bufs.get("psi"), power_ptr=bufs.get("power"),
+                                  sweeps_ptr=bufs.get("sweeps"))
             return {w: bufs[w].download(shapes[w][0], int(np.prod(shapes[w][1]))).reshape(shapes[w][1]) for w in want}
         finally:
             for b in bufs.values():

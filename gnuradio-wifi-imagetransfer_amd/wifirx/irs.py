@@ -220,7 +220,11 @@ class IrsConfig:
     draw from noisy channel estimates instead (wifirx_irs_estimate, NUMERICS.md rule 29; excludes ``psi``, ``align_bits`` and
     ``codebook``): the surface steps through the pilots, is observed in noise of standard deviation ``pilot_sigma``, and loads
     the ``pilot_bits``-bit codes decided from the de-spread estimate.  ``group`` ([N] uint16, :func:`groups`; None: G = N) puts
-    several elements behind one phase; ``est_scale`` is the estimator's kappa (None: 1 / T, least squares)."""
+    several elements behind one phase; ``est_scale`` is the estimator's kappa (None: 1 / T, least squares).
+
+    ``decision`` says how the codes are decided from the estimate: "ref" (the default: rule 29's decision on antenna 0, tap 0) or
+    "joint" (wifirx_irs_optimize, NUMERICS.md rule 30: at most ``sweeps`` = 0..16 sweeps of coordinate ascent on the power summed
+    over every antenna and tap, started from the "ref" codes).  "joint" requires ``pilots``."""
     scale: int | None = None
     irs_pos: tuple | None = None
     ap_pos: tuple | None = None
@@ -243,6 +247,8 @@ class IrsConfig:
     group: np.ndarray | None = None
     pilot_bits: int = 2
     est_scale: float | None = None
+    decision: str = "ref"
+    sweeps: int = 4
     n_elems: int = field(init=False, default=0)
 
     def __post_init__(self):
@@ -285,6 +291,13 @@ class IrsConfig:
         self.align_bits = int(self.align_bits)
         if self.align_bits not in (0, 1, 2, 3):
             raise ValueError("align_bits must be 0..3")
+        if self.decision not in ("ref", "joint"):
+            raise ValueError("decision must be ref or joint")
+        self.sweeps = int(self.sweeps)
+        if not 0 <= self.sweeps <= 16:
+            raise ValueError("sweeps must be 0..16")
+        if self.decision == "joint" and self.pilots is None:
+            raise ValueError("decision=joint needs pilots")
         if self.pilots is not None:
             if self.psi is not None or self.align_bits or self.codebook is not None:
                 raise ValueError("pilots exclude psi, align_bits and codebook")

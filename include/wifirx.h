@@ -559,7 +559,8 @@ int  wifirx_irs_sweep(wifirx_handle* h, float* taps_out, uint32_t n_sets, uint32
  *   psi          as wifirx_irs_taps: one configuration per set serves every antenna.
  *   align_bits   B in {1, 2, 3}: the genie of the reference antenna.  The codes are wifirx_irs_taps' argmax on ANTENNA 0, TAP 0
  *                (e_n = a_{0,n} b_n of tap 0, h_{d,0} of tap 0) and serve every antenna and tap of the set.  A genie for the
- *                sum of the antennas' powers has no closed form and is not offered; wifirx_irs_sweep_multi trains on that sum.
+ *                sum of the antennas' powers has no closed form; wifirx_irs_sweep_multi trains on that sum over a codebook, and
+ *                wifirx_irs_optimize ascends it from an estimate (or, at sigma = 0, from the exact coefficients).
  *   scatter      NULL: Philox4x32-10 draws keyed by irs_seed, counter word 3 = 2.  w_a(0) = words (x, y) and w_b = words (z, w)
  *                of the counter (n, r, l, 2); w_d(0) = words (x, y) of (0xFFFFFFFF, r, l, 2): wifirx_irs_taps' draws.  For
  *                m >= 1, w_a(m) comes from the counter (n, r, l + 16 ((m + 1) >> 1), 2) and w_d(m) from (0xFFFFFFFF, r,
@@ -624,8 +625,8 @@ int  wifirx_irs_sweep_multi(wifirx_handle* h, float* taps_out, uint32_t n_ant, u
  *                    the lowest c wins a tie, conj(ghat_{0,0}) -> 1 when both of its parts are zero and when direct_gain = 0
  *                    (a blocked direct path has nothing to align to: the real axis, as there);  psi_n = C_{c_{group[n]}}
  *     taps         = wifirx_irs_taps_multi of the TRUE elements with that psi given, bit for bit
- * A joint decision over antennas and taps, an estimate of noise_sigma, per-antenna noise weights, pilots carried through the
- * TX -> channel -> demod chain and more than 1023 groups are not offered.
+ * A decision that is joint over antennas and taps is wifirx_irs_optimize on est_out (below).  An estimate of noise_sigma,
+ * per-antenna noise weights, pilots carried through the TX -> channel -> demod chain and more than 1023 groups are not offered.
  *   taps_out     DEVICE complex64 [n_ant][n_sets][n_taps] (8-byte aligned) or NULL: antenna-major as wifirx_irs_taps_multi's.
  *   pilot        complex64 [n_pilots][n_groups], HOST or (pilot_on_device) DEVICE; 1 <= n_pilots <= 1024, 1 <= n_groups <=
  *                min(N, 1023).  Any complex value is taken (Python: wifirx.irs.dft_pilots, hadamard_pilots).
@@ -653,6 +654,50 @@ int  wifirx_irs_estimate(wifirx_handle* h, float* taps_out, uint32_t n_ant, uint
                          const float* scatter, uint32_t n_scatter, const float* noise, uint32_t n_noise, uint64_t irs_seed,
                          float* est_out   /* [n_sets][R][n_groups+1] complex64 */, uint8_t* codes_out /* [n_sets][n_groups] */,
                          float* obs_out   /* [n_sets][R][n_pilots] complex64 */);
+
+/* The joint phase decision over antennas and taps: cyclic coordinate ascent on the power an MRC receiver collects,
+ *     P = sum_rho |d_rho + sum_g e_{rho,g} C_{c_g}|^2,
+ * over the B-bit codes c_g; arithmetic = NUMERICS.md rule 30, float32 with wifirx_irs_taps' ch_mul / ch_add, no fma.  The
+ * coefficients are a matrix Q [n_sets][R][J] in the layout of wifirx_irs_estimate's est_out: column 0 the direct term d_rho,
+ * column g + 1 the coefficient e_{rho,g} of group g, G = J - 1, rows rho = m L + l.  Per set:
+ *     start      WIFIRX_IRS_START_REF: wifirx_irs_estimate's decision, the argmax of Re(conj(Q[0][0]) Q[0][g+1] C_c) on row 0,
+ *                conj(..) -> 1 when both parts are zero or direct_blocked; WIFIRX_IRS_START_GIVEN: codes_in (the low B bits of
+ *                every byte); WIFIRX_IRS_START_ZERO: all codes 0
+ *     state      s_rho = d_rho, then for g ascending s = ch_add(s, ch_mul(e_g, C_{c_g})); formed once, never recomputed
+ *     one sweep  for g ascending: p = ch_mul(e_g, C_{c_g}), r = s - p per part, t_rho = ch_mul(conj(r_rho), e_rho); lane i of a
+ *                64-wide wave forms t_i + t_{i+64} (absent rows are +0) and the 64 values are folded by wifirx_irs_taps'
+ *                butterfly (lane xor 32, 16, 8, 4, 2, 1) into z; c_new = wifirx_irs_taps' argmax on Re(ch_mul(z, C_c)):
+ *                ascending c, strict >, the lowest c wins a tie, a NaN never replaces the running maximum.  If c_new != c_g:
+ *                s = r + ch_mul(e_g, C_{c_new}) and c_g = c_new; otherwise s stays as it was (not (s - p) + p)
+ *     power      q_rho = s.re s.re + s.im s.im, the same lane pairing and butterfly; power[0] behind the state, power[i] behind
+ *                sweep i
+ *     stopping   a sweep that changes no code ends the call (every later sweep would repeat it bit for bit); the remaining power
+ *                entries repeat the last value; sweeps_out is the number of sweeps that changed a code
+ * With direct_blocked d_rho = +0 and column 0 is not read (wifirx_irs_estimate's direct_gain = 0).  max_sweeps = 0 with
+ * WIFIRX_IRS_START_REF gives wifirx_irs_estimate's codes.  Per-antenna noise weights, other objectives, R > 128, random restarts
+ * and other element orders are not offered.
+ *   coef         DEVICE complex64 [n_sets][n_rows][n_cols] (8-byte aligned): Q.  1 <= n_rows <= 128, 2 <= n_cols <= 1024.
+ *   bits         B in {1, 2, 3}.   max_sweeps  0..16.
+ *   codes_in     DEVICE uint8 [n_sets][G], required with WIFIRX_IRS_START_GIVEN and not read otherwise.
+ *   n_elems, group   for psi_out: HOST uint16 [n_elems], every value < G: the group of element n; NULL is the identity and needs
+ *                n_elems = G.  Without psi_out neither is looked at.
+ *   codes_out    DEVICE uint8 [n_sets][G] or NULL: the final codes.
+ *   psi_out      DEVICE complex64 [n_sets][n_elems] (8-byte aligned) or NULL: psi_n = C_{c_{group[n]}}, what wifirx_irs_taps_multi
+ *                reads with psi_on_device = 1, n_psi_sets = n_sets.  One of codes_out and psi_out at least.
+ *   power_out    DEVICE float32 [n_sets][max_sweeps + 1] (4-byte aligned) or NULL.   sweeps_out  DEVICE uint8 [n_sets] or NULL.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for a NULL coef, n_rows outside 1..128, n_cols outside 2..1024,
+ * bits outside 1..3, max_sweeps above 16, an unknown start, WIFIRX_IRS_START_GIVEN without codes_in, codes_out and psi_out both
+ * NULL, psi_out with n_elems outside 1..4096, with a NULL group and n_elems != G, or with a group value >= G, and misaligned
+ * pointers (complex64: 8 bytes, float32: 4, uint16: 2); WIFIRX_ERANGE for more than 2^31 - 1 sets.  n_sets = 0 does nothing and
+ * returns WIFIRX_OK.  One kernel launch per call, after one upload of the group map (none without it).  ORDER: as wifirx_channel. */
+#define WIFIRX_IRS_START_REF   0
+#define WIFIRX_IRS_START_GIVEN 1
+#define WIFIRX_IRS_START_ZERO  2
+int  wifirx_irs_optimize(wifirx_handle* h, const float* coef /* DEVICE [n_sets][R][J] complex64 */, uint32_t n_sets,
+                         uint32_t n_rows, uint32_t n_cols, uint32_t bits, uint32_t max_sweeps, int start, int direct_blocked,
+                         const uint8_t* codes_in /* DEVICE [n_sets][G] or NULL */,
+                         uint32_t n_elems, const uint16_t* group /* HOST [N] or NULL = identity, needs N == G */,
+                         uint8_t* codes_out, float* psi_out, float* power_out /* [n_sets][max_sweeps+1] */, uint8_t* sweeps_out);
 
 /* ieee802_11.mac (gnu_radio/IRS_user.py:192,204-205; IRS_tranceiver.py:271,313-314) for a batch: PSDU i, at
  * psdu + i * psdu_stride, is the 24 + payload_len[i] + 4 bytes

@@ -63,13 +63,15 @@ the combiner) and mode.  The counts nest: A antennas are the first A of the larg
 --irs: the link over a reflecting surface of N elements with B-bit phases (wifirx_irs_taps, NUMERICS.md rule 25): one tap set of 8
 taps per frame, made on the device and read there by wifirx_channel; FER against the surface size at SNRs of one unit-power path.
 --irs-mode: random phases, the one configuration aligned to the geometry, the genie aligned per draw, `estimate`: a surface
-trained per draw from a noisy pilot-based channel estimate (wifirx_irs_estimate; --irs-pilots, --pilot-snr-db, --irs-group), or `sweep`: a surface
+trained per draw from a noisy pilot-based channel estimate (wifirx_irs_estimate; --irs-pilots, --pilot-snr-db, --irs-group; with
+--irs-decision joint the codes are decided over every antenna and tap by wifirx_irs_optimize, --pilot-snr-db inf is its genie bound), or `sweep`: a surface
 trained per draw by a codebook sweep (wifirx_irs_sweep, rule 26; --irs-codebook dft / dft2 / traverse, quantised to --irs-bits).
 --irs 0 is the direct path alone.
 
     python tools/loopback_per.py --irs 0 16 64 256 --irs-bits 2 --irs-mode random los genie --k-factor 3 --direct-db -inf --psdu-len 294 --encoding 2 --snr -20 -10 0 [--frames 65536] [--out profiles/loopback_irs.json]
     python tools/loopback_per.py --irs 64 256 --irs-bits 2 --irs-mode random los genie sweep --irs-codebook dft2 --k-factor 3 --psdu-len 294 --encoding 2 --snr -30 -20 -10 [--out profiles/loopback_irs_sweep.json]
-    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode random sweep estimate genie --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_estimate.json]"""
+    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode random sweep estimate genie --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_estimate.json]
+    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode estimate --irs-decision ref joint --antennas 1 2 4 --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_optimize.json]"""
 import argparse
 import json
 import math
@@ -151,6 +153,10 @@ def main():
     ap.add_argument("--pilot-snr-db", type=float, default=0.0,
                     help="with --irs-mode estimate: the SNR of one unit-power path in one pilot observation (sigma = 10^(-dB / 20))")
     ap.add_argument("--irs-group", type=int, default=1, help="with --irs-mode estimate: c x c elements behind one phase (irs.groups)")
+    ap.add_argument("--irs-decision", nargs="+", choices=("ref", "joint"), default=["ref"],
+                    help="with --irs-mode estimate: the codes decided on antenna 0, tap 0 (wifirx_irs_estimate's own decision) or "
+                         "jointly over antennas and taps (wifirx_irs_optimize, NUMERICS.md rule 30; reported as mode estimate_joint)")
+    ap.add_argument("--irs-sweeps", type=int, default=4, help="with --irs-decision joint: the most sweeps, 0 .. 16")
     ap.add_argument("--irs-codebook", choices=("dft", "dft2", "traverse"), default="dft2",
                     help="with --irs-mode sweep: irs.dft_codebook at over = 1 / 2, or the reference controller's 10 x 10 grid "
                          "(irs.traverse_codebook), quantised to --irs-bits")
@@ -551,6 +557,37 @@ def estimate_keywords(a, S):
     return kw, {"pilots": a.irs_pilots, "slots": int(pl.shape[0]), "groups": G, "sigma": sigma, "est_scale": float(kw["est_scale"])}
 
 
+def estimate_taps(rx, a, decision, d_taps, n, pdp, b2r, r2u, b2u, est_kw, kw):
+    """--irs-mode estimate: the taps of n sets at d_taps under the codes decided from the estimate -- by wifirx_irs_estimate itself
+    (ref), or by estimate -> wifirx_irs_optimize -> wifirx_irs_taps_multi queued on the handle's stream (joint)"""
+    if decision != "joint":
+        rx.irs_estimate_dev(d_taps, n, pdp, b2r, r2u, b2u, **est_kw, **kw)
+        return
+    M, N = (1 if np.ndim(b2r) == 1 else np.shape(b2r)[0]), np.shape(b2r)[-1]
+    R, J = M * len(pdp), est_kw["pilots"].shape[1] + 1
+    coef, psi = rx.alloc(n * R * J * 8), rx.alloc(n * N * 8)
+    try:
+        rx.irs_estimate_dev(None, n, pdp, b2r, r2u, b2u, est_ptr=coef, **dict(est_kw, align_bits=0), **kw)
+        rx.irs_optimize_dev(coef, n, R, J, bits=est_kw["align_bits"], max_sweeps=a.irs_sweeps, start="ref",
+                            direct_blocked=kw["direct_gain"] == 0.0, n_elems=N, group=est_kw["group"], psi_ptr=psi)
+        rx.irs_taps_multi_dev(d_taps, n, pdp, b2r, r2u, b2u, psi=psi, n_psi_sets=n, **kw)
+        rx.sync()
+    finally:
+        coef.free()
+        psi.free()
+
+
+def expand_modes(a, modes):
+    """(mode, decision, label) per run: --irs-mode estimate once per --irs-decision, the joint one reported as estimate_joint"""
+    out = []
+    for m in modes:
+        if m == "estimate":
+            out += [(m, d, "estimate" if d == "ref" else "estimate_joint") for d in a.irs_decision]
+        else:
+            out.append((m, None, m))
+    return out
+
+
 def irs_main(a):
     if a.rates or a.host_stats or a.locked_clock or a.doppler is not None:
         raise SystemExit("--irs stands alone: not with --rates, --host-stats, --locked-clock or --doppler")
@@ -588,12 +625,11 @@ def irs_main(a):
         S = max(1, int(round(N ** 0.5)))
         irs_pos, ap_pos = [0.015, 0.015, 0], [S * 0.015, S * 0.015, 4.5]
         b2r, r2u, b2u = irs.los(S, irs_pos, ap_pos, [S * 0.015 + 0.3, S * 0.015 - 0.2, 1.0])
-        for mode in (a.irs_mode if N else ["none"]):
+        for mode, decision, label in expand_modes(a, a.irs_mode if N else ["none"]):
             kw = dict(k_factor=a.k_factor, direct_gain=direct_gain if N else (direct_gain or 1.0), seed=(a.seed << 32) + N)
             winners = None
             if mode == "estimate":
                 est_kw, winners = estimate_keywords(a, S)
-                kw.update(est_kw)
             elif mode == "sweep":
                 if a.irs_codebook == "traverse":
                     kw["codebook"] = irs.traverse_codebook(S, 0.03, irs_pos, ap_pos, accuracy=10, bits=bits)
@@ -609,7 +645,7 @@ def irs_main(a):
                 kw["psi"] = np.zeros(1, np.complex64)
             # one tap set per frame, made on the device and read there by the channel
             if mode == "estimate":
-                rx.irs_estimate_dev(d_taps, n, pdp, b2r, r2u, b2u, **kw)
+                estimate_taps(rx, a, decision, d_taps, n, pdp, b2r, r2u, b2u, est_kw, kw)
             elif mode == "sweep":
                 rx.irs_sweep_dev(d_taps, n, pdp, b2r, r2u, b2u, best_ptr=d_best, **kw)
                 hist = np.bincount(d_best.download(np.uint16, n), minlength=kw["codebook"].shape[0])
@@ -625,7 +661,7 @@ def irs_main(a):
                 rx.demod_batch_dev(iq.ptr, slot, n, dev)
                 rx.decode_batch_dev(n, dev)
                 r = rx.link_stats(n, dev, ref)
-                points.append({"n_elems": N, "mode": mode, "snr_db": snr, "frames": n, "fer": r["fer"], "coded_ber": r["coded_ber"],
+                points.append({"n_elems": N, "mode": label, "snr_db": snr, "frames": n, "fer": r["fer"], "coded_ber": r["coded_ber"],
                                "mean_channel_power": mean_power, "seconds": time.perf_counter() - t0,
                                "counts": {k: r[k] for k in COUNTERS}})
                 if winners is not None:
@@ -646,7 +682,9 @@ def irs_main(a):
                               "NUMERICS.md rule 26); 'winners' holds the histogram of the winning entries" % a.irs_codebook,
                      "estimate": "trained per draw from a noisy pilot-based estimate of the direct path and of every group's cascade "
                                  "coefficient (wifirx_irs_estimate, NUMERICS.md rule 29); 'training' holds the pilots, the groups and "
-                                 "the noise of one pilot observation"},
+                                 "the noise of one pilot observation",
+                     "estimate_joint": "the same estimate, the codes decided jointly over the taps by at most %d sweeps of "
+                                       "wifirx_irs_optimize from the estimate's own decision (NUMERICS.md rule 30)" % a.irs_sweeps},
            "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
@@ -703,12 +741,12 @@ def irs_multi_main(a):
         irs_pos, ap_pos, user_pos = [0.015, 0.015, 0], [S * 0.015, S * 0.015, 4.5], [S * 0.015 + 0.3, S * 0.015 - 0.2, 1.0]
         for A in counts:
             b2r, r2u, b2u = irs.los(S, irs_pos, ap_pos, user_pos, antennas=A)
-            for mode in modes:
+            for mode, decision, label in expand_modes(a, modes):
                 kw = dict(k_factor=a.k_factor, direct_gain=direct_gain, seed=(a.seed << 32) + N)       # irs_main's seeds
                 winners = None
                 if mode == "estimate":
                     est_kw, winners = estimate_keywords(a, S)
-                    rx.irs_estimate_dev(d_taps, n, pdp, b2r, r2u, b2u, **est_kw, **kw)
+                    estimate_taps(rx, a, decision, d_taps, n, pdp, b2r, r2u, b2u, est_kw, kw)
                 elif mode == "sweep":
                     kw["codebook"] = irs.dft_codebook(S, b2r[0], over=min(2 if a.irs_codebook == "dft2" else 1, max(1, 32 // S)), bits=bits)
                     rx.irs_sweep_multi_dev(d_taps, n, pdp, b2r, r2u, b2u, best_ptr=d_best, **kw)
@@ -736,7 +774,7 @@ def irs_multi_main(a):
                     hard = rx.link_stats(n, dev, ref)
                     rx.decode_batch_soft_dev(n, dev)
                     soft = rx.link_stats(n, dev, ref)
-                    points.append({"n_elems": N, "antennas": A, "mode": mode, "snr_db": snr, "frames": n, "fer": hard["fer"],
+                    points.append({"n_elems": N, "antennas": A, "mode": label, "snr_db": snr, "frames": n, "fer": hard["fer"],
                                    "fer_soft": soft["fer"], "mean_combined_channel_power": float(power.sum()),
                                    "mean_channel_power_per_antenna": [float(v) for v in power], "seconds": time.perf_counter() - t0,
                                    "counts": {c: hard[c] for c in COUNTERS}, "counts_soft": {c: soft[c] for c in COUNTERS}})
@@ -760,7 +798,9 @@ def irs_multi_main(a):
                      "sweep": "trained per draw on the sum of the antennas' channel powers: the best entry of the %s codebook, quantised to "
                               "the same bits (wifirx_irs_sweep_multi, NUMERICS.md rule 28)" % a.irs_codebook,
                      "estimate": "trained per draw from a noisy pilot-based estimate, the codes decided on antenna 0, tap 0 "
-                                 "(wifirx_irs_estimate, NUMERICS.md rule 29)"},
+                                 "(wifirx_irs_estimate, NUMERICS.md rule 29)",
+                     "estimate_joint": "the same estimate, the codes decided jointly over antennas and taps by at most %d sweeps of "
+                                       "wifirx_irs_optimize from the estimate's own decision (NUMERICS.md rule 30)" % a.irs_sweeps},
            "antennas": counts, "stats": "wifirx_link_stats on the device; reported, not asserted",
            "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
