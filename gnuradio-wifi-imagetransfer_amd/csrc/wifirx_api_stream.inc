@@ -227,6 +227,10 @@ static std::vector<wr::StreamTrig> stream_trig_rows(wifirx_handle* h, bool flush
         bool fin = flush;
         if (k + 1 < np && st.pending[k + 1].pos - pos <= L) { L = st.pending[k + 1].pos - pos; fin = true; }
         if (L >= WIFIRX_MAX_SAMPLES) { L = WIFIRX_MAX_SAMPLES; fin = true; }
+        // 383 samples are enough for the LTS search only when the 384th cannot come: it takes part in stage 1's exponent
+        // maximum (NUMERICS.md rule 6), so a search without it could give a record that depends on where a push ends.
+        // One sample fewer and the frame waits (DETECTED | TRUNCATED) like any other whose window is still on its way.
+        if (!fin && L == WIFIRX_SYNC_LENGTH + 63) L -= 1;
         trig[k].pos = pos - st.sbase;
         trig[k].usable = L;
         trig[k].cfo = st.pending[k].cfo;        // A[] of an earlier push is gone: reuse the value

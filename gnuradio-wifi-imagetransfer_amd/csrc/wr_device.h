@@ -130,7 +130,8 @@ __device__ __forceinline__ float sp_atan2(float y, float x)
     if (big) r = r + WR_PIO4;
     if (ay > ax) r = WR_PIO2 - r;
     if (x < 0.0f) r = WR_PI - r;
-    if (y < 0.0f) r = -r;
+    // y < 0 or y = -0 (the sign bit of a zero counts, as in atan2f: (-0, x < 0) is -pi); a NaN of either sign does not
+    if (__float_as_uint(y) - 0x80000000u <= 0x7f800000u) r = -r;
     return (mx == 0.0f) ? 0.0f : r;
 }
 

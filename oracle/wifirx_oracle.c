@@ -174,7 +174,10 @@ static inline float sp_atan2(float y, float x)
     if (big) r = r + WR_PIO4;
     if (ay > ax) r = WR_PIO2 - r;
     if (x < 0.0f) r = WR_PI - r;
-    if (y < 0.0f) r = -r;
+    /* y < 0 or y = -0 (the sign bit of a zero counts, as in atan2f: (-0, x < 0) is -pi); a NaN of either sign does not */
+    uint32_t yb;
+    memcpy(&yb, &y, 4);
+    if (yb - 0x80000000u <= 0x7f800000u) r = -r;
     return r;
 }
 
