@@ -3,8 +3,11 @@ wave in the four bytes of one register: start value 64 instead of the oracle's 2
 ((m0 + 0x7f7f7f7f) - m1: top bit of byte f = m1 < m0), survivor select by the resulting byte mask, final state by a
 minimum over (metric << 6 | state).  Pinned here on the CPU, step by step in numpy with exactly those word operations:
 the decoded bits equal the oracle's Viterbi (orc_viterbi, oracle/wifirx_oracle.c viterbi_decode) on random coded
-sequences -- clean, noisy and pure noise --, and no byte ever reaches 128.  (The kernel itself is compared with the
-oracle on every frame of the -m gpu suite; this test states WHY the packed form may replace the 32-bit one.)"""
+sequences -- clean, noisy and pure noise --, and no byte ever reaches 128.  This test states WHY the packed form may
+replace the 32-bit one.  The kernel itself runs on words far from every codeword, four different ones in the four bytes of a
+register, in tests/test_gpu_symbol_rows.py (rows of tests/symbol_rows.py; tests/test_symbol_rows.py runs this model on the
+same words); the transmitted frames of the rest of the -m gpu suite carry SIGNAL codewords, at low SNR with a few flips,
+and do not reach the tie rules or the free end state."""
 import numpy as np
 
 
@@ -21,9 +24,10 @@ A1 = np.array([parity(int(f) & 0o155) for f in F1], np.uint32) * np.uint32(0x010
 B1 = np.array([parity(int(f) & 0o117) for f in F1], np.uint32) * np.uint32(0x01010101)
 
 
-def packed_viterbi4(cb):
-    """cb: four 48-bit integers (bit j = coded bit j).  Returns the four 24-bit results and the largest metric byte seen."""
-    pm = np.where(S == 0, np.uint32(0), np.uint32(0x40404040)).astype(np.uint32)
+def packed_viterbi4(cb, start=0x40404040):
+    """cb: four 48-bit integers (bit j = coded bit j).  Returns the four 24-bit results and the largest metric byte seen.
+    start: the value of the 63 unreachable states (the kernel's 0x40404040)."""
+    pm = np.where(S == 0, np.uint32(0), np.uint32(start)).astype(np.uint32)
     surv = np.zeros((4, 24), np.uint64)
     top_byte = 0
     for t in range(24):
@@ -56,11 +60,12 @@ def packed_viterbi4(cb):
 
 
 def conv_encode(bits24):
+    """the code the decoder decodes: generators 0155 / 0117 over (state << 1 | input), the newest input in bit 0"""
     state, out = 0, []
     for b in bits24:
-        reg = (int(b) << 6) | state
+        reg = (state << 1) | int(b)
         out += [parity(reg & 0o155), parity(reg & 0o117)]
-        state = reg >> 1
+        state = reg & 63
     return out
 
 
@@ -81,6 +86,8 @@ def test_packed_byte_metrics_decode_like_the_oracle(orc):
                 coded = coded ^ flips
             cbs.append(int(sum(int(c) << j for j, c in enumerate(coded))))
             want.append(orc.viterbi(coded.astype(np.uint8), 24))
+            if kind == 0:
+                assert list(want[-1]) == list(msg)                               # a clean sequence is a codeword of this code
         got, top = packed_viterbi4(cbs)
         worst = max(worst, top)
         for f in range(4):
