@@ -417,10 +417,13 @@ extern "C" int wifirx_irs_estimate(wifirx_handle* h, float* taps_out, uint32_t n
 
 // ---- the joint phase decision over antennas and taps (wr_irs_optimize.hip, NUMERICS.md rule 30) ----
 
-extern "C" int wifirx_irs_optimize(wifirx_handle* h, const float* coef, uint32_t n_sets, uint32_t n_rows, uint32_t n_cols,
-                                   uint32_t bits, uint32_t max_sweeps, int start, int direct_blocked, const uint8_t* codes_in,
-                                   uint32_t n_elems, const uint16_t* group,
-                                   uint8_t* codes_out, float* psi_out, float* power_out, uint8_t* sweeps_out)
+// the body of wifirx_irs_optimize (weighted = false: weight, weight_on_device and n_weight_sets are not looked at) and of
+// wifirx_irs_optimize_weighted (NUMERICS.md rule 31)
+static int irs_optimize_call(wifirx_handle* h, const float* coef, uint32_t n_sets, uint32_t n_rows, uint32_t n_cols, bool weighted,
+                             const float* weight, int weight_on_device, uint32_t n_weight_sets,
+                             uint32_t bits, uint32_t max_sweeps, int start, int direct_blocked, const uint8_t* codes_in,
+                             uint32_t n_elems, const uint16_t* group,
+                             uint8_t* codes_out, float* psi_out, float* power_out, uint8_t* sweeps_out)
 {
     if (!h) return WIFIRX_EINVAL;
     // ---- the argument checks, before anything is queued ----
@@ -445,16 +448,29 @@ extern "C" int wifirx_irs_optimize(wifirx_handle* h, const float* coef, uint32_t
     if (psi_out && group)
         for (uint32_t n = 0; n < n_elems; n++)
             if (group[n] >= n_groups) return fail(h, WIFIRX_EINVAL, "a group value is not below n_cols - 1");
+    const bool host_weight = weighted && !weight_on_device;
+    if (weighted) {
+        if (!weight) return fail(h, WIFIRX_EINVAL, "weight is required");
+        if (n_weight_sets != 1 && n_weight_sets != n_sets) return fail(h, WIFIRX_EINVAL, "n_weight_sets must be 1 or n_sets");
+        if (host_weight && n_weight_sets != 1) return fail(h, WIFIRX_EINVAL, "host weights are one row block: n_weight_sets must be 1");
+        if (addr(weight) & 3) return fail(h, WIFIRX_EINVAL, "weight must be 4-byte aligned (float32)");
+        if (host_weight)
+            for (uint32_t r = 0; r < n_rows; r++)
+                if (!std::isfinite(weight[r])) return fail(h, WIFIRX_EINVAL, "a host weight is not finite");
+    }
     if (n_sets == 0) return WIFIRX_OK;
     if (n_sets > 0x7fffffffu) return fail(h, WIFIRX_ERANGE, "more than 2^31 - 1 sets");
 
     stream_worker_wait_idle(h);
     HIP_TRY(h, hipSetDevice(h->device));
     wr::IrsOptimizeArgs a{};
-    if (psi_out && group) {                             // the one upload: the group map, as wifirx_irs_estimate sends it
-        IrsMeta up;
+    a.weight = weighted ? weight : nullptr;
+    a.n_weight_sets = weighted ? n_weight_sets : 1;
+    if ((psi_out && group) || host_weight) {            // the one upload: the group map, as wifirx_irs_estimate sends it, and
+        IrsMeta up;                                     // the host weights
         int rc;
-        up.add(&a.group, group, 2ull * n_elems);
+        if (psi_out && group) up.add(&a.group, group, 2ull * n_elems);
+        if (host_weight) up.add(&a.weight, weight, 4ull * n_rows);
         if ((rc = up.send(h))) return rc;
     }
     a.coef = reinterpret_cast<const float2*>(coef);
@@ -473,4 +489,25 @@ extern "C" int wifirx_irs_optimize(wifirx_handle* h, const float* coef, uint32_t
     a.blocked = direct_blocked != 0;
     HIP_TRY(h, wr_launch_irs_optimize(h->stream, &a));
     return WIFIRX_OK;
+}
+
+extern "C" int wifirx_irs_optimize(wifirx_handle* h, const float* coef, uint32_t n_sets, uint32_t n_rows, uint32_t n_cols,
+                                   uint32_t bits, uint32_t max_sweeps, int start, int direct_blocked, const uint8_t* codes_in,
+                                   uint32_t n_elems, const uint16_t* group,
+                                   uint8_t* codes_out, float* psi_out, float* power_out, uint8_t* sweeps_out)
+{
+    return irs_optimize_call(h, coef, n_sets, n_rows, n_cols, false, nullptr, 0, 1, bits, max_sweeps, start, direct_blocked,
+                             codes_in, n_elems, group, codes_out, psi_out, power_out, sweeps_out);
+}
+
+// ---- the same decision with a signed weight on every row (NUMERICS.md rule 31) ----
+
+extern "C" int wifirx_irs_optimize_weighted(wifirx_handle* h, const float* coef, uint32_t n_sets, uint32_t n_rows, uint32_t n_cols,
+                                            const float* weight, int weight_on_device, uint32_t n_weight_sets,
+                                            uint32_t bits, uint32_t max_sweeps, int start, int direct_blocked, const uint8_t* codes_in,
+                                            uint32_t n_elems, const uint16_t* group,
+                                            uint8_t* codes_out, float* psi_out, float* power_out, uint8_t* sweeps_out)
+{
+    return irs_optimize_call(h, coef, n_sets, n_rows, n_cols, true, weight, weight_on_device, n_weight_sets, bits, max_sweeps, start,
+                             direct_blocked, codes_in, n_elems, group, codes_out, psi_out, power_out, sweeps_out);
 }

@@ -2,6 +2,8 @@
 // coordinate ascent on P = sum_rho |d_rho + sum_g e_{rho,g} C_{c_g}|^2 over the B-bit codes c_g, on the coefficient matrix that
 // wifirx_irs_estimate leaves in est_out.  For one group the best code is rule 25's argmax on z_g = sum_rho conj(r_rho) e_{rho,g},
 // r the running sum without the group's own term, so the decision is built from wr_irs_elem.h's irs_argmax and irs_butterfly.
+// The WEIGHTED instances (rule 31, wifirx_irs_optimize_weighted) ascend P_w = sum_rho w_rho |..|^2 for real weights of either sign:
+// the same body with w_rho on the row's term of z and of the power; the two weights of a lane live in two registers for the call.
 //
 // Work split: one wave owns one set, a workgroup holds four sets.  The rows go across the lanes: lane i holds the running sums of
 // the rows i and i + 64 in registers for the whole call, so a step costs no memory traffic but the group's column, and the sum over
@@ -49,7 +51,18 @@ __device__ __forceinline__ float opt_power(float2 s0, float2 s1, bool have0, boo
     return irs_butterfly(make_float2(q0 + q1, 0.0f)).x;
 }
 
-template <int BITS>
+// rule 31: a row's term w v of a sum over the rows, one multiply per part behind the value; +0 is selected, not multiplied, where
+// w == 0 (either sign), which an absent row's weight is
+__device__ __forceinline__ float opt_weigh(float w, float v) { return w != 0.0f ? w * v : 0.0f; }
+
+// rule 31's power: w_rho q_rho in place of q_rho
+__device__ __forceinline__ float opt_power_w(float2 s0, float2 s1, float w0, float w1)
+{
+    const float q0 = opt_weigh(w0, s0.x * s0.x + s0.y * s0.y), q1 = opt_weigh(w1, s1.x * s1.x + s1.y * s1.y);
+    return irs_butterfly(make_float2(q0 + q1, 0.0f)).x;
+}
+
+template <int BITS, bool WEIGHTED>
 __global__ __launch_bounds__(64 * OPT_WAVES)
 void irs_optimize_kernel(const IrsOptimizeArgs a)
 {
@@ -66,6 +79,14 @@ void irs_optimize_kernel(const IrsOptimizeArgs a)
     const float2 zero = make_float2(0.0f, 0.0f);
     uint8_t* cs = codes_s[wave];
     const bool blocked = a.blocked != 0;
+    // rule 31: the weights of the lane's two rows, loaded once; set r reads block r % n_weight_sets, and n_weight_sets is 1 or
+    // n_sets (the launcher refuses anything else), so that is block 0 or block r
+    float w0 = 0.0f, w1 = 0.0f;
+    if constexpr (WEIGHTED) {
+        const float* w = a.weight + (a.n_weight_sets == 1 ? 0 : set) * R;
+        if (have0) w0 = w[lane];
+        if (have1) w1 = w[lane + 64];
+    }
 
     // ---- 1, 2: the start codes and the state s = d + sum_g e_g C_{c_g}, g ascending ----
     float2 s0 = (have0 && !blocked) ? row0[0] : zero, s1 = (have1 && !blocked) ? row1[0] : zero;
@@ -98,7 +119,7 @@ void irs_optimize_kernel(const IrsOptimizeArgs a)
             cs[g] = (uint8_t)c;
         }
     }
-    float pw = opt_power(s0, s1, have0, have1);
+    float pw = WEIGHTED ? opt_power_w(s0, s1, w0, w1) : opt_power(s0, s1, have0, have1);
     float* pout = a.power_out ? a.power_out + set * (a.max_sweeps + 1) : nullptr;
     if (pout && lane == 0) pout[0] = pw;
 
@@ -124,7 +145,9 @@ void irs_optimize_kernel(const IrsOptimizeArgs a)
                 const float2 r0 = make_float2(s0.x - p0.x, s0.y - p0.y), r1 = make_float2(s1.x - p1.x, s1.y - p1.y);
                 const float2 t0 = have0 ? ch_mul(make_float2(r0.x, -r0.y), e0[k]) : zero;      // absent rows are +0
                 const float2 t1 = have1 ? ch_mul(make_float2(r1.x, -r1.y), e1[k]) : zero;
-                const float2 z = irs_butterfly(make_float2(t0.x + t1.x, t0.y + t1.y));
+                const float2 z = irs_butterfly(                 // rule 31: tw = (w t.re, w t.im), +0 where w == 0
+                    WEIGHTED ? make_float2(opt_weigh(w0, t0.x) + opt_weigh(w1, t1.x), opt_weigh(w0, t0.y) + opt_weigh(w1, t1.y))
+                             : make_float2(t0.x + t1.x, t0.y + t1.y));
                 const uint32_t cn = __builtin_amdgcn_readfirstlane(irs_argmax(z, irs_multi_phase, n_codes, up));
                 if (cn != c) {                                  // otherwise s stays as it was: not (s - p) + p
                     const float2 pn = opt_phase(cn << up);
@@ -136,7 +159,7 @@ void irs_optimize_kernel(const IrsOptimizeArgs a)
                 }
             }
         }
-        pw = opt_power(s0, s1, have0, have1);
+        pw = WEIGHTED ? opt_power_w(s0, s1, w0, w1) : opt_power(s0, s1, have0, have1);
         if (pout && lane == 0) pout[it] = pw;
         if (!changed) break;                                    // every later sweep would repeat this one bit for bit
         done++;
@@ -166,10 +189,15 @@ extern "C" hipError_t wr_launch_irs_optimize(hipStream_t st, const wr::IrsOptimi
         (args->start == OPT_START_GIVEN && !args->codes_in) || args->n_sets > 0x7fffffffu ||
         (args->psi_out && (args->n_elems < 1 || (!args->group && args->n_elems != G))))
         return hipErrorInvalidValue;                            // (the entry point refuses these first)
+    if (args->weight && args->n_weight_sets != 1 && args->n_weight_sets != args->n_sets) return hipErrorInvalidValue;
     const dim3 grid((args->n_sets + OPT_WAVES - 1) / OPT_WAVES), block(64 * OPT_WAVES);
-    if (args->bits == 1) hipLaunchKernelGGL((wr::irs_optimize_kernel<1>), grid, block, 0, st, *args);
-    else if (args->bits == 2) hipLaunchKernelGGL((wr::irs_optimize_kernel<2>), grid, block, 0, st, *args);
-    else hipLaunchKernelGGL((wr::irs_optimize_kernel<3>), grid, block, 0, st, *args);
+    if (args->weight) {                                         // rule 31
+        if (args->bits == 1) hipLaunchKernelGGL((wr::irs_optimize_kernel<1, true>), grid, block, 0, st, *args);
+        else if (args->bits == 2) hipLaunchKernelGGL((wr::irs_optimize_kernel<2, true>), grid, block, 0, st, *args);
+        else hipLaunchKernelGGL((wr::irs_optimize_kernel<3, true>), grid, block, 0, st, *args);
+    } else if (args->bits == 1) hipLaunchKernelGGL((wr::irs_optimize_kernel<1, false>), grid, block, 0, st, *args);
+    else if (args->bits == 2) hipLaunchKernelGGL((wr::irs_optimize_kernel<2, false>), grid, block, 0, st, *args);
+    else hipLaunchKernelGGL((wr::irs_optimize_kernel<3, false>), grid, block, 0, st, *args);
     return hipGetLastError();
 }
 

@@ -627,7 +627,8 @@ class channel_model(grshim.sync_block):
     NUMERICS.md rule 26), and ``irs_best`` holds the winning entries of the sets drawn so far.  With ``IrsConfig(pilots=...)``
     every tap set is trained from a noisy pilot-based estimate of its own (wifirx_irs_estimate, NUMERICS.md rule 29), and
     ``irs_codes`` holds the decided codes of the sets drawn so far.  ``IrsConfig(pilots=..., decision="joint")`` decides them over
-    every antenna and tap (wifirx_irs_estimate -> wifirx_irs_optimize -> wifirx_irs_taps_multi on one stream, NUMERICS.md rule 30).
+    every antenna and tap (wifirx_irs_estimate -> wifirx_irs_optimize -> wifirx_irs_taps_multi on one stream, NUMERICS.md rule 30);
+    with ``tap_weights`` or ``ant_weights`` the middle call is wifirx_irs_optimize_weighted (NUMERICS.md rule 31).
 
     ``IrsConfig(antennas=M)``, M = 2..8, puts an AP of M antennas behind the surface (wifirx_irs_taps_multi /
     wifirx_irs_sweep_multi, NUMERICS.md rules 27 and 28): the block then has M output ports, port m the input through plane m of
@@ -701,7 +702,7 @@ class channel_model(grshim.sync_block):
                         self._rx.irs_estimate_dev(None, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, est_ptr=coef, **est)
                         self._rx.irs_optimize_dev(coef, n, R, J, bits=c.pilot_bits, max_sweeps=c.sweeps, start="ref",
                                                   direct_blocked=c.direct_gain == 0.0, n_elems=c.n_elems, group=c.group,
-                                                  codes_ptr=self._irs_codes, psi_ptr=psi)
+                                                  codes_ptr=self._irs_codes, psi_ptr=psi, weights=c.row_weights)
                         self._rx.irs_taps_multi_dev(self._irs_sets, n, c.pdp, c.los_b2r, c.los_r2u, c.los_b2u, psi=psi,
                                                     n_psi_sets=n, **scene)
                         self._rx.sync()

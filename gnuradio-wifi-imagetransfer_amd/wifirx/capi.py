@@ -51,6 +51,7 @@ EXPORTS = [
     "wifirx_channelize", "wifirx_channelizer_table", "wifirx_combine", "wifirx_diversity_combine",
     "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi", "wifirx_irs_taps", "wifirx_irs_sweep",
     "wifirx_irs_taps_multi", "wifirx_irs_sweep_multi", "wifirx_irs_estimate", "wifirx_irs_optimize",
+    "wifirx_irs_optimize_weighted",
 ]
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
@@ -244,6 +245,8 @@ _lib.wifirx_irs_estimate.argtypes = _lib.wifirx_irs_taps_multi.argtypes[:13] + [
     C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.wifirx_irs_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                      C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.wifirx_irs_optimize_weighted.argtypes = _lib.wifirx_irs_optimize.argtypes[:5] + [C.c_void_p, C.c_int, C.c_uint32] + \
+    _lib.wifirx_irs_optimize.argtypes[5:]
 _lib.wifirx_resampler_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_mac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                   C.c_uint64, C.c_void_p, C.c_uint32]
@@ -1003,7 +1006,8 @@ class WifiRx:
 
     # -- the joint phase decision over antennas and taps (wifirx_irs_optimize; NUMERICS.md rule 30) --
     def irs_optimize_dev(self, coef_ptr, n_sets, n_rows, n_cols, *, bits=2, max_sweeps=4, start="ref", direct_blocked=False,
-                         codes_in=None, n_elems=None, group=None, codes_ptr=None, psi_ptr=None, power_ptr=None, sweeps_ptr=None):
+                         codes_in=None, n_elems=None, group=None, codes_ptr=None, psi_ptr=None, power_ptr=None, sweeps_ptr=None,
+                         weights=None, weights_ptr=None, n_weight_sets=1):
         """wifirx_irs_optimize on device memory: cyclic coordinate ascent on the power an MRC receiver collects, over the
         B = bits codes of the G = n_cols - 1 groups, on the coefficient matrix at coef_ptr (complex64 [n_sets, n_rows, n_cols]
         in the layout of irs_estimate_dev's est_ptr: column 0 the direct term, column g + 1 group g).  start: "ref" (the
@@ -1013,7 +1017,12 @@ class WifiRx:
         N = G; irs_taps_multi_dev reads them as psi=ptr, n_psi_sets=n_sets), the collected power behind the start and behind
         every sweep to power_ptr (float32 [n_sets, max_sweeps + 1]), the number of sweeps that changed a code to sweeps_ptr
         (uint8 [n_sets]).  Each is an int device pointer, a DevBuf or None; codes_ptr or psi_ptr at least.  Asynchronous on the
-        handle's stream."""
+        handle's stream.
+
+        With weights the call is wifirx_irs_optimize_weighted (NUMERICS.md rule 31): the ascent is on sum_rho w_rho |s_rho|^2, a
+        real weight of either sign on every row, a row of weight 0 absent.  ``weights`` is a host float32 array [n_rows]
+        (irs.row_weights); ``weights_ptr`` a device pointer or DevBuf to float32 [n_weight_sets, n_rows], n_weight_sets 1 or
+        n_sets (set r reads block r % n_weight_sets).  One of the two at most; with neither the call is wifirx_irs_optimize."""
         ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
         if start not in IRS_STARTS:
             raise ValueError("start must be ref, given or zero")
@@ -1023,15 +1032,31 @@ class WifiRx:
             if n_elems is not None and grp.size != int(n_elems):
                 raise ValueError("group must hold one value per element")
         N = int(n_elems) if n_elems is not None else (grp.size if grp is not None else int(n_cols) - 1)
+        if weights is not None or weights_ptr is not None:
+            if weights is not None and weights_ptr is not None:
+                raise ValueError("give weights (host) or weights_ptr (device), not both")
+            w = None
+            if weights is not None:
+                w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+                if w.size != int(n_rows) or int(n_weight_sets) != 1:
+                    raise ValueError("host weights hold one value per row; per-set weights go through weights_ptr")
+            self._check(_lib.wifirx_irs_optimize_weighted(
+                self._h, ptr(coef_ptr), int(n_sets), int(n_rows), int(n_cols), _np_ptr(w) if w is not None else ptr(weights_ptr),
+                0 if w is not None else 1, int(n_weight_sets), int(bits), int(max_sweeps), IRS_STARTS[start],
+                int(bool(direct_blocked)), ptr(codes_in), N, _np_ptr(grp), ptr(codes_ptr), ptr(psi_ptr), ptr(power_ptr),
+                ptr(sweeps_ptr)))
+            return
         self._check(_lib.wifirx_irs_optimize(self._h, ptr(coef_ptr), int(n_sets), int(n_rows), int(n_cols), int(bits),
                                              int(max_sweeps), IRS_STARTS[start], int(bool(direct_blocked)), ptr(codes_in), N,
                                              _np_ptr(grp), ptr(codes_ptr), ptr(psi_ptr), ptr(power_ptr), ptr(sweeps_ptr)))
 
     def irs_optimize(self, coef, *, bits=2, max_sweeps=4, start="ref", direct_blocked=False, codes_in=None, group=None,
-                     n_elems=None, want=("codes", "psi", "power", "sweeps")):
+                     n_elems=None, want=("codes", "psi", "power", "sweeps"), weights=None):
         """irs_optimize_dev with host arrays: coef complex64 [n_sets, R, J] (or [R, J]: one set), codes_in uint8 [n_sets, G]
         with start="given".  Returns a dict with the outputs named in `want`: "codes" uint8 [n_sets, G], "psi" complex64
-        [n_sets, N], "power" float32 [n_sets, max_sweeps + 1], "sweeps" uint8 [n_sets]; codes or psi at least."""
+        [n_sets, N], "power" float32 [n_sets, max_sweeps + 1], "sweeps" uint8 [n_sets]; codes or psi at least.  weights: None
+        (wifirx_irs_optimize), float32 [R] (host weights of wifirx_irs_optimize_weighted) or [n_sets, R] (uploaded for the call
+        and read as device weights, one row block per set)."""
         q = np.asarray(coef, dtype=np.complex64)
         q = np.ascontiguousarray(q[None] if q.ndim == 2 else q)
         if q.ndim != 3:
@@ -1055,10 +1080,20 @@ class WifiRx:
                 if ci.shape != (n_sets, G):
                     raise ValueError("codes_in must be [n_sets, G]")
                 bufs["codes_in"] = self.alloc(max(ci.nbytes, 8)).upload(ci)
+            wkw = {}
+            if weights is not None:
+                w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
+                if w.shape == (R,):
+                    wkw = dict(weights=w)
+                elif w.shape == (n_sets, R):
+                    bufs["weights"] = self.alloc(max(w.nbytes, 8)).upload(w)
+                    wkw = dict(weights_ptr=bufs["weights"], n_weight_sets=n_sets)
+                else:
+                    raise ValueError("weights must be [R] or [n_sets, R]")
             self.irs_optimize_dev(bufs["coef"], n_sets, R, J, bits=bits, max_sweeps=max_sweeps, start=start,
                                   direct_blocked=direct_blocked, codes_in=bufs.get("codes_in"), n_elems=N, group=group,
                                   codes_ptr=bufs.get("codes"), psi_ptr=bufs.get("psi"), power_ptr=bufs.get("power"),
-                                  sweeps_ptr=bufs.get("sweeps"))
+                                  sweeps_ptr=bufs.get("sweeps"), **wkw)
             return {w: bufs[w].download(shapes[w][0], int(np.prod(shapes[w][1]))).reshape(shapes[w][1]) for w in want}
         finally:
             for b in bufs.values():

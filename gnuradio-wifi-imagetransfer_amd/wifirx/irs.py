@@ -206,6 +206,32 @@ def est_scale(n_pilots, sigma=0.0, mmse=False):
     return F32(1.0 / (t + float(sigma) ** 2)) if mmse else F32(1.0 / t)
 
 
+def row_weights(antennas, taps, tap=None, ant=None):
+    """The row weights of wifirx_irs_optimize_weighted (NUMERICS.md rule 31) for M = antennas and L = taps: float32 [M L] with
+    w_{m L + l} = ant[m] * tap[l], the product formed in float32, and ones where a factor is None.  ``tap`` holds L values
+    (:func:`tap_weights`), ``ant`` M values (1 / sigma_m^2 for per-antenna noise weights)."""
+    m, l = int(antennas), int(taps)
+    if m < 1 or l < 1:
+        raise ValueError("antennas and taps must be >= 1")
+    a = np.ones(m, F32) if ant is None else np.asarray(ant, dtype=F32).reshape(-1)
+    t = np.ones(l, F32) if tap is None else np.asarray(tap, dtype=F32).reshape(-1)
+    if a.size != m or t.size != l:
+        raise ValueError("ant must hold one value per antenna and tap one value per tap")
+    return np.ascontiguousarray((a[:, None] * t[None, :]).reshape(-1))
+
+
+def tap_weights(taps, keep=1, penalty=0.0):
+    """Weights over the L = taps taps of one antenna: ``keep`` ones followed by ``-penalty``.  keep=1, penalty=0 aligns tap 0
+    alone and leaves the other taps incoherent; a positive penalty also lowers the energy of the later taps, which is what makes
+    the notches.  float32 [L]."""
+    l, k = int(taps), int(keep)
+    if l < 1 or not 0 <= k <= l:
+        raise ValueError("taps must be >= 1 and keep 0..taps")
+    w = np.full(l, -float(penalty), F32)
+    w[:k] = 1.0
+    return w
+
+
 @dataclass
 class IrsConfig:
     """What ``block.channel_model(irs=...)`` needs to draw its taps from wifirx_irs_taps.  The surface is given either by its
@@ -224,7 +250,11 @@ class IrsConfig:
 
     ``decision`` says how the codes are decided from the estimate: "ref" (the default: rule 29's decision on antenna 0, tap 0) or
     "joint" (wifirx_irs_optimize, NUMERICS.md rule 30: at most ``sweeps`` = 0..16 sweeps of coordinate ascent on the power summed
-    over every antenna and tap, started from the "ref" codes).  "joint" requires ``pilots``."""
+    over every antenna and tap, started from the "ref" codes).  "joint" requires ``pilots``.
+
+    ``tap_weights`` ([L], L the length of ``pdp``) and ``ant_weights`` ([antennas]) put a signed weight on every row of the joint
+    decision (wifirx_irs_optimize_weighted, NUMERICS.md rule 31: :func:`row_weights` of the two, ones where one is None).  Both
+    need ``decision="joint"`` and finite values; with both None the decision is rule 30's."""
     scale: int | None = None
     irs_pos: tuple | None = None
     ap_pos: tuple | None = None
@@ -249,6 +279,8 @@ class IrsConfig:
     est_scale: float | None = None
     decision: str = "ref"
     sweeps: int = 4
+    tap_weights: tuple | None = None
+    ant_weights: tuple | None = None
     n_elems: int = field(init=False, default=0)
 
     def __post_init__(self):
@@ -298,6 +330,16 @@ class IrsConfig:
             raise ValueError("sweeps must be 0..16")
         if self.decision == "joint" and self.pilots is None:
             raise ValueError("decision=joint needs pilots")
+        for name, n in (("tap_weights", self.pdp.size), ("ant_weights", self.antennas)):
+            w = getattr(self, name)
+            if w is None:
+                continue
+            if self.decision != "joint":
+                raise ValueError("%s needs decision=joint" % name)
+            w = np.asarray(w, dtype=np.float32).reshape(-1)
+            if w.size != n or not np.isfinite(w).all():
+                raise ValueError("%s must hold %d finite values" % (name, n))
+            setattr(self, name, np.ascontiguousarray(w))
         if self.pilots is not None:
             if self.psi is not None or self.align_bits or self.codebook is not None:
                 raise ValueError("pilots exclude psi, align_bits and codebook")
@@ -335,6 +377,13 @@ class IrsConfig:
         self.refresh = int(self.refresh)
         if self.refresh < 1:
             raise ValueError("refresh must be >= 1 sample")
+
+    @property
+    def row_weights(self):
+        """float32 [antennas * taps] for wifirx_irs_optimize_weighted, or None when neither weight is given (rule 30)"""
+        if self.tap_weights is None and self.ant_weights is None:
+            return None
+        return row_weights(self.antennas, self.pdp.size, tap=self.tap_weights, ant=self.ant_weights)
 
     def set_psi(self, psi):
         if psi is None:

@@ -674,8 +674,8 @@ int  wifirx_irs_estimate(wifirx_handle* h, float* taps_out, uint32_t n_ant, uint
  *     stopping   a sweep that changes no code ends the call (every later sweep would repeat it bit for bit); the remaining power
  *                entries repeat the last value; sweeps_out is the number of sweeps that changed a code
  * With direct_blocked d_rho = +0 and column 0 is not read (wifirx_irs_estimate's direct_gain = 0).  max_sweeps = 0 with
- * WIFIRX_IRS_START_REF gives wifirx_irs_estimate's codes.  Per-antenna noise weights, other objectives, R > 128, random restarts
- * and other element orders are not offered.
+ * WIFIRX_IRS_START_REF gives wifirx_irs_estimate's codes.  Per-antenna noise weights and weights over the taps are
+ * wifirx_irs_optimize_weighted (below); other objectives, R > 128, random restarts and other element orders are not offered.
  *   coef         DEVICE complex64 [n_sets][n_rows][n_cols] (8-byte aligned): Q.  1 <= n_rows <= 128, 2 <= n_cols <= 1024.
  *   bits         B in {1, 2, 3}.   max_sweeps  0..16.
  *   codes_in     DEVICE uint8 [n_sets][G], required with WIFIRX_IRS_START_GIVEN and not read otherwise.
@@ -698,6 +698,48 @@ int  wifirx_irs_optimize(wifirx_handle* h, const float* coef /* DEVICE [n_sets][
                          const uint8_t* codes_in /* DEVICE [n_sets][G] or NULL */,
                          uint32_t n_elems, const uint16_t* group /* HOST [N] or NULL = identity, needs N == G */,
                          uint8_t* codes_out, float* psi_out, float* power_out /* [n_sets][max_sweeps+1] */, uint8_t* sweeps_out);
+
+/* The joint phase decision with a real weight of either sign on every row: cyclic coordinate ascent on
+ *     P_w = sum_rho w_rho |d_rho + sum_g e_{rho,g} C_{c_g}|^2;
+ * arithmetic = NUMERICS.md rule 31, which is rule 30 (wifirx_irs_optimize, above) with three additions and nothing else changed.
+ * Because |C_c| = 1, for one group P_w(c) = const + 2 Re(z C_c) with z = sum_rho w_rho conj(r_rho) e_rho, so every step is still
+ * wifirx_irs_taps' argmax and still maximises P_w over that code exactly, for negative weights too: the ascent stays monotone
+ * and the early exit stays valid.
+ *     weights    w_rho float32, one per row rho = m L + l.  A row with w_rho == 0 (either sign of zero) is absent from both sums
+ *                below: its term is +0, selected and not multiplied, so a non-finite coefficient in an unweighted row cannot
+ *                reach a decision.  The state s_rho of such a row is still carried.
+ *     z          t_rho = ch_mul(conj(r_rho), e_rho) as in rule 30, then tw_rho = (w_rho t.re, w_rho t.im): one float32 multiply
+ *                per part behind the product, no fma; lane i forms tw_i + tw_{i+64} (absent rows are +0), then the butterfly
+ *                (lane xor 32, 16, 8, 4, 2, 1) and the argmax, unchanged
+ *     power      q_rho = s.re s.re + s.im s.im as in rule 30, then w_rho q_rho, the same lane pairing and butterfly: power_out
+ *                carries P_w, which may be negative
+ *     the rest   WIFIRX_IRS_START_REF stays wifirx_irs_estimate's decision on row 0, whatever w_0 is; the state update, "s stays
+ *                as it was", the stopping rule and sweeps_out are rule 30's
+ * Uses: w = (1, 0, .., 0) per antenna aligns tap 0 jointly over the antennas and leaves the other taps incoherent;
+ * w = (1, -lambda, ..) also penalises the energy that makes the notches; w_m = 1 / sigma_m^2 are per-antenna noise weights
+ * (Python: wifirx.irs.row_weights, wifirx.irs.tap_weights).  Exactly: with every weight 1.0f the outputs are
+ * wifirx_irs_optimize's bit for bit (a NaN stays a NaN); with every weight the same 2^k (no overflow or underflow) the codes and
+ * sweeps are wifirx_irs_optimize's and the power is 2^k times its power; rows of weight zero give the same bits whatever they
+ * hold (row 0 is still read by WIFIRX_IRS_START_REF), the same bits as the call with those rows zeroed and, when they are the last
+ * rows, as the call with fewer rows.  Weights estimated by the library, objectives that are not a weighted sum of row powers,
+ * R > 128, random restarts and other element orders are not offered.
+ *   weight       weight_on_device = 0: HOST float32 [n_rows], every value finite, n_weight_sets = 1; it is uploaded with the group
+ *                map in the one upload.  Otherwise DEVICE float32 [n_weight_sets][n_rows] (4-byte aligned), n_weight_sets 1 or
+ *                n_sets: set r reads row block r % n_weight_sets.  Device weights are not inspected: the arithmetic above says
+ *                what a NaN weight does (w != 0 holds, the term is NaN).
+ *   the other arguments   as wifirx_irs_optimize.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for every case of wifirx_irs_optimize, a NULL weight,
+ * n_weight_sets outside {1, n_sets} or != 1 with host weights, a non-finite host weight, a misaligned weight; WIFIRX_ERANGE for
+ * more than 2^31 - 1 sets.  n_sets = 0 does nothing and returns WIFIRX_OK.  One kernel launch per call, after one upload of the
+ * group map and the host weights (none without either).  ORDER: as wifirx_channel. */
+int  wifirx_irs_optimize_weighted(wifirx_handle* h, const float* coef /* DEVICE [n_sets][R][J] complex64 */, uint32_t n_sets,
+                                  uint32_t n_rows, uint32_t n_cols,
+                                  const float* weight /* HOST [R], or DEVICE [n_weight_sets][R] */, int weight_on_device,
+                                  uint32_t n_weight_sets, uint32_t bits, uint32_t max_sweeps, int start, int direct_blocked,
+                                  const uint8_t* codes_in /* DEVICE [n_sets][G] or NULL */,
+                                  uint32_t n_elems, const uint16_t* group /* HOST [N] or NULL = identity, needs N == G */,
+                                  uint8_t* codes_out, float* psi_out, float* power_out /* [n_sets][max_sweeps+1] */,
+                                  uint8_t* sweeps_out);
 
 /* ieee802_11.mac (gnu_radio/IRS_user.py:192,204-205; IRS_tranceiver.py:271,313-314) for a batch: PSDU i, at
  * psdu + i * psdu_stride, is the 24 + payload_len[i] + 4 bytes

@@ -10,7 +10,13 @@ rows of the result give the time per step of the chain and the bytes per second 
 
 Shapes (M, L, N): (1, 1, 64), (4, 1, 64), (4, 8, 64), (4, 8, 256).  Prints one JSON line, writes it to --out when given.
 
-    python tools/irs_optimize_bench.py [--iters 10] [--out profiles/irs_optimize_config.json]"""
+--weights times wifirx_irs_optimize_weighted (NUMERICS.md rule 31) beside wifirx_irs_optimize on the same coefficients in the same
+process: host weights (1, -0.5, ..) per antenna, which ride in the call's one upload, and the same weights as a device buffer of
+one row block; the chain of a step grows by two multiplies and a select.  --old-lib PATH also times wifirx_irs_optimize of another
+build of the library (the parent commit's), loaded beside this one, on the same device buffers through a handle of its own.
+
+    python tools/irs_optimize_bench.py [--iters 10] [--out profiles/irs_optimize_config.json]
+    python tools/irs_optimize_bench.py --weights [--old-lib PATH] [--out profiles/irs_optimize_w_config.json]"""
 import argparse
 import ctypes as C
 import json
@@ -33,6 +39,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--weights", action="store_true", help="time wifirx_irs_optimize_weighted beside wifirx_irs_optimize")
+    ap.add_argument("--old-lib", default=None, help="another build of libwifirx.so whose wifirx_irs_optimize is timed too")
     a = ap.parse_args()
     hip = C.CDLL("libamdhip64.so")
     rx = capi.WifiRx(max_sym=1, device=0)
@@ -43,9 +51,19 @@ def main():
     hip.hipEventSynchronize.argtypes = [C.c_void_p]
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
 
-    def timed(fn):
+    old = old_h = old_st = None
+    if a.old_lib:                                               # a handle of the other build, on a stream of its own
+        old, old_h = C.CDLL(os.path.abspath(a.old_lib)), C.c_void_p()
+        old.wifirx_create.argtypes = [C.POINTER(capi.Config), C.POINTER(C.c_void_p)]
+        old.wifirx_stream.restype, old.wifirx_stream.argtypes = C.c_void_p, [C.c_void_p]
+        old.wifirx_destroy.argtypes = old.wifirx_sync.argtypes = [C.c_void_p]
+        old.wifirx_irs_optimize.argtypes = capi.lib().wifirx_irs_optimize.argtypes
+        assert old.wifirx_create(C.byref(rx.cfg), C.byref(old_h)) == 0
+        old_st = C.c_void_p(old.wifirx_stream(old_h))
+
+    def timed(fn, st=st, sync=rx.sync):
         fn()                                                    # the warm-up
-        rx.sync()
+        sync()
         ms = []
         for _ in range(a.iters):
             assert hip.hipEventRecord(ev0, st) == 0
@@ -72,6 +90,24 @@ def main():
         kw["pilots"] = rx.alloc(pl.nbytes).upload(pl)
         est = timed(lambda: rx.irs_estimate_dev(taps, n, pdp, b2r, r2u, b2u, align_bits=BITS, codes_ptr=codes, est_ptr=coef, **kw))
         opt = timed(lambda: rx.irs_optimize_dev(coef, n, R, J, bits=BITS, max_sweeps=SWEEPS, codes_ptr=codes, psi_ptr=psi))
+        extra = {}
+        if a.weights:
+            w = irs.row_weights(M, L, tap=irs.tap_weights(L, penalty=0.5))
+            d_w = rx.alloc(w.nbytes).upload(w)
+            okw = dict(bits=BITS, max_sweeps=SWEEPS, codes_ptr=codes, psi_ptr=psi)
+            host = timed(lambda: rx.irs_optimize_dev(coef, n, R, J, weights=w, **okw))
+            dev = timed(lambda: rx.irs_optimize_dev(coef, n, R, J, weights_ptr=d_w, **okw))
+            again = timed(lambda: rx.irs_optimize_dev(coef, n, R, J, **okw))     # the unweighted call once more, behind the two
+            extra = {"weights": w.tolist(), "weighted_host_weights": host, "weighted_device_weights": dev,
+                     "optimize_again": again, "ratio_weighted_host_over_optimize": host["median_ms"] / opt["median_ms"],
+                     "ratio_weighted_device_over_optimize": dev["median_ms"] / opt["median_ms"]}
+            d_w.free()
+        if old is not None:
+            call = lambda: old.wifirx_irs_optimize(old_h, coef.ptr, n, R, J, BITS, SWEEPS, capi.IRS_START_REF, 0, None, N, None,
+                                                   codes.ptr, psi.ptr, None, None)
+            assert call() == 0
+            was = timed(call, old_st, lambda: old.wifirx_sync(old_h))
+            extra |= {"optimize_of_old_lib": was, "ratio_optimize_over_old_lib": opt["median_ms"] / was["median_ms"]}
         rx.irs_optimize_dev(coef, n, R, J, bits=BITS, max_sweeps=SWEEPS, codes_ptr=codes, power_ptr=power, sweeps_ptr=sweeps)
         done = sweeps.download(np.uint8, n).astype(np.float64)
         pw = power.download(np.float32, n * (SWEEPS + 1)).reshape(n, SWEEPS + 1).astype(np.float64)
@@ -82,13 +118,16 @@ def main():
                "sweeps_that_changed_a_code_mean": float(done.mean()), "passes_over_the_matrix_mean": passes,
                "power_ratio_last_over_start": float(pw[:, -1].sum() / pw[:, 0].sum()),
                "coef_bytes": n * R * J * 8, "read_gb_per_s": n * R * J * 8 * passes / sec / 1e9,
-               "ns_per_step_of_a_wave": sec / (passes * N) * 1e9, "waves": n}
+               "ns_per_step_of_a_wave": sec / (passes * N) * 1e9, "waves": n} | extra
         rows.append(row)
         print(json.dumps({k: row[k] for k in ("n_ant", "n_taps", "n_elems", "ratio_optimize_over_estimate", "read_gb_per_s",
                                               "ns_per_step_of_a_wave", "power_ratio_last_over_start")}
-                         | {"optimize_ms": opt["median_ms"], "estimate_ms": est["median_ms"]}), file=sys.stderr)
+                         | {"optimize_ms": opt["median_ms"], "estimate_ms": est["median_ms"]}
+                         | {k: v for k, v in extra.items() if k.startswith("ratio")}), file=sys.stderr)
         for b in (taps, codes, coef, psi, power, sweeps, kw["pilots"]):
             b.free()
+    if old is not None:
+        old.wifirx_destroy(old_h)
     rx.close()
     res = {"what": __doc__.split("\n\n")[0].replace("\n", " "), "iters": a.iters, "bits": BITS, "sigma": SIGMA, "runs": rows}
     print(json.dumps(res))

@@ -64,14 +64,18 @@ the combiner) and mode.  The counts nest: A antennas are the first A of the larg
 taps per frame, made on the device and read there by wifirx_channel; FER against the surface size at SNRs of one unit-power path.
 --irs-mode: random phases, the one configuration aligned to the geometry, the genie aligned per draw, `estimate`: a surface
 trained per draw from a noisy pilot-based channel estimate (wifirx_irs_estimate; --irs-pilots, --pilot-snr-db, --irs-group; with
---irs-decision joint the codes are decided over every antenna and tap by wifirx_irs_optimize, --pilot-snr-db inf is its genie bound), or `sweep`: a surface
+--irs-decision joint the codes are decided over every antenna and tap by wifirx_irs_optimize, --pilot-snr-db inf is its genie bound;
+--irs-tap-weights W0 [W1 ...] and --irs-ant-weights add arms decided by wifirx_irs_optimize_weighted, rule 31, reported as mode
+estimate_joint_w with the rows' weights in the record; --irs-taps sets the tap count; every point carries the tap-0 power and the
+median over the sets of the weakest subcarrier's power over the mean of the MRC-combined spectrum), or `sweep`: a surface
 trained per draw by a codebook sweep (wifirx_irs_sweep, rule 26; --irs-codebook dft / dft2 / traverse, quantised to --irs-bits).
 --irs 0 is the direct path alone.
 
     python tools/loopback_per.py --irs 0 16 64 256 --irs-bits 2 --irs-mode random los genie --k-factor 3 --direct-db -inf --psdu-len 294 --encoding 2 --snr -20 -10 0 [--frames 65536] [--out profiles/loopback_irs.json]
     python tools/loopback_per.py --irs 64 256 --irs-bits 2 --irs-mode random los genie sweep --irs-codebook dft2 --k-factor 3 --psdu-len 294 --encoding 2 --snr -30 -20 -10 [--out profiles/loopback_irs_sweep.json]
     python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode random sweep estimate genie --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_estimate.json]
-    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode estimate --irs-decision ref joint --antennas 1 2 4 --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_optimize.json]"""
+    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode estimate --irs-decision ref joint --antennas 1 2 4 --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_optimize.json]
+    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode estimate --irs-decision ref joint --irs-tap-weights 1 0 --irs-tap-weights 1 -1 [--irs-taps 1] --antennas 1 2 4 --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 --frames 16384 (the four runs of profiles/loopback_irs_optimize_w.json)"""
 import argparse
 import json
 import math
@@ -157,12 +161,24 @@ def main():
                     help="with --irs-mode estimate: the codes decided on antenna 0, tap 0 (wifirx_irs_estimate's own decision) or "
                          "jointly over antennas and taps (wifirx_irs_optimize, NUMERICS.md rule 30; reported as mode estimate_joint)")
     ap.add_argument("--irs-sweeps", type=int, default=4, help="with --irs-decision joint: the most sweeps, 0 .. 16")
+    ap.add_argument("--irs-tap-weights", type=float, nargs="+", action="append", default=None, metavar="W",
+                    help="with --irs-decision joint: also decide with these weights over the taps, W0 [W1 ...], the last value "
+                         "repeated up to the tap count (wifirx_irs_optimize_weighted, NUMERICS.md rule 31; reported as mode "
+                         "estimate_joint_w); may be given several times, one arm each")
+    ap.add_argument("--irs-ant-weights", type=float, nargs="+", default=None, metavar="W",
+                    help="with --irs-decision joint: weights over the antennas for the estimate_joint_w arms, the last value "
+                         "repeated up to the antenna count (alone: one arm with every tap weight 1)")
+    ap.add_argument("--irs-taps", type=int, default=8, help="with --irs: the taps of the power delay profile exp(-l/2), 1 .. 16")
     ap.add_argument("--irs-codebook", choices=("dft", "dft2", "traverse"), default="dft2",
                     help="with --irs-mode sweep: irs.dft_codebook at over = 1 / 2, or the reference controller's 10 x 10 grid "
                          "(irs.traverse_codebook), quantised to --irs-bits")
     ap.add_argument("--direct-db", type=float, default=float("-inf"), help="with --irs: gain of the direct path in dB (-inf: blocked)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if (a.irs_tap_weights or a.irs_ant_weights) and "joint" not in a.irs_decision:
+        raise SystemExit("--irs-tap-weights and --irs-ant-weights need --irs-decision joint")
+    if not 1 <= a.irs_taps <= capi.IRS_MAX_TAPS:
+        raise SystemExit("--irs-taps 1 .. %d" % capi.IRS_MAX_TAPS)
     if a.irs is not None and a.antennas is not None:
         return irs_multi_main(a)
     if a.irs is not None:
@@ -542,6 +558,15 @@ def fading_main(a):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def flatness(planes):
+    """DESIGN.md 9n's figure, on the host from downloaded taps [antennas, sets, L]: per set the weakest over the mean of the
+    MRC-combined spectrum sum_m |H_m[k]|^2 on the 52 occupied subcarriers (k = -26 .. 26 without 0) of the 64-point transform of
+    the taps; the median over the sets"""
+    spec = (np.abs(np.fft.fft(planes, 64, axis=2)) ** 2).sum(axis=0)
+    used = spec[:, np.r_[1:27, 38:64]]
+    return float(np.median(used.min(axis=1) / used.mean(axis=1)))
+
+
 def estimate_keywords(a, S):
     """--irs-mode estimate: the keywords of irs_estimate_dev for an S x S surface, and what the result file says about them"""
     from wifirx import irs
@@ -560,16 +585,17 @@ def estimate_keywords(a, S):
 def estimate_taps(rx, a, decision, d_taps, n, pdp, b2r, r2u, b2u, est_kw, kw):
     """--irs-mode estimate: the taps of n sets at d_taps under the codes decided from the estimate -- by wifirx_irs_estimate itself
     (ref), or by estimate -> wifirx_irs_optimize -> wifirx_irs_taps_multi queued on the handle's stream (joint)"""
-    if decision != "joint":
+    if decision == "ref":
         rx.irs_estimate_dev(d_taps, n, pdp, b2r, r2u, b2u, **est_kw, **kw)
         return
     M, N = (1 if np.ndim(b2r) == 1 else np.shape(b2r)[0]), np.shape(b2r)[-1]
+    weights = None if decision == "joint" else row_weights_of(a, decision[1], M, len(pdp))     # ("joint_w", tap weights or None)
     R, J = M * len(pdp), est_kw["pilots"].shape[1] + 1
     coef, psi = rx.alloc(n * R * J * 8), rx.alloc(n * N * 8)
     try:
         rx.irs_estimate_dev(None, n, pdp, b2r, r2u, b2u, est_ptr=coef, **dict(est_kw, align_bits=0), **kw)
         rx.irs_optimize_dev(coef, n, R, J, bits=est_kw["align_bits"], max_sweeps=a.irs_sweeps, start="ref",
-                            direct_blocked=kw["direct_gain"] == 0.0, n_elems=N, group=est_kw["group"], psi_ptr=psi)
+                            direct_blocked=kw["direct_gain"] == 0.0, n_elems=N, group=est_kw["group"], psi_ptr=psi, weights=weights)
         rx.irs_taps_multi_dev(d_taps, n, pdp, b2r, r2u, b2u, psi=psi, n_psi_sets=n, **kw)
         rx.sync()
     finally:
@@ -577,12 +603,29 @@ def estimate_taps(rx, a, decision, d_taps, n, pdp, b2r, r2u, b2u, est_kw, kw):
         psi.free()
 
 
+def stretch(values, n):
+    """W0 [W1 ...] of the command line as n values: the last one repeats"""
+    v = list(values)[:n]
+    return v + [v[-1]] * (n - len(v))
+
+
+def row_weights_of(a, tap, M, L):
+    """the rows' weights of an estimate_joint_w arm: irs.row_weights of the stretched --irs-tap-weights and --irs-ant-weights"""
+    from wifirx import irs
+    return irs.row_weights(M, L, tap=None if tap is None else stretch(tap, L),
+                           ant=None if a.irs_ant_weights is None else stretch(a.irs_ant_weights, M))
+
+
 def expand_modes(a, modes):
-    """(mode, decision, label) per run: --irs-mode estimate once per --irs-decision, the joint one reported as estimate_joint"""
+    """(mode, decision, label) per run: --irs-mode estimate once per --irs-decision, the joint one reported as estimate_joint and
+    once more per --irs-tap-weights (or once for --irs-ant-weights alone) as estimate_joint_w, decision ("joint_w", tap weights)"""
     out = []
     for m in modes:
         if m == "estimate":
             out += [(m, d, "estimate" if d == "ref" else "estimate_joint") for d in a.irs_decision]
+            if "joint" in a.irs_decision:
+                arms = a.irs_tap_weights or ([None] if a.irs_ant_weights else [])
+                out += [(m, ("joint_w", t), "estimate_joint_w") for t in arms]
         else:
             out.append((m, None, m))
     return out
@@ -604,7 +647,7 @@ def irs_main(a):
     slot = LEAD + txgen.frame_samples(plen, enc) + 79
     slot += slot & 1
     stride = (plen + 15) // 16 * 16
-    L = 8
+    L = a.irs_taps
     pdp = np.exp(-np.arange(L) / 2.0)
     pdp = (pdp / pdp.sum()).astype(np.float32)
     rx = capi.WifiRx(max_sym=n_sym, llr_bits=0, chan_est=capi.EQ_LS, device=0)
@@ -653,7 +696,8 @@ def irs_main(a):
                            "histogram": {str(k): int(hist[k]) for k in np.nonzero(hist)[0]}}
             else:
                 rx.irs_taps_dev(d_taps, n, pdp, b2r, r2u, b2u, **kw)
-            mean_power = float((np.abs(d_taps.download(np.complex64, min(n, 65536) * L).astype(np.complex128)) ** 2).sum() / min(n, 65536))
+            sets = d_taps.download(np.complex64, min(n, 65536) * L).reshape(1, -1, L).astype(np.complex128)
+            mean_power, tap0, flat = float((np.abs(sets) ** 2).sum() / sets.shape[1]), float((np.abs(sets[..., 0]) ** 2).mean()), flatness(sets)
             for snr in a.snr:
                 t0 = time.perf_counter()
                 rx.channel_dev(rows.ptr, iq.ptr, n * slot, n, row_len=slot, taps=d_taps.ptr, n_taps=L, n_tap_sets=n,
@@ -662,8 +706,11 @@ def irs_main(a):
                 rx.decode_batch_dev(n, dev)
                 r = rx.link_stats(n, dev, ref)
                 points.append({"n_elems": N, "mode": label, "snr_db": snr, "frames": n, "fer": r["fer"], "coded_ber": r["coded_ber"],
-                               "mean_channel_power": mean_power, "seconds": time.perf_counter() - t0,
+                               "mean_channel_power": mean_power, "mean_tap0_power": tap0,
+                               "median_weakest_subcarrier_over_mean": flat, "seconds": time.perf_counter() - t0,
                                "counts": {k: r[k] for k in COUNTERS}})
+                if label == "estimate_joint_w":
+                    points[-1]["row_weights"] = row_weights_of(a, decision[1], 1, L).tolist()
                 if winners is not None:
                     points[-1]["training" if mode == "estimate" else "winners"] = winners
                 print(json.dumps({k: points[-1][k] for k in ("n_elems", "mode", "snr_db", "fer", "mean_channel_power")}), file=sys.stderr)
@@ -673,8 +720,8 @@ def irs_main(a):
     rows.free(); iq.free(); d_taps.free(); d_best.free(); rx.close()
     res = {"workload": "loop-back on the device over a reflecting surface (wifirx_irs_taps / wifirx_irs_sweep -> wifirx_channel, tap sets never leave the "
                        "device): %d distinct frames per point, one tap set per frame, encoding %d, PSDU %d B (%d symbols), rows of %d, "
-                       "lead 160, 8 taps (pdp exp(-l/2), sum 1), k_factor %g, direct path %s, %d-bit phases, LS, hard decode_mac"
-                       % (n, enc, plen, n_sym, slot, a.k_factor, "blocked" if direct_gain == 0 else "%g dB" % a.direct_db, bits),
+                       "lead 160, %d taps (pdp exp(-l/2), sum 1), k_factor %g, direct path %s, %d-bit phases, LS, hard decode_mac"
+                       % (n, enc, plen, n_sym, slot, L, a.k_factor, "blocked" if direct_gain == 0 else "%g dB" % a.direct_db, bits),
            "snr": "of one unit-power path (an element's leg, or the unattenuated direct path); n_elems 0 is the direct path alone at 0 dB",
            "modes": {"random": "one random configuration", "los": "the one configuration aligned to the geometry (irs.align)",
                      "genie": "aligned per draw on tap 0 (align_bits)",
@@ -684,7 +731,9 @@ def irs_main(a):
                                  "coefficient (wifirx_irs_estimate, NUMERICS.md rule 29); 'training' holds the pilots, the groups and "
                                  "the noise of one pilot observation",
                      "estimate_joint": "the same estimate, the codes decided jointly over the taps by at most %d sweeps of "
-                                       "wifirx_irs_optimize from the estimate's own decision (NUMERICS.md rule 30)" % a.irs_sweeps},
+                                       "wifirx_irs_optimize from the estimate's own decision (NUMERICS.md rule 30)" % a.irs_sweeps,
+                     "estimate_joint_w": "the same, decided by wifirx_irs_optimize_weighted on sum_rho w_rho |s_rho|^2 (NUMERICS.md rule "
+                                         "31); 'row_weights' holds w, rho = antenna * taps + tap"},
            "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
@@ -721,7 +770,7 @@ def irs_multi_main(a):
     slot = LEAD + txgen.frame_samples(plen, enc) + 79
     slot += slot & 1
     stride = (plen + 15) // 16 * 16
-    L = 8
+    L = a.irs_taps
     pdp = np.exp(-np.arange(L) / 2.0)
     pdp = (pdp / pdp.sum()).astype(np.float32)
     rx = capi.WifiRx(max_sym=n_sym, llr_bits=nb, want_carrier=True, chan_est=capi.EQ_LS, device=0)
@@ -759,6 +808,7 @@ def irs_multi_main(a):
                 k = min(n, 65536)
                 planes = d_taps.download(np.complex64, A * n * L).reshape(A, n, L)[:, :k].astype(np.complex128)
                 power = (np.abs(planes) ** 2).sum(axis=2).mean(axis=1)          # per antenna: the mean over the sets of sum_l |t|^2
+                tap0, flat = float((np.abs(planes[..., 0]) ** 2).sum(axis=0).mean()), flatness(planes)
                 for snr in a.snr:
                     t0 = time.perf_counter()
                     for ant in range(A):
@@ -776,8 +826,11 @@ def irs_multi_main(a):
                     soft = rx.link_stats(n, dev, ref)
                     points.append({"n_elems": N, "antennas": A, "mode": label, "snr_db": snr, "frames": n, "fer": hard["fer"],
                                    "fer_soft": soft["fer"], "mean_combined_channel_power": float(power.sum()),
-                                   "mean_channel_power_per_antenna": [float(v) for v in power], "seconds": time.perf_counter() - t0,
+                                   "mean_channel_power_per_antenna": [float(v) for v in power], "mean_combined_tap0_power": tap0,
+                                   "median_weakest_subcarrier_over_mean": flat, "seconds": time.perf_counter() - t0,
                                    "counts": {c: hard[c] for c in COUNTERS}, "counts_soft": {c: soft[c] for c in COUNTERS}})
+                    if label == "estimate_joint_w":
+                        points[-1]["row_weights"] = row_weights_of(a, decision[1], A, L).tolist()
                     if winners is not None:
                         points[-1]["training" if mode == "estimate" else "winners"] = winners
                     print(json.dumps({c: points[-1][c] for c in ("n_elems", "antennas", "mode", "snr_db", "fer", "fer_soft",
@@ -790,9 +843,9 @@ def irs_multi_main(a):
     res = {"workload": "the diversity receiver behind a reflecting surface, on the device (wifirx_irs_taps_multi / wifirx_irs_sweep_multi -> one "
                        "wifirx_channel per antenna on its plane -> LS demod -> wifirx_diversity_combine (%s) -> hard and soft decode_mac; the tap "
                        "sets never leave the device): %d distinct frames per point, one tap set per frame and antenna, encoding %d, PSDU %d B "
-                       "(%d symbols), rows of %d, lead 160, 8 taps (pdp exp(-l/2), sum 1), k_factor %g, direct path %s, %d-bit phases; the AP a "
+                       "(%d symbols), rows of %d, lead 160, %d taps (pdp exp(-l/2), sum 1), k_factor %g, direct path %s, %d-bit phases; the AP a "
                        "half-wavelength array along x (irs.los(antennas=A))"
-                       % (div, n, enc, plen, n_sym, slot, a.k_factor, "blocked" if direct_gain == 0 else "%g dB" % a.direct_db, bits),
+                       % (div, n, enc, plen, n_sym, slot, L, a.k_factor, "blocked" if direct_gain == 0 else "%g dB" % a.direct_db, bits),
            "snr": "of one unit-power path at one antenna; every antenna has noise of variance 1 from a seed of its own",
            "modes": {"random": "one random configuration", "genie": "aligned per draw on antenna 0, tap 0 (align_bits)",
                      "sweep": "trained per draw on the sum of the antennas' channel powers: the best entry of the %s codebook, quantised to "
@@ -800,7 +853,9 @@ def irs_multi_main(a):
                      "estimate": "trained per draw from a noisy pilot-based estimate, the codes decided on antenna 0, tap 0 "
                                  "(wifirx_irs_estimate, NUMERICS.md rule 29)",
                      "estimate_joint": "the same estimate, the codes decided jointly over antennas and taps by at most %d sweeps of "
-                                       "wifirx_irs_optimize from the estimate's own decision (NUMERICS.md rule 30)" % a.irs_sweeps},
+                                       "wifirx_irs_optimize from the estimate's own decision (NUMERICS.md rule 30)" % a.irs_sweeps,
+                     "estimate_joint_w": "the same, decided by wifirx_irs_optimize_weighted on sum_rho w_rho |s_rho|^2 (NUMERICS.md rule "
+                                         "31); 'row_weights' holds w, rho = antenna * taps + tap"},
            "antennas": counts, "stats": "wifirx_link_stats on the device; reported, not asserted",
            "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
