@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=1 << 20)
     ap.add_argument("--format", choices=("fc32", "sc16", "sc8"), default="fc32")
     ap.add_argument("--scale", type=float, default=None, help="integer formats: value of one integer step")
+    ap.add_argument("--dc-block", action="store_true", help="remove the recording's DC offset on the device (NUMERICS.md rule 32)")
+    ap.add_argument("--iq-correct", action="store_true", help="blind IQ-imbalance correction on the device (NUMERICS.md rule 32)")
     a = ap.parse_args()
     if a.format == "fc32":
         x = np.fromfile(a.iq, dtype=np.complex64)
@@ -46,7 +48,7 @@ def main():
         n[0] += 1
 
     rx = block.wifi_phy_rx(bandwidth=a.bandwidth, frequency=a.frequency, chan_est=a.chan_est, publish_carrier=False,
-                           sample_format=a.format, sample_scale=a.scale)
+                           sample_format=a.format, sample_scale=a.scale, dc_block=a.dc_block, iq_correct=a.iq_correct)
     pics = app.extract_pics(sink=on_piece)
     grshim.msg_connect(rx, "mac_out", pics, "MAC")
     grshim.run_stream(rx, x, chunk=a.chunk)

@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=1 << 20)
     ap.add_argument("--format", choices=("fc32", "sc16", "sc8"), default="fc32")
     ap.add_argument("--scale", type=float, default=None, help="integer formats: value of one integer step")
+    ap.add_argument("--dc-block", action="store_true", help="DC removal on every channel stream, behind the bank (NUMERICS.md rule 32)")
+    ap.add_argument("--iq-correct", action="store_true", help="blind IQ-imbalance correction on every channel stream (NUMERICS.md rule 32)")
     ap.add_argument("--out", default=None, help="draw the image pieces of all channels into this file")
     a = ap.parse_args()
     if a.format == "fc32":
@@ -52,7 +54,8 @@ def main():
         per_channel[pdu[0]["channel"]] += 1
 
     rx = block.wifi_phy_rx_wideband(a.channels, a.stacking, a.center_frequency, bandwidth=a.bandwidth, chan_est=a.chan_est,
-                                    publish_carrier=False, sample_format=a.format, sample_scale=a.scale)
+                                    publish_carrier=False, sample_format=a.format, sample_scale=a.scale, dc_block=a.dc_block,
+                                    iq_correct=a.iq_correct)
     grshim.msg_connect(rx, "mac_out", grshim.sink_block(on_pdu), "in")
     if a.out:
         grshim.msg_connect(rx, "mac_out", pics, "MAC")

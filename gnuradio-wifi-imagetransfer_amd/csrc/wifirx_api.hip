@@ -33,6 +33,7 @@
 #include "wr_irs_optimize.h"
 #include "wr_link.h"
 #include "wr_convert.h"
+#include "wr_frontend.h"
 #include "wr_channelizer.h"
 #include "wr_combiner.h"
 #include "wr_diversity.h"
@@ -135,6 +136,7 @@ struct Staging {
     DevBuf link_meta, link_payload; // wifirx_mac_batch: payload lengths; host payloads
     DevBuf link_counts;             // wifirx_link_stats: the nine counters
     DevBuf iq_clipped;              // wifirx_iq_from_f32: the counter of clipped components
+    DevBuf fe_table;                // wifirx_frontend and the stream's front end: the block sums of a call
 };
 
 // decode workspace
@@ -167,6 +169,10 @@ struct StreamState {
     std::string dead_msg;
     size_t   push_consumed = 0;     // wifirx_push_consumed
     bool     single = false;        // wifirx_push / wifirx_push_iq has handed in samples: no wifirx_push_diversity on this handle
+    bool     fe_on = false;         // wifirx_stream_frontend: the front end (NUMERICS.md rule 32) runs on the samples a pass appends
+    wifirx_frontend_cfg fe_cfg{};
+    DevBuf   fe_state, fe_saved;    // its state, and the state in front of the current pass (what StreamRollback puts back)
+    bool     fe_dirty = false;      // the current pass has advanced fe_state
 };
 
 // the diversity stream (wifirx_api_stream_div.inc): what it keeps beside the StreamState it shares with the single stream.
@@ -630,6 +636,7 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 }  // extern "C"
 
 #include "wifirx_api_decode.inc"
+#include "wifirx_api_frontend.inc"
 #include "wifirx_api_stream.inc"
 #include "wifirx_api_tx.inc"
 #include "wifirx_api_channel.inc"

@@ -123,6 +123,7 @@ struct StreamRollback {
     explicit StreamRollback(wifirx_handle* hh) : h(hh), sfill(hh->st.sfill), sprocessed(hh->st.sprocessed), sdetected(hh->st.sdetected),
         last_trig(hh->st.last_trig), n_pending(hh->st.pending.size())
     {
+        h->st.fe_dirty = false;
         std::lock_guard<std::mutex> lk(h->w.mu);
         samples_in = h->stats.samples_in;
         frames_detected = h->stats.frames_detected;
@@ -132,6 +133,16 @@ struct StreamRollback {
         if (!armed) return;
         h->st.sfill = sfill; h->st.sprocessed = sprocessed; h->st.sdetected = sdetected; h->st.last_trig = last_trig;
         h->st.pending.resize(n_pending);
+        // the front end's state as it was in front of the pass (stream_frontend_run saved it), behind whatever the pass queued.
+        // Should this copy itself fail, the state no longer matches the samples the caller repeats: the stream is dead.
+        if (h->st.fe_dirty && (hipMemcpyAsync(h->st.fe_state.p, h->st.fe_saved.p, sizeof(wifirx_frontend_state), hipMemcpyDeviceToDevice,
+                                              h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)) {
+            (void)hipGetLastError();
+            std::lock_guard<std::mutex> lk(h->w.mu);
+            h->st.dead = true;
+            h->st.dead_msg = "the stream's front-end state could not be restored after a failed pass (destroy the handle)";
+        }
+        h->st.fe_dirty = false;
         std::lock_guard<std::mutex> lk(h->w.mu);
         h->stats.samples_in = samples_in;
         h->stats.frames_detected = frames_detected;
@@ -401,17 +412,21 @@ static int stream_process(wifirx_handle* h, const void* iq, size_t n, int iq_on_
     // the scratch copy starts where its first whole 16-byte piece, behind the widen kernel's head sample, is 16-byte aligned
     const size_t native_off = bps ? (16 - (size_t)(st.sfill & 1) * bps) & 15 : 0;
     if (n && bps && !iq_on_device && (rc = stream_native_reserve(h, native_off + n * bps))) return rc;
+    if ((rc = stream_frontend_reserve(h, n))) return rc;
     StreamRollback undo(h);
+    // with the front end on (NUMERICS.md rule 32) it takes the place of the widening, or runs in place on the float pairs
+    float2* const d_new = st.sbuf.as<float2>() + st.sfill;
     if (n && bps) {
         const void* d_native = iq;
         if (!iq_on_device) {
             d_native = st.native.as<uint8_t>() + native_off;
             HIP_TRY(h, hipMemcpyAsync(st.native.as<uint8_t>() + native_off, iq, n * bps, hipMemcpyHostToDevice, h->stream));
         }
-        HIP_TRY(h, wr_launch_iq_widen(h->stream, d_native, fmt, n, scale, st.sbuf.as<float2>() + st.sfill, h->n_cu));
+        if (st.fe_on) { if ((rc = stream_frontend_run(h, d_native, fmt, scale, n, d_new))) return rc; }
+        else HIP_TRY(h, wr_launch_iq_widen(h->stream, d_native, fmt, n, scale, d_new, h->n_cu));
     } else if (n) {
-        HIP_TRY(h, hipMemcpyAsync(st.sbuf.as<float2>() + st.sfill, iq, n * sizeof(float2),
-                                  iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(d_new, iq, n * sizeof(float2), iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        if (st.fe_on && (rc = stream_frontend_run(h, d_new, WIFIRX_IQ_FC32, 1.0f, n, d_new))) return rc;
     }
     if (n) {
         st.sfill += (int64_t)n;

@@ -293,6 +293,7 @@ extern "C" int wifirx_push_diversity(wifirx_handle* h, const wifirx_div_stream* 
     if (cfg->n_ant < 1 || cfg->n_ant > WR_DET_MAX_ANT) return fail(h, WIFIRX_EINVAL, "n_ant must be 1 .. 8");
     if (h->div.n_ant && cfg->n_ant != h->div.n_ant) return fail(h, WIFIRX_EINVAL, "n_ant differs from the handle's first wifirx_push_diversity");
     if (h->st.single) return fail(h, WIFIRX_EINVAL, "the handle's stream has taken samples through wifirx_push / wifirx_push_iq");
+    if (h->st.fe_on) return fail(h, WIFIRX_EINVAL, "the handle's front end is on (wifirx_stream_frontend): the diversity stream has none");
     if (cfg->mode != WIFIRX_DIV_MRC && cfg->mode != WIFIRX_DIV_SELECT) return fail(h, WIFIRX_EINVAL, "mode must be WIFIRX_DIV_MRC or WIFIRX_DIV_SELECT");
     if (cfg->fmt != WIFIRX_IQ_FC32 && cfg->fmt != WIFIRX_IQ_SC16 && cfg->fmt != WIFIRX_IQ_SC8)
         return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_FC32, WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");

@@ -37,7 +37,8 @@ LINKTYPE_IEEE802_11 = 105
 class wifi_phy_rx(grshim.sync_block):
     def __init__(self, bandwidth=10e6, chan_est=LS, encoding=0, frequency=5.89e9, sensitivity=0.56,
                  max_sym=511, publish_carrier=True, device=0, batch_samples=None, publish_csi=False, snr_probe=None,
-                 soft_decision=False, sample_format="fc32", sample_scale=None, antennas=1, diversity="mrc", ant_gain=None):
+                 soft_decision=False, sample_format="fc32", sample_scale=None, antennas=1, diversity="mrc", ant_gain=None,
+                 dc_block=False, iq_correct=False, fe_frac_bits=12, fe_dc_shift=2, fe_iq_shift=4):
         # sample_format: "fc32" (complex64 items, the default), or "sc16" / "sc8": items of two int16 / int8 (I, Q), the form
         # a UHD source with an sc16 CPU format delivers; they cross the bus as they are and are widened on the device
         # (value = integer * sample_scale, default 2^-15 / 2^-7; wifirx_push_iq, NUMERICS.md rule 20)
@@ -63,6 +64,16 @@ class wifi_phy_rx(grshim.sync_block):
             self.ant_gain = np.array(ant_gain, dtype=np.float32).reshape(-1)
             if self.ant_gain.size != self.antennas or not (np.isfinite(self.ant_gain).all() and (self.ant_gain >= 0).all()):
                 raise ValueError("ant_gain: one finite value >= 0 per antenna")
+        # dc_block / iq_correct: the receive front end of NUMERICS.md rule 32 on the samples as they come in, in front of the
+        # detection (wifirx_stream_frontend): the mean of the last 2^fe_dc_shift blocks of 4096 samples is removed, and the
+        # image of a gain / phase imbalance between I and Q is estimated blindly over 2^fe_iq_shift blocks and removed.  Both
+        # off by default; iq_correct assumes traffic whose frames are not all very short (rule 32).  One antenna only.
+        self.dc_block, self.iq_correct = bool(dc_block), bool(iq_correct)
+        self.fe_frac_bits, self.fe_dc_shift, self.fe_iq_shift = int(fe_frac_bits), int(fe_dc_shift), int(fe_iq_shift)
+        if not (0 <= self.fe_frac_bits <= 30 and 0 <= self.fe_dc_shift <= 6 and 0 <= self.fe_iq_shift <= 6):
+            raise ValueError("fe_frac_bits must be 0 .. 30, fe_dc_shift and fe_iq_shift 0 .. 6")
+        if (self.dc_block or self.iq_correct) and self.antennas > 1:
+            raise ValueError("dc_block / iq_correct are not available with antennas > 1")
         grshim.sync_block.__init__(self, name="wifi_phy_rx", in_sig=in_sig * self.antennas, out_sig=None)
         self.bandwidth = float(bandwidth)
         self.chan_est = int(chan_est)
@@ -99,6 +110,9 @@ class wifi_phy_rx(grshim.sync_block):
         self.soft_decision = False
         if soft_decision:
             self.set_soft_decision(True)
+        self._fe_on = False
+        if self.dc_block or self.iq_correct:
+            self._set_frontend()
         self._push = capi.lib().wifirx_push
         if self.sample_format != capi.IQ_FC32:
             push_iq, fmt, scale = capi.lib().wifirx_push_iq, self.sample_format, self.sample_scale
@@ -145,6 +159,43 @@ class wifi_phy_rx(grshim.sync_block):
     def set_sensitivity(self, sensitivity):
         self._rx.set_param(capi.P_SENSITIVITY, float(sensitivity))      # refuses a negative value or a NaN: the old one stays
         self.sensitivity = float(sensitivity)
+
+    def _set_frontend(self):
+        """the handle's front end as dc_block / iq_correct say; a front end that stays on keeps its state"""
+        on = self.dc_block or self.iq_correct
+        if on and self.antennas > 1:
+            raise ValueError("dc_block / iq_correct are not available with antennas > 1")
+        init = None
+        if on and self._fe_on:
+            self._rx.flush()                                    # what is staged runs under the old setting
+            init = self._rx.stream_frontend_state()
+        cfg = capi.frontend_cfg(self.dc_block, self.iq_correct, self.fe_frac_bits, self.fe_dc_shift, self.fe_iq_shift) if on else None
+        self._rx.stream_frontend(cfg, init)
+        self._fe_on = on
+
+    def get_dc_block(self):
+        return self.dc_block
+
+    def set_dc_block(self, dc_block):
+        """DC removal (NUMERICS.md rule 32) for the samples that come in after the call"""
+        old, self.dc_block = self.dc_block, bool(dc_block)
+        try:
+            self._set_frontend()
+        except Exception:
+            self.dc_block = old
+            raise
+
+    def get_iq_correct(self):
+        return self.iq_correct
+
+    def set_iq_correct(self, iq_correct):
+        """blind IQ-imbalance correction (NUMERICS.md rule 32) for the samples that come in after the call"""
+        old, self.iq_correct = self.iq_correct, bool(iq_correct)
+        try:
+            self._set_frontend()
+        except Exception:
+            self.iq_correct = old
+            raise
 
     def get_soft_decision(self):
         return self.soft_decision
@@ -639,7 +690,7 @@ class channel_model(grshim.sync_block):
     MAX_TAPS = 64
 
     def __init__(self, noise_voltage=1.0, frequency_offset=0.0, epsilon=1.0, taps=(1.0,), noise_seed=0, block_tags=False,
-                 device=0, doppler=None, k_factor=0.0, fade_seed=0, irs=None):
+                 device=0, doppler=None, k_factor=0.0, fade_seed=0, irs=None, dc_offset=0j, iq_gain_db=0.0, iq_phase_deg=0.0):
         if irs is not None and not isinstance(irs, irs_mod.IrsConfig):
             raise TypeError("irs must be an irs.IrsConfig")
         self._ports = 1 if irs is None else irs.antennas         # output ports: the AP antennas behind the surface
@@ -660,6 +711,7 @@ class channel_model(grshim.sync_block):
         self.set_frequency_offset(frequency_offset)
         self.set_taps(taps)
         self.set_doppler(doppler)
+        self.set_rx_impairments(dc_offset, iq_gain_db, iq_phase_deg)
         self.noise_seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
         self.block_tags = bool(block_tags)          # tags are not propagated by the shim; accepted for the signature
         self._rx = capi.WifiRx(max_sym=1, device=device)         # the handle's receive side stays unused
@@ -763,6 +815,8 @@ class channel_model(grshim.sync_block):
                     rx.channel_dev(d_in.ptr, d_out.ptr, row.size, 1, row_len=row.size, taps=self._irs_set(s, port), n_taps=L,
                                    n_tap_sets=1, cfo=cfo, phase0=(self._phase - inc * h) & m64, gain=1.0,
                                    noise_voltage=self._noise_voltage, seed=(self.noise_seed + port) & m64, sample0=self._pos - h)
+                    if self._impair is not None:
+                        rx.rx_impair_dev(d_out.ptr, d_out.ptr, row.size, *self._impair)
                     out[at:at + m] = d_out.download(np.complex64, row.size)[h:]
             finally:
                 d_in.free()
@@ -792,6 +846,16 @@ class channel_model(grshim.sync_block):
 
     def frequency_offset(self):
         return self._frequency_offset
+
+    def set_rx_impairments(self, dc_offset=0j, iq_gain_db=0.0, iq_phase_deg=0.0):
+        """the receiver's own defects, applied behind the noise (wifirx_rx_impair): y = mu x + nu conj(x) + dc_offset with
+        g = 10^(iq_gain_db / 20), mu = (1 + g e^{-j phi}) / 2, nu = (1 - g e^{j phi}) / 2.  All zero (the default): the
+        block is what it is without them, and no kernel runs."""
+        d, g, ph = complex(dc_offset), float(iq_gain_db), float(iq_phase_deg)
+        if not (math.isfinite(d.real) and math.isfinite(d.imag) and math.isfinite(g) and math.isfinite(ph)):
+            raise ValueError("dc_offset, iq_gain_db and iq_phase_deg must be finite")
+        self.dc_offset, self.iq_gain_db, self.iq_phase_deg = d, g, ph
+        self._impair = None if (d == 0 and g == 0.0 and ph == 0.0) else capi.iq_imbalance(g, ph) + (d,)
 
     def set_taps(self, taps):
         t = np.ascontiguousarray(np.asarray(taps, dtype=np.complex64).reshape(-1))
@@ -856,7 +920,7 @@ class channel_model(grshim.sync_block):
             fade = dict(doppler=self._doppler, k_factor=self._k_factor, fade_seed=self.fade_seed, time0=self._pos - h)
         y = self._rx.channel(row, taps=self._taps, cfo=cfo, phase0=(self._phase - inc * h) & m64, gain=1.0,
                              noise_voltage=self._noise_voltage, seed=self.noise_seed, sample0=self._pos - h, **fade)
-        out[:n] = y[h:]
+        out[:n] = y[h:] if self._impair is None else self._rx.rx_impair(y[h:], *self._impair)
         keep = self.MAX_TAPS - 1
         self._hist = np.concatenate([self._hist, x])[-keep:] if n < keep else x[n - keep:].copy()
         self._pos += n

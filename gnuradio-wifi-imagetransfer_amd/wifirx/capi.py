@@ -52,7 +52,13 @@ EXPORTS = [
     "wifirx_push_diversity", "wifirx_poll_diversity", "wifirx_detect_multi", "wifirx_irs_taps", "wifirx_irs_sweep",
     "wifirx_irs_taps_multi", "wifirx_irs_sweep_multi", "wifirx_irs_estimate", "wifirx_irs_optimize",
     "wifirx_irs_optimize_weighted",
+    "wifirx_frontend", "wifirx_frontend_estimate", "wifirx_rx_impair", "wifirx_stream_frontend", "wifirx_stream_frontend_state",
 ]
+FE_DC, FE_IQ = 1, 2                 # WIFIRX_FE_*: stages of the receive front end (NUMERICS.md rule 32)
+FE_BLOCK, FE_RING = 4096, 64        # WIFIRX_FE_BLOCK, WIFIRX_FE_RING
+# wifirx_frontend_state as a NumPy record (2632 bytes; np.zeros((), FE_STATE_DTYPE) is a fresh stream)
+FE_STATE_DTYPE = np.dtype([("n", "<u8"), ("part", "<i8", (5,)), ("ring", "<i8", (FE_RING, 5)), ("d0", "<i8", (2,)), ("w0", "<f4", (2,))])
+assert FE_STATE_DTYPE.itemsize == 2632
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
 DIV_MAX_ANT = 8
@@ -179,6 +185,31 @@ class DivStream(C.Structure):
                 ("scale", C.c_float), ("iq_on_device", C.c_int)]
 
 
+class FrontendCfg(C.Structure):
+    """wifirx_frontend_cfg"""
+    _fields_ = [("flags", C.c_uint32), ("frac_bits", C.c_uint32), ("dc_shift", C.c_uint32), ("iq_shift", C.c_uint32)]
+
+
+def frontend_cfg(dc=True, iq=False, frac_bits=12, dc_shift=2, iq_shift=4) -> FrontendCfg:
+    """a wifirx_frontend_cfg with rule 32's defaults: the DC stage on, the blind IQ stage off"""
+    return FrontendCfg((FE_DC if dc else 0) | (FE_IQ if iq else 0), int(frac_bits), int(dc_shift), int(iq_shift))
+
+
+def frontend_state(d0=0j, w0=0j, frac_bits=12) -> np.ndarray:
+    """a fresh wifirx_frontend_state (a FE_STATE_DTYPE record) whose block 0 is corrected with offset d0 and coefficient w0"""
+    st = np.zeros((), FE_STATE_DTYPE)
+    st["d0"] = [int(np.rint(np.real(d0) * 2.0 ** frac_bits)), int(np.rint(np.imag(d0) * 2.0 ** frac_bits))]
+    st["w0"] = [np.real(w0), np.imag(w0)]
+    return st
+
+
+def iq_imbalance(gain_db=0.0, phase_deg=0.0):
+    """(mu, nu) of a receiver whose Q branch has gain g = 10^(gain_db / 20) and phase error phi against I:
+    mu = (1 + g e^{-j phi}) / 2, nu = (1 - g e^{j phi}) / 2; the receiver delivers mu x + nu conj(x)"""
+    g, phi = 10.0 ** (gain_db / 20.0), np.deg2rad(phase_deg)
+    return complex((1 + g * np.exp(-1j * phi)) / 2), complex((1 - g * np.exp(1j * phi)) / 2)
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_in", C.c_uint64), ("frames_detected", C.c_uint64), ("frames_signal_ok", C.c_uint64),
                 ("frames_complete", C.c_uint64), ("frames_crc_ok", C.c_uint64), ("frames_dropped", C.c_uint64)]
@@ -258,6 +289,12 @@ _lib.wifirx_iq_to_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C
 _lib.wifirx_iq_from_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.c_uint32, C.c_void_p,
                                     C.POINTER(C.c_uint64)]
 _lib.wifirx_push_iq.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int]
+_lib.wifirx_frontend.argtypes = [C.c_void_p, C.POINTER(FrontendCfg), C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_void_p]
+_lib.wifirx_frontend_estimate.argtypes = [C.POINTER(FrontendCfg), C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+_lib.wifirx_rx_impair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float)]
+_lib.wifirx_stream_frontend.argtypes = [C.c_void_p, C.POINTER(FrontendCfg), C.c_void_p]
+_lib.wifirx_stream_frontend_state.argtypes = [C.c_void_p, C.c_void_p]
 _lib.wifirx_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                    C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
 _lib.wifirx_channelizer_table.argtypes = [C.c_uint32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
@@ -292,6 +329,27 @@ def iq_format(fmt) -> int:
 
 def _np_ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _fe_state_array(state) -> np.ndarray:
+    """a writable, contiguous FE_STATE_DTYPE record (a copy); None: a fresh stream"""
+    if state is None:
+        return np.zeros((), FE_STATE_DTYPE)
+    st = np.array(state, dtype=FE_STATE_DTYPE, copy=True)
+    if st.shape != ():
+        raise ValueError("one wifirx_frontend_state record is required")
+    return st
+
+
+def frontend_estimate(cfg, state):
+    """wifirx_frontend_estimate: (dc, w) as complex64 -- what the block of the stream's next sample is corrected with, from
+    a host copy of the state (no handle, no device)"""
+    st = _fe_state_array(state)
+    d, w = (C.c_float * 2)(), (C.c_float * 2)()
+    rc = _lib.wifirx_frontend_estimate(C.byref(cfg) if cfg is not None else None, _np_ptr(st), d, w)
+    if rc != OK:
+        raise WifiRxError(rc, _lib.wifirx_last_error(None).decode())
+    return np.complex64(complex(d[0], d[1])), np.complex64(complex(w[0], w[1]))
 
 
 class DevBuf:
@@ -1264,6 +1322,73 @@ class WifiRx:
         finally:
             d_in.free()
             d_out.free()
+
+    # -- receive front end (wifirx_frontend, wifirx_rx_impair; NUMERICS.md rule 32) --
+    def frontend_dev(self, cfg, state_ptr, in_ptr, fmt, n, out_ptr, scale=None):
+        """wifirx_frontend on device pointers: n samples of `fmt` at in_ptr -> corrected complex64 at out_ptr, the
+        wifirx_frontend_state at state_ptr advanced.  in_ptr == out_ptr is allowed for "fc32".  Asynchronous on the handle's
+        stream."""
+        fmt = iq_format(fmt)
+        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
+        self._check(_lib.wifirx_frontend(self._h, C.byref(cfg), state_ptr, in_ptr, fmt, float(scale), int(n), out_ptr))
+
+    def frontend(self, x, cfg=None, state=None, fmt=None, scale=None):
+        """frontend_dev on host arrays: complex64 samples (fmt None or "fc32") or int16 / int8 samples ([n, 2] or flat [2 n]);
+        cfg None: frontend_cfg(); state None: a fresh stream.  Returns (complex64 [n], the state behind the call as a
+        FE_STATE_DTYPE record), which continues the stream when it is handed in again."""
+        cfg = frontend_cfg() if cfg is None else cfg
+        x = np.asarray(x)
+        if fmt is None and x.dtype not in (np.dtype(np.int16), np.dtype(np.int8)):
+            fmt = IQ_FC32
+        if fmt is not None and iq_format(fmt) == IQ_FC32:
+            x, fmt = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1), IQ_FC32
+            n = x.size
+        else:
+            x, fmt, n = self._iq_array(x, fmt)
+        st = _fe_state_array(state)
+        d_in, d_out, d_st = self.alloc(max(x.nbytes, 1)), self.alloc(max(n, 1) * 8), self.alloc(FE_STATE_DTYPE.itemsize)
+        try:
+            d_in.upload(x)
+            d_st.upload(st.reshape(1))
+            self.frontend_dev(cfg, d_st.ptr, d_in.ptr, fmt, n, d_out.ptr, scale)
+            return d_out.download(np.complex64, n), d_st.download(FE_STATE_DTYPE, 1)[0]
+        finally:
+            d_in.free()
+            d_out.free()
+            d_st.free()
+
+    def rx_impair_dev(self, in_ptr, out_ptr, n, mu=1.0, nu=0.0, dc=0.0):
+        """wifirx_rx_impair on device pointers: out = mu x + nu conj(x) + dc over n complex64 samples (mu, nu, dc complex;
+        in_ptr == out_ptr is allowed).  Asynchronous on the handle's stream."""
+        v = [(C.c_float * 2)(np.float32(np.real(c)), np.float32(np.imag(c))) for c in (mu, nu, dc)]
+        self._check(_lib.wifirx_rx_impair(self._h, in_ptr, out_ptr, int(n), v[0], v[1], v[2]))
+
+    def rx_impair(self, x, mu=1.0, nu=0.0, dc=0.0) -> np.ndarray:
+        """rx_impair_dev on complex64 host samples (iq_imbalance() gives mu and nu of a gain / phase imbalance)"""
+        x = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1)
+        d = self.alloc(max(x.nbytes, 1))
+        try:
+            d.upload(x)
+            self.rx_impair_dev(d.ptr, d.ptr, x.size, mu, nu, dc)
+            return d.download(np.complex64, x.size)
+        finally:
+            d.free()
+
+    def stream_frontend(self, cfg=None, init=None, **kw):
+        """wifirx_stream_frontend: the front end on every later push / push_iq.  cfg: a FrontendCfg, True (the keywords of
+        frontend_cfg() in kw) or None / False (off).  init: a FE_STATE_DTYPE record to start from (None: fresh)."""
+        if cfg is None or cfg is False:
+            self._check(_lib.wifirx_stream_frontend(self._h, None, None))
+            return
+        cfg = frontend_cfg(**kw) if cfg is True else cfg
+        st = None if init is None else _fe_state_array(init)
+        self._check(_lib.wifirx_stream_frontend(self._h, C.byref(cfg), _np_ptr(st)))
+
+    def stream_frontend_state(self) -> np.ndarray:
+        """wifirx_stream_frontend_state: the stream's front-end state as a FE_STATE_DTYPE record (waits for the stream)"""
+        st = np.zeros((), FE_STATE_DTYPE)
+        self._check(_lib.wifirx_stream_frontend_state(self._h, _np_ptr(st)))
+        return st
 
     # -- wideband ingest (wifirx_channelize; NUMERICS.md rule 21) --
     def channelize_dev(self, in_ptr, fmt, n_out, n_channels, stacking, out_ptr, out_stride=None, hist_ptr=None,

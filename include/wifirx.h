@@ -1006,6 +1006,77 @@ int  wifirx_poll_diversity(wifirx_handle* h, const wifirx_poll_out* out, uint8_t
 int  wifirx_detect_multi(wifirx_handle* h, uint32_t n_ant, const float* const* iq_dev, uint64_t n,
                          float threshold, uint64_t* masks_dev, float* A_dev, float* P_dev);
 
+/* Receive front end (NUMERICS.md rule 32): DC removal and blind IQ-imbalance correction of a sample stream, between the
+ * ingest of rule 20 and the detection.  Opt-in everywhere; a handle or a call that does not ask for it computes what it did.
+ * The stream is cut into blocks of WIFIRX_FE_BLOCK samples aligned to its origin.  Of every block five integer sums of the RAW
+ * samples in Q-frac_bits fixed point are kept (sum u, sum v, sum u^2 + v^2, sum u^2 - v^2, sum 2uv), shifted right by 12 when
+ * the block completes, in a ring of the last WIFIRX_FE_RING blocks.  Block b >= 1 is corrected with the mean over the
+ * 2^min(shift, ilog2(b)) blocks in front of it (dc_shift for the offset d, iq_shift for the second moments that give the image
+ * coefficient w); block 0 uses the state's initial values d0 and w0.  Per sample y = x - d, z = y - w conj(y).  Integer
+ * statistics make the output and the state independent of how the stream is cut into calls, byte for byte.
+ * The IQ stage is blind: it assumes a proper signal, which the 802.11 preamble is not, so on traffic of very short frames w is
+ * biased (rule 32 gives figures); it is a switch of its own and off in every default.  The first block of a fresh state is
+ * not corrected. */
+#define WIFIRX_FE_DC    1u          /* flags: remove the offset */
+#define WIFIRX_FE_IQ    2u          /* flags: remove the image */
+#define WIFIRX_FE_BLOCK 4096
+#define WIFIRX_FE_RING  64
+typedef struct {
+    uint32_t flags;          /* WIFIRX_FE_DC | WIFIRX_FE_IQ; a stage that is off uses d = 0 / w = 0, the statistics are taken anyway */
+    uint32_t frac_bits;      /* F, 0 .. 30 (default 12): the statistics are rint(x * 2^F), clamped to +-(2^24 - 1) */
+    uint32_t dc_shift;       /* 0 .. 6 (default 2): the offset is the mean over up to 2^dc_shift blocks */
+    uint32_t iq_shift;       /* 0 .. 6 (default 4): the second moments are means over up to 2^iq_shift blocks */
+} wifirx_frontend_cfg;
+
+/* The state of one stream, 2632 bytes; all zero = a fresh stream.  The caller owns it (DEVICE memory for wifirx_frontend) and
+ * may set d0 / w0 of a fresh state: what block 0 is corrected with. */
+typedef struct {
+    uint64_t n;                          /* samples taken so far */
+    int64_t  part[5];                    /* the five sums of the block that is still open */
+    int64_t  ring[WIFIRX_FE_RING][5];    /* the means of block b at ring[b % 64] */
+    int64_t  d0[2];                      /* initial offset (I, Q) in Q-frac_bits */
+    float    w0[2];                      /* initial image coefficient (re, im) */
+} wifirx_frontend_state;
+
+/* n samples of `fmt` at in (integer formats widened by rule 20 with `scale`, FC32: scale is not looked at) -> n corrected float
+ * pairs at out, and *state_dev advanced by n samples.  DEVICE buffers: in at the format's natural alignment (8 / 4 / 2 bytes),
+ * out and state_dev 8-byte aligned.  in == out is allowed for WIFIRX_IQ_FC32.  The same cfg must accompany a state throughout.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for a NULL handle, cfg, state_dev, in or out, an unknown fmt,
+ * flags outside WIFIRX_FE_DC | WIFIRX_FE_IQ, frac_bits > 30, a shift > 6, a scale that is not finite or <= 0 (integer formats),
+ * misaligned buffers, n > 2^40, an overlap of in and out other than in == out for FC32, and a state that overlaps either.
+ * n = 0 does nothing and returns WIFIRX_OK.  Three kernel launches per call (statistics, apply, state), whatever n is; a small
+ * table of the call's block sums lives in the handle.
+ * ORDER: as wifirx_iq_to_f32 -- asynchronous on the handle's stream, behind the handle's earlier calls. */
+int  wifirx_frontend(wifirx_handle* h, const wifirx_frontend_cfg* cfg, wifirx_frontend_state* state_dev, const void* in,
+                     int fmt, float scale, uint64_t n, float* out);
+
+/* What the block that holds the stream's NEXT sample is corrected with, from a HOST copy of the state: dc = d (re, im),
+ * w = (re, im), stages that are off giving zeros.  Pure host arithmetic, no handle, no device.  WIFIRX_EINVAL for a NULL
+ * argument or a cfg that wifirx_frontend would refuse. */
+int  wifirx_frontend_estimate(const wifirx_frontend_cfg* cfg, const wifirx_frontend_state* state_host, float dc[2], float w[2]);
+
+/* Receiver impairments for the loop-back: out[i] = mu x[i] + nu conj(x[i]) + dc, elementwise in float32 (mu x and conj(x) nu
+ * by NUMERICS.md rule 2, then (a + b) + dc per component).  DEVICE buffers of n float pairs, 8-byte aligned; in == out is
+ * allowed, any other overlap is not.  mu, nu, dc: HOST, two finite floats each (they travel as kernel arguments).
+ * WIFIRX_EINVAL for NULL arguments, a value that is not finite, misaligned buffers, a partial overlap, n > 2^40.  n = 0 does
+ * nothing.  ORDER: as wifirx_iq_to_f32. */
+int  wifirx_rx_impair(wifirx_handle* h, const float* in, float* out, uint64_t n, const float mu[2], const float nu[2],
+                      const float dc[2]);
+
+/* Stream mode: with a cfg, every later wifirx_push / wifirx_push_iq runs the front end on the samples it appends -- fused with
+ * the widening for the integer formats, in place on the stream's sample buffer for FC32 -- in front of the detection, from the
+ * state *init (HOST; NULL = fresh).  cfg == NULL switches the front end off (init is not looked at).  To be called before the
+ * handle's first push or after a flush: samples already taken are not revisited.  The state lives in the handle; a push that
+ * fails leaves it as it was (the call stays all or nothing).
+ * OUT OF SCOPE: on a handle with the front end on, wifirx_push_diversity returns WIFIRX_EINVAL; wifirx_channelize has no
+ * front-end option (condition its channel streams with wifirx_frontend, or through the handles they are pushed to).
+ * WIFIRX_EINVAL for a NULL handle or a cfg that wifirx_frontend would refuse, and on a handle of a diversity stream. */
+int  wifirx_stream_frontend(wifirx_handle* h, const wifirx_frontend_cfg* cfg, const wifirx_frontend_state* init);
+
+/* The stream's front-end state to *out_host (waits for the handle's stream).  WIFIRX_EINVAL for NULL arguments or a handle
+ * whose front end is off. */
+int  wifirx_stream_frontend_state(wifirx_handle* h, wifirx_frontend_state* out_host);
+
 /* plain device memory helpers so that a host language without a HIP binding can own buffers */
 int  wifirx_dev_alloc(wifirx_handle* h, size_t bytes, void** out);
 int  wifirx_dev_free(wifirx_handle* h, void* p);

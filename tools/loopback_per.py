@@ -75,7 +75,13 @@ trained per draw by a codebook sweep (wifirx_irs_sweep, rule 26; --irs-codebook 
     python tools/loopback_per.py --irs 64 256 --irs-bits 2 --irs-mode random los genie sweep --irs-codebook dft2 --k-factor 3 --psdu-len 294 --encoding 2 --snr -30 -20 -10 [--out profiles/loopback_irs_sweep.json]
     python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode random sweep estimate genie --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_estimate.json]
     python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode estimate --irs-decision ref joint --antennas 1 2 4 --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 [--out profiles/loopback_irs_optimize.json]
-    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode estimate --irs-decision ref joint --irs-tap-weights 1 0 --irs-tap-weights 1 -1 [--irs-taps 1] --antennas 1 2 4 --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 --frames 16384 (the four runs of profiles/loopback_irs_optimize_w.json)"""
+    python tools/loopback_per.py --irs 64 --irs-bits 2 --irs-mode estimate --irs-decision ref joint --irs-tap-weights 1 0 --irs-tap-weights 1 -1 [--irs-taps 1] --antennas 1 2 4 --k-factor 0.1 --pilot-snr-db -6 --psdu-len 294 --encoding 2 --snr -30 -25 -20 --frames 16384 (the four runs of profiles/loopback_irs_optimize_w.json)
+
+--dc-db puts a zero-IF receiver's defects between the channel and the receiver (wifirx_rx_impair: a DC offset of these many dB
+above the noise power, and with --iq-imbalance GAIN_DB PHASE_DEG a gain / phase imbalance between I and Q) and runs the arms
+of --frontend: "off" demodulates the impaired slots as they are, "dc" and "dc+iq" first take the slot buffer, as ONE stream
+from a fresh state, through wifirx_frontend (NUMERICS.md rule 32: DC removal, blind IQ correction):
+    python tools/loopback_per.py --dc-db none 0 5 10 20 30 --iq-imbalance 1 5 --frontend off dc dc+iq --snr 20 26 30 [--frames 65536] [--out profiles/loopback_frontend.json]"""
 import argparse
 import json
 import math
@@ -173,6 +179,12 @@ def main():
                     help="with --irs-mode sweep: irs.dft_codebook at over = 1 / 2, or the reference controller's 10 x 10 grid "
                          "(irs.traverse_codebook), quantised to --irs-bits")
     ap.add_argument("--direct-db", type=float, default=float("-inf"), help="with --irs: gain of the direct path in dB (-inf: blocked)")
+    ap.add_argument("--dc-db", type=lambda s: float("-inf") if s == "none" else float(s), nargs="+", default=None,
+                    help="a receiver's DC offset, these many dB above the noise power ('none': no offset)")
+    ap.add_argument("--iq-imbalance", type=float, nargs=2, default=[0.0, 0.0], metavar=("GAIN_DB", "PHASE_DEG"),
+                    help="with --dc-db: gain and phase imbalance between I and Q")
+    ap.add_argument("--frontend", nargs="+", choices=("off", "dc", "dc+iq"), default=["off", "dc", "dc+iq"],
+                    help="with --dc-db: the arms -- no front end, wifirx_frontend with the DC stage, with both stages")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if (a.irs_tap_weights or a.irs_ant_weights) and "joint" not in a.irs_decision:
@@ -189,6 +201,8 @@ def main():
         return wideband_main(a)
     if a.adc_bits is not None:
         return adc_main(a)
+    if a.dc_db is not None:
+        return frontend_main(a)
     if a.doppler is not None:
         return fading_main(a)
     if a.rates:
@@ -314,6 +328,80 @@ def adc_main(a):
                        "channel output (its first 256 rows)" % (n, a.backoff_db),
            "columns": "per SNR: float32 = no converter; adc = one entry per B: fer (hard), fer_soft, clipped_share of the components",
            "backoff_db": a.backoff_db, "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def frontend_main(a):
+    if a.rates or a.host_stats or a.locked_clock or a.doppler is not None:
+        raise SystemExit("--dc-db stands alone: not with --rates, --host-stats, --locked-clock or --doppler")
+    n = a.frames or 65536
+    n_sym, nb = txgen.n_sym_for(PSDU_LEN, ENC), txgen.RATE_TABLE[ENC][0]
+    taps = np.load(os.path.join(ROOT, "tests", "golden", "sv_taps.npy")).astype(np.complex64)
+    rx = capi.WifiRx(max_sym=n_sym, llr_bits=nb, chan_est=capi.EQ_LS, device=0)
+    t_all = time.perf_counter()
+    d_psdu, rows, iq, iq_rx, iq_fe = rx.alloc(n * PSDU_LEN), rx.alloc(n * SLOT * 8), rx.alloc(n * SLOT * 8), rx.alloc(n * SLOT * 8), rx.alloc(n * SLOT * 8)
+    d_state = rx.alloc(capi.FE_STATE_DTYPE.itemsize)
+    rx.mac_batch_dev(d_psdu.ptr, PSDU_LEN, n, None, payload_len=PSDU_LEN - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, n * SLOT, d_psdu.ptr, ENC, psdu_len=np.full(n, PSDU_LEN, np.uint32), psdu_stride=PSDU_LEN, lead=LEAD, row_len=SLOT)
+    dev = rx.alloc_out(n, psdu_stride=304, want_hbits=True)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * n_sym * 48), hbits=rx.alloc(n * n_sym * 48), psdu=d_psdu,
+               psdu_stride=PSDU_LEN)
+    rx.demod_batch_dev(rows.ptr, SLOT, n, ref)
+    assert rx.link_stats(n, ref, ref)["frames_ref"] == n, "a clean frame was not demodulated"
+    mu, nu = capi.iq_imbalance(*a.iq_imbalance)
+    cfgs = {"dc": capi.frontend_cfg(dc=True, iq=False), "dc+iq": capi.frontend_cfg(dc=True, iq=True)}
+
+    def receive(ptr):
+        rx.demod_batch_dev(ptr, SLOT, n, dev)
+        rx.decode_batch_dev(n, dev)
+        hard = rx.link_stats(n, dev, ref)
+        rx.decode_batch_soft_dev(n, dev)
+        soft = rx.link_stats(n, dev, ref)
+        return {"fer": hard["fer"], "fer_soft": soft["fer"], "coded_ber": hard["coded_ber"], "counts": {k: hard[k] for k in COUNTERS},
+                "counts_soft": {k: soft[k] for k in COUNTERS}}
+
+    points = []
+    for snr in a.snr:
+        cfo = np.random.default_rng(int(1000 * snr) + a.seed).uniform(-CFO_20PPM, CFO_20PPM, n).astype(np.float32)
+        rx.channel_dev(rows.ptr, iq.ptr, n * SLOT, n, row_len=SLOT, taps=taps, cfo=cfo, gain=math.sqrt(10 ** (snr / 10)),
+                       noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32))
+        for dc_db in a.dc_db:
+            t0 = time.perf_counter()
+            dc = math.sqrt(10 ** (dc_db / 10)) * np.exp(0.7j) if math.isfinite(dc_db) else 0j
+            rx.rx_impair_dev(iq.ptr, iq_rx.ptr, n * SLOT, mu, nu, dc)
+            pt = {"snr_db": snr, "dc_db": dc_db if math.isfinite(dc_db) else None, "frames": n, "arms": {}}
+            for arm in a.frontend:
+                ptr = iq_rx.ptr
+                if arm != "off":
+                    d_state.upload(np.zeros(1, capi.FE_STATE_DTYPE))             # every arm starts a fresh stream
+                    rx.frontend_dev(cfgs[arm], d_state.ptr, iq_rx.ptr, "fc32", n * SLOT, iq_fe.ptr)
+                    ptr = iq_fe.ptr
+                pt["arms"][arm] = receive(ptr)
+                if arm != "off":
+                    st = d_state.download(capi.FE_STATE_DTYPE, 1)[0]
+                    d, w = capi.frontend_estimate(cfgs[arm], st)
+                    pt["arms"][arm].update(dc_estimate=[float(d.real), float(d.imag)], w_estimate=[float(w.real), float(w.imag)])
+            pt["seconds"] = time.perf_counter() - t0
+            points.append(pt)
+            print(json.dumps({"snr_db": snr, "dc_db": pt["dc_db"], "fer": {k: v["fer"] for k, v in pt["arms"].items()},
+                              "fer_soft": {k: v["fer_soft"] for k, v in pt["arms"].items()}}), file=sys.stderr)
+    seconds_total = time.perf_counter() - t_all
+    rx.free_out(ref)
+    rx.free_out(dev)
+    for d in (rows, iq, iq_rx, iq_fe, d_state):
+        d.free()
+    rx.close()
+    res = {"workload": "loop-back on the device, config 3 (%d distinct frames per point, 64-QAM 3/4, PSDU 294 B, rows of 1472, lead 160, "
+                       "sv_taps.npy sets cycling, CFO uniform in +-20 ppm, LS; hard and soft decode_mac) with a zero-IF receiver's defects "
+                       "behind the channel (wifirx_rx_impair: DC offset dc_db above the unit noise power at angle 0.7 rad, IQ imbalance "
+                       "%.2f dB / %.2f deg) and the receive front end (wifirx_frontend, NUMERICS.md rule 32, defaults) over the slot buffer "
+                       "as one stream from a fresh state" % (n, a.iq_imbalance[0], a.iq_imbalance[1]),
+           "columns": "per SNR and dc_db: arms[off | dc | dc+iq] = fer (hard), fer_soft, counters; dc_estimate / w_estimate: what the "
+                      "block behind the buffer would be corrected with (true image coefficient nu / conj(mu) = %s)" % str(nu / np.conj(mu)),
+           "iq_imbalance": list(a.iq_imbalance), "stats": "wifirx_link_stats on the device", "seconds_total": seconds_total, "points": points}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
