@@ -37,6 +37,7 @@
 #include "wr_channelizer.h"
 #include "wr_combiner.h"
 #include "wr_diversity.h"
+#include "wr_precombine.h"
 #include "wr_detect_multi.h"
 
 // The stream's per-frame outputs (stream_outs, wifirx_api_stream.inc) and the host copy of a batch of them, shared by its
@@ -645,4 +646,5 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_convert.inc"
 #include "wifirx_api_bank.inc"
 #include "wifirx_api_diversity.inc"
+#include "wifirx_api_precombine.inc"
 #include "wifirx_api_stream_div.inc"

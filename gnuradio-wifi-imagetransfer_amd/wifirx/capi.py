@@ -53,6 +53,7 @@ EXPORTS = [
     "wifirx_irs_taps_multi", "wifirx_irs_sweep_multi", "wifirx_irs_estimate", "wifirx_irs_optimize",
     "wifirx_irs_optimize_weighted",
     "wifirx_frontend", "wifirx_frontend_estimate", "wifirx_rx_impair", "wifirx_stream_frontend", "wifirx_stream_frontend_state",
+    "wifirx_precombine",
 ]
 FE_DC, FE_IQ = 1, 2                 # WIFIRX_FE_*: stages of the receive front end (NUMERICS.md rule 32)
 FE_BLOCK, FE_RING = 4096, 64        # WIFIRX_FE_BLOCK, WIFIRX_FE_RING
@@ -62,6 +63,11 @@ assert FE_STATE_DTYPE.itemsize == 2632
 DIV_MRC, DIV_SELECT = 0, 1          # WIFIRX_DIV_*: modes of wifirx_diversity_combine (NUMERICS.md rule 23)
 DIV_MODES = {"mrc": DIV_MRC, "select": DIV_SELECT}
 DIV_MAX_ANT = 8
+PRE_MAX_ANT, PRE_MAX_ITERS = 8, 4   # wifirx_precombine: antennas, power iterations (NUMERICS.md rule 33)
+PRE_DEGENERATE = 1                  # WIFIRX_PRE_DEGENERATE: the slot's y is antenna 0's samples
+# one stats row of wifirx_precombine
+PRE_STATS_DTYPE = np.dtype([("lambda", "<f4"), ("trace", "<f4"), ("ref", "<u4"), ("flags", "<u4")])
+assert PRE_STATS_DTYPE.itemsize == 16
 CHANNELIZER_CHANNELS = (2, 4, 8)    # wifirx_channelize: n_channels (NUMERICS.md rule 21)
 CHANNELIZER_HIST = 23               # input blocks of n_channels samples that a call takes from before its input
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
@@ -302,6 +308,8 @@ _lib.wifirx_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.
                                 C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
 _lib.wifirx_diversity_combine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.c_uint32, C.c_int, C.POINTER(C.c_float),
                                           C.POINTER(Out), C.c_void_p]
+_lib.wifirx_precombine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
 _lib.wifirx_push_diversity.argtypes = [C.c_void_p, C.POINTER(DivStream), C.POINTER(C.c_void_p), C.c_size_t]
 _lib.wifirx_poll_diversity.argtypes = [C.c_void_p, C.POINTER(PollOut), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
 _lib.wifirx_detect_multi.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint64, C.c_float, C.c_void_p, C.c_void_p,
@@ -1489,6 +1497,70 @@ class WifiRx:
                 self.free_out(out)
             if d_mask is not None:
                 d_mask.free()
+
+    # -- pre-detection combining (wifirx_precombine; NUMERICS.md rule 33) --
+    def precombine_dev(self, iq_ptrs, slot_len, n_slots, out_ptr, iters=2, weights_ptr=None, stats_ptr=None):
+        """wifirx_precombine on device buffers: iq_ptrs = one device pointer per antenna to [n_slots][slot_len] float pairs,
+        slot i of every antenna the same transmission; out_ptr receives the one row set that demod_batch_dev reads as it is.
+        iters: 0 .. 4 power iterations.  weights_ptr: [n_slots][n_ant] pairs, stats_ptr: [n_slots] PRE_STATS_DTYPE rows (None:
+        not wanted).  Asynchronous on the handle's stream, behind its earlier calls."""
+        arr = (C.c_void_p * max(len(iq_ptrs), 1))(*[None if p is None else int(p) for p in iq_ptrs])
+        self._check(_lib.wifirx_precombine(self._h, len(iq_ptrs), arr, int(slot_len), int(n_slots), int(iters), out_ptr,
+                                           weights_ptr, stats_ptr))
+
+    def _precombine_host(self, iqs, slot_len, iters, bufs):
+        """uploads the antennas, allocates y, weights and stats into `bufs` (the caller frees them) and queues the call:
+        (n_slots, n_ant, d_y, d_w, d_s)"""
+        iqs = [np.ascontiguousarray(x, dtype=np.complex64).reshape(-1) for x in iqs]
+        if not iqs or any(x.size != iqs[0].size for x in iqs) or iqs[0].size % slot_len:
+            raise ValueError("one array of n_slots * slot_len samples per antenna is required")
+        n, A = iqs[0].size // slot_len, len(iqs)
+        for x in iqs:
+            bufs.append(self.alloc(max(x.nbytes, 1)).upload(x))
+        for nbytes in (iqs[0].nbytes, n * A * 8, n * 16):
+            bufs.append(self.alloc(max(nbytes, 1)))
+        d_y, d_w, d_s = bufs[A:]
+        self.precombine_dev([b.ptr for b in bufs[:A]], slot_len, n, d_y.ptr, iters, d_w.ptr, d_s.ptr)
+        return n, A, d_y, d_w, d_s
+
+    def precombine(self, iqs, slot_len, iters=2):
+        """Host convenience (PCIe-bound: every antenna's samples cross the bus for one row set back): iqs = one complex64 array
+        per antenna.  Returns (y complex64 [n_slots, slot_len], weights complex64 [n_slots, n_ant], stats PRE_STATS_DTYPE
+        [n_slots])."""
+        bufs = []
+        try:
+            n, A, d_y, d_w, d_s = self._precombine_host(iqs, slot_len, iters, bufs)
+            self.sync()
+            return (d_y.download(np.complex64, n * slot_len).reshape(n, slot_len),
+                    d_w.download(np.complex64, n * A).reshape(n, A), d_s.download(PRE_STATS_DTYPE, n))
+        finally:
+            for b in bufs:
+                b.free()
+
+    def demod_precombined(self, iqs, slot_len, iters=2, soft=False, psdu_stride=2048) -> dict:
+        """Host convenience (PCIe-bound, as demod_diversity): iqs = one complex64 array per antenna, slot i of each the same
+        transmission.  The antennas are combined in front of the detector (precombine_dev), the one row set is demodulated
+        ONCE and decoded (soft=True: on the LLRs, which needs llr_bits > 0).  Returns the batch -- frames, psdu, idx, llr,
+        carrier where the handle produces them -- plus weights (complex64 [n_slots, n_ant]) and pre_stats (PRE_STATS_DTYPE)."""
+        bufs, out = [], None
+        try:
+            n, A, d_y, d_w, d_s = self._precombine_host(iqs, slot_len, iters, bufs)
+            out = self.alloc_out(n, psdu_stride=psdu_stride)
+            self.demod_batch_dev(d_y.ptr, slot_len, n, out)
+            if soft:
+                self.decode_batch_soft_dev(n, out)
+            else:
+                self.decode_batch_dev(n, out)
+            self.sync()
+            r = self.download_out(out, n)
+            r["weights"] = d_w.download(np.complex64, n * A).reshape(n, A)
+            r["pre_stats"] = d_s.download(PRE_STATS_DTYPE, n)
+            return r
+        finally:
+            for b in bufs:
+                b.free()
+            if out is not None:
+                self.free_out(out)
 
     # -- stream mode --
     def push(self, iq: np.ndarray):

@@ -955,6 +955,35 @@ int  wifirx_combine(wifirx_handle* h, const float* in, uint64_t in_stride, const
 int  wifirx_diversity_combine(wifirx_handle* h, uint32_t n_ant, const wifirx_out* in, uint32_t n_slots, int mode,
                               const float* ant_gain, const wifirx_out* out, uint8_t* used_mask);
 
+/* Pre-detection combining (NUMERICS.md rule 33): the SAMPLES of n_ant antennas into one row set that wifirx_demod_batch reads
+ * as it is.  Slot i of every antenna is the same transmission, sample for sample (the antennas of one radio).  Per slot the
+ * weights v are blind: the n_ant x n_ant sample covariance R of the slot, its column at the antenna of the greatest power
+ * (the lowest index on ties), `iters` power iterations, unit norm, rotated so that the reference antenna's weight is real and
+ * non-negative; then y[n] = sum_a conj(v_a) x_a[n].  For one complex gain per antenna (a flat channel) and equal noise this
+ * is maximal-ratio combining in front of the detector: plateau, LTS search, SIGNAL, the channel estimate and the data all get
+ * the array gain, and ONE demod replaces n_ant demods and wifirx_diversity_combine.  One weight per antenna cannot follow a
+ * frequency-selective channel: under multipath wifirx_diversity_combine is the better combiner.
+ *   iq_dev       HOST [n_ant] of DEVICE pointers, n_ant = 1 .. 8: [n_slots][slot_len] float pairs each, 8-byte aligned
+ *   slot_len     a multiple of 64, 64 .. 65536: the row stride of every antenna and of out_dev
+ *   iters        0 .. 4 power iterations (0: the covariance column itself; 2 is the Python default)
+ *   out_dev      DEVICE [n_slots][slot_len] pairs, 8-byte aligned, none of the inputs
+ *   weights_dev  DEVICE [n_slots][n_ant] pairs or NULL: v as used
+ *   stats_dev    DEVICE [n_slots] rows of 16 bytes or NULL: float lambda = Re(v^H R v), float trace = sum_a R_aa, uint32_t ref
+ *                (the reference antenna), uint32_t flags (WIFIRX_PRE_DEGENERATE)
+ * A slot whose trace or whose weight norm is not finite or not > 0 (silence, a NaN, an infinity, an overflow) is degenerate:
+ * y = x_0 bit for bit, v = (1, 0, ..), lambda = 0, ref = 0 and the flag is set.  With n_ant = 1 y is x_0 bit for bit, v = (1, 0)
+ * and the stats row is zero.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for NULL h, iq_dev, iq_dev[a] or out_dev, n_ant outside 1 .. 8,
+ * slot_len not a multiple of 64 or outside 64 .. 65536, iters above 4, a pointer that is not 8-byte aligned, out_dev equal to
+ * an input pointer; WIFIRX_ERANGE for n_slots above the handle's max_batch.  n_slots = 0 does nothing and returns WIFIRX_OK.
+ * One kernel launch per call.
+ * ORDER: as wifirx_diversity_combine -- iq_dev travels as kernel arguments, so it may be reused when the call returns; the
+ * kernel runs asynchronously on the handle's stream, behind the handle's earlier calls: precombine, demod, decode on one
+ * handle need no wifirx_sync in between. */
+#define WIFIRX_PRE_DEGENERATE 1u
+int  wifirx_precombine(wifirx_handle* h, uint32_t n_ant, const float* const* iq_dev, uint32_t slot_len, uint32_t n_slots,
+                       uint32_t iters, float* out_dev, float* weights_dev, void* stats_dev);
+
 /* Stream-mode receive diversity (NUMERICS.md rules 24 and 23): wifirx_push for the n_ant sample-synchronous antennas of ONE
  * radio (a multi-channel USRP).  Detection runs once, on the sum of the antennas' autocorrelations and powers (rule 24), so
  * every antenna gets the same triggers and the same coarse CFO, and slot i of every antenna is the same transmission by

@@ -60,6 +60,14 @@ the combiner) and mode.  The counts nest: A antennas are the first A of the larg
 
     python tools/loopback_per.py --antennas 1 2 4 --diversity mrc select --psdu-len 294 --encoding 2 --snr 5 10 15 20 25 [--frames 65536] [--out profiles/loopback_diversity.json]
 
+--antennas with --precombine asks what combining in FRONT of the detector buys (wifirx_precombine, NUMERICS.md rule 33): the scene
+of --antennas on rows of a multiple of 64 samples, every antenna's samples kept; per SNR and count A antenna 0 alone ('1'), A
+demods and rule 23's MRC ('A_mrc'), and the pre-combined row set through ONE demod ('A_pre').  --multipath replaces the one tap
+by the 8-tap sets of sv_taps.npy, every tap fading on its own: one weight per antenna cannot follow that channel, which is the
+known limit of the rule.  Both runs land in one file, under "flat" and "multipath".
+
+    python tools/loopback_per.py --antennas 2 4 --precombine [--precombine-iters 2] [--multipath] --psdu-len 100 --encoding 2 --snr 4 8 12 [--frames 65536] [--out profiles/loopback_precombine.json]
+
 --irs: the link over a reflecting surface of N elements with B-bit phases (wifirx_irs_taps, NUMERICS.md rule 25): one tap set of 8
 taps per frame, made on the device and read there by wifirx_channel; FER against the surface size at SNRs of one unit-power path.
 --irs-mode: random phases, the one configuration aligned to the geometry, the genie aligned per draw, `estimate`: a surface
@@ -153,6 +161,10 @@ def main():
     ap.add_argument("--antennas", type=int, nargs="+", default=None, help="receive diversity: these antenna counts, 1 .. 8")
     ap.add_argument("--diversity", nargs="+", choices=sorted(capi.DIV_MODES, key=capi.DIV_MODES.get), default=None,
                     help="with --antennas: the combiner's modes (default both)")
+    ap.add_argument("--precombine", action="store_true",
+                    help="with --antennas: pre-detection combining (wifirx_precombine, NUMERICS.md rule 33) and ONE demod, beside "
+                         "rule 23's MRC over the A demods and antenna 0 alone; --multipath: the sv_taps.npy sets in place of the flat channel")
+    ap.add_argument("--precombine-iters", type=int, default=2, help="with --precombine: power iterations, 0 .. 4")
     ap.add_argument("--irs", type=int, nargs="+", default=None, help="a reflecting surface of these many elements (squares; 0 = the direct path alone)")
     ap.add_argument("--irs-bits", type=int, default=2, choices=(1, 2, 3), help="with --irs: the phase resolution")
     ap.add_argument("--irs-mode", nargs="+", choices=("random", "los", "genie", "sweep", "estimate"), default=["genie"],
@@ -191,10 +203,14 @@ def main():
         raise SystemExit("--irs-tap-weights and --irs-ant-weights need --irs-decision joint")
     if not 1 <= a.irs_taps <= capi.IRS_MAX_TAPS:
         raise SystemExit("--irs-taps 1 .. %d" % capi.IRS_MAX_TAPS)
-    if a.irs is not None and a.antennas is not None:
+    if a.irs is not None and a.antennas is not None and not a.precombine:
         return irs_multi_main(a)
     if a.irs is not None:
         return irs_main(a)
+    if a.precombine:
+        if a.antennas is None or a.irs is not None:
+            raise SystemExit("--precombine goes with --antennas (and not with --irs)")
+        return precombine_main(a)
     if a.antennas is not None:
         return diversity_main(a)
     if a.wideband is not None:
@@ -584,6 +600,101 @@ def diversity_main(a):
     if a.out:
         with open(a.out, "w") as f:
             f.write(json.dumps(res, indent=1) + "\n")
+
+
+def precombine_main(a):
+    """--antennas with --precombine: what combining in FRONT of the detector buys.  Every antenna's samples are kept; per SNR and
+    antenna count A the same channel outputs go through (1) antenna 0's demod alone, (2) A demods and rule 23's MRC, (3)
+    wifirx_precombine and one demod.  Rule 33 needs rows of a multiple of 64 samples."""
+    if a.rates or a.host_stats or a.locked_clock or a.adc_bits is not None or a.wideband is not None:
+        raise SystemExit("--precombine stands alone: not with --rates, --host-stats, --locked-clock, --adc-bits or --wideband")
+    counts = sorted(set(a.antennas))
+    if counts[0] < 1 or counts[-1] > capi.PRE_MAX_ANT or not 0 <= a.precombine_iters <= capi.PRE_MAX_ITERS:
+        raise SystemExit("--antennas 1 .. %d, --precombine-iters 0 .. %d" % (capi.PRE_MAX_ANT, capi.PRE_MAX_ITERS))
+    n = a.frames or 65536
+    plen, enc = a.psdu_len, a.encoding
+    if not (28 <= plen <= 1528 and 0 <= enc <= 7):
+        raise SystemExit("--psdu-len 28 .. 1528, --encoding 0 .. 7")
+    fd = a.doppler[0] if a.doppler else 0.0
+    n_sym, nb = txgen.n_sym_for(plen, enc), txgen.RATE_TABLE[enc][0]
+    slot = (LEAD + txgen.frame_samples(plen, enc) + 79 + 63) // 64 * 64
+    stride = (plen + 15) // 16 * 16
+    taps = np.load(os.path.join(ROOT, "tests", "golden", "sv_taps.npy")).astype(np.complex64) if a.multipath else (1.0,)
+    rx = capi.WifiRx(max_sym=n_sym, llr_bits=nb, want_carrier=True, chan_est=capi.EQ_LS, device=0)
+    t_all = time.perf_counter()
+    d_psdu, rows, y = rx.alloc(n * plen), rx.alloc(n * slot * 8), rx.alloc(n * slot * 8)
+    iqs = [rx.alloc(n * slot * 8) for _ in range(counts[-1])]
+    d_stats = rx.alloc(n * 16)
+    rx.mac_batch_dev(d_psdu.ptr, plen, n, None, payload_len=plen - 28, payload_seed=a.seed)
+    rx.tx_batch_dev(rows.ptr, n * slot, d_psdu.ptr, enc, psdu_len=np.full(n, plen, np.uint32), psdu_stride=plen, lead=LEAD, row_len=slot)
+    ref = dict(frames=rx.alloc(n * 32).upload(np.zeros(n * 32, np.uint8)), idx=rx.alloc(n * n_sym * 48), psdu=d_psdu, psdu_stride=plen)
+    rx.demod_batch_dev(rows.ptr, slot, n, ref)
+    assert rx.link_stats(n, ref, ref)["frames_ref"] == n, "a clean frame was not demodulated"
+    ins = [rx.alloc_out(n, psdu_stride=stride, want_csi=True) for _ in range(counts[-1])]
+    out = rx.alloc_out(n, psdu_stride=stride)
+
+    def score(dev):
+        rx.decode_batch_dev(n, dev)
+        hard = rx.link_stats(n, dev, ref)
+        rx.decode_batch_soft_dev(n, dev)
+        soft = rx.link_stats(n, dev, ref)
+        return {"fer": hard["fer"], "fer_soft": soft["fer"], "counts": {k: hard[k] for k in COUNTERS}, "counts_soft": {k: soft[k] for k in COUNTERS}}
+
+    points = []
+    for snr in a.snr:
+        t0 = time.perf_counter()
+        for ant, dev in enumerate(ins):
+            # with --multipath every antenna cycles through the tap sets from another start, so that no two share a channel
+            rx.channel_dev(rows.ptr, iqs[ant].ptr, n * slot, n, row_len=slot, taps=np.roll(taps, -7 * ant, axis=0) if a.multipath else taps,
+                           gain=math.sqrt(10 ** (snr / 10)), noise_voltage=1.0, seed=9000 + int(snr) + (a.seed << 32) + (ant << 16),
+                           doppler=fd, k_factor=a.k_factor, fade_seed=100 * a.seed + ant)
+            rx.demod_batch_dev(iqs[ant].ptr, slot, n, dev)
+        res = {"1": score(ins[0])}
+        for A in counts:
+            if A == 1:
+                continue
+            rx.diversity_combine_dev(ins[:A], n, out, "mrc")
+            res["%d_mrc" % A] = score(out)
+            rx.precombine_dev([b.ptr for b in iqs[:A]], slot, n, y.ptr, a.precombine_iters, None, d_stats.ptr)
+            rx.demod_batch_dev(y.ptr, slot, n, out)
+            res["%d_pre" % A] = score(out)
+            res["%d_pre" % A]["degenerate_slots"] = int((d_stats.download(capi.PRE_STATS_DTYPE, n)["flags"] != 0).sum())
+        points.append({"snr_db": snr, "frames": n, "seconds": time.perf_counter() - t0, "fer": {k: v["fer"] for k, v in res.items()},
+                       "fer_soft": {k: v["fer_soft"] for k, v in res.items()}, "by_arm": res})
+        print(json.dumps({k: points[-1][k] for k in ("snr_db", "seconds", "fer", "fer_soft")}), file=sys.stderr)
+    seconds_total = time.perf_counter() - t_all
+    for d in ins + [out]:
+        rx.free_out(d)
+    rx.free_out(ref)
+    for b in [rows, y, d_stats] + iqs:
+        b.free()
+    rx.close()
+    res = {"workload": "pre-detection combining on the device: %d distinct frames per point (wifirx_mac_batch, Philox payloads), encoding %d, "
+                       "PSDU %d B (%d symbols), rows of %d, lead 160, per antenna one wifirx_channel_fading call (%s, doppler %g cycles per "
+                       "sample, k_factor %g, its own fade_seed and noise seed, no carrier offset); LS demod; hard and soft decode_mac"
+                       % (n, enc, plen, n_sym, slot, "sv_taps.npy sets cycling, every tap fading" if a.multipath else "flat", fd, a.k_factor),
+           "columns": "fer / fer_soft per SNR: '1' = antenna 0 alone, 'A_mrc' = A demods and wifirx_diversity_combine (NUMERICS.md rule 23), "
+                      "'A_pre' = wifirx_precombine (rule 33, %d power iterations) and ONE demod" % a.precombine_iters,
+           "antennas": counts, "multipath": bool(a.multipath), "stats": "wifirx_link_stats on the device; reported, not asserted",
+           "seconds_total": seconds_total, "points": points}
+    print(json.dumps(res))
+    if a.out:                                       # one file for both channels: the run lands under "flat" or "multipath"
+        runs = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                runs = json.load(f).get("runs", {})
+        runs["multipath" if a.multipath else "flat"] = res
+        with open(a.out, "w") as f:
+            f.write(json.dumps({"device": rx_device_name(), "runs": runs}, indent=1) + "\n")
+
+
+def rx_device_name():
+    try:
+        import torch
+        p = torch.cuda.get_device_properties(0)
+        return "%s (%s, %d CUs)" % (p.name, getattr(p, "gcnArchName", "?"), p.multi_processor_count)
+    except Exception as e:
+        return "unknown (%s)" % e
 
 
 def fading_main(a):
