@@ -28,7 +28,6 @@
 #include "wr_channel.h"
 #include "wr_irs.h"
 #include "wr_irs_sweep.h"
-#include "wr_irs_multi.h"
 #include "wr_irs_estimate.h"
 #include "wr_irs_optimize.h"
 #include "wr_link.h"

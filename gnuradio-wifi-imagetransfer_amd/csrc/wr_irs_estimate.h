@@ -3,15 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "wr_irs_multi.h"
+#include "wr_irs.h"
 
 namespace wr {
 
 // one wifirx_irs_estimate call up to the decided phases, every pointer on the device (NUMERICS.md rule 29).  M = n_ant, N = n_elems,
 // L = n_taps, R = M L rows per set, T = n_pilots, G = n_groups, J = G + 1.  The taps under the decided phases are a
-// wr_launch_irs_multi call on `psi_out`.
+// wr_launch_irs call on `psi_out`.
 struct IrsEstimateArgs {
-    IrsMultiArgs    m;            // the scene as wifirx_irs_taps_multi has it; m.s.align_bits = B (0: nothing is decided), m.s.codes_out
+    IrsArgs         s;            // the scene as wifirx_irs_taps_multi has it; s.align_bits = B (0: nothing is decided), s.codes_out
                                   // [n_sets][G] or null; taps_out, psi, n_psi_sets and elems_out are not looked at
     const float2*   pilot;        // [T][G]: slot t, group g
     const uint16_t* group;        // [N] the group of element n, or null: the identity (G = N)

@@ -2,9 +2,9 @@
 // Channel.DFT_matrix pilots, utils/channel.py), in the float32 arithmetic of NUMERICS.md rule 29.  Two float32 GEMMs on the matrix
 // cores and one decision pass:
 //
-// irs_observe_kernel is wr_irs_multi.hip's sweep GEMM without its metric: the rows rho = m L + l of the sets against the T pilot
-// configurations, contracted over the 2 N floats of a row's element products.  The elements, the direct path and s_l come from
-// wr_irs_multi_elem.h, so a seed gives the bits wifirx_irs_taps_multi draws.  Entry t reads pilot[t][group[n]]: the group map
+// irs_observe_kernel is wr_irs_sweep.hip's GEMM without its metric: the rows rho = m L + l of the sets against the T pilot
+// configurations, contracted over the 2 N floats of a row's element products.  The row tables and the chunk's products are
+// wr_irs_tile.h's, the elements, the direct path and s_l wr_irs_elem.h's, so a seed gives the bits wifirx_irs_taps_multi draws.  Entry t reads pilot[t][group[n]]: the group map
 // expands the pilots while they are read, no [T][N] array exists.  The epilogue adds the noise and writes obs [n_sets][R][T].
 //
 // irs_despread_kernel contracts over the 2 T floats of an observation row (the obs array as floats IS the A operand) against the
@@ -12,7 +12,7 @@
 // `col` reads pilot[t][j0 + col - 1]: contiguous in j, one 128-byte line per 16 lanes, where the sweep's codebook reads are N
 // apart.  The epilogue scales by kappa, writes the estimate and, with align_bits, decides the codes of every set whose row 0 lies
 // in the tile (rule 25's argmax fed with the estimate; a blocked direct path aligns to the real axis, as there), expands them through the group map and writes the phases for
-// irs_multi_kernel, which forms the taps of the TRUE elements under them.
+// wr_irs.hip's irs_kernel, which forms the taps of the TRUE elements under them.
 //
 // No sum runs across rows, so both kernels cut the n_sets R rows into tiles of 16 consecutive rows regardless of the set borders:
 // R < 16 puts several sets into a tile, R > 16 several tiles behind a set, and no row of a tile idles except in the last one.
@@ -20,19 +20,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "wr_irs_multi_elem.h"
+#include "wr_irs_tile.h"
 #include "wr_irs_estimate.h"
 
 namespace wr {
 
 #define EST_WAVES      4
-#define EST_CHUNK      64                  // complex terms per chunk: 128 floats of the chain, 32 steps of 4
-#define EST_RS         (2 * EST_CHUNK + 4) // LDS row stride in floats (wr_irs_sweep.hip: 64 different banks per A read)
+#define EST_CHUNK      IRS_TILE_CHUNK      // complex terms per chunk: 128 floats of the chain, 32 steps of 4
+#define EST_RS         IRS_TILE_RS         // LDS row stride in floats (64 different banks per A read)
 #define EST_MAX_PILOTS 1024
 #define EST_MAX_GROUPS 1023
 #define EST_NOISE_WORD 3u                  // counter word 3 of the observation noise (0 noise, 1 fader, 2 scatter are taken)
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t est_group(const IrsEstimateArgs& a, uint32_t n) { return a.group ? (uint32_t)a.group[n] : n; }
 
@@ -40,33 +38,21 @@ template <int NG>
 __global__ __launch_bounds__(64 * EST_WAVES)
 void irs_observe_kernel(const IrsEstimateArgs a)
 {
-    __shared__ float    tile[16 * EST_RS];
-    __shared__ float2   row_hd[16];
-    __shared__ float    row_scale[16];
-    __shared__ uint32_t row_set[16], row_tap[16], row_ant[16], row_rho[16];
-    __shared__ bool     row_used[16];
+    __shared__ float       tile[16 * EST_RS];
+    __shared__ IrsTileRows rows;
 
-    const IrsMultiArgs& mu = a.m;
-    const IrsArgs& sc = mu.s;
+    const IrsArgs& sc = a.s;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t col = lane & 15, kk = lane >> 4;             // MFMA: A[row = col][k = kk], B[k = kk][col], D[row 4 kk + j][col]
     const uint32_t N = sc.n_elems, L = sc.n_taps, T = a.n_pilots, G = a.n_groups;
-    const uint32_t R = mu.n_ant * L;                            // rows of a set: rho = m L + l
-    const uint64_t rows = (uint64_t)sc.n_sets * R, q0 = (uint64_t)blockIdx.x * 16;
+    const uint32_t R = sc.n_ant * L;                            // rows of a set: rho = m L + l
+    const uint64_t n_rows = (uint64_t)sc.n_sets * R, q0 = (uint64_t)blockIdx.x * 16;
     const uint2 key = make_uint2((uint32_t)sc.seed, (uint32_t)(sc.seed >> 32));
 
     if (tid < 16) {
         const uint64_t q = q0 + tid;
-        const bool used = q < rows;
-        const uint32_t r = used ? (uint32_t)(q / R) : 0, rho = used ? (uint32_t)(q - (uint64_t)r * R) : 0;
-        const uint32_t m = rho / L, l = rho - m * L;
-        row_used[tid] = used;
-        row_set[tid] = r;
-        row_rho[tid] = rho;
-        row_tap[tid] = l;
-        row_ant[tid] = m;
-        row_hd[tid] = used ? irsm_direct(mu, m, r, l, key) : make_float2(0.0f, 0.0f);
-        row_scale[tid] = used ? sc.scale[l] : 0.0f;
+        const uint32_t r = (uint32_t)(q / R);
+        irs_tile_row(rows, tid, sc, q < n_rows, r, (uint32_t)(q - (uint64_t)r * R), key);
     }
     __syncthreads();
 
@@ -79,20 +65,7 @@ void irs_observe_kernel(const IrsEstimateArgs a)
     const bool odd = kk & 1;                                    // ... and which part of it: A is e.re (even) or e.im (odd)
 
     for (uint32_t n0 = 0; n0 < N; n0 += EST_CHUNK) {
-        // the products of the chunk into the LDS tile: lane t forms element n0 + (t & 63) of the rows (t >> 6) + 4 j
-        {
-            const uint32_t n = n0 + lane;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint32_t row = wave + 4 * j;
-                float2 e = make_float2(0.0f, 0.0f);             // no such row or element: the chain's zero terms
-                if (row_used[row] && n < N) {
-                    const IrsElem el = irsm_elem(mu, row_ant[row], row_set[row], row_tap[row], n, key);
-                    e = ch_mul(el.a, el.b);
-                }
-                *reinterpret_cast<float2*>(&tile[row * EST_RS + 2 * lane]) = e;
-            }
-        }
+        irs_tile_form(tile, rows, sc, n0, lane, wave, key);
         __syncthreads();
         const uint32_t left = N - n0;
         const uint32_t steps = left >= EST_CHUNK ? EST_CHUNK / 2 : (left + 1) / 2;        // 2 N filled up to a multiple of 4, no further
@@ -125,9 +98,9 @@ void irs_observe_kernel(const IrsEstimateArgs a)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const uint32_t row = 4 * kk + j;
-            if (!row_used[row] || t >= T) continue;
-            const float2 h = ch_add(row_hd[row], make_float2(acc_re[i][j], acc_im[i][j]));
-            const float s = row_scale[row];
+            if (rows.set[row] == IRS_NO_SET || t >= T) continue;
+            const float2 h = ch_add(rows.hd[row], make_float2(acc_re[i][j], acc_im[i][j]));
+            const float s = rows.scale[row];
             a.obs[(q0 + row) * T + t] = make_float2(h.x * s, h.y * s);
         }
     }
@@ -137,13 +110,13 @@ void irs_observe_kernel(const IrsEstimateArgs a)
     // and the Box-Muller's code stands once) ----
     for (uint32_t v = 0; v < 4u * NG; v++) {
         const uint32_t t = t_first + 16 * EST_WAVES * (v >> 2), row = 4 * kk + (v & 3);
-        if (!row_used[row] || t >= T) continue;
+        if (rows.set[row] == IRS_NO_SET || t >= T) continue;
         const uint64_t q = q0 + row;
         float2 w;
         if (a.noise) {
             w = a.noise[(q % a.n_noise) * T + t];
         } else {
-            const uint4 d = philox4x32_10(make_uint4(t, row_set[row], row_rho[row], EST_NOISE_WORD), key);
+            const uint4 d = philox4x32_10(make_uint4(t, rows.set[row], rows.ant[row] * L + rows.tap[row], EST_NOISE_WORD), key);
             w = ch_noise(d.x, d.y, 0.70710678118654752f);
         }
         a.obs[q * T + t] = ch_add(a.obs[q * T + t], make_float2(a.sigma * w.x, a.sigma * w.y));
@@ -160,11 +133,11 @@ void irs_despread_kernel(const IrsEstimateArgs a)
     __shared__ bool     row_used[16], row_first[16];
     __shared__ uint8_t  codes_s[16][EST_MAX_GROUPS + 1];
 
-    const IrsArgs& sc = a.m.s;
+    const IrsArgs& sc = a.s;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t col = lane & 15, kk = lane >> 4;
     const uint32_t N = sc.n_elems, T = a.n_pilots, G = a.n_groups, J = G + 1;
-    const uint32_t R = a.m.n_ant * sc.n_taps;
+    const uint32_t R = sc.n_ant * sc.n_taps;
     const uint64_t rows = (uint64_t)sc.n_sets * R, q0 = (uint64_t)blockIdx.x * 16;
 
     if (tid < 16) {
@@ -256,13 +229,7 @@ void irs_despread_kernel(const IrsEstimateArgs a)
             const bool axis = sc.direct_gain == 0.0f || (hd.x == 0.0f && hd.y == 0.0f);
             float2 g = make_float2(acc_re[i][j], acc_im[i][j]);
             if (!axis) g = ch_mul(make_float2(hd.x, -hd.y), g);
-            uint32_t best = 0;
-            float top = ch_mul(g, irs_multi_phase[0]).x;
-            for (uint32_t c = 1; c < n_codes; c++) {
-                const float v = ch_mul(g, irs_multi_phase[c << up]).x;
-                if (v > top) { top = v; best = c; }            // the lowest c wins a tie
-            }
-            codes_s[row][jc[i] - 1] = (uint8_t)best;
+            codes_s[row][jc[i] - 1] = (uint8_t)irs_argmax(g, irs_phase, n_codes, up);
         }
     }
     __syncthreads();
@@ -273,7 +240,7 @@ void irs_despread_kernel(const IrsEstimateArgs a)
             for (uint32_t g = tid; g < G; g += 64 * EST_WAVES) sc.codes_out[(uint64_t)r * G + g] = codes_s[row][g];
         if (a.psi_out)
             for (uint32_t n = tid; n < N; n += 64 * EST_WAVES)
-                a.psi_out[(uint64_t)r * N + n] = irs_multi_phase[(uint32_t)codes_s[row][est_group(a, n)] << up];
+                a.psi_out[(uint64_t)r * N + n] = irs_phase[(uint32_t)codes_s[row][est_group(a, n)] << up];
     }
 }
 
@@ -281,12 +248,11 @@ void irs_despread_kernel(const IrsEstimateArgs a)
 
 static bool est_args_ok(const wr::IrsEstimateArgs* a)
 {
-    const wr::IrsArgs& s = a->m.s;
-    return s.n_elems >= 1 && s.n_elems <= IRS_MAX_ELEMS && s.n_taps >= 1 && s.n_taps <= IRS_MAX_TAPS && a->m.n_ant >= 1 &&
-           a->m.n_ant <= IRSM_MAX_ANT && a->m.los_d && s.n_scatter >= 1 && s.align_bits <= 3 && a->pilot && a->obs &&
+    const wr::IrsArgs& s = a->s;
+    return irs_scene_ok(s) && s.align_bits <= 3 && a->pilot && a->obs &&
            a->n_pilots >= 1 && a->n_pilots <= EST_MAX_PILOTS && a->n_groups >= 1 && a->n_groups <= EST_MAX_GROUPS &&
            a->n_groups <= s.n_elems && (a->group || a->n_groups == s.n_elems) && (!a->noise || a->n_noise >= 1) &&
-           ((uint64_t)s.n_sets * a->m.n_ant * s.n_taps + 15) / 16 <= 0x7fffffffu;
+           ((uint64_t)s.n_sets * s.n_ant * s.n_taps + 15) / 16 <= 0x7fffffffu;
 }
 
 #define EST_LAUNCH(KERNEL, COLS) \
@@ -301,9 +267,9 @@ static bool est_args_ok(const wr::IrsEstimateArgs* a)
 
 extern "C" hipError_t wr_launch_irs_observe(hipStream_t st, const wr::IrsEstimateArgs* args)
 {
-    if (args->m.s.n_sets == 0) return hipSuccess;
+    if (args->s.n_sets == 0) return hipSuccess;
     if (!est_args_ok(args)) return hipErrorInvalidValue;        // (the entry point refuses these first)
-    const uint64_t rows = (uint64_t)args->m.s.n_sets * args->m.n_ant * args->m.s.n_taps;
+    const uint64_t rows = (uint64_t)args->s.n_sets * args->s.n_ant * args->s.n_taps;
     const dim3 grid((uint32_t)((rows + 15) / 16)), block(64 * EST_WAVES);
     EST_LAUNCH(irs_observe_kernel, args->n_pilots);
     return hipGetLastError();
@@ -311,9 +277,9 @@ extern "C" hipError_t wr_launch_irs_observe(hipStream_t st, const wr::IrsEstimat
 
 extern "C" hipError_t wr_launch_irs_despread(hipStream_t st, const wr::IrsEstimateArgs* args)
 {
-    if (args->m.s.n_sets == 0) return hipSuccess;
+    if (args->s.n_sets == 0) return hipSuccess;
     if (!est_args_ok(args)) return hipErrorInvalidValue;        // (the entry point refuses these first)
-    const uint64_t rows = (uint64_t)args->m.s.n_sets * args->m.n_ant * args->m.s.n_taps;
+    const uint64_t rows = (uint64_t)args->s.n_sets * args->s.n_ant * args->s.n_taps;
     const dim3 grid((uint32_t)((rows + 15) / 16)), block(64 * EST_WAVES);
     EST_LAUNCH(irs_despread_kernel, args->n_groups + 1);
     return hipGetLastError();

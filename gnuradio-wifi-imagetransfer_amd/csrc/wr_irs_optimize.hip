@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "wr_irs_multi_elem.h"     // irs_multi_phase; wr_irs_elem.h's irs_argmax, irs_butterfly; wr_channel.h's ch_mul, ch_add
+#include "wr_irs_elem.h"           // irs_phase, irs_argmax, irs_butterfly; wr_channel.h's ch_mul, ch_add
 #include "wr_irs_optimize.h"
 
 namespace wr {
@@ -36,10 +36,10 @@ namespace wr {
 // C_k for a k that is the same in every lane: a chain of selects over the table's constants, no load behind the argmax
 __device__ __forceinline__ float2 opt_phase(uint32_t k)
 {
-    float2 v = irs_multi_phase[0];
+    float2 v = irs_phase[0];
 #pragma unroll
     for (uint32_t i = 1; i < 8; i++)
-        if (k == i) v = irs_multi_phase[i];
+        if (k == i) v = irs_phase[i];
     return v;
 }
 
@@ -110,7 +110,7 @@ void irs_optimize_kernel(const IrsOptimizeArgs a)
             } else if (a.start == OPT_START_REF) {              // rule 29's decision: row 0 alone
                 float2 v = q[g + 1];
                 if (!axis) v = ch_mul(make_float2(hd.x, -hd.y), v);
-                c = irs_argmax(v, irs_multi_phase, n_codes, up);
+                c = irs_argmax(v, irs_phase, n_codes, up);
             }
             c = __builtin_amdgcn_readfirstlane(c);
             const float2 ph = opt_phase(c << up);
@@ -148,7 +148,7 @@ void irs_optimize_kernel(const IrsOptimizeArgs a)
                 const float2 z = irs_butterfly(                 // rule 31: tw = (w t.re, w t.im), +0 where w == 0
                     WEIGHTED ? make_float2(opt_weigh(w0, t0.x) + opt_weigh(w1, t1.x), opt_weigh(w0, t0.y) + opt_weigh(w1, t1.y))
                              : make_float2(t0.x + t1.x, t0.y + t1.y));
-                const uint32_t cn = __builtin_amdgcn_readfirstlane(irs_argmax(z, irs_multi_phase, n_codes, up));
+                const uint32_t cn = __builtin_amdgcn_readfirstlane(irs_argmax(z, irs_phase, n_codes, up));
                 if (cn != c) {                                  // otherwise s stays as it was: not (s - p) + p
                     const float2 pn = opt_phase(cn << up);
                     const float2 n0 = ch_mul(e0[k], pn), n1 = ch_mul(e1[k], pn);
@@ -174,7 +174,7 @@ void irs_optimize_kernel(const IrsOptimizeArgs a)
     if (a.psi_out)
         for (uint32_t n = lane; n < a.n_elems; n += 64) {
             const uint32_t g = a.group ? (uint32_t)a.group[n] : n;
-            a.psi_out[set * a.n_elems + n] = irs_multi_phase[(uint32_t)cs[g] << up];
+            a.psi_out[set * a.n_elems + n] = irs_phase[(uint32_t)cs[g] << up];
         }
 }
 

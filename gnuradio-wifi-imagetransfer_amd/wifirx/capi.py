@@ -745,7 +745,123 @@ class WifiRx:
             d_out.free()
         return y.reshape(x.shape)
 
-    # -- reflecting surface (wifirx_irs_taps; NUMERICS.md rule 25) --
+    # -- reflecting surface behind an AP of M antennas (wifirx_irs_taps, wifirx_irs_sweep and their _multi forms; NUMERICS.md
+    #    rules 25 to 28).  One implementation serves each pair of wrappers; `multi` says whether the antenna axis is there: with
+    #    it the call is the _multi symbol and the taps are [M, n_sets, L], without it M = 1 and they are [n_sets, L] --
+    @staticmethod
+    def _irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u, multi=True):
+        """(pdp [L], A [M, N], B [N], D [M] or None) as contiguous float32 / complex64; a 1-D los_b2r is one antenna.  Without
+        `multi` los_b2r is flattened into the one antenna's N coefficients and los_b2u is one value"""
+        p = np.ascontiguousarray(np.asarray(pdp, dtype=np.float32).reshape(-1))
+        a = np.asarray(los_b2r, dtype=np.complex64)
+        a = np.ascontiguousarray(a.reshape(1, -1) if a.ndim == 1 or not multi else a)
+        b = np.ascontiguousarray(np.asarray(los_r2u, dtype=np.complex64).reshape(-1))
+        if a.ndim != 2 or a.shape[1] != b.size:
+            raise ValueError("los_b2r must be [M, N] and los_r2u [N]" if multi else
+                             "los_b2r and los_r2u must have one length, the number of elements")
+        d = None if los_b2u is None else np.ascontiguousarray(np.asarray(los_b2u, dtype=np.complex64).reshape(-1))
+        if d is not None and d.size != a.shape[0]:
+            raise ValueError("los_b2u is one complex value per antenna" if multi else "los_b2u is one complex value")
+        return p, a, b, d
+
+    @staticmethod
+    def _irs_shape(pdp, los_b2r, multi):
+        """(L, M, N) of a scene as the host-array wrappers are given it"""
+        a = np.asarray(los_b2r)
+        return np.asarray(pdp).size, (a.shape[0] if multi and a.ndim > 1 else 1), (a.shape[-1] if multi else a.size)
+
+    def _irs_scatter(self, bufs, kw, scatter, M, N, multi=True):
+        """upload a host `scatter` [n_scatter, (M + 1) N + M] into bufs["scatter"] and name it in the keywords of the _dev call"""
+        if scatter is None:
+            return
+        s = np.ascontiguousarray(scatter, dtype=np.complex64)
+        if s.ndim != 2 or s.shape[1] != (M + 1) * N + M:
+            raise ValueError("scatter must be [n_scatter, (M + 1) N + M]" if multi else "scatter must be [n_scatter, 2 N + 1]")
+        bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
+        kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
+
+    def _irs_call(self, fn, multi, taps_ptr, n_sets, scene, gain, k_factor, direct_gain, middle, scatter, n_scatter, seed, outs):
+        """one wifirx_irs_taps* / wifirx_irs_sweep* call: `scene` = (p, a, b, d) of _irs_multi_scene, `middle` the three
+        arguments between direct_gain and scatter (psi or the codebook), `outs` the two output pointers behind the seed.  The C
+        order: h, taps_out, [n_ant,] n_sets, n_taps, pdp, gain, n_elems, los_b2r, los_r2u, los_b2u, k_factor, direct_gain,
+        then (psi, psi_on_device, n_psi_sets, align_bits) or (codebook, codebook_on_device, n_codes), then scatter, n_scatter,
+        irs_seed, then (elems_out, codes_out) or (best_out, power_out)"""
+        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
+        p, a, b, d = scene
+        if scatter is not None and n_scatter is None:
+            raise ValueError("device scatter needs n_scatter")
+        ant = (a.shape[0],) if multi else ()
+        self._check(fn(self._h, ptr(taps_ptr), *ant, int(n_sets), p.size, _np_ptr(p), float(gain), b.size, _np_ptr(a), _np_ptr(b),
+                       _np_ptr(d), float(k_factor), float(direct_gain), *middle, ptr(scatter), int(n_scatter or 0),
+                       int(seed) & 0xFFFFFFFFFFFFFFFF, *(ptr(o) for o in outs)))
+
+    def _irs_taps_dev(self, multi, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u, gain, k_factor, direct_gain, psi,
+                      n_psi_sets, align_bits, scatter, n_scatter, seed, elems_ptr, codes_ptr):
+        scene = self._irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u, multi)
+        keep, psi_ptr, psi_dev, n_psi = None, None, 0, 0
+        if isinstance(psi, (int, DevBuf)):
+            psi_ptr, psi_dev, n_psi = (psi.ptr if isinstance(psi, DevBuf) else psi), 1, int(n_psi_sets or 1)
+        elif psi is not None:
+            keep = np.asarray(psi, dtype=np.complex64)
+            keep = np.ascontiguousarray(keep[None] if keep.ndim == 1 else keep)
+            if keep.ndim != 2 or keep.shape[1] != scene[2].size:
+                raise ValueError("psi must be [N] or [n_psi_sets, N]")
+            psi_ptr, n_psi = _np_ptr(keep), keep.shape[0]
+        self._irs_call(_lib.wifirx_irs_taps_multi if multi else _lib.wifirx_irs_taps, multi, taps_ptr, n_sets, scene, gain,
+                       k_factor, direct_gain, (psi_ptr, psi_dev, n_psi, int(align_bits)), scatter, n_scatter, seed,
+                       (elems_ptr, codes_ptr))
+
+    def _irs_sweep_dev(self, multi, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook, n_codes, gain, k_factor,
+                       direct_gain, scatter, n_scatter, seed, best_ptr, power_ptr):
+        scene = self._irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u, multi)
+        if isinstance(codebook, (int, DevBuf)):
+            keep, cb_ptr, cb_dev, n_cb = None, (codebook.ptr if isinstance(codebook, DevBuf) else codebook), 1, int(n_codes or 0)
+        else:
+            keep = np.ascontiguousarray(np.asarray(codebook, dtype=np.complex64))
+            if keep.ndim != 2 or keep.shape[1] != scene[2].size:
+                raise ValueError("codebook must be [K, N]")
+            cb_ptr, cb_dev, n_cb = _np_ptr(keep), 0, keep.shape[0]
+        self._irs_call(_lib.wifirx_irs_sweep_multi if multi else _lib.wifirx_irs_sweep, multi, taps_ptr, n_sets, scene, gain,
+                       k_factor, direct_gain, (cb_ptr, cb_dev, n_cb), scatter, n_scatter, seed, (best_ptr, power_ptr))
+
+    def _irs_taps(self, multi, n_sets, pdp, los_b2r, los_r2u, los_b2u, scatter, want_elems, want_codes, kw):
+        n_sets, (L, M, N) = int(n_sets), self._irs_shape(pdp, los_b2r, multi)
+        shapes = {"taps": (np.complex64, (M, n_sets, L) if multi else (n_sets, L))}
+        if want_elems:
+            shapes["elems"] = (np.complex64, (n_sets, L, M + 1, N))
+        if want_codes:
+            shapes["codes"] = (np.uint8, (n_sets, N))
+        bufs = {}
+        try:
+            for w, (dt, sh) in shapes.items():
+                bufs[w] = self.alloc(max(int(np.prod(sh)), 1) * np.dtype(dt).itemsize)
+            self._irs_scatter(bufs, kw, scatter, M, N, multi)
+            (self.irs_taps_multi_dev if multi else self.irs_taps_dev)(
+                bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, elems_ptr=bufs.get("elems"), codes_ptr=bufs.get("codes"), **kw)
+            out = {w: bufs[w].download(dt, int(np.prod(sh))).reshape(sh) for w, (dt, sh) in shapes.items()}
+        finally:
+            for b in bufs.values():
+                b.free()
+        return out if (want_elems or want_codes) else out["taps"]
+
+    def _irs_sweep(self, multi, n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook, scatter, kw):
+        n_sets, (L, M, N) = int(n_sets), self._irs_shape(pdp, los_b2r, multi)
+        K = int(kw.get("n_codes") or 0) if isinstance(codebook, (int, DevBuf)) else np.asarray(codebook).shape[0]
+        shapes = {"taps": (np.complex64, (M, n_sets, L) if multi else (n_sets, L)), "best": (np.uint16, (n_sets,)),
+                  "power": (np.float32, (n_sets, K))}
+        bufs = {}
+        try:
+            for w, (dt, sh) in shapes.items():
+                bufs[w] = self.alloc(max(int(np.prod(sh)), 1) * np.dtype(dt).itemsize)
+            self._irs_scatter(bufs, kw, scatter, M, N, multi)
+            (self.irs_sweep_multi_dev if multi else self.irs_sweep_dev)(
+                bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook=codebook, best_ptr=bufs["best"],
+                power_ptr=bufs["power"], **kw)
+            return {w: bufs[w].download(dt, int(np.prod(sh))).reshape(sh) for w, (dt, sh) in shapes.items()}
+        finally:
+            for b in bufs.values():
+                b.free()
+
     def irs_taps_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, gain=1.0, k_factor=0.0, direct_gain=1.0,
                      psi=None, n_psi_sets=None, align_bits=0, scatter=None, n_scatter=None, seed=0, elems_ptr=None,
                      codes_ptr=None):
@@ -756,61 +872,15 @@ class WifiRx:
         per draw instead and psi is not read.  scatter: None = Philox draws keyed by `seed`, or a device pointer to n_scatter
         rows of 2 N + 1 complex64.  elems_ptr / codes_ptr: optional device outputs [n_sets, L, 2, N] complex64 / [n_sets, N]
         uint8.  Asynchronous on the handle's stream."""
-        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
-        c64 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.complex64).reshape(-1))
-        p = np.ascontiguousarray(np.asarray(pdp, dtype=np.float32).reshape(-1))
-        a, b = c64(los_b2r), c64(los_r2u)
-        if a.size != b.size:
-            raise ValueError("los_b2r and los_r2u must have one length, the number of elements")
-        d = None if los_b2u is None else c64(los_b2u)
-        if d is not None and d.size != 1:
-            raise ValueError("los_b2u is one complex value")
-        keep, psi_ptr, psi_dev, n_psi = None, None, 0, 0
-        if isinstance(psi, (int, DevBuf)):
-            psi_ptr, psi_dev, n_psi = ptr(psi), 1, int(n_psi_sets or 1)
-        elif psi is not None:
-            keep = np.asarray(psi, dtype=np.complex64)
-            keep = np.ascontiguousarray(keep[None] if keep.ndim == 1 else keep)
-            if keep.ndim != 2 or keep.shape[1] != a.size:
-                raise ValueError("psi must be [N] or [n_psi_sets, N]")
-            psi_ptr, n_psi = _np_ptr(keep), keep.shape[0]
-        if scatter is not None and n_scatter is None:
-            raise ValueError("device scatter needs n_scatter")
-        self._check(_lib.wifirx_irs_taps(self._h, ptr(taps_ptr), int(n_sets), p.size, _np_ptr(p), float(gain), a.size, _np_ptr(a),
-                                         _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain), psi_ptr, psi_dev, n_psi,
-                                         int(align_bits), ptr(scatter), int(n_scatter or 0), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                         ptr(elems_ptr), ptr(codes_ptr)))
+        self._irs_taps_dev(False, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u, gain, k_factor, direct_gain, psi, n_psi_sets,
+                           align_bits, scatter, n_scatter, seed, elems_ptr, codes_ptr)
 
     def irs_taps(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, scatter=None, want_elems=False, want_codes=False, **kw):
         """irs_taps_dev with host arrays: returns the taps as complex64 [n_sets, L], or a dict with them under "taps" and the
         elements [n_sets, L, 2, N] under "elems" / the codes [n_sets, N] under "codes" when asked for.  scatter: None or a host
         array [n_scatter, 2 N + 1].  psi and the other keywords as irs_taps_dev."""
-        n_sets, L, N = int(n_sets), np.asarray(pdp).size, np.asarray(los_b2r).size
-        bufs = {"taps": self.alloc(max(n_sets * L, 1) * 8)}
-        try:
-            if scatter is not None:
-                s = np.ascontiguousarray(scatter, dtype=np.complex64)
-                if s.ndim != 2 or s.shape[1] != 2 * N + 1:
-                    raise ValueError("scatter must be [n_scatter, 2 N + 1]")
-                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
-                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
-            if want_elems:
-                bufs["elems"] = self.alloc(max(n_sets * L * 2 * N, 1) * 8)
-            if want_codes:
-                bufs["codes"] = self.alloc(max(n_sets * N, 1))
-            self.irs_taps_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, elems_ptr=bufs.get("elems"),
-                              codes_ptr=bufs.get("codes"), **kw)
-            out = {"taps": bufs["taps"].download(np.complex64, n_sets * L).reshape(n_sets, L)}
-            if want_elems:
-                out["elems"] = bufs["elems"].download(np.complex64, n_sets * L * 2 * N).reshape(n_sets, L, 2, N)
-            if want_codes:
-                out["codes"] = bufs["codes"].download(np.uint8, n_sets * N).reshape(n_sets, N)
-        finally:
-            for b in bufs.values():
-                b.free()
-        return out if (want_elems or want_codes) else out["taps"]
+        return self._irs_taps(False, n_sets, pdp, los_b2r, los_r2u, los_b2u, scatter, want_elems, want_codes, kw)
 
-    # -- beam training of the surface (wifirx_irs_sweep; NUMERICS.md rule 26) --
     def irs_sweep_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, codebook, n_codes=None, gain=1.0,
                       k_factor=0.0, direct_gain=1.0, scatter=None, n_scatter=None, seed=0, best_ptr=None, power_ptr=None):
         """wifirx_irs_sweep into device memory: for each of n_sets tap sets the elements of irs_taps_dev (the same seed gives
@@ -819,67 +889,14 @@ class WifiRx:
         [n_sets, K]).  Each of the three is an int device pointer, a DevBuf or None; one at least is required.  codebook: a host
         array [K, N] complex, or a device pointer (then n_codes says its rows); K <= 1024.  The other arguments as
         irs_taps_dev.  Asynchronous on the handle's stream."""
-        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
-        c64 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.complex64).reshape(-1))
-        p = np.ascontiguousarray(np.asarray(pdp, dtype=np.float32).reshape(-1))
-        a, b = c64(los_b2r), c64(los_r2u)
-        if a.size != b.size:
-            raise ValueError("los_b2r and los_r2u must have one length, the number of elements")
-        d = None if los_b2u is None else c64(los_b2u)
-        if d is not None and d.size != 1:
-            raise ValueError("los_b2u is one complex value")
-        if isinstance(codebook, (int, DevBuf)):
-            keep, cb_ptr, cb_dev, n_cb = None, ptr(codebook), 1, int(n_codes or 0)
-        else:
-            keep = np.ascontiguousarray(np.asarray(codebook, dtype=np.complex64))
-            if keep.ndim != 2 or keep.shape[1] != a.size:
-                raise ValueError("codebook must be [K, N]")
-            cb_ptr, cb_dev, n_cb = _np_ptr(keep), 0, keep.shape[0]
-        if scatter is not None and n_scatter is None:
-            raise ValueError("device scatter needs n_scatter")
-        self._check(_lib.wifirx_irs_sweep(self._h, ptr(taps_ptr), int(n_sets), p.size, _np_ptr(p), float(gain), a.size, _np_ptr(a),
-                                          _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain), cb_ptr, cb_dev, n_cb,
-                                          ptr(scatter), int(n_scatter or 0), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                          ptr(best_ptr), ptr(power_ptr)))
+        self._irs_sweep_dev(False, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook, n_codes, gain, k_factor,
+                            direct_gain, scatter, n_scatter, seed, best_ptr, power_ptr)
 
     def irs_sweep(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, codebook, scatter=None, **kw):
         """irs_sweep_dev with host arrays: returns {"taps": complex64 [n_sets, L], "best": uint16 [n_sets], "power": float32
         [n_sets, K]}.  codebook: a host array [K, N] or a device pointer with n_codes=K; scatter: None or a host array
         [n_scatter, 2 N + 1].  The other keywords as irs_sweep_dev."""
-        n_sets, L, N = int(n_sets), np.asarray(pdp).size, np.asarray(los_b2r).size
-        K = int(kw.get("n_codes") or 0) if isinstance(codebook, (int, DevBuf)) else np.asarray(codebook).shape[0]
-        bufs = {"taps": self.alloc(max(n_sets * L, 1) * 8), "best": self.alloc(max(n_sets, 1) * 2),
-                "power": self.alloc(max(n_sets * K, 1) * 4)}
-        try:
-            if scatter is not None:
-                s = np.ascontiguousarray(scatter, dtype=np.complex64)
-                if s.ndim != 2 or s.shape[1] != 2 * N + 1:
-                    raise ValueError("scatter must be [n_scatter, 2 N + 1]")
-                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
-                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
-            self.irs_sweep_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook=codebook, best_ptr=bufs["best"],
-                               power_ptr=bufs["power"], **kw)
-            return {"taps": bufs["taps"].download(np.complex64, n_sets * L).reshape(n_sets, L),
-                    "best": bufs["best"].download(np.uint16, n_sets),
-                    "power": bufs["power"].download(np.float32, n_sets * K).reshape(n_sets, K)}
-        finally:
-            for b in bufs.values():
-                b.free()
-
-    # -- the surface behind an AP of M antennas (wifirx_irs_taps_multi, wifirx_irs_sweep_multi; NUMERICS.md rules 27, 28) --
-    @staticmethod
-    def _irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u):
-        """(pdp [L], A [M, N], B [N], D [M] or None) as contiguous float32 / complex64; a 1-D los_b2r is one antenna"""
-        p = np.ascontiguousarray(np.asarray(pdp, dtype=np.float32).reshape(-1))
-        a = np.asarray(los_b2r, dtype=np.complex64)
-        a = np.ascontiguousarray(a[None] if a.ndim == 1 else a)
-        b = np.ascontiguousarray(np.asarray(los_r2u, dtype=np.complex64).reshape(-1))
-        if a.ndim != 2 or a.shape[1] != b.size:
-            raise ValueError("los_b2r must be [M, N] and los_r2u [N]")
-        d = None if los_b2u is None else np.ascontiguousarray(np.asarray(los_b2u, dtype=np.complex64).reshape(-1))
-        if d is not None and d.size != a.shape[0]:
-            raise ValueError("los_b2u is one complex value per antenna")
-        return p, a, b, d
+        return self._irs_sweep(False, n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook, scatter, kw)
 
     def irs_taps_multi_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, gain=1.0, k_factor=0.0,
                            direct_gain=1.0, psi=None, n_psi_sets=None, align_bits=0, scatter=None, n_scatter=None, seed=0,
@@ -891,54 +908,15 @@ class WifiRx:
         Philox draws keyed by `seed`, or a device pointer to n_scatter rows of (M + 1) N + M complex64.  elems_ptr / codes_ptr:
         optional device outputs [n_sets, L, M + 1, N] complex64 (a_0 .. a_{M-1}, b) / [n_sets, N] uint8.  The other arguments as
         irs_taps_dev.  Asynchronous on the handle's stream."""
-        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
-        p, a, b, d = self._irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u)
-        keep, psi_ptr, psi_dev, n_psi = None, None, 0, 0
-        if isinstance(psi, (int, DevBuf)):
-            psi_ptr, psi_dev, n_psi = ptr(psi), 1, int(n_psi_sets or 1)
-        elif psi is not None:
-            keep = np.asarray(psi, dtype=np.complex64)
-            keep = np.ascontiguousarray(keep[None] if keep.ndim == 1 else keep)
-            if keep.ndim != 2 or keep.shape[1] != b.size:
-                raise ValueError("psi must be [N] or [n_psi_sets, N]")
-            psi_ptr, n_psi = _np_ptr(keep), keep.shape[0]
-        if scatter is not None and n_scatter is None:
-            raise ValueError("device scatter needs n_scatter")
-        self._check(_lib.wifirx_irs_taps_multi(self._h, ptr(taps_ptr), a.shape[0], int(n_sets), p.size, _np_ptr(p), float(gain),
-                                               b.size, _np_ptr(a), _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain),
-                                               psi_ptr, psi_dev, n_psi, int(align_bits), ptr(scatter), int(n_scatter or 0),
-                                               int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(elems_ptr), ptr(codes_ptr)))
+        self._irs_taps_dev(True, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u, gain, k_factor, direct_gain, psi, n_psi_sets,
+                           align_bits, scatter, n_scatter, seed, elems_ptr, codes_ptr)
 
     def irs_taps_multi(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, scatter=None, want_elems=False, want_codes=False,
                        **kw):
         """irs_taps_multi_dev with host arrays: returns the taps as complex64 [M, n_sets, L], or a dict with them under "taps"
         and the elements [n_sets, L, M + 1, N] under "elems" / the codes [n_sets, N] under "codes" when asked for.  scatter:
         None or a host array [n_scatter, (M + 1) N + M]."""
-        a = np.asarray(los_b2r)
-        n_sets, L, M, N = int(n_sets), np.asarray(pdp).size, (1 if a.ndim == 1 else a.shape[0]), a.shape[-1]
-        bufs = {"taps": self.alloc(max(M * n_sets * L, 1) * 8)}
-        try:
-            if scatter is not None:
-                s = np.ascontiguousarray(scatter, dtype=np.complex64)
-                if s.ndim != 2 or s.shape[1] != (M + 1) * N + M:
-                    raise ValueError("scatter must be [n_scatter, (M + 1) N + M]")
-                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
-                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
-            if want_elems:
-                bufs["elems"] = self.alloc(max(n_sets * L * (M + 1) * N, 1) * 8)
-            if want_codes:
-                bufs["codes"] = self.alloc(max(n_sets * N, 1))
-            self.irs_taps_multi_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, elems_ptr=bufs.get("elems"),
-                                    codes_ptr=bufs.get("codes"), **kw)
-            out = {"taps": bufs["taps"].download(np.complex64, M * n_sets * L).reshape(M, n_sets, L)}
-            if want_elems:
-                out["elems"] = bufs["elems"].download(np.complex64, n_sets * L * (M + 1) * N).reshape(n_sets, L, M + 1, N)
-            if want_codes:
-                out["codes"] = bufs["codes"].download(np.uint8, n_sets * N).reshape(n_sets, N)
-        finally:
-            for b in bufs.values():
-                b.free()
-        return out if (want_elems or want_codes) else out["taps"]
+        return self._irs_taps(True, n_sets, pdp, los_b2r, los_r2u, los_b2u, scatter, want_elems, want_codes, kw)
 
     def irs_sweep_multi_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, codebook, n_codes=None, gain=1.0,
                             k_factor=0.0, direct_gain=1.0, scatter=None, n_scatter=None, seed=0, best_ptr=None, power_ptr=None):
@@ -947,45 +925,13 @@ class WifiRx:
         taps_ptr as [M, n_sets, L], the winning entry to best_ptr (uint16 [n_sets]), every entry's summed power to power_ptr
         (float32 [n_sets, K]); one of the three at least.  The other arguments as irs_sweep_dev and irs_taps_multi_dev.
         Asynchronous on the handle's stream."""
-        ptr = lambda p: p.ptr if isinstance(p, DevBuf) else p
-        p, a, b, d = self._irs_multi_scene(pdp, los_b2r, los_r2u, los_b2u)
-        if isinstance(codebook, (int, DevBuf)):
-            keep, cb_ptr, cb_dev, n_cb = None, ptr(codebook), 1, int(n_codes or 0)
-        else:
-            keep = np.ascontiguousarray(np.asarray(codebook, dtype=np.complex64))
-            if keep.ndim != 2 or keep.shape[1] != b.size:
-                raise ValueError("codebook must be [K, N]")
-            cb_ptr, cb_dev, n_cb = _np_ptr(keep), 0, keep.shape[0]
-        if scatter is not None and n_scatter is None:
-            raise ValueError("device scatter needs n_scatter")
-        self._check(_lib.wifirx_irs_sweep_multi(self._h, ptr(taps_ptr), a.shape[0], int(n_sets), p.size, _np_ptr(p), float(gain),
-                                                b.size, _np_ptr(a), _np_ptr(b), _np_ptr(d), float(k_factor), float(direct_gain),
-                                                cb_ptr, cb_dev, n_cb, ptr(scatter), int(n_scatter or 0),
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(best_ptr), ptr(power_ptr)))
+        self._irs_sweep_dev(True, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook, n_codes, gain, k_factor,
+                            direct_gain, scatter, n_scatter, seed, best_ptr, power_ptr)
 
     def irs_sweep_multi(self, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, codebook, scatter=None, **kw):
         """irs_sweep_multi_dev with host arrays: returns {"taps": complex64 [M, n_sets, L], "best": uint16 [n_sets], "power":
         float32 [n_sets, K]}.  scatter: None or a host array [n_scatter, (M + 1) N + M]."""
-        a = np.asarray(los_b2r)
-        n_sets, L, M, N = int(n_sets), np.asarray(pdp).size, (1 if a.ndim == 1 else a.shape[0]), a.shape[-1]
-        K = int(kw.get("n_codes") or 0) if isinstance(codebook, (int, DevBuf)) else np.asarray(codebook).shape[0]
-        bufs = {"taps": self.alloc(max(M * n_sets * L, 1) * 8), "best": self.alloc(max(n_sets, 1) * 2),
-                "power": self.alloc(max(n_sets * K, 1) * 4)}
-        try:
-            if scatter is not None:
-                s = np.ascontiguousarray(scatter, dtype=np.complex64)
-                if s.ndim != 2 or s.shape[1] != (M + 1) * N + M:
-                    raise ValueError("scatter must be [n_scatter, (M + 1) N + M]")
-                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
-                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
-            self.irs_sweep_multi_dev(bufs["taps"], n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook=codebook,
-                                     best_ptr=bufs["best"], power_ptr=bufs["power"], **kw)
-            return {"taps": bufs["taps"].download(np.complex64, M * n_sets * L).reshape(M, n_sets, L),
-                    "best": bufs["best"].download(np.uint16, n_sets),
-                    "power": bufs["power"].download(np.float32, n_sets * K).reshape(n_sets, K)}
-        finally:
-            for b in bufs.values():
-                b.free()
+        return self._irs_sweep(True, n_sets, pdp, los_b2r, los_r2u, los_b2u, codebook, scatter, kw)
 
     # -- the surface configured from noisy pilot observations (wifirx_irs_estimate; NUMERICS.md rule 29) --
     def irs_estimate_dev(self, taps_ptr, n_sets, pdp, los_b2r, los_r2u, los_b2u=None, *, pilots, n_pilots=None, n_groups=None,
@@ -1034,8 +980,7 @@ class WifiRx:
         "est" complex64 [n_sets, M L, G + 1], "codes" uint8 [n_sets, G], "obs" complex64 [n_sets, M L, T].  With align_bits = 0
         "taps" and "codes" are left out.  pilots: a host array [T, G]; scatter: None or a host array [n_scatter, (M + 1) N + M];
         noise: None or a host array [n_noise, T]."""
-        a = np.asarray(los_b2r)
-        n_sets, L, M, N = int(n_sets), np.asarray(pdp).size, (1 if a.ndim == 1 else a.shape[0]), a.shape[-1]
+        n_sets, (L, M, N) = int(n_sets), self._irs_shape(pdp, los_b2r, True)
         pl = np.asarray(pilots)
         if pl.ndim != 2:
             raise ValueError("pilots must be [T, G]")
@@ -1051,12 +996,7 @@ class WifiRx:
             for w in want:
                 dt, sh = shapes[w]
                 bufs[w] = self.alloc(max(int(np.prod(sh)) * np.dtype(dt).itemsize, 8))
-            if scatter is not None:
-                s = np.ascontiguousarray(scatter, dtype=np.complex64)
-                if s.ndim != 2 or s.shape[1] != (M + 1) * N + M:
-                    raise ValueError("scatter must be [n_scatter, (M + 1) N + M]")
-                bufs["scatter"] = self.alloc(max(s.nbytes, 1)).upload(s)
-                kw.update(scatter=bufs["scatter"], n_scatter=s.shape[0])
+            self._irs_scatter(bufs, kw, scatter, M, N)
             if noise is not None:
                 w = np.ascontiguousarray(noise, dtype=np.complex64)
                 if w.ndim != 2 or w.shape[1] != T:

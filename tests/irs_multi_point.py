@@ -25,7 +25,8 @@ import sys
 
 import numpy as np
 
-N_FRAMES, ENC, PLEN, LEAD, TAIL = 256, 2, 100, 160, 79
+from irs_point import ENC, LEAD, N_FRAMES, PLEN, TAIL, geometry     # the same frames in the same slots
+
 N_ANT = 4
 SNR_DB = -23.0
 SCALE, BITS, OVER, K_FACTOR = 8, 2, 2, 3.0
@@ -35,12 +36,6 @@ N_TAPS = 8
 PDP = tuple(float(v) for v in (np.exp(-np.arange(N_TAPS) / 2.0) / np.exp(-np.arange(N_TAPS) / 2.0).sum()).astype(np.float32))
 SINGLE_AT_MOST, MRC_AT_LEAST = N_FRAMES // 4, 3 * N_FRAMES // 4
 GRID = range(-32, -20)
-
-
-def geometry():
-    from wifirx import txgen
-    slot = LEAD + txgen.frame_samples(PLEN, ENC) + TAIL
-    return txgen.n_sym_for(PLEN, ENC), slot + (slot & 1)
 
 
 def scene(n_ant=N_ANT):

@@ -1,4 +1,4 @@
-"""NUMERICS.md rules 27 and 28 restated on the host: what wifirx_irs_taps_multi and wifirx_irs_sweep_multi (wr_irs_multi.hip)
+"""NUMERICS.md rules 27 and 28 restated on the host: what wifirx_irs_taps_multi and wifirx_irs_sweep_multi (wr_irs.hip, wr_irs_sweep.hip)
 compute, value for value.
 
 Built on tests/irs_ref.py (rule 25) and tests/irs_sweep_ref.py (rule 26): antenna m of rule 27 IS rule 25 on the scatter row

@@ -17,19 +17,14 @@ import sys
 
 import numpy as np
 
-N_FRAMES, ENC, PLEN, LEAD, TAIL = 256, 2, 100, 160, 79
+from irs_point import ENC, LEAD, N_FRAMES, PLEN, TAIL, geometry     # the same frames in the same slots
+
 SNR_DB = -22.0
 SCALE, BITS, OVER, K_FACTOR = 8, 2, 2, 3.0
 N_ELEMS = SCALE * SCALE
 PSDU_SEED, NOISE_SEED, IRS_SEED, PSI_SEED = 31, 9300, 41, 43
 ARMS = ("random", "sweep")
 RANDOM_AT_MOST, SWEEP_AT_LEAST = 64, 250
-
-
-def geometry():
-    from wifirx import txgen
-    slot = LEAD + txgen.frame_samples(PLEN, ENC) + TAIL
-    return txgen.n_sym_for(PLEN, ENC), slot + (slot & 1)
 
 
 def scene():

@@ -79,7 +79,7 @@ def test_reference_fixture_on_the_device(rx):
 # ---- 2. the aligned mode ----
 
 @pytest.mark.parametrize("bits", [1, 2, 3])
-@pytest.mark.parametrize("N", [1, 65, 300, 4096])
+@pytest.mark.parametrize("N", [1, 63, 64, 65, 300, 4096])
 def test_aligned_mode_value_for_value(rx, bits, N):
     rng = np.random.default_rng(50 * bits + N)
     L, n_sets = 3, 4

@@ -1,4 +1,4 @@
-"""wifirx_irs_taps_multi and wifirx_irs_sweep_multi, the reflecting surface behind an AP of M antennas (wr_irs_multi.hip, NUMERICS.md
+"""wifirx_irs_taps_multi and wifirx_irs_sweep_multi, the reflecting surface behind an AP of M antennas (wr_irs.hip, wr_irs_sweep.hip, NUMERICS.md
 rules 27 and 28), on the device:
   * given scatter: taps, elements, codes / powers, winners, taps value for value tests/irs_multi_ref.py, over 1 / 2 / 3 / 8 antennas,
     the lane tail and several passes of N, 1 / 3 / 16 taps, wrapped psi sets and scatter rows, Rayleigh and Rician, the direct path on

@@ -67,6 +67,7 @@ CASES = [(1, 1, 1, 1, 0.0, 1.0, False),
          (3, 5, 7, 16, 0.0, 0.0, False),
          (63, 16, 7, 17, 10.0, 1.0, False),
          (64, 1, 7, 100, 10.0, 1.0, True),
+         (64, 5, 7, 65, 10.0, 0.7, False),               # K = 65: the first entry of a wave's second group
          (65, 3, 7, 256, 0.0, 1.0, False),
          (130, 5, 1, 17, 10.0, 0.0, False),
          (257, 3, 7, 100, 10.0, 1.0, True),
