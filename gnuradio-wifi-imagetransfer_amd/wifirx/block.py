@@ -537,6 +537,224 @@ class wifi_phy_rx_wideband(grshim.sync_block):
             self._cz = None
 
 
+class _arb_stream:
+    """What ``arb_resampler`` and ``wifi_phy_rx_resampled`` share: one handle, the stream indices j0 and m0 of
+    wifirx_arb_resample (NUMERICS.md rule 34), the two history buffers used in turn, and the device buffers of a call."""
+
+    def __init__(self, rate_in, rate_out, sample_format, sample_scale, device):
+        self.fmt = capi.iq_format(sample_format)
+        if self.fmt not in capi.IQ_DTYPE:
+            raise ValueError("sample_format must be 'fc32', 'sc16' or 'sc8'")
+        self.scale = float(capi.IQ_SCALE[self.fmt] if sample_scale is None else sample_scale)
+        self.item = capi.IQ_DTYPE[self.fmt]
+        self.in_sig = [np.complex64] if self.fmt == capi.IQ_FC32 else [(self.item.type, 2)]
+        self.bps = 8 if self.fmt == capi.IQ_FC32 else 2 * self.item.itemsize             # bytes per sample
+        self.num, self.den = capi.arb_ratio(rate_in, rate_out)
+        self.S = max(self.num, self.den)
+        self.rx = capi.WifiRx(max_sym=1, device=device)            # the resampling handle: its receive side stays unused
+        self.j0 = self.m0 = 0                                       # stream indices of the next input and the next output
+        self.hist = [self.rx.alloc(capi.arb_hist(self.num, self.den) * self.bps) for _ in range(2)]
+        self.hist_cur = None                                        # index of the buffer that holds the history; None: a new stream
+        self.d_in = self.d_out = None
+        self.cap_in = self.cap_out = 0
+
+    def room(self, n_out):
+        """the most inputs with which the next call makes at most n_out outputs"""
+        return max(0, ((self.m0 + n_out) * self.num + 16 * self.S) // self.den - self.j0)
+
+    def flush_inputs(self):
+        """the zeros behind the stream with which every input instant so far has come out: ceil(16 S / den)"""
+        return -((-16 * self.S) // self.den)
+
+    def run(self, raw, n):
+        """n samples (raw: their bytes) -> (device pointer of the outputs, their number); asynchronous on the handle's stream"""
+        n_out = capi.arb_count(self.num, self.den, self.j0, n, self.m0)
+        if n > self.cap_in:
+            if self.d_in is not None:
+                self.d_in.free()
+            self.cap_in = n + n // 2
+            self.d_in = self.rx.alloc(self.cap_in * self.bps)
+        if n_out > self.cap_out:
+            if self.d_out is not None:
+                self.d_out.free()
+            self.cap_out = n_out + n_out // 2
+            self.d_out = self.rx.alloc(self.cap_out * 8)
+        rx = self.rx
+        rx._check(capi.lib().wifirx_memcpy_h2d(rx._h, self.d_in.ptr, raw.ctypes.data, n * self.bps))
+        nxt = 1 if self.hist_cur == 0 else 0
+        got = rx.arb_resample_dev(self.d_in.ptr, self.fmt, n, self.num, self.den, None if n_out == 0 else self.d_out.ptr,
+                                  self.cap_out, hist_ptr=None if self.hist_cur is None else self.hist[self.hist_cur].ptr,
+                                  hist_out_ptr=self.hist[nxt].ptr, j0=self.j0, m0=self.m0, scale=self.scale)
+        self.hist_cur, self.j0, self.m0 = nxt, self.j0 + n, self.m0 + got
+        return (self.d_out.ptr if got else None), got
+
+    def items(self, x):
+        """the scheduler's items as (contiguous bytes, number of samples)"""
+        if x.dtype != self.item or not x.flags.c_contiguous:
+            x = np.ascontiguousarray(x, dtype=self.item)
+        return x.reshape(-1).view(np.uint8), len(x)
+
+    def zeros(self, n):
+        return np.zeros(n * self.bps, np.uint8)
+
+    def close(self):
+        for b in list(self.hist) + [self.d_in, self.d_out]:
+            if b is not None:
+                b.free()
+        self.hist, self.d_in, self.d_out, self.cap_in, self.cap_out = [], None, None, 0, 0
+        if self.rx is not None:
+            self.rx.close()
+            self.rx = None
+
+
+class arb_resampler(grshim.basic_block):
+    """GNU Radio's ``rational_resampler`` / ``pfb_arb_resampler_ccf`` on the device: one stream of ``sample_format`` items at
+    ``rate_in`` Hz in, one ``complex64`` stream at ``rate_out`` Hz out, by wifirx_arb_resample (NUMERICS.md rule 34).  The
+    rates' ratio in lowest terms must lie within ``capi.arb_ratio``'s limits (25, 30.72, 40, 50, 61.44, 80 MS/s to or from
+    20 MS/s all do).
+
+    ``general_work()`` (``work()`` on the shim) consumes as many input items as the output buffer has room for, writes the
+    outputs they complete and returns their number; ``consumed`` holds the number of items the call took.  The stream
+    indices and the history stay with the block (two device buffers used in turn), so the output does not depend on how
+    the scheduler cuts the stream, and there is no delay: output m is the input at time m * rate_in / rate_out.  The last
+    ceil(16 S / den) input instants come out only after that many more samples: ``stop()`` pushes them as zeros and
+    leaves the outputs in ``tail``."""
+
+    def __init__(self, rate_in, rate_out, sample_format="fc32", sample_scale=None, device=0):
+        self._s = _arb_stream(rate_in, rate_out, sample_format, sample_scale, device)
+        grshim.basic_block.__init__(self, name="arb_resampler", in_sig=self._s.in_sig, out_sig=[np.complex64])
+        self.num, self.den = self._s.num, self._s.den
+        self.consumed = 0
+        self.tail = np.zeros(0, np.complex64)
+
+    def forecast(self, noutput_items, ninputs):
+        return [self._s.room(noutput_items) or 1]
+
+    def general_work(self, input_items, output_items):
+        s, out = self._s, output_items[0]
+        raw, n = s.items(input_items[0])
+        n = min(n, s.room(len(out)))
+        self.consumed = n
+        if hasattr(self, "consume"):                 # gr.basic_block's; the shim's caller reads `consumed`
+            self.consume(0, n)
+        if n == 0:
+            return 0
+        ptr, got = s.run(raw[:n * s.bps], n)
+        if got:
+            y = np.empty(got, np.complex64)
+            s.rx._check(capi.lib().wifirx_memcpy_d2h(s.rx._h, y.ctypes.data, ptr, 8 * got))     # ordered behind the kernel
+            out[:got] = y
+        return got
+
+    work = general_work
+
+    def stop(self):
+        """End of stream: push the flush zeros; the outputs they complete are in ``tail``"""
+        s = self._s
+        if s.rx is None or s.j0 == 0:
+            return True
+        n = s.flush_inputs()
+        ptr, got = s.run(s.zeros(n), n)
+        self.tail = np.zeros(0, np.complex64)
+        if got:
+            self.tail = np.empty(got, np.complex64)
+            s.rx._check(capi.lib().wifirx_memcpy_d2h(s.rx._h, self.tail.ctypes.data, ptr, 8 * got))
+        return True
+
+    def close(self):
+        """Release the device buffers and the handle."""
+        self._s.close()
+
+
+class _forward_rx(wifi_phy_rx):
+    """The receive chain of ``wifi_phy_rx_resampled``: a ``wifi_phy_rx`` whose PDUs leave on the owner's ports, unchanged."""
+
+    def __init__(self, owner, **kw):
+        self._owner = owner
+        wifi_phy_rx.__init__(self, **kw)
+
+    def message_port_pub(self, port, msg):
+        self._owner.message_port_pub(port, msg)
+
+
+class wifi_phy_rx_resampled(grshim.sync_block):
+    """``wifi_phy_rx`` for a capture that does not run at the channel rate: ``samp_in`` at ``sample_rate`` Hz (25, 30.72, 40,
+    50, 61.44, 80 MS/s ...; ``sample_format`` / ``sample_scale`` as ``wifi_phy_rx``), brought to ``bandwidth`` on the device
+    by wifirx_arb_resample (NUMERICS.md rule 34) and received there by one ``wifi_phy_rx`` chain, which takes every other
+    keyword.  ``mac_out`` and ``carrier`` carry what ``wifi_phy_rx`` publishes, unchanged: the PDUs of a ``wifi_phy_rx`` fed
+    the resampled stream.
+
+    ``work()`` uploads its items, runs one wifirx_arb_resample on the block's own handle (the history stays on the device,
+    in two buffers used in turn), WAITS for that handle (the chain's handle reads the output on its own stream:
+    include/wifirx.h, wifirx_push, DEVICE INPUT) and pushes the output to the chain as device input.  ``stop()`` pushes the
+    ceil(16 S / den) zeros that bring out the stream's last instants, then settles the chain."""
+
+    def __init__(self, sample_rate, bandwidth=20e6, sample_format="fc32", sample_scale=None, device=0, **rx_kwargs):
+        self._s = None
+        self._s = _arb_stream(sample_rate, bandwidth, sample_format, sample_scale, device)
+        grshim.sync_block.__init__(self, name="wifi_phy_rx_resampled", in_sig=self._s.in_sig, out_sig=None)
+        self.sample_rate, self.bandwidth = float(sample_rate), float(bandwidth)
+        self.num, self.den = self._s.num, self._s.den
+        self.message_port_register_out(grshim.intern("mac_out"))
+        self.message_port_register_out(grshim.intern("carrier"))
+        self._rx = None
+        try:
+            self._rx = _forward_rx(self, bandwidth=self.bandwidth, device=device, **rx_kwargs)
+        except Exception:
+            self.close()
+            raise
+        self._push = capi.lib().wifirx_push
+        self.raise_on_error = True
+
+    def _feed(self, raw, n):
+        s, rx = self._s, self._rx
+        ptr, got = s.run(raw, n)
+        if not got:
+            return
+        s.rx.sync()                                                 # the output is read on the chain's own stream
+        rc = self._push(rx._h, ptr, got, 1)
+        if rc:
+            rx.push_errors += 1
+            rx.last_error = capi.lib().wifirx_last_error(rx._h).decode()
+            if self.raise_on_error:
+                rx._rx._check(rc)
+        if rx._queued(rx._h):
+            rx._publish()
+
+    def work(self, input_items, output_items):
+        raw, n = self._s.items(input_items[0])
+        if n:
+            self._feed(raw, n)
+        return n
+
+    def stop(self):
+        """End of stream: the flush zeros, then the chain's pending frames."""
+        if self._s.j0:
+            n = self._s.flush_inputs()
+            self._feed(self._s.zeros(n), n)
+        self._rx.stop()
+        return True
+
+    @property
+    def frames_ok(self):
+        return self._rx.frames_ok
+
+    @property
+    def frames_dropped(self):
+        return self._rx.frames_dropped
+
+    def stats(self):
+        return self._rx.stats()
+
+    def close(self):
+        """Release the device buffers and both handles."""
+        if getattr(self, "_s", None) is not None:
+            self._s.close()
+        if getattr(self, "_rx", None) is not None:
+            self._rx.close()
+            self._rx = None
+
+
 class wifi_phy_tx(grshim.sync_block):
     """Drop-in for the TX half of ``wifi_phy_hier`` (mapper, SIGNAL, chunks->symbols, carrier allocator, IFFT, cyclic
     prefixer; gnu_radio/wifi_phy_hier.grc:279-479,570-586), optionally with ``foo.packet_pad2``'s zeros folded in

@@ -54,6 +54,7 @@ EXPORTS = [
     "wifirx_irs_optimize_weighted",
     "wifirx_frontend", "wifirx_frontend_estimate", "wifirx_rx_impair", "wifirx_stream_frontend", "wifirx_stream_frontend_state",
     "wifirx_precombine",
+    "wifirx_arb_resample", "wifirx_arb_hist", "wifirx_arb_count", "wifirx_arb_table",
 ]
 FE_DC, FE_IQ = 1, 2                 # WIFIRX_FE_*: stages of the receive front end (NUMERICS.md rule 32)
 FE_BLOCK, FE_RING = 4096, 64        # WIFIRX_FE_BLOCK, WIFIRX_FE_RING
@@ -70,6 +71,8 @@ PRE_STATS_DTYPE = np.dtype([("lambda", "<f4"), ("trace", "<f4"), ("ref", "<u4"),
 assert PRE_STATS_DTYPE.itemsize == 16
 CHANNELIZER_CHANNELS = (2, 4, 8)    # wifirx_channelize: n_channels (NUMERICS.md rule 21)
 CHANNELIZER_HIST = 23               # input blocks of n_channels samples that a call takes from before its input
+ARB_HIST_MAX = 128                  # WIFIRX_ARB_HIST_MAX: the most samples wifirx_arb_resample takes from before its input
+ARB_MAX_DEN, ARB_MAX_NUM, ARB_MAX_RATIO = 512, 2048, 4      # the limits of a reduced ratio (NUMERICS.md rule 34)
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
 
@@ -140,6 +143,57 @@ def channelizer_table(n_channels) -> np.ndarray:
     if rc != OK:
         raise WifiRxError(rc, "wifirx_channelizer_table: n_channels must be 2, 4 or 8")
     return np.ctypeslib.as_array(p, shape=(n.value,)).copy()
+
+
+def arb_table() -> np.ndarray:
+    """wifirx_arb_table: the rule-34 prototype as float32 [4097], 128 entries per unit (a copy; no handle, no device)"""
+    p, n, per = C.POINTER(C.c_float)(), C.c_uint32(), C.c_uint32()
+    rc = _lib.wifirx_arb_table(C.byref(p), C.byref(n), C.byref(per))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_arb_table")
+    return np.ctypeslib.as_array(p, shape=(n.value,)).copy()
+
+
+def arb_ratio(rate_in, rate_out):
+    """(num, den) of wifirx_arb_resample for a stream at rate_in Hz brought to rate_out Hz: the rounded Hz values in lowest
+    terms.  ValueError outside 1 <= den <= 512, 1 <= num <= 2048, 1/4 <= num / den <= 4."""
+    from fractions import Fraction
+    a, b = int(round(float(rate_in))), int(round(float(rate_out)))
+    if a <= 0 or b <= 0:
+        raise ValueError("sample rates must be positive")
+    f = Fraction(a, b)
+    num, den = f.numerator, f.denominator
+    if den > ARB_MAX_DEN or num > ARB_MAX_NUM or num > ARB_MAX_RATIO * den or den > ARB_MAX_RATIO * num:
+        raise ValueError("%g Hz -> %g Hz is the ratio %d/%d: outside den <= %d, num <= %d, 1/%d <= num/den <= %d"
+                         % (rate_in, rate_out, num, den, ARB_MAX_DEN, ARB_MAX_NUM, ARB_MAX_RATIO, ARB_MAX_RATIO))
+    return num, den
+
+
+def arb_hist(num, den) -> int:
+    """wifirx_arb_hist: HL = ceil(32 max(num, den) / den) of the reduced ratio (no handle, no device)"""
+    n = C.c_uint32()
+    rc = _lib.wifirx_arb_hist(int(num), int(den), C.byref(n))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_arb_hist: ratio outside the limits")
+    return int(n.value)
+
+
+def arb_count(num, den, j0, n_in, m0) -> int:
+    """wifirx_arb_count: the outputs a wifirx_arb_resample call makes (host integers only; no handle, no device)"""
+    n = C.c_uint64()
+    rc = _lib.wifirx_arb_count(int(num), int(den), int(j0), int(n_in), int(m0), C.byref(n))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_arb_count: ratio outside the limits" if rc == EINVAL else "wifirx_arb_count: index out of range")
+    return int(n.value)
+
+
+def arb_flush_inputs(num, den, n_in, n_out) -> int:
+    """the fewest zeros behind the n_in inputs of a stream with which it yields n_out outputs (the end-of-stream flush)"""
+    from math import gcd
+    g = gcd(int(num), int(den))
+    num, den = int(num) // g, int(den) // g
+    S = max(num, den)
+    return max(0, ((int(n_out) - 1) * num + 16 * S) // den + 1 - int(n_in)) if n_out > 0 else 0       # m_end(E) >= n_out
 
 
 def channel_centre(k, n_channels, stacking) -> float:
@@ -306,6 +360,11 @@ _lib.wifirx_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C
 _lib.wifirx_channelizer_table.argtypes = [C.c_uint32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
 _lib.wifirx_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_uint32,
                                 C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+_lib.wifirx_arb_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+_lib.wifirx_arb_hist.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+_lib.wifirx_arb_count.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+_lib.wifirx_arb_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _lib.wifirx_diversity_combine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.c_uint32, C.c_int, C.POINTER(C.c_float),
                                           C.POINTER(Out), C.c_void_p]
 _lib.wifirx_precombine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -1379,6 +1438,47 @@ class WifiRx:
             d_in.upload(u)
             self.combine_dev(d_in.ptr, n, n, M, stacking, d_out.ptr, gains)
             return d_out.download(np.complex64, n * M)       # ordered behind the kernel on the handle's stream
+        finally:
+            d_in.free()
+            d_out.free()
+
+    # -- receive resampler (wifirx_arb_resample; NUMERICS.md rule 34) --
+    def arb_resample_dev(self, in_ptr, fmt, n_in, num, den, out_ptr, out_cap, hist_ptr=None, hist_out_ptr=None, j0=0, m0=0,
+                         scale=None) -> int:
+        """wifirx_arb_resample on device pointers: n_in samples of `fmt` at in_ptr, in[0] being stream sample j0 -> the
+        outputs m0 .. as complex64 at out_ptr (room for out_cap).  hist_ptr: the arb_hist(num, den) samples in front (None:
+        zeros); hist_out_ptr: where the next call's hist goes (None: nowhere).  Returns n_out.  Asynchronous on the handle's
+        stream: sync() before another handle reads the output."""
+        fmt = iq_format(fmt)
+        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
+        n = C.c_uint64(0)
+        self._check(_lib.wifirx_arb_resample(self._h, in_ptr, fmt, float(scale), int(n_in), hist_ptr, hist_out_ptr, int(num),
+                                             int(den), int(j0), int(m0), out_ptr, int(out_cap), C.byref(n)))
+        return int(n.value)
+
+    def arb_resample(self, x, num, den, fmt=None, scale=None, n_out=None) -> np.ndarray:
+        """arb_resample_dev on host arrays, a whole stream from j0 = m0 = 0: complex64 samples (fmt None or "fc32") or int16 /
+        int8 samples ([n, 2] or flat [2 n]) -> complex64.  n_out: append the zeros of the end-of-stream flush and return
+        exactly that many outputs (None: what the samples alone give)."""
+        x = np.asarray(x)
+        if fmt is None and x.dtype not in (np.dtype(np.int16), np.dtype(np.int8)):
+            fmt = IQ_FC32
+        if fmt is not None and iq_format(fmt) == IQ_FC32:
+            x, fmt = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1), IQ_FC32
+            n = x.size
+        else:
+            x, fmt, n = self._iq_array(x, fmt)
+        if n_out is not None:
+            pad = arb_flush_inputs(num, den, n, n_out)
+            x = np.concatenate([x, np.zeros(pad * (1 if fmt == IQ_FC32 else 2), x.dtype)])
+            n += pad
+        made = arb_count(num, den, 0, n, 0)
+        d_in, d_out = self.alloc(max(x.nbytes, 1)), self.alloc(max(made, 1) * 8)
+        try:
+            d_in.upload(x)
+            got = self.arb_resample_dev(d_in.ptr, fmt, n, num, den, d_out.ptr, made, scale=scale)
+            y = d_out.download(np.complex64, got)            # ordered behind the kernel on the handle's stream
+            return y if n_out is None else y[:n_out]
         finally:
             d_in.free()
             d_out.free()

@@ -921,6 +921,58 @@ int  wifirx_channelizer_table(uint32_t n_channels, const float** taps, uint32_t*
 int  wifirx_combine(wifirx_handle* h, const float* in, uint64_t in_stride, const float* gains, const float* hist,
                     float* hist_out, uint32_t n_channels, int stacking, uint64_t n_in, uint64_t m0, float* out);
 
+/* Receive resampler (NUMERICS.md rule 34): one stream sampled at fs_in into one sampled at fs_out = fs_in * den / num, on the
+ * device -- a capture at 25, 30.72, 40, 61.44 or 100 MS/s into the 20 MS/s that wifirx_push takes, a 61.44 MS/s capture into
+ * the 80 MS/s of wifirx_channelize, or a transmit stream into a converter's rate (GNU Radio's rational_resampler /
+ * pfb_arb_resampler_ccf in front of wifi_phy_hier).  num / den = fs_in / fs_out is the step in input samples per output
+ * sample; the call divides both by their gcd first (10/8 and 5/4 give the same bytes), and the reduced ratio must satisfy
+ * 1 <= den <= 512, 1 <= num <= 2048, num <= 4 den and den <= 4 num.  With S = max(num, den), h the prototype of
+ * wifirx_arb_table (a Kaiser-windowed sinc of cutoff 1/2 in units of the slower rate, 32 units long), m the stream's output
+ * index and j its input index:  y[m] = g sum_j h((m num - j den) / S) x[j],  g = den / S for num > den and 1 otherwise.
+ * There is no delay: output m is the input at time m num / den, and it reads the inputs jlo(m) = floor((m num - 16 S) / den) + 1
+ * .. jhi(m) = floor((m num + 16 S) / den); x[j] = 0 for j < 0.  With the inputs [0, E) present the outputs m < m_end(E) =
+ * max(0, ceil((E den - 16 S) / num)) can be made, so the last ceil(16 S / den) input instants of a stream appear only after
+ * that many more samples: a caller ends a stream by pushing zeros.
+ *   in          DEVICE, n_in samples of `fmt` (WIFIRX_IQ_FC32 / SC16 / SC8) at the format's natural alignment (8 / 4 / 2
+ *               bytes); in[0] is stream sample j0.  Integer samples are widened by rule 20 with `scale` inside the kernel;
+ *               for FC32 scale is not looked at.
+ *   hist        DEVICE, the HL = wifirx_arb_hist(num, den) samples in front of in[0], same format; NULL = zeros (the start of
+ *               a stream).
+ *   hist_out    DEVICE, may be NULL: receives the last HL samples of (hist || in), in the input format, by copies queued
+ *               behind the kernel.  A caller that passes on j0 + n_in, m0 + *n_out and hist_out gets a stream that is
+ *               byte-identical to the uncut one, wherever it is cut.  It must not overlap hist, in or out: a caller
+ *               alternates between two buffers.
+ *   j0, m0      the stream indices of in[0] and of the call's first output.
+ *   out         DEVICE, 8-byte aligned, room for out_cap float pairs; the outputs m0 .. m_end(j0 + n_in) - 1 are written and
+ *               nothing else.  It is what wifirx_push(iq_on_device = 1) takes.
+ *   n_out       HOST, required: the number of outputs, the value wifirx_arb_count gives; filled before anything is queued.
+ * Checked on the host before anything is queued: WIFIRX_EINVAL for NULL in with n_in > 0, NULL out with outputs to make, NULL
+ * n_out, an unknown fmt, a scale that is not finite or <= 0 (integer formats), num or den of 0 or a reduced ratio outside
+ * the limits, misaligned buffers, any overlap among in, hist, hist_out and out, and a history that does not reach
+ * (jlo(m0) < j0 - HL with outputs to make); WIFIRX_ERANGE for n_out > out_cap, (j0 + n_in) * den >= 2^62 or
+ * (m0 + n_out) * num >= 2^62.  A refused call writes nothing, *n_out included.  n_in = 0 returns WIFIRX_OK, makes no output
+ * and still produces hist_out (= hist, or zeros) when asked.  One kernel launch per call, and at most two copies for hist_out.
+ * ORDER: as wifirx_iq_to_f32 -- asynchronous on the handle's stream, behind the handle's earlier calls; every buffer must stay
+ * valid until the work has run.  The output is usually consumed by ANOTHER handle on its own stream: see wifirx_push,
+ * DEVICE INPUT -- wifirx_sync() on this handle (or an event on wifirx_stream()) comes between this call and its push. */
+#define WIFIRX_ARB_HIST_MAX 128
+int  wifirx_arb_resample(wifirx_handle* h, const void* in, int fmt, float scale, uint64_t n_in, const void* hist,
+                         void* hist_out, uint32_t num, uint32_t den, uint64_t j0, uint64_t m0, float* out, uint64_t out_cap,
+                         uint64_t* n_out);
+
+/* HL = ceil(32 S / den) <= WIFIRX_ARB_HIST_MAX of the reduced ratio: the samples wifirx_arb_resample takes as hist and hands
+ * on as hist_out.  Needs no handle and no device.  WIFIRX_EINVAL for a ratio outside the limits or a NULL hist_len. */
+int  wifirx_arb_hist(uint32_t num, uint32_t den, uint32_t* hist_len);
+
+/* The outputs of a wifirx_arb_resample call with the same arguments: *n_out = max(0, m_end(j0 + n_in) - m0), host integers
+ * only.  WIFIRX_EINVAL for a ratio outside the limits or a NULL n_out, WIFIRX_ERANGE as wifirx_arb_resample. */
+int  wifirx_arb_count(uint32_t num, uint32_t den, uint64_t j0, uint64_t n_in, uint64_t m0, uint64_t* n_out);
+
+/* The resampler's prototype (NUMERICS.md rule 34; tools/gen_arb_table.py): *table = the *n_entries = 4097 float32 values
+ * h(-16 + q / 128), *per_unit = 128 entries per unit of the slower rate.  Host memory owned by the library.  Needs no handle
+ * and no device.  WIFIRX_EINVAL for a NULL argument. */
+int  wifirx_arb_table(const float** table, uint32_t* n_entries, uint32_t* per_unit);
+
 /* Receive diversity (NUMERICS.md rule 23): combine the equalised points of n_ant antennas' demodulated batches into one batch
  * to decode.  Slot i of every in[a] is the same transmission, demodulated from antenna a's samples by wifirx_demod_batch with
  * `carrier` and `csi` outputs (by this handle one after the other, or by other handles with the same max_sym).  Per slot: the
