@@ -10,6 +10,7 @@ int16 / int8 pairs: a UHD sc16 recording, or what hackrf_transfer writes; the sc
     python examples/make_iq_file.py kodim01 out.sc8 --format sc8 --backoff-db 12
     python examples/make_iq_file.py kodim01 wide.sc16 --format sc16 --channels 4 [--stacking 1]
     python examples/make_iq_file.py kodim01 cap25.sc16 --format sc16 --sample-rate 25e6
+    python examples/make_iq_file.py kodim01 band.sc16 --format sc16 --sample-rate 80e6 --offsets=-25e6,0,25e6
 
 --channels M (2, 4 or 8): a wideband capture at M times the channel rate for examples/wideband_file_rx.py.  The frames are
 dealt round-robin to M streams (frame k goes to channel k mod M), every stream is up-sampled by M with a float64 FFT, shifted
@@ -21,6 +22,11 @@ variance per channel bandwidth, so --snr means per channel what it means without
 rule 34, on the device (wifirx_arb_resample) when the library finds one and by the rule's NumPy restatement
 (tests/arb_ref.py) otherwise: the two give the same bytes.  The noise is added at the capture rate with unit variance per
 20 MHz, so --snr keeps its meaning.
+
+--offsets F0,F1,.. (with --sample-rate R): up to 8 channels centred F0, F1, .. Hz above the capture's centre, for
+examples/tuned_file_rx.py -- channels 1 / 6 / 11 of the 2.4 GHz band around 2437 MHz are --sample-rate 80e6
+--offsets=-25e6,0,25e6.  The frames are dealt round-robin to the channels, every stream is up-sampled to R as above, mixed to
+its offset in float64 and the streams are summed; |offset| + 10 MHz must stay inside R / 2.
 """
 import argparse
 import os
@@ -76,9 +82,16 @@ def main():
                     "channel width, 0 = at whole multiples")
     ap.add_argument("--sample-rate", type=float, default=None, help="one channel: the capture's rate in samples per second "
                     "(default: the channel's 20e6)")
+    ap.add_argument("--offsets", default=None, help="with --sample-rate: comma-separated centres of up to 8 channels in Hz above "
+                    "the capture's centre; the frames are dealt round-robin to them")
     a = ap.parse_args()
     if a.sample_rate is not None and a.channels != 1:
         ap.error("--sample-rate is for one channel")
+    offsets = [float(v) for v in a.offsets.split(",")] if a.offsets else []
+    if offsets and (a.sample_rate is None or a.channels != 1):
+        ap.error("--offsets needs --sample-rate and no --channels")
+    if len(offsets) > capi.TUNE_MAX_CHANNELS or any(abs(f) + 10e6 > (a.sample_rate or 0) / 2 for f in offsets):
+        ap.error("--offsets: at most 8 channels, each with |offset| + 10 MHz inside half the sample rate")
     gold = os.path.join(ROOT, "tests", "golden", "kodim_300.npz")
     if os.path.exists(a.image):
         from PIL import Image
@@ -109,7 +122,15 @@ def main():
         n = max(len(v) for v in streams)
         x = txgen.synthesise_wideband([np.concatenate([v, np.zeros(n - len(v), np.complex64)]) for v in streams], M, a.stacking)
     over = 1.0                                                # the capture's rate over the channel's
-    if a.sample_rate is not None and a.sample_rate != 20e6:
+    if offsets:
+        streams = [np.concatenate(padded[k::len(offsets)] or [np.zeros(0, np.complex64)]) for k in range(len(offsets))]
+        n = max(len(v) for v in streams)
+        x = 0.0
+        for v, f in zip(streams, offsets):
+            up = upsample(np.concatenate([v, np.zeros(n - len(v), np.complex64)]).astype(np.complex64), a.sample_rate)
+            x = x + up.astype(np.complex128) * np.exp(2j * np.pi * np.mod(f / a.sample_rate * np.arange(len(up)), 1.0))
+        over = a.sample_rate / 20e6
+    elif a.sample_rate is not None and a.sample_rate != 20e6:
         x = upsample(np.asarray(x, dtype=np.complex64), a.sample_rate)
         over = a.sample_rate / 20e6
     x = (x + (rng.standard_normal(x.size) + 1j * rng.standard_normal(x.size)) * np.sqrt(0.5 * M * over)).astype(np.complex64)

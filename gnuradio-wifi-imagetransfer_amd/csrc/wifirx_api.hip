@@ -647,6 +647,7 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_convert.inc"
 #include "wifirx_api_bank.inc"
 #include "wifirx_api_arb.inc"
+#include "wifirx_api_tune.inc"
 #include "wifirx_api_diversity.inc"
 #include "wifirx_api_precombine.inc"
 #include "wifirx_api_stream_div.inc"

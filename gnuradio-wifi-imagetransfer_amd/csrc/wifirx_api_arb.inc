@@ -17,6 +17,75 @@ bool arb_count(const wr_arb_ratio& r, uint64_t j0, uint64_t n_in, uint64_t m0, u
     return ((unsigned __int128)m0 + *n_out) * r.num < ARB_INDEX_LIMIT;
 }
 
+// What wifirx_arb_resample and wifirx_tune share.  A call's checked arguments:
+struct arb_call {
+    wr_arb_ratio r;
+    uint32_t bps;                    // bytes per input sample
+    uint64_t n;                      // outputs (per channel)
+    uint64_t in_bytes, hist_bytes;
+};
+
+// every check that needs no output buffer: the arguments, the ratio, the alignment, the counting; `room` float pairs per row
+int arb_check_call(wifirx_handle* h, const void* in, int fmt, float scale, uint64_t n_in, const void* hist, const void* hist_out,
+                   uint32_t num, uint32_t den, uint64_t j0, uint64_t m0, const float* out, uint64_t room, const uint64_t* n_out,
+                   arb_call* c)
+{
+    if (!n_out) return fail(h, WIFIRX_EINVAL, "n_out is required");
+    if (n_in && !in) return fail(h, WIFIRX_EINVAL, "in is required");
+    c->bps = fmt == WIFIRX_IQ_FC32 ? 8u : wr_iq_sample_bytes(fmt);
+    if (!c->bps) return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_FC32, WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");
+    if (fmt != WIFIRX_IQ_FC32 && (!std::isfinite(scale) || !(scale > 0))) return fail(h, WIFIRX_EINVAL, "scale must be finite and > 0");
+    if (!wr_arb_plan(num, den, &c->r))
+        return fail(h, WIFIRX_EINVAL, "num / den must reduce to 1 <= den <= 512, 1 <= num <= 2048, num <= 4 den, den <= 4 num");
+    const uintptr_t align = c->bps - 1;
+    if ((reinterpret_cast<uintptr_t>(in) & align) || (reinterpret_cast<uintptr_t>(hist) & align) ||
+        (reinterpret_cast<uintptr_t>(hist_out) & align) || (reinterpret_cast<uintptr_t>(out) & 7))
+        return fail(h, WIFIRX_EINVAL, "misaligned buffer (out: 8 bytes; in, hist, hist_out: fc32 8, sc16 4, sc8 2)");
+    c->n = 0;
+    if (!arb_count(c->r, j0, n_in, m0, &c->n))
+        return fail(h, WIFIRX_ERANGE, "(j0 + n_in) den and (m0 + n_out) num must stay below 2^62");
+    if (c->n && !out) return fail(h, WIFIRX_EINVAL, "out is required");
+    if (c->n > room) return fail(h, WIFIRX_ERANGE, "out_cap (out_stride) is smaller than n_out (wifirx_arb_count)");
+    if ((c->n + WR_ARB_TILE - 1) / WR_ARB_TILE > 0x7fffffffull) return fail(h, WIFIRX_ERANGE, "too many outputs for one call");
+    c->in_bytes = n_in * c->bps;
+    c->hist_bytes = (uint64_t)c->r.HL * c->bps;
+    return WIFIRX_OK;
+}
+
+// no overlap among in, hist, hist_out and the out_bytes of out; the history reaches the call's first output
+int arb_check_buffers(wifirx_handle* h, const arb_call& c, const void* in, const void* hist, const void* hist_out, const float* out,
+                      uint64_t out_bytes, uint64_t j0, uint64_t m0)
+{
+    const wr_arb_ratio& r = c.r;
+    const struct { const void* p; uint64_t bytes; } buf[4] = {
+        { in, c.in_bytes }, { out, out_bytes }, { hist, hist ? c.hist_bytes : 0 }, { hist_out, hist_out ? c.hist_bytes : 0 } };
+    for (int a = 0; a < 4; a++)
+        for (int b = a + 1; b < 4; b++)
+            if (ranges_overlap(buf[a].p, buf[a].bytes, buf[b].p, buf[b].bytes))
+                return fail(h, WIFIRX_EINVAL, "in, hist, hist_out and out must not overlap");
+    if (c.n) {
+        // jlo(m0) = floor((m0 num - 16 S) / den) + 1 must not lie in front of the history
+        const int64_t D = (int64_t)(m0 * r.num) - 16 * (int64_t)r.S;
+        int64_t fl = D / (int64_t)r.den;
+        if (D - fl * (int64_t)r.den < 0) fl -= 1;
+        if (fl + 1 < (int64_t)j0 - (int64_t)r.HL)
+            return fail(h, WIFIRX_EINVAL, "the history does not reach output m0: its first input lies in front of j0 - hist_len");
+    }
+    return WIFIRX_OK;
+}
+
+// hist_out = the last HL samples of (hist || in), queued behind the kernel: `keep` bytes of hist's tail, then in's tail
+int arb_queue_hist(wifirx_handle* h, const arb_call& c, const void* in, const void* hist, void* hist_out)
+{
+    uint8_t* dst = static_cast<uint8_t*>(hist_out);
+    const uint64_t from_in = std::min(c.in_bytes, c.hist_bytes), keep = c.hist_bytes - from_in;
+    if (keep && hist) HIP_TRY(h, hipMemcpyAsync(dst, static_cast<const uint8_t*>(hist) + from_in, keep, hipMemcpyDeviceToDevice, h->stream));
+    else if (keep) HIP_TRY(h, hipMemsetAsync(dst, 0, keep, h->stream));
+    if (from_in)
+        HIP_TRY(h, hipMemcpyAsync(dst + keep, static_cast<const uint8_t*>(in) + (c.in_bytes - from_in), from_in, hipMemcpyDeviceToDevice, h->stream));
+    return WIFIRX_OK;
+}
+
 }  // namespace
 
 extern "C" int wifirx_arb_hist(uint32_t num, uint32_t den, uint32_t* hist_len)
@@ -48,53 +117,14 @@ extern "C" int wifirx_arb_resample(wifirx_handle* h, const void* in, int fmt, fl
                                    uint64_t out_cap, uint64_t* n_out)
 {
     if (!h) return WIFIRX_EINVAL;
-    if (!n_out) return fail(h, WIFIRX_EINVAL, "n_out is required");
-    if (n_in && !in) return fail(h, WIFIRX_EINVAL, "in is required");
-    const uint32_t bps = fmt == WIFIRX_IQ_FC32 ? 8u : wr_iq_sample_bytes(fmt);
-    if (!bps) return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_FC32, WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");
-    if (fmt != WIFIRX_IQ_FC32 && (!std::isfinite(scale) || !(scale > 0))) return fail(h, WIFIRX_EINVAL, "scale must be finite and > 0");
-    wr_arb_ratio r;
-    if (!wr_arb_plan(num, den, &r))
-        return fail(h, WIFIRX_EINVAL, "num / den must reduce to 1 <= den <= 512, 1 <= num <= 2048, num <= 4 den, den <= 4 num");
-    const uintptr_t align = bps - 1;
-    if ((reinterpret_cast<uintptr_t>(in) & align) || (reinterpret_cast<uintptr_t>(hist) & align) ||
-        (reinterpret_cast<uintptr_t>(hist_out) & align) || (reinterpret_cast<uintptr_t>(out) & 7))
-        return fail(h, WIFIRX_EINVAL, "misaligned buffer (out: 8 bytes; in, hist, hist_out: fc32 8, sc16 4, sc8 2)");
-    uint64_t n = 0;
-    if (!arb_count(r, j0, n_in, m0, &n))
-        return fail(h, WIFIRX_ERANGE, "(j0 + n_in) den and (m0 + n_out) num must stay below 2^62");
-    if (n && !out) return fail(h, WIFIRX_EINVAL, "out is required");
-    if (n > out_cap) return fail(h, WIFIRX_ERANGE, "out_cap is smaller than n_out (wifirx_arb_count)");
-    if ((n + WR_ARB_TILE - 1) / WR_ARB_TILE > 0x7fffffffull) return fail(h, WIFIRX_ERANGE, "too many outputs for one call");
-    const uint64_t in_bytes = n_in * bps, hist_bytes = (uint64_t)r.HL * bps;
-    const struct { const void* p; uint64_t bytes; } buf[4] = {
-        { in, in_bytes }, { out, n * 8 }, { hist, hist ? hist_bytes : 0 }, { hist_out, hist_out ? hist_bytes : 0 } };
-    for (int a = 0; a < 4; a++)
-        for (int b = a + 1; b < 4; b++)
-            if (ranges_overlap(buf[a].p, buf[a].bytes, buf[b].p, buf[b].bytes))
-                return fail(h, WIFIRX_EINVAL, "in, hist, hist_out and out must not overlap");
-    if (n) {
-        // jlo(m0) = floor((m0 num - 16 S) / den) + 1 must not lie in front of the history
-        const int64_t D = (int64_t)(m0 * r.num) - 16 * (int64_t)r.S;
-        int64_t fl = D / (int64_t)r.den;
-        if (D - fl * (int64_t)r.den < 0) fl -= 1;
-        if (fl + 1 < (int64_t)j0 - (int64_t)r.HL)
-            return fail(h, WIFIRX_EINVAL, "the history does not reach output m0: its first input lies in front of j0 - hist_len");
-    }
-    *n_out = n;
-    if (n == 0 && !hist_out) return WIFIRX_OK;
+    arb_call c;
+    if (int rc = arb_check_call(h, in, fmt, scale, n_in, hist, hist_out, num, den, j0, m0, out, out_cap, n_out, &c)) return rc;
+    if (int rc = arb_check_buffers(h, c, in, hist, hist_out, out, c.n * 8, j0, m0)) return rc;
+    *n_out = c.n;
+    if (c.n == 0 && !hist_out) return WIFIRX_OK;
     stream_worker_wait_idle(h);
     HIP_TRY(h, hipSetDevice(h->device));
-    if (n)
-        HIP_TRY(h, wr_launch_arb(h->stream, in, fmt, scale, n_in, hist, &r, j0, m0, n, reinterpret_cast<float2*>(out)));
-    if (hist_out) {
-        // the last HL samples of (hist || in), queued behind the kernel: `keep` bytes of hist's tail, then in's tail
-        uint8_t* dst = static_cast<uint8_t*>(hist_out);
-        const uint64_t from_in = std::min(in_bytes, hist_bytes), keep = hist_bytes - from_in;
-        if (keep && hist) HIP_TRY(h, hipMemcpyAsync(dst, static_cast<const uint8_t*>(hist) + from_in, keep, hipMemcpyDeviceToDevice, h->stream));
-        else if (keep) HIP_TRY(h, hipMemsetAsync(dst, 0, keep, h->stream));
-        if (from_in)
-            HIP_TRY(h, hipMemcpyAsync(dst + keep, static_cast<const uint8_t*>(in) + (in_bytes - from_in), from_in, hipMemcpyDeviceToDevice, h->stream));
-    }
-    return WIFIRX_OK;
+    if (c.n)
+        HIP_TRY(h, wr_launch_arb(h->stream, in, fmt, scale, n_in, hist, &c.r, j0, m0, c.n, reinterpret_cast<float2*>(out)));
+    return hist_out ? arb_queue_hist(h, c, in, hist, hist_out) : WIFIRX_OK;
 }

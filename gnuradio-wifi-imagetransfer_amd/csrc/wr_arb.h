@@ -21,6 +21,13 @@ struct wr_arb_ratio {
     float gain;                 // (float)den / (float)S; applied when num > den
 };
 
+// The channels of a tuner call (NUMERICS.md rule 35), a kernel argument by value: nothing is uploaded for a call.
+struct wr_tune_channels {
+    uint64_t inc[WIFIRX_TUNE_MAX_CHANNELS];       // phase increment per input sample, 2^-64 turns
+    uint64_t phase0[WIFIRX_TUNE_MAX_CHANNELS];    // phase of stream sample 0
+    uint64_t out_stride;                          // float pairs from one channel's row of out to the next
+};
+
 extern "C" {
 // num / den reduced and checked against rule 34's limits; false outside them (or for a zero)
 bool wr_arb_plan(uint32_t num, uint32_t den, wr_arb_ratio* r);
@@ -31,6 +38,11 @@ uint64_t wr_arb_m_end(const wr_arb_ratio* r, uint64_t E);
 // The caller has checked that every input an output reads lies in [j0 - HL, j0 + n_in) and that (m0 + n_out) num < 2^62.
 hipError_t wr_launch_arb(hipStream_t st, const void* in, int fmt, float scale, uint64_t n_in, const void* hist,
                          const wr_arb_ratio* r, uint64_t j0, uint64_t m0, uint64_t n_out, float2* out);
+// The same for n_channels = 1 .. 8 channels in one launch, channel k mixed by c->inc[k], c->phase0[k] on the way into LDS and
+// written to out + k * c->out_stride (rule 35); the rows of out overlap nothing, each has room for n_out float pairs.
+hipError_t wr_launch_tune(hipStream_t st, const void* in, int fmt, float scale, uint64_t n_in, const void* hist,
+                          const wr_arb_ratio* r, uint64_t j0, uint64_t m0, uint64_t n_out, float2* out, uint32_t n_channels,
+                          const wr_tune_channels* c);
 // the 4097 float32 entries of the prototype (host memory, static)
 const float* wr_arb_host_table(void);
 }

@@ -7,6 +7,9 @@
 // of the stream are zeros.  The 64-bit arithmetic (m num, the floor division by den) is done once per tile; a lane works in
 // 32-bit integers relative to the tile's first input, and along its taps (q, r) fall by the constant 128 den = a S + b.
 //
+// Rule 35 (the tuner) is the same body with a rotation in the staging loop: tune_kernel runs one grid row per channel, each
+// with its own phase ramp over the stream index, so K channels at any centre come out of one capture in one launch.
+//
 // The table is kept in LDS phase-major, T[p][t] = H[128 t + p] with rows of 33 floats, p = 0 .. 128 (row 128 is row 0
 // shifted by one unit), so H[q + 1] is always T[p + 1][t].  The lanes of a decimating ratio hold q that differ by multiples
 // of 128 -- one bank in the flat layout; here they are neighbours in a row -- and lanes that differ in p are 33 words apart.
@@ -17,6 +20,7 @@
 
 #include "wr_arb.h"
 #include "wr_arb_table.h"
+#include "wr_device.h"     // sp_sincos (rule 1)
 #include "wr_iq.h"
 
 namespace wr {
@@ -28,6 +32,7 @@ static_assert(4 * WR_ARB_HALF * 2 == WIFIRX_ARB_HIST_MAX, "32 S / den <= 128 for
 
 constexpr uint32_t ARB_ROW = 2 * WR_ARB_HALF + 1;             // 33 floats: 32 units and one word of padding
 constexpr uint32_t ARB_ROWS = WR_ARB_PER_UNIT + 1;
+constexpr float ARB_PHASE_SCALE = (float)(6.283185307179586 / 4294967296.0);      // 2 pi / 2^32: radians per unit of P >> 32
 
 const float arb_host_table[WR_ARB_ENTRIES] = WR_ARB_TABLE_INIT;
 __device__ const float arb_dev_table[WR_ARB_ENTRIES] = WR_ARB_TABLE_INIT;
@@ -45,10 +50,14 @@ __device__ __forceinline__ uint32_t div_small(uint32_t n, uint32_t d, float rd, 
 
 }  // namespace
 
-template <int FMT>
-__global__ __launch_bounds__(WR_ARB_TILE)
-void arb_kernel(const void* __restrict__ in, const void* __restrict__ hist, float scale, uint64_t n_in, wr_arb_ratio R,
-                uint64_t j0, uint64_t m0, uint64_t n_out, float2* __restrict__ out)
+// The one statement of rule 34 on the device: the tile blockIdx.x of a call's outputs into out.  TUNE (rule 35): every staged
+// sample -- from in, from hist, a zero of a NULL history or of the front of the stream -- is first multiplied by
+// exp(j 2 pi P / 2^64), P = phase0 + inc * (its stream index) mod 2^64, in rule 17's arithmetic; a channel whose inc and
+// phase0 are both 0 is not rotated at all and is byte for byte the body without TUNE.
+template <int FMT, bool TUNE>
+__device__ __forceinline__ void arb_tile(const void* __restrict__ in, const void* __restrict__ hist, float scale, uint64_t n_in,
+                                         const wr_arb_ratio& R, uint64_t j0, uint64_t m0, uint64_t n_out, float2* __restrict__ out,
+                                         uint64_t inc, uint64_t phase0)
 {
     __shared__ float T[ARB_ROWS * ARB_ROW];
     __shared__ __attribute__((aligned(8))) float2 xs[WR_ARB_SPAN];
@@ -71,12 +80,20 @@ void arb_kernel(const void* __restrict__ in, const void* __restrict__ hist, floa
     const uint32_t span = (rem0 + (count - 1) * R.num + 32 * R.S) / R.den;       // inputs jbase .. jhi of the last output
     const int64_t rel = jbase - (int64_t)j0;                                     // xs[s] is in[rel + s]
     const int64_t lead = jbase < 0 ? -jbase : 0;                                 // xs[s], s < lead, lies in front of the stream
+    const bool rotate = TUNE && (inc | phase0) != 0;                             // uniform over the workgroup
+    const uint64_t Pbase = phase0 + inc * (uint64_t)jbase;                       // mod 2^64: jbase < 0 wraps
     for (uint32_t s = tid; s < span && s < WR_ARB_SPAN; s += WR_ARB_TILE) {
         const int64_t jj = rel + (int64_t)s;
         float2 x = make_float2(0.f, 0.f);
         if ((int64_t)s >= lead) {
             if (jj >= 0) { if ((uint64_t)jj < n_in) x = load_sample<FMT>(in, (uint64_t)jj, scale); }
             else if (hist && jj >= -(int64_t)R.HL) x = load_sample<FMT>(hist, (uint64_t)(jj + (int64_t)R.HL), scale);
+        }
+        if (rotate) {
+            const uint64_t P = Pbase + inc * s;
+            float sn, cs;
+            sp_sincos((float)(int32_t)(uint32_t)(P >> 32) * ARB_PHASE_SCALE, sn, cs);
+            x = make_float2(x.x * cs - x.y * sn, x.x * sn + x.y * cs);
         }
         xs[s] = x;
     }
@@ -107,6 +124,24 @@ void arb_kernel(const void* __restrict__ in, const void* __restrict__ hist, floa
     }
     if (R.num > R.den) { ar = ar * R.gain; ai = ai * R.gain; }
     out[first + tid] = make_float2(ar, ai);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(WR_ARB_TILE)
+void arb_kernel(const void* __restrict__ in, const void* __restrict__ hist, float scale, uint64_t n_in, wr_arb_ratio R,
+                uint64_t j0, uint64_t m0, uint64_t n_out, float2* __restrict__ out)
+{
+    arb_tile<FMT, false>(in, hist, scale, n_in, R, j0, m0, n_out, out, 0, 0);
+}
+
+// rule 35: blockIdx.y is the channel; its row starts at out + blockIdx.y * C.out_stride
+template <int FMT>
+__global__ __launch_bounds__(WR_ARB_TILE)
+void tune_kernel(const void* __restrict__ in, const void* __restrict__ hist, float scale, uint64_t n_in, wr_arb_ratio R,
+                 uint64_t j0, uint64_t m0, uint64_t n_out, float2* __restrict__ out, wr_tune_channels C)
+{
+    const uint32_t k = blockIdx.y;
+    arb_tile<FMT, true>(in, hist, scale, n_in, R, j0, m0, n_out, out + (uint64_t)k * C.out_stride, C.inc[k], C.phase0[k]);
 }
 
 }  // namespace wr
@@ -146,6 +181,21 @@ extern "C" hipError_t wr_launch_arb(hipStream_t st, const void* in, int fmt, flo
     if (fmt == WIFIRX_IQ_FC32) hipLaunchKernelGGL((wr::arb_kernel<WIFIRX_IQ_FC32>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out);
     else if (fmt == WIFIRX_IQ_SC16) hipLaunchKernelGGL((wr::arb_kernel<WIFIRX_IQ_SC16>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out);
     else if (fmt == WIFIRX_IQ_SC8) hipLaunchKernelGGL((wr::arb_kernel<WIFIRX_IQ_SC8>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+extern "C" hipError_t wr_launch_tune(hipStream_t st, const void* in, int fmt, float scale, uint64_t n_in, const void* hist,
+                                     const wr_arb_ratio* r, uint64_t j0, uint64_t m0, uint64_t n_out, float2* out,
+                                     uint32_t n_channels, const wr_tune_channels* c)
+{
+    if (n_out == 0) return hipSuccess;
+    const uint64_t tiles = (n_out + WR_ARB_TILE - 1) / WR_ARB_TILE;
+    if (tiles > 0x7fffffffull || n_channels < 1 || n_channels > WIFIRX_TUNE_MAX_CHANNELS) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)tiles, n_channels), block(WR_ARB_TILE);
+    if (fmt == WIFIRX_IQ_FC32) hipLaunchKernelGGL((wr::tune_kernel<WIFIRX_IQ_FC32>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out, *c);
+    else if (fmt == WIFIRX_IQ_SC16) hipLaunchKernelGGL((wr::tune_kernel<WIFIRX_IQ_SC16>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out, *c);
+    else if (fmt == WIFIRX_IQ_SC8) hipLaunchKernelGGL((wr::tune_kernel<WIFIRX_IQ_SC8>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out, *c);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -538,10 +538,12 @@ class wifi_phy_rx_wideband(grshim.sync_block):
 
 
 class _arb_stream:
-    """What ``arb_resampler`` and ``wifi_phy_rx_resampled`` share: one handle, the stream indices j0 and m0 of
-    wifirx_arb_resample (NUMERICS.md rule 34), the two history buffers used in turn, and the device buffers of a call."""
+    """What ``arb_resampler``, ``wifi_phy_rx_resampled`` and ``wifi_phy_rx_tuned`` share: one handle, the stream indices j0 and
+    m0 of wifirx_arb_resample (NUMERICS.md rule 34), the two history buffers used in turn, and the device buffers of a call.
+    With ``incs`` the call is wifirx_tune (rule 35) and the output holds one row of ``cap_out`` samples per increment."""
 
-    def __init__(self, rate_in, rate_out, sample_format, sample_scale, device):
+    def __init__(self, rate_in, rate_out, sample_format, sample_scale, device, incs=None):
+        self.incs = None if incs is None else [int(v) for v in incs]   # wifirx_tune's increments: one output row per channel
         self.fmt = capi.iq_format(sample_format)
         if self.fmt not in capi.IQ_DTYPE:
             raise ValueError("sample_format must be 'fc32', 'sc16' or 'sc8'")
@@ -577,14 +579,18 @@ class _arb_stream:
         if n_out > self.cap_out:
             if self.d_out is not None:
                 self.d_out.free()
-            self.cap_out = n_out + n_out // 2
-            self.d_out = self.rx.alloc(self.cap_out * 8)
+            self.cap_out = (n_out + n_out // 2 + 1) & ~1            # even: every row starts on 16 bytes
+            self.d_out = self.rx.alloc(self.cap_out * 8 * (1 if self.incs is None else len(self.incs)))
         rx = self.rx
         rx._check(capi.lib().wifirx_memcpy_h2d(rx._h, self.d_in.ptr, raw.ctypes.data, n * self.bps))
         nxt = 1 if self.hist_cur == 0 else 0
-        got = rx.arb_resample_dev(self.d_in.ptr, self.fmt, n, self.num, self.den, None if n_out == 0 else self.d_out.ptr,
-                                  self.cap_out, hist_ptr=None if self.hist_cur is None else self.hist[self.hist_cur].ptr,
-                                  hist_out_ptr=self.hist[nxt].ptr, j0=self.j0, m0=self.m0, scale=self.scale)
+        hist = dict(hist_ptr=None if self.hist_cur is None else self.hist[self.hist_cur].ptr, hist_out_ptr=self.hist[nxt].ptr,
+                    j0=self.j0, m0=self.m0, scale=self.scale)
+        out = None if n_out == 0 else self.d_out.ptr
+        if self.incs is None:
+            got = rx.arb_resample_dev(self.d_in.ptr, self.fmt, n, self.num, self.den, out, self.cap_out, **hist)
+        else:
+            got = rx.tune_dev(self.d_in.ptr, self.fmt, n, self.num, self.den, self.incs, out, self.cap_out, **hist)
         self.hist_cur, self.j0, self.m0 = nxt, self.j0 + n, self.m0 + got
         return (self.d_out.ptr if got else None), got
 
@@ -753,6 +759,104 @@ class wifi_phy_rx_resampled(grshim.sync_block):
         if getattr(self, "_rx", None) is not None:
             self._rx.close()
             self._rx = None
+
+
+class wifi_phy_rx_tuned(grshim.sync_block):
+    """``wifi_phy_rx`` for K <= 8 channels that lie anywhere in one capture: ``samp_in`` at ``sample_rate`` Hz around
+    ``center_frequency`` (``sample_format`` / ``sample_scale`` as ``wifi_phy_rx``), channel k centred ``offsets[k]`` Hz above
+    it -- channels 1 / 6 / 11 of the 2.4 GHz band at -25, 0 and +25 MHz of an 80 MS/s capture around 2437 MHz, which no
+    M x 20 MHz bank splits.  One wifirx_tune (NUMERICS.md rule 35) per ``work()`` mixes every channel down and brings it to
+    ``bandwidth`` on the device (GNU Radio's ``freq_xlating_fir_filter`` per channel); each row is received there by a
+    ``wifi_phy_rx`` chain of its own, which takes every other keyword.
+
+    ``mac_out`` and ``carrier`` carry what ``wifi_phy_rx`` publishes, with ``channel`` (k) added to the dictionaries;
+    ``freq`` is ``center_frequency + offsets[k]``.  Per channel the PDUs, in order, are those of a ``wifi_phy_rx`` fed that
+    channel's samples; between channels they come in the order the chains finish them.
+
+    The filter is rule 34's prototype: an offset must keep ``|offset| + bandwidth / 2`` inside ``sample_rate / 2`` (refused
+    otherwise), and channels closer than 11.7 MHz (at 20 MHz) to a tuned centre are not rejected.  ``work()`` uploads its
+    items, runs one wifirx_tune on the block's own handle (the history of raw samples stays on the device, in two buffers
+    used in turn), WAITS for that handle (the chains' handles read the rows on their own streams: include/wifirx.h,
+    wifirx_push, DEVICE INPUT) and pushes row k to chain k as device input.  ``stop()`` pushes the ceil(16 S / den) zeros
+    that bring out the stream's last instants, then settles the chains."""
+
+    def __init__(self, sample_rate, offsets=(-25e6, 0.0, 25e6), center_frequency=2.437e9, bandwidth=20e6, sample_format="fc32",
+                 sample_scale=None, device=0, **rx_kwargs):
+        self._s, self._rx = None, []
+        self.sample_rate, self.bandwidth, self.center_frequency = float(sample_rate), float(bandwidth), float(center_frequency)
+        self.offsets = [float(v) for v in offsets]
+        if not 1 <= len(self.offsets) <= capi.TUNE_MAX_CHANNELS:
+            raise ValueError("1 .. %d offsets are required" % capi.TUNE_MAX_CHANNELS)
+        for off in self.offsets:
+            if not abs(off) + self.bandwidth / 2 <= self.sample_rate / 2:
+                raise ValueError("offset %g Hz: |offset| + bandwidth / 2 = %g Hz lies outside sample_rate / 2 = %g Hz, the channel "
+                                 "would alias" % (off, abs(off) + self.bandwidth / 2, self.sample_rate / 2))
+        self.frequencies = [self.center_frequency + off for off in self.offsets]
+        self.incs = [capi.tune_inc(off, self.sample_rate) for off in self.offsets]
+        self._s = _arb_stream(self.sample_rate, self.bandwidth, sample_format, sample_scale, device, incs=self.incs)
+        grshim.sync_block.__init__(self, name="wifi_phy_rx_tuned", in_sig=self._s.in_sig, out_sig=None)
+        self.num, self.den = self._s.num, self._s.den
+        self.message_port_register_out(grshim.intern("mac_out"))
+        self.message_port_register_out(grshim.intern("carrier"))
+        try:
+            for k, f in enumerate(self.frequencies):
+                self._rx.append(_channel_rx(self, k, bandwidth=self.bandwidth, frequency=f, device=device, **rx_kwargs))
+        except Exception:
+            self.close()
+            raise
+        self._push = capi.lib().wifirx_push
+        self.raise_on_error = True
+
+    def _feed(self, raw, n):
+        s = self._s
+        ptr, got = s.run(raw, n)
+        if not got:
+            return
+        s.rx.sync()                                                 # the rows are read on the chains' own streams
+        for k, rx in enumerate(self._rx):
+            rc = self._push(rx._h, ptr + 8 * k * s.cap_out, got, 1)
+            if rc:
+                rx.push_errors += 1
+                rx.last_error = capi.lib().wifirx_last_error(rx._h).decode()
+                if self.raise_on_error:
+                    rx._rx._check(rc)
+            if rx._queued(rx._h):
+                rx._publish()
+
+    def work(self, input_items, output_items):
+        raw, n = self._s.items(input_items[0])
+        if n:
+            self._feed(raw, n)
+        return n
+
+    def stop(self):
+        """End of stream: the flush zeros, then every chain's pending frames."""
+        if self._s.j0:
+            n = self._s.flush_inputs()
+            self._feed(self._s.zeros(n), n)
+        for rx in self._rx:
+            rx.stop()
+        return True
+
+    @property
+    def frames_ok(self):
+        return sum(rx.frames_ok for rx in self._rx)
+
+    @property
+    def frames_dropped(self):
+        return sum(rx.frames_dropped for rx in self._rx)
+
+    def stats(self):
+        """the channels' wifirx_stats, channel 0 first"""
+        return [rx.stats() for rx in self._rx]
+
+    def close(self):
+        """Release the device buffers and every handle."""
+        if getattr(self, "_s", None) is not None:
+            self._s.close()
+        for rx in getattr(self, "_rx", []):
+            rx.close()
+        self._rx = []
 
 
 class wifi_phy_tx(grshim.sync_block):

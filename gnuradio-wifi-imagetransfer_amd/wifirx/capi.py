@@ -55,6 +55,7 @@ EXPORTS = [
     "wifirx_frontend", "wifirx_frontend_estimate", "wifirx_rx_impair", "wifirx_stream_frontend", "wifirx_stream_frontend_state",
     "wifirx_precombine",
     "wifirx_arb_resample", "wifirx_arb_hist", "wifirx_arb_count", "wifirx_arb_table",
+    "wifirx_tune", "wifirx_tune_inc",
 ]
 FE_DC, FE_IQ = 1, 2                 # WIFIRX_FE_*: stages of the receive front end (NUMERICS.md rule 32)
 FE_BLOCK, FE_RING = 4096, 64        # WIFIRX_FE_BLOCK, WIFIRX_FE_RING
@@ -73,6 +74,7 @@ CHANNELIZER_CHANNELS = (2, 4, 8)    # wifirx_channelize: n_channels (NUMERICS.md
 CHANNELIZER_HIST = 23               # input blocks of n_channels samples that a call takes from before its input
 ARB_HIST_MAX = 128                  # WIFIRX_ARB_HIST_MAX: the most samples wifirx_arb_resample takes from before its input
 ARB_MAX_DEN, ARB_MAX_NUM, ARB_MAX_RATIO = 512, 2048, 4      # the limits of a reduced ratio (NUMERICS.md rule 34)
+TUNE_MAX_CHANNELS = 8               # WIFIRX_TUNE_MAX_CHANNELS: the most channels of one wifirx_tune call (NUMERICS.md rule 35)
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
 
@@ -194,6 +196,17 @@ def arb_flush_inputs(num, den, n_in, n_out) -> int:
     num, den = int(num) // g, int(den) // g
     S = max(num, den)
     return max(0, ((int(n_out) - 1) * num + 16 * S) // den + 1 - int(n_in)) if n_out > 0 else 0       # m_end(E) >= n_out
+
+
+def tune_inc(offset_hz, sample_rate) -> int:
+    """wifirx_tune_inc: the uint64 phase increment per input sample (2^-64 turns) that brings a channel whose centre lies
+    offset_hz above the capture's centre down to 0 (no handle, no device).  A caller advances nothing: wifirx_tune forms the
+    phase from the stream index."""
+    v = C.c_uint64()
+    rc = _lib.wifirx_tune_inc(float(offset_hz), float(sample_rate), C.byref(v))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_tune_inc: offset_hz must be finite, sample_rate finite and > 0")
+    return int(v.value)
 
 
 def channel_centre(k, n_channels, stacking) -> float:
@@ -365,6 +378,10 @@ _lib.wifirx_arb_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float,
 _lib.wifirx_arb_hist.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
 _lib.wifirx_arb_count.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
 _lib.wifirx_arb_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+_lib.wifirx_tune.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                             C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.c_void_p,
+                             C.c_uint64, C.POINTER(C.c_uint64)]
+_lib.wifirx_tune_inc.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_uint64)]
 _lib.wifirx_diversity_combine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.c_uint32, C.c_int, C.POINTER(C.c_float),
                                           C.POINTER(Out), C.c_void_p]
 _lib.wifirx_precombine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -1479,6 +1496,55 @@ class WifiRx:
             got = self.arb_resample_dev(d_in.ptr, fmt, n, num, den, d_out.ptr, made, scale=scale)
             y = d_out.download(np.complex64, got)            # ordered behind the kernel on the handle's stream
             return y if n_out is None else y[:n_out]
+        finally:
+            d_in.free()
+            d_out.free()
+
+    # -- tuner (wifirx_tune; NUMERICS.md rule 35) --
+    def tune_dev(self, in_ptr, fmt, n_in, num, den, incs, out_ptr, out_stride, phase0s=None, hist_ptr=None, hist_out_ptr=None,
+                 j0=0, m0=0, scale=None) -> int:
+        """wifirx_tune on device pointers: n_in samples of `fmt` at in_ptr, in[0] being stream sample j0 -> per channel k the
+        outputs m0 .. as complex64 at out_ptr + 8 * k * out_stride.  incs: one uint64 increment per channel (tune_inc);
+        phase0s: the phases of stream sample 0 (None: zeros).  hist_ptr / hist_out_ptr as arb_resample_dev: raw input
+        samples.  Returns n_out per channel.  Asynchronous on the handle's stream: sync() before another handle reads a row."""
+        fmt = iq_format(fmt)
+        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
+        K = len(incs)
+        inc = (C.c_uint64 * max(K, 1))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in incs])
+        ph = None
+        if phase0s is not None:
+            if len(phase0s) != K:
+                raise ValueError("one phase0 per channel is required")
+            ph = (C.c_uint64 * max(K, 1))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in phase0s])
+        n = C.c_uint64(0)
+        self._check(_lib.wifirx_tune(self._h, in_ptr, fmt, float(scale), int(n_in), hist_ptr, hist_out_ptr, int(num), int(den), K,
+                                     inc, ph, int(j0), int(m0), out_ptr, int(out_stride), C.byref(n)))
+        return int(n.value)
+
+    def tune(self, x, num, den, incs, phase0s=None, fmt=None, scale=None, n_out=None) -> np.ndarray:
+        """tune_dev on host arrays, a whole stream from j0 = m0 = 0: complex64 samples (fmt None or "fc32") or int16 / int8
+        samples ([n, 2] or flat [2 n]) -> complex64 [K, n_out].  n_out: append the zeros of the end-of-stream flush and return
+        exactly that many outputs per channel (None: what the samples alone give)."""
+        x = np.asarray(x)
+        if fmt is None and x.dtype not in (np.dtype(np.int16), np.dtype(np.int8)):
+            fmt = IQ_FC32
+        if fmt is not None and iq_format(fmt) == IQ_FC32:
+            x, fmt = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1), IQ_FC32
+            n = x.size
+        else:
+            x, fmt, n = self._iq_array(x, fmt)
+        if n_out is not None:
+            pad = arb_flush_inputs(num, den, n, n_out)
+            x = np.concatenate([x, np.zeros(pad * (1 if fmt == IQ_FC32 else 2), x.dtype)])
+            n += pad
+        K = len(incs)
+        made = arb_count(num, den, 0, n, 0)
+        d_in, d_out = self.alloc(max(x.nbytes, 1)), self.alloc(max(made * K, 1) * 8)
+        try:
+            d_in.upload(x)
+            got = self.tune_dev(d_in.ptr, fmt, n, num, den, incs, d_out.ptr, made, phase0s=phase0s, scale=scale)
+            y = d_out.download(np.complex64, got * K).reshape(K, got)       # ordered behind the kernel on the handle's stream
+            return y if n_out is None else y[:, :n_out]
         finally:
             d_in.free()
             d_out.free()

@@ -973,6 +973,48 @@ int  wifirx_arb_count(uint32_t num, uint32_t den, uint64_t j0, uint64_t n_in, ui
  * and no device.  WIFIRX_EINVAL for a NULL argument. */
 int  wifirx_arb_table(const float** table, uint32_t* n_entries, uint32_t* per_unit);
 
+/* Tuner (NUMERICS.md rule 35): n_channels = 1 .. 8 channels at any centre out of ONE capture, on the device -- channels 1 / 6 /
+ * 11 of the 2.4 GHz band (25 MHz apart) out of an 80 MS/s capture around 2437 MHz, which no M x 20 MHz bank can split (GNU
+ * Radio's freq_xlating_fir_filter, or rotator + rational_resampler, per channel in front of wifi_phy_hier).  Channel k is the
+ * capture multiplied by exp(j 2 pi P_k(j) / 2^64), P_k(j) = phase0[k] + inc[k] * j mod 2^64 at STREAM index j (rule 17's
+ * fixed-point mixer: the angle is the float32 of the top 32 bits of P, sine and cosine by rule 1, the product in plain
+ * float32), and then resampled exactly as wifirx_arb_resample does: the same ratio, prototype, sum, gain and counting
+ * (wifirx_arb_count, wifirx_arb_hist).  Every sample the sum reads is rotated first, the zeros in front of the stream and
+ * of a NULL hist included, so a NULL hist and a hist of zeros give the same bytes.  The phase depends on the stream index
+ * alone: a stream cut anywhere is byte-identical to the uncut one with nothing more than j0, m0 and hist_out passed on, and
+ * hist / hist_out hold RAW input samples as in wifirx_arb_resample.  A channel with inc[k] == 0 and phase0[k] == 0 is not
+ * rotated at all: its row holds the bytes of wifirx_arb_resample.
+ * THE FILTER is wifirx_arb_resample's prototype and nothing sharper: a tuned centre must keep |offset| + 8.3 MHz inside
+ * fs_in / 2, or the channel itself aliases, and what lies more than (1 - 26.5/64) * 20 MHz = 11.7 MHz from the tuned centre
+ * is down by 69 dB (for fs_out = 20 MS/s).  25 MHz in a 61.44 MS/s capture aliases (25 + 8.3 > 30.72: the radio's filters
+ * have removed the channel's upper edge, or folded something else onto it, before the samples exist); in 80 MS/s it does not.
+ *   in, fmt, scale, n_in, hist, hist_out, num, den, j0, m0      as wifirx_arb_resample
+ *   n_channels  1 .. WIFIRX_TUNE_MAX_CHANNELS
+ *   inc         HOST [n_channels], required: the phase increments per input sample in 2^-64 turns (wifirx_tune_inc); read
+ *               before the call returns
+ *   phase0      HOST [n_channels], the phases of stream sample 0; NULL = zeros; read before the call returns
+ *   out         DEVICE, 8-byte aligned: row k starts at out + 2 * k * out_stride floats; of each row the outputs
+ *               m0 .. m_end(j0 + n_in) - 1 are written and nothing else.  A row is what wifirx_push(iq_on_device = 1) takes.
+ *   out_stride  float pairs from one row to the next, >= n_out
+ *   n_out       HOST, required: the outputs PER CHANNEL, the value wifirx_arb_count gives
+ * Checked on the host before anything is queued: everything wifirx_arb_resample checks, with out_stride in out_cap's place and
+ * the n_channels * out_stride * 8 bytes of out as the output buffer; WIFIRX_EINVAL also for n_channels of 0 or above 8 and a
+ * NULL inc; WIFIRX_ERANGE also for out_stride < n_out (whatever n_channels is), for out_stride >= 2^56 (8 rows of it stay
+ * below 2^62 bytes), and for more than 2^31 - 1 tiles of 256 outputs.  A refused call writes nothing, *n_out included.  One kernel launch per call, and at most two copies
+ * for hist_out.
+ * ORDER: as wifirx_arb_resample. */
+#define WIFIRX_TUNE_MAX_CHANNELS 8
+int  wifirx_tune(wifirx_handle* h, const void* in, int fmt, float scale, uint64_t n_in, const void* hist, void* hist_out,
+                 uint32_t num, uint32_t den, uint32_t n_channels, const uint64_t* inc, const uint64_t* phase0, uint64_t j0,
+                 uint64_t m0, float* out, uint64_t out_stride, uint64_t* n_out);
+
+/* The increment that brings a channel whose centre lies offset_hz ABOVE the capture's centre down to 0: t = offset_hz /
+ * sample_rate in double, reduced to [-1/2, 1/2] by subtracting its nearest integer, *inc = (uint64_t)(-llround(t * 2^64));
+ * +-1/2 turn gives 2^63 (rule 17's phase increment without the 2 pi).  +25 MHz in 80 MS/s gives 0xB000000000000000.  Needs no
+ * handle and no device.  WIFIRX_EINVAL for a NULL inc, a sample_rate that is not finite or <= 0, an offset_hz that is not
+ * finite. */
+int  wifirx_tune_inc(double offset_hz, double sample_rate, uint64_t* inc);
+
 /* Receive diversity (NUMERICS.md rule 23): combine the equalised points of n_ant antennas' demodulated batches into one batch
  * to decode.  Slot i of every in[a] is the same transmission, demodulated from antenna a's samples by wifirx_demod_batch with
  * `carrier` and `csi` outputs (by this handle one after the other, or by other handles with the same max_sym).  Per slot: the
