@@ -638,6 +638,7 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 }  // extern "C"
 
 #include "wifirx_api_decode.inc"
+#include "wifirx_api_ingest.inc"
 #include "wifirx_api_frontend.inc"
 #include "wifirx_api_stream.inc"
 #include "wifirx_api_tx.inc"

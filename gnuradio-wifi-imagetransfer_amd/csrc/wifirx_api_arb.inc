@@ -32,9 +32,7 @@ int arb_check_call(wifirx_handle* h, const void* in, int fmt, float scale, uint6
 {
     if (!n_out) return fail(h, WIFIRX_EINVAL, "n_out is required");
     if (n_in && !in) return fail(h, WIFIRX_EINVAL, "in is required");
-    c->bps = fmt == WIFIRX_IQ_FC32 ? 8u : wr_iq_sample_bytes(fmt);
-    if (!c->bps) return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_FC32, WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");
-    if (fmt != WIFIRX_IQ_FC32 && (!std::isfinite(scale) || !(scale > 0))) return fail(h, WIFIRX_EINVAL, "scale must be finite and > 0");
+    if (int rc = iq_check_format(h, fmt, scale, true, &c->bps)) return rc;
     if (!wr_arb_plan(num, den, &c->r))
         return fail(h, WIFIRX_EINVAL, "num / den must reduce to 1 <= den <= 512, 1 <= num <= 2048, num <= 4 den, den <= 4 num");
     const uintptr_t align = c->bps - 1;
@@ -57,12 +55,8 @@ int arb_check_buffers(wifirx_handle* h, const arb_call& c, const void* in, const
                       uint64_t out_bytes, uint64_t j0, uint64_t m0)
 {
     const wr_arb_ratio& r = c.r;
-    const struct { const void* p; uint64_t bytes; } buf[4] = {
-        { in, c.in_bytes }, { out, out_bytes }, { hist, hist ? c.hist_bytes : 0 }, { hist_out, hist_out ? c.hist_bytes : 0 } };
-    for (int a = 0; a < 4; a++)
-        for (int b = a + 1; b < 4; b++)
-            if (ranges_overlap(buf[a].p, buf[a].bytes, buf[b].p, buf[b].bytes))
-                return fail(h, WIFIRX_EINVAL, "in, hist, hist_out and out must not overlap");
+    const ByteRange buf[4] = { { in, c.in_bytes }, { out, out_bytes }, { hist, hist ? c.hist_bytes : 0 }, { hist_out, hist_out ? c.hist_bytes : 0 } };
+    if (any_overlap(buf)) return fail(h, WIFIRX_EINVAL, "in, hist, hist_out and out must not overlap");
     if (c.n) {
         // jlo(m0) = floor((m0 num - 16 S) / den) + 1 must not lie in front of the history
         const int64_t D = (int64_t)(m0 * r.num) - 16 * (int64_t)r.S;
@@ -71,18 +65,6 @@ int arb_check_buffers(wifirx_handle* h, const arb_call& c, const void* in, const
         if (fl + 1 < (int64_t)j0 - (int64_t)r.HL)
             return fail(h, WIFIRX_EINVAL, "the history does not reach output m0: its first input lies in front of j0 - hist_len");
     }
-    return WIFIRX_OK;
-}
-
-// hist_out = the last HL samples of (hist || in), queued behind the kernel: `keep` bytes of hist's tail, then in's tail
-int arb_queue_hist(wifirx_handle* h, const arb_call& c, const void* in, const void* hist, void* hist_out)
-{
-    uint8_t* dst = static_cast<uint8_t*>(hist_out);
-    const uint64_t from_in = std::min(c.in_bytes, c.hist_bytes), keep = c.hist_bytes - from_in;
-    if (keep && hist) HIP_TRY(h, hipMemcpyAsync(dst, static_cast<const uint8_t*>(hist) + from_in, keep, hipMemcpyDeviceToDevice, h->stream));
-    else if (keep) HIP_TRY(h, hipMemsetAsync(dst, 0, keep, h->stream));
-    if (from_in)
-        HIP_TRY(h, hipMemcpyAsync(dst + keep, static_cast<const uint8_t*>(in) + (c.in_bytes - from_in), from_in, hipMemcpyDeviceToDevice, h->stream));
     return WIFIRX_OK;
 }
 
@@ -126,5 +108,5 @@ extern "C" int wifirx_arb_resample(wifirx_handle* h, const void* in, int fmt, fl
     HIP_TRY(h, hipSetDevice(h->device));
     if (c.n)
         HIP_TRY(h, wr_launch_arb(h->stream, in, fmt, scale, n_in, hist, &c.r, j0, m0, c.n, reinterpret_cast<float2*>(out)));
-    return hist_out ? arb_queue_hist(h, c, in, hist, hist_out) : WIFIRX_OK;
+    return hist_out ? queue_hist_tail(h, in, c.in_bytes, hist, hist_out, c.hist_bytes) : WIFIRX_OK;
 }

@@ -5,13 +5,6 @@ namespace {
 
 static_assert(WR_CZ_HIST == WR_CB_HIST, "one history length for both banks");
 
-// do the byte ranges [a, a + na) and [b, b + nb) share a byte?  (an empty range shares none)
-bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return na && nb && pa < pb + nb && pb < pa + na;
-}
-
 // The buffers of a bank call.  `wide`: one interleaved stream of n * M samples of bps bytes, aligned to bps, as are hist and
 // hist_out of 23 * M such samples each.  `rows`: M rows of n float pairs, `stride` pairs apart, aligned to 8 bytes.  No two
 // of the four may share a byte.  side ("in" or "out") is what the caller calls its rows; misaligned is its text for that.
@@ -25,13 +18,10 @@ int bank_check(wifirx_handle* h, const void* wide, uint32_t bps, const void* row
     if (n > (1ull << 40)) return fail(h, WIFIRX_ERANGE, "n_" + side + " out of range");
     if (stride < n || stride > (1ull << 44)) return fail(h, WIFIRX_ERANGE, side + "_stride must be n_" + side + " .. 2^44");
     const uint64_t hist_bytes = (uint64_t)WR_CZ_HIST * M * bps;
-    const struct { const void* p; uint64_t bytes; } r[4] = {
+    const ByteRange r[4] = {
         { wide, n * M * bps }, { rows, n ? ((M - 1) * stride + n) * 8 : 0 },         // first byte of row 0 to the last of row M - 1
         { hist, hist ? hist_bytes : 0 }, { hist_out, hist_out ? hist_bytes : 0 } };
-    for (int a = 0; a < 4; a++)
-        for (int b = a + 1; b < 4; b++)
-            if (ranges_overlap(r[a].p, r[a].bytes, r[b].p, r[b].bytes))
-                return fail(h, WIFIRX_EINVAL, "in, hist, hist_out and out must not overlap");
+    if (any_overlap(r)) return fail(h, WIFIRX_EINVAL, "in, hist, hist_out and out must not overlap");
     return WIFIRX_OK;
 }
 
@@ -42,30 +32,20 @@ extern "C" int wifirx_channelize(wifirx_handle* h, const void* in, int fmt, floa
 {
     if (!h) return WIFIRX_EINVAL;
     if (n_out && (!in || !out)) return fail(h, WIFIRX_EINVAL, "in and out are required");
-    const uint32_t bps = fmt == WIFIRX_IQ_FC32 ? 8u : wr_iq_sample_bytes(fmt);
-    if (!bps) return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_FC32, WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");
-    if (fmt != WIFIRX_IQ_FC32 && (!std::isfinite(scale) || !(scale > 0))) return fail(h, WIFIRX_EINVAL, "scale must be finite and > 0");
+    uint32_t bps;
+    if (int rc = iq_check_format(h, fmt, scale, true, &bps)) return rc;
     if (n_channels != 2 && n_channels != 4 && n_channels != 8) return fail(h, WIFIRX_EINVAL, "n_channels must be 2, 4 or 8");
     if (stacking != 0 && stacking != 1) return fail(h, WIFIRX_EINVAL, "stacking must be 0 or 1");
     if (const int rc = bank_check(h, in, bps, out, out_stride, n_out, n_channels, hist, hist_out, "out",
                                   "misaligned buffer (out: 8 bytes; in, hist, hist_out: fc32 8, sc16 4, sc8 2)"))
         return rc;
-    const uint64_t in_bytes = n_out * n_channels * bps, hist_bytes = (uint64_t)WR_CZ_HIST * n_channels * bps;
     if (n_out == 0 && !hist_out) return WIFIRX_OK;
     stream_worker_wait_idle(h);
     HIP_TRY(h, hipSetDevice(h->device));
     if (n_out)
         HIP_TRY(h, wr_launch_channelize(h->stream, in, fmt, scale, hist, n_channels, stacking, n_out, m0, reinterpret_cast<float2*>(out), out_stride));
-    if (hist_out) {
-        // the last 23 M samples of (hist || in), queued behind the kernel: `keep` bytes of hist's tail, then in's tail
-        uint8_t* dst = static_cast<uint8_t*>(hist_out);
-        const uint64_t from_in = std::min(in_bytes, hist_bytes), keep = hist_bytes - from_in;
-        if (keep && hist) HIP_TRY(h, hipMemcpyAsync(dst, static_cast<const uint8_t*>(hist) + from_in, keep, hipMemcpyDeviceToDevice, h->stream));
-        else if (keep) HIP_TRY(h, hipMemsetAsync(dst, 0, keep, h->stream));
-        if (from_in)
-            HIP_TRY(h, hipMemcpyAsync(dst + keep, static_cast<const uint8_t*>(in) + (in_bytes - from_in), from_in, hipMemcpyDeviceToDevice, h->stream));
-    }
-    return WIFIRX_OK;
+    // the last 23 M samples of (hist || in)
+    return hist_out ? queue_hist_tail(h, in, n_out * n_channels * bps, hist, hist_out, (uint64_t)WR_CZ_HIST * n_channels * bps) : WIFIRX_OK;
 }
 
 extern "C" int wifirx_channelizer_table(uint32_t n_channels, const float** taps, uint32_t* n_taps)

@@ -7,13 +7,12 @@ namespace {
 int check_convert(wifirx_handle* h, const void* ints, const void* floats, int fmt, uint64_t n, float scale)
 {
     if (!ints || !floats) return fail(h, WIFIRX_EINVAL, "src and dst are required");
-    const uint32_t bps = wr_iq_sample_bytes(fmt);
-    if (!bps) return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");
-    if (!std::isfinite(scale) || !(scale > 0)) return fail(h, WIFIRX_EINVAL, "scale must be finite and > 0");
+    uint32_t bps;
+    if (int rc = iq_check_format(h, fmt, scale, false, &bps)) return rc;
     const uintptr_t pi = reinterpret_cast<uintptr_t>(ints), pf = reinterpret_cast<uintptr_t>(floats);
     if ((pi & (bps - 1)) || (pf & 7)) return fail(h, WIFIRX_EINVAL, "misaligned buffer (float pairs: 8 bytes; sc16: 4; sc8: 2)");
     if (n > (UINT64_MAX >> 4)) return fail(h, WIFIRX_EINVAL, "n out of range");
-    if (pi < pf + n * 8 && pf < pi + n * bps) return fail(h, WIFIRX_EINVAL, "src and dst overlap");
+    if (ranges_overlap(ints, n * bps, floats, n * 8)) return fail(h, WIFIRX_EINVAL, "src and dst overlap");
     return WIFIRX_OK;
 }
 
@@ -63,9 +62,8 @@ extern "C" int wifirx_push_iq(wifirx_handle* h, const void* iq, size_t n, int fm
     if (!h) return WIFIRX_EINVAL;
     if (fmt == WIFIRX_IQ_FC32) return wifirx_push(h, static_cast<const float*>(iq), n, iq_on_device);
     h->st.push_consumed = 0;
-    const uint32_t bps = wr_iq_sample_bytes(fmt);
-    if (!bps) return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_FC32, WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");
-    if (!std::isfinite(scale) || !(scale > 0)) return fail(h, WIFIRX_EINVAL, "scale must be finite and > 0");
+    uint32_t bps;
+    if (int rc = iq_check_format(h, fmt, scale, true, &bps)) return rc;         // (float pairs have gone to wifirx_push)
     if (reinterpret_cast<uintptr_t>(iq) & (bps - 1)) return fail(h, WIFIRX_EINVAL, "iq is misaligned (sc16: 4 bytes; sc8: 2)");
     return stream_push(h, iq, n, fmt, scale, iq_on_device);
 }

@@ -16,24 +16,21 @@ int check_frontend_cfg(wifirx_handle* h, const wifirx_frontend_cfg* cfg)
     return WIFIRX_OK;
 }
 
-bool ranges_overlap(uintptr_t a, uint64_t a_bytes, uintptr_t b, uint64_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; }
-
 // what wifirx_frontend checks before anything is queued
 int check_frontend(wifirx_handle* h, const wifirx_frontend_cfg* cfg, const wifirx_frontend_state* state, const void* in, int fmt,
                    float scale, uint64_t n, const float* out)
 {
     if (int rc = check_frontend_cfg(h, cfg)) return rc;
     if (!state || !in || !out) return fail(h, WIFIRX_EINVAL, "state_dev, in and out are required");
-    const uint32_t bps = fmt == WIFIRX_IQ_FC32 ? 8u : wr_iq_sample_bytes(fmt);
-    if (!bps) return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_FC32, WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");
-    if (fmt != WIFIRX_IQ_FC32 && (!std::isfinite(scale) || !(scale > 0))) return fail(h, WIFIRX_EINVAL, "scale must be finite and > 0");
+    uint32_t bps;
+    if (int rc = iq_check_format(h, fmt, scale, true, &bps)) return rc;
     const uintptr_t pi = reinterpret_cast<uintptr_t>(in), po = reinterpret_cast<uintptr_t>(out), ps = reinterpret_cast<uintptr_t>(state);
     if ((pi & (bps - 1)) || (po & 7) || (ps & 7))
         return fail(h, WIFIRX_EINVAL, "misaligned buffer (float pairs and the state: 8 bytes; sc16: 4; sc8: 2)");
     if (n > (1ull << 40)) return fail(h, WIFIRX_EINVAL, "n out of range (at most 2^40 samples per call)");
-    if (!(fmt == WIFIRX_IQ_FC32 && pi == po) && ranges_overlap(pi, n * bps, po, n * 8))
+    if (!(fmt == WIFIRX_IQ_FC32 && pi == po) && ranges_overlap(in, n * bps, out, n * 8))
         return fail(h, WIFIRX_EINVAL, "in and out overlap (only in == out, for WIFIRX_IQ_FC32, is allowed)");
-    if (ranges_overlap(ps, sizeof(wifirx_frontend_state), pi, n * bps) || ranges_overlap(ps, sizeof(wifirx_frontend_state), po, n * 8))
+    if (ranges_overlap(state, sizeof(wifirx_frontend_state), in, n * bps) || ranges_overlap(state, sizeof(wifirx_frontend_state), out, n * 8))
         return fail(h, WIFIRX_EINVAL, "the state overlaps in or out");
     return WIFIRX_OK;
 }
@@ -97,7 +94,7 @@ extern "C" int wifirx_rx_impair(wifirx_handle* h, const float* in, float* out, u
     const uintptr_t pi = reinterpret_cast<uintptr_t>(in), po = reinterpret_cast<uintptr_t>(out);
     if ((pi & 7) || (po & 7)) return fail(h, WIFIRX_EINVAL, "misaligned buffer (float pairs: 8 bytes)");
     if (n > (1ull << 40)) return fail(h, WIFIRX_EINVAL, "n out of range (at most 2^40 samples per call)");
-    if (pi != po && ranges_overlap(pi, n * 8, po, n * 8)) return fail(h, WIFIRX_EINVAL, "in and out overlap (only in == out is allowed)");
+    if (pi != po && ranges_overlap(in, n * 8, out, n * 8)) return fail(h, WIFIRX_EINVAL, "in and out overlap (only in == out is allowed)");
     if (n == 0) return WIFIRX_OK;
     stream_worker_wait_idle(h);
     HIP_TRY(h, hipSetDevice(h->device));

@@ -295,14 +295,12 @@ extern "C" int wifirx_push_diversity(wifirx_handle* h, const wifirx_div_stream* 
     if (h->st.single) return fail(h, WIFIRX_EINVAL, "the handle's stream has taken samples through wifirx_push / wifirx_push_iq");
     if (h->st.fe_on) return fail(h, WIFIRX_EINVAL, "the handle's front end is on (wifirx_stream_frontend): the diversity stream has none");
     if (cfg->mode != WIFIRX_DIV_MRC && cfg->mode != WIFIRX_DIV_SELECT) return fail(h, WIFIRX_EINVAL, "mode must be WIFIRX_DIV_MRC or WIFIRX_DIV_SELECT");
-    if (cfg->fmt != WIFIRX_IQ_FC32 && cfg->fmt != WIFIRX_IQ_SC16 && cfg->fmt != WIFIRX_IQ_SC8)
-        return fail(h, WIFIRX_EINVAL, "fmt must be WIFIRX_IQ_FC32, WIFIRX_IQ_SC16 or WIFIRX_IQ_SC8");
-    const uint32_t bps = wr_iq_sample_bytes(cfg->fmt);
-    if (bps && (!std::isfinite(cfg->scale) || !(cfg->scale > 0))) return fail(h, WIFIRX_EINVAL, "scale must be finite and > 0");
+    uint32_t bps;
+    if (int rc = iq_check_format(h, cfg->fmt, cfg->scale, true, &bps)) return rc;
     for (uint32_t a = 0; a < cfg->n_ant; a++) {
         if (cfg->ant_gain && !(std::isfinite(cfg->ant_gain[a]) && cfg->ant_gain[a] >= 0.0f)) return fail(h, WIFIRX_EINVAL, "ant_gain must be finite and >= 0");
         if (n > 0 && !iq[a]) return fail(h, WIFIRX_EINVAL, "iq[a] is null");
-        const uintptr_t align = bps ? bps : (cfg->iq_on_device ? sizeof(float2) : 1);
+        const uintptr_t align = cfg->fmt != WIFIRX_IQ_FC32 || cfg->iq_on_device ? bps : 1;       // float pairs on the host: any address
         if (reinterpret_cast<uintptr_t>(iq[a]) & (align - 1)) return fail(h, WIFIRX_EINVAL, "iq[a] is misaligned (float pairs on the device: 8 bytes; sc16: 4; sc8: 2)");
     }
     if (n > (size_t)1 << 40) return fail(h, WIFIRX_EINVAL, "n out of range");

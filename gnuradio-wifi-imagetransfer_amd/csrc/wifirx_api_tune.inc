@@ -1,6 +1,6 @@
 // the tuner on device buffers (NUMERICS.md rule 35; wr_arb.hip, tune_kernel): K channels at any centre out of one capture,
-// each mixed by rule 17's fixed-point phase ramp on the way into rule 34's sum.  The checks, the counting and the history are
-// wifirx_arb_resample's (wifirx_api_arb.inc).
+// each mixed by rule 17's fixed-point phase ramp on the way into rule 34's sum.  The checks and the counting are
+// wifirx_arb_resample's (wifirx_api_arb.inc), the history's copies every ingest call's (wifirx_api_ingest.inc).
 
 extern "C" int wifirx_tune_inc(double offset_hz, double sample_rate, uint64_t* inc)
 {
@@ -38,5 +38,5 @@ extern "C" int wifirx_tune(wifirx_handle* h, const void* in, int fmt, float scal
     if (c.n)
         HIP_TRY(h, wr_launch_tune(h->stream, in, fmt, scale, n_in, hist, &c.r, j0, m0, c.n, reinterpret_cast<float2*>(out),
                                   n_channels, &ch));
-    return hist_out ? arb_queue_hist(h, c, in, hist, hist_out) : WIFIRX_OK;
+    return hist_out ? queue_hist_tail(h, in, c.in_bytes, hist, hist_out, c.hist_bytes) : WIFIRX_OK;
 }

@@ -20,7 +20,7 @@
 
 #include "wr_arb.h"
 #include "wr_arb_table.h"
-#include "wr_device.h"     // sp_sincos (rule 1)
+#include "wr_device.h"     // sp_sincos_phase (rules 1 and 17)
 #include "wr_iq.h"
 
 namespace wr {
@@ -32,7 +32,6 @@ static_assert(4 * WR_ARB_HALF * 2 == WIFIRX_ARB_HIST_MAX, "32 S / den <= 128 for
 
 constexpr uint32_t ARB_ROW = 2 * WR_ARB_HALF + 1;             // 33 floats: 32 units and one word of padding
 constexpr uint32_t ARB_ROWS = WR_ARB_PER_UNIT + 1;
-constexpr float ARB_PHASE_SCALE = (float)(6.283185307179586 / 4294967296.0);      // 2 pi / 2^32: radians per unit of P >> 32
 
 const float arb_host_table[WR_ARB_ENTRIES] = WR_ARB_TABLE_INIT;
 __device__ const float arb_dev_table[WR_ARB_ENTRIES] = WR_ARB_TABLE_INIT;
@@ -92,7 +91,7 @@ __device__ __forceinline__ void arb_tile(const void* __restrict__ in, const void
         if (rotate) {
             const uint64_t P = Pbase + inc * s;
             float sn, cs;
-            sp_sincos((float)(int32_t)(uint32_t)(P >> 32) * ARB_PHASE_SCALE, sn, cs);
+            sp_sincos_phase((uint32_t)(P >> 32), sn, cs);
             x = make_float2(x.x * cs - x.y * sn, x.x * sn + x.y * cs);
         }
         xs[s] = x;
@@ -178,11 +177,10 @@ extern "C" hipError_t wr_launch_arb(hipStream_t st, const void* in, int fmt, flo
     const uint64_t tiles = (n_out + WR_ARB_TILE - 1) / WR_ARB_TILE;
     if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 grid((uint32_t)tiles), block(WR_ARB_TILE);
-    if (fmt == WIFIRX_IQ_FC32) hipLaunchKernelGGL((wr::arb_kernel<WIFIRX_IQ_FC32>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out);
-    else if (fmt == WIFIRX_IQ_SC16) hipLaunchKernelGGL((wr::arb_kernel<WIFIRX_IQ_SC16>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out);
-    else if (fmt == WIFIRX_IQ_SC8) hipLaunchKernelGGL((wr::arb_kernel<WIFIRX_IQ_SC8>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const bool known = wr::iq_dispatch(fmt, [&](auto F) {
+        hipLaunchKernelGGL((wr::arb_kernel<decltype(F)::value>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 extern "C" hipError_t wr_launch_tune(hipStream_t st, const void* in, int fmt, float scale, uint64_t n_in, const void* hist,
@@ -193,11 +191,10 @@ extern "C" hipError_t wr_launch_tune(hipStream_t st, const void* in, int fmt, fl
     const uint64_t tiles = (n_out + WR_ARB_TILE - 1) / WR_ARB_TILE;
     if (tiles > 0x7fffffffull || n_channels < 1 || n_channels > WIFIRX_TUNE_MAX_CHANNELS) return hipErrorInvalidValue;
     const dim3 grid((uint32_t)tiles, n_channels), block(WR_ARB_TILE);
-    if (fmt == WIFIRX_IQ_FC32) hipLaunchKernelGGL((wr::tune_kernel<WIFIRX_IQ_FC32>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out, *c);
-    else if (fmt == WIFIRX_IQ_SC16) hipLaunchKernelGGL((wr::tune_kernel<WIFIRX_IQ_SC16>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out, *c);
-    else if (fmt == WIFIRX_IQ_SC8) hipLaunchKernelGGL((wr::tune_kernel<WIFIRX_IQ_SC8>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out, *c);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const bool known = wr::iq_dispatch(fmt, [&](auto F) {
+        hipLaunchKernelGGL((wr::tune_kernel<decltype(F)::value>), grid, block, 0, st, in, hist, scale, n_in, *r, j0, m0, n_out, out, *c);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 extern "C" const float* wr_arb_host_table(void) { return wr::arb_host_table; }

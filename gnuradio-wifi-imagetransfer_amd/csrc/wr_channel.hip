@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "wr_device.h"     // sp_sincos (rule 1)
+#include "wr_device.h"     // sp_sincos (rule 1), sp_sincos_phase (rule 17)
 #include "wr_rng.h"        // philox4x32_10, u01, ch_noise
 #include "wr_channel.h"    // ch_mul, ch_add
 #include "wr_resample_table.h"
@@ -41,13 +41,11 @@ namespace wr {
 
 __device__ const float rs_table[(WR_RS_PHASES + 1) * WR_RS_TAPS] = WR_RS_TABLE_INIT;
 
-constexpr float CH_PHASE_SCALE = (float)(6.283185307179586 / 4294967296.0);      // 2 pi / 2^32: radians per unit of P >> 32
-
 // sample n of the row after the FIR: gain * (s * exp(j phi(n)))
 __device__ __forceinline__ float2 ch_rotate(float2 s, uint64_t P, float gain)
 {
     float sn, cs;
-    sp_sincos((float)(int32_t)(uint32_t)(P >> 32) * CH_PHASE_SCALE, sn, cs);
+    sp_sincos_phase((uint32_t)(P >> 32), sn, cs);
     const float2 y = ch_mul(s, make_float2(cs, sn));
     return make_float2(gain * y.x, gain * y.y);
 }
@@ -72,7 +70,7 @@ __device__ __forceinline__ uint4 ch_draw(uint64_t pair, uint32_t row, uint2 key)
 __device__ __forceinline__ float2 fade_osc(uint64_t phi, uint64_t inc, uint64_t t)
 {
     float sn, cs;
-    sp_sincos((float)(int32_t)(uint32_t)((phi + inc * t) >> 32) * CH_PHASE_SCALE, sn, cs);
+    sp_sincos_phase((uint32_t)((phi + inc * t) >> 32), sn, cs);
     return make_float2(cs, sn);
 }
 
@@ -144,7 +142,7 @@ void channel_kernel(const ChanArgs a)
         if (tid < CH_FADE_SINES * L || tid == CH_FADE_LOS) {
             const uint4 d = philox4x32_10(make_uint4(tid, r, 0u, 1u), make_uint2((uint32_t)a.fade_seed, (uint32_t)(a.fade_seed >> 32)));
             float sn, cs;
-            sp_sincos((float)(int32_t)d.x * CH_PHASE_SCALE, sn, cs);
+            sp_sincos_phase(d.x, sn, cs);
             osc_inc[tid] = (uint64_t)(int64_t)__builtin_round((double)a.doppler[r] * (double)cs * 0x1p64);      // |.| <= 2^54
             osc_phi[tid] = ((uint64_t)d.y << 32) | d.z;
         }

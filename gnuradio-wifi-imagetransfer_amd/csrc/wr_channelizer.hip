@@ -126,11 +126,10 @@ hipError_t launch_channelize(hipStream_t st, const void* in, int fmt, float scal
                              float2* out, uint64_t out_stride)
 {
     const dim3 grid((uint32_t)((n_out + WR_CZ_TILE - 1) / WR_CZ_TILE)), block(BANK_THREADS);
-    if (fmt == WIFIRX_IQ_FC32) hipLaunchKernelGGL((channelize_kernel<M, S, WIFIRX_IQ_FC32>), grid, block, 0, st, in, hist, scale, n_out, m0, out, out_stride);
-    else if (fmt == WIFIRX_IQ_SC16) hipLaunchKernelGGL((channelize_kernel<M, S, WIFIRX_IQ_SC16>), grid, block, 0, st, in, hist, scale, n_out, m0, out, out_stride);
-    else if (fmt == WIFIRX_IQ_SC8) hipLaunchKernelGGL((channelize_kernel<M, S, WIFIRX_IQ_SC8>), grid, block, 0, st, in, hist, scale, n_out, m0, out, out_stride);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const bool known = iq_dispatch(fmt, [&](auto F) {
+        hipLaunchKernelGGL((channelize_kernel<M, S, decltype(F)::value>), grid, block, 0, st, in, hist, scale, n_out, m0, out, out_stride);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace

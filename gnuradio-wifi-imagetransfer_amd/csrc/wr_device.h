@@ -42,6 +42,11 @@ __device__ __forceinline__ void sp_sincos(float x, float& s, float& c)
     c = ((k + 1) & 2) ? -c0 : c0;
 }
 
+// NUMERICS.md rule 17's rotor: sine and cosine of a phase P in 2^-64 turns, given its top 32 bits p = P >> 32 (signed: the
+// angle lies in [-pi, pi))
+constexpr float PHASE_SCALE = (float)(6.283185307179586 / 4294967296.0);         // 2 pi / 2^32: radians per unit of P >> 32
+__device__ __forceinline__ void sp_sincos_phase(uint32_t p, float& s, float& c) { sp_sincos((float)(int32_t)p * PHASE_SCALE, s, c); }
+
 // sp_sincos for callers whose angles are usually small: when every lane has |x * 2/pi| < 0.5 the reduction
 // of sp_sincos yields k = 0 and r = x exactly, so the polynomials alone give bit-identical results.
 __device__ __forceinline__ void sp_sincos_small(float x, float& s, float& c)

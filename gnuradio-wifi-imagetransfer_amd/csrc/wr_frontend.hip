@@ -346,10 +346,9 @@ extern "C" hipError_t wr_launch_frontend(hipStream_t st, const wifirx_frontend_c
     if (n == 0) return hipSuccess;
     if (n > (1ull << 40)) return hipErrorInvalidValue;         // the statistics grid is one workgroup per block
     const wr::FeParams prm = wr::fe_params(cfg);
-    if (fmt == WIFIRX_IQ_FC32) return wr::launch_frontend<WIFIRX_IQ_FC32>(st, prm, state, in, scale, n, out, table, n_cu);
-    if (fmt == WIFIRX_IQ_SC16) return wr::launch_frontend<WIFIRX_IQ_SC16>(st, prm, state, in, scale, n, out, table, n_cu);
-    if (fmt == WIFIRX_IQ_SC8) return wr::launch_frontend<WIFIRX_IQ_SC8>(st, prm, state, in, scale, n, out, table, n_cu);
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    wr::iq_dispatch(fmt, [&](auto F) { e = wr::launch_frontend<decltype(F)::value>(st, prm, state, in, scale, n, out, table, n_cu); });
+    return e;
 }
 
 // wifirx_frontend_estimate: what the block of the stream's next sample is corrected with, on the host

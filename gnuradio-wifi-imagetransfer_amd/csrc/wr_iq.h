@@ -1,7 +1,10 @@
-// wr_iq.h -- the sample formats of NUMERICS.md rule 20 as the kernels read them (internal; wr_convert.hip, wr_channelizer.hip).
+// wr_iq.h -- the sample formats of NUMERICS.md rule 20 as the kernels read them, and as their launchers pick the kernel of one
+// (internal; wr_convert.hip, wr_frontend.hip, wr_channelizer.hip, wr_arb.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "wifirx.h"
 
@@ -33,6 +36,18 @@ __device__ __forceinline__ float2 load_sample(const void* p, uint64_t s, float s
         const uint32_t w = static_cast<const uint16_t*>(p)[s];
         return make_float2((float)(int8_t)(w & 0xffu) * scale, (float)(int8_t)(w >> 8) * scale);
     }
+}
+
+// Host side: a run-time fmt as a compile-time one.  f(std::integral_constant<int, FMT>{}) for the launchers that take all
+// three formats; false for an fmt that is none of them.
+template <class F>
+bool iq_dispatch(int fmt, F&& f)
+{
+    if (fmt == WIFIRX_IQ_FC32) f(std::integral_constant<int, WIFIRX_IQ_FC32>{});
+    else if (fmt == WIFIRX_IQ_SC16) f(std::integral_constant<int, WIFIRX_IQ_SC16>{});
+    else if (fmt == WIFIRX_IQ_SC8) f(std::integral_constant<int, WIFIRX_IQ_SC8>{});
+    else return false;
+    return true;
 }
 
 }  // namespace

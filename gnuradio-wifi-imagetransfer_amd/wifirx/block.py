@@ -42,12 +42,8 @@ class wifi_phy_rx(grshim.sync_block):
         # sample_format: "fc32" (complex64 items, the default), or "sc16" / "sc8": items of two int16 / int8 (I, Q), the form
         # a UHD source with an sc16 CPU format delivers; they cross the bus as they are and are widened on the device
         # (value = integer * sample_scale, default 2^-15 / 2^-7; wifirx_push_iq, NUMERICS.md rule 20)
-        self.sample_format = capi.iq_format(sample_format)
-        if self.sample_format not in capi.IQ_DTYPE:
-            raise ValueError("sample_format must be 'fc32', 'sc16' or 'sc8'")
-        self.sample_scale = float(capi.IQ_SCALE[self.sample_format] if sample_scale is None else sample_scale)
-        self._item = capi.IQ_DTYPE[self.sample_format]
-        in_sig = [np.complex64] if self.sample_format == capi.IQ_FC32 else [(self._item.type, 2)]
+        sf = _sample_format(sample_format, sample_scale)
+        self.sample_format, self.sample_scale, self._item, in_sig = sf.fmt, sf.scale, sf.item, sf.in_sig
         # antennas = A > 1: A `samp_in` ports of the item type, the sample-synchronous channels of ONE radio (a two-channel
         # uhd.usrp_source).  Detection runs once, on all of them (NUMERICS.md rule 24), the antennas' equalised points are
         # combined (`diversity`: "mrc" or "select"; ant_gain: the inverse noise power per antenna, None = equal; rule 23) and
@@ -385,22 +381,151 @@ class wifi_phy_rx(grshim.sync_block):
         self._rx.close()
 
 
-class _channel_rx(wifi_phy_rx):
-    """One channel of ``wifi_phy_rx_wideband``: a ``wifi_phy_rx`` whose PDUs leave on the owner's ports, with ``channel`` (and
-    on ``mac_out`` the ``freq`` it already carries: the channel's own centre) in their dictionaries."""
+class _sample_format:
+    """A block's input format: ``fmt`` (the WIFIRX_IQ_* value), ``scale`` (value = integer * scale; None: the format's
+    conventional one), the dtype ``item`` of one component, the block's ``in_sig`` and ``bps``, the bytes per sample."""
 
-    def __init__(self, owner, channel, **kw):
-        self._owner, self._channel = owner, int(channel)
+    def __init__(self, sample_format, sample_scale):
+        self.fmt = capi.iq_format(sample_format)
+        if self.fmt not in capi.IQ_DTYPE:
+            raise ValueError("sample_format must be 'fc32', 'sc16' or 'sc8'")
+        self.scale = float(capi.IQ_SCALE[self.fmt] if sample_scale is None else sample_scale)
+        self.item = capi.IQ_DTYPE[self.fmt]
+        self.in_sig = [np.complex64] if self.fmt == capi.IQ_FC32 else [(self.item.type, 2)]
+        self.bps = 8 if self.fmt == capi.IQ_FC32 else 2 * self.item.itemsize
+
+    def items(self, x):
+        """the scheduler's items as (contiguous bytes, number of samples)"""
+        if x.dtype != self.item or not x.flags.c_contiguous:
+            x = np.ascontiguousarray(x, dtype=self.item)
+        return x.reshape(-1).view(np.uint8), len(x)
+
+    def zeros(self, n):
+        return np.zeros(n * self.bps, np.uint8)
+
+
+class _hist_pair:
+    """The history of a stream of calls, in two device buffers of ``nbytes`` used in turn: a call reads ``cur`` (None in
+    front of a stream) and writes ``nxt``; ``advance()`` behind it."""
+
+    def __init__(self, rx, nbytes):
+        self._bufs = [rx.alloc(nbytes) for _ in range(2)]
+        self._cur = None                                            # index of the buffer that holds the history
+
+    @property
+    def cur(self):
+        return None if self._cur is None else self._bufs[self._cur].ptr
+
+    @property
+    def nxt(self):
+        return self._bufs[1 if self._cur == 0 else 0].ptr
+
+    def advance(self):
+        self._cur = 1 if self._cur == 0 else 0
+
+    def free(self):
+        for b in self._bufs:
+            b.free()
+        self._bufs = []
+
+
+class _channel_rx(wifi_phy_rx):
+    """A receive chain of ``_fed_rx``: a ``wifi_phy_rx`` whose PDUs leave on the owner's ports, with ``channel`` (and on
+    ``mac_out`` the ``freq`` it already carries: the channel's own centre) in their dictionaries; ``channel`` None: unchanged."""
+
+    def __init__(self, owner, channel=None, **kw):
+        self._owner, self._channel = owner, channel if channel is None else int(channel)
         wifi_phy_rx.__init__(self, **kw)
 
     def message_port_pub(self, port, msg):
-        meta, vec = grshim.to_python(msg)
-        meta = dict(meta or {})
-        meta["channel"] = self._channel
-        self._owner.message_port_pub(port, grshim.make_pdu(meta, vec) if grshim.HAVE_GNURADIO else (meta, vec))
+        if self._channel is not None:
+            meta, vec = grshim.to_python(msg)
+            meta = dict(meta or {})
+            meta["channel"] = self._channel
+            msg = grshim.make_pdu(meta, vec) if grshim.HAVE_GNURADIO else (meta, vec)
+        self._owner.message_port_pub(port, msg)
 
 
-class wifi_phy_rx_wideband(grshim.sync_block):
+class _fed_rx(grshim.sync_block):
+    """What ``wifi_phy_rx_wideband``, ``wifi_phy_rx_resampled`` and ``wifi_phy_rx_tuned`` share: a front stage on a handle
+    of its own, then K ``wifi_phy_rx`` chains, chain k fed row k of the front stage's output as device input.  A subclass
+    gives ``_front(raw, n)`` -> (device pointer of the rows, their stride in samples, samples per row), asynchronous on the
+    front stage's handle, ``_close_front()`` and, where its stream ends with a flush, ``_flush_zeros()``."""
+
+    def _build(self, name, sf, open_front, chains, **rx_kwargs):
+        """The block's signature and ports, then -- the first touch of the library -- ``open_front()`` -> the front stage's
+        handle, then one chain per dictionary of ``chains``; a failure closes what was built."""
+        grshim.sync_block.__init__(self, name=name, in_sig=sf.in_sig, out_sig=None)
+        self.message_port_register_out(grshim.intern("mac_out"))
+        self.message_port_register_out(grshim.intern("carrier"))
+        self._sf, self._rx = sf, []
+        self._push = capi.lib().wifirx_push
+        self.raise_on_error = True
+        try:
+            self._fh = open_front()
+            for kw in chains:
+                self._rx.append(_channel_rx(self, bandwidth=self.bandwidth, **kw, **rx_kwargs))
+        except Exception:
+            self.close()
+            raise
+
+    def _push_rows(self, ptr, stride, n):
+        for k, rx in enumerate(self._rx):
+            rc = self._push(rx._h, ptr + 8 * k * stride, n, 1)
+            if rc:
+                rx.push_errors += 1
+                rx.last_error = capi.lib().wifirx_last_error(rx._h).decode()
+                if self.raise_on_error:
+                    rx._rx._check(rc)
+            if rx._queued(rx._h):
+                rx._publish()
+
+    def _feed(self, raw, n):
+        ptr, stride, got = self._front(raw, n)
+        if got:
+            self._fh.sync()                                         # the rows are read on the chains' own streams
+            self._push_rows(ptr, stride, got)
+
+    def work(self, input_items, output_items):
+        raw, n = self._sf.items(input_items[0])
+        if n:
+            self._feed(raw, n)
+        return n
+
+    def _flush_zeros(self):
+        """the zero samples that end the front stage's stream"""
+        return 0
+
+    def stop(self):
+        """End of stream: the front stage's flush zeros, then every chain's pending frames."""
+        n = self._flush_zeros()
+        if n:
+            self._feed(self._sf.zeros(n), n)
+        for rx in self._rx:
+            rx.stop()
+        return True
+
+    @property
+    def frames_ok(self):
+        return sum(rx.frames_ok for rx in self._rx)
+
+    @property
+    def frames_dropped(self):
+        return sum(rx.frames_dropped for rx in self._rx)
+
+    def stats(self):
+        """the channels' wifirx_stats, channel 0 first"""
+        return [rx.stats() for rx in self._rx]
+
+    def close(self):
+        """Release the device buffers and every handle."""
+        self._close_front()
+        for rx in getattr(self, "_rx", []):
+            rx.close()
+        self._rx = []
+
+
+class wifi_phy_rx_wideband(_fed_rx):
     """``wifi_phy_rx`` for a front end that covers ``n_channels`` = 2, 4 or 8 adjacent channels in one stream: ``samp_in`` at
     ``n_channels * bandwidth``, split on the device by wifirx_channelize (NUMERICS.md rule 21) into ``n_channels`` streams
     that never leave it, each received by a ``wifi_phy_rx`` chain of its own.  ``stacking`` = 1: the channels' centres lie at
@@ -425,36 +550,22 @@ class wifi_phy_rx_wideband(grshim.sync_block):
             raise ValueError("n_channels must be 2, 4 or 8")
         if self.stacking not in (0, 1):
             raise ValueError("stacking must be 0 or 1")
-        self.sample_format = capi.iq_format(sample_format)
-        if self.sample_format not in capi.IQ_DTYPE:
-            raise ValueError("sample_format must be 'fc32', 'sc16' or 'sc8'")
-        self.sample_scale = float(capi.IQ_SCALE[self.sample_format] if sample_scale is None else sample_scale)
-        self._item = capi.IQ_DTYPE[self.sample_format]
-        in_sig = [np.complex64] if self.sample_format == capi.IQ_FC32 else [(self._item.type, 2)]
-        grshim.sync_block.__init__(self, name="wifi_phy_rx_wideband", in_sig=in_sig, out_sig=None)
+        sf = _sample_format(sample_format, sample_scale)
+        self.sample_format, self.sample_scale = sf.fmt, sf.scale
         self.bandwidth, self.center_frequency = float(bandwidth), float(center_frequency)
         M = self.n_channels
         self.frequencies = [self.center_frequency + capi.channel_centre(k, M, self.stacking) * M * self.bandwidth for k in range(M)]
-        self.message_port_register_out(grshim.intern("mac_out"))
-        self.message_port_register_out(grshim.intern("carrier"))
-        self._bps = 8 if self.sample_format == capi.IQ_FC32 else 2 * self._item.itemsize        # bytes per sample
-        self._cz = capi.WifiRx(max_sym=1, device=device)           # the channelising handle: its receive side stays unused
-        self._rx = []
-        try:
-            for k in range(M):
-                self._rx.append(_channel_rx(self, k, bandwidth=self.bandwidth, frequency=self.frequencies[k], device=device,
-                                            **rx_kwargs))
-        except Exception:
-            self.close()
-            raise
         self._rem = np.zeros(0, dtype=np.uint8)                     # bytes of the fewer than M samples not yet channelised
         self._m0 = 0                                                # stream index of the next output
-        self._hist = [self._cz.alloc(capi.CHANNELIZER_HIST * M * self._bps) for _ in range(2)]
-        self._hist_cur = None                                       # index of the buffer that holds the history; None: a new stream
-        self._d_in = self._d_out = None
+        self._cz = self._hist = self._d_in = self._d_out = None
         self._cap = 0                                               # outputs per channel the two buffers hold
-        self._push = capi.lib().wifirx_push
-        self.raise_on_error = True
+        self._build("wifi_phy_rx_wideband", sf, lambda: self._open(device),
+                    [dict(channel=k, frequency=f) for k, f in enumerate(self.frequencies)], device=device, **rx_kwargs)
+
+    def _open(self, device):
+        self._cz = capi.WifiRx(max_sym=1, device=device)           # the channelising handle: its receive side stays unused
+        self._hist = _hist_pair(self._cz, capi.CHANNELIZER_HIST * self.n_channels * self._sf.bps)
+        return self._cz
 
     def _reserve(self, n_out):
         if n_out <= self._cap:
@@ -464,74 +575,34 @@ class wifi_phy_rx_wideband(grshim.sync_block):
                 b.free()
         M = self.n_channels
         self._cap = (n_out + n_out // 2 + 1) & ~1                   # even: every row starts on 16 bytes
-        self._d_in = self._cz.alloc((self._cap + 1) * M * self._bps)
+        self._d_in = self._cz.alloc((self._cap + 1) * M * self._sf.bps)
         self._d_out = self._cz.alloc(self._cap * M * 8)
 
-    def work(self, input_items, output_items):
-        x = input_items[0]
-        n = len(x)
-        if n == 0:
-            return 0
-        if x.dtype != self._item or not x.flags.c_contiguous:
-            x = np.ascontiguousarray(x, dtype=self._item)
-        M, bps = self.n_channels, self._bps
-        raw = x.reshape(-1).view(np.uint8)
+    def _front(self, raw, n):
+        M, bps = self.n_channels, self._sf.bps
         n_rem = self._rem.size // bps
         n_out = (n_rem + n) // M
         if n_out == 0:
             self._rem = np.concatenate([self._rem, raw])
-            return n
+            return None, 0, 0
         self._reserve(n_out)
         cz, d_in = self._cz, self._d_in
         if n_rem:
             d_in.upload(self._rem)
-        used = (n_out * M - n_rem) * bps                            # bytes of x this call channelises
+        used = (n_out * M - n_rem) * bps                            # bytes of the items this call channelises
         cz._check(capi.lib().wifirx_memcpy_h2d(cz._h, d_in.ptr + n_rem * bps, raw.ctypes.data, used))
-        nxt = 1 if self._hist_cur == 0 else 0
-        cz.channelize_dev(d_in.ptr, self.sample_format, n_out, M, self.stacking, self._d_out.ptr, self._cap,
-                          hist_ptr=None if self._hist_cur is None else self._hist[self._hist_cur].ptr,
-                          hist_out_ptr=self._hist[nxt].ptr, m0=self._m0, scale=self.sample_scale)
-        cz.sync()                                                   # the rows are read on the channels' own streams
-        self._hist_cur, self._m0 = nxt, self._m0 + n_out
-        self._rem = raw[used:].copy()
-        for k, rx in enumerate(self._rx):
-            rc = self._push(rx._h, self._d_out.ptr + 8 * k * self._cap, n_out, 1)
-            if rc:
-                rx.push_errors += 1
-                rx.last_error = capi.lib().wifirx_last_error(rx._h).decode()
-                if self.raise_on_error:
-                    rx._rx._check(rc)
-            if rx._queued(rx._h):
-                rx._publish()
-        return n
+        cz.channelize_dev(d_in.ptr, self._sf.fmt, n_out, M, self.stacking, self._d_out.ptr, self._cap, hist_ptr=self._hist.cur,
+                          hist_out_ptr=self._hist.nxt, m0=self._m0, scale=self._sf.scale)
+        self._hist.advance()
+        self._m0 += n_out
+        self._rem = raw[used:].copy()                               # (the fewer than n_channels samples left over make no output)
+        return self._d_out.ptr, self._cap, n_out
 
-    def stop(self):
-        """End of stream: settle every channel's pending frames.  The fewer than n_channels samples left over make no output."""
-        for rx in self._rx:
-            rx.stop()
-        return True
-
-    @property
-    def frames_ok(self):
-        return sum(rx.frames_ok for rx in self._rx)
-
-    @property
-    def frames_dropped(self):
-        return sum(rx.frames_dropped for rx in self._rx)
-
-    def stats(self):
-        """the channels' wifirx_stats, channel 0 first"""
-        return [rx.stats() for rx in self._rx]
-
-    def close(self):
-        """Release the device buffers and every handle."""
-        for b in list(getattr(self, "_hist", [])) + [getattr(self, "_d_in", None), getattr(self, "_d_out", None)]:
+    def _close_front(self):
+        for b in (getattr(self, "_hist", None), getattr(self, "_d_in", None), getattr(self, "_d_out", None)):
             if b is not None:
                 b.free()
-        self._hist, self._d_in, self._d_out, self._cap = [], None, None, 0
-        for rx in getattr(self, "_rx", []):
-            rx.close()
-        self._rx = []
+        self._hist, self._d_in, self._d_out, self._cap = None, None, None, 0
         if getattr(self, "_cz", None) is not None:
             self._cz.close()
             self._cz = None
@@ -542,21 +613,14 @@ class _arb_stream:
     m0 of wifirx_arb_resample (NUMERICS.md rule 34), the two history buffers used in turn, and the device buffers of a call.
     With ``incs`` the call is wifirx_tune (rule 35) and the output holds one row of ``cap_out`` samples per increment."""
 
-    def __init__(self, rate_in, rate_out, sample_format, sample_scale, device, incs=None):
+    def __init__(self, rate_in, rate_out, sf, device, incs=None):
         self.incs = None if incs is None else [int(v) for v in incs]   # wifirx_tune's increments: one output row per channel
-        self.fmt = capi.iq_format(sample_format)
-        if self.fmt not in capi.IQ_DTYPE:
-            raise ValueError("sample_format must be 'fc32', 'sc16' or 'sc8'")
-        self.scale = float(capi.IQ_SCALE[self.fmt] if sample_scale is None else sample_scale)
-        self.item = capi.IQ_DTYPE[self.fmt]
-        self.in_sig = [np.complex64] if self.fmt == capi.IQ_FC32 else [(self.item.type, 2)]
-        self.bps = 8 if self.fmt == capi.IQ_FC32 else 2 * self.item.itemsize             # bytes per sample
+        self.sf = sf
         self.num, self.den = capi.arb_ratio(rate_in, rate_out)
         self.S = max(self.num, self.den)
         self.rx = capi.WifiRx(max_sym=1, device=device)            # the resampling handle: its receive side stays unused
         self.j0 = self.m0 = 0                                       # stream indices of the next input and the next output
-        self.hist = [self.rx.alloc(capi.arb_hist(self.num, self.den) * self.bps) for _ in range(2)]
-        self.hist_cur = None                                        # index of the buffer that holds the history; None: a new stream
+        self.hist = _hist_pair(self.rx, capi.arb_hist(self.num, self.den) * sf.bps)
         self.d_in = self.d_out = None
         self.cap_in = self.cap_out = 0
 
@@ -575,39 +639,29 @@ class _arb_stream:
             if self.d_in is not None:
                 self.d_in.free()
             self.cap_in = n + n // 2
-            self.d_in = self.rx.alloc(self.cap_in * self.bps)
+            self.d_in = self.rx.alloc(self.cap_in * self.sf.bps)
         if n_out > self.cap_out:
             if self.d_out is not None:
                 self.d_out.free()
             self.cap_out = (n_out + n_out // 2 + 1) & ~1            # even: every row starts on 16 bytes
             self.d_out = self.rx.alloc(self.cap_out * 8 * (1 if self.incs is None else len(self.incs)))
         rx = self.rx
-        rx._check(capi.lib().wifirx_memcpy_h2d(rx._h, self.d_in.ptr, raw.ctypes.data, n * self.bps))
-        nxt = 1 if self.hist_cur == 0 else 0
-        hist = dict(hist_ptr=None if self.hist_cur is None else self.hist[self.hist_cur].ptr, hist_out_ptr=self.hist[nxt].ptr,
-                    j0=self.j0, m0=self.m0, scale=self.scale)
+        rx._check(capi.lib().wifirx_memcpy_h2d(rx._h, self.d_in.ptr, raw.ctypes.data, n * self.sf.bps))
+        hist = dict(hist_ptr=self.hist.cur, hist_out_ptr=self.hist.nxt, j0=self.j0, m0=self.m0, scale=self.sf.scale)
         out = None if n_out == 0 else self.d_out.ptr
         if self.incs is None:
-            got = rx.arb_resample_dev(self.d_in.ptr, self.fmt, n, self.num, self.den, out, self.cap_out, **hist)
+            got = rx.arb_resample_dev(self.d_in.ptr, self.sf.fmt, n, self.num, self.den, out, self.cap_out, **hist)
         else:
-            got = rx.tune_dev(self.d_in.ptr, self.fmt, n, self.num, self.den, self.incs, out, self.cap_out, **hist)
-        self.hist_cur, self.j0, self.m0 = nxt, self.j0 + n, self.m0 + got
+            got = rx.tune_dev(self.d_in.ptr, self.sf.fmt, n, self.num, self.den, self.incs, out, self.cap_out, **hist)
+        self.hist.advance()
+        self.j0, self.m0 = self.j0 + n, self.m0 + got
         return (self.d_out.ptr if got else None), got
 
-    def items(self, x):
-        """the scheduler's items as (contiguous bytes, number of samples)"""
-        if x.dtype != self.item or not x.flags.c_contiguous:
-            x = np.ascontiguousarray(x, dtype=self.item)
-        return x.reshape(-1).view(np.uint8), len(x)
-
-    def zeros(self, n):
-        return np.zeros(n * self.bps, np.uint8)
-
     def close(self):
-        for b in list(self.hist) + [self.d_in, self.d_out]:
+        for b in (self.hist, self.d_in, self.d_out):
             if b is not None:
                 b.free()
-        self.hist, self.d_in, self.d_out, self.cap_in, self.cap_out = [], None, None, 0, 0
+        self.hist, self.d_in, self.d_out, self.cap_in, self.cap_out = None, None, None, 0, 0
         if self.rx is not None:
             self.rx.close()
             self.rx = None
@@ -627,8 +681,9 @@ class arb_resampler(grshim.basic_block):
     leaves the outputs in ``tail``."""
 
     def __init__(self, rate_in, rate_out, sample_format="fc32", sample_scale=None, device=0):
-        self._s = _arb_stream(rate_in, rate_out, sample_format, sample_scale, device)
-        grshim.basic_block.__init__(self, name="arb_resampler", in_sig=self._s.in_sig, out_sig=[np.complex64])
+        sf = _sample_format(sample_format, sample_scale)
+        self._s = _arb_stream(rate_in, rate_out, sf, device)
+        grshim.basic_block.__init__(self, name="arb_resampler", in_sig=sf.in_sig, out_sig=[np.complex64])
         self.num, self.den = self._s.num, self._s.den
         self.consumed = 0
         self.tail = np.zeros(0, np.complex64)
@@ -638,14 +693,14 @@ class arb_resampler(grshim.basic_block):
 
     def general_work(self, input_items, output_items):
         s, out = self._s, output_items[0]
-        raw, n = s.items(input_items[0])
+        raw, n = s.sf.items(input_items[0])
         n = min(n, s.room(len(out)))
         self.consumed = n
         if hasattr(self, "consume"):                 # gr.basic_block's; the shim's caller reads `consumed`
             self.consume(0, n)
         if n == 0:
             return 0
-        ptr, got = s.run(raw[:n * s.bps], n)
+        ptr, got = s.run(raw[:n * s.sf.bps], n)
         if got:
             y = np.empty(got, np.complex64)
             s.rx._check(capi.lib().wifirx_memcpy_d2h(s.rx._h, y.ctypes.data, ptr, 8 * got))     # ordered behind the kernel
@@ -660,7 +715,7 @@ class arb_resampler(grshim.basic_block):
         if s.rx is None or s.j0 == 0:
             return True
         n = s.flush_inputs()
-        ptr, got = s.run(s.zeros(n), n)
+        ptr, got = s.run(s.sf.zeros(n), n)
         self.tail = np.zeros(0, np.complex64)
         if got:
             self.tail = np.empty(got, np.complex64)
@@ -672,18 +727,27 @@ class arb_resampler(grshim.basic_block):
         self._s.close()
 
 
-class _forward_rx(wifi_phy_rx):
-    """The receive chain of ``wifi_phy_rx_resampled``: a ``wifi_phy_rx`` whose PDUs leave on the owner's ports, unchanged."""
+class _arb_fed_rx(_fed_rx):
+    """``_fed_rx`` behind an ``_arb_stream``: the front stage of ``wifi_phy_rx_resampled`` and ``wifi_phy_rx_tuned``"""
 
-    def __init__(self, owner, **kw):
-        self._owner = owner
-        wifi_phy_rx.__init__(self, **kw)
+    def _open(self, sample_rate, device, incs=None):
+        self._s = _arb_stream(sample_rate, self.bandwidth, self._sf, device, incs=incs)
+        self.num, self.den = self._s.num, self._s.den
+        return self._s.rx
 
-    def message_port_pub(self, port, msg):
-        self._owner.message_port_pub(port, msg)
+    def _front(self, raw, n):
+        ptr, got = self._s.run(raw, n)
+        return ptr, self._s.cap_out, got
+
+    def _flush_zeros(self):
+        return self._s.flush_inputs() if self._s.j0 else 0
+
+    def _close_front(self):
+        if getattr(self, "_s", None) is not None:
+            self._s.close()
 
 
-class wifi_phy_rx_resampled(grshim.sync_block):
+class wifi_phy_rx_resampled(_arb_fed_rx):
     """``wifi_phy_rx`` for a capture that does not run at the channel rate: ``samp_in`` at ``sample_rate`` Hz (25, 30.72, 40,
     50, 61.44, 80 MS/s ...; ``sample_format`` / ``sample_scale`` as ``wifi_phy_rx``), brought to ``bandwidth`` on the device
     by wifirx_arb_resample (NUMERICS.md rule 34) and received there by one ``wifi_phy_rx`` chain, which takes every other
@@ -696,72 +760,15 @@ class wifi_phy_rx_resampled(grshim.sync_block):
     ceil(16 S / den) zeros that bring out the stream's last instants, then settles the chain."""
 
     def __init__(self, sample_rate, bandwidth=20e6, sample_format="fc32", sample_scale=None, device=0, **rx_kwargs):
-        self._s = None
-        self._s = _arb_stream(sample_rate, bandwidth, sample_format, sample_scale, device)
-        grshim.sync_block.__init__(self, name="wifi_phy_rx_resampled", in_sig=self._s.in_sig, out_sig=None)
         self.sample_rate, self.bandwidth = float(sample_rate), float(bandwidth)
-        self.num, self.den = self._s.num, self._s.den
-        self.message_port_register_out(grshim.intern("mac_out"))
-        self.message_port_register_out(grshim.intern("carrier"))
-        self._rx = None
-        try:
-            self._rx = _forward_rx(self, bandwidth=self.bandwidth, device=device, **rx_kwargs)
-        except Exception:
-            self.close()
-            raise
-        self._push = capi.lib().wifirx_push
-        self.raise_on_error = True
-
-    def _feed(self, raw, n):
-        s, rx = self._s, self._rx
-        ptr, got = s.run(raw, n)
-        if not got:
-            return
-        s.rx.sync()                                                 # the output is read on the chain's own stream
-        rc = self._push(rx._h, ptr, got, 1)
-        if rc:
-            rx.push_errors += 1
-            rx.last_error = capi.lib().wifirx_last_error(rx._h).decode()
-            if self.raise_on_error:
-                rx._rx._check(rc)
-        if rx._queued(rx._h):
-            rx._publish()
-
-    def work(self, input_items, output_items):
-        raw, n = self._s.items(input_items[0])
-        if n:
-            self._feed(raw, n)
-        return n
-
-    def stop(self):
-        """End of stream: the flush zeros, then the chain's pending frames."""
-        if self._s.j0:
-            n = self._s.flush_inputs()
-            self._feed(self._s.zeros(n), n)
-        self._rx.stop()
-        return True
-
-    @property
-    def frames_ok(self):
-        return self._rx.frames_ok
-
-    @property
-    def frames_dropped(self):
-        return self._rx.frames_dropped
+        self._build("wifi_phy_rx_resampled", _sample_format(sample_format, sample_scale), lambda: self._open(sample_rate, device),
+                    [{}], device=device, **rx_kwargs)
 
     def stats(self):
-        return self._rx.stats()
-
-    def close(self):
-        """Release the device buffers and both handles."""
-        if getattr(self, "_s", None) is not None:
-            self._s.close()
-        if getattr(self, "_rx", None) is not None:
-            self._rx.close()
-            self._rx = None
+        return self._rx[0].stats()
 
 
-class wifi_phy_rx_tuned(grshim.sync_block):
+class wifi_phy_rx_tuned(_arb_fed_rx):
     """``wifi_phy_rx`` for K <= 8 channels that lie anywhere in one capture: ``samp_in`` at ``sample_rate`` Hz around
     ``center_frequency`` (``sample_format`` / ``sample_scale`` as ``wifi_phy_rx``), channel k centred ``offsets[k]`` Hz above
     it -- channels 1 / 6 / 11 of the 2.4 GHz band at -25, 0 and +25 MHz of an 80 MS/s capture around 2437 MHz, which no
@@ -782,7 +789,6 @@ class wifi_phy_rx_tuned(grshim.sync_block):
 
     def __init__(self, sample_rate, offsets=(-25e6, 0.0, 25e6), center_frequency=2.437e9, bandwidth=20e6, sample_format="fc32",
                  sample_scale=None, device=0, **rx_kwargs):
-        self._s, self._rx = None, []
         self.sample_rate, self.bandwidth, self.center_frequency = float(sample_rate), float(bandwidth), float(center_frequency)
         self.offsets = [float(v) for v in offsets]
         if not 1 <= len(self.offsets) <= capi.TUNE_MAX_CHANNELS:
@@ -793,70 +799,9 @@ class wifi_phy_rx_tuned(grshim.sync_block):
                                  "would alias" % (off, abs(off) + self.bandwidth / 2, self.sample_rate / 2))
         self.frequencies = [self.center_frequency + off for off in self.offsets]
         self.incs = [capi.tune_inc(off, self.sample_rate) for off in self.offsets]
-        self._s = _arb_stream(self.sample_rate, self.bandwidth, sample_format, sample_scale, device, incs=self.incs)
-        grshim.sync_block.__init__(self, name="wifi_phy_rx_tuned", in_sig=self._s.in_sig, out_sig=None)
-        self.num, self.den = self._s.num, self._s.den
-        self.message_port_register_out(grshim.intern("mac_out"))
-        self.message_port_register_out(grshim.intern("carrier"))
-        try:
-            for k, f in enumerate(self.frequencies):
-                self._rx.append(_channel_rx(self, k, bandwidth=self.bandwidth, frequency=f, device=device, **rx_kwargs))
-        except Exception:
-            self.close()
-            raise
-        self._push = capi.lib().wifirx_push
-        self.raise_on_error = True
-
-    def _feed(self, raw, n):
-        s = self._s
-        ptr, got = s.run(raw, n)
-        if not got:
-            return
-        s.rx.sync()                                                 # the rows are read on the chains' own streams
-        for k, rx in enumerate(self._rx):
-            rc = self._push(rx._h, ptr + 8 * k * s.cap_out, got, 1)
-            if rc:
-                rx.push_errors += 1
-                rx.last_error = capi.lib().wifirx_last_error(rx._h).decode()
-                if self.raise_on_error:
-                    rx._rx._check(rc)
-            if rx._queued(rx._h):
-                rx._publish()
-
-    def work(self, input_items, output_items):
-        raw, n = self._s.items(input_items[0])
-        if n:
-            self._feed(raw, n)
-        return n
-
-    def stop(self):
-        """End of stream: the flush zeros, then every chain's pending frames."""
-        if self._s.j0:
-            n = self._s.flush_inputs()
-            self._feed(self._s.zeros(n), n)
-        for rx in self._rx:
-            rx.stop()
-        return True
-
-    @property
-    def frames_ok(self):
-        return sum(rx.frames_ok for rx in self._rx)
-
-    @property
-    def frames_dropped(self):
-        return sum(rx.frames_dropped for rx in self._rx)
-
-    def stats(self):
-        """the channels' wifirx_stats, channel 0 first"""
-        return [rx.stats() for rx in self._rx]
-
-    def close(self):
-        """Release the device buffers and every handle."""
-        if getattr(self, "_s", None) is not None:
-            self._s.close()
-        for rx in getattr(self, "_rx", []):
-            rx.close()
-        self._rx = []
+        self._build("wifi_phy_rx_tuned", _sample_format(sample_format, sample_scale),
+                    lambda: self._open(self.sample_rate, device, incs=self.incs),
+                    [dict(channel=k, frequency=f) for k, f in enumerate(self.frequencies)], device=device, **rx_kwargs)
 
 
 class wifi_phy_tx(grshim.sync_block):
@@ -1285,8 +1230,7 @@ class wideband_combiner(grshim.sync_interpolator):
         self.set_gains(gains)
         self._rx = capi.WifiRx(max_sym=1, device=device)           # the handle's receive side stays unused
         self._m0 = 0                                                # stream index of the next input sample
-        self._hist = [self._rx.alloc(capi.CHANNELIZER_HIST * M * 8) for _ in range(2)]
-        self._hist_cur = None                                       # index of the buffer that holds the history; None: a new stream
+        self._hist = _hist_pair(self._rx, capi.CHANNELIZER_HIST * M * 8)
         self._d_in = self._d_out = None
         self._cap = 0                                               # samples per channel the two buffers hold
 
@@ -1318,20 +1262,19 @@ class wideband_combiner(grshim.sync_interpolator):
         for k in range(M):
             x = np.ascontiguousarray(input_items[k][:n], dtype=np.complex64)
             rx._check(capi.lib().wifirx_memcpy_h2d(rx._h, self._d_in.ptr + 8 * k * self._cap, x.ctypes.data, 8 * n))
-        nxt = 1 if self._hist_cur == 0 else 0
         rx.combine_dev(self._d_in.ptr, self._cap, n, M, self.stacking, self._d_out.ptr, gains=self.gains,
-                       hist_ptr=None if self._hist_cur is None else self._hist[self._hist_cur].ptr,
-                       hist_out_ptr=self._hist[nxt].ptr, m0=self._m0)
+                       hist_ptr=self._hist.cur, hist_out_ptr=self._hist.nxt, m0=self._m0)
         out[:n * M] = self._d_out.download(np.complex64, n * M)    # ordered behind the kernel on the handle's stream
-        self._hist_cur, self._m0 = nxt, self._m0 + n
+        self._hist.advance()
+        self._m0 += n
         return n * M
 
     def close(self):
         """Release the device buffers and the handle."""
-        for b in list(getattr(self, "_hist", [])) + [getattr(self, "_d_in", None), getattr(self, "_d_out", None)]:
+        for b in (getattr(self, "_hist", None), getattr(self, "_d_in", None), getattr(self, "_d_out", None)):
             if b is not None:
                 b.free()
-        self._hist, self._d_in, self._d_out, self._cap = [], None, None, 0
+        self._hist, self._d_in, self._d_out, self._cap = None, None, None, 0
         if getattr(self, "_rx", None) is not None:
             self._rx.close()
             self._rx = None

@@ -411,6 +411,12 @@ def iq_format(fmt) -> int:
     return int(fmt)
 
 
+def _fmt_scale(fmt, scale):
+    """(the WIFIRX_IQ_* value of fmt, scale as a float: None is the format's conventional widening scale, 1 for "fc32")"""
+    fmt = iq_format(fmt)
+    return fmt, float(IQ_SCALE.get(fmt, 1.0) if scale is None else scale)
+
+
 def _np_ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -1288,9 +1294,8 @@ class WifiRx:
     def iq_to_f32_dev(self, src_ptr, fmt, n, dst_ptr, scale=None):
         """wifirx_iq_to_f32 on device pointers: n samples of `fmt` at src_ptr -> complex64 at dst_ptr.  Asynchronous on the
         handle's stream."""
-        fmt = iq_format(fmt)
-        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
-        self._check(_lib.wifirx_iq_to_f32(self._h, src_ptr, fmt, int(n), float(scale), dst_ptr))
+        fmt, scale = _fmt_scale(fmt, scale)
+        self._check(_lib.wifirx_iq_to_f32(self._h, src_ptr, fmt, int(n), scale, dst_ptr))
 
     def iq_from_f32_dev(self, src_ptr, n, fmt, dst_ptr, scale=None, bits=None, count=False):
         """wifirx_iq_from_f32 on device pointers: n complex64 samples at src_ptr -> samples of `fmt` at dst_ptr, quantised to
@@ -1320,6 +1325,17 @@ class WifiRx:
                 raise ValueError("integer samples come as [n, 2] or flat [2 n]")
         x = np.ascontiguousarray(x).reshape(-1)
         return x, fmt, x.size // 2 if fmt in IQ_MAX_BITS else x.size
+
+    @classmethod
+    def _host_samples(cls, x, fmt=None):
+        """complex samples (fmt None or "fc32") or int16 / int8 samples (_iq_array) -> (contiguous flat array, format, n)"""
+        x = np.asarray(x)
+        if fmt is None and x.dtype not in (np.dtype(np.int16), np.dtype(np.int8)):
+            fmt = IQ_FC32
+        if fmt is not None and iq_format(fmt) == IQ_FC32:
+            x = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1)
+            return x, IQ_FC32, x.size
+        return cls._iq_array(x, fmt)
 
     def iq_to_f32(self, q, fmt=None, scale=None) -> np.ndarray:
         """iq_to_f32_dev on a NumPy array of int16 / int8 samples ([n, 2] or flat [2 n]): returns complex64 [n]"""
@@ -1352,23 +1368,15 @@ class WifiRx:
         """wifirx_frontend on device pointers: n samples of `fmt` at in_ptr -> corrected complex64 at out_ptr, the
         wifirx_frontend_state at state_ptr advanced.  in_ptr == out_ptr is allowed for "fc32".  Asynchronous on the handle's
         stream."""
-        fmt = iq_format(fmt)
-        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
-        self._check(_lib.wifirx_frontend(self._h, C.byref(cfg), state_ptr, in_ptr, fmt, float(scale), int(n), out_ptr))
+        fmt, scale = _fmt_scale(fmt, scale)
+        self._check(_lib.wifirx_frontend(self._h, C.byref(cfg), state_ptr, in_ptr, fmt, scale, int(n), out_ptr))
 
     def frontend(self, x, cfg=None, state=None, fmt=None, scale=None):
         """frontend_dev on host arrays: complex64 samples (fmt None or "fc32") or int16 / int8 samples ([n, 2] or flat [2 n]);
         cfg None: frontend_cfg(); state None: a fresh stream.  Returns (complex64 [n], the state behind the call as a
         FE_STATE_DTYPE record), which continues the stream when it is handed in again."""
         cfg = frontend_cfg() if cfg is None else cfg
-        x = np.asarray(x)
-        if fmt is None and x.dtype not in (np.dtype(np.int16), np.dtype(np.int8)):
-            fmt = IQ_FC32
-        if fmt is not None and iq_format(fmt) == IQ_FC32:
-            x, fmt = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1), IQ_FC32
-            n = x.size
-        else:
-            x, fmt, n = self._iq_array(x, fmt)
+        x, fmt, n = self._host_samples(x, fmt)
         st = _fe_state_array(state)
         d_in, d_out, d_st = self.alloc(max(x.nbytes, 1)), self.alloc(max(n, 1) * 8), self.alloc(FE_STATE_DTYPE.itemsize)
         try:
@@ -1421,9 +1429,8 @@ class WifiRx:
         complex64 at out_ptr, row k at out_ptr + 8 * k * out_stride bytes (out_stride None: n_out).  hist_ptr: the
         23 * n_channels samples in front (None: zeros); hist_out_ptr: where the next call's hist goes (None: nowhere).
         Asynchronous on the handle's stream: sync() before another handle reads the rows."""
-        fmt = iq_format(fmt)
-        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
-        self._check(_lib.wifirx_channelize(self._h, in_ptr, fmt, float(scale), hist_ptr, hist_out_ptr, int(n_channels),
+        fmt, scale = _fmt_scale(fmt, scale)
+        self._check(_lib.wifirx_channelize(self._h, in_ptr, fmt, scale, hist_ptr, hist_out_ptr, int(n_channels),
                                            int(stacking), int(n_out), int(m0) & 0xFFFFFFFFFFFFFFFF, out_ptr,
                                            int(n_out if out_stride is None else out_stride)))
 
@@ -1466,10 +1473,9 @@ class WifiRx:
         outputs m0 .. as complex64 at out_ptr (room for out_cap).  hist_ptr: the arb_hist(num, den) samples in front (None:
         zeros); hist_out_ptr: where the next call's hist goes (None: nowhere).  Returns n_out.  Asynchronous on the handle's
         stream: sync() before another handle reads the output."""
-        fmt = iq_format(fmt)
-        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
+        fmt, scale = _fmt_scale(fmt, scale)
         n = C.c_uint64(0)
-        self._check(_lib.wifirx_arb_resample(self._h, in_ptr, fmt, float(scale), int(n_in), hist_ptr, hist_out_ptr, int(num),
+        self._check(_lib.wifirx_arb_resample(self._h, in_ptr, fmt, scale, int(n_in), hist_ptr, hist_out_ptr, int(num),
                                              int(den), int(j0), int(m0), out_ptr, int(out_cap), C.byref(n)))
         return int(n.value)
 
@@ -1477,25 +1483,24 @@ class WifiRx:
         """arb_resample_dev on host arrays, a whole stream from j0 = m0 = 0: complex64 samples (fmt None or "fc32") or int16 /
         int8 samples ([n, 2] or flat [2 n]) -> complex64.  n_out: append the zeros of the end-of-stream flush and return
         exactly that many outputs (None: what the samples alone give)."""
-        x = np.asarray(x)
-        if fmt is None and x.dtype not in (np.dtype(np.int16), np.dtype(np.int8)):
-            fmt = IQ_FC32
-        if fmt is not None and iq_format(fmt) == IQ_FC32:
-            x, fmt = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1), IQ_FC32
-            n = x.size
-        else:
-            x, fmt, n = self._iq_array(x, fmt)
+        return self._arb_host(x, num, den, fmt, n_out, 1, lambda src, fmt, n, dst, made: self.arb_resample_dev(
+            src, fmt, n, num, den, dst, made, scale=scale))[0]
+
+    def _arb_host(self, x, num, den, fmt, n_out, K, call_dev) -> np.ndarray:
+        """what arb_resample and tune do around their call: the samples (_host_samples) and the zeros of the flush up,
+        call_dev(in_ptr, fmt, n_in, out_ptr, row length) -> n_out per row, the K rows down, cut to n_out"""
+        x, fmt, n = self._host_samples(x, fmt)
         if n_out is not None:
             pad = arb_flush_inputs(num, den, n, n_out)
             x = np.concatenate([x, np.zeros(pad * (1 if fmt == IQ_FC32 else 2), x.dtype)])
             n += pad
         made = arb_count(num, den, 0, n, 0)
-        d_in, d_out = self.alloc(max(x.nbytes, 1)), self.alloc(max(made, 1) * 8)
+        d_in, d_out = self.alloc(max(x.nbytes, 1)), self.alloc(max(made * K, 1) * 8)
         try:
             d_in.upload(x)
-            got = self.arb_resample_dev(d_in.ptr, fmt, n, num, den, d_out.ptr, made, scale=scale)
-            y = d_out.download(np.complex64, got)            # ordered behind the kernel on the handle's stream
-            return y if n_out is None else y[:n_out]
+            got = call_dev(d_in.ptr, fmt, n, d_out.ptr, made)
+            y = d_out.download(np.complex64, got * K).reshape(K, got)       # ordered behind the kernel on the handle's stream
+            return y if n_out is None else y[:, :n_out]
         finally:
             d_in.free()
             d_out.free()
@@ -1507,8 +1512,7 @@ class WifiRx:
         outputs m0 .. as complex64 at out_ptr + 8 * k * out_stride.  incs: one uint64 increment per channel (tune_inc);
         phase0s: the phases of stream sample 0 (None: zeros).  hist_ptr / hist_out_ptr as arb_resample_dev: raw input
         samples.  Returns n_out per channel.  Asynchronous on the handle's stream: sync() before another handle reads a row."""
-        fmt = iq_format(fmt)
-        scale = IQ_SCALE.get(fmt, 1.0) if scale is None else scale
+        fmt, scale = _fmt_scale(fmt, scale)
         K = len(incs)
         inc = (C.c_uint64 * max(K, 1))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in incs])
         ph = None
@@ -1517,7 +1521,7 @@ class WifiRx:
                 raise ValueError("one phase0 per channel is required")
             ph = (C.c_uint64 * max(K, 1))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in phase0s])
         n = C.c_uint64(0)
-        self._check(_lib.wifirx_tune(self._h, in_ptr, fmt, float(scale), int(n_in), hist_ptr, hist_out_ptr, int(num), int(den), K,
+        self._check(_lib.wifirx_tune(self._h, in_ptr, fmt, scale, int(n_in), hist_ptr, hist_out_ptr, int(num), int(den), K,
                                      inc, ph, int(j0), int(m0), out_ptr, int(out_stride), C.byref(n)))
         return int(n.value)
 
@@ -1525,29 +1529,8 @@ class WifiRx:
         """tune_dev on host arrays, a whole stream from j0 = m0 = 0: complex64 samples (fmt None or "fc32") or int16 / int8
         samples ([n, 2] or flat [2 n]) -> complex64 [K, n_out].  n_out: append the zeros of the end-of-stream flush and return
         exactly that many outputs per channel (None: what the samples alone give)."""
-        x = np.asarray(x)
-        if fmt is None and x.dtype not in (np.dtype(np.int16), np.dtype(np.int8)):
-            fmt = IQ_FC32
-        if fmt is not None and iq_format(fmt) == IQ_FC32:
-            x, fmt = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1), IQ_FC32
-            n = x.size
-        else:
-            x, fmt, n = self._iq_array(x, fmt)
-        if n_out is not None:
-            pad = arb_flush_inputs(num, den, n, n_out)
-            x = np.concatenate([x, np.zeros(pad * (1 if fmt == IQ_FC32 else 2), x.dtype)])
-            n += pad
-        K = len(incs)
-        made = arb_count(num, den, 0, n, 0)
-        d_in, d_out = self.alloc(max(x.nbytes, 1)), self.alloc(max(made * K, 1) * 8)
-        try:
-            d_in.upload(x)
-            got = self.tune_dev(d_in.ptr, fmt, n, num, den, incs, d_out.ptr, made, phase0s=phase0s, scale=scale)
-            y = d_out.download(np.complex64, got * K).reshape(K, got)       # ordered behind the kernel on the handle's stream
-            return y if n_out is None else y[:, :n_out]
-        finally:
-            d_in.free()
-            d_out.free()
+        return self._arb_host(x, num, den, fmt, n_out, len(incs), lambda src, fmt, n, dst, made: self.tune_dev(
+            src, fmt, n, num, den, incs, dst, made, phase0s=phase0s, scale=scale))
 
     # -- receive diversity (wifirx_diversity_combine; NUMERICS.md rule 23) --
     def diversity_combine_dev(self, ins, n_slots, out, mode=DIV_MRC, ant_gain=None, used_mask_ptr=None):
@@ -1681,12 +1664,11 @@ class WifiRx:
             self._check(_lib.wifirx_push_iq(self._h, _np_ptr(x), x.size, IQ_FC32, float(1.0 if scale is None else scale), 0))
             return
         x, fmt, n = self._iq_array(x, fmt)
-        self._check(_lib.wifirx_push_iq(self._h, _np_ptr(x), n, fmt, float(IQ_SCALE.get(fmt, 1.0) if scale is None else scale), 0))
+        self._check(_lib.wifirx_push_iq(self._h, _np_ptr(x), n, *_fmt_scale(fmt, scale), 0))
 
     def push_iq_dev(self, ptr, n, fmt, scale=None):
         """wifirx_push_iq on n samples of `fmt` in device memory at ptr"""
-        fmt = iq_format(fmt)
-        self._check(_lib.wifirx_push_iq(self._h, ptr, int(n), fmt, float(IQ_SCALE.get(fmt, 1.0) if scale is None else scale), 1))
+        self._check(_lib.wifirx_push_iq(self._h, ptr, int(n), *_fmt_scale(fmt, scale), 1))
 
     def flush(self):
         self._check(_lib.wifirx_push(self._h, None, 0, 0))
@@ -1700,8 +1682,8 @@ class WifiRx:
             g = np.ascontiguousarray(ant_gain, dtype=np.float32).reshape(-1)
             if g.size != n_ant:
                 raise ValueError("one gain per antenna is required")
-        cfg = DivStream(n_ant, mode, None if g is None else g.ctypes.data_as(C.POINTER(C.c_float)), fmt,
-                        float(IQ_SCALE.get(fmt, 1.0) if scale is None else scale), int(on_device))
+        cfg = DivStream(n_ant, mode, None if g is None else g.ctypes.data_as(C.POINTER(C.c_float)), *_fmt_scale(fmt, scale),
+                        int(on_device))
         arr = (C.c_void_p * max(n_ant, 1))(*ptrs)
         self._check(_lib.wifirx_push_diversity(self._h, C.byref(cfg), arr, int(n)))
         self._div_n_ant = n_ant

@@ -95,3 +95,21 @@ def test_wideband_block_settles_its_signature_before_it_touches_the_library(monk
             block.wifi_phy_rx_wideband(center_frequency=5.21e9, **bad)
     with pytest.raises(ValueError):
         block.wifi_phy_rx_wideband(4, 1, 5.21e9, sample_format="sc12")
+
+
+def test_fed_blocks_pass_a_failing_handle_on_and_close_half_built(monkeypatch):
+    """the three blocks with a front stage and K chains: a handle that cannot be made is the constructor's error, and what
+    was built up to there closes without one"""
+    from wifirx import block, capi
+
+    class NoDevice:
+        def __init__(self, *a, **k):
+            raise RuntimeError("no device")
+    monkeypatch.setattr(capi, "WifiRx", NoDevice)
+    for cls, args in ((block.wifi_phy_rx_wideband, (4, 1, 5.21e9)), (block.wifi_phy_rx_resampled, (25e6,)),
+                      (block.wifi_phy_rx_tuned, (80e6,))):
+        blk = cls.__new__(cls)
+        with pytest.raises(RuntimeError, match="no device"):
+            cls.__init__(blk, *args)
+        blk.close()
+        blk.close()

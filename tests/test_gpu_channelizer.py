@@ -127,6 +127,18 @@ def test_no_outputs_still_hands_on_the_history(rx, bufs):
     assert capi.lib().wifirx_channelize(rx._h, None, fmt, 1.0, None, None, M, 1, 0, 0, None, 0) == capi.OK
 
 
+def test_hist_out_of_a_call_one_block_short_of_the_history(rx, bufs):
+    """M = 2, sc16: the call's input is whole blocks of M samples, and SIZES has 0, 1, 23, 24 and 25 of them -- none, one, and
+    the history's 23 with one more and two more.  The one that is missing, 22: hist_out is hist's last block (zeros for a
+    NULL hist), then the whole input."""
+    M, fmt, H = 2, cr.SC16, 23 * 2
+    rng = np.random.default_rng(9)
+    x, h = samples(rng, 22 * M, fmt), samples(rng, H, fmt)
+    for hist in (None, h):
+        _, hout = run_dev(rx, bufs, x, fmt, M, 1, hist, 0, None)
+        assert same_bits(hout, np.concatenate([np.zeros_like(h) if hist is None else h, x])[-H:]), hist is None
+
+
 def test_one_large_call(rx):
     """2^20 outputs per channel at M = 8, sc8: 4096 sampled outputs per channel, the last ones included"""
     M, s, fmt, n_out = 8, 1, cr.SC8, 1 << 20

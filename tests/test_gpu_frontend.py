@@ -204,6 +204,7 @@ def test_einval(rx):
         assert call(fmt=fr.FC32, scale=float("nan")) == capi.OK                 # FC32: scale is not looked at
         assert call(fmt=fr.FC32, i=dst, o=dst) == capi.OK                       # in == out
         assert call(k=0, i=src + 8, o=src) == capi.OK                           # n = 0: nothing overlaps
+        assert call(k=0, i=st.ptr + 8, o=st.ptr + 16) == capi.OK                # not the state either: an empty range shares no byte
         rx.sync()
     finally:
         buf.free()
