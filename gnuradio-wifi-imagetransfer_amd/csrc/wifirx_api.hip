@@ -148,14 +148,15 @@ struct DecodeWork {
     DevBuf hbits;                   // decode_mac over `idx` alone: its bit planes (wifirx_out.hbits form)
 };
 
-// stream mode (wifirx_api_stream.inc)
+// stream mode (wifirx_api_stream.inc), of both kinds of stream: the single stream is a stream of one sample plane, the
+// diversity stream one of div.n_ant planes that fill, are scanned and are carried together
 struct StreamState {
-    DevBuf   sbuf;                  // device sample buffer of sbuf_cap samples
-    DevBuf   native;                // wifirx_push_iq: a pass's host samples in their integer format, widened from here into sbuf
+    DevBuf   sbuf;                  // the sample planes, plane a at sbuf + a * sbuf_cap samples (stream_plane)
+    DevBuf   native;                // host input in an integer format: every plane's chunk of a pass, widened from here into the planes
     DevBuf   above, A;              // the detection side buffers, sized by sbuf_cap too
-    int64_t  sbuf_cap = 0;
-    int64_t  sbase = 0;             // absolute index of sbuf[0] (multiple of 64)
-    int64_t  sfill = 0;             // valid samples in sbuf
+    int64_t  sbuf_cap = 0;          // samples a plane holds
+    int64_t  sbase = 0;             // absolute index of a plane's first sample (multiple of 64)
+    int64_t  sfill = 0;             // valid samples in every plane
     int64_t  sdetected = 0;         // absolute index up to which triggers have been selected
     int64_t  sprocessed = 0;        // absolute index up to which pushes have been processed
     int64_t  last_trig = -(1ll << 40);
@@ -167,7 +168,7 @@ struct StreamState {
     DevBuf   llr;                   // WIFIRX_P_STREAM_SOFT: LLR rows of the triggers (6 bits per carrier reserved)
     DevBuf   pack;                  // stream outputs, rows cut to their filled width
     PinnedBuf host;                 // pinned landing zone of the packed outputs
-    bool     dead = false;          // the carry step failed after it had begun to move the sample buffer
+    bool     dead = false;          // the carry step failed after it had begun to move the sample planes
     std::string dead_msg;
     size_t   push_consumed = 0;     // wifirx_push_consumed
     bool     single = false;        // wifirx_push / wifirx_push_iq has handed in samples: no wifirx_push_diversity on this handle
@@ -177,15 +178,13 @@ struct StreamState {
     bool     fe_dirty = false;      // the current pass has advanced fe_state
 };
 
-// the diversity stream (wifirx_api_stream_div.inc): what it keeps beside the StreamState it shares with the single stream.
-// There st.sbuf holds the n_ant sample planes, plane a at sbuf + a * sbuf_cap samples, and the st.* output rows are the
-// combined set.
+// the diversity stream (wifirx_api_stream_div.inc): what its frames step keeps beside the StreamState, whose pass it shares
+// with the single stream.  n_ant is the StreamState's plane count, and the st.* output rows are the combined set.
 struct DivStream {
     uint32_t n_ant = 0;             // fixed by the handle's first wifirx_push_diversity; 0: none yet
     uint32_t cap = 0;               // triggers the per-antenna rows hold
     DevBuf   frames, car, csi, stats;   // n_ant sets of frame-kernel rows, set a at cap rows times a
     DevBuf   used, src;             // per trigger: the contributing antennas (the combiner's), the antenna of the csi / sym_stats rows
-    DevBuf   native;                // host input in an integer format: the n_ant chunks of a pass, widened from here
 };
 
 // A batch handed to the worker: `n` samples of format `fmt` (WIFIRX_IQ_*; `scale` widens the integer ones) at `ptr` (a ring

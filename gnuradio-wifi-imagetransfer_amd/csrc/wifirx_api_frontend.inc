@@ -1,5 +1,5 @@
 // receive front end (NUMERICS.md rule 32; wr_frontend.hip): the call on device buffers, the host estimate, the receiver
-// impairments of the loop-back, and the stream's switch.  The stream side is stream_frontend_run below, which stream_process
+// impairments of the loop-back, and the stream's switch.  The stream side is stream_frontend_run below, which stream_ingest
 // (wifirx_api_stream.inc) calls on the samples it appends.
 
 extern "C" void wr_frontend_estimate_host(const wifirx_frontend_cfg* cfg, const wifirx_frontend_state* s, float dc[2], float w[2]);

@@ -4,10 +4,20 @@
 // (3) the per-frame kernel + decode_mac for every trigger whose samples are present, and queues
 // the finished frames for wifirx_poll.  Samples that a still-pending trigger needs, plus the
 // detection history, are carried over to the next push.
+// A stream is a stream of `planes` sample planes: one for wifirx_push / wifirx_push_iq, n_ant for the diversity stream
+// (wifirx_api_stream_div.inc), whose pass is the same pass with a joint detection launch and a frames step of its own.
 
 namespace {
 
 const int64_t kHistory = 256;     // samples kept in front of the detection frontier (2 tiles + delay 16, rounded)
+
+// What a push varies in a pass (stream_process): per plane the input pointer, the samples' format and scale and the side they
+// are on, whether the pass ends the stream; for the diversity frames step the combining mode and the antennas' gains.
+struct StreamCall { const void* const* iq; int fmt; float scale; int iq_on_device; bool flush; int mode; const float* ant_gain; };
+
+// The sample planes: 1, or the antennas of a diversity stream; plane a at sbuf + a * sbuf_cap samples
+uint32_t stream_planes(const wifirx_handle* h) { return h->div.n_ant ? h->div.n_ant : 1; }
+float2* stream_plane(const wifirx_handle* h, uint32_t a) { return h->st.sbuf.as<float2>() + (size_t)a * (size_t)h->st.sbuf_cap; }
 
 // Test hook for the allocation-failure paths (tests/test_gpu_stream.py): a handle created with
 // WIFIRX_TEST_FAIL_ALLOC=<k> in the environment fails its k-th stream-mode allocation (counted from 1) once.
@@ -17,23 +27,26 @@ int stream_alloc(wifirx_handle* h, DevBuf& b, size_t bytes, const char* what)
     return b.alloc(h, bytes, what);
 }
 
-// Grows the sample buffer and the two detection side buffers together.  All three are allocated before anything of
-// the handle changes: after a failure the old buffers and capacities are still in place and a later push starts over.
+// Grows the sample planes (one allocation) and the two detection side buffers together, to `need` samples a plane.  All
+// three are allocated before anything of the handle changes: after a failure the old buffers and capacities are still in
+// place and a later push starts over.
 int stream_reserve(wifirx_handle* h, int64_t need)
 {
     StreamState& s = h->st;
     if (need <= s.sbuf_cap) return WIFIRX_OK;
+    const uint32_t planes = stream_planes(h);
     int64_t cap = std::max<int64_t>(need + need / 2, 1 << 16);
     cap = (cap + 63) / 64 * 64;
     DevBuf nb, n_above, n_A;
     const char* what = "hipMalloc(stream buffers)";
-    int rc = stream_alloc(h, nb, (size_t)cap * sizeof(float2), what);
+    int rc = stream_alloc(h, nb, (size_t)planes * (size_t)cap * sizeof(float2), what);
     if (!rc) rc = stream_alloc(h, n_above, (size_t)(cap / 64 + 2) * sizeof(uint64_t), what);
     if (!rc) rc = stream_alloc(h, n_A, (size_t)cap * sizeof(float2), what);
     if (rc) return rc;
     hipError_t e = hipSuccess;
-    if (s.sbuf.p && s.sfill > 0)
-        e = hipMemcpyAsync(nb.p, s.sbuf.p, (size_t)s.sfill * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
+    for (uint32_t a = 0; a < planes && e == hipSuccess && s.sbuf.p && s.sfill > 0; a++)      // the filled part, plane by plane to the new pitch
+        e = hipMemcpyAsync(nb.as<float2>() + (size_t)a * (size_t)cap, stream_plane(h, a), (size_t)s.sfill * sizeof(float2),
+                           hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, WIFIRX_EHIP, std::string("stream buffer move: ") + hipGetErrorString(e));
     s.sbuf = std::move(nb);
@@ -43,7 +56,7 @@ int stream_reserve(wifirx_handle* h, int64_t need)
     return WIFIRX_OK;
 }
 
-// wifirx_push_iq, host input: room for a pass's samples in their integer format (grows like the sample buffer)
+// Host input in an integer format: room for a pass's samples as they come, every plane's chunk (grows like the sample buffer)
 int stream_native_reserve(wifirx_handle* h, size_t need)
 {
     if (h->st.native.bytes >= need) return WIFIRX_OK;
@@ -203,8 +216,9 @@ static void stream_select_triggers(wifirx_handle* h, const std::vector<uint64_t>
     stage("host state machine");
 }
 
-// Detect: (1) detection over the tiles with not yet scanned samples (plus one tile of mask history); (2) the sync_short state
-// machine (stream_select_triggers) appends to st.pending
+// Detect: (1) detection over the tiles with not yet scanned samples (plus one tile of mask history) -- of a diversity stream
+// the joint detection over its planes (NUMERICS.md rule 24), whatever n_ant; (2) the sync_short state machine
+// (stream_select_triggers) appends to st.pending
 static int stream_detect(wifirx_handle* h, StageClock& stage)
 {
     StreamState& st = h->st;
@@ -213,8 +227,21 @@ static int stream_detect(wifirx_handle* h, StageClock& stage)
     int64_t t_first = (st.sdetected - st.sbase) / 64;
     if (t_first > 0) t_first -= 1;
     const int64_t n_tiles = (st.sfill + 63) / 64 - t_first;
-    HIP_TRY(h, wr_launch_stream_detect(h->stream, st.sbuf.as<float2>(), st.sfill, t_first, n_tiles, h->cfg.sensitivity,
-                                       st.above.as<uint64_t>(), st.A.as<float2>()));
+    if (h->div.n_ant) {
+        wr::DetectMultiArgs args{};
+        for (uint32_t a = 0; a < h->div.n_ant; a++) args.x[a] = stream_plane(h, a);
+        args.n_samp = st.sfill;
+        args.tile0 = t_first;
+        args.n_tiles = n_tiles;
+        args.thr = h->cfg.sensitivity;
+        args.n_ant = h->div.n_ant;
+        args.masks = st.above.as<uint64_t>();
+        args.A = st.A.as<float2>();
+        HIP_TRY(h, wr_launch_stream_detect_multi(h->stream, &args));
+    } else {
+        HIP_TRY(h, wr_launch_stream_detect(h->stream, st.sbuf.as<float2>(), st.sfill, t_first, n_tiles, h->cfg.sensitivity,
+                                           st.above.as<uint64_t>(), st.A.as<float2>()));
+    }
     std::vector<uint64_t> masks((size_t)n_tiles);
     HIP_TRY(h, hipMemcpyAsync(masks.data(), st.above.as<uint64_t>() + t_first,
                               (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
@@ -284,40 +311,60 @@ static int stream_pack_outputs(wifirx_handle* h, const std::array<StreamOut, SO_
     return WIFIRX_OK;
 }
 
+// What both frames steps begin with (stream_frames_begin): the pending triggers, WIFIRX_P_STREAM_SOFT, the frame kernel's
+// parameters, the table of outputs, the decoder's LLR rows (null: hard decisions); the rows the trigger upload reads, which
+// live until the step has waited for the stream
+struct FramesBegin {
+    uint32_t np = 0; bool soft = false; wr::DemodParams prm{}; std::array<StreamOut, SO_N> outs{}; float* d_llr = nullptr;
+    std::vector<wr::StreamTrig> trig;
+};
+
+// The prologue of a frames step: the output rows (`out_reserve`: the stream's, or with the antennas' behind them) and the LLR rows
+// for the pending triggers, the triggers to the device, zeros in the produced outputs that want them.  np = 0: nothing to do.
+static int stream_frames_begin(wifirx_handle* h, int (*out_reserve)(wifirx_handle*, uint32_t), bool flush, FramePass& p, FramesBegin& f)
+{
+    StreamState& st = h->st;
+    f.np = (uint32_t)st.pending.size();
+    if (!f.np) return WIFIRX_OK;
+    int rc;
+    if ((rc = out_reserve(h, f.np))) return rc;
+    f.soft = h->tune.stream_soft != 0;
+    if (f.soft && (rc = stream_llr_reserve(h))) return rc;
+    f.trig = stream_trig_rows(h, flush, p);
+    f.prm = params_of(h);
+    if (f.soft) f.prm.llr_bits = 6;             // the stream's own LLR rows: every rate fits, whatever cfg.llr_bits says
+    HIP_TRY(h, hipMemcpyAsync(st.trig.p, f.trig.data(), f.np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
+    f.outs = stream_outs(h);
+    for (const StreamOut& so : f.outs)
+        if (so.produced && so.zero) HIP_TRY(h, hipMemsetAsync(so.dev->p, 0, f.np * so.pitch, h->stream));
+    f.d_llr = f.soft ? st.llr.as<float>() : nullptr;
+    return WIFIRX_OK;
+}
+
 // Frames: (3) the frame kernel + decode_mac over every pending trigger whose samples are (partly) here; records, outputs
 static int stream_frames(wifirx_handle* h, bool flush, StageClock& stage, FramePass& p)
 {
     StreamState& st = h->st;
-    const uint32_t np = (uint32_t)st.pending.size();
-    if (!np) return WIFIRX_OK;
-    int rc;
-    if ((rc = stream_out_reserve(h, np))) return rc;
-    const bool soft = h->tune.stream_soft != 0;
-    if (soft && (rc = stream_llr_reserve(h))) return rc;
-    const std::vector<wr::StreamTrig> trig = stream_trig_rows(h, flush, p);
-    wr::DemodParams prm = params_of(h);
-    if (soft) prm.llr_bits = 6;                 // the stream's own LLR rows: every rate fits, whatever cfg.llr_bits says
-    HIP_TRY(h, hipMemcpyAsync(st.trig.p, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
-    const std::array<StreamOut, SO_N> outs = stream_outs(h);
-    for (const StreamOut& so : outs)
-        if (so.produced && so.zero) HIP_TRY(h, hipMemsetAsync(so.dev->p, 0, np * so.pitch, h->stream));
+    FramesBegin f;
+    int rc = stream_frames_begin(h, stream_out_reserve, flush, p, f);
+    if (rc || !f.np) return rc;
+    const uint32_t np = f.np;
     // hard decisions as bytes only when the caller polls them (WIFIRX_P_STREAM_IDX); decode_mac reads the bit planes
-    uint8_t* d_idx = outs[SO_IDX].produced ? st.idx.as<uint8_t>() : nullptr;
-    float* d_llr = soft ? st.llr.as<float>() : nullptr;
-    const wr::DemodOut dout = { st.frames.as<wifirx_frame>(), d_idx, d_llr, st.car.as<float2>(), st.csi.as<float2>(),
+    uint8_t* d_idx = f.outs[SO_IDX].produced ? st.idx.as<uint8_t>() : nullptr;
+    const wr::DemodOut dout = { st.frames.as<wifirx_frame>(), d_idx, f.d_llr, st.car.as<float2>(), st.csi.as<float2>(),
                                 st.stats.as<float4>(), st.hbits.as<uint32_t>() };
     HIP_TRY(h, wr_launch_demod_stream(h->stream, st.sbuf.as<float2>(), st.sfill, st.trig.as<wr::StreamTrig>(), np,
-                                      &prm, st.A.as<float2>(), &dout));
-    const wifirx_out o = { st.frames.as<wifirx_frame>(), d_idx, d_llr, nullptr, st.psdu.as<uint8_t>(), 2048, 1,
+                                      &f.prm, st.A.as<float2>(), &dout));
+    const wifirx_out o = { st.frames.as<wifirx_frame>(), d_idx, f.d_llr, nullptr, st.psdu.as<uint8_t>(), 2048, 1,
                            nullptr, nullptr, st.hbits.as<uint32_t>() };
     stage("enqueue frame kernel");
-    if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
+    if ((rc = f.soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
     stage("frame kernel + decode_mac");
     // the frame records first: they say how much of every output row is worth bringing back (stream_pack_outputs)
     p.fr.resize(np);
     HIP_TRY(h, hipMemcpyAsync(p.fr.data(), st.frames.p, np * sizeof(wifirx_frame), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return stream_pack_outputs(h, outs, stage, p);
+    return stream_pack_outputs(h, f.outs, stage, p);
 }
 
 // Queue: the settled frames go to wifirx_poll, the others stay pending with the coarse CFO the device found (cannot fail)
@@ -351,11 +398,11 @@ static void stream_queue(wifirx_handle* h, const FramePass& p, StageClock& stage
     stage("queue frames");
 }
 
-// Carry: (4) samples a pending trigger still needs + the detection history.  It runs behind the commit (frames queued, fill
-// and frontier advanced) and reports no error, which every caller reads as "nothing was consumed, hand the samples in
-// again" -- that would double them (include/wifirx.h, WIFIRX_P_STREAM_BATCH: ERRORS).  A failure before the buffer has
-// been touched leaves base and fill as they are (the next pass moves it); one after the move began leaves a buffer that
-// cannot be trusted: the stream is marked dead and every later push says so (WIFIRX_EDEAD, never "retry").
+// Carry: (4) samples a pending trigger still needs + the detection history, in every plane.  It runs behind the commit
+// (frames queued, fill and frontier advanced) and reports no error, which every caller reads as "nothing was consumed, hand
+// the samples in again" -- that would double them (include/wifirx.h, WIFIRX_P_STREAM_BATCH: ERRORS).  A failure before a
+// plane has been touched leaves base and fill as they are (the next pass moves them); one after the move began leaves
+// planes that cannot be trusted: the stream is marked dead and every later push says so (WIFIRX_EDEAD, never "retry").
 static void stream_carry(wifirx_handle* h, StageClock& stage)
 {
     StreamState& st = h->st;
@@ -372,12 +419,12 @@ static void stream_carry(wifirx_handle* h, StageClock& stage)
             ce = hipErrorUnknown;
             touched = h->env.fail_carry < 0;
         }
-        if (ce == hipSuccess && left > 0) {
-            // overlapping move: stage through the A buffer (same capacity, free between pushes)
-            ce = hipMemcpyAsync(st.A.p, st.sbuf.as<float2>() + off, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
+        for (uint32_t a = 0; a < stream_planes(h) && ce == hipSuccess && left > 0; a++) {
+            // overlapping move: stage through the A buffer (a plane's capacity, free between pushes)
+            ce = hipMemcpyAsync(st.A.p, stream_plane(h, a) + off, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
             if (ce == hipSuccess) {
                 touched = true;
-                ce = hipMemcpyAsync(st.sbuf.p, st.A.p, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
+                ce = hipMemcpyAsync(stream_plane(h, a), st.A.p, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
             }
         }
         if (ce == hipSuccess) ce = hipStreamSynchronize(h->stream);
@@ -396,11 +443,44 @@ static void stream_carry(wifirx_handle* h, StageClock& stage)
     stage("carry");
 }
 
-// One pass of the stream pipeline over `n` more samples of format `fmt` (what every push was before the staging ring existed).
-// Integer samples (NUMERICS.md rule 20) are widened into the sample buffer by a launch in front of the detection: from the
-// caller's device buffer, or from the handle's scratch buffer, which host samples cross the bus into in their native format.
+// Ingest: `n` more samples of format c.fmt into every plane at sfill.  Integer samples (NUMERICS.md rule 20) are widened into
+// the plane by a launch: from the caller's device buffer, or from the plane's chunk of the native scratch (at a * pitch +
+// native_off), which host samples cross the bus into as they come.  With the front end on (rule 32; wifirx_push_diversity
+// refuses it: one plane) it takes the place of the widening, or runs in place on the float pairs.
+static int stream_ingest(wifirx_handle* h, const StreamCall& c, size_t n, size_t native_off, size_t pitch)
+{
+    StreamState& st = h->st;
+    const uint32_t bps = wr_iq_sample_bytes(c.fmt);     // 0: float pairs
+    int rc;
+    for (uint32_t a = 0; n && a < stream_planes(h); a++) {
+        float2* const d_new = stream_plane(h, a) + st.sfill;
+        if (bps) {
+            const void* d_native = c.iq[a];
+            if (!c.iq_on_device) {
+                uint8_t* const chunk = st.native.as<uint8_t>() + a * pitch + native_off;
+                HIP_TRY(h, hipMemcpyAsync(chunk, c.iq[a], n * bps, hipMemcpyHostToDevice, h->stream));
+                d_native = chunk;
+            }
+            if (st.fe_on) { if ((rc = stream_frontend_run(h, d_native, c.fmt, c.scale, n, d_new))) return rc; }
+            else HIP_TRY(h, wr_launch_iq_widen(h->stream, d_native, c.fmt, n, c.scale, d_new, h->n_cu));
+        } else {
+            HIP_TRY(h, hipMemcpyAsync(d_new, c.iq[a], n * sizeof(float2), c.iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+            if (st.fe_on && (rc = stream_frontend_run(h, d_new, WIFIRX_IQ_FC32, 1.0f, n, d_new))) return rc;
+        }
+    }
+    if (n) {
+        st.sfill += (int64_t)n;
+        { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.samples_in += n; }
+    }
+    return WIFIRX_OK;
+}
+
+static int div_frames(wifirx_handle* h, const StreamCall& c, StageClock& stage, FramePass& p);      // wifirx_api_stream_div.inc
+
+// One pass of the stream pipeline over `n` more samples of every plane (what every push was before the staging ring existed):
+// ingest, detect, frames (the diversity stream's own step for its kind), queue, carry.
 // All or nothing: on an error return the handle's stream state is what it was before the call.
-static int stream_process(wifirx_handle* h, const void* iq, size_t n, int iq_on_device, bool flush, int fmt, float scale)
+static int stream_process(wifirx_handle* h, const StreamCall& c, size_t n)
 {
     StageClock stage;
     StreamState& st = h->st;
@@ -408,37 +488,21 @@ static int stream_process(wifirx_handle* h, const void* iq, size_t n, int iq_on_
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = stream_reserve(h, st.sfill + (int64_t)n + 64);
     if (rc) return rc;
-    const uint32_t bps = wr_iq_sample_bytes(fmt);       // 0: float pairs
-    // the scratch copy starts where its first whole 16-byte piece, behind the widen kernel's head sample, is 16-byte aligned
+    const uint32_t bps = wr_iq_sample_bytes(c.fmt);
+    // a plane's scratch copy starts where its first whole 16-byte piece, behind the widen kernel's head sample, is 16-byte aligned
     const size_t native_off = bps ? (16 - (size_t)(st.sfill & 1) * bps) & 15 : 0;
-    if (n && bps && !iq_on_device && (rc = stream_native_reserve(h, native_off + n * bps))) return rc;
+    const size_t pitch = (native_off + n * bps + 63) / 64 * 64;
+    if (n && bps && !c.iq_on_device && (rc = stream_native_reserve(h, (stream_planes(h) - 1) * pitch + native_off + n * bps))) return rc;
     if ((rc = stream_frontend_reserve(h, n))) return rc;
     StreamRollback undo(h);
-    // with the front end on (NUMERICS.md rule 32) it takes the place of the widening, or runs in place on the float pairs
-    float2* const d_new = st.sbuf.as<float2>() + st.sfill;
-    if (n && bps) {
-        const void* d_native = iq;
-        if (!iq_on_device) {
-            d_native = st.native.as<uint8_t>() + native_off;
-            HIP_TRY(h, hipMemcpyAsync(st.native.as<uint8_t>() + native_off, iq, n * bps, hipMemcpyHostToDevice, h->stream));
-        }
-        if (st.fe_on) { if ((rc = stream_frontend_run(h, d_native, fmt, scale, n, d_new))) return rc; }
-        else HIP_TRY(h, wr_launch_iq_widen(h->stream, d_native, fmt, n, scale, d_new, h->n_cu));
-    } else if (n) {
-        HIP_TRY(h, hipMemcpyAsync(d_new, iq, n * sizeof(float2), iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        if (st.fe_on && (rc = stream_frontend_run(h, d_new, WIFIRX_IQ_FC32, 1.0f, n, d_new))) return rc;
-    }
-    if (n) {
-        st.sfill += (int64_t)n;
-        { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.samples_in += n; }
-    }
+    if ((rc = stream_ingest(h, c, n, native_off, pitch))) return rc;
     stage("reserve + enqueue input copy");
-    const bool run = flush || h->tune.stream_batch <= 0 || st.sbase + st.sfill - st.sprocessed >= h->tune.stream_batch;
-    if (!run) HIP_TRY(h, hipStreamSynchronize(h->stream));     // keep collecting (WIFIRX_P_STREAM_BATCH); the caller may reuse its buffer
+    const bool run = c.flush || h->tune.stream_batch <= 0 || st.sbase + st.sfill - st.sprocessed >= h->tune.stream_batch;
+    if (!run) HIP_TRY(h, hipStreamSynchronize(h->stream));     // keep collecting (WIFIRX_P_STREAM_BATCH); the caller may reuse its buffers
     else st.sprocessed = st.sbase + st.sfill;
     FramePass pass;
     if (run && (rc = stream_detect(h, stage))) return rc;
-    if (run && (rc = stream_frames(h, flush, stage, pass))) return rc;
+    if (run && (rc = h->div.n_ant ? div_frames(h, c, stage, pass) : stream_frames(h, c.flush, stage, pass))) return rc;
     undo.armed = false;                 // the commit: the samples are consumed and the frames queued below; nothing after it fails
     if (run) {
         stream_queue(h, pass, stage);
@@ -461,7 +525,7 @@ static void stream_worker_main(wifirx_handle* h)
         lk.unlock();
         int rc;
         try {
-            rc = stream_process(h, job.ptr, job.n, 0, job.flush, job.fmt, job.scale);
+            rc = stream_process(h, StreamCall{ &job.ptr, job.fmt, job.scale, 0, job.flush, 0, nullptr }, job.n);
         } catch (const std::exception& e) {          // nothing may escape a thread (or the C boundary)
             rc = WIFIRX_ENOMEM;
             w.err_local = std::string("stream worker: ") + e.what();
@@ -596,7 +660,7 @@ static int stream_push(wifirx_handle* h, const void* iq, size_t n, int fmt, floa
         const int drc = stream_drain_staged(h);                   // samples staged before the mode changed
         if (drc) return drc;
         try {
-            const int rc = stream_process(h, iq, n, iq_on_device, flush, fmt, scale);
+            const int rc = stream_process(h, StreamCall{ &iq, fmt, scale, iq_on_device, flush, 0, nullptr }, n);
             if (rc == WIFIRX_OK) h->st.push_consumed = n;
             return rc;
         } catch (const std::exception& e) {

@@ -1,46 +1,14 @@
 // Stream-mode receive diversity: the stream pipeline for the n_ant sample-synchronous antennas of one radio.  Detection runs
 // once, on the sum of the antennas' autocorrelations and powers (NUMERICS.md rule 24, wr_detect_multi.hip), so every antenna
-// gets the same triggers and the same coarse CFO and slot i of every antenna is the same transmission by construction.  A pass
-// is that of stream_process (wifirx_api_stream.inc), with its phases and its all-or-nothing contract: copy or widen the n_ant
-// inputs, joint detection, the host state machine over the masks (stream_select_triggers), one frame-kernel launch per
-// antenna on that antenna's plane with the same triggers and the joint A, the combiner (rule 23, wr_diversity.hip) over the
-// n_ant row sets, decode_mac on the combined rows, the outputs to the host, the queue, the carry of all planes.
+// gets the same triggers and the same coarse CFO and slot i of every antenna is the same transmission by construction.
+// The pass is stream_process (wifirx_api_stream.inc) over n_ant sample planes: its reserve, ingest, joint detection, host state
+// machine, queue and carry, and its all-or-nothing contract.  What this file adds is the frames step of such a pass
+// (div_frames): one frame-kernel launch per antenna on that antenna's plane with the same triggers and the joint A, the
+// combiner (rule 23, wr_diversity.hip) over the n_ant row sets, decode_mac on the combined rows; and the entry points.
 // Everything runs in the caller's thread on the handle's stream: the pinned ring and the worker of the single stream are not
-// built for n_ant host streams.  The handle's StreamState is shared with the single stream (a handle runs one kind only):
-// st.sbuf holds the planes, the st.* output rows are the combined set; DivStream holds the antennas' own rows.
+// built for n_ant host streams.  The st.* output rows are the combined set; DivStream holds the antennas' own rows.
 
 namespace {
-
-struct DivCall { int mode; const float* ant_gain; int fmt; float scale; int iq_on_device; };
-
-float2* div_plane(const wifirx_handle* h, uint32_t a) { return h->st.sbuf.as<float2>() + (size_t)a * (size_t)h->st.sbuf_cap; }
-
-// stream_reserve for n_ant planes in one allocation: everything is allocated before anything of the handle changes
-int div_reserve(wifirx_handle* h, int64_t need)
-{
-    StreamState& s = h->st;
-    const uint32_t A = h->div.n_ant;
-    if (need <= s.sbuf_cap) return WIFIRX_OK;
-    int64_t cap = std::max<int64_t>(need + need / 2, 1 << 16);
-    cap = (cap + 63) / 64 * 64;
-    DevBuf nb, n_above, n_A;
-    const char* what = "hipMalloc(diversity stream buffers)";
-    int rc = stream_alloc(h, nb, (size_t)A * (size_t)cap * sizeof(float2), what);
-    if (!rc) rc = stream_alloc(h, n_above, (size_t)(cap / 64 + 2) * sizeof(uint64_t), what);
-    if (!rc) rc = stream_alloc(h, n_A, (size_t)cap * sizeof(float2), what);
-    if (rc) return rc;
-    hipError_t e = hipSuccess;
-    for (uint32_t a = 0; a < A && e == hipSuccess && s.sbuf.p && s.sfill > 0; a++)
-        e = hipMemcpyAsync(nb.as<float2>() + (size_t)a * (size_t)cap, div_plane(h, a), (size_t)s.sfill * sizeof(float2),
-                           hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(h, WIFIRX_EHIP, std::string("diversity stream buffer move: ") + hipGetErrorString(e));
-    s.sbuf = std::move(nb);
-    s.above = std::move(n_above);
-    s.A = std::move(n_A);
-    s.sbuf_cap = cap;
-    return WIFIRX_OK;
-}
 
 // the combined rows (stream_out_reserve) and the antennas' own rows for up to `n` triggers
 int div_out_reserve(wifirx_handle* h, uint32_t n)
@@ -74,52 +42,17 @@ bool div_usable(const wifirx_handle* h, const wifirx_frame& f)
 
 }  // namespace
 
-// Detect: the joint detection over the tiles with not yet scanned samples (plus one tile of mask history), then the state machine
-static int div_detect(wifirx_handle* h, StageClock& stage)
-{
-    StreamState& st = h->st;
-    if (st.sbase + st.sfill <= st.sdetected) return WIFIRX_OK;
-    int64_t t_first = (st.sdetected - st.sbase) / 64;
-    if (t_first > 0) t_first -= 1;
-    const int64_t n_tiles = (st.sfill + 63) / 64 - t_first;
-    wr::DetectMultiArgs args{};
-    for (uint32_t a = 0; a < h->div.n_ant; a++) args.x[a] = div_plane(h, a);
-    args.n_samp = st.sfill;
-    args.tile0 = t_first;
-    args.n_tiles = n_tiles;
-    args.thr = h->cfg.sensitivity;
-    args.n_ant = h->div.n_ant;
-    args.masks = st.above.as<uint64_t>();
-    args.A = st.A.as<float2>();
-    HIP_TRY(h, wr_launch_stream_detect_multi(h->stream, &args));
-    std::vector<uint64_t> masks((size_t)n_tiles);
-    HIP_TRY(h, hipMemcpyAsync(masks.data(), st.above.as<uint64_t>() + t_first, (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    stage("input copy + joint detect + masks");
-    stream_select_triggers(h, masks, t_first, stage);
-    return WIFIRX_OK;
-}
-
 // Frames: per antenna the frame kernel over every pending trigger, the combiner, decode_mac on the combined rows; records, outputs
-static int div_frames(wifirx_handle* h, const DivCall& c, bool flush, StageClock& stage, FramePass& p)
+static int div_frames(wifirx_handle* h, const StreamCall& c, StageClock& stage, FramePass& p)
 {
     StreamState& st = h->st;
     DivStream& d = h->div;
-    const uint32_t np = (uint32_t)st.pending.size(), A = d.n_ant;
-    if (!np) return WIFIRX_OK;
-    int rc;
-    if ((rc = div_out_reserve(h, np))) return rc;
-    const bool soft = h->tune.stream_soft != 0;
-    if (soft && (rc = stream_llr_reserve(h))) return rc;
-    const std::vector<wr::StreamTrig> trig = stream_trig_rows(h, flush, p);
-    wr::DemodParams prm = params_of(h);
-    if (soft) prm.llr_bits = 6;
-    HIP_TRY(h, hipMemcpyAsync(st.trig.p, trig.data(), np * sizeof(wr::StreamTrig), hipMemcpyHostToDevice, h->stream));
-    const std::array<StreamOut, SO_N> outs = stream_outs(h);
-    for (const StreamOut& so : outs)
-        if (so.produced && so.zero) HIP_TRY(h, hipMemsetAsync(so.dev->p, 0, np * so.pitch, h->stream));
+    FramesBegin f;
+    int rc = stream_frames_begin(h, div_out_reserve, c.flush, p, f);
+    if (rc || !f.np) return rc;
+    const uint32_t np = f.np, A = d.n_ant;
     const size_t per = (size_t)h->cfg.max_sym * 48;
-    if (!outs[SO_IDX].produced) HIP_TRY(h, hipMemsetAsync(st.idx.p, 0, np * per, h->stream));       // the decoder reads them all the same
+    if (!f.outs[SO_IDX].produced) HIP_TRY(h, hipMemsetAsync(st.idx.p, 0, np * per, h->stream));       // the decoder reads them all the same
     wr::DivArgs args{};
     for (uint32_t a = 0; a < A; a++) {
         const size_t row0 = (size_t)a * d.cap;
@@ -127,22 +60,21 @@ static int div_frames(wifirx_handle* h, const DivCall& c, bool flush, StageClock
         HIP_TRY(h, hipMemsetAsync(d.csi.as<float2>() + row0 * 52, 0, (size_t)np * 52 * sizeof(float2), h->stream));
         const wr::DemodOut dout = { d.frames.as<wifirx_frame>() + row0, nullptr, nullptr, d.car.as<float2>() + row0 * per,
                                     d.csi.as<float2>() + row0 * 52, d.stats.as<float4>() + row0, nullptr };
-        HIP_TRY(h, wr_launch_demod_stream(h->stream, div_plane(h, a), st.sfill, st.trig.as<wr::StreamTrig>(), np, &prm, st.A.as<float2>(), &dout));
+        HIP_TRY(h, wr_launch_demod_stream(h->stream, stream_plane(h, a), st.sfill, st.trig.as<wr::StreamTrig>(), np, &f.prm, st.A.as<float2>(), &dout));
         args.frames[a] = dout.frames;
         args.carrier[a] = reinterpret_cast<const float*>(dout.carrier);
         args.csi[a] = reinterpret_cast<const float*>(dout.csi);
         args.gain[a] = c.ant_gain ? c.ant_gain[a] : 1.0f;
     }
-    float* d_llr = soft ? st.llr.as<float>() : nullptr;
     args.out_frames = st.frames.as<wifirx_frame>();
     args.out_idx = st.idx.as<uint8_t>();
-    args.out_llr = d_llr;
+    args.out_llr = f.d_llr;
     args.out_carrier = h->cfg.want_carrier ? st.car.as<float>() : nullptr;
     args.used_mask = d.used.as<uint8_t>();
     args.n_ant = A;
     args.n_slots = np;
     args.max_sym = h->cfg.max_sym;
-    args.llr_bits = prm.llr_bits;
+    args.llr_bits = f.prm.llr_bits;
     args.select = c.mode == WIFIRX_DIV_SELECT;
     args.has_gain = c.ant_gain != nullptr;
     args.llr_csi = h->tune.llr_csi != 0;
@@ -150,9 +82,9 @@ static int div_frames(wifirx_handle* h, const DivCall& c, bool flush, StageClock
     HIP_TRY(h, wr_launch_diversity(h->stream, &args, h->n_cu));
     stage("enqueue frame kernels + combiner");
     // hbits stays NULL: the decoder packs the planes from idx, as it does behind the batch combiner
-    const wifirx_out o = { st.frames.as<wifirx_frame>(), st.idx.as<uint8_t>(), d_llr, nullptr, st.psdu.as<uint8_t>(), 2048, 1,
+    const wifirx_out o = { st.frames.as<wifirx_frame>(), st.idx.as<uint8_t>(), f.d_llr, nullptr, st.psdu.as<uint8_t>(), 2048, 1,
                            nullptr, nullptr, nullptr };
-    if ((rc = soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
+    if ((rc = f.soft ? decode_batch_soft_impl(h, np, &o, 6, false) : decode_batch_impl(h, np, &o))) return rc;
     stage("frame kernels + combiner + decode_mac");
     // the records: the combined ones, every antenna's own, the contributing antennas
     p.fr.resize(np);
@@ -192,98 +124,7 @@ static int div_frames(wifirx_handle* h, const DivCall& c, bool flush, StageClock
     g.n = np;
     g.n_ant = A;
     HIP_TRY(h, wr_launch_row_gather(h->stream, &g));
-    return stream_pack_outputs(h, outs, stage, p);       // (waits: src stays alive until then)
-}
-
-// Carry: stream_carry for every plane (behind the commit: it reports no error; a failure after a plane was touched kills the stream)
-static void div_carry(wifirx_handle* h, StageClock& stage)
-{
-    StreamState& st = h->st;
-    int64_t keep_from = st.sdetected - kHistory;
-    if (!st.pending.empty()) keep_from = std::min(keep_from, st.pending.front().pos - 16);
-    if (keep_from < st.sbase) keep_from = st.sbase;
-    keep_from = keep_from / 64 * 64;
-    if (keep_from > st.sbase) {
-        const int64_t off = keep_from - st.sbase, left = st.sfill - off;
-        hipError_t ce = hipSuccess;
-        bool touched = false;
-        // test hook, as in stream_carry: WIFIRX_TEST_FAIL_CARRY=<k> fails the k-th carry before / =-<k> after the move began
-        if (h->env.fail_carry != 0 && ++h->env.carry_count == std::abs(h->env.fail_carry)) {
-            ce = hipErrorUnknown;
-            touched = h->env.fail_carry < 0;
-        }
-        for (uint32_t a = 0; a < h->div.n_ant && ce == hipSuccess && left > 0; a++) {
-            // overlapping move: stage through the A buffer (a plane's capacity, free between pushes)
-            ce = hipMemcpyAsync(st.A.p, div_plane(h, a) + off, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
-            if (ce == hipSuccess) {
-                touched = true;
-                ce = hipMemcpyAsync(div_plane(h, a), st.A.p, (size_t)left * sizeof(float2), hipMemcpyDeviceToDevice, h->stream);
-            }
-        }
-        if (ce == hipSuccess) ce = hipStreamSynchronize(h->stream);
-        if (ce == hipSuccess) {
-            st.sbase = keep_from;
-            st.sfill = left > 0 ? left : 0;
-        } else if (touched) {
-            std::lock_guard<std::mutex> lk(h->w.mu);
-            st.dead = true;
-            st.dead_msg = std::string("diversity stream sample planes lost in the carry step: ") + hipGetErrorString(ce) +
-                          " (frames up to here were delivered; destroy the handle)";
-        } else {
-            (void)hipGetLastError();        // nothing was moved: the next pass carries from the same base
-        }
-    }
-    stage("carry");
-}
-
-// One pass over `n` more samples of every antenna.  All or nothing: on an error return the stream state is what it was.
-static int div_process(wifirx_handle* h, const DivCall& c, const void* const* iq, size_t n, bool flush)
-{
-    StageClock stage;
-    StreamState& st = h->st;
-    const uint32_t A = h->div.n_ant;
-    { std::lock_guard<std::mutex> lk(h->w.mu); if (st.dead) return fail(h, WIFIRX_EDEAD, st.dead_msg); }
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = div_reserve(h, st.sfill + (int64_t)n + 64);
-    if (rc) return rc;
-    const uint32_t bps = wr_iq_sample_bytes(c.fmt);     // 0: float pairs
-    // host integers: antenna a's chunk of the scratch starts where the widen kernel's first whole 16-byte piece is aligned (stream_process)
-    const size_t native_off = bps ? (16 - (size_t)(st.sfill & 1) * bps) & 15 : 0;
-    const size_t chunk = (native_off + n * bps + 63) / 64 * 64;
-    if (n && bps && !c.iq_on_device && h->div.native.bytes < A * chunk &&
-        (rc = stream_alloc(h, h->div.native, A * chunk + A * chunk / 2, "hipMalloc(diversity stream native samples)"))) return rc;
-    StreamRollback undo(h);
-    for (uint32_t a = 0; n && a < A; a++) {
-        float2* dst = div_plane(h, a) + st.sfill;
-        if (bps) {
-            const void* d_native = iq[a];
-            if (!c.iq_on_device) {
-                uint8_t* stage_a = h->div.native.as<uint8_t>() + a * chunk + native_off;
-                HIP_TRY(h, hipMemcpyAsync(stage_a, iq[a], n * bps, hipMemcpyHostToDevice, h->stream));
-                d_native = stage_a;
-            }
-            HIP_TRY(h, wr_launch_iq_widen(h->stream, d_native, c.fmt, n, c.scale, dst, h->n_cu));
-        } else {
-            HIP_TRY(h, hipMemcpyAsync(dst, iq[a], n * sizeof(float2), c.iq_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        }
-    }
-    if (n) {
-        st.sfill += (int64_t)n;
-        { std::lock_guard<std::mutex> lk(h->w.mu); h->stats.samples_in += n; }
-    }
-    stage("reserve + enqueue input copies");
-    const bool run = flush || h->tune.stream_batch <= 0 || st.sbase + st.sfill - st.sprocessed >= h->tune.stream_batch;
-    if (!run) HIP_TRY(h, hipStreamSynchronize(h->stream));     // keep collecting (WIFIRX_P_STREAM_BATCH); the caller may reuse its buffers
-    else st.sprocessed = st.sbase + st.sfill;
-    FramePass pass;
-    if (run && (rc = div_detect(h, stage))) return rc;
-    if (run && (rc = div_frames(h, c, flush, stage, pass))) return rc;
-    undo.armed = false;                 // the commit
-    if (run) {
-        stream_queue(h, pass, stage);
-        div_carry(h, stage);
-    }
-    return WIFIRX_OK;
+    return stream_pack_outputs(h, f.outs, stage, p);       // (waits: src stays alive until then)
 }
 
 extern "C" int wifirx_push_diversity(wifirx_handle* h, const wifirx_div_stream* cfg, const void* const* iq, size_t n)
@@ -305,9 +146,8 @@ extern "C" int wifirx_push_diversity(wifirx_handle* h, const wifirx_div_stream* 
     }
     if (n > (size_t)1 << 40) return fail(h, WIFIRX_EINVAL, "n out of range");
     h->div.n_ant = cfg->n_ant;
-    const DivCall c = { cfg->mode, cfg->ant_gain, cfg->fmt, cfg->scale, cfg->iq_on_device };
     try {
-        return div_process(h, c, iq, n, n == 0);
+        return stream_process(h, StreamCall{ iq, cfg->fmt, cfg->scale, cfg->iq_on_device, n == 0, cfg->mode, cfg->ant_gain }, n);
     } catch (const std::exception& e) {
         return fail(h, WIFIRX_ENOMEM, std::string("wifirx_push_diversity: ") + e.what());
     }

@@ -1,7 +1,8 @@
 """Stream-mode receive diversity on the device: wifirx_detect_multi against the restatement of NUMERICS.md rule 24
 (tests/detect_multi_ref.py) bit for bit, and wifirx_push_diversity / wifirx_poll_diversity -- one antenna against wifirx_push
 byte for byte, identical and all-zero antennas, independence of chunking / batching / input side / sample format, the
-end-to-end gain at the operating point of tests/stream_diversity_point.py, the all-or-nothing contract, a failure behind the
+regrowth of three partly filled planes, the end-to-end gain at the operating point of tests/stream_diversity_point.py, the
+all-or-nothing contract (float and integer host input), a failure behind the
 commit of a pass (WIFIRX_EDEAD), every refused argument, and the wifi_phy_rx block with two input ports."""
 import ctypes as C
 import functools
@@ -105,8 +106,9 @@ def single_run(key, chunk=0, soft=0):
         rx.close()
 
 
-def div_run(xs, chunk=0, soft=0, batch=0, mode=capi.DIV_MRC, ant_gain=None, on_device=False, fmt=None, scale=None):
-    """the antennas' streams xs through wifirx_push_diversity: complex64 arrays, or (with fmt) int16 arrays [n, 2]"""
+def div_run(xs, chunk=0, soft=0, batch=0, mode=capi.DIV_MRC, ant_gain=None, on_device=False, fmt=None, scale=None, edges=None):
+    """the antennas' streams xs through wifirx_push_diversity: complex64 arrays, or (with fmt) int16 / int8 arrays [n, 2];
+    one push per chunk, or per pair of `edges`"""
     rx = new_handle(batch, soft)
     dev = []
     try:
@@ -115,7 +117,7 @@ def div_run(xs, chunk=0, soft=0, batch=0, mode=capi.DIV_MRC, ant_gain=None, on_d
         if on_device:
             dev = [rx.alloc(x.nbytes).upload(x) for x in xs]
         item = xs[0].nbytes // n
-        for a, b in cuts(n, chunk):
+        for a, b in edges or cuts(n, chunk):
             if on_device:
                 rx.push_diversity_dev([d.ptr + a * item for d in dev], b - a, mode, ant_gain, "fc32" if fmt is None else fmt, scale)
             else:
@@ -237,6 +239,33 @@ def test_sc16_input_equals_fc32_input_of_the_widened_samples(on_device):
     got = div_run(q, 4096, ant_gain=GAIN2, on_device=on_device, fmt="sc16", scale=float(scale_w))
     assert len(want["frames"]) == 10
     same_bytes(got, want, KEYS + ("used_mask", "ant_frames"))
+
+
+GAIN3 = ((1.0, 7), (0.7 * np.exp(0.8j), 8), (0.5 * np.exp(-2.0j), 9))      # (gain, noise seed) per antenna
+FIRST_CAP = 1 << 16             # samples a plane holds after the first reserve (stream_reserve)
+
+
+@pytest.mark.parametrize("fmt", ["fc32", "sc8"])
+def test_three_planes_regrow_with_their_samples_kept(fmt):
+    """The first push ends inside the first frame (samples 100 .. 2180 of the stream): its trigger stays pending and the carry
+    keeps its samples in all three planes.  The second push needs more than the planes' first capacity, so the reserve moves
+    three partly filled planes to a new pitch.  Delivered is, byte for byte, what one push of the same streams delivers.  The
+    first push is odd, so with sc8 host input the second pass stages its chunks at the odd-fill offset of the native scratch."""
+    clean, _ = sdr.clean_stream()
+    clean = np.tile(clean, -(-(FIRST_CAP + 4096) // clean.size))
+    xs = [sdr.antenna(clean, g, seed) for g, seed in GAIN3]
+    n, first = clean.size, 1201
+    kw = {}
+    if fmt == "sc8":
+        scale_q = cr.full_scale(xs[0], 12.0, cr.SC8)
+        xs = [cr.quantise(cr.pairs(x), scale_q, cr.SC8)[0] for x in xs]
+        kw = dict(fmt="sc8", scale=float(np.float32(1.0) / scale_q))
+    assert first % 2 == 1 and 100 + 320 < first < 2180 and n - first + 64 > FIRST_CAP
+    want = div_run(xs, **kw)
+    got = div_run(xs, edges=[(0, first), (first, n)], **kw)
+    assert len(want["frames"]) == 10 * (n // sdr.clean_stream()[0].size) and want["stats"]["frames_detected"] == len(want["frames"])
+    same_bytes(got, want, KEYS + ("used_mask", "ant_frames"))
+    assert got["stats"] == want["stats"]
 
 
 def test_every_antennas_record_carries_the_joint_trigger_and_cfo():
@@ -376,6 +405,46 @@ def test_a_failed_pass_consumed_nothing(monkeypatch):
         finally:
             rx.close()
     assert failures >= 12
+
+
+def test_a_failed_pass_of_host_integers_consumed_nothing(monkeypatch):
+    """test_a_failed_pass_consumed_nothing with sc16 host input: the native scratch is one more allocation in the numbered
+    sequence (behind the three sample-side buffers), so one k more is covered and one failure more is the least."""
+    xs = streams("two")
+    scale_q = cr.full_scale(xs[0], 12.0, cr.SC16)
+    q = [cr.quantise(cr.pairs(x), scale_q, cr.SC16)[0] for x in xs]
+    kw = dict(ant_gain=GAIN2, fmt="sc16", scale=float(np.float32(1.0) / scale_q))
+    chunk = 30000
+    want = div_run(q, chunk, **kw)
+    assert len(want["frames"]) == 10
+    failures = 0
+    for k in range(1, 23):
+        monkeypatch.setenv("WIFIRX_TEST_FAIL_ALLOC", str(k))
+        rx = new_handle()
+        try:
+            got = []
+            for a, b in cuts(len(q[0]), chunk):
+                piece = [x[a:b] for x in q]
+                before = rx.stats()
+                try:
+                    rx.push_diversity(piece, **kw)
+                except capi.WifiRxError as e:
+                    assert e.code == capi.ENOMEM, str(e)
+                    failures += 1
+                    assert rx.stats() == before and rx.queued() == 0
+                    rx.push_diversity(piece, **kw)
+                got.append(rx.poll_diversity(cap=64, want_idx=True, want_csi=True, want_stats=True))
+            try:
+                rx.flush_diversity(ant_gain=GAIN2)
+            except capi.WifiRxError as e:
+                assert e.code == capi.ENOMEM, str(e)
+                failures += 1
+                rx.flush_diversity(ant_gain=GAIN2)
+            got.append(rx.poll_diversity(cap=64, want_idx=True, want_csi=True, want_stats=True))
+            same_bytes(collect(rx, got, KEYS + ("used_mask", "ant_frames")), want, KEYS + ("used_mask", "ant_frames"))
+        finally:
+            rx.close()
+    assert failures >= 13
 
 
 @pytest.mark.parametrize("when", [1, -1], ids=["before the move", "after the move began"])
