@@ -37,6 +37,7 @@
 #include "wr_combiner.h"
 #include "wr_arb.h"
 #include "wr_arb_table.h"
+#include "wr_spectrum.h"
 #include "wr_diversity.h"
 #include "wr_precombine.h"
 #include "wr_detect_multi.h"
@@ -648,6 +649,7 @@ int wifirx_synth_slots(wifirx_handle* h, const float* templates, int templates_o
 #include "wifirx_api_bank.inc"
 #include "wifirx_api_arb.inc"
 #include "wifirx_api_tune.inc"
+#include "wifirx_api_spectrum.inc"
 #include "wifirx_api_diversity.inc"
 #include "wifirx_api_precombine.inc"
 #include "wifirx_api_stream_div.inc"

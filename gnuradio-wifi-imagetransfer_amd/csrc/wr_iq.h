@@ -1,5 +1,5 @@
 // wr_iq.h -- the sample formats of NUMERICS.md rule 20 as the kernels read them, and as their launchers pick the kernel of one
-// (internal; wr_convert.hip, wr_frontend.hip, wr_channelizer.hip, wr_arb.hip).
+// (internal; wr_convert.hip, wr_frontend.hip, wr_channelizer.hip, wr_arb.hip, wr_spectrum.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

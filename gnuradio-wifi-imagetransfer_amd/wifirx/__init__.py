@@ -5,4 +5,4 @@ include/wifirx.h; this package holds the ctypes binding (capi), the GNU-Radio-sh
 mirrors the RX half of the reference's wifi_phy_hier (block, grshim), the CPU transmitter used as
 synthetic source (txgen) and the application-layer helpers of the image demo (app).
 """
-__all__ = ["capi", "txgen", "grshim", "block", "app", "dist"]
+__all__ = ["capi", "txgen", "grshim", "block", "app", "dist", "spectrum"]

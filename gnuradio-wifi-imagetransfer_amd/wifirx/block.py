@@ -804,6 +804,111 @@ class wifi_phy_rx_tuned(_arb_fed_rx):
                     [dict(channel=k, frequency=f) for k, f in enumerate(self.frequencies)], device=device, **rx_kwargs)
 
 
+class spectrum_probe(grshim.sync_block):
+    """The numbers behind the reference's ``qtgui.sink_c(1024, window.WIN_BLACKMAN_hARRIS, fc, samp_rate, ...)`` spectrum and
+    waterfall, on the device (wifirx_spectrum, NUMERICS.md rule 36): a sink with ``samp_in`` at ``sample_rate`` Hz around
+    ``center_frequency`` (``sample_format`` / ``sample_scale`` as ``wifi_phy_rx``) that publishes one PDU per complete row on
+    ``spectrum``: the row as an f32 vector of ``n_fft`` powers, bin i at ``center_frequency + (i - n_fft / 2) sample_rate /
+    n_fft``, and the entries ``sample_rate``, ``center_frequency``, ``row_index``, ``n_fft``.  A row folds ``avg`` segments of
+    ``n_fft`` samples, ``hop`` apart (None: ``n_fft``), by ``mode`` ("sum" / "max"), times ``norm`` (None: power per bin,
+    ``spectrum.norm``).  With ``offsets`` (up to 16 candidate centres in Hz above ``center_frequency``, each ``width`` wide)
+    a PDU also carries ``band_power_db``, one value per offset, from wifirx_spectrum_bands; ``band_rows`` collects the band
+    powers of every row for ``spectrum.busy_channels``.
+
+    ``work()`` keeps the samples that complete no row yet (the overlap of rule 36 stays with the caller), so the rows do not
+    depend on how the scheduler cuts the stream: they are those of one call on the whole stream."""
+
+    def __init__(self, sample_rate, n_fft=1024, window="blackman_harris", hop=None, avg=16, mode="sum", offsets=None, width=20e6,
+                 center_frequency=0.0, sample_format="fc32", sample_scale=None, norm=None, device=0):
+        from . import spectrum as _spectrum
+        self.sample_rate, self.center_frequency, self.width = float(sample_rate), float(center_frequency), float(width)
+        self.n_fft, self.avg = int(n_fft), int(avg)
+        self.hop = self.n_fft if hop is None else int(hop)
+        self.window, self.mode = window, mode
+        capi.spectrum_count(self.n_fft, self.hop, self.avg, 0)       # refuses an n_fft, hop or avg outside the rule
+        if window not in capi.SPEC_WINDOWS or mode not in capi.SPEC_MODES:
+            raise ValueError("window must be one of %s, mode one of %s" % (sorted(capi.SPEC_WINDOWS), sorted(capi.SPEC_MODES)))
+        self.norm = float(_spectrum.norm(self.n_fft, window, self.avg if mode == "sum" else 1) if norm is None else norm)
+        self.offsets = None if offsets is None else [float(v) for v in offsets]
+        self.bands = []
+        if self.offsets is not None:
+            if not 1 <= len(self.offsets) <= capi.SPEC_MAX_BANDS:
+                raise ValueError("1 .. %d offsets are required" % capi.SPEC_MAX_BANDS)
+            self.bands = [capi.spectrum_band(off, self.width, self.sample_rate, self.n_fft) for off in self.offsets]
+        self._sf = _sample_format(sample_format, sample_scale)
+        grshim.sync_block.__init__(self, name="spectrum_probe", in_sig=self._sf.in_sig, out_sig=None)
+        self.message_port_register_out(grshim.intern("spectrum"))
+        self._to_db = _spectrum.to_db
+        self._rx = capi.WifiRx(max_sym=1, device=device)             # the survey's handle: its receive side stays unused
+        self._pending = np.zeros(0, np.uint8)                        # samples that complete no row yet
+        self._d_in = self._d_rows = self._d_bands = None
+        self._cap_in = self._cap_rows = 0
+        self.rows_made = 0
+        self.band_rows = []
+
+    def _room(self, n, rows):
+        if n > self._cap_in:
+            if self._d_in is not None:
+                self._d_in.free()
+            self._cap_in = n + n // 2
+            self._d_in = self._rx.alloc(self._cap_in * self._sf.bps)
+        if rows > self._cap_rows:
+            for b in (self._d_rows, self._d_bands):
+                if b is not None:
+                    b.free()
+            self._cap_rows = rows + rows // 2
+            self._d_rows = self._rx.alloc(self._cap_rows * self.n_fft * 4)
+            self._d_bands = self._rx.alloc(self._cap_rows * max(len(self.bands), 1) * 4)
+
+    def work(self, input_items, output_items):
+        raw, n = self._sf.items(input_items[0])
+        if n == 0:
+            return 0
+        sf, rx = self._sf, self._rx
+        data = np.concatenate([self._pending, raw]) if len(self._pending) else raw
+        have = len(data) // sf.bps
+        rows, consumed = capi.spectrum_count(self.n_fft, self.hop, self.avg, have)
+        if rows:
+            self._room(have, rows)
+            data = np.ascontiguousarray(data)
+            rx._check(capi.lib().wifirx_memcpy_h2d(rx._h, self._d_in.ptr, data.ctypes.data, have * sf.bps))
+            got = rx.spectrum_dev(self._d_in.ptr, sf.fmt, have, self.n_fft, self.hop, self.avg, self._d_rows.ptr, self._cap_rows,
+                                  self.window, self.mode, self.norm, scale=sf.scale)
+            band = None
+            if self.bands:
+                rx.spectrum_bands_dev(self._d_rows.ptr, got, self.n_fft, self.bands, self._d_bands.ptr)
+                band = self._d_bands.download(np.float32, got * len(self.bands)).reshape(got, len(self.bands))
+            out = self._d_rows.download(np.float32, got * self.n_fft).reshape(got, self.n_fft)
+            for r in range(got):
+                meta = {"sample_rate": self.sample_rate, "center_frequency": self.center_frequency, "row_index": self.rows_made,
+                        "n_fft": self.n_fft}
+                if band is not None:
+                    self.band_rows.append(band[r].copy())
+                    meta["band_power_db"] = [float(v) for v in self._to_db(band[r])]
+                self.message_port_pub(grshim.intern("spectrum"), grshim.make_pdu(meta, out[r].copy()))
+                self.rows_made += 1
+        self._pending = data[consumed * sf.bps:].copy()
+        return n
+
+    def busy_offsets(self, margin_db=10.0):
+        """the offsets whose band was busy in the rows so far (``spectrum.busy_channels``)"""
+        from . import spectrum as _spectrum
+        if not self.band_rows:
+            return []
+        return [self.offsets[k] for k in _spectrum.busy_channels(np.stack(self.band_rows), margin_db)]
+
+    def close(self):
+        """Release the device buffers and the handle."""
+        for b in (getattr(self, "_d_in", None), getattr(self, "_d_rows", None), getattr(self, "_d_bands", None)):
+            if b is not None:
+                b.free()
+        self._d_in = self._d_rows = self._d_bands = None
+        self._cap_in = self._cap_rows = 0
+        if getattr(self, "_rx", None) is not None:
+            self._rx.close()
+            self._rx = None
+
+
 class wifi_phy_tx(grshim.sync_block):
     """Drop-in for the TX half of ``wifi_phy_hier`` (mapper, SIGNAL, chunks->symbols, carrier allocator, IFFT, cyclic
     prefixer; gnu_radio/wifi_phy_hier.grc:279-479,570-586), optionally with ``foo.packet_pad2``'s zeros folded in

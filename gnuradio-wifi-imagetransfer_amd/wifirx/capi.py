@@ -56,6 +56,8 @@ EXPORTS = [
     "wifirx_precombine",
     "wifirx_arb_resample", "wifirx_arb_hist", "wifirx_arb_count", "wifirx_arb_table",
     "wifirx_tune", "wifirx_tune_inc",
+    "wifirx_spectrum", "wifirx_spectrum_count", "wifirx_spectrum_fold", "wifirx_spectrum_bands", "wifirx_spectrum_band",
+    "wifirx_spectrum_table",
 ]
 FE_DC, FE_IQ = 1, 2                 # WIFIRX_FE_*: stages of the receive front end (NUMERICS.md rule 32)
 FE_BLOCK, FE_RING = 4096, 64        # WIFIRX_FE_BLOCK, WIFIRX_FE_RING
@@ -75,6 +77,12 @@ CHANNELIZER_HIST = 23               # input blocks of n_channels samples that a 
 ARB_HIST_MAX = 128                  # WIFIRX_ARB_HIST_MAX: the most samples wifirx_arb_resample takes from before its input
 ARB_MAX_DEN, ARB_MAX_NUM, ARB_MAX_RATIO = 512, 2048, 4      # the limits of a reduced ratio (NUMERICS.md rule 34)
 TUNE_MAX_CHANNELS = 8               # WIFIRX_TUNE_MAX_CHANNELS: the most channels of one wifirx_tune call (NUMERICS.md rule 35)
+# wifirx_spectrum (NUMERICS.md rule 36): WIFIRX_SPEC_*
+SPEC_RECT, SPEC_HANN, SPEC_BLACKMAN_HARRIS = 0, 1, 2
+SPEC_WINDOWS = {"rect": SPEC_RECT, "hann": SPEC_HANN, "blackman_harris": SPEC_BLACKMAN_HARRIS}
+SPEC_SUM, SPEC_MAX = 0, 1
+SPEC_MODES = {"sum": SPEC_SUM, "max": SPEC_MAX}
+SPEC_MAX_BANDS, SPEC_MAX_HOP, SPEC_N_FFT = 16, 1 << 20, (64, 256, 1024, 4096)
 MAX_PAYLOAD = 1500                  # WIFIRX_MAX_PSDU - 28: the longest payload wifirx_mac_batch frames
 
 
@@ -207,6 +215,37 @@ def tune_inc(offset_hz, sample_rate) -> int:
     if rc != OK:
         raise WifiRxError(rc, "wifirx_tune_inc: offset_hz must be finite, sample_rate finite and > 0")
     return int(v.value)
+
+
+def spectrum_count(n_fft, hop, avg, n_in):
+    """wifirx_spectrum_count: (n_rows, consumed) of a wifirx_spectrum call on n_in samples (host integers only)"""
+    r, c = C.c_uint64(), C.c_uint64()
+    rc = _lib.wifirx_spectrum_count(int(n_fft), int(hop), int(avg), int(n_in), C.byref(r), C.byref(c))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_spectrum_count: n_fft must be 64, 256, 1024 or 4096, hop and avg 1 .. 2^20, n_in < 2^62")
+    return int(r.value), int(c.value)
+
+
+def spectrum_band(offset_hz, width_hz, sample_rate, n_fft):
+    """wifirx_spectrum_band: (lo, hi), the bins of a row whose centres lie in [offset - width / 2, offset + width / 2)"""
+    lo, hi = C.c_uint32(), C.c_uint32()
+    rc = _lib.wifirx_spectrum_band(float(offset_hz), float(width_hz), float(sample_rate), int(n_fft), C.byref(lo), C.byref(hi))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_spectrum_band: the band holds no bin or leaves the capture" if rc == ERANGE
+                          else "wifirx_spectrum_band: values must be finite, sample_rate and width_hz > 0, n_fft 64, 256, 1024 or 4096")
+    return int(lo.value), int(hi.value)
+
+
+def spectrum_table():
+    """wifirx_spectrum_table: (hann float32 [4096], blackman_harris float32 [4096], twiddle float32 [4096, 2]) of rule 36
+    (copies; no handle, no device)"""
+    hn, bh, tw, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_uint32()
+    rc = _lib.wifirx_spectrum_table(C.byref(hn), C.byref(bh), C.byref(tw), C.byref(n))
+    if rc != OK:
+        raise WifiRxError(rc, "wifirx_spectrum_table")
+    k = n.value
+    return (np.ctypeslib.as_array(hn, shape=(k,)).copy(), np.ctypeslib.as_array(bh, shape=(k,)).copy(),
+            np.ctypeslib.as_array(tw, shape=(k, 2)).copy())
 
 
 def channel_centre(k, n_channels, stacking) -> float:
@@ -382,6 +421,16 @@ _lib.wifirx_tune.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uin
                              C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.c_void_p,
                              C.c_uint64, C.POINTER(C.c_uint64)]
 _lib.wifirx_tune_inc.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_uint64)]
+_lib.wifirx_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                 C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+_lib.wifirx_spectrum_count.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+_lib.wifirx_spectrum_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64,
+                                      C.POINTER(C.c_uint64)]
+_lib.wifirx_spectrum_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32), C.c_void_p]
+_lib.wifirx_spectrum_band.argtypes = [C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+_lib.wifirx_spectrum_table.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
+                                       C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
 _lib.wifirx_diversity_combine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Out), C.c_uint32, C.c_int, C.POINTER(C.c_float),
                                           C.POINTER(Out), C.c_void_p]
 _lib.wifirx_precombine.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -1531,6 +1580,79 @@ class WifiRx:
         exactly that many outputs per channel (None: what the samples alone give)."""
         return self._arb_host(x, num, den, fmt, n_out, len(incs), lambda src, fmt, n, dst, made: self.tune_dev(
             src, fmt, n, num, den, incs, dst, made, phase0s=phase0s, scale=scale))
+
+    # -- band survey (wifirx_spectrum, _fold, _bands; NUMERICS.md rule 36) --
+    def spectrum_dev(self, in_ptr, fmt, n_in, n_fft, hop, avg, rows_ptr, rows_cap, window="blackman_harris", mode="sum", norm=1.0,
+                     scale=None) -> int:
+        """wifirx_spectrum on device pointers: n_in samples of `fmt` at in_ptr -> power rows of n_fft float32 at rows_ptr (room
+        for rows_cap rows).  window: "rect" / "hann" / "blackman_harris" or SPEC_*; mode: "sum" / "max" or SPEC_*.  Returns
+        n_rows.  Asynchronous on the handle's stream: sync() before another handle reads the rows."""
+        fmt, scale = _fmt_scale(fmt, scale)
+        window = SPEC_WINDOWS[window] if isinstance(window, str) else int(window)
+        mode = SPEC_MODES[mode] if isinstance(mode, str) else int(mode)
+        n = C.c_uint64(0)
+        self._check(_lib.wifirx_spectrum(self._h, in_ptr, fmt, scale, int(n_in), int(n_fft), int(hop), int(avg), window, mode,
+                                         float(norm), rows_ptr, int(rows_cap), C.byref(n)))
+        return int(n.value)
+
+    def spectrum(self, x, n_fft=1024, hop=None, avg=1, window="blackman_harris", mode="sum", norm=1.0, fmt=None, scale=None) -> np.ndarray:
+        """spectrum_dev on a host array: complex64 samples (fmt None or "fc32") or int16 / int8 samples ([n, 2] or flat [2 n])
+        -> float32 [n_rows, n_fft].  hop None: n_fft."""
+        x, fmt, n = self._host_samples(x, fmt)
+        hop = int(n_fft) if hop is None else int(hop)
+        rows, _ = spectrum_count(n_fft, hop, avg, n)
+        d_in, d_out = self.alloc(max(x.nbytes, 1)), self.alloc(max(rows * int(n_fft), 1) * 4)
+        try:
+            d_in.upload(x)
+            got = self.spectrum_dev(d_in.ptr, fmt, n, n_fft, hop, avg, d_out.ptr, rows, window, mode, norm, scale)
+            return d_out.download(np.float32, got * int(n_fft)).reshape(got, int(n_fft))
+        finally:
+            d_in.free()
+            d_out.free()
+
+    def spectrum_fold_dev(self, rows_ptr, n_rows, n_fft, group, out_ptr, out_cap, mode="sum") -> int:
+        """wifirx_spectrum_fold on device pointers: out row q = the fold of rows q * group .. q * group + group - 1.  Returns
+        n_out = n_rows // group."""
+        mode = SPEC_MODES[mode] if isinstance(mode, str) else int(mode)
+        n = C.c_uint64(0)
+        self._check(_lib.wifirx_spectrum_fold(self._h, rows_ptr, int(n_rows), int(n_fft), int(group), mode, out_ptr, int(out_cap),
+                                              C.byref(n)))
+        return int(n.value)
+
+    def spectrum_fold(self, rows, group=None, mode="sum") -> np.ndarray:
+        """spectrum_fold_dev on a host array float32 [n_rows, n_fft] -> [n_rows // group, n_fft].  group None: all rows"""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        n_rows, n_fft = rows.shape
+        group = max(n_rows, 1) if group is None else int(group)
+        made = n_rows // group if group else 0
+        d_in, d_out = self.alloc(max(rows.nbytes, 4)), self.alloc(max(made * n_fft, 1) * 4)
+        try:
+            d_in.upload(rows)
+            got = self.spectrum_fold_dev(d_in.ptr, n_rows, n_fft, group, d_out.ptr, made, mode)
+            return d_out.download(np.float32, got * n_fft).reshape(got, n_fft)
+        finally:
+            d_in.free()
+            d_out.free()
+
+    def spectrum_bands_dev(self, rows_ptr, n_rows, n_fft, bands, out_ptr):
+        """wifirx_spectrum_bands on device pointers: bands = [(lo, hi), ..] bins; out [n_rows, len(bands)] float32 at out_ptr"""
+        K = len(bands)
+        lo = (C.c_uint32 * max(K, 1))(*[int(b[0]) for b in bands])
+        hi = (C.c_uint32 * max(K, 1))(*[int(b[1]) for b in bands])
+        self._check(_lib.wifirx_spectrum_bands(self._h, rows_ptr, int(n_rows), int(n_fft), K, lo, hi, out_ptr))
+
+    def spectrum_bands(self, rows, bands) -> np.ndarray:
+        """spectrum_bands_dev on a host array float32 [n_rows, n_fft] -> float32 [n_rows, len(bands)]"""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        n_rows, n_fft = rows.shape
+        d_in, d_out = self.alloc(max(rows.nbytes, 4)), self.alloc(max(n_rows * len(bands), 1) * 4)
+        try:
+            d_in.upload(rows)
+            self.spectrum_bands_dev(d_in.ptr, n_rows, n_fft, bands, d_out.ptr)
+            return d_out.download(np.float32, n_rows * len(bands)).reshape(n_rows, len(bands))
+        finally:
+            d_in.free()
+            d_out.free()
 
     # -- receive diversity (wifirx_diversity_combine; NUMERICS.md rule 23) --
     def diversity_combine_dev(self, ins, n_slots, out, mode=DIV_MRC, ant_gain=None, used_mask_ptr=None):

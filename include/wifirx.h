@@ -1015,6 +1015,70 @@ int  wifirx_tune(wifirx_handle* h, const void* in, int fmt, float scale, uint64_
  * finite. */
 int  wifirx_tune_inc(double offset_hz, double sample_rate, uint64_t* inc);
 
+/* Band survey (NUMERICS.md rule 36): what is in a capture, before anything is tuned to.  Windowed-FFT power rows of a stream in
+ * its native format (the numbers behind a spectrum display and a waterfall), the fold of rows into fewer rows, and the power of
+ * each candidate channel per row.  The reference's flowgraphs show the same of the receiver's stream with
+ * qtgui.sink_c(1024, window.WIN_BLACKMAN_hARRIS, ...).
+ *
+ * wifirx_spectrum: segment s is in[s * hop .. s * hop + n_fft - 1]; S = (n_in >= n_fft) ? (n_in - n_fft) / hop + 1 : 0 segments.
+ * Row r is the fold (WIFIRX_SPEC_SUM: sum, WIFIRX_SPEC_MAX: maximum, a NaN sticks) of the powers |FFT(w * segment)|^2 of segments
+ * r * avg .. r * avg + avg - 1, times norm; bin i of a row is the frequency (i - n_fft / 2) / n_fft cycles per sample.  Only
+ * complete rows are made: *n_rows = S / avg, and the next row's first segment starts at sample *n_rows * avg * hop
+ * (wifirx_spectrum_count's consumed): a caller that cuts a stream there and keeps the overlap gets byte-identical rows.
+ *   in          DEVICE, n_in samples of `fmt` (WIFIRX_IQ_FC32 / SC16 / SC8) at the format's natural alignment (8 / 4 / 2
+ *               bytes); scale widens the integer formats (rule 20; not looked at for fc32)
+ *   n_fft       64, 256, 1024 or 4096;  hop, avg  1 .. WIFIRX_SPEC_MAX_HOP;  window  WIFIRX_SPEC_RECT / HANN / BLACKMAN_HARRIS
+ *               (periodic forms);  norm  any float32 (1: the fold itself)
+ *   rows_out    DEVICE, 4-byte aligned, room for rows_cap rows of n_fft floats; exactly *n_rows rows are written
+ * Checked on the host before anything is queued, and before a device is looked for: WIFIRX_EINVAL for a NULL handle or n_rows,
+ * NULL in with n_in > 0, NULL rows_out with rows to make, an unknown fmt, window or mode, a scale that is not finite or <= 0,
+ * an n_fft outside the set, hop or avg of 0 or above 2^20, misaligned buffers, an overlap of in and the rows written;
+ * WIFIRX_ERANGE for rows_cap < *n_rows, n_in >= 2^62, more than 2^31 - 1 tiles.  A refused call writes nothing, *n_rows
+ * included.  n_in < n_fft, or fewer than avg segments, returns WIFIRX_OK with *n_rows = 0 and writes nothing else.  One kernel
+ * launch per call.  ORDER: as wifirx_arb_resample. */
+#define WIFIRX_SPEC_RECT 0
+#define WIFIRX_SPEC_HANN 1
+#define WIFIRX_SPEC_BLACKMAN_HARRIS 2
+#define WIFIRX_SPEC_SUM 0
+#define WIFIRX_SPEC_MAX 1
+#define WIFIRX_SPEC_MAX_BANDS 16
+#define WIFIRX_SPEC_MAX_HOP 1048576        /* 2^20: the largest hop and the largest avg */
+int  wifirx_spectrum(wifirx_handle* h, const void* in, int fmt, float scale, uint64_t n_in, uint32_t n_fft, uint32_t hop,
+                     uint32_t avg, int window, int mode, float norm, float* rows_out, uint64_t rows_cap, uint64_t* n_rows);
+
+/* The rows a wifirx_spectrum call makes and the samples they consume (*consumed = *n_rows * avg * hop), host integers only; needs
+ * no handle and no device.  WIFIRX_EINVAL for a NULL output or arguments wifirx_spectrum refuses, WIFIRX_ERANGE for
+ * n_in >= 2^62.  Nothing is written by a refused call. */
+int  wifirx_spectrum_count(uint32_t n_fft, uint32_t hop, uint32_t avg, uint64_t n_in, uint64_t* n_rows, uint64_t* consumed);
+
+/* Output row q = the ascending fold, by wifirx_spectrum's two modes, of rows q * group .. q * group + group - 1, per bin;
+ * *n_out = n_rows / group complete groups.  A Welch spectrum of a whole capture is wifirx_spectrum(avg <= 64) followed by
+ * wifirx_spectrum_fold(group = n_rows).  rows, out: DEVICE, 4-byte aligned, [..][n_fft]; they must not overlap.
+ * WIFIRX_EINVAL for a NULL handle, n_out, rows or out with rows to make, an n_fft outside the set, an unknown mode, group = 0,
+ * misaligned or overlapping buffers; WIFIRX_ERANGE for out_cap < *n_out or n_rows >= 2^40.  One kernel launch per call. */
+int  wifirx_spectrum_fold(wifirx_handle* h, const float* rows, uint64_t n_rows, uint32_t n_fft, uint64_t group, int mode,
+                          float* out, uint64_t out_cap, uint64_t* n_out);
+
+/* out[r][b] = the sum of row r's bins lo[b] .. hi[b] - 1: one wave per (row, band), lane l adding bins lo + l, lo + l + 64, ..
+ * in ascending order, then the xor-butterfly tree of rule 5 over the 64 lanes.  rows, out: DEVICE, 4-byte aligned; lo, hi: HOST
+ * [n_bands], read before the call returns.  Bands may overlap one another.
+ * WIFIRX_EINVAL for a NULL handle, rows, out, lo or hi, n_bands outside 1 .. WIFIRX_SPEC_MAX_BANDS, an n_fft outside the set,
+ * lo[b] >= hi[b] or hi[b] > n_fft, misaligned or overlapping buffers; WIFIRX_ERANGE for n_rows > 2^31 - 1.  n_rows = 0 does
+ * nothing and returns WIFIRX_OK.  One kernel launch per call. */
+int  wifirx_spectrum_bands(wifirx_handle* h, const float* rows, uint64_t n_rows, uint32_t n_fft, uint32_t n_bands,
+                           const uint32_t* lo, const uint32_t* hi, float* out);
+
+/* The bins of a row whose centres lie in [offset_hz - width_hz / 2, offset_hz + width_hz / 2): in double,
+ * *lo = ceil((offset_hz - width_hz / 2) * n_fft / sample_rate) + n_fft / 2 and *hi the same of the upper edge (rule 36).  Needs
+ * no handle and no device.  WIFIRX_EINVAL for a NULL output, an n_fft outside the set, values that are not finite,
+ * sample_rate <= 0, width_hz <= 0; WIFIRX_ERANGE when the band holds no bin or leaves [-sample_rate / 2, sample_rate / 2). */
+int  wifirx_spectrum_band(double offset_hz, double width_hz, double sample_rate, uint32_t n_fft, uint32_t* lo, uint32_t* hi);
+
+/* The tables of rule 36 (host memory, static): the periodic Hann and 4-term Blackman-Harris windows of *n_entries = 4096 points and
+ * T[k] = exp(-j 2 pi k / 4096) as *n_entries (re, im) pairs; a transform of n_fft points reads every (4096 / n_fft)-th entry.
+ * Needs no handle and no device.  WIFIRX_EINVAL for a NULL argument. */
+int  wifirx_spectrum_table(const float** hann, const float** blackman_harris, const float** twiddle, uint32_t* n_entries);
+
 /* Receive diversity (NUMERICS.md rule 23): combine the equalised points of n_ant antennas' demodulated batches into one batch
  * to decode.  Slot i of every in[a] is the same transmission, demodulated from antenna a's samples by wifirx_demod_batch with
  * `carrier` and `csi` outputs (by this handle one after the other, or by other handles with the same max_sym).  Per slot: the
